@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- candidate-trajectory-steps/sec of the batched lattice planner on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (torch.distributed.run as a child process, before
@@ -175,6 +175,42 @@ def emit(full, stream=None, rk=None):
     return line
 
 
+DUMP_MAX_BYTES = 64 * 10**6      # --dump-outputs: every .npy file together, headers included
+DUMP_COSTS = ("best_cost", "all_cost")   # +inf by contract for a candidate in collision (f1p.h check_collision): always carry a _nonfinite file
+
+
+def dump_outputs(path, arrays, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: name -> array (one row per ego along axis 0) -> path/<name>.npy.  Integer columns are written as float64 (exact), float32
+    stays float32.  Every file is finite: a non-finite entry is written as 0 and <name>_nonfinite.npy holds, at the same index, +1 for +inf,
+    -1 for -inf, 2 for NaN and 0 for a finite value (written for the DUMP_COSTS arrays always, for any other array when it has such an entry).
+    When the set would exceed max_bytes, every array keeps the same rows: a sorted sample of egos drawn with a fixed seed, whose indices go
+    to ego_rows.npy."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)) for k, v in arrays.items()}
+    for name in list(arrays):
+        v = arrays[name]
+        bad = ~np.isfinite(v)
+        if name in DUMP_COSTS or bad.any():
+            code = np.zeros(v.shape)
+            code[v == np.inf], code[v == -np.inf], code[np.isnan(v)] = 1.0, -1.0, 2.0
+            arrays[name + "_nonfinite"] = code
+            arrays[name] = np.where(bad, v.dtype.type(0), v)
+    n = len(next(iter(arrays.values())))
+    header = 256                                           # an .npy header is 128 bytes for these shapes; twice that to be safe
+    budget = max_bytes - header * (len(arrays) + 1)
+    row_bytes = sum(v[:1].nbytes for v in arrays.values())
+    if n * row_bytes > budget:
+        k = budget // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+        arrays = {name: v[rows] for name, v in arrays.items()}
+        arrays["ego_rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    print("bench.py: outputs of the last timed step (%s) -> %s" % (", ".join("%s %s" % (k, list(v.shape)) for k, v in arrays.items()), path),
+          file=sys.stderr, flush=True)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -187,6 +223,10 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--full-record", default=None, help="where rank 0 writes the full record (default: bench_full.json beside this script, and gpurun_out/ "
                                                         "when it exists); stdout's last line is the compact record either way")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step computed (the arrays a caller of that path receives) as "
+                         "DIR/<name>.npy, float64 (float32 stays float32), at most 64 MB in all: a fixed, seeded sample of egos when larger; "
+                         "every file is finite, +-inf / NaN entries (a blocked ego's +inf best_cost) are flagged in <name>_nonfinite.npy")
     ap.add_argument("--no-secondary", action="store_true", help="skip the candidate-sharded and kmpc legs of the default run")
     ap.add_argument("--only-timed", action="store_true",
                     help="profiling runs (tools/profile_gpu.sh): nothing but the warm-up and the timed steady-state region touches the GPU, so that "
@@ -476,6 +516,10 @@ def leg_candidate_sharded(rk, ctx, rl, steps, E=4096, C=512, S=50, timed=True):
         ctx.lattice_plan_dev(d_poses, E, sh, None, None, d_idx, d_cost, d_prev_theta=d_prev)             # this rank's candidate slice
         rk.exchange(ctx, d_cost, d_idx, E)                                                               # RCCL, same stream
         ctx.lattice_emit_dev(d_poses, E, cfg, d_idx, d_cost, d_steer, d_speed, d_status, d_near, d_traj)
+    step.outputs = lambda: {"steer": d_steer.download(np.float64, (E,)), "speed": d_speed.download(np.float64, (E,)),   # --dump-outputs
+                            "best_idx": d_idx.download(np.int32, (E,)), "best_cost": d_cost.download(np.float64, (E,)),
+                            "status": d_status.download(np.int32, (E,)), "near_idx": d_near.download(np.int32, (E,)),
+                            "best_traj": d_traj.download(np.float64, (E, S, 4))}
 
     step(); ctx.sync()
     same = all(np.array_equal(a.download(t, s), b.download(t, s), equal_nan=(t == np.float64)) for a, b, t, s in
@@ -1433,6 +1477,17 @@ def main_lattice(args):
 
     elapsed, kernel_ms_total = timed_region(rk, ctx, step, args.warmup, args.steps)
     per_rank_s = list(rk.last_per_rank_s or [elapsed])
+    if args.dump_outputs and rank == 0:                         # before the parity plan below overwrites them
+        if cand_sharded:
+            dumped = step.outputs()
+        else:
+            dumped = {"steer": d_steer.download(np.float64, (E,)), "speed": d_speed.download(np.float64, (E,)),
+                      "best_idx": d_bidx.download(np.int32, (E,)), "best_cost": d_bcost.download(np.float64, (E,)),
+                      "status": d_status.download(np.int32, (E,)), "near_idx": d_near.download(np.int32, (E,)),
+                      "best_traj": d_traj.download(np.float64, (E, S, 4))}
+            if materialised:
+                dumped.update(all_cost=d_all_cost.download(np.float64, (E, C)), all_traj=d_all_traj.download(np.float64, (E, C, S, 4)))
+        dump_outputs(args.dump_outputs, dumped)
 
     # outputs the parity gate and the other schedules are compared with: ONE more plan of the chain, whose previous path (the headings the
     # last timed plan left) is copied first so that every comparison below can hand it over explicitly
@@ -1720,6 +1775,10 @@ def main_pursuit(args):
         ctx.pure_pursuit_dev(d_poses, E, 0.8, d_steer, d_speed, d_near, d_la, d_st)
     elapsed, ms_total = timed_region(rk, ctx, step, args.warmup, args.steps)
     kernel_ms = ms_total / args.steps
+    if args.dump_outputs and rk.rank == 0:
+        dump_outputs(args.dump_outputs, {"steer": d_steer.download(np.float64, (E,)), "speed": d_speed.download(np.float64, (E,)),
+                                         "near_idx": d_near.download(np.int32, (E,)), "la_idx": d_la.download(np.int32, (E,)),
+                                         "status": d_st.download(np.int32, (E,))})
     if rk.rank == 0:
         out = {"metric": "ego-plans/sec (batched pure pursuit)", "value": E * args.steps * rk.world / elapsed, "unit": "plans/s", "n_gpus": rk.world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
@@ -1772,6 +1831,9 @@ def main_stmpc(args):
         ctx.stmpc_shoot_dev(d_x0, d_ref, d_ctrl, E, cfg, d_steer, d_speed, d_bi, d_bc)
     elapsed, ms_total = timed_region(rk, ctx, step, args.warmup, args.steps)
     kernel_ms = ms_total / args.steps
+    if args.dump_outputs and rk.rank == 0:
+        dump_outputs(args.dump_outputs, {"steer": d_steer.download(np.float64, (E,)), "speed": d_speed.download(np.float64, (E,)),
+                                         "best_idx": d_bi.download(np.int32, (E,)), "best_cost": d_bc.download(np.float64, (E,))})
     # the all-fp64 kernel (k_stmpc_shoot) on the same inputs: same outputs bit for bit (tests/test_gpu_stmpc.py), here only timed
     bi_mixed = d_bi.download(np.int32, (E,))
     ctx.stmpc_set_mode(False)
@@ -1855,6 +1917,11 @@ def main_kmpc(args):
             ctx.kmpc_plan_dev(d_x0, d_ref, E, cfg, smp, d_steer, d_speed, d_bi, d_bc if args.kmpc_cost else None)
     elapsed, ms_total = timed_region(rk, ctx, step, args.warmup, args.steps)
     kernel_ms = ms_total / args.steps
+    if args.dump_outputs and rank == 0:
+        dumped = {"steer": d_steer.download(np.float64, (E,)), "speed": d_speed.download(np.float64, (E,)), "best_idx": d_bi.download(np.int32, (E,))}
+        if args.kmpc_cost or args.kmpc_f64:                                # the step only writes best_cost when asked to
+            dumped["best_cost"] = d_bc.download(np.float64, (E,))
+        dump_outputs(args.dump_outputs, dumped)
     env_ok = rk.env_ok()
     if not stream and not args.no_cpu_baseline and rank == 0:      # parity leg: the last plan's controls, materialised, for the oracle
         ctx.kmpc_warm_reset()

@@ -105,3 +105,57 @@ def test_emit_writes_the_full_record_and_prints_the_compact_line_last(tmp_path, 
     assert rec["full_record"] == "full.json" and "full.json" in cap.err
     side = _strict_loads(open(path).read())                      # strict JSON too: nan / inf became null
     assert side["roofline"]["achieved"] is None and side["scene_sweep"]["a"]["note"] == "x" * 5000 and side["steps"] == 20
+
+
+def test_dump_outputs_writes_every_array_and_samples_the_same_egos_when_over_the_cap(tmp_path):
+    """--dump-outputs: float64 / float32 files, integer columns exact, and above the cap ONE seeded sample of egos for every array"""
+    assert bench.parse_args(["--dump-outputs", str(tmp_path), "--steps", "7"]).dump_outputs == str(tmp_path)
+    rng = np.random.default_rng(3)
+    E, S = 2048, 50
+    arrays = {"steer": rng.normal(size=E), "best_idx": rng.integers(-1, 256, E).astype(np.int32),
+              "best_traj": rng.normal(size=(E, S, 4)), "all_traj": rng.normal(size=(E, 8, S, 4)).astype(np.float32)}
+
+    small = os.path.join(tmp_path, "small")
+    bench.dump_outputs(small, {k: arrays[k] for k in ("steer", "best_idx")})
+    assert sorted(os.listdir(small)) == ["best_idx.npy", "steer.npy"]
+    got = np.load(os.path.join(small, "best_idx.npy"))
+    assert got.dtype == np.float64 and (got == arrays["best_idx"]).all()
+    assert (np.load(os.path.join(small, "steer.npy")) == arrays["steer"]).all()
+
+    cap = 2 * 10**6
+    runs = []
+    for name in ("a", "b"):
+        d = os.path.join(tmp_path, name)
+        bench.dump_outputs(d, arrays, max_bytes=cap)
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= cap
+        runs.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    a, b = runs
+    assert sorted(a) == sorted(list(arrays) + ["ego_rows"])
+    rows = a["ego_rows"].astype(np.int64)
+    assert 0 < len(rows) < E and (np.diff(rows) > 0).all() and (a["ego_rows"] == b["ego_rows"]).all()
+    for k, v in arrays.items():
+        assert a[k].dtype == (np.float32 if v.dtype == np.float32 else np.float64)
+        assert (a[k] == v[rows]).all() and (b[k] == a[k]).all()
+
+
+def test_dump_outputs_files_are_finite_and_flag_what_was_not(tmp_path):
+    """a blocked ego's best_cost is +inf by contract: the dump writes 0 there and says so in best_cost_nonfinite.npy (+1 +inf, -1 -inf, 2 NaN);
+    a cost array always gets that file, another array only when it holds a non-finite entry"""
+    E = 64
+    cost = np.linspace(0.5, 2.0, E)
+    cost[[3, 40]], cost[7], cost[9] = np.inf, -np.inf, np.nan
+    traj = np.ones((E, 5, 4), np.float32)
+    traj[11, 2, 1] = np.nan
+    arrays = {"best_cost": cost, "all_cost": np.ones((E, 8)), "best_traj": traj, "steer": np.zeros(E)}
+    bench.dump_outputs(str(tmp_path), arrays)
+    files = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert sorted(files) == sorted(["best_cost", "best_cost_nonfinite", "all_cost", "all_cost_nonfinite", "best_traj", "best_traj_nonfinite", "steer"])
+    for k, v in files.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), k
+    want = np.zeros(E)
+    want[[3, 40]], want[7], want[9] = 1.0, -1.0, 2.0
+    assert (files["best_cost_nonfinite"] == want).all()
+    ok = want == 0
+    assert (files["best_cost"][ok] == cost[ok]).all() and (files["best_cost"][~ok] == 0).all()
+    assert (files["all_cost_nonfinite"] == 0).all() and (files["all_cost"] == 1).all()
+    assert files["best_traj"].dtype == np.float32 and files["best_traj"][11, 2, 1] == 0 and files["best_traj_nonfinite"].sum() == 2.0
