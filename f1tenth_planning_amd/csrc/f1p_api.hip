@@ -870,7 +870,7 @@ static int lattice_plan_batch_impl(f1p_ctx* ctx, const double* poses, const doub
     d_prev = cl.prev;
     double* d_steer = s.out(steer, e); double* d_speed = s.out(speed, e); int32_t* d_bi = s.out(best_idx, e);
     double* d_bc = s.out(best_cost, e); int32_t* d_st = s.out(status, e); int32_t* d_ni = s.out(near_idx, e);
-    // Trajectories into PAGE-LOCKED host memory (f1p_host_alloc / hipHostRegister), 2048 <= E < 8192: the selection kernel writes
+    // Trajectories into PAGE-LOCKED host memory (f1p_host_alloc / hipHostRegister), F1P_ZEROCOPY_MIN_EGOS <= E < 8192: the selection kernel writes
     // them straight into the caller's array (it is device-visible), so the PCIe writes stream while the kernel still runs and no
     // copy is submitted at all -- measured at 4096 egos, p50 host to host: fp64 rows 0.277 ms (0.287 with one hipMemcpyAsync behind
     // the plan, 0.294 with the plan in two slices and the copies on a second stream, the round-2 scheme), f32 rows 0.214 (0.230 /

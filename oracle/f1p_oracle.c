@@ -102,7 +102,9 @@ static int orc_seg_hit(double px, double py, double radius, double sx, double sy
 
 ORC_API int orc_intersect_point(double px, double py, double radius, const double* wx, const double* wy, int n,
                                 double t, int wrap, double* first_p, int* first_i, double* first_t) {
-    int start_i = (int)t;          /* :78 */
+    /* :78  a NaN t comes only from a NaN pose (nearest_point's t = NaN / l2), whose every segment test below misses; the reference's
+     * int(t) raises there, and (int)NaN is undefined in C (x86 gives INT_MIN: wx[INT_MIN]).  Start at 0 like the device's conversion. */
+    int start_i = isnan(t) ? 0 : (int)t;
     double start_t = fmod(t, 1.0); /* :79  t % 1.0 (t >= 0 at every call site) */
     double th = 0, hx = 0, hy = 0;
     for (int i = start_i; i < n - 1; ++i) { /* :84 */

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from f1tenth_planning_amd import _abi, synth
+from lattice_helpers import compare as _compare
 
 pytestmark = pytest.mark.gpu
 
@@ -25,19 +26,6 @@ def ctx(scene):
     c.set_grid(img, 0.058, origin, 206)
     yield c
     c.close()
-
-
-def _compare(got, want, tol_traj=1e-9):
-    np.testing.assert_array_equal(got["near_idx"], want["near_idx"])
-    np.testing.assert_array_equal(got["best_idx"], want["best_idx"])
-    np.testing.assert_array_equal(got["status"], want["status"])
-    fin = np.isfinite(want["best_cost"])
-    np.testing.assert_array_equal(np.isfinite(got["best_cost"]), fin)
-    np.testing.assert_allclose(got["best_cost"][fin], want["best_cost"][fin], rtol=1e-10, atol=1e-12)
-    np.testing.assert_allclose(got["steer"], want["steer"], rtol=0, atol=1e-5)      # north_star tolerance
-    np.testing.assert_allclose(got["speed"], want["speed"], rtol=0, atol=1e-5)
-    np.testing.assert_allclose(got["best_traj"], want["best_traj"], rtol=0, atol=tol_traj)
-    return float(np.abs(got["steer"] - want["steer"]).max()), float(np.abs(got["best_traj"] - want["best_traj"]).max())
 
 
 def test_clothoid_fit_vs_oracle_and_known_answers(ctx, orc):
@@ -201,11 +189,12 @@ def test_cubic_generator_vs_oracle(ctx, orc, scene):
 
 
 def test_pinned_pipelined_batch_equals_plain_batch(ctx, scene):
-    """With page-locked result arrays a batch >= 2048 egos is planned in two slices whose D2H overlaps the next slice
-    (f1p_lattice_plan_batch); every output must be bit-identical to the single-launch path, also for an odd split."""
+    """With page-locked result arrays (f1p_lattice_plan_batch) a batch of F1P_ZEROCOPY_MIN_EGOS <= E < 8192 egos is read and written in place by the
+    kernels, and a batch >= 8192 egos is planned in min(E / 4096, 8) slices whose row D2H overlaps the next slice; every output must be bit-identical
+    to the staged path (pageable arrays), also for an odd split.  (tests/test_gpu_lattice_large.py takes the sliced path up to 36 865 egos.)"""
     rl, img, origin = scene
     cfg = synth.bench_lattice_cfg(n_cand=256, n_stations=50)
-    for E in (2049, 4096, 12289):                      # two slices, two slices, three slices with an odd split
+    for E in (2049, 4096, 12289):                      # in place, in place, three slices with an odd split
         poses = synth.make_egos(rl, E, seed=77)
         plain = ctx.lattice_plan(poses, cfg)
         pinned = ctx.lattice_plan(poses, cfg, reuse_outputs=True)
@@ -458,7 +447,7 @@ def test_candidate_slices_over_several_workgroups(ctx, scene):
 def test_f32_trajectory_output_mode(ctx, orc, scene, E):
     """f1p_lattice_plan_batch_f32: the winner's rows as f32 = the fp64 rows rounded ONCE (bit for bit), every other
     output unchanged; against the oracle at BASELINE.md's best_traj tolerance (1e-4), with both schedules (all fp64 below 512
-    egos, the mixed one above), pageable and page-locked destinations (the latter takes the sliced copy path at 4096 egos)."""
+    egos, the mixed one above), pageable and page-locked destinations (the latter is written in place at 4096 egos: the sliced copy path starts at 8192)."""
     rl, img, origin = scene
     cfg = synth.bench_lattice_cfg(n_cand=128 if E < 1000 else 256, n_stations=50)
     poses = synth.make_egos(rl, E, seed=77)

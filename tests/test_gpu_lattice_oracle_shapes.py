@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from f1tenth_planning_amd import _abi, synth
+from lattice_helpers import compare as _compare
 
 pytestmark = pytest.mark.gpu
 RES = 0.058
@@ -21,18 +22,6 @@ def scene():
     rl = synth.make_raceline(seed=0)
     img, origin = synth.make_grid(rl[:, :2], size=(2000, 2000), resolution=RES, half_width=0.9)
     return rl, img, origin
-
-
-def _compare(got, want, tol_traj=1e-9):
-    np.testing.assert_array_equal(got["near_idx"], want["near_idx"])
-    np.testing.assert_array_equal(got["best_idx"], want["best_idx"])
-    np.testing.assert_array_equal(got["status"], want["status"])
-    fin = np.isfinite(want["best_cost"])
-    np.testing.assert_array_equal(np.isfinite(got["best_cost"]), fin)
-    np.testing.assert_allclose(got["best_cost"][fin], want["best_cost"][fin], rtol=1e-10, atol=1e-12)
-    np.testing.assert_allclose(got["steer"], want["steer"], rtol=0, atol=1e-5)
-    np.testing.assert_allclose(got["speed"], want["speed"], rtol=0, atol=1e-5)
-    np.testing.assert_allclose(got["best_traj"], want["best_traj"], rtol=0, atol=tol_traj)
 
 
 def _host_goals(E, C, seed):

@@ -61,6 +61,24 @@ def test_intersect_point_golden(orc, golden, tracks, name, cols):
     assert seen_neg > 0
 
 
+def test_degenerate_poses_plan_as_all_blocked(orc):
+    """Poses the reference cannot take (its int(t) raises on the NaN t a NaN pose gets from nearest_point): the oracle finds no look-ahead
+    point for them and plans them as ALL_BLOCKED -- the device kernels' answer -- next to an ordinary ego.  A NaN x once turned into segment
+    index INT_MIN inside orc_intersect_point (run under the CPU sanitizer leg, tests/test_oracle_asan.py)."""
+    from f1tenth_planning_amd import _abi, synth
+    rl = synth.make_raceline(seed=0)
+    img, origin = synth.make_grid(rl[:, :2], size=(600, 600), resolution=0.2)
+    cfg = synth.bench_lattice_cfg(n_cand=32, n_stations=20)
+    assert orc.intersect_point((np.nan, 1.0), 0.8, rl[:, :2], np.nan, wrap=True)[1] is None
+    poses = np.repeat(synth.make_egos(rl, 1, seed=4), 4, axis=0)
+    poses[1, :2] += 400.0; poses[2, 0] = np.nan; poses[3, 2] = np.inf
+    out = orc.lattice_plan_batch(poses, rl, cfg, grid=(img, 0.2, origin[0], origin[1], 206))
+    assert out["status"][0] == _abi.ST_INTERSECT
+    np.testing.assert_array_equal(out["status"][1:], _abi.ST_ALL_BLOCKED)
+    assert (out["steer"][1:] == 0).all() and (out["speed"][1:] == 0).all() and (out["best_traj"][1:] == 0).all()
+    assert np.isinf(out["best_cost"][1:]).all() and out["near_idx"][2] == 0     # np.argmin over all-NaN distances: the first
+
+
 def test_get_actuation_and_angles_golden(orc, golden):
     g = golden("g3_g9_actuation_angles.npz")
     for j in range(len(g["theta"])):
