@@ -1,4 +1,4 @@
-"""Kinematic MPC (random shooting on the GPU) in closed loop (loop shape of the reference's
+"""Kinematic MPC (random shooting, or with --solver qp the reference's linearised QP, on the GPU) in closed loop (loop shape of the reference's
 examples/control/kinematic_mpc.py:35-67): the planner gets the simulator's 7-state and the waypoints as [x, y, yaw, v]."""
 import os
 import sys
@@ -14,11 +14,13 @@ from f1tenth_planning.control.kinematic_mpc.kinematic_mpc import KMPCPlanner, mp
 def main():
     ap = common.parser(__doc__, steps=600)
     ap.add_argument("--rollouts", type=int, default=512)
+    ap.add_argument("--solver", choices=["shooting", "qp"], default="shooting")
     args = ap.parse_args()
     rl = common.raceline(args, centerline=True)
     waypoints = [rl[:, 0], rl[:, 1], rl[:, 3], rl[:, 2]]          # [x, y, yaw, v]
     cfg = mpc_config()
     cfg.N_ROLLOUTS = args.rollouts
+    cfg.SOLVER = args.solver
     planner = KMPCPlanner(waypoints=waypoints, config=cfg)
 
     def plan(obs, env):

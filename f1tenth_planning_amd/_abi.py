@@ -59,6 +59,17 @@ def kmpc_sampler(seed=0, call=0, use_warm=True, sigma_accel=1.5, sigma_steer=0.1
     return s
 
 
+class KmpcQpOpts(C.Structure):
+    """struct f1p_kmpc_qp_opts (include/f1p.h)"""
+    _fields_ = [("max_iter", C.c_int32), ("pad", C.c_int32), ("tol", C.c_double)]
+
+
+def kmpc_qp_opts(max_iter=50, tol=1e-10):
+    o = KmpcQpOpts()
+    o.max_iter, o.tol = int(max_iter), float(tol)
+    return o
+
+
 class StmpcCfg(C.Structure):
     """struct f1p_stmpc_cfg (include/f1p.h)"""
     _fields_ = [
@@ -220,6 +231,14 @@ PROTOTYPES = {
     "f1p_kmpc_set_groups": (C.c_int, [_P, _I]),
     "f1p_stmpc_set_mode": (C.c_int, [_P, _I, _P, _P]),
     "f1p_kmpc_set_yaw_fixup": (C.c_int, [_P, _I]),
+    "f1p_kmpc_qp_opts_default": (None, [C.POINTER(KmpcQpOpts)]),
+    "f1p_kmpc_qp_batch": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(KmpcCfg), C.POINTER(KmpcQpOpts), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f1p_kmpc_qp_dev": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(KmpcCfg), C.POINTER(KmpcQpOpts), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f1p_kmpc_qp_plan_batch": (C.c_int, [_P, _P, _I, C.POINTER(KmpcCfg), _D, C.POINTER(KmpcQpOpts), _P, _P, _P, _P, _P]),
+    "f1p_kmpc_qp_warm_reset": (C.c_int, [_P]),
+    "f1p_kmpc_qp_warm_get": (C.c_int, [_P, _P, _I, _I]),
+    "f1p_kmpc_qp_warm_set": (C.c_int, [_P, _P, _I, _I]),
+    "f1p_kmpc_qp_set_pack": (C.c_int, [_P, _I]),
     "f1p_stmpc_cfg_default": (None, [C.POINTER(StmpcCfg)]),
     "f1p_stmpc_predict_batch": (C.c_int, [_P, _P, _P, _P, _I, C.POINTER(StmpcCfg), _P]),
     "f1p_stmpc_ref_batch": (C.c_int, [_P, _P, _I, _I, _D, _D, _P]),

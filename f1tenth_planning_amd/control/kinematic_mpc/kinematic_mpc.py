@@ -9,6 +9,9 @@ rolled out through the reference's own nonlinear step (update_state_kinematic :2
 applied (:506-508).  The candidates are generated inside the kernel (counter-based Philox4x32-10, include/f1p.h
 f1p_kmpc_sampler) around a warm start that stays on the device; a plan uploads 32 bytes per vehicle.  The reference trajectory extraction (calc_ref_trajectory_kinematic :162-206) also runs on the
 GPU.
+
+mpc_config.SOLVER = "qp" selects the reference's own solver instead: the linearised QP of :245-450, solved exactly (to QP_TOL) by
+a batched fp64 interior-point kernel (csrc/k_kmpc_qp.hip), warm-started like the reference from the previous solution (unshifted).
 """
 import os
 from dataclasses import dataclass, field
@@ -45,6 +48,10 @@ class mpc_config:
     SIGMA_ACCEL: float = 1.5  # std of the acceleration samples [m/ss]
     SIGMA_STEER: float = 0.15  # std of the steering samples [rad]
     SEED: int = 0
+    # solver: "shooting" (the default above) or "qp" -- the reference's own linearised QP (:283-450) solved exactly in fp64 on the GPU
+    SOLVER: str = "shooting"
+    QP_TOL: float = 1e-10  # interior point: scaled KKT residuals and duality gap below this
+    QP_MAX_ITER: int = 50  # interior-point iterations at most (status 2 beyond: the last iterate, like cvxpy's OPTIMAL_INACCURATE)
 
 
 @dataclass
@@ -65,6 +72,25 @@ def _fold_cyaw_inplace(cyaw, yaw):
     cyaw[m] = np.abs(cyaw[m] - (2 * np.pi))
     m = cyaw - yaw < -4.5
     cyaw[m] = np.abs(cyaw[m] + (2 * np.pi))
+
+
+_SOLVERS = ("shooting", "qp")
+
+
+def _check_solver(c: mpc_config):
+    """ValueError before anything touches the GPU: an unknown SOLVER, or weights the QP path does not take (diagonal only)"""
+    if c.SOLVER not in _SOLVERS:
+        raise ValueError(f"mpc_config.SOLVER must be one of {_SOLVERS}, not {c.SOLVER!r}")
+    if c.SOLVER == "qp":
+        for name in ("Rk", "Rdk", "Qk", "Qfk"):
+            w = np.asarray(getattr(c, name), dtype=np.float64)
+            n = 2 if name in ("Rk", "Rdk") else 4
+            if w.shape != (n, n) or np.any(w - np.diag(np.diag(w)) != 0):
+                raise ValueError(f"SOLVER='qp' takes diagonal {n}x{n} weights only; mpc_config.{name} is not")
+
+
+def _qp_opts(c: mpc_config):
+    return _abi.kmpc_qp_opts(max_iter=c.QP_MAX_ITER, tol=c.QP_TOL)
 
 
 def _cfg_struct(c: mpc_config, n_rollouts=None):
@@ -96,6 +122,7 @@ class KMPCPlanner:
         self._device = device
         self._ctx = None
         self._calls = 0
+        _check_solver(config)
 
     def _context(self):
         if self._ctx is None:
@@ -134,10 +161,19 @@ class KMPCPlanner:
         states: [x, y, delta, v, yaw, yawrate, beta] (the 7-state of f110_gym, :139-147).
         Returns (steering_angle, speed).
         """
+        _check_solver(self.config)
         ctx = self._bind(waypoints, fold_yaw=float(states[4]))
         vehicle_state = State(x=states[0], y=states[1], delta=states[2], v=states[3], yaw=states[4], yawrate=states[5],
                               beta=states[6])
         x0 = np.array([[vehicle_state.x, vehicle_state.y, vehicle_state.v, vehicle_state.yaw]], dtype=np.float64)   # :487
+        if self.config.SOLVER == "qp":
+            out = self._qp(ctx, x0)
+            st = int(out["status"][0])
+            if st in (1, 3):        # the reference cannot go on either: its oa / odelta_v are None (:444-448, :500-505)
+                raise RuntimeError("kinematic MPC QP: " + ("infeasible (speed outside [MIN_SPEED, MAX_SPEED])" if st == 1 else "non-finite input"))
+            self.oa = out["u"][0, :, 0]                        # fp64; the next call linearises about them (device-resident copy)
+            self.odelta_v = out["u"][0, :, 1]
+            return float(out["steer"][0]), float(out["speed"][0])
         out = self._shoot(ctx, x0)
         self.oa = out["best_seq"][0, :, 0]                 # the reference's attributes (:108-110); the warm start itself lives on the device
         self.odelta_v = out["best_seq"][0, :, 1]
@@ -151,18 +187,32 @@ class KMPCPlanner:
         c = self.config
         return ctx.kmpc_plan(x0, _cfg_struct(c), self._sampler(), dl=c.dlk, want_seq=want_seq)
 
+    def _qp(self, ctx, x0, want_u=True):
+        """One C call per plan (f1p_kmpc_qp_plan_batch): reference extraction (:162-206), linearisation about the previous solution held
+        on the device (unshifted, :462-468), the QP of :283-450 solved to tolerance, output map (:500-505), new warm start."""
+        c = self.config
+        return ctx.kmpc_qp_plan(x0, _cfg_struct(c), dl=c.dlk, opts=_qp_opts(c), want_u=want_u)
+
     def reset(self):
-        """forget the warm start and restart the sampler's call counter (a new episode)"""
+        """forget the warm starts (shooting and QP) and restart the sampler's call counter (a new episode)"""
         self._calls = 0
         self.oa = self.odelta_v = None
         if self._ctx is not None:
             self._ctx.kmpc_warm_reset()
+            self._ctx.kmpc_qp_warm_reset()
 
     def plan_batch(self, x0, waypoints=None, controls=None, want_seq=True):
         """x0 [E, 4] = (x, y, v, yaw) -> dict(steer, speed, best_idx, best_cost[, best_seq]).  `controls`
-        (f32 [E, T, 2, R]) overrides the in-kernel sampler with a caller-supplied candidate set (streamed from HBM)."""
+        (f32 [E, T, 2, R]) overrides the in-kernel sampler with a caller-supplied candidate set (streamed from HBM).
+        SOLVER == "qp": dict(steer, speed, status, obj[, u [E, T, 2]]) -- per-ego status (0 solved, 1 infeasible, 2 not converged,
+        3 non-finite input), never raised."""
+        _check_solver(self.config)
+        if self.config.SOLVER == "qp" and controls is not None:
+            raise ValueError("controls are candidates of the shooting solver; SOLVER='qp' takes none")
         ctx = self._bind(waypoints)
         x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, 4)
+        if self.config.SOLVER == "qp":
+            return self._qp(ctx, x0, want_u=want_seq)
         if controls is None:
             return self._shoot(ctx, x0, want_seq=want_seq)
         c = self.config

@@ -315,7 +315,7 @@ void f1p_destroy(f1p_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     f1p_comm_destroy(ctx);
-    void* ptrs[] = {ctx->d_wx, ctx->d_wy, ctx->d_wv, ctx->d_wpsi, ctx->d_wkappa, ctx->d_wbox, ctx->d_bits, ctx->d_bits0, ctx->d_bits_clear, ctx->d_bb_scratch, ctx->d_arena, ctx->d_comm_key, ctx->d_comm_idx, ctx->d_kmpc_warm, ctx->d_kmpc_scratch, ctx->d_mix_scratch, ctx->d_split_scratch, ctx->d_rec_scratch, ctx->d_st_scratch, ctx->d_audit, ctx->d_audit_buf, ctx->d_cl_theta[0], ctx->d_cl_theta[1], ctx->d_step, ctx->d_comm_rec, ctx->d_order, ctx->d_kmpc_cfg};
+    void* ptrs[] = {ctx->d_wx, ctx->d_wy, ctx->d_wv, ctx->d_wpsi, ctx->d_wkappa, ctx->d_wbox, ctx->d_bits, ctx->d_bits0, ctx->d_bits_clear, ctx->d_bb_scratch, ctx->d_arena, ctx->d_comm_key, ctx->d_comm_idx, ctx->d_kmpc_warm, ctx->d_kmpc_qp_warm, ctx->d_kmpc_scratch, ctx->d_mix_scratch, ctx->d_split_scratch, ctx->d_rec_scratch, ctx->d_st_scratch, ctx->d_audit, ctx->d_audit_buf, ctx->d_cl_theta[0], ctx->d_cl_theta[1], ctx->d_step, ctx->d_comm_rec, ctx->d_order, ctx->d_kmpc_cfg};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -1341,6 +1341,144 @@ int f1p_kmpc_set_groups(f1p_ctx* ctx, int32_t groups) {
     if (!ctx) return F1P_EINVAL;
     if (groups < 0 || groups > 64) return set_error(ctx, F1P_EINVAL, "groups must be in [0, 64]");
     ctx->kmpc_groups = groups;
+    return F1P_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// the reference's linearised QP (k_kmpc_qp.hip)
+// ---------------------------------------------------------------------------------------------------
+void f1p_kmpc_qp_opts_default(f1p_kmpc_qp_opts* opts) {
+    if (!opts) return;
+    memset(opts, 0, sizeof(*opts));
+    opts->max_iter = 50; opts->tol = 1e-10;
+}
+
+// the cfg checks of the shooting path, the diagonal weights' and bounds' sanity, horizon <= 32 (n = 2T inputs, one lane each); opts
+static int validate_kmpc_qp(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, int E, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o) {
+    int rc = validate_kmpc(ctx, cfg, E); if (rc) return rc;
+    if (cfg->horizon > 32) return set_error(ctx, F1P_EINVAL, "kmpc qp: horizon must be <= 32");
+    if (cfg->horizon < 2) return set_error(ctx, F1P_EINVAL, "kmpc qp: horizon must be >= 2");
+    for (int k = 0; k < 4; ++k)
+        if (!(cfg->q[k] >= 0) || !(cfg->qf[k] >= 0) || !isfinite(cfg->q[k]) || !isfinite(cfg->qf[k]))
+            return set_error(ctx, F1P_EINVAL, "kmpc qp: state weights must be finite and >= 0");
+    for (int k = 0; k < 2; ++k)
+        if (!(cfg->r[k] > 0) || !(cfg->rd[k] >= 0) || !isfinite(cfg->r[k]) || !isfinite(cfg->rd[k]))
+            return set_error(ctx, F1P_EINVAL, "kmpc qp: input weights must be finite, r > 0 (strict convexity), rd >= 0");
+    if (!(cfg->max_accel > 0) || !(cfg->max_steer > 0) || !(cfg->max_dsteer > 0) || !(cfg->max_speed >= cfg->min_speed))
+        return set_error(ctx, F1P_EINVAL, "kmpc qp: bounds must be > 0 and max_speed >= min_speed");
+    f1p_kmpc_qp_opts_default(o);
+    if (opts) *o = *opts;
+    if (o->max_iter < 0 || o->max_iter > 1000 || !(o->tol > 0) || !isfinite(o->tol))
+        return set_error(ctx, F1P_EINVAL, "kmpc qp: max_iter must be in [0, 1000] and tol finite and > 0");
+    return F1P_OK;
+}
+
+int f1p_kmpc_qp_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_prev, int32_t E,
+                    const f1p_kmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, double* d_steer, double* d_speed, int32_t* d_status,
+                    double* d_u, double* d_xk, double* d_obj, double* d_duals, int32_t* d_iters) {
+    F1P_ENTER(ctx);
+    f1p_kmpc_qp_opts o;
+    int rc = validate_kmpc_qp(ctx, cfg, E, opts, &o); if (rc) return rc;
+    if (E > 0 && (!d_x0 || !d_ref || !d_steer || !d_speed || !d_status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
+    return launch_kmpc_qp(ctx, d_x0, d_ref, d_oa_prev, d_od_prev, 1, E, cfg, o.max_iter, o.tol, d_steer, d_speed, d_status, d_u, d_xk, d_obj,
+                          d_duals, d_iters, nullptr);
+}
+
+int f1p_kmpc_qp_batch(f1p_ctx* ctx, const double* x0, const double* ref, const double* oa_prev, const double* od_prev, int32_t E,
+                      const f1p_kmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, double* steer, double* speed, int32_t* status, double* u,
+                      double* xk, double* obj, double* duals, int32_t* iters) {
+    F1P_ENTER(ctx);
+    f1p_kmpc_qp_opts o;
+    int rc = validate_kmpc_qp(ctx, cfg, E, opts, &o); if (rc) return rc;
+    if (E > 0 && (!x0 || !ref || !steer || !speed || !status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
+    const size_t T = cfg->horizon, e = E;
+    Stage s(ctx);
+    s.need(8 * 4 * e); s.need(8 * e * 4 * (T + 1)); s.need(8 * e * T, oa_prev); s.need(8 * e * T, od_prev);
+    s.need(8 * e); s.need(8 * e); s.need(4 * e); s.need(8 * e * T * 2, u); s.need(8 * e * 4 * (T + 1), xk); s.need(8 * e, obj);
+    s.need(8 * e * (8 * T - 2), duals); s.need(4 * e, iters);
+    if ((rc = s.begin())) return rc;
+    const double *d_x0, *d_ref, *d_oa, *d_od;
+    if ((rc = s.in(x0, 4 * e, &d_x0))) return rc;
+    if ((rc = s.in(ref, e * 4 * (T + 1), &d_ref))) return rc;
+    if ((rc = s.in(oa_prev, e * T, &d_oa))) return rc;
+    if ((rc = s.in(od_prev, e * T, &d_od))) return rc;
+    double* d_steer = s.out(steer, e); double* d_speed = s.out(speed, e); int32_t* d_st = s.out(status, e);
+    double* d_u = s.out(u, e * T * 2); double* d_xk = s.out(xk, e * 4 * (T + 1)); double* d_obj = s.out(obj, e);
+    double* d_du = s.out(duals, e * (8 * T - 2)); int32_t* d_it = s.out(iters, e);
+    if ((rc = launch_kmpc_qp(ctx, d_x0, d_ref, d_oa, d_od, 1, E, cfg, o.max_iter, o.tol, d_steer, d_speed, d_st, d_u, d_xk, d_obj, d_du, d_it,
+                             nullptr))) return rc;
+    return s.finish();
+}
+
+// the ctx's fp64 QP warm buffer for (E, T); a change of shape drops the old contents
+static int ensure_qp_warm(f1p_ctx* ctx, int E, int T) {
+    if (ctx->d_kmpc_qp_warm && ctx->kmpc_qp_warm_E == E && ctx->kmpc_qp_warm_T == T) return F1P_OK;
+    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->d_kmpc_qp_warm) (void)hipFree(ctx->d_kmpc_qp_warm);
+    ctx->d_kmpc_qp_warm = nullptr; ctx->kmpc_qp_warm_valid = false; ctx->kmpc_qp_warm_E = ctx->kmpc_qp_warm_T = 0;
+    F1P_HIP(ctx, hipMalloc((void**)&ctx->d_kmpc_qp_warm, sizeof(double) * 2 * (size_t)E * T));
+    ctx->kmpc_qp_warm_E = E; ctx->kmpc_qp_warm_T = T;
+    return F1P_OK;
+}
+
+int f1p_kmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_kmpc_cfg* cfg, double dl, const f1p_kmpc_qp_opts* opts,
+                           double* steer, double* speed, int32_t* status, double* u, double* obj) {
+    F1P_ENTER(ctx);
+    f1p_kmpc_qp_opts o;
+    int rc = validate_kmpc_qp(ctx, cfg, E, opts, &o); if (rc) return rc;
+    if (E > 0 && (!x0 || !steer || !speed || !status)) return set_error(ctx, F1P_EINVAL, "x0, steer, speed and status are required");
+    if (!(dl > 0)) return set_error(ctx, F1P_EINVAL, "dl must be > 0");
+    if (ctx->n_wp < 2 || !ctx->has_psi) return set_error(ctx, F1P_ESTATE, "waypoints with a heading column are required");
+    if (E == 0) return F1P_OK;
+    const size_t T = cfg->horizon, e = E;
+    if ((rc = ensure_qp_warm(ctx, E, cfg->horizon))) return rc;
+    Stage s(ctx);
+    s.need(8 * 4 * e); s.need(8 * e * 4 * (T + 1));
+    s.need(8 * e); s.need(8 * e); s.need(4 * e); s.need(8 * e * T * 2, u); s.need(8 * e, obj);
+    if ((rc = s.begin())) return rc;
+    const double* d_x0;
+    if ((rc = s.in(x0, 4 * e, &d_x0))) return rc;
+    double* d_ref = (double*)arena_take(ctx, 8 * e * 4 * (T + 1));
+    double* d_steer = s.out(steer, e); double* d_speed = s.out(speed, e); int32_t* d_st = s.out(status, e);
+    double* d_u = s.out(u, e * T * 2); double* d_obj = s.out(obj, e);
+    if ((rc = launch_kmpc_ref(ctx, d_x0, E, cfg->horizon, cfg->dt, dl, d_ref))) return rc;            // calc_ref_trajectory_kinematic :162-206
+    const double* warm = ctx->kmpc_qp_warm_valid ? ctx->d_kmpc_qp_warm : nullptr;                    // None on the first call (:461-463)
+    // (oa, od) interleaved in the warm buffer [E][T][2]: stride 2; each ego's group reads its slice before it writes it
+    if ((rc = launch_kmpc_qp(ctx, d_x0, d_ref, warm, warm ? warm + 1 : nullptr, 2, E, cfg, o.max_iter, o.tol, d_steer, d_speed, d_st, d_u,
+                             nullptr, d_obj, nullptr, nullptr, ctx->d_kmpc_qp_warm))) return rc;
+    ctx->kmpc_qp_warm_valid = true;
+    return s.finish();
+}
+
+int f1p_kmpc_qp_warm_reset(f1p_ctx* ctx) {
+    if (!ctx) return F1P_EINVAL;
+    ctx->kmpc_qp_warm_valid = false;
+    return F1P_OK;
+}
+
+int f1p_kmpc_qp_warm_get(f1p_ctx* ctx, double* warm, int32_t E, int32_t T) {
+    F1P_ENTER(ctx);
+    if (!warm) return set_error(ctx, F1P_EINVAL, "warm is NULL");
+    if (!ctx->kmpc_qp_warm_valid || ctx->kmpc_qp_warm_E != E || ctx->kmpc_qp_warm_T != T) return set_error(ctx, F1P_ESTATE, "no qp warm start of this shape is held");
+    F1P_HIP(ctx, hipMemcpyAsync(warm, ctx->d_kmpc_qp_warm, sizeof(double) * 2 * (size_t)E * T, hipMemcpyDeviceToHost, ctx->stream));
+    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return F1P_OK;
+}
+
+int f1p_kmpc_qp_warm_set(f1p_ctx* ctx, const double* warm, int32_t E, int32_t T) {
+    F1P_ENTER(ctx);
+    if (!warm || E < 1 || T < 1) return set_error(ctx, F1P_EINVAL, "bad warm / E / T");
+    int rc = ensure_qp_warm(ctx, E, T); if (rc) return rc;
+    F1P_HIP(ctx, hipMemcpyAsync(ctx->d_kmpc_qp_warm, warm, sizeof(double) * 2 * (size_t)E * T, hipMemcpyHostToDevice, ctx->stream));
+    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->kmpc_qp_warm_valid = true;
+    return F1P_OK;
+}
+
+int f1p_kmpc_qp_set_pack(f1p_ctx* ctx, int32_t egos_per_wave) {
+    if (!ctx) return F1P_EINVAL;
+    if (egos_per_wave != 0 && egos_per_wave != 1 && egos_per_wave != 4) return set_error(ctx, F1P_EINVAL, "egos_per_wave must be 0, 1 or 4");
+    ctx->kmpc_qp_pack = egos_per_wave;
     return F1P_OK;
 }
 

@@ -449,4 +449,36 @@ __device__ __forceinline__ bool cell_of(const GridDev& g, double x, double y, in
     return inside;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// the kinematic bicycle (k_kmpc.hip's rollouts and predict, k_kmpc_qp.hip's linearisation point)
+// ---------------------------------------------------------------------------------------------------
+struct KmpcStep { double x, y, v, yaw; };
+
+// update_state_kinematic :223-243 (delta already clamped by the caller's projection; the clamp is repeated
+// here because the reference does it inside the step)
+// FAST: the range-reduced sincos core for cos/sin(yaw) and tan = sin/cos (valid while |yaw| <= 1e5, which the caller
+// checks once per ego: a rollout changes yaw by < 1 rad per step); otherwise the device library's full-range functions.
+template <bool FAST>
+__device__ __forceinline__ void kmpc_step(KmpcStep& s, double a, double delta, const f1p_kmpc_cfg& c) {
+    if (delta >= c.max_steer) delta = c.max_steer;             // :226-229
+    else if (delta <= -c.max_steer) delta = -c.max_steer;
+    double sn, cs, tn;
+    if (FAST) {
+        double sd, cd;
+        sincos_core(s.yaw, &sn, &cs);
+        sincos_core(delta, &sd, &cd);
+        tn = sd / cd;
+    } else {
+        sincos(s.yaw, &sn, &cs);
+        tn = tan(delta);
+    }
+    const double x = s.x + s.v * cs * c.dt;                    // :231
+    const double y = s.y + s.v * sn * c.dt;                    // :232
+    const double yaw = s.yaw + (s.v / c.wheelbase) * tn * c.dt;   // :233-235
+    double v = s.v + a * c.dt;                                 // :236
+    if (v > c.max_speed) v = c.max_speed;                      // :238-241
+    else if (v < c.min_speed) v = c.min_speed;
+    s.x = x; s.y = y; s.yaw = yaw; s.v = v;
+}
+
 }  // namespace f1p

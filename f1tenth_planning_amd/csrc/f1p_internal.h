@@ -72,6 +72,11 @@ struct f1p_ctx {
     int kmpc_cap_E = 0, kmpc_cap_R = 0;
     int kmpc_yaw_fixup = 1;            // k_kmpc_ref folds gathered course headings (kinematic_mpc.py:198-203); 0: the caller maintains the array
     int kmpc_groups = 0;               // 0 = automatic number of workgroups per ego; > 0 forces it (tests, A/B runs)
+    // the linearised-QP MPC (f1p_kmpc_qp_*): its fp64 warm start [E][T][2], keyed by (E, T) like the shooting one, and the packing knob
+    double* d_kmpc_qp_warm = nullptr;
+    int kmpc_qp_warm_E = 0, kmpc_qp_warm_T = 0;
+    bool kmpc_qp_warm_valid = false;
+    int kmpc_qp_pack = 0;              // egos per wave at T <= 8: 0 = default, 1 or 4 forces it (timing runs)
 
     // two-kernel branch and bound of the lattice planner: bounds and clothoids handed from the fit kernel to the evaluation kernel
     char* d_bb_scratch = nullptr;
@@ -197,6 +202,11 @@ int launch_kmpc_plan_gen(f1p_ctx* ctx, const double* d_x0, const double* d_ref, 
                          int32_t* d_best_idx, double* d_best_cost, double* d_best_seq);
 int launch_kmpc_gen_controls(f1p_ctx* ctx, float* d_controls, int E, const f1p_kmpc_cfg* cfg, const f1p_kmpc_sampler* smp, const float* d_warm);
 int kmpc_plan_groups(const f1p_ctx* ctx, int E, int R);
+// k_kmpc_qp.hip: prev (oa, od) read at pa[(e T + t) pstride], pd[...] (nullable: zeros); every output but steer / speed nullable
+int launch_kmpc_qp(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
+                   const f1p_kmpc_cfg* cfg, int max_iter, double tol, double* d_steer, double* d_speed, int32_t* d_status, double* d_u,
+                   double* d_xk, double* d_obj, double* d_duals, int32_t* d_iters, double* d_warm_out);
+int kmpc_qp_pack(const f1p_ctx* ctx, int T);
 int launch_kmpc_predict(f1p_ctx* ctx, const double* d_x0, const double* d_oa, const double* d_od, int E,
                         const f1p_kmpc_cfg* cfg, double* d_path);
 int launch_kmpc_ref(f1p_ctx* ctx, const double* d_states, int E, int horizon, double dt, double dl, double* d_ref);

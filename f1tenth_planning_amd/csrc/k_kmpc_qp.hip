@@ -1,0 +1,431 @@
+// k_kmpc_qp.hip -- the reference's linearised kinematic MPC QP (control/kinematic_mpc/kinematic_mpc.py:245-508), solved per ego in fp64.
+//
+// Per ego, in one launch:
+//   1. linearisation point (:452-475): (v_t, phi_t), t < T, of predict_motion_kinematic(x0, oa_prev, od_prev) -- the previous solution,
+//      NOT shifted -- through kmpc_step<false>, the step of k_kmpc_predict; get_kinematic_model_matrix(v_t, phi_t, 0) (:245-278)
+//   2. condensing: x = S u + s (s: the free response of the linear model, S: one column per input), so the objective of :324-331 becomes
+//      1/2 u'Hu + g'u + c over u = vec(uk) = (a_0, d_0, a_1, d_1, ...), n = 2T
+//   3. a primal-dual interior-point method (Mehrotra predictor-corrector) on  G u <= h  with the bounds of :379-389:
+//        a upper / lower, delta upper / lower (unit rows), rate upper / lower (first differences of delta),
+//        v_1..T upper / lower (DTK x prefix sums of a; v_0 is x0's speed: feasible iff MIN_SPEED <= v0 <= MAX_SPEED)
+//      Newton system (H + G' diag(lambda / s) G) du = rhs: the G'DG term is O(n^2) from suffix sums (G is never formed), factored by
+//      Cholesky.  Stop: |r_d| <= tol (1 + |g|), |r_p| <= tol (1 + |h|) and s'lambda <= tol (max-norms), or max_iter.  An ego whose
+//      Newton matrix stops being numerically positive definite before that (lambda / s ~ 1e16 on its active rows) stops there, solved
+//      when its residuals are below tol and s'lambda <= tol (1 + |objective|), otherwise not converged (status 2).
+//
+// Mapping: a group of G lanes per ego (G = 64: one ego per wave, T <= 32; G = 16: four egos per wave, T <= 8).  Lane i owns input u_i,
+// row i of H and of the Newton matrix, and the four inequality rows next to it:
+//   i = 2t   (a_t):     a_t upper, a_t lower, v_{t+1} upper, v_{t+1} lower
+//   i = 2t+1 (delta_t): delta_t upper, delta_t lower, rate_t upper, rate_t lower (none for t = T-1)
+// Matrices live in LDS (row i written by lane i, the pivot column read as broadcasts); group reductions are xor butterflies of width G.
+// Every ego runs until the last ego of its workgroup stops, but an ego that has stopped takes no further steps, so its result does not
+// depend on its neighbours (tests/test_gpu_kmpc_qp.py: batch invariance).
+#include "f1p_internal.h"
+
+namespace f1p {
+
+namespace {
+
+template <int G>
+__device__ __forceinline__ double gsum(double v) {
+#pragma unroll
+    for (int m = 1; m < G; m <<= 1) v += __shfl_xor(v, m, G);
+    return v;
+}
+template <int G>
+__device__ __forceinline__ double gmax(double v) {
+#pragma unroll
+    for (int m = 1; m < G; m <<= 1) {                    // NaN-propagating: a broken-down ego never looks converged
+        const double o = __shfl_xor(v, m, G);
+        v = (o > v || o != o) ? o : v;
+    }
+    return v;
+}
+template <int G>
+__device__ __forceinline__ double gmin(double v) {
+#pragma unroll
+    for (int m = 1; m < G; m <<= 1) v = fmin(v, __shfl_xor(v, m, G));
+    return v;
+}
+
+// doubles of LDS per ego
+__host__ __device__ inline int qp_lds_doubles(int T) {
+    const int n = 2 * T, Tp = T + 1;
+    return 4 * Tp * n + n * n + 3 * n + T + 4 + 8 * Tp + 6 * T;
+}
+
+struct QpLds {
+    double *S, *M, *H, *U, *W, *Y, *SUF, *x0, *ref, *fr, *vb, *pb, *cp, *sp, *pa, *pd;
+    __device__ QpLds(double* b, int T) {
+        const int n = 2 * T, Tp = T + 1;
+        S = b; M = b; b += 4 * Tp * n;             // S until H and g are formed, then the Newton matrix (n * n <= 4 (T+1) n)
+        H = b; b += n * n;
+        U = b; b += n; W = b; b += n; Y = b; b += n;
+        SUF = b; b += T;
+        x0 = b; b += 4;
+        ref = b; b += 4 * Tp;
+        fr = b; b += 4 * Tp;
+        vb = b; b += T; pb = b; b += T; cp = b; b += T; sp = b; b += T; pa = b; b += T; pd = b; b += T;
+    }
+};
+
+}  // namespace
+
+template <int G>
+__global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, const double* __restrict__ refg,
+                                                const double* pa_g, const double* pd_g, int pstride, int E, f1p_kmpc_cfg cfg,
+                                                int max_iter, double tol, double* __restrict__ steer, double* __restrict__ speed,
+                                                int32_t* __restrict__ status, double* __restrict__ u_out, double* __restrict__ xk_out,
+                                                double* __restrict__ obj_out, double* __restrict__ duals, int32_t* __restrict__ iters_out,
+                                                double* warm_out) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    constexpr int EPW = 64 / G;
+    const int T = cfg.horizon, n = 2 * T, Tp = T + 1;
+    const int grp = threadIdx.x / G, i = threadIdx.x % G;
+    const int e = blockIdx.x * EPW + grp;
+    const bool ego = e < E;
+    QpLds L(reinterpret_cast<double*>(lds_raw) + (size_t)grp * qp_lds_doubles(T), T);
+    const int tau = i >> 1, j = i & 1;
+    const bool in_n = i < n;
+    const double DTK = cfg.dt;
+    const double NaN = __builtin_nan("");
+
+    // ---- inputs -> LDS; finiteness ----------------------------------------------------------------------------------------------------
+    bool bad = false;
+    if (ego) {
+        for (int k = i; k < 4; k += G) { const double v = x0g[(size_t)e * 4 + k]; L.x0[k] = v; bad |= !isfinite(v); }
+        for (int k = i; k < 4 * Tp; k += G) { const double v = refg[(size_t)e * 4 * Tp + k]; L.ref[k] = v; bad |= !isfinite(v); }
+        for (int k = i; k < T; k += G) {
+            const double a = pa_g ? pa_g[((size_t)e * T + k) * pstride] : 0.0;
+            const double d = pd_g ? pd_g[((size_t)e * T + k) * pstride] : 0.0;
+            L.pa[k] = a; L.pd[k] = d; bad |= !(isfinite(a) && isfinite(d));
+        }
+    }
+    bad = gmax<G>(bad ? 1.0 : 0.0) > 0.0;
+    __syncthreads();
+    const double v0 = ego ? L.x0[2] : 0.0;
+    int st = !ego ? 0 : bad ? 3 : (v0 >= cfg.min_speed && v0 <= cfg.max_speed) ? 0 : 1;    // status 1: the t = 0 speed bound cannot hold
+    bool done = !ego || st != 0;
+
+    // ---- 1. linearisation point and the free response of the linear model ---------------------------------------------------------------
+    if (i == 0 && !done) {
+        KmpcStep s;
+        s.x = L.x0[0]; s.y = L.x0[1]; s.v = L.x0[2]; s.yaw = L.x0[3];
+        double fx = s.x, fy = s.y, fv = s.v, fw = s.yaw;
+        L.fr[0] = fx; L.fr[Tp] = fy; L.fr[2 * Tp] = fv; L.fr[3 * Tp] = fw;
+        for (int t = 0; t < T; ++t) {
+            const double vb = s.v, pb = s.yaw;          // path_predict[2, t], path_predict[3, t]
+            double sn, cs;
+            sincos(pb, &sn, &cs);
+            L.vb[t] = vb; L.pb[t] = pb; L.cp[t] = cs; L.sp[t] = sn;
+            // A x + C with delta_bar = 0: A[3, 2] = 0, C[3] = 0 (:262-276)
+            const double nx = fx + DTK * cs * fv + (-DTK * vb * sn) * fw + DTK * vb * sn * pb;
+            const double ny = fy + DTK * sn * fv + (DTK * vb * cs) * fw + (-DTK * vb * cs * pb);
+            fx = nx; fy = ny;
+            L.fr[t + 1] = fx; L.fr[Tp + t + 1] = fy; L.fr[2 * Tp + t + 1] = fv; L.fr[3 * Tp + t + 1] = fw;
+            kmpc_step<false>(s, L.pa[t], L.pd[t], cfg);
+        }
+    }
+    __syncthreads();
+
+    // ---- 2. condensing: column i of S, then row i of H and g_i ---------------------------------------------------------------------------
+    if (in_n && !done) {
+        double d0 = 0.0, d1 = 0.0, d2 = 0.0, d3 = 0.0;
+        for (int t = 0; t < Tp; ++t) {
+            if (t == tau + 1) {                          // B_tau e_j: B[2, 0] = DTK, B[3, 1] = DTK v / WB (cos(0)^2 = 1)
+                if (j == 0) d2 = DTK; else d3 = DTK * L.vb[tau] / cfg.wheelbase;
+            } else if (t > tau + 1) {                    // A_{t-1} d
+                const int q = t - 1;
+                const double n0 = d0 + DTK * L.cp[q] * d2 + (-DTK * L.vb[q] * L.sp[q]) * d3;
+                const double n1 = d1 + DTK * L.sp[q] * d2 + (DTK * L.vb[q] * L.cp[q]) * d3;
+                d0 = n0; d1 = n1;
+            }
+            L.S[(4 * t + 0) * n + i] = d0; L.S[(4 * t + 1) * n + i] = d1; L.S[(4 * t + 2) * n + i] = d2; L.S[(4 * t + 3) * n + i] = d3;
+        }
+    }
+    __syncthreads();
+    double g = 0.0;
+    if (in_n && !done) {
+        for (int t = 1; t < Tp; ++t) {
+            const double* w = t == T ? cfg.qf : cfg.q;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g += 2.0 * w[k] * L.S[(4 * t + k) * n + i] * (L.fr[k * Tp + t] - L.ref[k * Tp + t]);
+        }
+        for (int c = 0; c < n; ++c) {
+            double h = 0.0;
+            for (int t = 1; t < Tp; ++t) {
+                const double* w = t == T ? cfg.qf : cfg.q;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) h += 2.0 * w[k] * L.S[(4 * t + k) * n + i] * L.S[(4 * t + k) * n + c];
+            }
+            if (c == i) h += 2.0 * (cfg.r[j] + ((tau > 0) + (tau < T - 1)) * cfg.rd[j]);
+            if (c == i - 2 || c == i + 2) h -= 2.0 * cfg.rd[j];
+            L.H[i * n + c] = h;
+        }
+    }
+
+    // ---- 3. interior point ------------------------------------------------------------------------------------------------------------
+    const double MD = cfg.max_dsteer * DTK;
+    double h[4];
+    bool valid[4];
+    if (j == 0) { h[0] = cfg.max_accel; h[1] = cfg.max_accel; h[2] = cfg.max_speed - v0; h[3] = v0 - cfg.min_speed; }
+    else        { h[0] = cfg.max_steer; h[1] = cfg.max_steer; h[2] = MD; h[3] = MD; }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) valid[r] = in_n && (j == 0 || r < 2 || tau < T - 1);
+    double u = 0.0, s[4], lam[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { s[r] = valid[r] ? fmax(h[r], 1.0) : 1.0; lam[r] = valid[r] ? 1.0 : 0.0; }
+    double hmax = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) hmax = fmax(hmax, valid[r] ? fabs(h[r]) : 0.0);
+    const double gn = 1.0 + gmax<G>(in_n ? fabs(g) : 0.0), hn = 1.0 + gmax<G>(hmax);
+    const double m_rows = 8.0 * T - 2.0;
+    int it_done = 0;
+
+    // G x for this lane's rows (x published in vec[])
+    auto gmul = [&](const double* vec, double xi, double out[4]) {
+        if (!in_n) {
+            out[0] = out[1] = out[2] = out[3] = 0.0;
+        } else if (j == 0) {
+            double pre = 0.0;
+            for (int q = 0; q <= tau; ++q) pre += vec[2 * q];
+            out[0] = xi; out[1] = -xi; out[2] = DTK * pre; out[3] = -(DTK * pre);
+        } else {
+            const double r = tau < T - 1 ? vec[i + 2] - xi : 0.0;
+            out[0] = xi; out[1] = -xi; out[2] = r; out[3] = -r;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) out[r] = valid[r] ? out[r] : 0.0;
+    };
+    // (G' w)_i: the rows' w_2 - w_3 published in W[]
+    auto gtmul = [&](const double w[4]) -> double {
+        double w2 = valid[2] ? w[2] - w[3] : 0.0;
+        __syncthreads();
+        if (in_n) L.W[i] = w2;
+        __syncthreads();
+        double o = (valid[0] ? w[0] : 0.0) - (valid[1] ? w[1] : 0.0);
+        if (!in_n) {
+            o = 0.0;
+        } else if (j == 0) {
+            double suf = 0.0;
+            for (int q = T - 1; q >= tau; --q) suf += L.W[2 * q];
+            o += DTK * suf;
+        } else {
+            o += -w2 + (tau > 0 ? L.W[i - 2] : 0.0);
+        }
+        return o;
+    };
+    // publish x_i in U[] and return it (barriers on both sides)
+    auto publish = [&](double* vec, double xi) {
+        __syncthreads();
+        if (in_n) vec[i] = xi;
+        __syncthreads();
+    };
+
+    for (int it = 0;; ++it) {
+        // residuals
+        publish(L.U, u);
+        double Gu[4], rp[4];
+        gmul(L.U, u, Gu);
+        double rpmax = 0.0, gap = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            rp[r] = valid[r] ? Gu[r] + s[r] - h[r] : 0.0;
+            rpmax = fmax(rpmax, fabs(rp[r]));
+            gap += valid[r] ? s[r] * lam[r] : 0.0;
+        }
+        double Hu = 0.0;
+        if (in_n) for (int c = 0; c < n; ++c) Hu += L.H[i * n + c] * L.U[c];
+        const double gtl = gtmul(lam);
+        const double rd = in_n ? Hu + g + gtl : 0.0;
+        const double rdn = gmax<G>(fabs(rd)) / gn, rpn = gmax<G>(rpmax) / hn;
+        gap = gsum<G>(gap);
+        const double f = gsum<G>(in_n ? u * (0.5 * Hu + g) : 0.0);
+        // converged: residuals and the gap s'lambda below tol.  The gap relative to the objective is the fallback for an ego whose
+        // Newton matrix can no longer be factored (lambda / s ~ 1e16 on its active rows) before the absolute gap is reached.
+        const bool res_ok = rdn <= tol && rpn <= tol;
+        const bool gap_rel_ok = res_ok && gap <= tol * (1.0 + fabs(f));
+        if (!done) {
+            if (res_ok && gap <= tol) { done = true; st = 0; it_done = it; }
+            else if (it >= max_iter) { done = true; st = 2; it_done = it; }
+        }
+        if (!__syncthreads_or(!done)) break;
+
+        // Newton matrix M = H + G' diag(lambda / s) G, row i
+        double D[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) D[r] = valid[r] ? lam[r] / s[r] : 0.0;
+        publish(L.W, D[2] + D[3]);
+        if (j == 0 && in_n) {
+            double suf = 0.0;
+            for (int q = T - 1; q >= tau; --q) suf += L.W[2 * q];
+            L.SUF[tau] = suf;
+        }
+        __syncthreads();
+        if (in_n) {
+            for (int c = 0; c < n; ++c) {
+                double m = L.H[i * n + c];
+                if (j == 0 && (c & 1) == 0) m += DTK * DTK * L.SUF[max(tau, c >> 1)];
+                if (c == i) m += D[0] + D[1] + (j == 1 ? L.W[i] + (tau > 0 ? L.W[i - 2] : 0.0) : 0.0);
+                if (j == 1 && c == i + 2) m -= L.W[i];
+                if (j == 1 && c == i - 2) m -= L.W[i - 2];
+                L.M[i * n + c] = m;
+            }
+        }
+        // Cholesky, in place: lower triangle of M = L
+        bool broke = false;
+        for (int k = 0; k < n; ++k) {
+            __syncthreads();
+            const double mk = L.M[k * n + k];
+            broke |= !(mk > 0.0 && mk < INFINITY);
+            const double dk = sqrt(mk);
+            double l = 0.0;
+            if (i > k && in_n) { l = L.M[i * n + k] / dk; L.M[i * n + k] = l; }
+            __syncthreads();
+            if (i == k) L.M[k * n + k] = dk;
+            if (i > k && in_n) for (int c = k + 1; c <= i; ++c) L.M[i * n + c] -= l * L.M[c * n + k];
+        }
+        __syncthreads();
+        if (broke && !done) { done = true; st = gap_rel_ok ? 0 : 2; it_done = it; }     // (broke is uniform over the group)
+
+        // one Newton solve for the complementarity right-hand side rc
+        auto newton = [&](const double rc[4], double& du, double ds[4], double dl[4]) {
+            double w[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) w[r] = valid[r] ? (lam[r] * rp[r] - rc[r]) / s[r] : 0.0;
+            double b = -rd - gtmul(w);
+            for (int k = 0; k < n; ++k) {                // L y = b
+                if (i == k) { b = b / L.M[k * n + k]; L.Y[k] = b; }
+                __syncthreads();
+                if (i > k && in_n) b -= L.M[i * n + k] * L.Y[k];
+            }
+            for (int k = n - 1; k >= 0; --k) {           // L' x = y
+                if (i == k) { b = b / L.M[k * n + k]; L.Y[k] = b; }
+                __syncthreads();
+                if (i < k) b -= L.M[k * n + i] * L.Y[k];
+            }
+            du = in_n ? b : 0.0;
+            double Gd[4];
+            publish(L.U, du);
+            gmul(L.U, du, Gd);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                ds[r] = valid[r] ? -rp[r] - Gd[r] : 0.0;
+                dl[r] = valid[r] ? (-rc[r] - lam[r] * ds[r]) / s[r] : 0.0;
+            }
+        };
+        auto step_max = [&](const double ds[4], const double dl[4]) -> double {
+            double a = 1.0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (valid[r] && ds[r] < 0.0) a = fmin(a, -s[r] / ds[r]);
+                if (valid[r] && dl[r] < 0.0) a = fmin(a, -lam[r] / dl[r]);
+            }
+            return gmin<G>(a);
+        };
+        const double mu = gap / m_rows;
+        double rc[4], du, ds[4], dl[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rc[r] = valid[r] ? s[r] * lam[r] : 0.0;
+        newton(rc, du, ds, dl);                          // predictor (affine scaling)
+        double a = step_max(ds, dl), gap_aff = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) gap_aff += valid[r] ? (s[r] + a * ds[r]) * (lam[r] + a * dl[r]) : 0.0;
+        gap_aff = gsum<G>(gap_aff);
+        const double ratio = gap_aff / gap, sigma = ratio * ratio * ratio;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rc[r] = valid[r] ? s[r] * lam[r] + ds[r] * dl[r] - sigma * mu : 0.0;
+        newton(rc, du, ds, dl);                          // corrector
+        a = fmin(1.0, 0.99 * step_max(ds, dl));
+        if (!done) {
+            u += a * du;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) if (valid[r]) { s[r] += a * ds[r]; lam[r] += a * dl[r]; }
+        }
+    }
+
+    // ---- outputs --------------------------------------------------------------------------------------------------------------------
+    if (!ego) return;
+    const bool ok = st == 0 || st == 2;
+    publish(L.U, u);
+    if (in_n) {
+        if (u_out) u_out[(size_t)e * n + i] = ok ? u : NaN;
+        if (warm_out) warm_out[(size_t)e * n + i] = ok ? u : 0.0;     // a failed solve leaves the reference's oa / od = None: zeros next call
+        if (duals) {
+            double* du_ = duals + (size_t)e * (8 * T - 2);
+            const int R4 = 4 * T, R6 = 6 * T - 2;
+            if (j == 0) {
+                du_[tau] = ok ? lam[0] : NaN; du_[T + tau] = ok ? lam[1] : NaN;
+                du_[R6 + tau] = ok ? lam[2] : NaN; du_[R6 + T + tau] = ok ? lam[3] : NaN;
+            } else {
+                du_[2 * T + tau] = ok ? lam[0] : NaN; du_[3 * T + tau] = ok ? lam[1] : NaN;
+                if (tau < T - 1) { du_[R4 + tau] = ok ? lam[2] : NaN; du_[R4 + T - 1 + tau] = ok ? lam[3] : NaN; }
+            }
+        }
+    }
+    if (i == 0) {
+        if (status) status[e] = st;
+        if (iters_out) iters_out[e] = ok ? it_done : 0;
+        steer[e] = ok ? L.U[1] : NaN;                                   // :503
+        speed[e] = ok ? v0 + L.U[0] * DTK : NaN;                        // :505
+        if (xk_out || obj_out) {
+            // x_{t+1} = A_t x_t + B_t u_t + C_t and the objective cvxpy reports (:324-331), the constant t = 0 term included
+            double x = L.x0[0], y = L.x0[1], v = L.x0[2], w = L.x0[3], f = 0.0;
+            double* xo = xk_out ? xk_out + (size_t)e * 4 * Tp : nullptr;
+            for (int t = 0; t < Tp; ++t) {
+                if (xo) { xo[t] = ok ? x : NaN; xo[Tp + t] = ok ? y : NaN; xo[2 * Tp + t] = ok ? v : NaN; xo[3 * Tp + t] = ok ? w : NaN; }
+                const double* q = t == T ? cfg.qf : cfg.q;
+                const double ex = x - L.ref[t], ey = y - L.ref[Tp + t], ev = v - L.ref[2 * Tp + t], ew = w - L.ref[3 * Tp + t];
+                f += q[0] * ex * ex + q[1] * ey * ey + q[2] * ev * ev + q[3] * ew * ew;
+                if (t == T) break;
+                const double a = L.U[2 * t], d = L.U[2 * t + 1];
+                f += cfg.r[0] * a * a + cfg.r[1] * d * d;
+                if (t < T - 1) {
+                    const double da = L.U[2 * t + 2] - a, dd = L.U[2 * t + 3] - d;
+                    f += cfg.rd[0] * da * da + cfg.rd[1] * dd * dd;
+                }
+                const double vb = L.vb[t], pb = L.pb[t], cs = L.cp[t], sn = L.sp[t];
+                const double nx = x + DTK * cs * v + (-DTK * vb * sn) * w + DTK * vb * sn * pb;
+                const double ny = y + DTK * sn * v + (DTK * vb * cs) * w + (-DTK * vb * cs * pb);
+                const double nv = v + DTK * a;
+                const double nw = w + (DTK * vb / cfg.wheelbase) * d;
+                x = nx; y = ny; v = nv; w = nw;
+            }
+            if (obj_out) obj_out[e] = ok ? f : NaN;
+        }
+    }
+}
+
+#ifndef F1P_KMPC_QP_PACK_T8
+#define F1P_KMPC_QP_PACK_T8 4         // egos per wave at T <= 8 (1 or 4)
+#endif
+
+int kmpc_qp_pack(const f1p_ctx* ctx, int T) {
+    if (T > 8) return 1;
+    return ctx->kmpc_qp_pack > 0 ? ctx->kmpc_qp_pack : F1P_KMPC_QP_PACK_T8;
+}
+
+int launch_kmpc_qp(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
+                   const f1p_kmpc_cfg* cfg, int max_iter, double tol, double* d_steer, double* d_speed, int32_t* d_status, double* d_u,
+                   double* d_xk, double* d_obj, double* d_duals, int32_t* d_iters, double* d_warm_out) {
+    if (E <= 0) return F1P_OK;
+    const int T = cfg->horizon;
+    const int epw = kmpc_qp_pack(ctx, T) == 4 ? 4 : 1;
+    const size_t lds = sizeof(double) * (size_t)qp_lds_doubles(T) * epw;
+    const void* kern = epw == 4 ? reinterpret_cast<const void*>(&k_kmpc_qp<16>) : reinterpret_cast<const void*>(&k_kmpc_qp<64>);
+    if (lds > (size_t)ctx->prop.sharedMemPerBlock) {
+        if (lds > (size_t)ctx->prop.maxSharedMemoryPerMultiProcessor)
+            return set_error(ctx, F1P_EINVAL, "kmpc qp: horizon too long for the CU's LDS");
+        F1P_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    const dim3 grid((unsigned)((E + epw - 1) / epw));
+    if (epw == 4)
+        hipLaunchKernelGGL(k_kmpc_qp<16>, grid, dim3(64), lds, ctx->stream, d_x0, d_ref, d_pa, d_pd, pstride, E, *cfg, max_iter, tol, d_steer,
+                           d_speed, d_status, d_u, d_xk, d_obj, d_duals, d_iters, d_warm_out);
+    else
+        hipLaunchKernelGGL(k_kmpc_qp<64>, grid, dim3(64), lds, ctx->stream, d_x0, d_ref, d_pa, d_pd, pstride, E, *cfg, max_iter, tol, d_steer,
+                           d_speed, d_status, d_u, d_xk, d_obj, d_duals, d_iters, d_warm_out);
+    return check_hip(ctx, hipGetLastError(), "k_kmpc_qp launch");
+}
+
+}  // namespace f1p

@@ -590,6 +590,64 @@ class Context:
     def kmpc_set_groups(self, groups=0):
         self._check(self.lib.f1p_kmpc_set_groups(self.h, int(groups)))
 
+    # ---- kinematic MPC, the reference's linearised QP (f1p_kmpc_qp_*) ----------------------------------------------------------------
+    def kmpc_qp(self, x0, ref, cfg: KmpcCfg, oa_prev=None, od_prev=None, opts=None, want_u=True, want_xk=False, want_obj=True,
+                want_duals=False, want_iters=True):
+        """linear_mpc_control_kinematic (kinematic_mpc.py:452-475) solved exactly for E egos: x0 [E, 4], ref [E, 4, T+1], the previous
+        solution oa_prev / od_prev [E, T] (None: zeros) -> dict(steer, speed, status[, u [E, T, 2], xk [E, 4, T+1], obj, duals [E, 8T-2],
+        iters]).  status: 0 solved, 1 infeasible, 2 not converged, 3 non-finite input (1 and 3: NaN outputs)."""
+        x0 = _f64(x0, (-1, 4)); E = x0.shape[0]; T = cfg.horizon
+        ref = _f64(ref, (E, 4, T + 1))
+        oa = None if oa_prev is None else _f64(oa_prev, (E, T))
+        od = None if od_prev is None else _f64(od_prev, (E, T))
+        out = dict(steer=np.empty(E), speed=np.empty(E), status=np.empty(E, np.int32))
+        for k, want, shape, dt in (("u", want_u, (E, T, 2), np.float64), ("xk", want_xk, (E, 4, T + 1), np.float64), ("obj", want_obj, (E,), np.float64),
+                                   ("duals", want_duals, (E, 8 * T - 2), np.float64), ("iters", want_iters, (E,), np.int32)):
+            if want:
+                out[k] = np.empty(shape, dt)
+        self._check(self.lib.f1p_kmpc_qp_batch(self.h, _ptr(x0), _ptr(ref), _ptr(oa), _ptr(od), E, C.byref(cfg),
+                                               None if opts is None else C.byref(opts), _ptr(out["steer"]), _ptr(out["speed"]),
+                                               _ptr(out["status"]), _ptr(out.get("u")), _ptr(out.get("xk")), _ptr(out.get("obj")),
+                                               _ptr(out.get("duals")), _ptr(out.get("iters"))))
+        return out
+
+    def kmpc_qp_dev(self, d_x0, d_ref, E, cfg: KmpcCfg, d_steer, d_speed, d_status, d_oa_prev=None, d_od_prev=None, opts=None, d_u=None,
+                    d_xk=None, d_obj=None, d_duals=None, d_iters=None):
+        p = lambda b: None if b is None else b.ptr   # noqa: E731
+        self._check(self.lib.f1p_kmpc_qp_dev(self.h, p(d_x0), p(d_ref), p(d_oa_prev), p(d_od_prev), int(E), C.byref(cfg),
+                                             None if opts is None else C.byref(opts), p(d_steer), p(d_speed), p(d_status), p(d_u), p(d_xk),
+                                             p(d_obj), p(d_duals), p(d_iters)))
+
+    def kmpc_qp_plan(self, x0, cfg: KmpcCfg, dl=0.03, opts=None, want_u=True, want_obj=True):
+        """KMPCPlanner.plan with the QP solver for E egos in ONE call: reference extraction, linearisation about the ctx's fp64 warm start
+        (the previous call's solution, unshifted), solve, output map, new warm start -> dict(steer, speed, status[, u, obj])"""
+        x0 = _f64(x0, (-1, 4)); E = x0.shape[0]; T = cfg.horizon
+        out = dict(steer=np.empty(E), speed=np.empty(E), status=np.empty(E, np.int32))
+        if want_u:
+            out["u"] = np.empty((E, T, 2))
+        if want_obj:
+            out["obj"] = np.empty(E)
+        self._check(self.lib.f1p_kmpc_qp_plan_batch(self.h, _ptr(x0), E, C.byref(cfg), float(dl), None if opts is None else C.byref(opts),
+                                                    _ptr(out["steer"]), _ptr(out["speed"]), _ptr(out["status"]), _ptr(out.get("u")),
+                                                    _ptr(out.get("obj"))))
+        return out
+
+    def kmpc_qp_warm_reset(self):
+        self._check(self.lib.f1p_kmpc_qp_warm_reset(self.h))
+
+    def kmpc_qp_warm_get(self, E, T):
+        w = np.empty((int(E), int(T), 2))
+        self._check(self.lib.f1p_kmpc_qp_warm_get(self.h, _ptr(w), int(E), int(T)))
+        return w
+
+    def kmpc_qp_warm_set(self, warm):
+        w = _f64(warm)
+        self._check(self.lib.f1p_kmpc_qp_warm_set(self.h, _ptr(w), w.shape[0], w.shape[1]))
+
+    def kmpc_qp_set_pack(self, egos_per_wave=0):
+        """egos per wave of the QP kernel at T <= 8 (0: default, 1 or 4)"""
+        self._check(self.lib.f1p_kmpc_qp_set_pack(self.h, int(egos_per_wave)))
+
     def kmpc_sample_controls_dev(self, d_controls, E, cfg: KmpcCfg, seed, sigma_accel=1.5, sigma_steer=0.15):
         self._check(self.lib.f1p_kmpc_sample_controls_dev(self.h, d_controls.ptr, int(E), C.byref(cfg),
                                                           C.c_uint64(int(seed)), float(sigma_accel), float(sigma_steer)))

@@ -503,6 +503,55 @@ int f1p_kmpc_set_groups(f1p_ctx* ctx, int32_t groups);
 int f1p_kmpc_set_yaw_fixup(f1p_ctx* ctx, int32_t on);
 
 /* ------------------------------------------------------------------------------------------------
+ * Kinematic MPC as the reference solves it: the linearised QP of control/kinematic_mpc/kinematic_mpc.py, batched, fp64
+ * (csrc/k_kmpc_qp.hip; DESIGN.md "The linearised QP").  Per ego:
+ *   linearisation point (linear_mpc_control_kinematic :452-475): rows v, yaw of predict_motion_kinematic(x0, oa_prev, od_prev)
+ *     (:208-243) -- the previous solution NOT shifted; zeros when NULL (the first call, after a reset);
+ *   model (get_kinematic_model_matrix :245-278) at (v_t, phi_t, delta = 0): A[3][2] = 0, B[3][1] = DTK v / WB, C[3] = 0;
+ *   problem (mpc_prob_init_kinematic :283-405):  min  sum_t u_t' Rk u_t + sum_{t<=T} (x_t - ref_t)' Q (x_t - ref_t) (Qfk at T)
+ *     + sum_{t<T-1} (u_{t+1} - u_t)' Rdk (u_{t+1} - u_t)  s.t.  x_{t+1} = A_t x_t + B_t u_t + C_t, x_0 = x0, |a_t| <= MAX_ACCEL,
+ *     |delta_t| <= MAX_STEER, |delta_{t+1} - delta_t| <= MAX_DSTEER DTK, MIN_SPEED <= v_t <= MAX_SPEED (t = 0..T);
+ *     diagonal weights only (cfg q, qf, r, rd); r > 0 makes it strictly convex: one optimum;
+ *   output map (:500-505): steer = delta_0, speed = v0 + a_0 DTK.
+ * Feasible iff MIN_SPEED <= v0 <= MAX_SPEED (then a = delta = 0 is feasible; otherwise the t = 0 speed bound cannot hold).
+ * Solver: primal-dual interior point (Mehrotra predictor-corrector) on the condensed problem (2T inputs), stopping when the scaled
+ * KKT residuals and the duality gap are below opts->tol, or after opts->max_iter iterations (an ego whose Newton matrix stops being
+ * numerically positive definite first counts as solved when its gap is below tol (1 + |objective|)).  2 <= horizon <= 32 (else
+ * F1P_EINVAL).
+ *   x0 [E][4] (x, y, v, yaw); ref [E][4][T+1] (f1p_kmpc_ref_batch); oa_prev, od_prev [E][T] (nullable: zeros)
+ * Outputs: steer, speed [E]; status [E]: 0 solved, 1 infeasible, 2 not converged (the last iterate, like cvxpy's OPTIMAL_INACCURATE),
+ *   3 non-finite input; statuses 1 and 3 give NaN in every output.  Nullable: u [E][T][2] (accel, steer), xk [E][4][T+1] (the
+ *   states of the linear model), obj [E] (the value cvxpy reports, the constant t = 0 term included), iters [E], and
+ *   duals [E][8T-2]: the multipliers of  a_t <= MAX_ACCEL (T), -a_t <= MAX_ACCEL (T), delta_t <= MAX_STEER (T), -delta_t <= MAX_STEER (T),
+ *   delta_{t+1} - delta_t <= MAX_DSTEER DTK (T-1), its negation (T-1), v_t <= MAX_SPEED for t = 1..T (T), -v_t <= -MIN_SPEED (T).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct f1p_kmpc_qp_opts {
+    int32_t max_iter;        /* interior-point iterations at most (50)                                              */
+    int32_t pad;
+    double tol;              /* stop when the scaled KKT residuals and the gap are below it (1e-10)                  */
+} f1p_kmpc_qp_opts;
+void f1p_kmpc_qp_opts_default(f1p_kmpc_qp_opts* opts);
+int f1p_kmpc_qp_batch(f1p_ctx* ctx, const double* x0, const double* ref, const double* oa_prev, const double* od_prev, int32_t E,
+                      const f1p_kmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, double* steer, double* speed, int32_t* status, double* u,
+                      double* xk, double* obj, double* duals, int32_t* iters);
+/* the same on device buffers; asynchronous on the ctx stream */
+int f1p_kmpc_qp_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_prev, int32_t E,
+                    const f1p_kmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, double* d_steer, double* d_speed, int32_t* d_status,
+                    double* d_u, double* d_xk, double* d_obj, double* d_duals, int32_t* d_iters);
+/* What KMPCPlanner.plan does per call with the QP solver (MPC_Control_kinematic :477-508) for E egos in one call: reference extraction
+ * (:162-206) from the ctx waypoints (dl = mpc_config.dlk), linearisation about the ctx's QP warm start, solve, output map.  The warm start
+ * is the previous call's solution u [E][T][2] fp64 (self.oa / self.odelta_v, :490-498), kept on the device and keyed by (E, T) like the
+ * shooting one (separate from it); statuses 1 and 3 reset an ego's to zeros (the reference's None).  u, obj nullable. */
+int f1p_kmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_kmpc_cfg* cfg, double dl, const f1p_kmpc_qp_opts* opts,
+                           double* steer, double* speed, int32_t* status, double* u, double* obj);
+/* the QP warm start: forget it / read it back / install one (warm [E][T][2] fp64 host) */
+int f1p_kmpc_qp_warm_reset(f1p_ctx* ctx);
+int f1p_kmpc_qp_warm_get(f1p_ctx* ctx, double* warm, int32_t E, int32_t T);
+int f1p_kmpc_qp_warm_set(f1p_ctx* ctx, const double* warm, int32_t E, int32_t T);
+/* egos per wave of the QP kernel at T <= 8: 0 = default, 1 or 4 forces it (timing runs; longer horizons always take one per wave) */
+int f1p_kmpc_qp_set_pack(f1p_ctx* ctx, int32_t egos_per_wave);
+
+/* ------------------------------------------------------------------------------------------------
  * SURVEY.md 8f rank 2 -- the dynamic single-track model as a second model for shooting MPC
  * (control/dynamic_mpc/dynamic_mpc.py): predict_motion / update_state (:280-404), calc_ref_trajectory (:195-233),
  * objective :616-622, bounds :685-706, output map :1112-1117.
