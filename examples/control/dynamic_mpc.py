@@ -1,4 +1,4 @@
-"""Single-track MPC (random shooting; kinematic model below V_KS, dynamic model above) in closed loop
+"""Single-track MPC (random shooting, or with --solver qp the reference's linearised QPs; kinematic model below V_KS, dynamic model above) in closed loop
 (loop shape of the reference's examples/control/dynamic_mpc.py)."""
 import os
 import sys
@@ -11,11 +11,12 @@ from f1tenth_planning.control.dynamic_mpc.dynamic_mpc import STMPCPlanner, mpc_c
 
 def main():
     ap = common.parser(__doc__, steps=600)
+    ap.add_argument("--solver", choices=["shooting", "qp"], default="shooting")
     args = ap.parse_args()
     if args.envs != 1:
         raise SystemExit("STMPCPlanner.plan drives one vehicle; use kinematic_mpc.py --envs N for the batched path")
     rl = common.raceline(args, centerline=True)
-    planner = STMPCPlanner(waypoints=[rl[:, 0], rl[:, 1], rl[:, 3], rl[:, 2]], config=mpc_config())
+    planner = STMPCPlanner(waypoints=[rl[:, 0], rl[:, 1], rl[:, 3], rl[:, 2]], config=mpc_config(SOLVER=args.solver))
 
     def plan(obs, env):
         steer, speed = planner.plan(env.sim.agents[0].state)

@@ -239,6 +239,13 @@ PROTOTYPES = {
     "f1p_kmpc_qp_warm_get": (C.c_int, [_P, _P, _I, _I]),
     "f1p_kmpc_qp_warm_set": (C.c_int, [_P, _P, _I, _I]),
     "f1p_kmpc_qp_set_pack": (C.c_int, [_P, _I]),
+    "f1p_stmpc_qp_batch": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcQpOpts), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f1p_stmpc_qp_dev": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcQpOpts), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f1p_stmpc_qp_plan_batch": (C.c_int, [_P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcCfg), _D, _D, _D, C.POINTER(KmpcQpOpts), _P, _P,
+                                          _P, _P, _P, _P]),
+    "f1p_stmpc_qp_warm_reset": (C.c_int, [_P]),
+    "f1p_stmpc_qp_warm_get": (C.c_int, [_P, _P, _P, _I, _I]),
+    "f1p_stmpc_qp_warm_set": (C.c_int, [_P, _P, _P, _I, _I]),
     "f1p_stmpc_cfg_default": (None, [C.POINTER(StmpcCfg)]),
     "f1p_stmpc_predict_batch": (C.c_int, [_P, _P, _P, _P, _I, C.POINTER(StmpcCfg), _P]),
     "f1p_stmpc_ref_batch": (C.c_int, [_P, _P, _I, _I, _D, _D, _P]),

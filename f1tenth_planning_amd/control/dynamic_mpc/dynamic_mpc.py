@@ -5,6 +5,10 @@ reference (f1tenth_planning/control/dynamic_mpc/dynamic_mpc.py:40-191).  Like th
 at or below V_KS the kinematic model is used (:168-180), above it the dynamic single-track model (:181-191).  Both are
 solved by rolling R sampled control sequences through the reference's own nonlinear step on the GPU (csrc/k_kmpc.hip,
 csrc/k_stmpc.hip) instead of the reference's cvxpy/OSQP QP (third-party, out of scope).
+
+mpc_config.SOLVER = "qp" selects the reference's own solver instead: the linearised QPs of :575-833, solved exactly (to QP_TOL) by
+batched fp64 interior-point kernels -- csrc/k_stmpc_qp.hip for the dynamic branch, csrc/k_kmpc_qp.hip for the kinematic one --
+warm-started like the reference from the previous solution (unshifted, with its reset rules :1005, :1052).
 """
 import os
 from dataclasses import dataclass, field
@@ -53,11 +57,32 @@ class mpc_config:
     SIGMA_ACCEL: float = 1.5     # std of the acceleration samples [m/ss]
     SIGMA_STEER: float = 0.15    # std of the steering samples of the kinematic branch [rad]
     SEED: int = 0
+    # solver: "shooting" (the default above) or "qp" -- the reference's own linearised QPs (:575-833) solved exactly in fp64 on the GPU
+    SOLVER: str = "shooting"
+    QP_TOL: float = 1e-10  # interior point: scaled KKT residuals and duality gap below this
+    QP_MAX_ITER: int = 50  # interior-point iterations at most (status 2 beyond: the last iterate, like cvxpy's OPTIMAL_INACCURATE)
 
 
 def _diag(m):
     m = np.asarray(m.todense()) if hasattr(m, "todense") else np.asarray(m)
     return np.diag(m) if m.ndim == 2 else m
+
+
+_SOLVERS = ("shooting", "qp")
+
+
+def _check_solver(c: mpc_config):
+    """ValueError before anything touches the GPU: an unknown SOLVER, or weights the QP path does not take (diagonal only)"""
+    if c.SOLVER not in _SOLVERS:
+        raise ValueError(f"mpc_config.SOLVER must be one of {_SOLVERS}, not {c.SOLVER!r}")
+    if c.SOLVER == "qp":
+        for name, n in (("R", 2), ("Rd", 2), ("Q", 7), ("Qf", 7), ("Rk", 2), ("Rdk", 2), ("Qk", 4), ("Qfk", 4)):
+            w = getattr(c, name)
+            w = np.asarray(w.todense() if hasattr(w, "todense") else w, dtype=np.float64)
+            if w.shape != (n, n) or np.any(w - np.diag(np.diag(w)) != 0):
+                raise ValueError(f"SOLVER='qp' takes diagonal {n}x{n} weights only; mpc_config.{name} is not")
+        if c.TK > c.T:
+            raise ValueError("SOLVER='qp' needs TK <= T (the reference's kinematic branch would linearise about a cut-short prediction)")
 
 
 class STMPCPlanner:
@@ -83,6 +108,7 @@ class STMPCPlanner:
         self._device = device
         self._ctx = None
         self._calls = 0
+        _check_solver(config)
 
     def _context(self):
         if self._ctx is None:
@@ -123,11 +149,46 @@ class STMPCPlanner:
         ctrl[0, :, :, 0] = 0.0                                    # rollout 0: coast
         return ctrl
 
+    def _qp(self, ctx, x0, want_u=True):
+        """One C call per plan (f1p_stmpc_qp_plan_batch): per ego the branch (:168), reference extraction (:195-276), linearisation about
+        the previous solution held on the device (unshifted, reset by the rules of :1005 / :1052), the branch's QP solved to tolerance,
+        output map (:1112-1117, :1205-1207), new warm start."""
+        c = self.config
+        return ctx.stmpc_qp_plan(x0, self._dyn_cfg(), self._kin_cfg(), v_ks=c.V_KS, dl=c.dl, dlk=c.dlk,
+                                 opts=_abi.kmpc_qp_opts(max_iter=c.QP_MAX_ITER, tol=c.QP_TOL), want_u=want_u)
+
+    def plan_batch(self, states, waypoints=None, want_u=True):
+        """SOLVER == "qp": states [E, 7] -> dict(steer, speed, status, branch (1 dynamic, 0 kinematic), obj[, u [E, max(T, TK), 2] =
+        (oa, odelta_v), NaN past the branch's horizon]) -- per-ego status (0 solved, 1 infeasible, 2 not converged, 3 non-finite input
+        or model data), never raised."""
+        _check_solver(self.config)
+        if self.config.SOLVER != "qp":
+            raise ValueError("plan_batch needs SOLVER='qp'")
+        ctx = self._bind(waypoints)
+        return self._qp(ctx, np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 7), want_u=want_u)
+
+    def reset(self):
+        """forget the warm start (a new episode)"""
+        self._calls = 0
+        self.oa = self.odelta_v = None
+        if self._ctx is not None:
+            self._ctx.stmpc_qp_warm_reset()
+
     def plan(self, states, waypoints=None):
         """states: [x, y, delta, v, yaw, yawrate, beta].  Returns (steering_angle, speed)."""
+        _check_solver(self.config)
         ctx = self._bind(waypoints)
         c = self.config
         st = np.asarray(states, dtype=np.float64)
+        if c.SOLVER == "qp":
+            out = self._qp(ctx, st[None, :7])
+            s = int(out["status"][0])
+            if s in (1, 3):         # the reference cannot go on either: its oa / odelta_v are None (:1112, :1205)
+                raise RuntimeError("dynamic MPC QP: " + ("infeasible (steering or speed outside its bounds)" if s == 1 else
+                                                         "non-finite input or model data"))
+            n = c.T if out["branch"][0] else c.TK
+            self.oa, self.odelta_v = out["u"][0, :n, 0].copy(), out["u"][0, :n, 1].copy()
+            return float(out["steer"][0]), float(out["speed"][0])
         if st[3] <= c.V_KS:                                      # kinematic branch (:168-180)
             cfg = self._kin_cfg()
             x0 = np.array([[st[0], st[1], st[3], st[4]]])

@@ -315,7 +315,7 @@ void f1p_destroy(f1p_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     f1p_comm_destroy(ctx);
-    void* ptrs[] = {ctx->d_wx, ctx->d_wy, ctx->d_wv, ctx->d_wpsi, ctx->d_wkappa, ctx->d_wbox, ctx->d_bits, ctx->d_bits0, ctx->d_bits_clear, ctx->d_bb_scratch, ctx->d_arena, ctx->d_comm_key, ctx->d_comm_idx, ctx->d_kmpc_warm, ctx->d_kmpc_qp_warm, ctx->d_kmpc_scratch, ctx->d_mix_scratch, ctx->d_split_scratch, ctx->d_rec_scratch, ctx->d_st_scratch, ctx->d_audit, ctx->d_audit_buf, ctx->d_cl_theta[0], ctx->d_cl_theta[1], ctx->d_step, ctx->d_comm_rec, ctx->d_order, ctx->d_kmpc_cfg};
+    void* ptrs[] = {ctx->d_wx, ctx->d_wy, ctx->d_wv, ctx->d_wpsi, ctx->d_wkappa, ctx->d_wbox, ctx->d_bits, ctx->d_bits0, ctx->d_bits_clear, ctx->d_bb_scratch, ctx->d_arena, ctx->d_comm_key, ctx->d_comm_idx, ctx->d_kmpc_warm, ctx->d_kmpc_qp_warm, ctx->d_stmpc_qp_warm, ctx->d_kmpc_scratch, ctx->d_mix_scratch, ctx->d_split_scratch, ctx->d_rec_scratch, ctx->d_st_scratch, ctx->d_audit, ctx->d_audit_buf, ctx->d_cl_theta[0], ctx->d_cl_theta[1], ctx->d_step, ctx->d_comm_rec, ctx->d_order, ctx->d_kmpc_cfg};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -1472,6 +1472,221 @@ int f1p_kmpc_qp_warm_set(f1p_ctx* ctx, const double* warm, int32_t E, int32_t T)
     F1P_HIP(ctx, hipMemcpyAsync(ctx->d_kmpc_qp_warm, warm, sizeof(double) * 2 * (size_t)E * T, hipMemcpyHostToDevice, ctx->stream));
     F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->kmpc_qp_warm_valid = true;
+    return F1P_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// the reference's linearised dynamic-MPC QP (k_stmpc_qp.hip) and STMPCPlanner.plan with it
+// ---------------------------------------------------------------------------------------------------
+static int validate_stmpc(f1p_ctx* ctx, const f1p_stmpc_cfg* cfg, int E);
+
+// the cfg checks of the shooting path, diagonal weights and bounds sane, 2 <= horizon <= F1P_STMPC_QP_MAX_T; opts
+static int validate_stmpc_qp(f1p_ctx* ctx, const f1p_stmpc_cfg* cfg, int E, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o) {
+    int rc = validate_stmpc(ctx, cfg, E); if (rc) return rc;
+    if (cfg->horizon > F1P_STMPC_QP_MAX_T) return set_error(ctx, F1P_EINVAL, "stmpc qp: horizon must be <= F1P_STMPC_QP_MAX_T (44)");
+    if (cfg->horizon < 2) return set_error(ctx, F1P_EINVAL, "stmpc qp: horizon must be >= 2");
+    for (int k = 0; k < 7; ++k)
+        if (!(cfg->q[k] >= 0) || !(cfg->qf[k] >= 0) || !isfinite(cfg->q[k]) || !isfinite(cfg->qf[k]))
+            return set_error(ctx, F1P_EINVAL, "stmpc qp: state weights must be finite and >= 0");
+    for (int k = 0; k < 2; ++k)
+        if (!(cfg->r[k] > 0) || !(cfg->rd[k] >= 0) || !isfinite(cfg->r[k]) || !isfinite(cfg->rd[k]))
+            return set_error(ctx, F1P_EINVAL, "stmpc qp: input weights must be finite, r > 0 (strict convexity), rd >= 0");
+    if (!(cfg->max_accel > 0) || !(cfg->max_steer > 0) || !(cfg->max_steer_v > 0) || !(cfg->max_speed >= cfg->min_speed))
+        return set_error(ctx, F1P_EINVAL, "stmpc qp: bounds must be > 0 and max_speed >= min_speed");
+    for (int k = 0; k < 8; ++k)
+        if (!isfinite(cfg->params[k])) return set_error(ctx, F1P_EINVAL, "stmpc qp: vehicle parameters must be finite");
+    f1p_kmpc_qp_opts_default(o);
+    if (opts) *o = *opts;
+    if (o->max_iter < 0 || o->max_iter > 1000 || !(o->tol > 0) || !isfinite(o->tol))
+        return set_error(ctx, F1P_EINVAL, "stmpc qp: max_iter must be in [0, 1000] and tol finite and > 0");
+    return F1P_OK;
+}
+
+int f1p_stmpc_qp_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_v_prev, int32_t E,
+                     const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, double* d_steer, double* d_speed, int32_t* d_status,
+                     double* d_u, double* d_x, double* d_obj, double* d_duals, int32_t* d_iters) {
+    F1P_ENTER(ctx);
+    f1p_kmpc_qp_opts o;
+    int rc = validate_stmpc_qp(ctx, cfg, E, opts, &o); if (rc) return rc;
+    if (E > 0 && (!d_x0 || !d_ref || !d_steer || !d_speed || !d_status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
+    return launch_stmpc_qp(ctx, d_x0, d_ref, d_oa_prev, d_od_v_prev, 1, E, cfg, o.max_iter, o.tol, d_steer, d_speed, d_status, d_u, d_x,
+                           d_obj, d_duals, d_iters, nullptr);
+}
+
+int f1p_stmpc_qp_batch(f1p_ctx* ctx, const double* x0, const double* ref, const double* oa_prev, const double* od_v_prev, int32_t E,
+                       const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, double* steer, double* speed, int32_t* status, double* u,
+                       double* x, double* obj, double* duals, int32_t* iters) {
+    F1P_ENTER(ctx);
+    f1p_kmpc_qp_opts o;
+    int rc = validate_stmpc_qp(ctx, cfg, E, opts, &o); if (rc) return rc;
+    if (E > 0 && (!x0 || !ref || !steer || !speed || !status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
+    if (E == 0) return F1P_OK;
+    const size_t T = cfg->horizon, e = E;
+    Stage s(ctx);
+    s.need(8 * 7 * e); s.need(8 * e * 7 * (T + 1)); s.need(8 * e * T, oa_prev); s.need(8 * e * T, od_v_prev);
+    s.need(8 * e); s.need(8 * e); s.need(4 * e); s.need(8 * e * T * 2, u); s.need(8 * e * 7 * (T + 1), x); s.need(8 * e, obj);
+    s.need(8 * e * (10 * T - 2), duals); s.need(4 * e, iters);
+    if ((rc = s.begin())) return rc;
+    const double *d_x0, *d_ref, *d_oa, *d_od;
+    if ((rc = s.in(x0, 7 * e, &d_x0))) return rc;
+    if ((rc = s.in(ref, e * 7 * (T + 1), &d_ref))) return rc;
+    if ((rc = s.in(oa_prev, e * T, &d_oa))) return rc;
+    if ((rc = s.in(od_v_prev, e * T, &d_od))) return rc;
+    double* d_steer = s.out(steer, e); double* d_speed = s.out(speed, e); int32_t* d_st = s.out(status, e);
+    double* d_u = s.out(u, e * T * 2); double* d_x = s.out(x, e * 7 * (T + 1)); double* d_obj = s.out(obj, e);
+    double* d_du = s.out(duals, e * (10 * T - 2)); int32_t* d_it = s.out(iters, e);
+    if ((rc = launch_stmpc_qp(ctx, d_x0, d_ref, d_oa, d_od, 1, E, cfg, o.max_iter, o.tol, d_steer, d_speed, d_st, d_u, d_x, d_obj, d_du, d_it,
+                              nullptr))) return rc;
+    return s.finish();
+}
+
+// the ctx's plan warm start for (E, W); a change of shape drops the old contents (every length back to 0 = None)
+static int ensure_stqp_warm(f1p_ctx* ctx, int E, int W) {
+    if (ctx->d_stmpc_qp_warm && ctx->stmpc_qp_warm_E == E && ctx->stmpc_qp_warm_W == W) return F1P_OK;
+    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->d_stmpc_qp_warm) (void)hipFree(ctx->d_stmpc_qp_warm);
+    ctx->d_stmpc_qp_warm = nullptr; ctx->stmpc_qp_warm_E = ctx->stmpc_qp_warm_W = 0;
+    ctx->stmpc_qp_len.assign((size_t)E, 0);
+    F1P_HIP(ctx, hipMalloc((void**)&ctx->d_stmpc_qp_warm, sizeof(double) * 2 * (size_t)E * W));
+    ctx->stmpc_qp_warm_E = E; ctx->stmpc_qp_warm_W = W;
+    return F1P_OK;
+}
+
+int f1p_stmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_stmpc_cfg* dcfg, const f1p_kmpc_cfg* kcfg, double v_ks,
+                            double dl, double dlk, const f1p_kmpc_qp_opts* opts, double* steer, double* speed, int32_t* status,
+                            int32_t* branch, double* u, double* obj) {
+    F1P_ENTER(ctx);
+    f1p_kmpc_qp_opts o, ok_;
+    int rc = validate_stmpc_qp(ctx, dcfg, E, opts, &o); if (rc) return rc;
+    if ((rc = validate_kmpc_qp(ctx, kcfg, E, opts, &ok_))) return rc;
+    if (kcfg->horizon > dcfg->horizon) return set_error(ctx, F1P_EINVAL, "stmpc qp plan: TK must be <= T");
+    if (E > 0 && (!x0 || !steer || !speed || !status)) return set_error(ctx, F1P_EINVAL, "x0, steer, speed and status are required");
+    if (!(dl > 0) || !(dlk > 0)) return set_error(ctx, F1P_EINVAL, "dl and dlk must be > 0");
+    if (ctx->n_wp < 2 || !ctx->has_psi) return set_error(ctx, F1P_ESTATE, "waypoints with a heading column are required");
+    if (E == 0) return F1P_OK;
+    const int T = dcfg->horizon, TK = kcfg->horizon, W = T;                   // W = max(T, TK)
+    if ((rc = ensure_stqp_warm(ctx, E, W))) return rc;
+    // the branch split (:168) and the reset rules (:1005, :1052), on the host
+    std::vector<int32_t> idx[2], use[2];
+    for (int e = 0; e < E; ++e) {
+        const bool dyn = !(x0[(size_t)e * 7 + 3] <= v_ks);
+        const int len = ctx->stmpc_qp_len[e];
+        idx[dyn].push_back(e);
+        use[dyn].push_back(dyn ? (len >= T) : (len > 0 && len <= TK));
+    }
+    const size_t nd = idx[1].size(), nk = idx[0].size();
+    const size_t need = al256(8 * 7 * nd) + al256(8 * 4 * nd) + al256(8 * 7 * (T + 1) * nd) + 2 * al256(8 * 2 * T * nd) + al256(8 * 4 * nk) +
+                        al256(8 * 7 * (TK + 1) * nk) + al256(8 * 4 * (TK + 1) * nk) + 2 * al256(8 * 2 * TK * nk) + 2 * (al256(4 * nd) + al256(4 * nk)) +
+                        3 * al256(8 * (size_t)E) + al256(4 * (size_t)E);
+    if ((rc = arena_reset(ctx, need))) return rc;
+    double* d_steer = (double*)arena_take(ctx, 8 * (size_t)E);
+    double* d_speed = (double*)arena_take(ctx, 8 * (size_t)E);
+    double* d_obj = (double*)arena_take(ctx, 8 * (size_t)E);
+    int32_t* d_st = (int32_t*)arena_take(ctx, 4 * (size_t)E);
+    std::vector<double> hx;
+    double* d_win[2] = {nullptr, nullptr};
+    double* d_wout[2] = {nullptr, nullptr};
+    for (int b = 0; b < 2; ++b) {                                             // b = 1: dynamic (:181-191), b = 0: kinematic (:168-180)
+        const int nb = (int)idx[b].size(), Tb = b ? T : TK;
+        if (nb == 0) continue;
+        int32_t* d_idx = (int32_t*)arena_take(ctx, 4 * (size_t)nb);
+        int32_t* d_use = (int32_t*)arena_take(ctx, 4 * (size_t)nb);
+        double* d_s4 = (double*)arena_take(ctx, 8 * 4 * (size_t)nb);
+        double* d_ref7 = (double*)arena_take(ctx, 8 * 7 * (size_t)(Tb + 1) * nb);
+        d_win[b] = (double*)arena_take(ctx, 8 * 2 * (size_t)Tb * nb);
+        d_wout[b] = (double*)arena_take(ctx, 8 * 2 * (size_t)Tb * nb);
+        hx.assign((size_t)nb * 4, 0.0);
+        for (int k = 0; k < nb; ++k) {
+            const double* s = x0 + (size_t)idx[b][k] * 7;
+            hx[4 * k] = s[0]; hx[4 * k + 1] = s[1]; hx[4 * k + 2] = s[3]; hx[4 * k + 3] = s[4];     // (x, y, v, yaw)
+        }
+        F1P_HIP(ctx, hipMemcpyAsync(d_idx, idx[b].data(), 4 * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
+        F1P_HIP(ctx, hipMemcpyAsync(d_use, use[b].data(), 4 * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
+        F1P_HIP(ctx, hipMemcpyAsync(d_s4, hx.data(), 8 * 4 * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
+        F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));                     // hx is reused by the next branch
+        if ((rc = launch_stmpc_qp_warm_in(ctx, ctx->d_stmpc_qp_warm, d_idx, d_use, nb, Tb, W, d_win[b]))) return rc;
+        double *o_steer = d_steer, *o_speed = d_speed, *o_obj = d_obj; int32_t* o_st = d_st;
+        // this branch's egos are written contiguously from offset 0 of its own slice: kinematic egos after the dynamic ones
+        const size_t off = b ? 0 : nd;
+        o_steer += off; o_speed += off; o_obj += off; o_st += off;
+        if (b) {
+            double* d_x7 = (double*)arena_take(ctx, 8 * 7 * (size_t)nb);
+            std::vector<double> h7((size_t)nb * 7);
+            for (int k = 0; k < nb; ++k) memcpy(&h7[7 * (size_t)k], x0 + (size_t)idx[b][k] * 7, 7 * sizeof(double));
+            F1P_HIP(ctx, hipMemcpyAsync(d_x7, h7.data(), 8 * 7 * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
+            if ((rc = launch_stmpc_ref(ctx, d_s4, nb, T, dcfg->dt, dl, d_ref7))) return rc;                     // :195-233
+            if ((rc = launch_stmpc_qp(ctx, d_x7, d_ref7, d_win[b], d_win[b] + 1, 2, nb, dcfg, o.max_iter, o.tol, o_steer, o_speed, o_st,
+                                      nullptr, nullptr, o_obj, nullptr, nullptr, d_wout[b]))) return rc;
+            F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));                 // h7 leaves scope
+        } else {
+            double* d_ref4 = (double*)arena_take(ctx, 8 * 4 * (size_t)(Tb + 1) * nb);
+            if ((rc = launch_stmpc_ref(ctx, d_s4, nb, TK, kcfg->dt, dlk, d_ref7))) return rc;                  // :237-276
+            if ((rc = launch_stmpc_qp_kref(ctx, d_ref7, nb, TK, d_ref4))) return rc;
+            if ((rc = launch_kmpc_qp(ctx, d_s4, d_ref4, d_win[b], d_win[b] + 1, 2, nb, kcfg, ok_.max_iter, ok_.tol, o_steer, o_speed, o_st,
+                                     nullptr, nullptr, o_obj, nullptr, nullptr, d_wout[b]))) return rc;
+        }
+        if ((rc = launch_stmpc_qp_warm_out(ctx, d_wout[b], d_idx, nb, Tb, W, ctx->d_stmpc_qp_warm))) return rc;
+    }
+    // results: [dynamic egos | kinematic egos] -> the caller's order
+    std::vector<double> hs(E), hv(E), ho(E), hw[2];
+    std::vector<int32_t> hst(E);
+    F1P_HIP(ctx, hipMemcpyAsync(hs.data(), d_steer, 8 * (size_t)E, hipMemcpyDeviceToHost, ctx->stream));
+    F1P_HIP(ctx, hipMemcpyAsync(hv.data(), d_speed, 8 * (size_t)E, hipMemcpyDeviceToHost, ctx->stream));
+    F1P_HIP(ctx, hipMemcpyAsync(ho.data(), d_obj, 8 * (size_t)E, hipMemcpyDeviceToHost, ctx->stream));
+    F1P_HIP(ctx, hipMemcpyAsync(hst.data(), d_st, 4 * (size_t)E, hipMemcpyDeviceToHost, ctx->stream));
+    for (int b = 0; b < 2; ++b) {
+        if (!u || idx[b].empty()) continue;
+        const size_t Tb = b ? T : TK;
+        hw[b].resize(idx[b].size() * 2 * Tb);
+        F1P_HIP(ctx, hipMemcpyAsync(hw[b].data(), d_wout[b], 8 * hw[b].size(), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const double NaN = nan("");
+    for (int b = 0; b < 2; ++b) {
+        const size_t off = b ? 0 : nd, Tb = b ? T : TK;
+        for (size_t k = 0; k < idx[b].size(); ++k) {
+            const int e = idx[b][k];
+            const int st = hst[off + k];
+            steer[e] = hs[off + k]; speed[e] = hv[off + k]; status[e] = st;
+            if (branch) branch[e] = b;
+            if (obj) obj[e] = ho[off + k];
+            const bool ok = st == 0 || st == 2;
+            ctx->stmpc_qp_len[e] = ok ? (int32_t)Tb : 0;                      // statuses 1, 3: the reference's None
+            if (u) {
+                double* ue = u + (size_t)e * W * 2;
+                for (size_t j = 0; j < (size_t)W * 2; ++j) ue[j] = ok && j < 2 * Tb ? hw[b][k * 2 * Tb + j] : NaN;
+            }
+        }
+    }
+    return F1P_OK;
+}
+
+int f1p_stmpc_qp_warm_reset(f1p_ctx* ctx) {
+    if (!ctx) return F1P_EINVAL;
+    std::fill(ctx->stmpc_qp_len.begin(), ctx->stmpc_qp_len.end(), 0);
+    return F1P_OK;
+}
+
+int f1p_stmpc_qp_warm_get(f1p_ctx* ctx, double* warm, int32_t* len, int32_t E, int32_t W) {
+    F1P_ENTER(ctx);
+    if (!warm || !len) return set_error(ctx, F1P_EINVAL, "warm / len is NULL");
+    if (!ctx->d_stmpc_qp_warm || ctx->stmpc_qp_warm_E != E || ctx->stmpc_qp_warm_W != W)
+        return set_error(ctx, F1P_ESTATE, "no stmpc qp warm start of this shape is held");
+    F1P_HIP(ctx, hipMemcpyAsync(warm, ctx->d_stmpc_qp_warm, sizeof(double) * 2 * (size_t)E * W, hipMemcpyDeviceToHost, ctx->stream));
+    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(len, ctx->stmpc_qp_len.data(), sizeof(int32_t) * (size_t)E);
+    return F1P_OK;
+}
+
+int f1p_stmpc_qp_warm_set(f1p_ctx* ctx, const double* warm, const int32_t* len, int32_t E, int32_t W) {
+    F1P_ENTER(ctx);
+    if (!warm || !len || E < 1 || W < 1) return set_error(ctx, F1P_EINVAL, "bad warm / len / E / W");
+    for (int e = 0; e < E; ++e)
+        if (len[e] < 0 || len[e] > W) return set_error(ctx, F1P_EINVAL, "len must be in [0, W]");
+    int rc = ensure_stqp_warm(ctx, E, W); if (rc) return rc;
+    F1P_HIP(ctx, hipMemcpyAsync(ctx->d_stmpc_qp_warm, warm, sizeof(double) * 2 * (size_t)E * W, hipMemcpyHostToDevice, ctx->stream));
+    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(ctx->stmpc_qp_len.data(), len, sizeof(int32_t) * (size_t)E);
     return F1P_OK;
 }
 

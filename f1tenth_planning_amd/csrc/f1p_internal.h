@@ -77,6 +77,11 @@ struct f1p_ctx {
     int kmpc_qp_warm_E = 0, kmpc_qp_warm_T = 0;
     bool kmpc_qp_warm_valid = false;
     int kmpc_qp_pack = 0;              // egos per wave at T <= 8: 0 = default, 1 or 4 forces it (timing runs)
+    // the dynamic-MPC QP plan (f1p_stmpc_qp_plan_batch): fp64 warm start [E][W][2] = (oa, odelta_v), W = max(T, TK), keyed by (E, W);
+    // per ego the length of the reference's self.oa (0: None) -- the branch's horizon -- on the host (the branch split is made there)
+    double* d_stmpc_qp_warm = nullptr;
+    int stmpc_qp_warm_E = 0, stmpc_qp_warm_W = 0;
+    std::vector<int32_t> stmpc_qp_len;
 
     // two-kernel branch and bound of the lattice planner: bounds and clothoids handed from the fit kernel to the evaluation kernel
     char* d_bb_scratch = nullptr;
@@ -207,6 +212,14 @@ int launch_kmpc_qp(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const 
                    const f1p_kmpc_cfg* cfg, int max_iter, double tol, double* d_steer, double* d_speed, int32_t* d_status, double* d_u,
                    double* d_xk, double* d_obj, double* d_duals, int32_t* d_iters, double* d_warm_out);
 int kmpc_qp_pack(const f1p_ctx* ctx, int T);
+// k_stmpc_qp.hip: prev (oa, od_v) read at pa[(e T + t) pstride], pd[...] (nullable: zeros); warm_out [E][T][2] = (oa, od_v)
+int launch_stmpc_qp(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
+                    const f1p_stmpc_cfg* cfg, int max_iter, double tol, double* d_steer, double* d_speed, int32_t* d_status, double* d_u,
+                    double* d_x, double* d_obj, double* d_duals, int32_t* d_iters, double* d_warm_out);
+size_t stmpc_qp_lds_bytes(int T);
+int launch_stmpc_qp_warm_in(f1p_ctx* ctx, const double* d_warm, const int32_t* d_idx, const int32_t* d_use, int nb, int Tb, int W, double* d_out);
+int launch_stmpc_qp_warm_out(f1p_ctx* ctx, const double* d_in, const int32_t* d_idx, int nb, int Tb, int W, double* d_warm);
+int launch_stmpc_qp_kref(f1p_ctx* ctx, const double* d_ref7, int nb, int T, double* d_ref4);
 int launch_kmpc_predict(f1p_ctx* ctx, const double* d_x0, const double* d_oa, const double* d_od, int E,
                         const f1p_kmpc_cfg* cfg, double* d_path);
 int launch_kmpc_ref(f1p_ctx* ctx, const double* d_states, int E, int horizon, double dt, double dl, double* d_ref);

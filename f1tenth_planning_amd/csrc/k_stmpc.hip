@@ -8,66 +8,6 @@
 
 namespace f1p {
 
-struct DynState { double x, y, delta, v, yaw, yr, beta; };
-struct DynConst { double K, gl_r, gl_f, h, F, R, M, N, lf2cf, lr2cr, l_r, l_f; };
-
-__device__ __forceinline__ DynConst dyn_const(const f1p_stmpc_cfg& c) {
-    const double* p = c.params;
-    const double mass = p[0], l_f = p[1], l_r = p[2], h_cog = p[3], c_f = p[4], c_r = p[5], iz = p[6], mu = p[7];
-    const double g = 9.81;
-    DynConst k;
-    k.K = (mu * mass) / ((l_f + l_r) * iz);     // :342
-    k.gl_r = g * l_r; k.gl_f = g * l_f; k.h = h_cog;
-    k.F = l_f * c_f; k.R = l_r * c_r;           // :345-346
-    k.M = (mu * c_f) / (l_f + l_r);             // :347
-    k.N = (mu * c_r) / (l_f + l_r);             // :348
-    k.lf2cf = l_f * l_f * c_f; k.lr2cr = l_r * l_r * c_r;
-    k.l_r = l_r; k.l_f = l_f;
-    return k;
-}
-
-// update_state :317-404, operation order kept.
-// FAST: the range-reduced sincos core for cos/sin(yaw + beta) and tan(delta) = sin / cos (valid while the arguments stay below
-// 1e5 in magnitude, which the shooting kernel checks once per ego; delta is clamped to +-max_steer); otherwise the device
-// library's full-range functions.  Same split as kmpc_step.
-template <bool FAST>
-__device__ __forceinline__ void dyn_step(DynState& s, double a, double delta_v, const f1p_stmpc_cfg& c, const DynConst& k) {
-    if (delta_v >= c.max_steer_v) delta_v = c.max_steer_v;             // :330-333
-    else if (delta_v <= -c.max_steer_v) delta_v = -c.max_steer_v;
-    if (a >= c.max_accel) a = c.max_accel;                             // :336-339
-    else if (a <= -c.max_accel) a = -c.max_accel;
-    const double T = k.gl_r - (a * k.h);                               // :343
-    const double V = k.gl_f + (a * k.h);                               // :344
-    const double A1 = k.K * k.F * T;                                   // :350-355
-    const double A2 = k.K * (k.R * V - k.F * T);
-    const double A3 = k.K * (k.lf2cf * T + k.lr2cr * V);
-    const double A4 = k.M * T;
-    const double A5 = k.N * V + k.M * T;
-    const double A6 = k.N * V * k.l_r - k.M * T * k.l_f;
-    double sn, cs, tn;
-    if (FAST) {
-        double sd, cd;
-        sincos_fast(s.yaw + s.beta, &sn, &cs);      // guarded: beta can run away when a rollout brakes to v ~ 0
-        sincos_core(s.delta, &sd, &cd);
-        tn = sd / cd;
-    } else {
-        sincos(s.yaw + s.beta, &sn, &cs);
-        tn = tan(s.delta);
-    }
-    const double x_new = s.x + s.v * cs * c.dt;                        // :358
-    const double y_new = s.y + s.v * sn * c.dt;                        // :359
-    double delta_new = s.delta + delta_v * c.dt;                       // :360
-    double v_new = s.v + a * c.dt;                                     // :361
-    const double yaw_new = s.yaw + s.v / c.wheelbase * tn * c.dt;             // :362-365
-    const double yr_new = s.yr + (A1 * s.delta + A2 * s.beta - A3 * (s.yr / s.v)) * c.dt;                             // :367-371
-    const double beta_new = s.beta + (A4 * (s.delta / s.v) - A5 * (s.beta / s.v) + A6 * (s.yr / (s.v * s.v)) - s.yr) * c.dt;   // :372-381
-    if (v_new > c.max_speed) v_new = c.max_speed;                      // :393-396
-    else if (v_new < c.min_speed) v_new = c.min_speed;
-    if (delta_new >= c.max_steer) delta_new = c.max_steer;             // :399-402
-    else if (delta_new <= -c.max_steer) delta_new = -c.max_steer;
-    s.x = x_new; s.y = y_new; s.delta = delta_new; s.v = v_new; s.yaw = yaw_new; s.yr = yr_new; s.beta = beta_new;
-}
-
 __device__ __forceinline__ double clampd2(double v, double lo, double hi) { return v > hi ? hi : (v < lo ? lo : v); }
 
 // predict_motion :280-300, one thread per ego

@@ -648,6 +648,63 @@ class Context:
         """egos per wave of the QP kernel at T <= 8 (0: default, 1 or 4)"""
         self._check(self.lib.f1p_kmpc_qp_set_pack(self.h, int(egos_per_wave)))
 
+    # ---- dynamic MPC, the reference's linearised QP (f1p_stmpc_qp_*) -------------------------------------------------------------------
+    def stmpc_qp(self, x0, ref, cfg: _abi.StmpcCfg, oa_prev=None, od_v_prev=None, opts=None, want_u=True, want_x=False, want_obj=True,
+                 want_duals=False, want_iters=True):
+        """linear_mpc_control (dynamic_mpc.py:995-1040) solved exactly for E egos: x0 [E, 7], ref [E, 7, T+1], the previous solution
+        oa_prev / od_v_prev [E, T] (None: zeros) -> dict(steer, speed, status[, u [E, T, 2] (steering speed, accel), x [E, 7, T+1], obj,
+        duals [E, 10T-2], iters]).  status: 0 solved, 1 infeasible, 2 not converged, 3 non-finite input or model data (1, 3: NaN outputs)."""
+        x0 = _f64(x0, (-1, 7)); E = x0.shape[0]; T = cfg.horizon
+        ref = _f64(ref, (E, 7, T + 1))
+        oa = None if oa_prev is None else _f64(oa_prev, (E, T))
+        od = None if od_v_prev is None else _f64(od_v_prev, (E, T))
+        out = dict(steer=np.empty(E), speed=np.empty(E), status=np.empty(E, np.int32))
+        for k, want, shape, dt in (("u", want_u, (E, T, 2), np.float64), ("x", want_x, (E, 7, T + 1), np.float64), ("obj", want_obj, (E,), np.float64),
+                                   ("duals", want_duals, (E, 10 * T - 2), np.float64), ("iters", want_iters, (E,), np.int32)):
+            if want:
+                out[k] = np.empty(shape, dt)
+        self._check(self.lib.f1p_stmpc_qp_batch(self.h, _ptr(x0), _ptr(ref), _ptr(oa), _ptr(od), E, C.byref(cfg),
+                                                None if opts is None else C.byref(opts), _ptr(out["steer"]), _ptr(out["speed"]),
+                                                _ptr(out["status"]), _ptr(out.get("u")), _ptr(out.get("x")), _ptr(out.get("obj")),
+                                                _ptr(out.get("duals")), _ptr(out.get("iters"))))
+        return out
+
+    def stmpc_qp_dev(self, d_x0, d_ref, E, cfg: _abi.StmpcCfg, d_steer, d_speed, d_status, d_oa_prev=None, d_od_v_prev=None, opts=None, d_u=None,
+                     d_x=None, d_obj=None, d_duals=None, d_iters=None):
+        p = lambda b: None if b is None else b.ptr   # noqa: E731
+        self._check(self.lib.f1p_stmpc_qp_dev(self.h, p(d_x0), p(d_ref), p(d_oa_prev), p(d_od_v_prev), int(E), C.byref(cfg),
+                                              None if opts is None else C.byref(opts), p(d_steer), p(d_speed), p(d_status), p(d_u), p(d_x),
+                                              p(d_obj), p(d_duals), p(d_iters)))
+
+    def stmpc_qp_plan(self, x0, dcfg: _abi.StmpcCfg, kcfg: KmpcCfg, v_ks=2.0, dl=0.03, dlk=0.03, opts=None, want_u=True, want_obj=True):
+        """STMPCPlanner.plan with the QP solver for E egos in ONE call: x0 [E, 7]; per ego the kinematic branch at v <= v_ks, the dynamic
+        one above; reference extraction, linearisation about the ctx's warm start (the reference's self.oa / self.odelta_v with its length
+        rules), solve, output map -> dict(steer, speed, status, branch (1 dynamic, 0 kinematic)[, u [E, max(T, TK), 2] = the new
+        (oa, odelta_v), NaN past the branch's horizon][, obj])"""
+        x0 = _f64(x0, (-1, 7)); E = x0.shape[0]; W = max(dcfg.horizon, kcfg.horizon)
+        out = dict(steer=np.empty(E), speed=np.empty(E), status=np.empty(E, np.int32), branch=np.empty(E, np.int32))
+        if want_u:
+            out["u"] = np.empty((E, W, 2))
+        if want_obj:
+            out["obj"] = np.empty(E)
+        self._check(self.lib.f1p_stmpc_qp_plan_batch(self.h, _ptr(x0), E, C.byref(dcfg), C.byref(kcfg), float(v_ks), float(dl), float(dlk),
+                                                     None if opts is None else C.byref(opts), _ptr(out["steer"]), _ptr(out["speed"]),
+                                                     _ptr(out["status"]), _ptr(out["branch"]), _ptr(out.get("u")), _ptr(out.get("obj"))))
+        return out
+
+    def stmpc_qp_warm_reset(self):
+        self._check(self.lib.f1p_stmpc_qp_warm_reset(self.h))
+
+    def stmpc_qp_warm_get(self, E, W):
+        """-> (warm [E, W, 2] = (oa, odelta_v), len [E]: the length of each ego's oa, 0 = None)"""
+        w = np.empty((int(E), int(W), 2)); n = np.empty(int(E), np.int32)
+        self._check(self.lib.f1p_stmpc_qp_warm_get(self.h, _ptr(w), _ptr(n), int(E), int(W)))
+        return w, n
+
+    def stmpc_qp_warm_set(self, warm, lengths):
+        w = _f64(warm); n = np.ascontiguousarray(lengths, dtype=np.int32)
+        self._check(self.lib.f1p_stmpc_qp_warm_set(self.h, _ptr(w), _ptr(n), w.shape[0], w.shape[1]))
+
     def kmpc_sample_controls_dev(self, d_controls, E, cfg: KmpcCfg, seed, sigma_accel=1.5, sigma_steer=0.15):
         self._check(self.lib.f1p_kmpc_sample_controls_dev(self.h, d_controls.ptr, int(E), C.byref(cfg),
                                                           C.c_uint64(int(seed)), float(sigma_accel), float(sigma_steer)))

@@ -552,6 +552,57 @@ int f1p_kmpc_qp_warm_set(f1p_ctx* ctx, const double* warm, int32_t E, int32_t T)
 int f1p_kmpc_qp_set_pack(f1p_ctx* ctx, int32_t egos_per_wave);
 
 /* ------------------------------------------------------------------------------------------------
+ * Dynamic single-track MPC as the reference solves it: the linearised QP of control/dynamic_mpc/dynamic_mpc.py, batched, fp64
+ * (csrc/k_stmpc_qp.hip).  Per ego:
+ *   linearisation point (linear_mpc_control :995-1040): rows delta, v, yaw, yawrate, beta of predict_motion(x0, oa_prev, od_v_prev)
+ *     (:279-300, update_state :317-404 with its clamps) -- the previous solution NOT shifted; zeros when NULL;
+ *   model (get_dynamic_model_matrix :428-535) at (delta_t, v_t, yaw_t, yawrate_t, beta_t, oa_prev[t]): the dense 7x7 Jacobian;
+ *   problem (mpc_prob_init :575-710):  min  sum_t u_t' R u_t + sum_{t<=T} (x_t - ref_t)' Q (x_t - ref_t) (Qf at T)
+ *     + sum_{t<T-1} (u_{t+1} - u_t)' Rd (u_{t+1} - u_t)  s.t.  x_{t+1} = A_t x_t + B_t u_t + C_t, x_0 = x0,
+ *     |u0_{t+1} - u0_t| <= MAX_STEER_V (:685, no DT factor), |delta_t| <= MAX_STEER and MIN_SPEED <= v_t <= MAX_SPEED (t = 0..T),
+ *     |u0_t| <= MAX_STEER_V, |u1_t| <= MAX_ACCEL;  u = (steering speed, accel); diagonal weights only (cfg q, qf, r, rd), r > 0;
+ *   output map (:1112-1117): steer = delta0 + u0_0 DT, speed = v0 + u1_0 DT.
+ * Feasible iff |delta0| <= MAX_STEER and MIN_SPEED <= v0 <= MAX_SPEED (then u = 0 is feasible).  Solver, stopping rule and opts are
+ * those of f1p_kmpc_qp_* (the reference's OSQP runs at eps 1e-1, :878-885; this solves its problem exactly).
+ * 2 <= horizon <= F1P_STMPC_QP_MAX_T (else F1P_EINVAL).  cfg->n_rollouts is not used.
+ *   x0 [E][7]; ref [E][7][T+1] (f1p_stmpc_ref_batch); oa_prev, od_v_prev [E][T] (nullable: zeros)
+ * Outputs: steer, speed [E]; status [E]: 0 solved, 1 infeasible, 2 not converged (the last iterate), 3 non-finite input or model data
+ *   (a predicted speed of 0 divides by v in update_state and the Jacobian); statuses 1 and 3 give NaN in every output.
+ *   Nullable: u [E][T][2] (steering speed, accel), x [E][7][T+1] (the states of the linear model), obj [E] (the value cvxpy reports,
+ *   the constant t = 0 term included), iters [E], and duals [E][10T-2]: the multipliers of
+ *   u0_{t+1} - u0_t <= MAX_STEER_V (T-1), its negation (T-1), delta_t <= MAX_STEER for t = 1..T (T), -delta_t <= MAX_STEER (T),
+ *   v_t <= MAX_SPEED (T), -v_t <= -MIN_SPEED (T), u0_t <= MAX_STEER_V (T), -u0_t (T), u1_t <= MAX_ACCEL (T), -u1_t (T)
+ *   -- the reference's row order (:685-706) without the constant t = 0 rows.
+ * ---------------------------------------------------------------------------------------------- */
+#define F1P_STMPC_QP_MAX_T 44
+int f1p_stmpc_qp_batch(f1p_ctx* ctx, const double* x0, const double* ref, const double* oa_prev, const double* od_v_prev, int32_t E,
+                       const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, double* steer, double* speed, int32_t* status, double* u,
+                       double* x, double* obj, double* duals, int32_t* iters);
+/* the same on device buffers; asynchronous on the ctx stream */
+int f1p_stmpc_qp_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_v_prev, int32_t E,
+                     const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, double* d_steer, double* d_speed, int32_t* d_status,
+                     double* d_u, double* d_x, double* d_obj, double* d_duals, int32_t* d_iters);
+/* What STMPCPlanner.plan does per call with the QP solver (:133-191) for E egos in one call.  Each ego takes the kinematic branch when
+ * v0 <= v_ks (:168), the dynamic one otherwise:
+ *   dynamic (MPC_Control :1067-1117): reference (calc_ref_trajectory :195-233, dl) from the ctx waypoints, f1p_stmpc_qp_* on dcfg;
+ *   kinematic (MPC_Control_kinematic :1176-1207): reference (calc_ref_trajectory_kinematic :237-276 with kcfg's horizon and dt, dlk;
+ *     rows x, y, v, yaw), the kinematic QP of f1p_kmpc_qp_* on kcfg (STMPC's TK, DTK, Rk, Rdk, Qk, Qfk; its problem :712-833 is the
+ *     kinematic planner's); output steer = delta_0 of the solution, speed = v0 + a_0 DTK.
+ * The warm start is the reference's self.oa / self.odelta_v, one pair per ego shared by both branches and never shifted, kept on the
+ * device with its length (0 = None): the dynamic branch restarts from zeros when the length is < T (:1005), the kinematic one when it
+ * is > TK (:1052); statuses 1 and 3 reset it (the reference's None).  Requires kcfg->horizon <= dcfg->horizon (with TK > T the
+ * reference's kinematic branch would linearise about a prediction cut short at the dynamic solution's length; not supported: F1P_EINVAL).
+ *   x0 [E][7] host.  Outputs: steer, speed, status [E]; nullable: branch [E] (1 dynamic, 0 kinematic), obj [E], and
+ *   u [E][W][2], W = max(T, TK): the new (self.oa, self.odelta_v) -- the branch's horizon of steps, NaN beyond it and for statuses 1, 3. */
+int f1p_stmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_stmpc_cfg* dcfg, const f1p_kmpc_cfg* kcfg, double v_ks,
+                            double dl, double dlk, const f1p_kmpc_qp_opts* opts, double* steer, double* speed, int32_t* status,
+                            int32_t* branch, double* u, double* obj);
+/* the plan's warm start: forget it / read it back / install one (warm [E][W][2] fp64 = (oa, odelta_v), len [E] = its length, 0 = None) */
+int f1p_stmpc_qp_warm_reset(f1p_ctx* ctx);
+int f1p_stmpc_qp_warm_get(f1p_ctx* ctx, double* warm, int32_t* len, int32_t E, int32_t W);
+int f1p_stmpc_qp_warm_set(f1p_ctx* ctx, const double* warm, const int32_t* len, int32_t E, int32_t W);
+
+/* ------------------------------------------------------------------------------------------------
  * SURVEY.md 8f rank 2 -- the dynamic single-track model as a second model for shooting MPC
  * (control/dynamic_mpc/dynamic_mpc.py): predict_motion / update_state (:280-404), calc_ref_trajectory (:195-233),
  * objective :616-622, bounds :685-706, output map :1112-1117.
