@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(HERE, "csrc", "libf1p.so")
 
 F1P_OK = 0
 F1P_EINVAL, F1P_ENODEV, F1P_EHIP, F1P_ESTATE, F1P_ENOMEM, F1P_ECOMM = -1, -2, -3, -4, -5, -6
-ST_INTERSECT, ST_REACQUIRE, ST_NO_LOOKAHEAD, ST_ALL_BLOCKED = 0, 1, 2, 3
+ST_INTERSECT, ST_REACQUIRE, ST_NO_LOOKAHEAD, ST_ALL_BLOCKED, ST_BAD_TRACK = 0, 1, 2, 3, 4
 MAX_LOOKAHEADS = 64
 MAX_WIDTHS = 64
 COMM_ID_BYTES = 128
@@ -193,6 +193,14 @@ PROTOTYPES = {
     "f1p_pure_pursuit_set_form": (C.c_int, [_P, _I]),
     "f1p_stanley_batch": (C.c_int, [_P, _P, _I, _D, _D, _P, _P, _P]),
     "f1p_lqr_batch": (C.c_int, [_P, _P, _P, _I, _D, _D, _P, _D, _I, _D, _P, _P, _P]),
+    "f1p_set_track_set": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
+    "f1p_nearest_point_tracks_batch": (C.c_int, [_P, _P, _P, _I, _P, _P, _P, _P]),
+    "f1p_pure_pursuit_tracks_batch": (C.c_int, [_P, _P, _P, _I, _D, _D, _D, _P, _P, _P, _P, _P]),
+    "f1p_pure_pursuit_tracks_dev": (C.c_int, [_P, _P, _P, _I, _D, _D, _D, _P, _P, _P, _P, _P]),
+    "f1p_stanley_tracks_batch": (C.c_int, [_P, _P, _P, _I, _D, _D, _P, _P, _P]),
+    "f1p_lqr_tracks_batch": (C.c_int, [_P, _P, _P, _P, _I, _D, _D, _P, _D, _I, _D, _P, _P, _P]),
+    "f1p_kmpc_ref_tracks_batch": (C.c_int, [_P, _P, _P, _I, _I, _D, _D, _P]),
+    "f1p_kmpc_ref_tracks_dev": (C.c_int, [_P, _P, _P, _I, _I, _D, _D, _P]),
     "f1p_lattice_plan_batch": (C.c_int, [_P, _P, _P, _P, _I, C.POINTER(LatticeCfg)] + [_P] * 9),
     "f1p_lattice_plan_dev": (C.c_int, [_P, _P, _P, _P, _I, C.POINTER(LatticeCfg)] + [_P] * 9),
     "f1p_lattice_plan_batch_f32": (C.c_int, [_P, _P, _P, _P, _I, C.POINTER(LatticeCfg)] + [_P] * 7),

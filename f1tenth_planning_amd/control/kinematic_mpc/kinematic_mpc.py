@@ -122,6 +122,7 @@ class KMPCPlanner:
         self._device = device
         self._ctx = None
         self._calls = 0
+        self._trk_qp_warm = None           # the QP warm start of the track-set path (plan_batch(tracks=...)): u [E, T, 2] fp64
         _check_solver(config)
 
     def _context(self):
@@ -197,18 +198,24 @@ class KMPCPlanner:
         """forget the warm starts (shooting and QP) and restart the sampler's call counter (a new episode)"""
         self._calls = 0
         self.oa = self.odelta_v = None
+        self._trk_qp_warm = None
         if self._ctx is not None:
             self._ctx.kmpc_warm_reset()
             self._ctx.kmpc_qp_warm_reset()
 
-    def plan_batch(self, x0, waypoints=None, controls=None, want_seq=True):
+    def plan_batch(self, x0, waypoints=None, controls=None, want_seq=True, tracks=None, track_ids=None):
         """x0 [E, 4] = (x, y, v, yaw) -> dict(steer, speed, best_idx, best_cost[, best_seq]).  `controls`
         (f32 [E, T, 2, R]) overrides the in-kernel sampler with a caller-supplied candidate set (streamed from HBM).
         SOLVER == "qp": dict(steer, speed, status, obj[, u [E, T, 2]]) -- per-ego status (0 solved, 1 infeasible, 2 not converged,
-        3 non-finite input), never raised."""
+        3 non-finite input), never raised.
+        tracks: K courses in the `waypoints` format ([x, y, yaw, v]: four 1-D arrays or an array [4, N]) with track_ids [E]: ego e
+        follows tracks[track_ids[e]]; `waypoints` is then not used.  The references come from one k_kmpc_ref_tracks launch (an id
+        outside [0, K) gives NaN rows, hence NaN outputs and QP status 3 for that ego) and go to the same solvers."""
         _check_solver(self.config)
         if self.config.SOLVER == "qp" and controls is not None:
             raise ValueError("controls are candidates of the shooting solver; SOLVER='qp' takes none")
+        if tracks is not None:
+            return self._plan_tracks(x0, tracks, track_ids, controls, want_seq)
         ctx = self._bind(waypoints)
         x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, 4)
         if self.config.SOLVER == "qp":
@@ -219,6 +226,71 @@ class KMPCPlanner:
         cfg = _cfg_struct(c, n_rollouts=controls.shape[3])
         ref = ctx.kmpc_ref(x0, c.TK, c.DTK, c.dlk)
         return ctx.kmpc_shoot(x0, ref, controls, cfg)
+
+    def _plan_tracks(self, x0, tracks, track_ids, controls, want_seq):
+        if track_ids is None:
+            raise ValueError("tracks needs track_ids: one track index per ego")
+        if len(tracks) == 0:
+            raise ValueError("tracks must hold at least one course")
+        cols = []
+        for path in tracks:
+            if len(path) < 4:
+                raise ValueError("every track must hold [x, y, yaw, v]")
+            cx, cy, cyaw, sp = (np.asarray(path[k], dtype=np.float64) for k in range(4))             # :479-482
+            cols.append(np.column_stack([cx, cy, sp, cyaw]))
+        ctx = self._context()
+        ctx.kmpc_set_yaw_fixup(True)                           # a batch: per-ego fold of the gathered headings, the courses stay as given
+        ctx.set_tracks_cached(cols, cols=(0, 1, 2, 3))
+        c = self.config
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, 4)
+        E, T = x0.shape[0], c.TK
+        ids = Context._ids(track_ids, E)
+        if controls is not None:
+            cfg = _cfg_struct(c, n_rollouts=controls.shape[3])
+            return ctx.kmpc_shoot(x0, ctx.kmpc_ref_tracks(x0, ids, T, c.DTK, c.dlk), controls, cfg)
+        d = self._track_buffers(ctx, E, T)
+        d["x0"].upload(x0)
+        d["ids"].upload(ids)
+        ctx.kmpc_ref_tracks_dev(d["x0"], d["ids"], E, T, d["ref"], c.DTK, c.dlk)            # calc_ref_trajectory_kinematic :162-206
+        if c.SOLVER == "qp":
+            # the warm start of the single-track path (f1p_kmpc_qp_plan_batch): the previous call's solution, unshifted, per (E, T); a failed
+            # solve (status 1 / 3) leaves zeros, the reference's None
+            warm = self._trk_qp_warm if self._trk_qp_warm is not None and self._trk_qp_warm.shape == (E, T, 2) else None
+            if warm is not None:
+                d["oa"].upload(np.ascontiguousarray(warm[:, :, 0]))
+                d["od"].upload(np.ascontiguousarray(warm[:, :, 1]))
+            ctx.kmpc_qp_dev(d["x0"], d["ref"], E, _cfg_struct(c), d["steer"], d["speed"], d["status"],
+                            d["oa"] if warm is not None else None, d["od"] if warm is not None else None, opts=_qp_opts(c), d_u=d["u"],
+                            d_obj=d["obj"])
+            out = dict(steer=d["steer"].download(np.float64, E), speed=d["speed"].download(np.float64, E),
+                       status=d["status"].download(np.int32, E), obj=d["obj"].download(np.float64, E))
+            u = d["u"].download(np.float64, (E, T, 2))
+            nw = u.copy()
+            nw[(out["status"] == 1) | (out["status"] == 3)] = 0.0
+            self._trk_qp_warm = nw
+            if want_seq:
+                out["u"] = u
+            return out
+        ctx.kmpc_plan_dev(d["x0"], d["ref"], E, _cfg_struct(c), self._sampler(), d["steer"], d["speed"], d["best_idx"], d["best_cost"],
+                          d["best_seq"] if want_seq else None)
+        out = dict(steer=d["steer"].download(np.float64, E), speed=d["speed"].download(np.float64, E),
+                   best_idx=d["best_idx"].download(np.int32, E), best_cost=d["best_cost"].download(np.float64, E))
+        if want_seq:
+            out["best_seq"] = d["best_seq"].download(np.float64, (E, T, 2))
+        return out
+
+    def _track_buffers(self, ctx, E, T):
+        """device buffers of the track-set path, kept per (context, E, T)"""
+        key = (id(ctx), E, T)
+        if getattr(self, "_trk_key", None) != key:
+            for b in getattr(self, "_trk_bufs", {}).values():
+                b.free()
+            n = max(E, 1)
+            sizes = dict(x0=32 * n, ids=4 * n, ref=32 * n * (T + 1), oa=8 * n * T, od=8 * n * T, steer=8 * n, speed=8 * n, status=4 * n,
+                         u=16 * n * T, obj=8 * n, best_idx=4 * n, best_cost=8 * n, best_seq=16 * n * T)
+            self._trk_bufs = {k: ctx.alloc(v) for k, v in sizes.items()}
+            self._trk_key = key
+        return self._trk_bufs
 
     # the reference's helper methods, on the GPU ---------------------------------------------------------------------
     def predict_motion_kinematic(self, x0, oa, od, xref=None):

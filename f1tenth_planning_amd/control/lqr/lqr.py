@@ -10,6 +10,7 @@ import os
 import numpy as np
 
 from ...runtime import Context
+from ..pure_pursuit.pure_pursuit import _check_tracks
 
 
 class LQRPlanner():
@@ -56,12 +57,24 @@ class LQRPlanner():
         return float(out["steer"][0]), float(out["speed"][0])
 
     def plan_batch(self, states, timestep=0.01, q=(0.999, 0.0, 0.0066, 0.0), r=0.75, iterations=50, eps=0.001, waypoints=None,
-                   reset=False):
-        """states [E, 4] -> dict(steer, speed, near_idx, err); the per-ego previous errors persist between calls."""
-        ctx = self._bind(waypoints)
+                   reset=False, tracks=None, track_ids=None):
+        """states [E, 4] -> dict(steer, speed, near_idx, err); the per-ego previous errors persist between calls.
+        tracks: K waypoint arrays [N_k x m], m >= 5, with track_ids [E]: ego e follows tracks[track_ids[e]] (an id outside [0, K):
+        NaN steer / speed, near_idx -1, its error kept); `waypoints` is then not used."""
+        if tracks is not None:
+            _check_tracks(tracks, track_ids, 5)
+            if self._ctx is None:
+                self._ctx = Context(self._device if self._device is not None else int(os.environ.get("LOCAL_RANK", "0")))
+            ctx = self._ctx
+            ctx.set_tracks_cached(tracks)
+        else:
+            ctx = self._bind(waypoints)
         states = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 4)
         if reset or self._batch_err is None or self._batch_err.shape[0] != states.shape[0]:
             self._batch_err = np.zeros((states.shape[0], 2))
-        out = ctx.lqr(states, self._batch_err, self.wheelbase, timestep, q, r, iterations, eps)
+        if tracks is not None:
+            out = ctx.lqr_tracks(states, track_ids, self._batch_err, self.wheelbase, timestep, q, r, iterations, eps)
+        else:
+            out = ctx.lqr(states, self._batch_err, self.wheelbase, timestep, q, r, iterations, eps)
         self._batch_err = out["err"]
         return out

@@ -83,18 +83,45 @@ class PurePursuitPlanner():
             return 0.0, 0.0
         return float(out["steer"][0]), float(out["speed"][0])
 
-    def plan_batch(self, poses, lookahead_distance, waypoints=None, devices=None):
+    def plan_batch(self, poses, lookahead_distance, waypoints=None, devices=None, tracks=None, track_ids=None):
         """poses [E, 3] = (x, y, theta) -> dict(steer [E], speed [E], near_idx, la_idx, status).  Egos without a
         look-ahead point get (0.0, 0.0) and status 2 instead of a warning per ego.
-        devices: GPU indices (or "all"): contiguous ego ranges, one context and one host thread per GPU, no collective."""
+        devices: GPU indices (or "all"): contiguous ego ranges, one context and one host thread per GPU, no collective.
+        tracks: K waypoint arrays [N_k x m], m >= 3, all with the same columns, and track_ids [E]: ego e follows
+        tracks[track_ids[e]] (the reference's plan(..., waypoints) per vehicle); an id outside [0, K) gives NaN steer / speed and
+        status 4.  `waypoints` is then not used."""
+        if tracks is not None:
+            _check_tracks(tracks, track_ids, 3)
+            if devices is not None:
+                mc = self._multi(devices)
+                mc.set_tracks_cached(tracks)
+                return mc.pure_pursuit_tracks(poses, track_ids, lookahead_distance, self.wheelbase, self.max_reacquire)
+            ctx = self._context()
+            ctx.set_tracks_cached(tracks)
+            return ctx.pure_pursuit_tracks(poses, track_ids, lookahead_distance, self.wheelbase, self.max_reacquire)
         ctx = self._bind_waypoints(waypoints)
         if devices is not None:
-            from ...runtime import MultiContext
-            key = "all" if isinstance(devices, str) else tuple(int(d) for d in devices)
-            if getattr(self, "_mc_key", None) != key:
-                if getattr(self, "_mc", None) is not None:
-                    self._mc.close()
-                self._mc, self._mc_key = MultiContext(None if key == "all" else key), key
-            self._mc.set_waypoints_cached(self.waypoints)
-            return self._mc.pure_pursuit(poses, lookahead_distance, self.wheelbase, self.max_reacquire)
+            mc = self._multi(devices)
+            mc.set_waypoints_cached(self.waypoints)
+            return mc.pure_pursuit(poses, lookahead_distance, self.wheelbase, self.max_reacquire)
         return ctx.pure_pursuit(poses, lookahead_distance, self.wheelbase, self.max_reacquire)
+
+    def _multi(self, devices):
+        from ...runtime import MultiContext
+        key = "all" if isinstance(devices, str) else tuple(int(d) for d in devices)
+        if getattr(self, "_mc_key", None) != key:
+            if getattr(self, "_mc", None) is not None:
+                self._mc.close()
+            self._mc, self._mc_key = MultiContext(None if key == "all" else key), key
+        return self._mc
+
+
+def _check_tracks(tracks, track_ids, min_cols):
+    """the per-vehicle waypoint validation of the reference (pure_pursuit.py:100-102, stanley.py:131-132, lqr.py:195-196) for every track"""
+    if track_ids is None:
+        raise ValueError("tracks needs track_ids: one track index per ego")
+    if len(tracks) == 0:
+        raise ValueError("tracks must hold at least one waypoint array")
+    for t in tracks:
+        if len(np.shape(t)) != 2 or np.shape(t)[1] < min_cols:
+            raise ValueError(f'Waypoints needs to be a (Nxm), m >= {min_cols}, numpy array!')

@@ -8,6 +8,7 @@ import os
 import numpy as np
 
 from ...runtime import Context
+from ..pure_pursuit.pure_pursuit import _check_tracks
 
 
 class StanleyPlanner():
@@ -43,6 +44,14 @@ class StanleyPlanner():
         out = ctx.stanley(np.array([[pose_x, pose_y, pose_theta, velocity]], dtype=np.float64), self.wheelbase, k_path)
         return float(out["steer"][0]), float(out["speed"][0])
 
-    def plan_batch(self, states, k_path=5., waypoints=None):
-        """states [E, 4] = (x, y, theta, velocity) -> dict(steer [E], speed [E], near_idx [E])"""
+    def plan_batch(self, states, k_path=5., waypoints=None, tracks=None, track_ids=None):
+        """states [E, 4] = (x, y, theta, velocity) -> dict(steer [E], speed [E], near_idx [E]).
+        tracks: K waypoint arrays [N_k x m], m >= 4, with track_ids [E]: ego e follows tracks[track_ids[e]] (an id outside [0, K):
+        NaN steer / speed, near_idx -1); `waypoints` is then not used."""
+        if tracks is not None:
+            _check_tracks(tracks, track_ids, 4)
+            if self._ctx is None:
+                self._ctx = Context(self._device if self._device is not None else int(os.environ.get("LOCAL_RANK", "0")))
+            self._ctx.set_tracks_cached(tracks)
+            return self._ctx.stanley_tracks(states, track_ids, self.wheelbase, k_path)
         return self._bind(waypoints).stanley(states, self.wheelbase, k_path)

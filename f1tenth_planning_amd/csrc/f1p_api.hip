@@ -315,7 +315,7 @@ void f1p_destroy(f1p_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     f1p_comm_destroy(ctx);
-    void* ptrs[] = {ctx->d_wx, ctx->d_wy, ctx->d_wv, ctx->d_wpsi, ctx->d_wkappa, ctx->d_wbox, ctx->d_bits, ctx->d_bits0, ctx->d_bits_clear, ctx->d_bb_scratch, ctx->d_arena, ctx->d_comm_key, ctx->d_comm_idx, ctx->d_kmpc_warm, ctx->d_kmpc_qp_warm, ctx->d_stmpc_qp_warm, ctx->d_kmpc_scratch, ctx->d_mix_scratch, ctx->d_split_scratch, ctx->d_rec_scratch, ctx->d_st_scratch, ctx->d_audit, ctx->d_audit_buf, ctx->d_cl_theta[0], ctx->d_cl_theta[1], ctx->d_step, ctx->d_comm_rec, ctx->d_order, ctx->d_kmpc_cfg};
+    void* ptrs[] = {ctx->d_wx, ctx->d_wy, ctx->d_wv, ctx->d_wpsi, ctx->d_wkappa, ctx->d_wbox, ctx->d_tx, ctx->d_ty, ctx->d_tv, ctx->d_tpsi, ctx->d_tkappa, ctx->d_tbox, ctx->d_ttab, ctx->d_bits, ctx->d_bits0, ctx->d_bits_clear, ctx->d_bb_scratch, ctx->d_arena, ctx->d_comm_key, ctx->d_comm_idx, ctx->d_kmpc_warm, ctx->d_kmpc_qp_warm, ctx->d_stmpc_qp_warm, ctx->d_kmpc_scratch, ctx->d_mix_scratch, ctx->d_split_scratch, ctx->d_rec_scratch, ctx->d_st_scratch, ctx->d_audit, ctx->d_audit_buf, ctx->d_cl_theta[0], ctx->d_cl_theta[1], ctx->d_step, ctx->d_comm_rec, ctx->d_order, ctx->d_kmpc_cfg};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -421,6 +421,28 @@ int f1p_set_waypoints(f1p_ctx* ctx, const double* wp, int32_t n, int32_t ncols, 
     return f1p_set_waypoints_ex(ctx, wp, n, ncols, col_x, col_y, col_v, col_psi, -1);
 }
 
+// bounding box of every 64-segment chunk of the polyline (x, y) [n] (nearest_scan_boxed): box [ceil((n-1)/64)][4] = (xmin, xmax, ymin, ymax);
+// infinite = "never skip this chunk".  The context's raceline and every track of a track set get their boxes from here.
+static void chunk_boxes(const double* px, const double* py, int n, double* box) {
+    const int nchunk = (n - 1 + 63) / 64;
+    for (int c = 0; c < nchunk; ++c) {
+        const int lo = 64 * c, hi = std::min(64 * c + 64, n - 1);
+        double xmin = HUGE_VAL, xmax = -HUGE_VAL, ymin = HUGE_VAL, ymax = -HUGE_VAL;
+        bool open_box = false;
+        for (int i = lo; i <= hi; ++i) {
+            const double x = px[i], y = py[i];
+            if (!(fabs(x) <= 1.0e6) || !(fabs(y) <= 1.0e6)) open_box = true;
+            if (i < hi) {
+                const double dx = px[i + 1] - x, dy = py[i + 1] - y;
+                if (!(dx * dx + dy * dy >= 1e-300)) open_box = true;   // zero-length (0/0 = NaN wins np.argmin) or NaN
+            }
+            xmin = std::min(xmin, x); xmax = std::max(xmax, x); ymin = std::min(ymin, y); ymax = std::max(ymax, y);
+        }
+        if (open_box) { xmin = ymin = -HUGE_VAL; xmax = ymax = HUGE_VAL; }
+        box[4 * (size_t)c] = xmin; box[4 * (size_t)c + 1] = xmax; box[4 * (size_t)c + 2] = ymin; box[4 * (size_t)c + 3] = ymax;
+    }
+}
+
 int f1p_set_waypoints_ex(f1p_ctx* ctx, const double* wp, int32_t n, int32_t ncols, int32_t col_x, int32_t col_y,
                          int32_t col_v, int32_t col_psi, int32_t col_kappa) {
     F1P_ENTER(ctx);
@@ -443,25 +465,9 @@ int f1p_set_waypoints_ex(f1p_ctx* ctx, const double* wp, int32_t n, int32_t ncol
         soa[(size_t)3 * n + i] = col_psi >= 0 ? wp[(size_t)i * ncols + col_psi] : 0.0;
         soa[(size_t)4 * n + i] = col_kappa >= 0 ? wp[(size_t)i * ncols + col_kappa] : 0.0;
     }
-    // bounding box of every 64-segment chunk (nearest_scan_boxed); infinite = "never skip this chunk"
     const int nchunk = (n - 1 + 63) / 64;
     std::vector<double> box((size_t)4 * nchunk);
-    for (int c = 0; c < nchunk; ++c) {
-        const int lo = 64 * c, hi = std::min(64 * c + 64, n - 1);
-        double xmin = HUGE_VAL, xmax = -HUGE_VAL, ymin = HUGE_VAL, ymax = -HUGE_VAL;
-        bool open_box = false;
-        for (int i = lo; i <= hi; ++i) {
-            const double x = soa[i], y = soa[(size_t)n + i];
-            if (!(fabs(x) <= 1.0e6) || !(fabs(y) <= 1.0e6)) open_box = true;
-            if (i < hi) {
-                const double dx = soa[i + 1] - x, dy = soa[(size_t)n + i + 1] - y;
-                if (!(dx * dx + dy * dy >= 1e-300)) open_box = true;   // zero-length (0/0 = NaN wins np.argmin) or NaN
-            }
-            xmin = std::min(xmin, x); xmax = std::max(xmax, x); ymin = std::min(ymin, y); ymax = std::max(ymax, y);
-        }
-        if (open_box) { xmin = ymin = -HUGE_VAL; xmax = ymax = HUGE_VAL; }
-        box[4 * (size_t)c] = xmin; box[4 * (size_t)c + 1] = xmax; box[4 * (size_t)c + 2] = ymin; box[4 * (size_t)c + 3] = ymax;
-    }
+    chunk_boxes(soa.data(), soa.data() + n, n, box.data());
     F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (n != ctx->n_wp) {
         double** ps[] = {&ctx->d_wx, &ctx->d_wy, &ctx->d_wv, &ctx->d_wpsi, &ctx->d_wkappa, &ctx->d_wbox};
@@ -684,6 +690,203 @@ int f1p_lqr_batch(f1p_ctx* ctx, const double* states, double* err, int32_t E, do
     if (E > 0) s.outs.push_back({(void*)err, (void*)d_err, sizeof(double) * 2 * (size_t)E});   // in/out
     double* d_steer = s.out(steer, E); double* d_speed = s.out(speed, E); int32_t* d_n = s.out(near_idx, E);
     if ((rc = launch_lqr(ctx, d_st, d_err, E, wheelbase, timestep, q, r, max_iter, eps, d_steer, d_speed, d_n))) return rc;
+    return s.finish();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// track set: K polylines, each ego follows the one its track id names (k_tracks.hip)
+static void drop_track_set(f1p_ctx* ctx) {
+    double** ps[] = {&ctx->d_tx, &ctx->d_ty, &ctx->d_tv, &ctx->d_tpsi, &ctx->d_tkappa, &ctx->d_tbox};
+    for (double** p : ps) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    if (ctx->d_ttab) (void)hipFree(ctx->d_ttab);
+    ctx->d_ttab = nullptr;
+    ctx->trk_K = 0; ctx->trk_rows = 0; ctx->trk_chunks = 0; ctx->trk_has_psi = false; ctx->trk_has_kappa = false;
+}
+
+int f1p_set_track_set(f1p_ctx* ctx, const double* wp, const int64_t* row_offsets, int32_t K, int32_t ncols, int32_t col_x, int32_t col_y,
+                      int32_t col_v, int32_t col_psi, int32_t col_kappa) {
+    F1P_ENTER(ctx);
+    if (K < 0) return set_error(ctx, F1P_EINVAL, "K must be >= 0");
+    if (K == 0) {                                                   // clear
+        F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        drop_track_set(ctx);
+        return F1P_OK;
+    }
+    if (!wp || !row_offsets) return set_error(ctx, F1P_EINVAL, "waypoints and row offsets are required");
+    if (ncols < 3) return set_error(ctx, F1P_EINVAL, "Waypoints needs to be a (Nxm), m >= 3, numpy array!");   // pure_pursuit.py:101-102
+    auto bad = [&](int c) { return c < 0 || c >= ncols; };
+    if (bad(col_x) || bad(col_y) || bad(col_v) || (col_psi >= 0 && bad(col_psi)) || (col_kappa >= 0 && bad(col_kappa)))
+        return set_error(ctx, F1P_EINVAL, "column index out of range");
+    if (row_offsets[0] != 0) return set_error(ctx, F1P_EINVAL, "row_offsets[0] must be 0");
+    int64_t nchunk_all = 0;
+    for (int k = 0; k < K; ++k) {
+        const int64_t n = row_offsets[k + 1] - row_offsets[k];
+        if (!(row_offsets[k + 1] > row_offsets[k]) || n < 2) return set_error(ctx, F1P_EINVAL, "row offsets must increase by at least 2 rows per track");
+        if (row_offsets[k + 1] >= ((int64_t)1 << 31)) return set_error(ctx, F1P_EINVAL, "a track set holds fewer than 2^31 rows");
+        nchunk_all += (n - 1 + 63) / 64;
+    }
+    const int64_t rows = row_offsets[K];
+    if (col_psi >= 0)
+        for (int64_t i = 0; i < rows; ++i) {
+            const double psi = wp[(size_t)i * ncols + col_psi];
+            if (!(psi >= -1.0e4 && psi <= 1.0e4)) return set_error(ctx, F1P_EINVAL, "waypoint heading must be finite and within +-1e4 rad");
+        }
+    // everything validated: the previous set stays in place until the new one is complete on the device
+    std::vector<double> soa((size_t)5 * rows, 0.0);
+    for (int64_t i = 0; i < rows; ++i) {
+        const double* r = wp + (size_t)i * ncols;
+        soa[i] = r[col_x];
+        soa[(size_t)rows + i] = r[col_y];
+        soa[(size_t)2 * rows + i] = r[col_v];
+        soa[(size_t)3 * rows + i] = col_psi >= 0 ? r[col_psi] : 0.0;
+        soa[(size_t)4 * rows + i] = col_kappa >= 0 ? r[col_kappa] : 0.0;
+    }
+    std::vector<double> box((size_t)4 * nchunk_all);
+    std::vector<int32_t> tab((size_t)4 * K);
+    int64_t c0 = 0;
+    for (int k = 0; k < K; ++k) {
+        const int64_t off = row_offsets[k], n = row_offsets[k + 1] - off;
+        chunk_boxes(soa.data() + off, soa.data() + rows + off, (int)n, box.data() + 4 * c0);   // the rule of the context's raceline
+        tab[4 * (size_t)k] = (int32_t)off; tab[4 * (size_t)k + 1] = (int32_t)n; tab[4 * (size_t)k + 2] = (int32_t)c0; tab[4 * (size_t)k + 3] = 0;
+        c0 += (n - 1 + 63) / 64;
+    }
+    double* d[6] = {};
+    int32_t* d_tab = nullptr;
+    auto release = [&]() { for (double* p : d) if (p) (void)hipFree(p); if (d_tab) (void)hipFree(d_tab); };
+    int rc = F1P_OK;
+    for (int c = 0; c < 5 && rc == F1P_OK; ++c) {
+        rc = check_hip(ctx, hipMalloc((void**)&d[c], sizeof(double) * (size_t)rows), "hipMalloc(track set)");
+        if (rc == F1P_OK) rc = check_hip(ctx, hipMemcpy(d[c], soa.data() + (size_t)c * rows, sizeof(double) * (size_t)rows, hipMemcpyHostToDevice), "hipMemcpy(track set)");
+    }
+    if (rc == F1P_OK) rc = check_hip(ctx, hipMalloc((void**)&d[5], sizeof(double) * box.size()), "hipMalloc(track boxes)");
+    if (rc == F1P_OK) rc = check_hip(ctx, hipMemcpy(d[5], box.data(), sizeof(double) * box.size(), hipMemcpyHostToDevice), "hipMemcpy(track boxes)");
+    if (rc == F1P_OK) rc = check_hip(ctx, hipMalloc((void**)&d_tab, sizeof(int32_t) * tab.size()), "hipMalloc(track table)");
+    if (rc == F1P_OK) rc = check_hip(ctx, hipMemcpy(d_tab, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice), "hipMemcpy(track table)");
+    if (rc == F1P_OK) rc = check_hip(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");   // no launch still reads the old set
+    if (rc != F1P_OK) { release(); return rc; }
+    drop_track_set(ctx);
+    ctx->d_tx = d[0]; ctx->d_ty = d[1]; ctx->d_tv = d[2]; ctx->d_tpsi = d[3]; ctx->d_tkappa = d[4]; ctx->d_tbox = d[5]; ctx->d_ttab = d_tab;
+    ctx->trk_K = K; ctx->trk_rows = (int)rows; ctx->trk_chunks = (int)nchunk_all;
+    ctx->trk_has_psi = col_psi >= 0;
+    ctx->trk_has_kappa = col_kappa >= 0;
+    return F1P_OK;
+}
+
+static int need_tracks(f1p_ctx* ctx, bool psi, bool kappa) {
+    if (ctx->trk_K < 1) return set_error(ctx, F1P_ESTATE, "no track set: call f1p_set_track_set first");
+    if (psi && !ctx->trk_has_psi) return set_error(ctx, F1P_ESTATE, "the track set has no heading column");
+    if (kappa && !ctx->trk_has_kappa) return set_error(ctx, F1P_ESTATE, "the track set has no curvature column");
+    return F1P_OK;
+}
+
+int f1p_nearest_point_tracks_batch(f1p_ctx* ctx, const double* pts, const int32_t* track_id, int32_t E, double* proj, double* dist, double* t,
+                                   int32_t* idx) {
+    F1P_ENTER(ctx);
+    if (E < 0 || (E > 0 && (!pts || !track_id))) return set_error(ctx, F1P_EINVAL, "bad pts / track_id / E");
+    int rc = need_tracks(ctx, false, false); if (rc) return rc;
+    Stage s(ctx);
+    s.need(sizeof(double) * 2 * E); s.need(sizeof(int32_t) * E); s.need(sizeof(double) * 2 * E, proj); s.need(sizeof(double) * E, dist);
+    s.need(sizeof(double) * E, t); s.need(sizeof(int32_t) * E, idx);
+    if ((rc = s.begin())) return rc;
+    const double* d_pts; const int32_t* d_tid;
+    if ((rc = s.in(pts, (size_t)2 * E, &d_pts))) return rc;
+    if ((rc = s.in(track_id, (size_t)E, &d_tid))) return rc;
+    double* d_proj = s.out(proj, (size_t)2 * E); double* d_dist = s.out(dist, E); double* d_t = s.out(t, E);
+    int32_t* d_idx = s.out(idx, E);
+    if ((rc = launch_nearest_tracks(ctx, d_pts, d_tid, E, d_proj, d_dist, d_t, d_idx))) return rc;
+    return s.finish();
+}
+
+int f1p_pure_pursuit_tracks_dev(f1p_ctx* ctx, const double* d_poses, const int32_t* d_track_id, int32_t E, double lookahead, double wheelbase,
+                                double max_reacquire, double* d_steer, double* d_speed, int32_t* d_near_idx, int32_t* d_la_idx,
+                                int32_t* d_status) {
+    F1P_ENTER(ctx);
+    if (E < 0 || (E > 0 && (!d_poses || !d_track_id || !d_steer || !d_speed))) return set_error(ctx, F1P_EINVAL, "poses, track_id, steer and speed are required");
+    const int rc = need_tracks(ctx, false, false); if (rc) return rc;
+    return launch_pure_pursuit_tracks(ctx, d_poses, d_track_id, E, lookahead, wheelbase, max_reacquire, d_steer, d_speed, d_near_idx, d_la_idx,
+                                      d_status);
+}
+
+int f1p_pure_pursuit_tracks_batch(f1p_ctx* ctx, const double* poses, const int32_t* track_id, int32_t E, double lookahead, double wheelbase,
+                                  double max_reacquire, double* steer, double* speed, int32_t* near_idx, int32_t* la_idx, int32_t* status) {
+    F1P_ENTER(ctx);
+    if (E < 0 || (E > 0 && (!poses || !track_id || !steer || !speed))) return set_error(ctx, F1P_EINVAL, "poses, track_id, steer and speed are required");
+    int rc = need_tracks(ctx, false, false); if (rc) return rc;
+    Stage s(ctx);
+    s.need(sizeof(double) * 3 * E); s.need(sizeof(int32_t) * E); s.need(sizeof(double) * E); s.need(sizeof(double) * E);
+    s.need(sizeof(int32_t) * E, near_idx); s.need(sizeof(int32_t) * E, la_idx); s.need(sizeof(int32_t) * E, status);
+    if ((rc = s.begin())) return rc;
+    const double* d_poses; const int32_t* d_tid;
+    if ((rc = s.in(poses, (size_t)3 * E, &d_poses))) return rc;
+    if ((rc = s.in(track_id, (size_t)E, &d_tid))) return rc;
+    double* d_steer = s.out(steer, E); double* d_speed = s.out(speed, E);
+    int32_t* d_n = s.out(near_idx, E); int32_t* d_l = s.out(la_idx, E); int32_t* d_s = s.out(status, E);
+    if ((rc = launch_pure_pursuit_tracks(ctx, d_poses, d_tid, E, lookahead, wheelbase, max_reacquire, d_steer, d_speed, d_n, d_l, d_s))) return rc;
+    return s.finish();
+}
+
+int f1p_stanley_tracks_batch(f1p_ctx* ctx, const double* states, const int32_t* track_id, int32_t E, double wheelbase, double k_path,
+                             double* steer, double* speed, int32_t* near_idx) {
+    F1P_ENTER(ctx);
+    if (E < 0 || (E > 0 && (!states || !track_id || !steer || !speed))) return set_error(ctx, F1P_EINVAL, "states, track_id, steer and speed are required");
+    int rc = need_tracks(ctx, true, false); if (rc) return rc;
+    Stage s(ctx);
+    s.need(8 * 4 * (size_t)E); s.need(4 * (size_t)E); s.need(8 * (size_t)E); s.need(8 * (size_t)E); s.need(4 * (size_t)E, near_idx);
+    if ((rc = s.begin())) return rc;
+    const double* d_st; const int32_t* d_tid;
+    if ((rc = s.in(states, (size_t)4 * E, &d_st))) return rc;
+    if ((rc = s.in(track_id, (size_t)E, &d_tid))) return rc;
+    double* d_steer = s.out(steer, E); double* d_speed = s.out(speed, E); int32_t* d_n = s.out(near_idx, E);
+    if ((rc = launch_stanley_tracks(ctx, d_st, d_tid, E, wheelbase, k_path, d_steer, d_speed, d_n))) return rc;
+    return s.finish();
+}
+
+int f1p_lqr_tracks_batch(f1p_ctx* ctx, const double* states, const int32_t* track_id, double* err, int32_t E, double wheelbase, double timestep,
+                         const double q[4], double r, int32_t max_iter, double eps, double* steer, double* speed, int32_t* near_idx) {
+    F1P_ENTER(ctx);
+    if (E < 0 || (E > 0 && (!states || !track_id || !err || !steer || !speed)) || !q)
+        return set_error(ctx, F1P_EINVAL, "states, track_id, err, q, steer and speed are required");
+    if (!(timestep > 0.0) || !(wheelbase > 0.0) || max_iter < 0) return set_error(ctx, F1P_EINVAL, "timestep and wheelbase must be > 0, max_iter >= 0");
+    int rc = need_tracks(ctx, true, true); if (rc) return rc;
+    Stage s(ctx);
+    s.need(8 * 4 * (size_t)E); s.need(4 * (size_t)E); s.need(8 * 2 * (size_t)E); s.need(8 * (size_t)E); s.need(8 * (size_t)E);
+    s.need(4 * (size_t)E, near_idx);
+    if ((rc = s.begin())) return rc;
+    const double* d_st; const int32_t* d_tid;
+    if ((rc = s.in(states, (size_t)4 * E, &d_st))) return rc;
+    if ((rc = s.in(track_id, (size_t)E, &d_tid))) return rc;
+    const double* d_err_in;
+    if ((rc = s.in((const double*)err, (size_t)2 * E, &d_err_in))) return rc;
+    double* d_err = const_cast<double*>(d_err_in);
+    if (E > 0) s.outs.push_back({(void*)err, (void*)d_err, sizeof(double) * 2 * (size_t)E});   // in/out
+    double* d_steer = s.out(steer, E); double* d_speed = s.out(speed, E); int32_t* d_n = s.out(near_idx, E);
+    if ((rc = launch_lqr_tracks(ctx, d_st, d_tid, d_err, E, wheelbase, timestep, q, r, max_iter, eps, d_steer, d_speed, d_n))) return rc;
+    return s.finish();
+}
+
+int f1p_kmpc_ref_tracks_dev(f1p_ctx* ctx, const double* d_states, const int32_t* d_track_id, int32_t E, int32_t horizon, double dt, double dl,
+                            double* d_ref) {
+    F1P_ENTER(ctx);
+    if (E < 0 || (E > 0 && (!d_states || !d_track_id || !d_ref))) return set_error(ctx, F1P_EINVAL, "bad states / track_id / ref / E");
+    if (horizon < 1 || !(dt > 0) || !(dl > 0)) return set_error(ctx, F1P_EINVAL, "horizon, dt and dl must be positive");
+    const int rc = need_tracks(ctx, true, false); if (rc) return rc;
+    return launch_kmpc_ref_tracks(ctx, d_states, d_track_id, E, horizon, dt, dl, d_ref);
+}
+
+int f1p_kmpc_ref_tracks_batch(f1p_ctx* ctx, const double* states, const int32_t* track_id, int32_t E, int32_t horizon, double dt, double dl,
+                              double* ref) {
+    F1P_ENTER(ctx);
+    if (E < 0 || (E > 0 && (!states || !track_id || !ref))) return set_error(ctx, F1P_EINVAL, "bad states / track_id / ref / E");
+    if (horizon < 1 || !(dt > 0) || !(dl > 0)) return set_error(ctx, F1P_EINVAL, "horizon, dt and dl must be positive");
+    int rc = need_tracks(ctx, true, false); if (rc) return rc;
+    Stage s(ctx);
+    s.need(8 * 4 * (size_t)E); s.need(4 * (size_t)E); s.need(8 * (size_t)E * 4 * (horizon + 1));
+    if ((rc = s.begin())) return rc;
+    const double* d_s; const int32_t* d_tid;
+    if ((rc = s.in(states, (size_t)4 * E, &d_s))) return rc;
+    if ((rc = s.in(track_id, (size_t)E, &d_tid))) return rc;
+    double* d_ref = s.out(ref, (size_t)E * 4 * (horizon + 1));
+    if ((rc = launch_kmpc_ref_tracks(ctx, d_s, d_tid, E, horizon, dt, dl, d_ref))) return rc;
     return s.finish();
 }
 

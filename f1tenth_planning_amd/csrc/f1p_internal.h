@@ -26,6 +26,14 @@ struct f1p_ctx {
     bool has_kappa = false;
     double* d_wbox = nullptr;   // [ceil((n_wp-1)/64)][4] chunk bounding boxes for nearest_scan_boxed
 
+    // track set (f1p_set_track_set), independent of the raceline above: K polylines back to back, struct-of-arrays fp64, their chunk
+    // boxes back to back, and the table int32 [K][4] = (first row, rows, first chunk box, 0) the k_*_tracks kernels index by track id
+    int trk_K = 0;
+    int trk_rows = 0, trk_chunks = 0;
+    bool trk_has_psi = false, trk_has_kappa = false;
+    double *d_tx = nullptr, *d_ty = nullptr, *d_tv = nullptr, *d_tpsi = nullptr, *d_tkappa = nullptr, *d_tbox = nullptr;
+    int32_t* d_ttab = nullptr;
+
     // occupancy grid, bit-packed and row-flipped
     bool has_grid = false;
     uint32_t* d_bits = nullptr;    // active collision bitmap (the uploaded grid, or its inflation by f1p_inflate_grid)
@@ -233,6 +241,22 @@ int launch_stmpc_predict(f1p_ctx* ctx, const double* d_x0, const double* d_oa, c
 int launch_stmpc_shoot(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const float* d_controls, int E, const f1p_stmpc_cfg* cfg,
                        double* d_steer, double* d_speed, int32_t* d_best_idx, double* d_best_cost, double* d_best_seq);
 int launch_stmpc_ref(f1p_ctx* ctx, const double* d_states, int E, int horizon, double dt, double dl, double* d_ref);
+// k_tracks.hip: the trackers over the ctx's track set, ego e on track d_tid[e]
+struct TrackSetDev {
+    const double *x, *y, *v, *psi, *kappa, *box;   // psi / kappa null when the set has no such column
+    const int4* tab;                                 // [K] (first row, rows, first chunk box, 0)
+    int K;
+};
+TrackSetDev track_set_dev(const f1p_ctx* ctx);
+int launch_nearest_tracks(f1p_ctx* ctx, const double* d_pts, const int32_t* d_tid, int E, double* d_proj, double* d_dist, double* d_t,
+                          int32_t* d_idx);
+int launch_pure_pursuit_tracks(f1p_ctx* ctx, const double* d_poses, const int32_t* d_tid, int E, double lookahead, double wheelbase,
+                               double max_reacquire, double* d_steer, double* d_speed, int32_t* d_near, int32_t* d_la, int32_t* d_status);
+int launch_stanley_tracks(f1p_ctx* ctx, const double* d_states, const int32_t* d_tid, int E, double wheelbase, double k_path,
+                          double* d_steer, double* d_speed, int32_t* d_near);
+int launch_lqr_tracks(f1p_ctx* ctx, const double* d_states, const int32_t* d_tid, double* d_err, int E, double wheelbase, double ts,
+                      const double* q, double r, int max_iter, double eps, double* d_steer, double* d_speed, int32_t* d_near);
+int launch_kmpc_ref_tracks(f1p_ctx* ctx, const double* d_states, const int32_t* d_tid, int E, int horizon, double dt, double dl, double* d_ref);
 int launch_argmin_key(f1p_ctx* ctx, const double* d_cost, uint64_t* d_key, int E);
 int launch_argmin_mask(f1p_ctx* ctx, const uint64_t* d_own, const uint64_t* d_min, const int32_t* d_idx, int32_t* d_masked,
                        double* d_cost_out, int E);

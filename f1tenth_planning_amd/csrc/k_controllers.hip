@@ -8,32 +8,9 @@
 // first resolves the front-axle errors of its 256 egos wave by wave into LDS and then iterates with ONE THREAD PER EGO, all
 // lanes busy, everything in registers.  fp64 throughout.
 #include "f1p_internal.h"
+#include "tracker_device.h"
 
 namespace f1p {
-
-struct FrontErr { double theta_e, ef; int idx; };
-
-// front-axle point -> nearest raceline segment -> cross-track and heading error (stanley.py:57-88 == lqr.py:60-103)
-__device__ __forceinline__ FrontErr front_axle_errors(double x, double y, double theta, double wheelbase,
-                                                      const double* __restrict__ wx, const double* __restrict__ wy,
-                                                      const double* __restrict__ wpsi, const double* __restrict__ wbox, int n) {
-    // executed by ONE wave: all 64 lanes call it with the same arguments and get the same result
-    const double fx = x + wheelbase * cos(theta);            // stanley.py:66
-    const double fy = y + wheelbase * sin(theta);            // :67
-    double bd; int bi;
-    nearest_scan_boxed(fx, fy, wx, wy, wbox, n, threadIdx.x & 63, 64, bd, bi);   // :69
-    wave_argmin(bd, bi);
-    const SegProj s = seg_project(fx, fy, wx[bi], wy[bi], wx[bi + 1], wy[bi + 1]);
-    const double vx = fx - s.qx, vy = fy - s.qy;             // :70
-    FrontErr r;
-    r.ef = dot2(vx, vy, cos(theta - F1P_PI / 2.0), sin(theta - F1P_PI / 2.0));   // :73-75 (np.dot)
-    double te = wpsi[bi] - theta;                            // :79-80 pi_2_pi: a single wrap
-    if (te > F1P_PI) te = te - 2.0 * F1P_PI;
-    else if (te < -F1P_PI) te = te + 2.0 * F1P_PI;
-    r.theta_e = te;
-    r.idx = bi;
-    return r;
-}
 
 __global__ __launch_bounds__(256) void k_stanley(const double* __restrict__ states, int E, double wheelbase, double k_path,
                                                  const double* __restrict__ wx, const double* __restrict__ wy,
@@ -50,98 +27,6 @@ __global__ __launch_bounds__(256) void k_stanley(const double* __restrict__ stat
         if (near_idx) near_idx[e] = fe.idx;
     }
 }
-
-// row-major 4x4 product
-__device__ __forceinline__ void mat4_mul(const double* a, const double* b, double* c) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s += a[4 * i + k] * b[4 * k + j];
-            c[4 * i + j] = s;
-        }
-}
-
-// solve_lqr (utils/utils.py:167-205) for one input: pinv of the 1x1 matrix R + B^T P B is a reciprocal
-__device__ void solve_lqr4(const double* A, const double* B, const double* q, double R, double tolerance, int max_iter, double* K) {
-    double AT[16], P[16], Pn[16], T1[16], T2[16];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { AT[4 * i + j] = A[4 * j + i]; P[4 * i + j] = (i == j) ? q[i] : 0.0; }   // P = Q  :190
-    int it = 0;
-    double diff = __builtin_huge_val();
-    while (it < max_iter && diff > tolerance) {                // :194
-        ++it;
-        mat4_mul(AT, P, T1);                                   // A^T P
-        mat4_mul(T1, A, T2);                                   // A^T P A
-        double atpb[4], pb[4], btp[4], btpa[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            double s = 0.0, s2 = 0.0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { s += T1[4 * i + k] * B[k]; s2 += P[4 * i + k] * B[k]; }
-            atpb[i] = s; pb[i] = s2;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s += B[k] * P[4 * k + j];
-            btp[j] = s;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s += btp[k] * A[4 * k + j];
-            btpa[j] = s;
-        }
-        double btpb = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) btpb += btp[k] * B[k];   /* (B^T P) B, the order numpy evaluates BT @ P @ B */
-        const double den = R + btpb;
-        const double inv = den != 0.0 ? 1.0 / den : 0.0;
-        double mx = -__builtin_huge_val();
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                Pn[4 * i + j] = T2[4 * i + j] - atpb[i] * inv * btpa[j] + ((i == j) ? q[i] : 0.0);   // :196-197
-                const double d = Pn[4 * i + j] - P[4 * i + j];
-                if (d > mx) mx = d;
-            }
-        diff = fabs(mx);                                       // :200 np.abs(np.max(P_next - P))
-#pragma unroll
-        for (int i = 0; i < 16; ++i) P[i] = Pn[i];
-    }
-    double btp[4], pb[4], btpa[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        double s = 0.0, s2 = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { s += B[k] * P[4 * k + j]; s2 += P[4 * j + k] * B[k]; }
-        btp[j] = s; pb[j] = s2;
-    }
-    double btpb = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) btpb += btp[k] * B[k];   /* (B^T P) B, the order numpy evaluates BT @ P @ B */
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s += btp[k] * A[4 * k + j];
-        btpa[j] = s;
-    }
-    const double den = btpb + R;
-    const double inv = den != 0.0 ? 1.0 / den : 0.0;           // :203
-#pragma unroll
-    for (int j = 0; j < 4; ++j) K[j] = inv * btpa[j];
-}
-
-struct LqrParams { double wheelbase, ts, q[4], r, eps; int max_iter; };
 
 __global__ __launch_bounds__(256) void k_lqr(const double* __restrict__ states, double* __restrict__ err, int E, LqrParams p,
                                              const double* __restrict__ wx, const double* __restrict__ wy,

@@ -135,6 +135,8 @@ class Context:
         self.device = int(device)
         self.n_waypoints = 0
         self._wp_key = None
+        self.n_tracks = 0
+        self._tracks_key = None
         self.has_grid = False
         self._pinned = {}        # (tag, shape, dtype) -> numpy view of page-locked memory
         self._pinned_ptrs = []
@@ -231,6 +233,36 @@ class Context:
         if key != self._wp_key:
             self.set_waypoints(wp, cols)
             self._wp_key = key
+
+    def set_tracks(self, tracks, cols=None):
+        """Track set (f1p_set_track_set): `tracks` = K arrays [N_k, m], m >= 3, every N_k >= 2, all with the same columns; cols as
+        set_waypoints.  The *_tracks calls then take track_ids [E] int32 (ego e follows tracks[track_ids[e]]).  Independent of the
+        raceline of set_waypoints.  An empty list clears the set."""
+        tracks = [np.asarray(t) for t in tracks]
+        if not tracks:
+            self._check(self.lib.f1p_set_track_set(self.h, None, None, 0, 0, 0, 0, 0, -1, -1))
+            self.n_tracks = 0
+            return
+        m = tracks[0].shape[1] if tracks[0].ndim == 2 else -1
+        if any(t.ndim != 2 or t.shape[1] != m for t in tracks) or m < 3:
+            raise ValueError("tracks must be 2-D arrays [N_k, m], m >= 3, all with the same m")
+        wp = _f64(np.concatenate(tracks, axis=0))
+        offsets = np.zeros(len(tracks) + 1, np.int64)
+        offsets[1:] = np.cumsum([t.shape[0] for t in tracks])
+        if cols is None:
+            cols = (0, 1, 2, 3 if m >= 4 else -1, 4 if m >= 5 else -1)
+        cols = tuple(int(c) for c in cols) + (-1,) * (5 - len(cols))      # (x, y, v, psi, kappa)
+        self._check(self.lib.f1p_set_track_set(self.h, _ptr(wp), _ptr(offsets), len(tracks), m, *cols))
+        self.n_tracks = len(tracks)
+
+    def set_tracks_cached(self, tracks, cols=None):
+        """set_tracks, skipping the upload when neither the arrays' content nor the columns changed since the last upload"""
+        tracks = [np.asarray(t) for t in tracks]
+        key = (tuple((t.shape, t.dtype.str, _content_signature(t)) for t in tracks), None if cols is None else tuple(cols))
+        if key != self._tracks_key:
+            self._tracks_key = None
+            self.set_tracks(tracks, cols)
+            self._tracks_key = key
 
     def set_grid(self, img, resolution, origin, occupied_below):
         """img [h, w] u8, row 0 = top (ROS map_server); a cell is occupied iff value < occupied_below."""
@@ -334,6 +366,64 @@ class Context:
         self._check(self.lib.f1p_lqr_batch(self.h, _ptr(st), _ptr(err), E, float(wheelbase), float(timestep), _ptr(qa), float(r),
                                            int(max_iter), float(eps), _ptr(out["steer"]), _ptr(out["speed"]), _ptr(out["near_idx"])))
         return out
+
+    # ---- track sets: ego e follows track track_ids[e] of set_tracks --------------------------------------------
+    @staticmethod
+    def _ids(track_ids, E):
+        ids = np.ascontiguousarray(track_ids, dtype=np.int32).reshape(-1)
+        if ids.shape[0] != E:
+            raise ValueError(f"track_ids must hold one id per ego ({E}), not {ids.shape[0]}")
+        return ids
+
+    def nearest_point_tracks(self, pts, track_ids):
+        pts = _f64(pts, (-1, 2)); E = pts.shape[0]; ids = self._ids(track_ids, E)
+        proj = np.empty((E, 2)); dist = np.empty(E); t = np.empty(E); idx = np.empty(E, np.int32)
+        self._check(self.lib.f1p_nearest_point_tracks_batch(self.h, _ptr(pts), _ptr(ids), E, _ptr(proj), _ptr(dist), _ptr(t), _ptr(idx)))
+        return proj, dist, t, idx
+
+    def pure_pursuit_tracks(self, poses, track_ids, lookahead, wheelbase=0.33, max_reacquire=20.0):
+        poses = _f64(poses, (-1, 3)); E = poses.shape[0]; ids = self._ids(track_ids, E)
+        out = dict(steer=np.empty(E), speed=np.empty(E), near_idx=np.empty(E, np.int32), la_idx=np.empty(E, np.int32),
+                   status=np.empty(E, np.int32))
+        self._check(self.lib.f1p_pure_pursuit_tracks_batch(self.h, _ptr(poses), _ptr(ids), E, float(lookahead), float(wheelbase),
+                                                           float(max_reacquire), _ptr(out["steer"]), _ptr(out["speed"]),
+                                                           _ptr(out["near_idx"]), _ptr(out["la_idx"]), _ptr(out["status"])))
+        return out
+
+    def pure_pursuit_tracks_dev(self, d_poses, d_track_ids, E, lookahead, d_steer, d_speed, d_near_idx=None, d_la_idx=None, d_status=None,
+                                wheelbase=0.33, max_reacquire=20.0):
+        """Asynchronous launch on HBM-resident buffers; poses [E][3], track ids [E] int32."""
+        p = lambda b: None if b is None else b.ptr   # noqa: E731
+        self._check(self.lib.f1p_pure_pursuit_tracks_dev(self.h, p(d_poses), p(d_track_ids), int(E), float(lookahead), float(wheelbase),
+                                                         float(max_reacquire), p(d_steer), p(d_speed), p(d_near_idx), p(d_la_idx),
+                                                         p(d_status)))
+
+    def stanley_tracks(self, states, track_ids, wheelbase=0.33, k_path=5.0):
+        st = _f64(states, (-1, 4)); E = st.shape[0]; ids = self._ids(track_ids, E)
+        out = dict(steer=np.empty(E), speed=np.empty(E), near_idx=np.empty(E, np.int32))
+        self._check(self.lib.f1p_stanley_tracks_batch(self.h, _ptr(st), _ptr(ids), E, float(wheelbase), float(k_path), _ptr(out["steer"]),
+                                                      _ptr(out["speed"]), _ptr(out["near_idx"])))
+        return out
+
+    def lqr_tracks(self, states, track_ids, err, wheelbase=0.33, timestep=0.01, q=(0.999, 0.0, 0.0066, 0.0), r=0.75, max_iter=50, eps=0.001):
+        """as lqr(); an ego with a bad track id keeps its err"""
+        st = _f64(states, (-1, 4)); E = st.shape[0]; ids = self._ids(track_ids, E)
+        err = _f64(err, (E, 2)).copy(); qa = _f64(q, (4,))
+        out = dict(steer=np.empty(E), speed=np.empty(E), near_idx=np.empty(E, np.int32), err=err)
+        self._check(self.lib.f1p_lqr_tracks_batch(self.h, _ptr(st), _ptr(ids), _ptr(err), E, float(wheelbase), float(timestep), _ptr(qa),
+                                                  float(r), int(max_iter), float(eps), _ptr(out["steer"]), _ptr(out["speed"]),
+                                                  _ptr(out["near_idx"])))
+        return out
+
+    def kmpc_ref_tracks(self, states, track_ids, horizon, dt=0.1, dl=0.03):
+        st = _f64(states, (-1, 4)); E = st.shape[0]; ids = self._ids(track_ids, E)
+        ref = np.empty((E, 4, horizon + 1))
+        self._check(self.lib.f1p_kmpc_ref_tracks_batch(self.h, _ptr(st), _ptr(ids), E, int(horizon), float(dt), float(dl), _ptr(ref)))
+        return ref
+
+    def kmpc_ref_tracks_dev(self, d_states, d_track_ids, E, horizon, d_ref, dt=0.1, dl=0.03):
+        p = lambda b: None if b is None else b.ptr   # noqa: E731
+        self._check(self.lib.f1p_kmpc_ref_tracks_dev(self.h, p(d_states), p(d_track_ids), int(E), int(horizon), float(dt), float(dl), p(d_ref)))
 
     # ---- lattice -------------------------------------------------------------------------------------------
     def lattice_plan(self, poses, cfg: LatticeCfg, goals=None, prev_theta=None, want_traj=True, want_all=False,
@@ -851,6 +941,12 @@ class MultiContext:
     def set_waypoints_cached(self, waypoints, cols=None):
         self._each(lambda c, g: c.set_waypoints_cached(waypoints, cols))
 
+    def set_tracks(self, tracks, cols=None):
+        self._each(lambda c, g: c.set_tracks(tracks, cols))
+
+    def set_tracks_cached(self, tracks, cols=None):
+        self._each(lambda c, g: c.set_tracks_cached(tracks, cols))
+
     def set_grid(self, img, resolution, origin, occupied_below):
         self._each(lambda c, g: c.set_grid(img, resolution, origin, occupied_below))
 
@@ -898,6 +994,14 @@ class MultiContext:
     def pure_pursuit(self, poses, lookahead, wheelbase=0.33, max_reacquire=20.0):
         poses = _f64(poses, (-1, 3))
         return self._sharded(poses.shape[0], lambda c, lo, hi: c.pure_pursuit(poses[lo:hi], lookahead, wheelbase, max_reacquire))
+
+    def pure_pursuit_tracks(self, poses, track_ids, lookahead, wheelbase=0.33, max_reacquire=20.0):
+        poses = _f64(poses, (-1, 3)); ids = Context._ids(track_ids, poses.shape[0])
+        return self._sharded(poses.shape[0], lambda c, lo, hi: c.pure_pursuit_tracks(poses[lo:hi], ids[lo:hi], lookahead, wheelbase, max_reacquire))
+
+    def kmpc_ref_tracks(self, states, track_ids, horizon, dt=0.1, dl=0.03):
+        st = _f64(states, (-1, 4)); ids = Context._ids(track_ids, st.shape[0])
+        return self._sharded(st.shape[0], lambda c, lo, hi: dict(ref=c.kmpc_ref_tracks(st[lo:hi], ids[lo:hi], horizon, dt, dl)))["ref"]
 
     def kmpc_ref(self, states, horizon, dt=0.1, dl=0.03):
         st = _f64(states, (-1, 4))

@@ -45,6 +45,7 @@ extern "C" {
 #define F1P_ST_REACQUIRE 1      /* nearest waypoint used, dist < max_reacquire (pure_pursuit.py:80-81) */
 #define F1P_ST_NO_LOOKAHEAD 2   /* no look-ahead point: (0.0, 0.0) + warning (pure_pursuit.py:112-114) */
 #define F1P_ST_ALL_BLOCKED 3    /* lattice: every candidate is in collision / infeasible               */
+#define F1P_ST_BAD_TRACK 4      /* track-set calls: the ego's track id is outside [0, K) (NaN outputs)  */
 
 /* candidate trajectory generators of the lattice planner */
 #define F1P_GEN_CLOTHOID 0      /* G1 Hermite clothoid, what the reference builds with pyclothoids (lattice_planner.py:196) */
@@ -258,6 +259,50 @@ int f1p_stanley_batch(f1p_ctx* ctx, const double* states, int32_t E, double whee
 int f1p_lqr_batch(f1p_ctx* ctx, const double* states, double* err, int32_t E, double wheelbase, double timestep,
                   const double q[4], double r, int32_t max_iter, double eps, double* steer, double* speed,
                   int32_t* near_idx);
+
+/* ------------------------------------------------------------------------------------------------
+ * Track sets: every ego follows its own polyline.  The reference hands each planner its waypoints per call --
+ * PurePursuitPlanner.plan(..., waypoints) (control/pure_pursuit/pure_pursuit.py:85), StanleyPlanner.plan
+ * (control/stanley/stanley.py:114), LQRPlanner.plan (control/lqr/lqr.py:156), KMPCPlanner.plan(states, waypoints)
+ * (control/kinematic_mpc/kinematic_mpc.py:115) -- so one planner per vehicle can follow any line.  A track set holds K such
+ * lines next to the ctx's raceline (the two are independent; f1p_set_waypoints does not touch the set, nor the reverse), and
+ * the *_tracks calls take track_id [E] int32: ego e follows track track_id[e].  Each ego's outputs are bit-identical to the
+ * single-raceline call on a ctx whose raceline is that ego's track.  An id outside [0, K) gives that ego NaN steer / speed
+ * (NaN rows for the MPC reference), near_idx / idx -1, status F1P_ST_BAD_TRACK, and the call still succeeds; the other egos
+ * are unaffected.  A *_tracks call without a track set returns F1P_ESTATE.
+ * ---------------------------------------------------------------------------------------------- */
+/* wp: row-major [row_offsets[K]][ncols] fp64, track k = rows [row_offsets[k], row_offsets[k+1]); columns as
+ * f1p_set_waypoints_ex (col_psi / col_kappa < 0: none).  row_offsets[0] = 0, every track >= 2 rows, fewer than 2^31 rows in
+ * all, headings finite within +-1e4 rad; otherwise F1P_EINVAL and the previous set stays in place.  A second call replaces
+ * the set; K = 0 clears it (wp and row_offsets may then be NULL). */
+int f1p_set_track_set(f1p_ctx* ctx, const double* wp, const int64_t* row_offsets, int32_t K, int32_t ncols, int32_t col_x,
+                      int32_t col_y, int32_t col_v, int32_t col_psi, int32_t col_kappa);
+/* nearest_point (utils/utils.py:37-67) of pts [E][2] on each ego's track: outputs as f1p_nearest_point_batch */
+int f1p_nearest_point_tracks_batch(f1p_ctx* ctx, const double* pts, const int32_t* track_id, int32_t E, double* proj, double* dist,
+                                   double* t, int32_t* idx);
+/* PurePursuitPlanner.plan (pure_pursuit.py:85-122) on each ego's track: arguments and outputs as f1p_pure_pursuit_batch / _dev
+ * (one ego per wave whatever f1p_pure_pursuit_set_form says) */
+int f1p_pure_pursuit_tracks_batch(f1p_ctx* ctx, const double* poses, const int32_t* track_id, int32_t E, double lookahead,
+                                  double wheelbase, double max_reacquire, double* steer, double* speed, int32_t* near_idx,
+                                  int32_t* la_idx, int32_t* status);
+int f1p_pure_pursuit_tracks_dev(f1p_ctx* ctx, const double* d_poses, const int32_t* d_track_id, int32_t E, double lookahead,
+                                double wheelbase, double max_reacquire, double* d_steer, double* d_speed, int32_t* d_near_idx,
+                                int32_t* d_la_idx, int32_t* d_status);
+/* StanleyPlanner.plan (stanley.py:114-139) on each ego's track (needs a heading column, else F1P_ESTATE) */
+int f1p_stanley_tracks_batch(f1p_ctx* ctx, const double* states, const int32_t* track_id, int32_t E, double wheelbase, double k_path,
+                             double* steer, double* speed, int32_t* near_idx);
+/* LQRPlanner.plan (lqr.py:156-210) on each ego's track (needs heading and curvature columns, else F1P_ESTATE); err as
+ * f1p_lqr_batch, left untouched for an ego with a bad track id */
+int f1p_lqr_tracks_batch(f1p_ctx* ctx, const double* states, const int32_t* track_id, double* err, int32_t E, double wheelbase,
+                         double timestep, const double q[4], double r, int32_t max_iter, double eps, double* steer, double* speed,
+                         int32_t* near_idx);
+/* calc_ref_trajectory_kinematic (kinematic_mpc.py:162-206) on each ego's track (cols x, y, v, psi; needs a heading column):
+ * as f1p_kmpc_ref_batch, with f1p_kmpc_set_yaw_fixup honoured the same way (the fix-up acts on a per-ego view, never on the
+ * stored tracks).  The _dev twin is asynchronous on device buffers, for f1p_kmpc_plan_dev / f1p_kmpc_qp_dev. */
+int f1p_kmpc_ref_tracks_batch(f1p_ctx* ctx, const double* states, const int32_t* track_id, int32_t E, int32_t horizon, double dt,
+                              double dl, double* ref);
+int f1p_kmpc_ref_tracks_dev(f1p_ctx* ctx, const double* d_states, const int32_t* d_track_id, int32_t E, int32_t horizon, double dt,
+                            double dl, double* d_ref);
 
 /* ------------------------------------------------------------------------------------------------
  * LatticePlanner.plan (planning/lattice_planner/lattice_planner.py:174-214) for E egos, one fused launch:
