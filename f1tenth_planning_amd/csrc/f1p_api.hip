@@ -189,7 +189,8 @@ static int ensure_copy_stream(f1p_ctx* ctx) {
     return F1P_OK;
 }
 
-static int validate_lattice(f1p_ctx* ctx, const f1p_lattice_cfg* cfg, int E, bool device_goals, bool need_outputs_ok) {
+// tracks: a track plan (f1p_lattice_*_tracks_*) reads the track set instead of the raceline
+static int validate_lattice(f1p_ctx* ctx, const f1p_lattice_cfg* cfg, int E, bool device_goals, bool need_outputs_ok, bool tracks = false) {
     if (!cfg) return set_error(ctx, F1P_EINVAL, "cfg is NULL");
     if (E < 0) return set_error(ctx, F1P_EINVAL, "E must be >= 0");
     if (!need_outputs_ok) return set_error(ctx, F1P_EINVAL, "steer, speed and best_idx outputs are required");
@@ -201,6 +202,12 @@ static int validate_lattice(f1p_ctx* ctx, const f1p_lattice_cfg* cfg, int E, boo
     if (cfg->cand_begin < 0 || cfg->cand_count < 0 || cfg->cand_begin + cfg->cand_count > C || (cfg->cand_count == 0 && cfg->cand_begin != 0))
         return set_error(ctx, F1P_EINVAL, "candidate shard [cand_begin, cand_begin+cand_count) outside [0, C)");
     if (cfg->generator != F1P_GEN_CLOTHOID && cfg->generator != F1P_GEN_CUBIC) return set_error(ctx, F1P_EINVAL, "unknown trajectory generator");
+    if (tracks) {
+        if (ctx->trk_K < 1) return set_error(ctx, F1P_ESTATE, "no track set: call f1p_set_track_set first");
+        if (device_goals && !ctx->trk_has_psi) return set_error(ctx, F1P_ESTATE, "device goal sampling needs a heading column in the track set (col_psi >= 0)");
+        if (cfg->cand_count > 0) return set_error(ctx, F1P_EINVAL, "track plans take whole egos: cfg.cand_count must be 0");
+        return F1P_OK;
+    }
     if (ctx->n_wp < 2) return set_error(ctx, F1P_ESTATE, "waypoints not set: call f1p_set_waypoints first");
     if (device_goals && !ctx->has_psi) return set_error(ctx, F1P_ESTATE, "device goal sampling needs a heading column (col_psi >= 0)");
     return F1P_OK;
@@ -933,30 +940,33 @@ static int lattice_plan_dev_impl(f1p_ctx* ctx, const double* d_poses, const doub
                                  int32_t E, const f1p_lattice_cfg* cfg, double* d_steer, double* d_speed,
                                  int32_t* d_best_idx, double* d_best_cost, int32_t* d_status, int32_t* d_near_idx,
                                  double* d_best_traj, double* d_all_cost, double* d_all_traj, float* d_best_traj32, double* d_theta_out = nullptr,
-                                 double* d_pose_copy = nullptr) {
-    int rc = validate_lattice(ctx, cfg, E, d_goals == nullptr, E == 0 || (d_poses && d_best_idx && (cfg && cfg->cand_count > 0 ? true : (d_steer && d_speed))));
+                                 double* d_pose_copy = nullptr, const int32_t* d_track_id = nullptr, bool tracks = false) {
+    int rc = validate_lattice(ctx, cfg, E, d_goals == nullptr, E == 0 || (d_poses && d_best_idx && (cfg && cfg->cand_count > 0 ? true : (d_steer && d_speed))), tracks);
     if (rc) return rc;
+    if (tracks && E > 0 && !d_track_id) return set_error(ctx, F1P_EINVAL, "track_id is NULL");
     // a candidate shard evaluates only (cost + index); the emit half runs after the cross-rank argmin
     const int mode = cfg->cand_count > 0 ? LATTICE_EVAL : LATTICE_FULL;
     return launch_lattice(ctx, mode, d_poses, d_goals, d_prev_theta, E, cfg, nullptr, nullptr, d_steer, d_speed, d_best_idx,
-                          d_best_cost, d_status, d_near_idx, d_best_traj, d_all_cost, d_all_traj, d_best_traj32, d_theta_out, d_pose_copy);
+                          d_best_cost, d_status, d_near_idx, d_best_traj, d_all_cost, d_all_traj, d_best_traj32, d_theta_out, d_pose_copy, d_track_id);
 }
 
 // the *_dev entry points in closed-loop mode: prev_theta == NULL means "the headings the previous plan left on the device"
 static int lattice_plan_dev_cl(f1p_ctx* ctx, const double* d_poses, const double* d_goals, const double* d_prev_theta,
                                int32_t E, const f1p_lattice_cfg* cfg, double* d_steer, double* d_speed,
                                int32_t* d_best_idx, double* d_best_cost, int32_t* d_status, int32_t* d_near_idx,
-                               double* d_best_traj, double* d_all_cost, double* d_all_traj, float* d_best_traj32) {
+                               double* d_best_traj, double* d_all_cost, double* d_all_traj, float* d_best_traj32,
+                               const int32_t* d_track_id = nullptr, bool tracks = false) {
     ClosedLoop cl;
     // the configuration is validated BEFORE cl_begin touches the kept headings (an invalid cfg -- a huge n_stations -- used to free
     // them and fail in hipMalloc instead of returning F1P_EINVAL); lattice_plan_dev_impl validates again, with the output pointers
-    if (const int rcv = validate_lattice(ctx, cfg, E, d_goals == nullptr, true)) return rcv;
+    if (const int rcv = validate_lattice(ctx, cfg, E, d_goals == nullptr, true, tracks)) return rcv;
+    if (tracks && E > 0 && !d_track_id) return set_error(ctx, F1P_EINVAL, "track_id is NULL");
     if (cfg && E > 0 && cfg->n_stations >= 2) {
         const int rc0 = cl_begin(ctx, d_prev_theta, E, cfg->n_stations, cfg->cand_count == 0, &cl);
         if (rc0) return rc0;
     } else cl.prev = d_prev_theta;
     const int rc = lattice_plan_dev_impl(ctx, d_poses, d_goals, cl.prev, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost, d_status, d_near_idx,
-                                         d_best_traj, d_all_cost, d_all_traj, d_best_traj32, cl.out);
+                                         d_best_traj, d_all_cost, d_all_traj, d_best_traj32, cl.out, nullptr, d_track_id, tracks);
     if (rc == F1P_OK) cl_commit(ctx, cl, E, cfg->n_stations);
     return rc;
 }
@@ -976,6 +986,15 @@ int f1p_lattice_plan_dev_f32(f1p_ctx* ctx, const double* d_poses, const double* 
     F1P_ENTER(ctx);
     return lattice_plan_dev_cl(ctx, d_poses, d_goals, d_prev_theta, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost, d_status, d_near_idx,
                                nullptr, nullptr, nullptr, d_best_traj32);
+}
+
+int f1p_lattice_plan_tracks_dev(f1p_ctx* ctx, const double* d_poses, const double* d_goals, const double* d_prev_theta, const int32_t* d_track_id,
+                                int32_t E, const f1p_lattice_cfg* cfg, double* d_steer, double* d_speed,
+                                int32_t* d_best_idx, double* d_best_cost, int32_t* d_status, int32_t* d_near_idx,
+                                double* d_best_traj, double* d_all_cost, double* d_all_traj) {
+    F1P_ENTER(ctx);
+    return lattice_plan_dev_cl(ctx, d_poses, d_goals, d_prev_theta, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost, d_status, d_near_idx,
+                               d_best_traj, d_all_cost, d_all_traj, nullptr, d_track_id, true);
 }
 
 int f1p_lattice_emit_dev(f1p_ctx* ctx, const double* d_poses, const double* d_goals, int32_t E,
@@ -1011,14 +1030,16 @@ int f1p_lattice_closed_loop_state(f1p_ctx* ctx, const double** d_prev_theta, int
 
 // TRAJ = double (the reference's fp64 rows) or float (f1p_lattice_plan_batch_f32: the same rows rounded once on the device)
 extern "C++" {
+// tracks: a track plan, ego e on track track_id[e] (host array; every slice passes its own part of it)
 template <typename TRAJ>
 static int lattice_plan_batch_impl(f1p_ctx* ctx, const double* poses, const double* goals, const double* prev_theta,
                                    int32_t E, const f1p_lattice_cfg* cfg, double* steer, double* speed, int32_t* best_idx,
                                    double* best_cost, int32_t* status, int32_t* near_idx, TRAJ* best_traj,
-                                   double* all_cost, double* all_traj) {
+                                   double* all_cost, double* all_traj, const int32_t* track_id = nullptr, bool tracks = false) {
     constexpr bool F32 = sizeof(TRAJ) == 4;
-    int rc = validate_lattice(ctx, cfg, E, goals == nullptr, E == 0 || (poses && best_idx && ((cfg && cfg->cand_count > 0) || (steer && speed))));
+    int rc = validate_lattice(ctx, cfg, E, goals == nullptr, E == 0 || (poses && best_idx && ((cfg && cfg->cand_count > 0) || (steer && speed))), tracks);
     if (rc) return rc;
+    if (tracks && E > 0 && !track_id) return set_error(ctx, F1P_EINVAL, "track_id is NULL");
     if (cfg->cand_count > 0 && (steer || speed || status || best_traj))
         return set_error(ctx, F1P_EINVAL, "a candidate shard (cfg.cand_count > 0) only evaluates: it produces best_idx, best_cost and near_idx; "
                                           "pass NULL for steer / speed / status / best_traj and emit the global winner with f1p_lattice_emit_dev");
@@ -1044,23 +1065,28 @@ static int lattice_plan_batch_impl(f1p_ctx* ctx, const double* poses, const doub
         zn = near_idx ? (int32_t*)pinned_device_ptr(ctx, near_idx, 4 * e) : nullptr;
         zc_io = zp && zs && zv && zi && (!best_cost || zc_) && (!status || zt) && (!near_idx || zn);
     }
+    // track ids: read in place when page-locked, else staged like the poses
+    const int32_t* ztid = (zc_io && tracks) ? (const int32_t*)pinned_device_ptr(ctx, track_id, 4 * e) : nullptr;
     Stage s(ctx);
     if (zc_io) {
         s.need(8 * 4 * e);                                      // the device copy of the poses
+        s.need(4 * e, tracks && !ztid);
         if ((rc = s.begin())) return rc;
         double* d_pose_copy = (double*)arena_take(ctx, 8 * 4 * e);
+        if (tracks && !ztid && (rc = s.in(track_id, e, &ztid))) return rc;
         ClosedLoop cl;
         if ((rc = cl_begin(ctx, nullptr, E, (int)S, true, &cl))) return rc;
         struct HostDst { f1p_ctx* c; ~HostDst() { c->traj_dst_host = false; } } host_dst{ctx};
         ctx->traj_dst_host = best_traj != nullptr;
         double* bt64 = nullptr; float* bt32 = nullptr;
         if (best_traj) { if (F32) bt32 = reinterpret_cast<float*>(bt_dev); else bt64 = reinterpret_cast<double*>(bt_dev); }
-        if ((rc = lattice_plan_dev_impl(ctx, zp, nullptr, cl.prev, E, cfg, zs, zv, zi, zc_, zt, zn, bt64, nullptr, nullptr, bt32, cl.out, d_pose_copy))) return rc;
+        if ((rc = lattice_plan_dev_impl(ctx, zp, nullptr, cl.prev, E, cfg, zs, zv, zi, zc_, zt, zn, bt64, nullptr, nullptr, bt32, cl.out, d_pose_copy, ztid, tracks)))
+            return rc;
         cl_commit(ctx, cl, E, (int)S);
         F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return F1P_OK;
     }
-    s.need(8 * 4 * e); s.need(8 * e * C * 3, goals); s.need(8 * e * S, prev_theta);
+    s.need(8 * 4 * e); s.need(8 * e * C * 3, goals); s.need(8 * e * S, prev_theta); s.need(4 * e, tracks);
     s.need(8 * e, steer); s.need(8 * e, speed); s.need(4 * e); s.need(8 * e, best_cost); s.need(4 * e, status); s.need(4 * e, near_idx);
     s.need(sizeof(TRAJ) * e * S * 4, best_traj && !zero_copy_traj); s.need(8 * e * C, all_cost); s.need(8 * e * C * S * 4, all_traj);
     if ((rc = s.begin())) return rc;
@@ -1068,6 +1094,8 @@ static int lattice_plan_batch_impl(f1p_ctx* ctx, const double* poses, const doub
     if ((rc = s.in(poses, 4 * e, &d_poses))) return rc;
     if ((rc = s.in(goals, e * C * 3, &d_goals))) return rc;
     if ((rc = s.in(prev_theta, e * S, &d_prev))) return rc;
+    const int32_t* d_tid = nullptr;
+    if (tracks && (rc = s.in(track_id, e, &d_tid))) return rc;
     ClosedLoop cl;                                             // closed-loop mode: prev_theta == NULL = the headings the previous plan left on the device
     if (E > 0 && (rc = cl_begin(ctx, d_prev, E, (int)S, cfg->cand_count == 0, &cl))) return rc;
     d_prev = cl.prev;
@@ -1090,7 +1118,7 @@ static int lattice_plan_batch_impl(f1p_ctx* ctx, const double* poses, const doub
         return lattice_plan_dev_impl(ctx, d_poses + 4 * e0, d_goals ? d_goals + e0 * C * 3 : nullptr, d_prev ? d_prev + e0 * S : nullptr,
                                      (int32_t)n, cfg, d_steer ? d_steer + e0 : nullptr, d_speed ? d_speed + e0 : nullptr, d_bi + e0, d_bc ? d_bc + e0 : nullptr,
                                      d_st ? d_st + e0 : nullptr, d_ni ? d_ni + e0 : nullptr, bt64, e0 == 0 && n == e ? d_ac : nullptr,
-                                     e0 == 0 && n == e ? d_at : nullptr, bt32, cl.out ? cl.out + e0 * S : nullptr);
+                                     e0 == 0 && n == e ? d_at : nullptr, bt32, cl.out ? cl.out + e0 * S : nullptr, nullptr, d_tid ? d_tid + e0 : nullptr, tracks);
     };
     const int K = (pinned && E >= 8192) ? (E / 4096 < F1P_PLAN_CHUNKS_MAX ? E / 4096 : F1P_PLAN_CHUNKS_MAX) : 1;
     if (K > 1 && (rc = ensure_copy_stream(ctx))) return rc;
@@ -1128,6 +1156,23 @@ int f1p_lattice_plan_batch_f32(f1p_ctx* ctx, const double* poses, const double* 
     return lattice_plan_batch_impl<float>(ctx, poses, goals, prev_theta, E, cfg, steer, speed, best_idx, best_cost, status, near_idx, best_traj32, nullptr, nullptr);
 }
 
+int f1p_lattice_plan_tracks_batch(f1p_ctx* ctx, const double* poses, const double* goals, const double* prev_theta, const int32_t* track_id,
+                                  int32_t E, const f1p_lattice_cfg* cfg, double* steer, double* speed, int32_t* best_idx,
+                                  double* best_cost, int32_t* status, int32_t* near_idx, double* best_traj,
+                                  double* all_cost, double* all_traj) {
+    F1P_ENTER(ctx);
+    return lattice_plan_batch_impl<double>(ctx, poses, goals, prev_theta, E, cfg, steer, speed, best_idx, best_cost, status, near_idx, best_traj, all_cost, all_traj,
+                                           track_id, true);
+}
+
+int f1p_lattice_plan_tracks_batch_f32(f1p_ctx* ctx, const double* poses, const double* goals, const double* prev_theta, const int32_t* track_id,
+                                      int32_t E, const f1p_lattice_cfg* cfg, double* steer, double* speed, int32_t* best_idx,
+                                      double* best_cost, int32_t* status, int32_t* near_idx, float* best_traj32) {
+    F1P_ENTER(ctx);
+    return lattice_plan_batch_impl<float>(ctx, poses, goals, prev_theta, E, cfg, steer, speed, best_idx, best_cost, status, near_idx, best_traj32, nullptr, nullptr,
+                                          track_id, true);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // One closed-loop control step: poses in, (steer, speed, status) out, nothing else across PCIe.  No copy is submitted in either
 // direction: k_lattice_prologue reads the poses straight out of page-locked host memory (one 32-byte read per ego-wave, hidden by
@@ -1158,12 +1203,13 @@ static int ensure_step(f1p_ctx* ctx, int E, int S, bool keep_traj) {
     return F1P_OK;
 }
 
-int f1p_lattice_step_batch(f1p_ctx* ctx, const double* poses, int32_t E, const f1p_lattice_cfg* cfg, double* steer, double* speed,
-                           int32_t* status, int32_t keep_traj) {
-    F1P_ENTER(ctx);
-    int rc = validate_lattice(ctx, cfg, E, true, E == 0 || (poses && steer && speed));
+// tracks: f1p_lattice_step_tracks_batch, ego e on track track_id[e] (host array)
+static int lattice_step_impl(f1p_ctx* ctx, const double* poses, int32_t E, const f1p_lattice_cfg* cfg, double* steer, double* speed,
+                             int32_t* status, int32_t keep_traj, const int32_t* track_id, bool tracks) {
+    int rc = validate_lattice(ctx, cfg, E, true, E == 0 || (poses && steer && speed), tracks);
     if (rc) return rc;
     if (cfg->cand_count > 0) return set_error(ctx, F1P_EINVAL, "f1p_lattice_step_batch plans whole egos: cfg.cand_count must be 0");
+    if (tracks && E > 0 && !track_id) return set_error(ctx, F1P_EINVAL, "track_id is NULL");
     if (E == 0) return F1P_OK;
     const int S = cfg->n_stations;
     const size_t e = (size_t)E;
@@ -1184,6 +1230,14 @@ int f1p_lattice_step_batch(f1p_ctx* ctx, const double* poses, int32_t E, const f
     if (own_speed) k_speed = (double*)pinned_device_ptr(ctx, h_speed, 8 * e);
     if (own_status) k_status = (int32_t*)pinned_device_ptr(ctx, h_status, 4 * e);
     if (!k_poses || !k_steer || !k_speed || (status && !k_status)) return set_error(ctx, F1P_ESTATE, "page-locked step block is not device-visible");
+    // track ids: read in place when page-locked, else one copy into the arena
+    const int32_t* k_tid = tracks ? (const int32_t*)pinned_device_ptr(ctx, track_id, 4 * e) : nullptr;
+    if (tracks && !k_tid) {
+        if ((rc = arena_reset(ctx, al256(4 * e)))) return rc;
+        int32_t* d = (int32_t*)arena_take(ctx, 4 * e);
+        F1P_HIP(ctx, hipMemcpyAsync(d, track_id, 4 * e, hipMemcpyHostToDevice, ctx->stream));
+        k_tid = d;
+    }
     // a step IS a link of a closed loop -- for the duration of the step.  The mode the caller set with f1p_lattice_set_closed_loop is restored
     // afterwards (the step used to arm it for good, and a later f1p_lattice_plan_* with prev_theta == NULL and the same batch shape
     // silently picked up -- and overwrote -- the step chain's headings).  The chain's headings stay in the context between steps.
@@ -1194,7 +1248,7 @@ int f1p_lattice_step_batch(f1p_ctx* ctx, const double* poses, int32_t E, const f
     rc = cl_begin(ctx, nullptr, E, S, true, &cl);
     if (rc == F1P_OK)
         rc = launch_lattice(ctx, LATTICE_FULL, k_poses, nullptr, cl.prev, E, cfg, nullptr, nullptr, k_steer, k_speed, d_idx, nullptr, k_status, d_near,
-                            d_traj, nullptr, nullptr, nullptr, cl.out, d_pose_copy);
+                            d_traj, nullptr, nullptr, nullptr, cl.out, d_pose_copy, k_tid);
     ctx->lattice_closed_loop = was_armed;
     if (rc) return rc;
     cl_commit(ctx, cl, E, S);
@@ -1205,6 +1259,18 @@ int f1p_lattice_step_batch(f1p_ctx* ctx, const double* poses, int32_t E, const f
     if (own_speed) memcpy(speed, h_speed, 8 * e);
     if (own_status) memcpy(status, h_status, 4 * e);
     return F1P_OK;
+}
+
+int f1p_lattice_step_batch(f1p_ctx* ctx, const double* poses, int32_t E, const f1p_lattice_cfg* cfg, double* steer, double* speed,
+                           int32_t* status, int32_t keep_traj) {
+    F1P_ENTER(ctx);
+    return lattice_step_impl(ctx, poses, E, cfg, steer, speed, status, keep_traj, nullptr, false);
+}
+
+int f1p_lattice_step_tracks_batch(f1p_ctx* ctx, const double* poses, const int32_t* track_id, int32_t E, const f1p_lattice_cfg* cfg, double* steer,
+                                  double* speed, int32_t* status, int32_t keep_traj) {
+    F1P_ENTER(ctx);
+    return lattice_step_impl(ctx, poses, E, cfg, steer, speed, status, keep_traj, track_id, true);
 }
 
 int f1p_lattice_fetch_traj(f1p_ctx* ctx, double* best_traj, int32_t E, int32_t S) {

@@ -203,7 +203,8 @@ int launch_lattice(f1p_ctx* ctx, int mode, const double* d_poses, const double* 
                    double* d_steer, double* d_speed, int32_t* d_best_idx, double* d_best_cost, int32_t* d_status,
                    int32_t* d_near_idx, double* d_best_traj, double* d_all_cost, double* d_all_traj, float* d_best_traj32 = nullptr,
                    double* d_theta_out = nullptr,    // d_theta_out [E][S]: the winners' heading column (closed-loop mode), or null
-                   double* d_pose_copy = nullptr);   // d_poses is page-locked HOST memory: the first kernel leaves a device copy here for the others
+                   double* d_pose_copy = nullptr,    // d_poses is page-locked HOST memory: the first kernel leaves a device copy here for the others
+                   const int32_t* d_track_id = nullptr);   // [E] a track plan: ego e follows track d_track_id[e] of the context's track set
 int launch_clothoid_sample(f1p_ctx* ctx, const double* d_params, int n, int S, double* d_rows);
 int launch_clothoid_g1(f1p_ctx* ctx, const double* d_goals, int n, double* d_k0, double* d_dk, double* d_len, int32_t* d_ok);
 

@@ -64,7 +64,8 @@ __device__ __forceinline__ bool split_merge(const LatticeArgs& a, int e, int g, 
 // FOOT = oriented footprint (f1p_set_footprint): further instantiations, so the point-test kernels keep their register budget.
 // (round 6: the materialised clothoid instantiation with the footprint is held to TWO waves per SIMD -- at three it carried 23 spilled VGPRs / 104 B of scratch;
 // spill-free it is 1 % faster, tools/time_mat_footprint.py 0.2373 -> 0.2349 ms at 1024 egos.  The cubic one, 12 spills at three waves, measured 4 % SLOWER at two and stays.)
-template <bool STAGING, int GEN, bool PRUNE = false, bool FOOT = false>
+// TRK = a track plan (LatticeArgs::track_id): the workgroup's ego plans along its own track of the set; the other instantiations keep their code.
+template <bool STAGING, int GEN, bool PRUNE = false, bool FOOT = false, bool TRK = false>
 __global__ __launch_bounds__(256, (STAGING && GEN != F1P_GEN_CLOTHOID && !FOOT) ? F1P_K3_WAVES_STAGE2 : ((STAGING && FOOT && GEN == F1P_GEN_CLOTHOID) ? 2 : ((STAGING || FOOT) ? F1P_K3_WAVES_STAGE : F1P_K3_WAVES))) void k_lattice(LatticeArgs a, f1p_lattice_cfg cfg) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     // ---- LDS carve-up (all offsets multiples of 8) -------------------------------------------------
@@ -92,6 +93,16 @@ __global__ __launch_bounds__(256, (STAGING && GEN != F1P_GEN_CLOTHOID && !FOOT) 
     const int e = blockIdx.x / G, g = blockIdx.x - e * G;
     if (e >= a.E) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+    // r: the raceline of steps 1-2 -- the ego's track in a track plan (a copy of the arguments, bound again for the tracker below: nothing of the
+    // view stays live across the candidate loop)
+    LatticeArgs rt = a;
+    if constexpr (TRK) {
+        if (!lattice_bind_track(rt, e)) {                            // (workgroup-uniform: every slice of the ego leaves here, its merge ticket untouched)
+            if (g == 0) lattice_bad_track(a, cfg, e, tid, blockDim.x);
+            return;
+        }
+    }
+    const LatticeArgs& r = TRK ? rt : a;
     const int C = cfg.n_lookahead * cfg.n_width;
     int sc0 = cfg.cand_begin, sc1 = cfg.cand_count > 0 ? cfg.cand_begin + cfg.cand_count : C;
     if (G > 1) {
@@ -104,19 +115,19 @@ __global__ __launch_bounds__(256, (STAGING && GEN != F1P_GEN_CLOTHOID && !FOOT) 
 
     // ---- 1. nearest raceline segment (K1 logic) ------------------------------------------------------
     double nd; int ni;
-    nearest_scan_boxed(px, py, a.wx, a.wy, a.wbox, a.n, tid, blockDim.x, nd, ni);
+    nearest_scan_boxed(px, py, r.wx, r.wy, r.wbox, r.n, tid, blockDim.x, nd, ni);
     block_argmin(nd, ni, red_d, red_i);
-    const SegProj ns = seg_project(px, py, a.wx[ni], a.wy[ni], a.wx[ni + 1], a.wy[ni + 1]);
+    const SegProj ns = seg_project(px, py, r.wx[ni], r.wy[ni], r.wx[ni + 1], r.wy[ni + 1]);
 
     // ---- 2. look-ahead centres (K2 logic), one wave per look-ahead distance --------------------------
     if (!a.goals) {
         for (int l = wave; l < cfg.n_lookahead; l += nwaves) {
-            const Intersect it = wave_intersect(px, py, cfg.lookahead[l], a.wx, a.wy, a.n, (double)ni + ns.t, true);
+            const Intersect it = wave_intersect(px, py, cfg.lookahead[l], r.wx, r.wy, r.n, (double)ni + ns.t, true);
             if (lane == 0) {
                 cen_ok[l] = it.found ? 1 : 0;
                 if (it.found) {
-                    const int r = it.i < 0 ? it.i + a.n : it.i;
-                    cen_x[l] = a.wx[r]; cen_y[l] = a.wy[r]; cen_psi[l] = a.wpsi[r];   // waypoints[i2, [0,1,3]]
+                    const int i2 = it.i < 0 ? it.i + r.n : it.i;
+                    cen_x[l] = r.wx[i2]; cen_y[l] = r.wy[i2]; cen_psi[l] = r.wpsi[i2];   // waypoints[i2, [0,1,3]]
                 }
             }
         }
@@ -353,7 +364,12 @@ __global__ __launch_bounds__(256, (STAGING && GEN != F1P_GEN_CLOTHOID && !FOOT) 
             else cl = g1_fit(gx, gy, gth);
         }
     }
-    emit_and_track<GEN>(a, cfg, e, lane, ni, den, cl, bc, tr_x, tr_y, inc_x, inc_y);
+    if constexpr (TRK) {                               // the speed command: waypoints[ni, v] of the ego's track
+        LatticeArgs vt = a;
+        lattice_bind_track(vt, e);
+        const double v_near = vt.wv[ni];
+        emit_and_track<GEN>(a, cfg, e, lane, ni, den, cl, bc, tr_x, tr_y, inc_x, inc_y, nullptr, &v_near);
+    } else emit_and_track<GEN>(a, cfg, e, lane, ni, den, cl, bc, tr_x, tr_y, inc_x, inc_y);
 }
 
 // Second kernel of the two-kernel branch and bound: ONE WAVE PER EGO (4 egos per workgroup, no workgroup barriers) runs the
@@ -497,17 +513,84 @@ int launch_clothoid_sample(f1p_ctx* ctx, const double* d_params, int n, int S, d
     return check_hip(ctx, hipGetLastError(), "k_clothoid_sample launch");
 }
 
+// the all-fp64 kernel's launch (every instantiation the plan shape may take): TRK = a track plan
+template <bool TRK>
+static int launch_k_lattice(f1p_ctx* ctx, LatticeArgs& a, const f1p_lattice_cfg* cfg, int E, size_t lds, bool all_traj, bool all_cost, int mode,
+                            bool foot, bool cubic, bool prune, int n_cand) {
+    {
+        bool fits;
+        if (all_traj) fits = cubic ? lds_fits(ctx, k_lattice<true, F1P_GEN_CUBIC, false, false, TRK>, lds) : lds_fits(ctx, k_lattice<true, F1P_GEN_CLOTHOID, false, false, TRK>, lds);
+        else if (cubic) fits = lds_fits(ctx, k_lattice<false, F1P_GEN_CUBIC, false, false, TRK>, lds);
+        else if (prune) fits = lds_fits(ctx, k_lattice<false, F1P_GEN_CLOTHOID, true, false, TRK>, lds);
+        else fits = lds_fits(ctx, k_lattice<false, F1P_GEN_CLOTHOID, false, false, TRK>, lds);
+        if (!fits)
+            return set_error(ctx, F1P_EINVAL, "n_stations / occupancy tile need " + std::to_string(lds) + " B of LDS per workgroup, more than this device offers (" +
+                                                  std::to_string((size_t)ctx->prop.maxSharedMemoryPerMultiProcessor) + " B): reduce n_stations");
+    }
+    // BASELINE configs[1] (one ego, 512 candidates): fewer egos than half the CUs and more candidates than one workgroup holds ->
+    // one workgroup per 256 candidates, merged by the last one to finish (split_merge)
+    unsigned grid = (unsigned)E;
+    {
+        const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+        int G = ctx->lattice_split > 0 ? ctx->lattice_split : ((2 * E < cus && n_cand > 256) ? (n_cand + 255) / 256 : 1);
+        if (G > 16) G = 16;
+        if (G > 1 && !all_traj && !all_cost && mode != LATTICE_EMIT && !cubic && !foot) {
+            // layout by CAPACITY (tickets [cap_E] | partials [cap_E][16][6]): a launch with another E must find the tickets where the
+            // previous launches left them zeroed, never on top of old partials
+            if (E > ctx->split_cap_E) {
+                F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                if (ctx->d_split_scratch) (void)hipFree(ctx->d_split_scratch);
+                ctx->d_split_scratch = nullptr; ctx->split_cap_E = 0;
+                const size_t cap = (size_t)E + ((size_t)E >> 1) + 64;
+                const size_t need = ((sizeof(unsigned int) * cap + 255) & ~(size_t)255) + sizeof(double) * 6 * cap * 16;
+                F1P_HIP(ctx, hipMalloc((void**)&ctx->d_split_scratch, need));
+                F1P_HIP(ctx, hipMemsetAsync(ctx->d_split_scratch, 0, need, ctx->stream));
+                ctx->split_cap_E = (int)cap;
+            }
+            a.split_g = G;
+            a.split_tickets = reinterpret_cast<unsigned int*>(ctx->d_split_scratch);
+            a.split_part = reinterpret_cast<double*>(ctx->d_split_scratch + ((sizeof(unsigned int) * (size_t)ctx->split_cap_E + 255) & ~(size_t)255));
+            grid = (unsigned)((size_t)E * G);
+        }
+    }
+    if (foot) {
+        if (all_traj) {
+            if (cubic) hipLaunchKernelGGL((k_lattice<true, F1P_GEN_CUBIC, false, true, TRK>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
+            else hipLaunchKernelGGL((k_lattice<true, F1P_GEN_CLOTHOID, false, true, TRK>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
+        } else {
+            if (cubic) hipLaunchKernelGGL((k_lattice<false, F1P_GEN_CUBIC, false, true, TRK>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
+            else hipLaunchKernelGGL((k_lattice<false, F1P_GEN_CLOTHOID, false, true, TRK>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
+        }
+    } else if (all_traj) {
+        if (cubic) hipLaunchKernelGGL((k_lattice<true, F1P_GEN_CUBIC, false, false, TRK>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
+        else hipLaunchKernelGGL((k_lattice<true, F1P_GEN_CLOTHOID, false, false, TRK>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
+    } else {
+        if (cubic) hipLaunchKernelGGL((k_lattice<false, F1P_GEN_CUBIC, false, false, TRK>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
+        else if (prune) hipLaunchKernelGGL((k_lattice<false, F1P_GEN_CLOTHOID, true, false, TRK>), dim3(grid), dim3(256), lds, ctx->stream, a, *cfg);
+        else hipLaunchKernelGGL((k_lattice<false, F1P_GEN_CLOTHOID, false, false, TRK>), dim3(grid), dim3(256), lds, ctx->stream, a, *cfg);
+    }
+    return check_hip(ctx, hipGetLastError(), TRK ? "k_lattice (tracks) launch" : "k_lattice launch");
+}
+
 int launch_lattice(f1p_ctx* ctx, int mode, const double* d_poses, const double* d_goals, const double* d_prev_theta,
                    int E, const f1p_lattice_cfg* cfg, const int32_t* d_emit_idx, const double* d_emit_cost,
                    double* d_steer, double* d_speed, int32_t* d_best_idx, double* d_best_cost, int32_t* d_status,
                    int32_t* d_near_idx, double* d_best_traj, double* d_all_cost, double* d_all_traj, float* d_best_traj32, double* d_theta_out,
-                   double* d_pose_copy) {
+                   double* d_pose_copy, const int32_t* d_track_id) {
     if (E <= 0) return F1P_OK;
     LatticeArgs a;
     a.theta_out = d_theta_out; a.pose_copy = nullptr; a.traj_in_hbm = ctx->traj_dst_host ? 0 : 1;
     a.poses = d_poses; a.goals = d_goals; a.prev_theta = d_prev_theta;
     a.E = E; a.mode = mode; a.e0 = 0;
     a.wx = ctx->d_wx; a.wy = ctx->d_wy; a.wv = ctx->d_wv; a.wpsi = ctx->d_wpsi; a.wbox = ctx->d_wbox; a.n = ctx->n_wp;
+    // a track plan: the raceline fields carry the track set's columns, each ego's kernel offsets them by its table entry (lattice_bind_track)
+    const bool tracks = d_track_id != nullptr;
+    a.track_id = d_track_id; a.track_tab = nullptr; a.track_K = 0;
+    if (tracks) {
+        const TrackSetDev ts = track_set_dev(ctx);
+        a.wx = ts.x; a.wy = ts.y; a.wv = ts.v; a.wpsi = ts.psi; a.wbox = ts.box; a.n = 0;
+        a.track_tab = ts.tab; a.track_K = ts.K;
+    }
     a.grid = grid_dev(ctx);
     a.has_grid = ctx->has_grid ? 1 : 0;
     a.emit_idx = d_emit_idx; a.emit_cost = d_emit_cost;
@@ -574,7 +657,8 @@ int launch_lattice(f1p_ctx* ctx, int mode, const double* d_poses, const double* 
     // the two-kernel schedule needs 4 per-wave LDS blocks in k_lattice_eval; a long station count that does not fit falls back to
     // the single-kernel branch and bound below
     const bool split_fits = lds_fits(ctx, k_lattice_eval, 4 * wl) && lds_fits(ctx, k_lattice<false, F1P_GEN_CLOTHOID, true>, lds);
-    if (prune && n_cand <= 256 && E >= F1P_BB_SPLIT_MIN_EGOS && split_fits) {
+    // (a track plan takes the single-kernel branch and bound: the same winners, bit for bit, without a track path in k_lattice_eval)
+    if (prune && n_cand <= 256 && E >= F1P_BB_SPLIT_MIN_EGOS && split_fits && !tracks) {
         // two kernels: fit + bound + sort with every wave busy, then one wave per ego for the station rounds
         const size_t need = (size_t)E * (256 * 8 + 256 * 32 + 4) + 64;
         if (need > ctx->bb_scratch_bytes) {
@@ -597,59 +681,8 @@ int launch_lattice(f1p_ctx* ctx, int mode, const double* d_poses, const double* 
         hipLaunchKernelGGL(k_lattice_eval, dim3((E + 3) / 4), dim3(256), 4 * wl, ctx->stream, a, *cfg);
         return check_hip(ctx, hipGetLastError(), "k_lattice_eval launch");
     }
-    {
-        bool fits;
-        if (d_all_traj) fits = cubic ? lds_fits(ctx, k_lattice<true, F1P_GEN_CUBIC>, lds) : lds_fits(ctx, k_lattice<true, F1P_GEN_CLOTHOID>, lds);
-        else if (cubic) fits = lds_fits(ctx, k_lattice<false, F1P_GEN_CUBIC>, lds);
-        else if (prune) fits = lds_fits(ctx, k_lattice<false, F1P_GEN_CLOTHOID, true>, lds);
-        else fits = lds_fits(ctx, k_lattice<false, F1P_GEN_CLOTHOID>, lds);
-        if (!fits)
-            return set_error(ctx, F1P_EINVAL, "n_stations / occupancy tile need " + std::to_string(lds) + " B of LDS per workgroup, more than this device offers (" +
-                                                  std::to_string((size_t)ctx->prop.maxSharedMemoryPerMultiProcessor) + " B): reduce n_stations");
-    }
-    // BASELINE configs[1] (one ego, 512 candidates): fewer egos than half the CUs and more candidates than one workgroup holds ->
-    // one workgroup per 256 candidates, merged by the last one to finish (split_merge)
-    unsigned grid = (unsigned)E;
-    {
-        const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-        int G = ctx->lattice_split > 0 ? ctx->lattice_split : ((2 * E < cus && n_cand > 256) ? (n_cand + 255) / 256 : 1);
-        if (G > 16) G = 16;
-        if (G > 1 && !d_all_traj && !d_all_cost && mode != LATTICE_EMIT && !cubic && !foot) {
-            // layout by CAPACITY (tickets [cap_E] | partials [cap_E][16][6]): a launch with another E must find the tickets where the
-            // previous launches left them zeroed, never on top of old partials
-            if (E > ctx->split_cap_E) {
-                F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                if (ctx->d_split_scratch) (void)hipFree(ctx->d_split_scratch);
-                ctx->d_split_scratch = nullptr; ctx->split_cap_E = 0;
-                const size_t cap = (size_t)E + ((size_t)E >> 1) + 64;
-                const size_t need = ((sizeof(unsigned int) * cap + 255) & ~(size_t)255) + sizeof(double) * 6 * cap * 16;
-                F1P_HIP(ctx, hipMalloc((void**)&ctx->d_split_scratch, need));
-                F1P_HIP(ctx, hipMemsetAsync(ctx->d_split_scratch, 0, need, ctx->stream));
-                ctx->split_cap_E = (int)cap;
-            }
-            a.split_g = G;
-            a.split_tickets = reinterpret_cast<unsigned int*>(ctx->d_split_scratch);
-            a.split_part = reinterpret_cast<double*>(ctx->d_split_scratch + ((sizeof(unsigned int) * (size_t)ctx->split_cap_E + 255) & ~(size_t)255));
-            grid = (unsigned)((size_t)E * G);
-        }
-    }
-    if (foot) {
-        if (d_all_traj) {
-            if (cubic) hipLaunchKernelGGL((k_lattice<true, F1P_GEN_CUBIC, false, true>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
-            else hipLaunchKernelGGL((k_lattice<true, F1P_GEN_CLOTHOID, false, true>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
-        } else {
-            if (cubic) hipLaunchKernelGGL((k_lattice<false, F1P_GEN_CUBIC, false, true>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
-            else hipLaunchKernelGGL((k_lattice<false, F1P_GEN_CLOTHOID, false, true>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
-        }
-    } else if (d_all_traj) {
-        if (cubic) hipLaunchKernelGGL((k_lattice<true, F1P_GEN_CUBIC>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
-        else hipLaunchKernelGGL((k_lattice<true, F1P_GEN_CLOTHOID>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
-    } else {
-        if (cubic) hipLaunchKernelGGL((k_lattice<false, F1P_GEN_CUBIC>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
-        else if (prune) hipLaunchKernelGGL((k_lattice<false, F1P_GEN_CLOTHOID, true>), dim3(grid), dim3(256), lds, ctx->stream, a, *cfg);
-        else hipLaunchKernelGGL((k_lattice<false, F1P_GEN_CLOTHOID>), dim3(grid), dim3(256), lds, ctx->stream, a, *cfg);
-    }
-    return check_hip(ctx, hipGetLastError(), "k_lattice launch");
+    return tracks ? launch_k_lattice<true>(ctx, a, cfg, E, lds, d_all_traj != nullptr, d_all_cost != nullptr, mode, foot, cubic, prune, n_cand)
+                  : launch_k_lattice<false>(ctx, a, cfg, E, lds, d_all_traj != nullptr, d_all_cost != nullptr, mode, foot, cubic, prune, n_cand);
 }
 
 int launch_clothoid_g1(f1p_ctx* ctx, const double* d_goals, int n, double* d_k0, double* d_dk, double* d_len, int32_t* d_ok) {

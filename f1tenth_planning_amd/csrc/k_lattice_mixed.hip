@@ -35,7 +35,7 @@ __global__ void k_lattice_audit_compare(int n, int S, const double* steer, const
     if (i == 0) { atomicAdd(&counters[0], 1ull); atomicAdd(&counters[1], (unsigned long long)n); }
 }
 
-static int lattice_audit(f1p_ctx* ctx, const double* d_poses, const double* d_prev_theta, int E, const f1p_lattice_cfg* cfg,
+static int lattice_audit(f1p_ctx* ctx, const double* d_poses, const double* d_prev_theta, const int32_t* d_track_id, int E, const f1p_lattice_cfg* cfg,
                          double* d_steer, double* d_speed, int32_t* d_best_idx, double* d_best_cost, int32_t* d_status,
                          int32_t* d_near_idx, double* d_best_traj, float* d_best_traj32) {
     const int n = ctx->audit_egos < E ? ctx->audit_egos : E;
@@ -66,7 +66,8 @@ static int lattice_audit(f1p_ctx* ctx, const double* d_poses, const double* d_pr
     const int mixed = ctx->lattice_mixed;
     ctx->lattice_mixed = 0; ctx->auditing = true;
     const int rc = launch_lattice(ctx, LATTICE_FULL, d_poses + 4 * (size_t)w0, nullptr, d_prev_theta ? d_prev_theta + (size_t)w0 * S : nullptr, n, &ref_cfg,
-                                  nullptr, nullptr, r_steer, r_speed, r_idx, r_cost, r_status, r_near, r_traj, nullptr, nullptr, nullptr);
+                                  nullptr, nullptr, r_steer, r_speed, r_idx, r_cost, r_status, r_near, r_traj, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  d_track_id ? d_track_id + w0 : nullptr);   // (a track plan's window: re-planned with the same track ids)
     ctx->lattice_mixed = mixed; ctx->auditing = false;
     if (rc) return rc;
     hipLaunchKernelGGL(k_lattice_audit_compare, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, S,
@@ -138,7 +139,8 @@ int launch_lattice_mixed(f1p_ctx* ctx, LatticeArgs& a, const f1p_lattice_cfg* cf
         // filter and the selection kernel and leave the queue counter armed)
         const bool groups16 = mixed_refine_fits(ctx, 16, foot, lds_r16 + lds_r_static);
         const bool refine_fits = groups16 || mixed_refine_fits(ctx, 64, foot, lds_r64 + lds_r_static);
-        if (refine_fits && mixed_select_fits(ctx, false, lds_s)) {
+        const bool tracks = a.track_id != nullptr;
+        if (refine_fits && mixed_select_fits(ctx, false, lds_s, tracks)) {
             MixArgs mx;
             mx.margin_rel = F1P_MIX_MARGIN_REL; mx.margin_abs = F1P_MIX_MARGIN_ABS; mx.edge0 = F1P_MIX_EDGE0; mx.edge1 = F1P_MIX_EDGE1;
             if (ctx->dbg_margins) { mx.margin_rel = ctx->dbg_margin_rel; mx.margin_abs = ctx->dbg_margin_abs; }   // test hook (f1p_lattice_debug_margins)
@@ -173,7 +175,7 @@ int launch_lattice_mixed(f1p_ctx* ctx, LatticeArgs& a, const f1p_lattice_cfg* cf
             const int cr = mx.clear_r == 2 ? 2 : 1;
             // (every instantiation the plan shape may launch: checked -- and configured for > 64 KB of dynamic LDS -- in the kernels' own translation units)
             bool v3 = mixed_filter3_fits(ctx, cr, mx.n_disc > 0, cubic, lds_f3);
-            if (cubic) v3 = v3 && S <= 256 && mixed_refine_cubic_fits(ctx, lds_rc) && mixed_select_fits(ctx, true, lds_s);
+            if (cubic) v3 = v3 && S <= 256 && mixed_refine_cubic_fits(ctx, lds_rc) && mixed_select_fits(ctx, true, lds_s, tracks);
             if (!v3) return F1P_OK;                                  // (not handled: the all-fp64 kernel takes the plan)
             // ---- pipeline: the batch in chunks of egos, chunk k on internal stream k % 2, the second stream one stage behind the
             // first (it waits for the first prologue): one chunk's latency-bound kernels (prologue, refinement, selection: a few waves
@@ -283,7 +285,7 @@ int launch_lattice_mixed(f1p_ctx* ctx, LatticeArgs& a, const f1p_lattice_cfg* cf
                     // 10.9 against 11.9 us, 2048: 11.6 / 11.9, 4096: 15.4 / 14.3, 8192: 23.3 / 18.9; f1p_lattice_set_mode(2) takes the two-ego kernel at any size)
                     const bool pro2 = F1P_PRO2 && ctx->lattice_mixed != 3 && cfg->n_lookahead <= 32 && ak.wbox != nullptr && (Ek >= F1P_PRO2_MIN_EGOS || ctx->lattice_mixed == 2);
 #endif
-                    mixed_launch_prologue(pro2, Ek, st, ak, *cfg, mk, (unsigned char*)ctx->d_rec_scratch);
+                    mixed_launch_prologue(pro2, tracks, Ek, st, ak, *cfg, mk, (unsigned char*)ctx->d_rec_scratch);
                     if (d_pose_copy) { ak.poses = d_pose_copy; ak.pose_copy = nullptr; }      // the kernels behind the prologue read HBM
                     if (prof) F1P_HIP(ctx, hipEventRecord(ctx->ev_prof[1], st));
                     if (nch > 1 && k == 0) {                         // the side stream starts one stage behind (and after everything the caller enqueued before this plan)
@@ -307,7 +309,7 @@ int launch_lattice_mixed(f1p_ctx* ctx, LatticeArgs& a, const f1p_lattice_cfg* cf
                 mixed_launch_refine(cubic, groups16 ? 16 : 64, mk.n_disc > 0, (unsigned)rb, cubic ? lds_rc : (groups16 ? lds_r16 : lds_r64), st, ak, *cfg, mk);
                 if ((rc = check_hip(ctx, hipGetLastError(), "k_lattice_refine launch"))) break;
                 if (prof) F1P_HIP(ctx, hipEventRecord(ctx->ev_prof[3], st));
-                mixed_launch_select(cubic, (unsigned)((Ek + 3) / 4 + (mk.perm_fill ? (Ek + 255) / 256 : 0)), lds_s, st, ak, *cfg, mk);
+                mixed_launch_select(cubic, tracks, (unsigned)((Ek + 3) / 4 + (mk.perm_fill ? (Ek + 255) / 256 : 0)), lds_s, st, ak, *cfg, mk);
                 rc = check_hip(ctx, hipGetLastError(), "k_lattice_select launch");
                 if (mk.perm_fill) ctx->order_valid = rc == F1P_OK;
             }
@@ -320,7 +322,8 @@ int launch_lattice_mixed(f1p_ctx* ctx, LatticeArgs& a, const f1p_lattice_cfg* cf
             // runtime audit (f1p_lattice_set_audit): this plan's outputs on a window of egos against the all-fp64 exhaustive kernel
             if (rc == F1P_OK && ctx->audit_every > 0 && !ctx->auditing && mode == LATTICE_FULL && !a.goals && cfg->cand_count == 0) {
                 if (ctx->audit_plans++ % (unsigned long long)ctx->audit_every == 0)
-                    rc = lattice_audit(ctx, d_poses, d_prev_theta, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost, d_status, d_near_idx, d_best_traj, d_best_traj32);
+                    rc = lattice_audit(ctx, d_poses, d_prev_theta, a.track_id, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost, d_status, d_near_idx, d_best_traj,
+                                       d_best_traj32);
             }
             *handled = true;
             return rc;

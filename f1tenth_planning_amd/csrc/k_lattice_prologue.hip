@@ -324,6 +324,9 @@ __device__ __forceinline__ void ego_record_write(const LatticeArgs& a, const f1p
 // round, the kernel 87 us).  As two kernels the prologue is executed by one wave per ego at four waves per SIMD (latency hidden
 // by occupancy), and the candidate kernel is uniform VALU work.
 // ===================================================================================================================
+// TRK = a track plan (LatticeArgs::track_id): the wave's ego reads its own track of the set.  An ego whose id is outside [0, K) reads nothing of
+// it and gets a record without goals (device goals) and nearest segment 0; k_lattice_select writes its outputs.
+template <bool TRK = false>
 __global__ __launch_bounds__(256) void k_lattice_prologue(LatticeArgs a, f1p_lattice_cfg cfg, MixArgs mx, unsigned char* __restrict__ recs) {
     __shared__ double s_cen[4][3 * F1P_MAX_LOOKAHEADS];
     __shared__ int s_ok[4][F1P_MAX_LOOKAHEADS];
@@ -333,6 +336,8 @@ __global__ __launch_bounds__(256) void k_lattice_prologue(LatticeArgs a, f1p_lat
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int e = a.e0 + blockIdx.x * 4 + wave;
     if (e >= a.E) return;                                        // wave-uniform
+    bool bad = false;                                            // (wave-uniform; false but in the track instantiation)
+    if constexpr (TRK) bad = !lattice_bind_track(a, e);
     const int nl = cfg.n_lookahead, S = cfg.n_stations;
     double* cen_x = s_cen[wave]; double* cen_y = cen_x + F1P_MAX_LOOKAHEADS; double* cen_psi = cen_y + F1P_MAX_LOOKAHEADS;
     int* cen_ok = s_ok[wave];
@@ -345,7 +350,7 @@ __global__ __launch_bounds__(256) void k_lattice_prologue(LatticeArgs a, f1p_lat
     F1P_PPH();
     // what the nearest-segment scan reads first (chunk boxes, sample waypoints) does not depend on the pose: requested together with it
     double scan_pre[6];
-    nearest_scan_preload(a.wx, a.wy, a.wbox, a.n, lane, scan_pre);
+    if (!bad) nearest_scan_preload(a.wx, a.wy, a.wbox, a.n, lane, scan_pre);
     const double px = a.poses[4 * e], py = a.poses[4 * e + 1], theta = a.poses[4 * e + 2];
     if (a.pose_copy && lane < 4) a.pose_copy[4 * e + lane] = a.poses[4 * e + lane];   // the poses came from host memory: HBM copy for the kernels behind this one
     // moments of the previous path's headings for the filter's closed-form similarity term (EgoParamsF2::M0..M2): the loads are
@@ -370,7 +375,8 @@ __global__ __launch_bounds__(256) void k_lattice_prologue(LatticeArgs a, f1p_lat
     // ---- nearest segment and look-ahead centres: the arithmetic of k_lattice (fp64: these decide indices), one wave ---------------
     double nd; int ni;
     double my_t = 0.0;
-    nearest_scan_boxed(px, py, a.wx, a.wy, a.wbox, a.n, lane, 64, nd, ni, &my_t, a.wbox ? scan_pre : nullptr);
+    if (!bad) nearest_scan_boxed(px, py, a.wx, a.wy, a.wbox, a.n, lane, 64, nd, ni, &my_t, a.wbox ? scan_pre : nullptr);
+    else { nd = 0.0; ni = 0; }
     F1P_PPH();
     // nearest_point's t of the winning segment: the lane that projected it still holds it (the same seg_project call, the same bits) --
     // round 3 loaded the segment again and projected a second time, a dependent round trip + ~60 fp64 instructions per ego
@@ -385,13 +391,14 @@ __global__ __launch_bounds__(256) void k_lattice_prologue(LatticeArgs a, f1p_lat
 #ifdef F1P_PRO_PHASES
     int lstat[4] = {0, 0, 0, 0};
     long long lat[5] = {0, 0, 0, 0, 0};
-    wave_lookahead_centres(px, py, cfg, a.wx, a.wy, a.wpsi, a.n, (double)ni + ns.t, 0, 1, cen_x, cen_y, cen_psi, cen_ok, s_first[wave], s_pairs[wave], nd, lstat, a.wbox, F1P_MAX_LOOKAHEADS, lat);
+    if (!bad) wave_lookahead_centres(px, py, cfg, a.wx, a.wy, a.wpsi, a.n, (double)ni + ns.t, 0, 1, cen_x, cen_y, cen_psi, cen_ok, s_first[wave], s_pairs[wave], nd, lstat, a.wbox, F1P_MAX_LOOKAHEADS, lat);
     if (lane == 0 && mx.dbg_cost32) for (int k = 0; k < 4; ++k) mx.dbg_cost32[(size_t)e * nl * cfg.n_width + 40 + k] = (float)lstat[k];
     if (lane == 0 && mx.dbg_cost32) for (int k = 0; k < 4; ++k) mx.dbg_cost32[(size_t)e * nl * cfg.n_width + 48 + k] = (float)(lat[k + 1] - lat[k]);
 #else
     // (host-supplied goals, round 5: no look-ahead pass -- the caller's [E][C][3] array IS the goal set; the candidate kernel reads it)
-    if (!a.goals) wave_lookahead_centres(px, py, cfg, a.wx, a.wy, a.wpsi, a.n, (double)ni + ns.t, 0, 1, cen_x, cen_y, cen_psi, cen_ok, s_first[wave], s_pairs[wave], nd, nullptr, a.wbox, F1P_MAX_LOOKAHEADS);
+    if (!a.goals && !bad) wave_lookahead_centres(px, py, cfg, a.wx, a.wy, a.wpsi, a.n, (double)ni + ns.t, 0, 1, cen_x, cen_y, cen_psi, cen_ok, s_first[wave], s_pairs[wave], nd, nullptr, a.wbox, F1P_MAX_LOOKAHEADS);
 #endif
+    if (bad && lane < nl) cen_ok[lane] = 0;                      // no goal: the filter queues nothing of this ego
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
     F1P_PPH();
@@ -849,9 +856,11 @@ __global__ __launch_bounds__(256) void k_lattice_prologue2(LatticeArgs a, f1p_la
 #undef F1P_LAT
 }
 
-void mixed_launch_prologue(bool two_per_wave, int egos, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx, unsigned char* recs) {
-    if (two_per_wave) hipLaunchKernelGGL(k_lattice_prologue2, dim3((egos + 7) / 8), dim3(256), 0, st, a, cfg, mx, recs);
-    else hipLaunchKernelGGL(k_lattice_prologue, dim3((egos + 3) / 4), dim3(256), 0, st, a, cfg, mx, recs);
+void mixed_launch_prologue(bool two_per_wave, bool tracks, int egos, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx,
+                           unsigned char* recs) {
+    if (tracks) hipLaunchKernelGGL(k_lattice_prologue<true>, dim3((egos + 3) / 4), dim3(256), 0, st, a, cfg, mx, recs);   // (one ego per wave at every size)
+    else if (two_per_wave) hipLaunchKernelGGL(k_lattice_prologue2, dim3((egos + 7) / 8), dim3(256), 0, st, a, cfg, mx, recs);
+    else hipLaunchKernelGGL(k_lattice_prologue<false>, dim3((egos + 3) / 4), dim3(256), 0, st, a, cfg, mx, recs);
 }
 
 }  // namespace f1p

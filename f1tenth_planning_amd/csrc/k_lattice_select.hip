@@ -5,7 +5,8 @@
 namespace f1p {
 
 // wave per ego: select() over the refined candidates, winner re-emission, tracking (the tail of k_lattice_eval)
-template <int GEN = F1P_GEN_CLOTHOID>
+// TRK = a track plan (LatticeArgs::track_id): the speed command is the ego's own track's; an id outside [0, K) gets the bad-track outputs
+template <int GEN = F1P_GEN_CLOTHOID, bool TRK = false>
 __global__ __launch_bounds__(256, 3) void k_lattice_select(LatticeArgs a, f1p_lattice_cfg cfg, MixArgs mx) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     warm_kernargs<sizeof(LatticeArgs) + sizeof(f1p_lattice_cfg) + sizeof(MixArgs)>();
@@ -23,6 +24,9 @@ __global__ __launch_bounds__(256, 3) void k_lattice_select(LatticeArgs a, f1p_la
     const int e = a.e0 + blockIdx.x * 4 + wave;
     if (blockIdx.x == 0 && tid < F1P_MIX_QSHARDS) mx.qcount[tid * 32u] = 0u;   // the refinement kernel is done with them: ready for the next plan
     if (e >= a.E) return;
+    if constexpr (TRK) {
+        if (!lattice_bind_track(a, e)) { lattice_bad_track(a, cfg, e, lane, 64); return; }   // (wave-uniform)
+    }
     const int S = cfg.n_stations;
     double* tr_x = reinterpret_cast<double*>(lds_raw) + (size_t)wave * 4 * S;
     double* tr_y = tr_x + S;
@@ -132,12 +136,16 @@ __global__ __launch_bounds__(256, 3) void k_lattice_select(LatticeArgs a, f1p_la
 }
 
 // ---- launch wrappers (host) --------------------------------------------------------------------------------------------------------------
-bool mixed_select_fits(f1p_ctx* ctx, bool cubic, size_t lds) {
+bool mixed_select_fits(f1p_ctx* ctx, bool cubic, size_t lds, bool tracks) {
+    if (tracks) return cubic ? lds_fits(ctx, k_lattice_select<F1P_GEN_CUBIC, true>, lds) : lds_fits(ctx, k_lattice_select<F1P_GEN_CLOTHOID, true>, lds);
     return cubic ? lds_fits(ctx, k_lattice_select<F1P_GEN_CUBIC>, lds) : lds_fits(ctx, k_lattice_select<F1P_GEN_CLOTHOID>, lds);
 }
 
-void mixed_launch_select(bool cubic, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx) {
-    if (cubic) hipLaunchKernelGGL(k_lattice_select<F1P_GEN_CUBIC>, dim3(grid), dim3(256), lds, st, a, cfg, mx);
+void mixed_launch_select(bool cubic, bool tracks, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx) {
+    if (tracks) {
+        if (cubic) hipLaunchKernelGGL((k_lattice_select<F1P_GEN_CUBIC, true>), dim3(grid), dim3(256), lds, st, a, cfg, mx);
+        else hipLaunchKernelGGL((k_lattice_select<F1P_GEN_CLOTHOID, true>), dim3(grid), dim3(256), lds, st, a, cfg, mx);
+    } else if (cubic) hipLaunchKernelGGL(k_lattice_select<F1P_GEN_CUBIC>, dim3(grid), dim3(256), lds, st, a, cfg, mx);
     else hipLaunchKernelGGL(k_lattice_select<F1P_GEN_CLOTHOID>, dim3(grid), dim3(256), lds, st, a, cfg, mx);
 }
 

@@ -15,26 +15,6 @@
 
 namespace f1p {
 
-// one track of the set, as the single-raceline kernels see the context's raceline
-struct TrackView {
-    const double *x, *y, *v, *psi, *kappa, *box;
-    int n, off;
-};
-
-// the track of ego e (every lane of the calling wave passes the same e): false for an id outside [0, K)
-__device__ __forceinline__ bool track_of(const TrackSetDev& ts, const int32_t* __restrict__ track_id, int e, TrackView& tv) {
-    const int k = __builtin_amdgcn_readfirstlane(track_id[e]);
-    if (k < 0 || k >= ts.K) return false;                   // wave-uniform
-    const int4 t = ts.tab[k];
-    const int off = __builtin_amdgcn_readfirstlane(t.x), n = __builtin_amdgcn_readfirstlane(t.y), bo = __builtin_amdgcn_readfirstlane(t.z);
-    tv.x = ts.x + off; tv.y = ts.y + off; tv.v = ts.v + off;
-    tv.psi = ts.psi ? ts.psi + off : nullptr;
-    tv.kappa = ts.kappa ? ts.kappa + off : nullptr;
-    tv.box = ts.box + 4 * (size_t)bo;
-    tv.n = n; tv.off = off;
-    return true;
-}
-
 // k_nearest over the track set: one wave per query, 4 queries per workgroup
 __global__ __launch_bounds__(256) void k_nearest_tracks(const double* __restrict__ pts, const int32_t* __restrict__ track_id, int E,
                                                         TrackSetDev ts, double* __restrict__ proj, double* __restrict__ dist,

@@ -243,7 +243,7 @@ __host__ __device__ inline size_t ego_rec_stride(int nl) { return (sizeof(EgoRec
 
 // ---- launch wrappers: every kernel family lives in its own translation unit and is reached through these (host) --------------------------------------
 // k_lattice_prologue.hip: two_per_wave = k_lattice_prologue2 (n_lookahead <= 32), else k_lattice_prologue
-void mixed_launch_prologue(bool two_per_wave, int egos, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx, unsigned char* recs);
+void mixed_launch_prologue(bool two_per_wave, bool tracks, int egos, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx, unsigned char* recs);
 // k_lattice_filter3.hip: cr = clearance mode (1 | 2), hooks = the instantiation with the test hooks; *_fits: every instantiation the plan shape may launch
 // fits the device's LDS (and is configured for > 64 KB where needed)
 bool mixed_filter3_fits(f1p_ctx* ctx, int cr, bool foot, bool cubic, size_t lds);
@@ -254,7 +254,7 @@ bool mixed_refine_fits(f1p_ctx* ctx, int lanes, bool foot, size_t lds);
 bool mixed_refine_cubic_fits(f1p_ctx* ctx, size_t lds);
 void mixed_launch_refine(bool cubic, int lanes, bool foot, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx);
 // k_lattice_select.hip
-bool mixed_select_fits(f1p_ctx* ctx, bool cubic, size_t lds);
-void mixed_launch_select(bool cubic, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx);
+bool mixed_select_fits(f1p_ctx* ctx, bool cubic, size_t lds, bool tracks = false);
+void mixed_launch_select(bool cubic, bool tracks, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx);
 
 }  // namespace f1p

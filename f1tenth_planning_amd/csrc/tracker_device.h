@@ -1,8 +1,9 @@
 // tracker_device.h -- device helpers of the waypoint trackers, shared by the single-raceline kernels (k_controllers.hip) and their
 // track-set twins (k_tracks.hip): the front-axle errors of Stanley / LQR and the LQR's Riccati iteration, moved here unchanged from
-// k_controllers.hip (whose ISA is the same as before the move), and the reference extraction of the kinematic MPC.
+// k_controllers.hip (whose ISA is the same as before the move), the reference extraction of the kinematic MPC, and the per-ego
+// track look-up of the track-set kernels (k_tracks.hip and the lattice planner's track plans).
 #pragma once
-#include "f1p_device.h"
+#include "f1p_internal.h"
 
 namespace f1p {
 
@@ -148,6 +149,26 @@ __device__ __forceinline__ void kmpc_ref_rows(double v, double yaw, int ind, int
         r[2 * (T + 1) + j] = wv[il];
         r[3 * (T + 1) + j] = cyw;
     }
+}
+
+// one track of the set, as the single-raceline kernels see the context's raceline
+struct TrackView {
+    const double *x, *y, *v, *psi, *kappa, *box;
+    int n, off;
+};
+
+// the track of ego e (every lane of the calling wave passes the same e): false for an id outside [0, K)
+__device__ __forceinline__ bool track_of(const TrackSetDev& ts, const int32_t* __restrict__ track_id, int e, TrackView& tv) {
+    const int k = __builtin_amdgcn_readfirstlane(track_id[e]);
+    if (k < 0 || k >= ts.K) return false;                   // wave-uniform
+    const int4 t = ts.tab[k];
+    const int off = __builtin_amdgcn_readfirstlane(t.x), n = __builtin_amdgcn_readfirstlane(t.y), bo = __builtin_amdgcn_readfirstlane(t.z);
+    tv.x = ts.x + off; tv.y = ts.y + off; tv.v = ts.v + off;
+    tv.psi = ts.psi ? ts.psi + off : nullptr;
+    tv.kappa = ts.kappa ? ts.kappa + off : nullptr;
+    tv.box = ts.box + 4 * (size_t)bo;
+    tv.n = n; tv.off = off;
+    return true;
 }
 
 }  // namespace f1p

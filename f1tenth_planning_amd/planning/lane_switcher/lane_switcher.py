@@ -34,9 +34,12 @@ class LaneSwitcherPlanner(LatticePlanner):
         self.current_lane = int(out["best_idx"][0]) % len(self.lane_offsets) if out["status"][0] != 3 else None
         return float(out["steer"][0]), float(out["speed"][0]), out["best_traj"][0]
 
-    def plan_batch(self, poses, waypoints=None, prev_theta=None, want_traj=True):
-        out = super().plan_batch(poses, waypoints=waypoints, prev_theta=prev_theta, want_traj=want_traj)
-        out["lane"] = np.where(out["status"] != 3, out["best_idx"] % len(self.lane_offsets), -1)
+    def plan_batch(self, poses, waypoints=None, prev_theta=None, want_traj=True, tracks=None, track_ids=None):
+        """tracks / track_ids: as LatticePlanner.plan_batch -- every ego's lanes are offsets of ITS track, `lane` the lane index on it
+        (-1 when blocked or for a bad track id)"""
+        out = super().plan_batch(poses, waypoints=waypoints, prev_theta=prev_theta, want_traj=want_traj, tracks=tracks, track_ids=track_ids)
+        ok = (out["status"] != 3) & (out["status"] != 4)
+        out["lane"] = np.where(ok, out["best_idx"] % len(self.lane_offsets), -1)
         return out
 
 

@@ -23,7 +23,7 @@ import warnings
 import numpy as np
 
 from ... import _abi
-from ...control.pure_pursuit.pure_pursuit import PurePursuitPlanner
+from ...control.pure_pursuit.pure_pursuit import PurePursuitPlanner, _check_tracks
 from ...runtime import Context
 
 
@@ -296,13 +296,27 @@ class LatticePlanner():
                     b.free()
         return steer, speed, status, traj
 
-    def plan_batch(self, poses, waypoints=None, prev_theta=None, want_traj=True, devices=None, traj_dtype=np.float64):
+    def plan_batch(self, poses, waypoints=None, prev_theta=None, want_traj=True, devices=None, traj_dtype=np.float64, tracks=None,
+                   track_ids=None):
         """poses [E, 4] = (x, y, theta, velocity) -> dict(steer, speed, best_idx, best_cost, status, near_idx[, best_traj]).
         Fused device path only (Python callables cannot run per ego on the GPU).
         devices: list of GPU indices (or "all") -- the egos are cut into contiguous ranges, one per GPU, each planned by its own
         context on its own host thread (runtime.MultiContext; egos are independent, so there is no collective and the result
         is identical to the single-GPU plan).
-        traj_dtype=np.float32: best_traj as f32 rows (the fp64 rows rounded once on the device; half the bytes across PCIe)."""
+        traj_dtype=np.float32: best_traj as f32 rows (the fp64 rows rounded once on the device; half the bytes across PCIe).
+        tracks: K waypoint arrays [N_k x m], m >= 4 (x, y, velocity, heading), all with the same columns, and track_ids [E]: ego e
+        plans along tracks[track_ids[e]] (the reference's plan(..., waypoints) per vehicle), bit-identical to a plan whose waypoints
+        are that track; near_idx is the row within it.  An id outside [0, K) gives NaN steer / speed / best_cost, best_idx and
+        near_idx -1, status 4 and zero rows.  `waypoints` is then not used."""
+        if tracks is not None:
+            _check_tracks(tracks, track_ids, 4)
+            if devices is None:
+                ctx = self._context()
+                ctx.set_tracks_cached(tracks)
+                return ctx.lattice_plan_tracks(poses, track_ids, self._cfg(), prev_theta=prev_theta, want_traj=want_traj, traj_dtype=traj_dtype)
+            mc = self._multi(devices)
+            mc.set_tracks_cached(tracks)
+            return mc.lattice_plan_tracks(poses, track_ids, self._cfg(), prev_theta=prev_theta, want_traj=want_traj, traj_dtype=traj_dtype)
         ctx = self._bind(waypoints)
         if devices is None:
             return ctx.lattice_plan(poses, self._cfg(), prev_theta=prev_theta, want_traj=want_traj, traj_dtype=traj_dtype)
@@ -319,14 +333,21 @@ class LatticePlanner():
         if getattr(self, "_mc", None) is not None:           # the multi-GPU replicas too (they used to plan with the term silently zero)
             self._mc.lattice_set_closed_loop(on)
 
-    def step_batch(self, poses, waypoints=None, keep_traj=False):
+    def step_batch(self, poses, waypoints=None, keep_traj=False, tracks=None, track_ids=None):
         """One control step for E vehicles: poses [E, 4] -> dict(steer, speed, status) (page-locked arrays owned by the context, valid
         until the next step).  Always a link of a closed loop (previous headings stay on the device); nothing but the poses and the
         three result columns touches host memory, and no copy is submitted (f1p_lattice_step_batch).  keep_traj=True keeps the winners'
-        rows on the device: fetch_traj() returns them."""
-        ctx = self._bind(waypoints)
+        rows on the device: fetch_traj() returns them.  tracks / track_ids: as plan_batch (f1p_lattice_step_tracks_batch)."""
+        if tracks is not None:
+            _check_tracks(tracks, track_ids, 4)
+            ctx = self._context()
+            ctx.set_tracks_cached(tracks)
+        else:
+            ctx = self._bind(waypoints)
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4)
         self._step_shape = (poses.shape[0], self._cfg().n_stations)
+        if tracks is not None:
+            return ctx.lattice_step_tracks(poses, track_ids, self._cfg(), keep_traj=keep_traj)
         return ctx.lattice_step(poses, self._cfg(), keep_traj=keep_traj)
 
     def fetch_traj(self):

@@ -432,6 +432,17 @@ class Context:
         call); they are overwritten by the next call with the same batch shape.
         traj_dtype=np.float32: best_traj comes back as f32 rows (f1p_lattice_plan_batch_f32: the fp64 rows rounded once on the
         device, half the PCIe bytes); everything else is unchanged."""
+        return self._lattice_plan(poses, cfg, goals, prev_theta, want_traj, want_all, reuse_outputs, traj_dtype, None)
+
+    def lattice_plan_tracks(self, poses, track_ids, cfg: LatticeCfg, goals=None, prev_theta=None, want_traj=True, want_all=False,
+                            reuse_outputs=False, traj_dtype=np.float64):
+        """lattice_plan on the track set (set_tracks): ego e plans along track track_ids[e], bit-identical to lattice_plan on a context
+        whose raceline is that track.  An id outside [0, K): NaN steer / speed / best_cost, best_idx and near_idx -1, status
+        F1P_ST_BAD_TRACK, zero rows."""
+        E = int(np.shape(poses)[0])
+        return self._lattice_plan(poses, cfg, goals, prev_theta, want_traj, want_all, reuse_outputs, traj_dtype, self._ids(track_ids, E))
+
+    def _lattice_plan(self, poses, cfg, goals, prev_theta, want_traj, want_all, reuse_outputs, traj_dtype, ids):
         f32 = np.dtype(traj_dtype) == np.float32
         if f32 and want_all:
             raise ValueError("traj_dtype=float32 is a winner-only mode (no all_cost / all_traj)")
@@ -456,6 +467,9 @@ class Context:
             hp, o, ptrs, php = b
             hp[...] = poses; poses = hp
             out = dict(o)
+            if ids is not None:                # (page-locked too: the kernels read them in place)
+                hi = self.pinned("lat_tid", E, np.int32)
+                hi[...] = ids; ids = hi
         else:
             # fresh arrays for the caller: the six result columns are views of ONE buffer, so that one address look-up (1.5 us each) serves all of them
             cols = np.empty(36 * E + 8, np.uint8)
@@ -481,6 +495,16 @@ class Context:
         else:
             P = lambda k: _ptr(out.get(k))                # noqa: E731
             pp = _ptr(poses)
+        if ids is not None:
+            if f32:
+                self._check(self.lib.f1p_lattice_plan_tracks_batch_f32(self.h, pp, _ptr(g), _ptr(pt), _ptr(ids), E, C.byref(cfg),
+                                                                       P("steer"), P("speed"), P("best_idx"), P("best_cost"), P("status"), P("near_idx"),
+                                                                       P("best_traj")))
+                return out
+            self._check(self.lib.f1p_lattice_plan_tracks_batch(self.h, pp, _ptr(g), _ptr(pt), _ptr(ids), E, C.byref(cfg),
+                                                               P("steer"), P("speed"), P("best_idx"), P("best_cost"), P("status"), P("near_idx"),
+                                                               P("best_traj"), _ptr(out.get("all_cost")), _ptr(out.get("all_traj"))))
+            return out
         if f32:
             self._check(self.lib.f1p_lattice_plan_batch_f32(self.h, pp, _ptr(g), _ptr(pt), E, C.byref(cfg),
                                                             P("steer"), P("speed"), P("best_idx"), P("best_cost"), P("status"), P("near_idx"), P("best_traj")))
@@ -498,6 +522,31 @@ class Context:
         self._check(self.lib.f1p_lattice_plan_dev(self.h, p(d_poses), p(d_goals), p(d_prev_theta), int(E), C.byref(cfg),
                                                   p(d_steer), p(d_speed), p(d_best_idx), p(d_best_cost), p(d_status),
                                                   p(d_near_idx), p(d_best_traj), p(d_all_cost), p(d_all_traj)))
+
+    def lattice_plan_tracks_dev(self, d_poses, d_track_ids, E, cfg: LatticeCfg, d_steer, d_speed, d_best_idx, d_best_cost=None, d_status=None,
+                                d_near_idx=None, d_best_traj=None, d_goals=None, d_prev_theta=None, d_all_cost=None, d_all_traj=None):
+        """lattice_plan_dev on the track set: ego e on track d_track_ids[e] ([E] int32 on the device); asynchronous."""
+        p = lambda b: None if b is None else b.ptr   # noqa: E731
+        self._check(self.lib.f1p_lattice_plan_tracks_dev(self.h, p(d_poses), p(d_goals), p(d_prev_theta), p(d_track_ids), int(E), C.byref(cfg),
+                                                         p(d_steer), p(d_speed), p(d_best_idx), p(d_best_cost), p(d_status),
+                                                         p(d_near_idx), p(d_best_traj), p(d_all_cost), p(d_all_traj)))
+
+    def lattice_step_tracks(self, poses, track_ids, cfg: LatticeCfg, keep_traj=False):
+        """lattice_step on the track set (f1p_lattice_step_tracks_batch): ego e on track track_ids[e]; the chain as lattice_step's."""
+        E = int(np.shape(poses)[0])
+        ids = self._ids(track_ids, E)
+        b = self._bundles.get(("step", E))
+        if b is None:
+            hp = self.pinned("step_poses", (E, 4), np.float64)
+            o = dict(steer=self.pinned("step_steer", E, np.float64), speed=self.pinned("step_speed", E, np.float64),
+                     status=self.pinned("step_status", E, np.int32))
+            b = self._bundles[("step", E)] = (hp, o, (_ptr(hp), _ptr(o["steer"]), _ptr(o["speed"]), _ptr(o["status"])))
+        hp, o, (php, ps, pv, pt) = b
+        hp[...] = poses
+        hi = self.pinned("step_tid", E, np.int32)
+        hi[...] = ids
+        self._check(self.lib.f1p_lattice_step_tracks_batch(self.h, php, _ptr(hi), E, C.byref(cfg), ps, pv, pt, 1 if keep_traj else 0))
+        return dict(o)
 
     def lattice_step(self, poses, cfg: LatticeCfg, keep_traj=False):
         """One closed-loop control step (f1p_lattice_step_batch): poses [E, 4] -> dict(steer, speed, status), page-locked arrays owned by
@@ -990,6 +1039,15 @@ class MultiContext:
         pt = None if prev_theta is None else _f64(prev_theta, (E, cfg.n_stations))
         return self._sharded(E, lambda c, lo, hi: c.lattice_plan(poses[lo:hi], cfg, None if g is None else g[lo:hi],
                                                                    None if pt is None else pt[lo:hi], want_traj=want_traj, traj_dtype=traj_dtype))
+
+    def lattice_plan_tracks(self, poses, track_ids, cfg, goals=None, prev_theta=None, want_traj=True, traj_dtype=np.float64):
+        """lattice_plan on the track set, sharded by ego ranges like lattice_plan (set_tracks replicates the set)"""
+        poses = _f64(poses, (-1, 4)); E = poses.shape[0]; ids = Context._ids(track_ids, E)
+        g = None if goals is None else _f64(goals, (E, cfg.n_cand, 3))
+        pt = None if prev_theta is None else _f64(prev_theta, (E, cfg.n_stations))
+        return self._sharded(E, lambda c, lo, hi: c.lattice_plan_tracks(poses[lo:hi], ids[lo:hi], cfg, None if g is None else g[lo:hi],
+                                                                          None if pt is None else pt[lo:hi], want_traj=want_traj,
+                                                                          traj_dtype=traj_dtype))
 
     def pure_pursuit(self, poses, lookahead, wheelbase=0.33, max_reacquire=20.0):
         poses = _f64(poses, (-1, 3))

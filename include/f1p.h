@@ -369,6 +369,30 @@ int f1p_lattice_step_batch(f1p_ctx* ctx, const double* poses, int32_t E, const f
                            int32_t* status, int32_t keep_traj);
 int f1p_lattice_fetch_traj(f1p_ctx* ctx, double* best_traj, int32_t E, int32_t S);
 
+/* The lattice plan on a TRACK SET (f1p_set_track_set): ego e plans along track k = track_id[e], exactly as f1p_lattice_plan_* /
+ * f1p_lattice_step_batch on a ctx whose raceline is track k (same map, footprint, clearance, cfg and prev_theta) -- nearest segment,
+ * look-ahead goals and the speed command come from track k, near_idx is the row index within track k; every output bit for bit.
+ * Arguments as the single-raceline calls plus track_id [E] int32 (d_track_id: device memory, asynchronous).  Every path of those
+ * calls is taken (page-locked arrays, slices, pipeline, candidate slices, host goals -- which use the track for the nearest segment
+ * and the speed only --, all_cost / all_traj, f1p_lattice_set_mode, the runtime audit); the step chains as f1p_lattice_step_batch.
+ * An id outside [0, K) reads nothing of the set: NaN steer / speed / best_cost, best_idx and near_idx -1, status F1P_ST_BAD_TRACK,
+ * zero rows and zero kept headings (its next plan with a valid id sees a zero previous path); the other egos are unaffected and the
+ * call succeeds.  No track set, or device goals on a set without a heading column: F1P_ESTATE.  cfg.cand_count > 0 or a NULL
+ * track_id with E > 0: F1P_EINVAL.  The ctx's raceline is not needed. */
+int f1p_lattice_plan_tracks_batch(f1p_ctx* ctx, const double* poses, const double* goals, const double* prev_theta, const int32_t* track_id,
+                                  int32_t E, const f1p_lattice_cfg* cfg, double* steer, double* speed, int32_t* best_idx,
+                                  double* best_cost, int32_t* status, int32_t* near_idx, double* best_traj, double* all_cost,
+                                  double* all_traj);
+int f1p_lattice_plan_tracks_batch_f32(f1p_ctx* ctx, const double* poses, const double* goals, const double* prev_theta,
+                                      const int32_t* track_id, int32_t E, const f1p_lattice_cfg* cfg, double* steer, double* speed,
+                                      int32_t* best_idx, double* best_cost, int32_t* status, int32_t* near_idx, float* best_traj32);
+int f1p_lattice_plan_tracks_dev(f1p_ctx* ctx, const double* d_poses, const double* d_goals, const double* d_prev_theta,
+                                const int32_t* d_track_id, int32_t E, const f1p_lattice_cfg* cfg, double* d_steer, double* d_speed,
+                                int32_t* d_best_idx, double* d_best_cost, int32_t* d_status, int32_t* d_near_idx,
+                                double* d_best_traj, double* d_all_cost, double* d_all_traj);
+int f1p_lattice_step_tracks_batch(f1p_ctx* ctx, const double* poses, const int32_t* track_id, int32_t E, const f1p_lattice_cfg* cfg,
+                                  double* steer, double* speed, int32_t* status, int32_t keep_traj);
+
 /* Evaluation schedule of f1p_lattice_plan_* (clothoid generator, winner-only outputs).
  *   mixed = 1 (default): every plan shape at every batch size (device- or host-supplied goals, clothoid or cubic candidates, point or
  *     oriented footprint, with or without a map; round 5) runs an f32 filter over the candidates (fit, cost bracket; lazily: stations,
