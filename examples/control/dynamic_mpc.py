@@ -3,6 +3,8 @@
 import os
 import sys
 
+import numpy as np
+
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import common  # noqa: E402
 
@@ -12,13 +14,29 @@ from f1tenth_planning.control.dynamic_mpc.dynamic_mpc import STMPCPlanner, mpc_c
 def main():
     ap = common.parser(__doc__, steps=600)
     ap.add_argument("--solver", choices=["shooting", "qp"], default="shooting")
+    ap.add_argument("--tracks", type=int, default=0, help="N agents on N lanes offset sideways from the centreline, one track set (--solver qp)")
     args = ap.parse_args()
-    if args.envs != 1:
+    lanes = ids = None
+    if args.tracks > 0:
+        if args.solver != "qp":
+            raise SystemExit("--tracks plans with STMPCPlanner.plan_batch, which needs --solver qp")
+        args.envs = args.tracks
+    if args.envs != 1 and args.tracks == 0:
         raise SystemExit("STMPCPlanner.plan drives one vehicle; use kinematic_mpc.py --envs N for the batched path")
     rl = common.raceline(args, centerline=True)
     planner = STMPCPlanner(waypoints=[rl[:, 0], rl[:, 1], rl[:, 3], rl[:, 2]], config=mpc_config(SOLVER=args.solver))
+    if args.tracks > 0:
+        normal = rl[:, 3] + np.pi / 2
+        lanes = []
+        for k in range(args.tracks):                           # lanes 0.25 m apart, centred on the centreline
+            d = 0.25 * (k - (args.tracks - 1) / 2)
+            lanes.append([rl[:, 0] + d * np.cos(normal), rl[:, 1] + d * np.sin(normal), rl[:, 3], rl[:, 2]])   # [x, y, yaw, v]
+        ids = np.arange(args.tracks, dtype=np.int32)           # agent i follows lane i
 
     def plan(obs, env):
+        if lanes is not None:
+            out = planner.plan_batch(env.state, tracks=lanes, track_ids=ids)
+            return np.column_stack([out["steer"], out["speed"]])
         steer, speed = planner.plan(env.sim.agents[0].state)
         return [[steer, speed]]
 

@@ -201,6 +201,8 @@ PROTOTYPES = {
     "f1p_lqr_tracks_batch": (C.c_int, [_P, _P, _P, _P, _I, _D, _D, _P, _D, _I, _D, _P, _P, _P]),
     "f1p_kmpc_ref_tracks_batch": (C.c_int, [_P, _P, _P, _I, _I, _D, _D, _P]),
     "f1p_kmpc_ref_tracks_dev": (C.c_int, [_P, _P, _P, _I, _I, _D, _D, _P]),
+    "f1p_stmpc_ref_tracks_batch": (C.c_int, [_P, _P, _P, _I, _I, _D, _D, _P]),
+    "f1p_stmpc_ref_tracks_dev": (C.c_int, [_P, _P, _P, _I, _I, _D, _D, _P]),
     "f1p_lattice_plan_batch": (C.c_int, [_P, _P, _P, _P, _I, C.POINTER(LatticeCfg)] + [_P] * 9),
     "f1p_lattice_plan_dev": (C.c_int, [_P, _P, _P, _P, _I, C.POINTER(LatticeCfg)] + [_P] * 9),
     "f1p_lattice_plan_batch_f32": (C.c_int, [_P, _P, _P, _P, _I, C.POINTER(LatticeCfg)] + [_P] * 7),
@@ -255,6 +257,8 @@ PROTOTYPES = {
     "f1p_stmpc_qp_dev": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcQpOpts), _P, _P, _P, _P, _P, _P, _P, _P]),
     "f1p_stmpc_qp_plan_batch": (C.c_int, [_P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcCfg), _D, _D, _D, C.POINTER(KmpcQpOpts), _P, _P,
                                           _P, _P, _P, _P]),
+    "f1p_stmpc_qp_plan_tracks_batch": (C.c_int, [_P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcCfg), _D, _D, _D, C.POINTER(KmpcQpOpts),
+                                                 _P, _P, _P, _P, _P, _P]),
     "f1p_stmpc_qp_warm_reset": (C.c_int, [_P]),
     "f1p_stmpc_qp_warm_get": (C.c_int, [_P, _P, _P, _I, _I]),
     "f1p_stmpc_qp_warm_set": (C.c_int, [_P, _P, _P, _I, _I]),

@@ -157,15 +157,45 @@ class STMPCPlanner:
         return ctx.stmpc_qp_plan(x0, self._dyn_cfg(), self._kin_cfg(), v_ks=c.V_KS, dl=c.dl, dlk=c.dlk,
                                  opts=_abi.kmpc_qp_opts(max_iter=c.QP_MAX_ITER, tol=c.QP_TOL), want_u=want_u)
 
-    def plan_batch(self, states, waypoints=None, want_u=True):
+    def plan_batch(self, states, waypoints=None, want_u=True, tracks=None, track_ids=None):
         """SOLVER == "qp": states [E, 7] -> dict(steer, speed, status, branch (1 dynamic, 0 kinematic), obj[, u [E, max(T, TK), 2] =
         (oa, odelta_v), NaN past the branch's horizon]) -- per-ego status (0 solved, 1 infeasible, 2 not converged, 3 non-finite input
-        or model data), never raised."""
+        or model data), never raised.
+        tracks: K courses in the `waypoints` format ([x, y, yaw, v]: four 1-D arrays or an array [4, N]) with track_ids [E]: ego e
+        follows tracks[track_ids[e]] (f1p_stmpc_qp_plan_tracks_batch); `waypoints` is then not used and the raceline stays as it is.
+        The warm start is the one plan() and the raceline batch use: it follows the ego, not the track.  An id outside [0, K) gives
+        that ego status 4 (F1P_ST_BAD_TRACK), branch -1 and NaN outputs, and leaves its warm start as it was.  The shooting solver on
+        tracks is a Context-level chain: ctx.stmpc_ref_tracks -> ctx.stmpc_shoot, or its rows [0, 1, 3, 4] with (TK, DTK, dlk) ->
+        ctx.kmpc_shoot for the kinematic branch."""
         _check_solver(self.config)
         if self.config.SOLVER != "qp":
             raise ValueError("plan_batch needs SOLVER='qp'")
+        if tracks is not None:
+            cols = self._track_columns(tracks, track_ids)
+            ctx = self._context()
+            ctx.set_tracks_cached(cols, cols=(0, 1, 2, 3))
+            x0 = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 7)
+            c = self.config
+            return ctx.stmpc_qp_plan_tracks(x0, Context._ids(track_ids, x0.shape[0]), self._dyn_cfg(), self._kin_cfg(), v_ks=c.V_KS,
+                                            dl=c.dl, dlk=c.dlk, opts=_abi.kmpc_qp_opts(max_iter=c.QP_MAX_ITER, tol=c.QP_TOL),
+                                            want_u=want_u)
         ctx = self._bind(waypoints)
         return self._qp(ctx, np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 7), want_u=want_u)
+
+    @staticmethod
+    def _track_columns(tracks, track_ids):
+        """ValueError before anything touches the GPU; -> the courses as (x, y, v, yaw) columns, _bind's order"""
+        if track_ids is None:
+            raise ValueError("tracks needs track_ids: one track index per ego")
+        if len(tracks) == 0:
+            raise ValueError("tracks must hold at least one course")
+        cols = []
+        for path in tracks:
+            if len(path) < 4:
+                raise ValueError("every track must hold [x, y, yaw, v]")
+            cx, cy, cyaw, sp = (np.asarray(path[k], dtype=np.float64) for k in range(4))
+            cols.append(np.column_stack([cx, cy, sp, cyaw]))
+        return cols
 
     def reset(self):
         """forget the warm start (a new episode)"""

@@ -897,6 +897,32 @@ int f1p_kmpc_ref_tracks_batch(f1p_ctx* ctx, const double* states, const int32_t*
     return s.finish();
 }
 
+int f1p_stmpc_ref_tracks_dev(f1p_ctx* ctx, const double* d_states, const int32_t* d_track_id, int32_t E, int32_t horizon, double dt, double dl,
+                             double* d_ref) {
+    F1P_ENTER(ctx);
+    if (E < 0 || (E > 0 && (!d_states || !d_track_id || !d_ref))) return set_error(ctx, F1P_EINVAL, "bad states / track_id / ref / E");
+    if (horizon < 1 || !(dt > 0) || !(dl > 0)) return set_error(ctx, F1P_EINVAL, "horizon, dt and dl must be positive");
+    const int rc = need_tracks(ctx, true, false); if (rc) return rc;
+    return launch_stmpc_ref_tracks(ctx, d_states, d_track_id, E, horizon, dt, dl, d_ref);
+}
+
+int f1p_stmpc_ref_tracks_batch(f1p_ctx* ctx, const double* states, const int32_t* track_id, int32_t E, int32_t horizon, double dt, double dl,
+                               double* ref) {
+    F1P_ENTER(ctx);
+    if (E < 0 || (E > 0 && (!states || !track_id || !ref))) return set_error(ctx, F1P_EINVAL, "bad states / track_id / ref / E");
+    if (horizon < 1 || !(dt > 0) || !(dl > 0)) return set_error(ctx, F1P_EINVAL, "horizon, dt and dl must be positive");
+    int rc = need_tracks(ctx, true, false); if (rc) return rc;
+    Stage s(ctx);
+    s.need(8 * 4 * (size_t)E); s.need(4 * (size_t)E); s.need(8 * (size_t)E * 7 * (horizon + 1));
+    if ((rc = s.begin())) return rc;
+    const double* d_s; const int32_t* d_tid;
+    if ((rc = s.in(states, (size_t)4 * E, &d_s))) return rc;
+    if ((rc = s.in(track_id, (size_t)E, &d_tid))) return rc;
+    double* d_ref = s.out(ref, (size_t)E * 7 * (horizon + 1));
+    if ((rc = launch_stmpc_ref_tracks(ctx, d_s, d_tid, E, horizon, dt, dl, d_ref))) return rc;
+    return s.finish();
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Closed-loop mode (f1p_lattice_set_closed_loop): every plan leaves its winners' heading column on the device, [E][S] fp64 in one of two
 // ctx-owned buffers used alternately, and the next plan of the same shape that passes prev_theta == NULL takes it as its previous path
@@ -1821,9 +1847,11 @@ static int ensure_stqp_warm(f1p_ctx* ctx, int E, int W) {
     return F1P_OK;
 }
 
-int f1p_stmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_stmpc_cfg* dcfg, const f1p_kmpc_cfg* kcfg, double v_ks,
-                            double dl, double dlk, const f1p_kmpc_qp_opts* opts, double* steer, double* speed, int32_t* status,
-                            int32_t* branch, double* u, double* obj) {
+// f1p_stmpc_qp_plan_batch (track_id == nullptr: every reference from the raceline) and f1p_stmpc_qp_plan_tracks_batch (track_id [E] host:
+// ego e's references from track track_id[e]; an id outside [0, K) joins neither branch, its warm start is neither read nor written)
+static int stmpc_qp_plan_impl(f1p_ctx* ctx, const double* x0, const int32_t* track_id, bool tracks, int32_t E, const f1p_stmpc_cfg* dcfg,
+                              const f1p_kmpc_cfg* kcfg, double v_ks, double dl, double dlk, const f1p_kmpc_qp_opts* opts, double* steer,
+                              double* speed, int32_t* status, int32_t* branch, double* u, double* obj) {
     F1P_ENTER(ctx);
     f1p_kmpc_qp_opts o, ok_;
     int rc = validate_stmpc_qp(ctx, dcfg, E, opts, &o); if (rc) return rc;
@@ -1831,13 +1859,19 @@ int f1p_stmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p
     if (kcfg->horizon > dcfg->horizon) return set_error(ctx, F1P_EINVAL, "stmpc qp plan: TK must be <= T");
     if (E > 0 && (!x0 || !steer || !speed || !status)) return set_error(ctx, F1P_EINVAL, "x0, steer, speed and status are required");
     if (!(dl > 0) || !(dlk > 0)) return set_error(ctx, F1P_EINVAL, "dl and dlk must be > 0");
-    if (ctx->n_wp < 2 || !ctx->has_psi) return set_error(ctx, F1P_ESTATE, "waypoints with a heading column are required");
+    if (tracks) {
+        if (E > 0 && !track_id) return set_error(ctx, F1P_EINVAL, "track_id is NULL");
+        if ((rc = need_tracks(ctx, true, false))) return rc;
+    } else if (ctx->n_wp < 2 || !ctx->has_psi) {
+        return set_error(ctx, F1P_ESTATE, "waypoints with a heading column are required");
+    }
     if (E == 0) return F1P_OK;
     const int T = dcfg->horizon, TK = kcfg->horizon, W = T;                   // W = max(T, TK)
     if ((rc = ensure_stqp_warm(ctx, E, W))) return rc;
     // the branch split (:168) and the reset rules (:1005, :1052), on the host
-    std::vector<int32_t> idx[2], use[2];
+    std::vector<int32_t> idx[2], use[2], bad;
     for (int e = 0; e < E; ++e) {
+        if (tracks && (track_id[e] < 0 || track_id[e] >= ctx->trk_K)) { bad.push_back(e); continue; }   // k_stmpc_ref_tracks's test
         const bool dyn = !(x0[(size_t)e * 7 + 3] <= v_ks);
         const int len = ctx->stmpc_qp_len[e];
         idx[dyn].push_back(e);
@@ -1846,13 +1880,14 @@ int f1p_stmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p
     const size_t nd = idx[1].size(), nk = idx[0].size();
     const size_t need = al256(8 * 7 * nd) + al256(8 * 4 * nd) + al256(8 * 7 * (T + 1) * nd) + 2 * al256(8 * 2 * T * nd) + al256(8 * 4 * nk) +
                         al256(8 * 7 * (TK + 1) * nk) + al256(8 * 4 * (TK + 1) * nk) + 2 * al256(8 * 2 * TK * nk) + 2 * (al256(4 * nd) + al256(4 * nk)) +
-                        3 * al256(8 * (size_t)E) + al256(4 * (size_t)E);
+                        3 * al256(8 * (size_t)E) + al256(4 * (size_t)E) + (tracks ? al256(4 * nd) + al256(4 * nk) : 0);
     if ((rc = arena_reset(ctx, need))) return rc;
     double* d_steer = (double*)arena_take(ctx, 8 * (size_t)E);
     double* d_speed = (double*)arena_take(ctx, 8 * (size_t)E);
     double* d_obj = (double*)arena_take(ctx, 8 * (size_t)E);
     int32_t* d_st = (int32_t*)arena_take(ctx, 4 * (size_t)E);
     std::vector<double> hx;
+    std::vector<int32_t> htid;
     double* d_win[2] = {nullptr, nullptr};
     double* d_wout[2] = {nullptr, nullptr};
     for (int b = 0; b < 2; ++b) {                                             // b = 1: dynamic (:181-191), b = 0: kinematic (:168-180)
@@ -1872,7 +1907,14 @@ int f1p_stmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p
         F1P_HIP(ctx, hipMemcpyAsync(d_idx, idx[b].data(), 4 * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
         F1P_HIP(ctx, hipMemcpyAsync(d_use, use[b].data(), 4 * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
         F1P_HIP(ctx, hipMemcpyAsync(d_s4, hx.data(), 8 * 4 * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
-        F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));                     // hx is reused by the next branch
+        int32_t* d_tid = nullptr;
+        if (tracks) {                                                        // this branch's slice of the ids
+            d_tid = (int32_t*)arena_take(ctx, 4 * (size_t)nb);
+            htid.resize((size_t)nb);
+            for (int k = 0; k < nb; ++k) htid[k] = track_id[idx[b][k]];
+            F1P_HIP(ctx, hipMemcpyAsync(d_tid, htid.data(), 4 * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
+        }
+        F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));                     // hx (and htid) are reused by the next branch
         if ((rc = launch_stmpc_qp_warm_in(ctx, ctx->d_stmpc_qp_warm, d_idx, d_use, nb, Tb, W, d_win[b]))) return rc;
         double *o_steer = d_steer, *o_speed = d_speed, *o_obj = d_obj; int32_t* o_st = d_st;
         // this branch's egos are written contiguously from offset 0 of its own slice: kinematic egos after the dynamic ones
@@ -1883,13 +1925,15 @@ int f1p_stmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p
             std::vector<double> h7((size_t)nb * 7);
             for (int k = 0; k < nb; ++k) memcpy(&h7[7 * (size_t)k], x0 + (size_t)idx[b][k] * 7, 7 * sizeof(double));
             F1P_HIP(ctx, hipMemcpyAsync(d_x7, h7.data(), 8 * 7 * (size_t)nb, hipMemcpyHostToDevice, ctx->stream));
-            if ((rc = launch_stmpc_ref(ctx, d_s4, nb, T, dcfg->dt, dl, d_ref7))) return rc;                     // :195-233
+            if ((rc = tracks ? launch_stmpc_ref_tracks(ctx, d_s4, d_tid, nb, T, dcfg->dt, dl, d_ref7)
+                             : launch_stmpc_ref(ctx, d_s4, nb, T, dcfg->dt, dl, d_ref7))) return rc;                     // :195-233
             if ((rc = launch_stmpc_qp(ctx, d_x7, d_ref7, d_win[b], d_win[b] + 1, 2, nb, dcfg, o.max_iter, o.tol, o_steer, o_speed, o_st,
                                       nullptr, nullptr, o_obj, nullptr, nullptr, d_wout[b]))) return rc;
             F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));                 // h7 leaves scope
         } else {
             double* d_ref4 = (double*)arena_take(ctx, 8 * 4 * (size_t)(Tb + 1) * nb);
-            if ((rc = launch_stmpc_ref(ctx, d_s4, nb, TK, kcfg->dt, dlk, d_ref7))) return rc;                  // :237-276
+            if ((rc = tracks ? launch_stmpc_ref_tracks(ctx, d_s4, d_tid, nb, TK, kcfg->dt, dlk, d_ref7)
+                             : launch_stmpc_ref(ctx, d_s4, nb, TK, kcfg->dt, dlk, d_ref7))) return rc;                  // :237-276
             if ((rc = launch_stmpc_qp_kref(ctx, d_ref7, nb, TK, d_ref4))) return rc;
             if ((rc = launch_kmpc_qp(ctx, d_s4, d_ref4, d_win[b], d_win[b] + 1, 2, nb, kcfg, ok_.max_iter, ok_.tol, o_steer, o_speed, o_st,
                                      nullptr, nullptr, o_obj, nullptr, nullptr, d_wout[b]))) return rc;
@@ -1927,7 +1971,25 @@ int f1p_stmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p
             }
         }
     }
+    for (const int e : bad) {                                                 // a bad track id: its warm start and length stay as they were
+        steer[e] = NaN; speed[e] = NaN; status[e] = F1P_ST_BAD_TRACK;
+        if (branch) branch[e] = -1;
+        if (obj) obj[e] = NaN;
+        if (u) std::fill(u + (size_t)e * W * 2, u + (size_t)(e + 1) * W * 2, NaN);
+    }
     return F1P_OK;
+}
+
+int f1p_stmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_stmpc_cfg* dcfg, const f1p_kmpc_cfg* kcfg, double v_ks,
+                            double dl, double dlk, const f1p_kmpc_qp_opts* opts, double* steer, double* speed, int32_t* status,
+                            int32_t* branch, double* u, double* obj) {
+    return stmpc_qp_plan_impl(ctx, x0, nullptr, false, E, dcfg, kcfg, v_ks, dl, dlk, opts, steer, speed, status, branch, u, obj);
+}
+
+int f1p_stmpc_qp_plan_tracks_batch(f1p_ctx* ctx, const double* x0, const int32_t* track_id, int32_t E, const f1p_stmpc_cfg* dcfg,
+                                   const f1p_kmpc_cfg* kcfg, double v_ks, double dl, double dlk, const f1p_kmpc_qp_opts* opts,
+                                   double* steer, double* speed, int32_t* status, int32_t* branch, double* u, double* obj) {
+    return stmpc_qp_plan_impl(ctx, x0, track_id, true, E, dcfg, kcfg, v_ks, dl, dlk, opts, steer, speed, status, branch, u, obj);
 }
 
 int f1p_stmpc_qp_warm_reset(f1p_ctx* ctx) {

@@ -258,6 +258,7 @@ int launch_stanley_tracks(f1p_ctx* ctx, const double* d_states, const int32_t* d
 int launch_lqr_tracks(f1p_ctx* ctx, const double* d_states, const int32_t* d_tid, double* d_err, int E, double wheelbase, double ts,
                       const double* q, double r, int max_iter, double eps, double* d_steer, double* d_speed, int32_t* d_near);
 int launch_kmpc_ref_tracks(f1p_ctx* ctx, const double* d_states, const int32_t* d_tid, int E, int horizon, double dt, double dl, double* d_ref);
+int launch_stmpc_ref_tracks(f1p_ctx* ctx, const double* d_states, const int32_t* d_tid, int E, int horizon, double dt, double dl, double* d_ref);
 int launch_argmin_key(f1p_ctx* ctx, const double* d_cost, uint64_t* d_key, int E);
 int launch_argmin_mask(f1p_ctx* ctx, const uint64_t* d_own, const uint64_t* d_min, const int32_t* d_idx, int32_t* d_masked,
                        double* d_cost_out, int E);

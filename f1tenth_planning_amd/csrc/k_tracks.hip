@@ -1,7 +1,8 @@
 // k_tracks.hip -- the waypoint trackers over a TRACK SET: every ego follows its own polyline (f1p_set_track_set).
 //
 // The reference builds one planner per vehicle and hands each its own waypoints per call (PurePursuitPlanner.plan(..., waypoints),
-// pure_pursuit.py:85; StanleyPlanner.plan, stanley.py:114; LQRPlanner.plan, lqr.py:156; KMPCPlanner.plan, kinematic_mpc.py:115).
+// pure_pursuit.py:85; StanleyPlanner.plan, stanley.py:114; LQRPlanner.plan, lqr.py:156; KMPCPlanner.plan, kinematic_mpc.py:115;
+// STMPCPlanner.plan, dynamic_mpc.py:133).
 // Here K polylines are stored back to back, struct-of-arrays fp64 like the context's raceline, with a table int32 [K][4] =
 // (first row, rows, first 64-segment chunk box, 0).  Each kernel is the single-raceline kernel's mapping (one wave per ego; one
 // workgroup per ego for the MPC reference) with a prologue: the ego's track id, then its table entry -- wave-uniform values, kept in
@@ -170,6 +171,46 @@ __global__ __launch_bounds__(256) void k_kmpc_ref_tracks(const double* __restric
     kmpc_ref_rows(v, yaw, ind, e, T, dt, dl, tv.x, tv.y, tv.v, tv.psi, tv.n, yaw_fixup, ref);   // :189-205
 }
 
+// k_stmpc_ref over the track set: one workgroup per ego.  states [E][4] = (x, y, v, yaw) -> ref [E][7][T+1] rows x, y, 0, v, yaw, 0, 0
+// (calc_ref_trajectory dynamic_mpc.py:195-233; with (TK, DTK, dlk) STMPC's calc_ref_trajectory_kinematic :237-276, rows 0, 1, 3, 4).
+// The statements of k_stmpc_ref (k_stmpc.hip) on the ego's track; that kernel keeps its own copy.
+__global__ __launch_bounds__(256) void k_stmpc_ref_tracks(const double* __restrict__ states, const int32_t* __restrict__ track_id, int E, int T,
+                                                          double dt, double dl, TrackSetDev ts, double* __restrict__ ref) {
+    __shared__ double sd[4];
+    __shared__ int si[4];
+    const int e = blockIdx.x;
+    if (e >= E) return;
+    double* r = ref + (size_t)e * 7 * (T + 1);
+    TrackView tv;
+    if (!track_of(ts, track_id, e, tv)) {                    // workgroup-uniform
+        for (int j = threadIdx.x; j < 7 * (T + 1); j += blockDim.x) r[j] = __builtin_nan("");
+        return;
+    }
+    const double px = states[4 * e], py = states[4 * e + 1], v = states[4 * e + 2], yaw = states[4 * e + 3];
+    double bd; int ind;
+    nearest_scan_boxed(px, py, tv.x, tv.y, tv.box, tv.n, threadIdx.x, blockDim.x, bd, ind);
+    block_argmin(bd, ind, sd, si);
+    const int n = tv.n;
+    const double dind = (fabs(v) * dt) / dl;
+    for (int j = threadIdx.x; j <= T; j += blockDim.x) {
+        double cum = 0.0;
+        for (int q = 0; q < j; ++q) cum += dind;
+        int il = ind + (int)cum;
+        if (il >= n) il -= n;
+        if (il < 0 || il >= n) il = il < 0 ? 0 : n - 1;
+        double cyw = tv.psi[il];
+        if (cyw - yaw > 5) cyw = fabs(cyw - (2 * F1P_PI));      // :227
+        if (cyw - yaw < -5) cyw = fabs(cyw + (2 * F1P_PI));     // :228
+        r[0 * (T + 1) + j] = tv.x[il];
+        r[1 * (T + 1) + j] = tv.y[il];
+        r[2 * (T + 1) + j] = 0.0;
+        r[3 * (T + 1) + j] = tv.v[il];
+        r[4 * (T + 1) + j] = cyw;
+        r[5 * (T + 1) + j] = 0.0;
+        r[6 * (T + 1) + j] = 0.0;
+    }
+}
+
 TrackSetDev track_set_dev(const f1p_ctx* ctx) {
     TrackSetDev ts;
     ts.x = ctx->d_tx; ts.y = ctx->d_ty; ts.v = ctx->d_tv;
@@ -221,6 +262,12 @@ int launch_kmpc_ref_tracks(f1p_ctx* ctx, const double* d_states, const int32_t* 
     hipLaunchKernelGGL(k_kmpc_ref_tracks, dim3(E), dim3(256), 0, ctx->stream, d_states, d_tid, E, horizon, dt, dl, track_set_dev(ctx),
                        ctx->kmpc_yaw_fixup, d_ref);
     return check_hip(ctx, hipGetLastError(), "k_kmpc_ref_tracks launch");
+}
+
+int launch_stmpc_ref_tracks(f1p_ctx* ctx, const double* d_states, const int32_t* d_tid, int E, int horizon, double dt, double dl, double* d_ref) {
+    if (E <= 0) return F1P_OK;
+    hipLaunchKernelGGL(k_stmpc_ref_tracks, dim3(E), dim3(256), 0, ctx->stream, d_states, d_tid, E, horizon, dt, dl, track_set_dev(ctx), d_ref);
+    return check_hip(ctx, hipGetLastError(), "k_stmpc_ref_tracks launch");
 }
 
 }  // namespace f1p

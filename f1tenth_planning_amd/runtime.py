@@ -425,6 +425,18 @@ class Context:
         p = lambda b: None if b is None else b.ptr   # noqa: E731
         self._check(self.lib.f1p_kmpc_ref_tracks_dev(self.h, p(d_states), p(d_track_ids), int(E), int(horizon), float(dt), float(dl), p(d_ref)))
 
+    def stmpc_ref_tracks(self, states, track_ids, horizon, dt=0.025, dl=0.03):
+        """stmpc_ref on each ego's track -> ref [E, 7, T+1] (a bad id: NaN rows).  With (TK, DTK, dlk), rows [0, 1, 3, 4] are STMPC's
+        kinematic reference, for kmpc_shoot; the full rows go to stmpc_shoot."""
+        st = _f64(states, (-1, 4)); E = st.shape[0]; ids = self._ids(track_ids, E)
+        ref = np.empty((E, 7, horizon + 1))
+        self._check(self.lib.f1p_stmpc_ref_tracks_batch(self.h, _ptr(st), _ptr(ids), E, int(horizon), float(dt), float(dl), _ptr(ref)))
+        return ref
+
+    def stmpc_ref_tracks_dev(self, d_states, d_track_ids, E, horizon, d_ref, dt=0.025, dl=0.03):
+        p = lambda b: None if b is None else b.ptr   # noqa: E731
+        self._check(self.lib.f1p_stmpc_ref_tracks_dev(self.h, p(d_states), p(d_track_ids), int(E), int(horizon), float(dt), float(dl), p(d_ref)))
+
     # ---- lattice -------------------------------------------------------------------------------------------
     def lattice_plan(self, poses, cfg: LatticeCfg, goals=None, prev_theta=None, want_traj=True, want_all=False,
                      reuse_outputs=False, traj_dtype=np.float64):
@@ -831,6 +843,23 @@ class Context:
                                                      _ptr(out["status"]), _ptr(out["branch"]), _ptr(out.get("u")), _ptr(out.get("obj"))))
         return out
 
+    def stmpc_qp_plan_tracks(self, x0, track_ids, dcfg: _abi.StmpcCfg, kcfg: KmpcCfg, v_ks=2.0, dl=0.03, dlk=0.03, opts=None, want_u=True,
+                             want_obj=True):
+        """stmpc_qp_plan with ego e's references from track track_ids[e] of set_tracks; the same dict.  The warm start is the one of
+        stmpc_qp_plan (it follows the ego, not the track).  A bad id: status F1P_ST_BAD_TRACK, branch -1, NaN outputs, its warm start
+        untouched."""
+        x0 = _f64(x0, (-1, 7)); E = x0.shape[0]; ids = self._ids(track_ids, E); W = max(dcfg.horizon, kcfg.horizon)
+        out = dict(steer=np.empty(E), speed=np.empty(E), status=np.empty(E, np.int32), branch=np.empty(E, np.int32))
+        if want_u:
+            out["u"] = np.empty((E, W, 2))
+        if want_obj:
+            out["obj"] = np.empty(E)
+        self._check(self.lib.f1p_stmpc_qp_plan_tracks_batch(self.h, _ptr(x0), _ptr(ids), E, C.byref(dcfg), C.byref(kcfg), float(v_ks),
+                                                            float(dl), float(dlk), None if opts is None else C.byref(opts),
+                                                            _ptr(out["steer"]), _ptr(out["speed"]), _ptr(out["status"]), _ptr(out["branch"]),
+                                                            _ptr(out.get("u")), _ptr(out.get("obj"))))
+        return out
+
     def stmpc_qp_warm_reset(self):
         self._check(self.lib.f1p_stmpc_qp_warm_reset(self.h))
 
@@ -1060,6 +1089,17 @@ class MultiContext:
     def kmpc_ref_tracks(self, states, track_ids, horizon, dt=0.1, dl=0.03):
         st = _f64(states, (-1, 4)); ids = Context._ids(track_ids, st.shape[0])
         return self._sharded(st.shape[0], lambda c, lo, hi: dict(ref=c.kmpc_ref_tracks(st[lo:hi], ids[lo:hi], horizon, dt, dl)))["ref"]
+
+    def stmpc_ref_tracks(self, states, track_ids, horizon, dt=0.025, dl=0.03):
+        st = _f64(states, (-1, 4)); ids = Context._ids(track_ids, st.shape[0])
+        return self._sharded(st.shape[0], lambda c, lo, hi: dict(ref=c.stmpc_ref_tracks(st[lo:hi], ids[lo:hi], horizon, dt, dl)))["ref"]
+
+    def stmpc_qp_plan_tracks(self, x0, track_ids, dcfg, kcfg, v_ks=2.0, dl=0.03, dlk=0.03, opts=None, want_u=True, want_obj=True):
+        """Context.stmpc_qp_plan_tracks sharded by ego ranges.  Each context holds the warm start of ITS range, so E and the device list
+        must stay the same from call to call for the chain to equal the single-context chain (a new E restarts every warm start)."""
+        x0 = _f64(x0, (-1, 7)); ids = Context._ids(track_ids, x0.shape[0])
+        return self._sharded(x0.shape[0], lambda c, lo, hi: c.stmpc_qp_plan_tracks(x0[lo:hi], ids[lo:hi], dcfg, kcfg, v_ks, dl, dlk, opts,
+                                                                                   want_u, want_obj))
 
     def kmpc_ref(self, states, horizon, dt=0.1, dl=0.03):
         st = _f64(states, (-1, 4))

@@ -264,7 +264,8 @@ int f1p_lqr_batch(f1p_ctx* ctx, const double* states, double* err, int32_t E, do
  * Track sets: every ego follows its own polyline.  The reference hands each planner its waypoints per call --
  * PurePursuitPlanner.plan(..., waypoints) (control/pure_pursuit/pure_pursuit.py:85), StanleyPlanner.plan
  * (control/stanley/stanley.py:114), LQRPlanner.plan (control/lqr/lqr.py:156), KMPCPlanner.plan(states, waypoints)
- * (control/kinematic_mpc/kinematic_mpc.py:115) -- so one planner per vehicle can follow any line.  A track set holds K such
+ * (control/kinematic_mpc/kinematic_mpc.py:115), STMPCPlanner.plan (control/dynamic_mpc/dynamic_mpc.py:133) -- so one planner
+ * per vehicle can follow any line.  A track set holds K such
  * lines next to the ctx's raceline (the two are independent; f1p_set_waypoints does not touch the set, nor the reverse), and
  * the *_tracks calls take track_id [E] int32: ego e follows track track_id[e].  Each ego's outputs are bit-identical to the
  * single-raceline call on a ctx whose raceline is that ego's track.  An id outside [0, K) gives that ego NaN steer / speed
@@ -303,6 +304,15 @@ int f1p_kmpc_ref_tracks_batch(f1p_ctx* ctx, const double* states, const int32_t*
                               double dl, double* ref);
 int f1p_kmpc_ref_tracks_dev(f1p_ctx* ctx, const double* d_states, const int32_t* d_track_id, int32_t E, int32_t horizon, double dt,
                             double dl, double* d_ref);
+/* calc_ref_trajectory (dynamic_mpc.py:195-233) on each ego's track: as f1p_stmpc_ref_batch (needs a heading column); with
+ * (TK, DTK, dlk) STMPCPlanner's calc_ref_trajectory_kinematic (:237-276), rows 0, 1, 3, 4.  A bad id gives all 7 (T+1) entries NaN.
+ * The _dev twin is asynchronous on device buffers, for f1p_stmpc_shoot_dev / f1p_stmpc_qp_dev. */
+int f1p_stmpc_ref_tracks_batch(f1p_ctx* ctx, const double* states, const int32_t* track_id, int32_t E, int32_t horizon, double dt,
+                               double dl, double* ref);
+int f1p_stmpc_ref_tracks_dev(f1p_ctx* ctx, const double* d_states, const int32_t* d_track_id, int32_t E, int32_t horizon, double dt,
+                             double dl, double* d_ref);
+/* f1p_stmpc_qp_plan_tracks_batch, STMPCPlanner.plan's QP on each ego's track, is declared after f1p_stmpc_qp_plan_batch below (it
+ * takes the dynamic-MPC structs). */
 
 /* ------------------------------------------------------------------------------------------------
  * LatticePlanner.plan (planning/lattice_planner/lattice_planner.py:174-214) for E egos, one fused launch:
@@ -670,6 +680,15 @@ int f1p_stmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p
 int f1p_stmpc_qp_warm_reset(f1p_ctx* ctx);
 int f1p_stmpc_qp_warm_get(f1p_ctx* ctx, double* warm, int32_t* len, int32_t E, int32_t W);
 int f1p_stmpc_qp_warm_set(f1p_ctx* ctx, const double* warm, const int32_t* len, int32_t E, int32_t W);
+/* f1p_stmpc_qp_plan_batch with each ego's reference taken from its own track (track_id [E] host; needs a heading column, no raceline).
+ * Ego e on track k gets outputs bit-identical to f1p_stmpc_qp_plan_batch on a ctx whose raceline is track k and which holds the same
+ * warm start for e.  The warm start is the ctx's one per-ego buffer of the raceline plan (f1p_stmpc_qp_warm_*): it follows the ego,
+ * not the track, as the reference's self.oa / self.odelta_v survive a change of waypoints, and the two calls may be interleaved.
+ * A bad id: the ego joins neither branch, steer / speed / obj NaN, u NaN over all W steps, status F1P_ST_BAD_TRACK, branch -1, and
+ * its warm start and length are neither read nor written. */
+int f1p_stmpc_qp_plan_tracks_batch(f1p_ctx* ctx, const double* x0, const int32_t* track_id, int32_t E, const f1p_stmpc_cfg* dcfg,
+                                   const f1p_kmpc_cfg* kcfg, double v_ks, double dl, double dlk, const f1p_kmpc_qp_opts* opts,
+                                   double* steer, double* speed, int32_t* status, int32_t* branch, double* u, double* obj);
 
 /* ------------------------------------------------------------------------------------------------
  * SURVEY.md 8f rank 2 -- the dynamic single-track model as a second model for shooting MPC
