@@ -1648,6 +1648,15 @@ void f1p_kmpc_qp_opts_default(f1p_kmpc_qp_opts* opts) {
     opts->max_iter = 50; opts->tol = 1e-10;
 }
 
+// opts (nullable: the defaults) into *o, range-checked; `what` prefixes the error message
+static int qp_opts(f1p_ctx* ctx, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o, const char* what) {
+    f1p_kmpc_qp_opts_default(o);
+    if (opts) *o = *opts;
+    if (o->max_iter < 0 || o->max_iter > 1000 || !(o->tol > 0) || !isfinite(o->tol))
+        return set_error(ctx, F1P_EINVAL, std::string(what) + ": max_iter must be in [0, 1000] and tol finite and > 0");
+    return F1P_OK;
+}
+
 // the cfg checks of the shooting path, the diagonal weights' and bounds' sanity, horizon <= 32 (n = 2T inputs, one lane each); opts
 static int validate_kmpc_qp(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, int E, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o) {
     int rc = validate_kmpc(ctx, cfg, E); if (rc) return rc;
@@ -1661,11 +1670,7 @@ static int validate_kmpc_qp(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, int E, const 
             return set_error(ctx, F1P_EINVAL, "kmpc qp: input weights must be finite, r > 0 (strict convexity), rd >= 0");
     if (!(cfg->max_accel > 0) || !(cfg->max_steer > 0) || !(cfg->max_dsteer > 0) || !(cfg->max_speed >= cfg->min_speed))
         return set_error(ctx, F1P_EINVAL, "kmpc qp: bounds must be > 0 and max_speed >= min_speed");
-    f1p_kmpc_qp_opts_default(o);
-    if (opts) *o = *opts;
-    if (o->max_iter < 0 || o->max_iter > 1000 || !(o->tol > 0) || !isfinite(o->tol))
-        return set_error(ctx, F1P_EINVAL, "kmpc qp: max_iter must be in [0, 1000] and tol finite and > 0");
-    return F1P_OK;
+    return qp_opts(ctx, opts, o, "kmpc qp");
 }
 
 int f1p_kmpc_qp_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_prev, int32_t E,
@@ -1790,11 +1795,7 @@ static int validate_stmpc_qp(f1p_ctx* ctx, const f1p_stmpc_cfg* cfg, int E, cons
         return set_error(ctx, F1P_EINVAL, "stmpc qp: bounds must be > 0 and max_speed >= min_speed");
     for (int k = 0; k < 8; ++k)
         if (!isfinite(cfg->params[k])) return set_error(ctx, F1P_EINVAL, "stmpc qp: vehicle parameters must be finite");
-    f1p_kmpc_qp_opts_default(o);
-    if (opts) *o = *opts;
-    if (o->max_iter < 0 || o->max_iter > 1000 || !(o->tol > 0) || !isfinite(o->tol))
-        return set_error(ctx, F1P_EINVAL, "stmpc qp: max_iter must be in [0, 1000] and tol finite and > 0");
-    return F1P_OK;
+    return qp_opts(ctx, opts, o, "stmpc qp");
 }
 
 int f1p_stmpc_qp_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_v_prev, int32_t E,

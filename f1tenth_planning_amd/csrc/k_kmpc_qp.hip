@@ -5,48 +5,21 @@
 //      NOT shifted -- through kmpc_step<false>, the step of k_kmpc_predict; get_kinematic_model_matrix(v_t, phi_t, 0) (:245-278)
 //   2. condensing: x = S u + s (s: the free response of the linear model, S: one column per input), so the objective of :324-331 becomes
 //      1/2 u'Hu + g'u + c over u = vec(uk) = (a_0, d_0, a_1, d_1, ...), n = 2T
-//   3. a primal-dual interior-point method (Mehrotra predictor-corrector) on  G u <= h  with the bounds of :379-389:
+//   3. the interior point of qp_ipm.h on  G u <= h  with the bounds of :379-389:
 //        a upper / lower, delta upper / lower (unit rows), rate upper / lower (first differences of delta),
 //        v_1..T upper / lower (DTK x prefix sums of a; v_0 is x0's speed: feasible iff MIN_SPEED <= v0 <= MAX_SPEED)
-//      Newton system (H + G' diag(lambda / s) G) du = rhs: the G'DG term is O(n^2) from suffix sums (G is never formed), factored by
-//      Cholesky.  Stop: |r_d| <= tol (1 + |g|), |r_p| <= tol (1 + |h|) and s'lambda <= tol (max-norms), or max_iter.  An ego whose
-//      Newton matrix stops being numerically positive definite before that (lambda / s ~ 1e16 on its active rows) stops there, solved
-//      when its residuals are below tol and s'lambda <= tol (1 + |objective|), otherwise not converged (status 2).
+//      G is never formed: G'DG in the Newton matrix is O(n^2) from suffix sums.
 //
 // Mapping: a group of G lanes per ego (G = 64: one ego per wave, T <= 32; G = 16: four egos per wave, T <= 8).  Lane i owns input u_i,
 // row i of H and of the Newton matrix, and the four inequality rows next to it:
 //   i = 2t   (a_t):     a_t upper, a_t lower, v_{t+1} upper, v_{t+1} lower
 //   i = 2t+1 (delta_t): delta_t upper, delta_t lower, rate_t upper, rate_t lower (none for t = T-1)
-// Matrices live in LDS (row i written by lane i, the pivot column read as broadcasts); group reductions are xor butterflies of width G.
-// Every ego runs until the last ego of its workgroup stops, but an ego that has stopped takes no further steps, so its result does not
-// depend on its neighbours (tests/test_gpu_kmpc_qp.py: batch invariance).
-#include "f1p_internal.h"
+// An ego's result does not depend on its neighbours (tests/test_gpu_kmpc_qp.py: batch invariance).
+#include "qp_ipm.h"
 
 namespace f1p {
 
 namespace {
-
-template <int G>
-__device__ __forceinline__ double gsum(double v) {
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) v += __shfl_xor(v, m, G);
-    return v;
-}
-template <int G>
-__device__ __forceinline__ double gmax(double v) {
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) {                    // NaN-propagating: a broken-down ego never looks converged
-        const double o = __shfl_xor(v, m, G);
-        v = (o > v || o != o) ? o : v;
-    }
-    return v;
-}
-template <int G>
-__device__ __forceinline__ double gmin(double v) {
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) v = fmin(v, __shfl_xor(v, m, G));
-    return v;
-}
 
 // doubles of LDS per ego
 __host__ __device__ inline int qp_lds_doubles(int T) {
@@ -164,7 +137,7 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
         }
     }
 
-    // ---- 3. interior point ------------------------------------------------------------------------------------------------------------
+    // ---- 3. interior point (qp_ipm.h) ----------------------------------------------------------------------------------------------------
     const double MD = cfg.max_dsteer * DTK;
     double h[4];
     bool valid[4];
@@ -172,18 +145,10 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
     else        { h[0] = cfg.max_steer; h[1] = cfg.max_steer; h[2] = MD; h[3] = MD; }
 #pragma unroll
     for (int r = 0; r < 4; ++r) valid[r] = in_n && (j == 0 || r < 2 || tau < T - 1);
-    double u = 0.0, s[4], lam[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { s[r] = valid[r] ? fmax(h[r], 1.0) : 1.0; lam[r] = valid[r] ? 1.0 : 0.0; }
-    double hmax = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) hmax = fmax(hmax, valid[r] ? fabs(h[r]) : 0.0);
-    const double gn = 1.0 + gmax<G>(in_n ? fabs(g) : 0.0), hn = 1.0 + gmax<G>(hmax);
-    const double m_rows = 8.0 * T - 2.0;
-    int it_done = 0;
 
     // G x for this lane's rows (x published in vec[])
-    auto gmul = [&](const double* vec, double xi, double out[4]) {
+    auto gmul = [&](const double* vec, const double (&x)[1], double (&out)[4]) {
+        const double xi = x[0];
         if (!in_n) {
             out[0] = out[1] = out[2] = out[3] = 0.0;
         } else if (j == 0) {
@@ -198,64 +163,28 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
         for (int r = 0; r < 4; ++r) out[r] = valid[r] ? out[r] : 0.0;
     };
     // (G' w)_i: the rows' w_2 - w_3 published in W[]
-    auto gtmul = [&](const double w[4]) -> double {
+    auto gtmul = [&](const double (&w)[4], double (&o)[1]) {
         double w2 = valid[2] ? w[2] - w[3] : 0.0;
         __syncthreads();
         if (in_n) L.W[i] = w2;
         __syncthreads();
-        double o = (valid[0] ? w[0] : 0.0) - (valid[1] ? w[1] : 0.0);
+        o[0] = (valid[0] ? w[0] : 0.0) - (valid[1] ? w[1] : 0.0);
         if (!in_n) {
-            o = 0.0;
+            o[0] = 0.0;
         } else if (j == 0) {
             double suf = 0.0;
             for (int q = T - 1; q >= tau; --q) suf += L.W[2 * q];
-            o += DTK * suf;
+            o[0] += DTK * suf;
         } else {
-            o += -w2 + (tau > 0 ? L.W[i - 2] : 0.0);
+            o[0] += -w2 + (tau > 0 ? L.W[i - 2] : 0.0);
         }
-        return o;
     };
-    // publish x_i in U[] and return it (barriers on both sides)
-    auto publish = [&](double* vec, double xi) {
+    // row i of M = H + G' diag(D) G, lower triangle: a diagonal, the rate rows' tridiagonal (delta), DTK^2 x suffix sums of the
+    // v rows' D over max(tau, c / 2) (a)
+    auto newton_rows = [&](const double (&D)[4]) {
         __syncthreads();
-        if (in_n) vec[i] = xi;
+        if (in_n) L.W[i] = D[2] + D[3];
         __syncthreads();
-    };
-
-    for (int it = 0;; ++it) {
-        // residuals
-        publish(L.U, u);
-        double Gu[4], rp[4];
-        gmul(L.U, u, Gu);
-        double rpmax = 0.0, gap = 0.0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            rp[r] = valid[r] ? Gu[r] + s[r] - h[r] : 0.0;
-            rpmax = fmax(rpmax, fabs(rp[r]));
-            gap += valid[r] ? s[r] * lam[r] : 0.0;
-        }
-        double Hu = 0.0;
-        if (in_n) for (int c = 0; c < n; ++c) Hu += L.H[i * n + c] * L.U[c];
-        const double gtl = gtmul(lam);
-        const double rd = in_n ? Hu + g + gtl : 0.0;
-        const double rdn = gmax<G>(fabs(rd)) / gn, rpn = gmax<G>(rpmax) / hn;
-        gap = gsum<G>(gap);
-        const double f = gsum<G>(in_n ? u * (0.5 * Hu + g) : 0.0);
-        // converged: residuals and the gap s'lambda below tol.  The gap relative to the objective is the fallback for an ego whose
-        // Newton matrix can no longer be factored (lambda / s ~ 1e16 on its active rows) before the absolute gap is reached.
-        const bool res_ok = rdn <= tol && rpn <= tol;
-        const bool gap_rel_ok = res_ok && gap <= tol * (1.0 + fabs(f));
-        if (!done) {
-            if (res_ok && gap <= tol) { done = true; st = 0; it_done = it; }
-            else if (it >= max_iter) { done = true; st = 2; it_done = it; }
-        }
-        if (!__syncthreads_or(!done)) break;
-
-        // Newton matrix M = H + G' diag(lambda / s) G, row i
-        double D[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) D[r] = valid[r] ? lam[r] / s[r] : 0.0;
-        publish(L.W, D[2] + D[3]);
         if (j == 0 && in_n) {
             double suf = 0.0;
             for (int q = T - 1; q >= tau; --q) suf += L.W[2 * q];
@@ -263,94 +192,28 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
         }
         __syncthreads();
         if (in_n) {
-            for (int c = 0; c < n; ++c) {
+            for (int c = 0; c <= i; ++c) {
                 double m = L.H[i * n + c];
                 if (j == 0 && (c & 1) == 0) m += DTK * DTK * L.SUF[max(tau, c >> 1)];
                 if (c == i) m += D[0] + D[1] + (j == 1 ? L.W[i] + (tau > 0 ? L.W[i - 2] : 0.0) : 0.0);
-                if (j == 1 && c == i + 2) m -= L.W[i];
                 if (j == 1 && c == i - 2) m -= L.W[i - 2];
                 L.M[i * n + c] = m;
             }
         }
-        // Cholesky, in place: lower triangle of M = L
-        bool broke = false;
-        for (int k = 0; k < n; ++k) {
-            __syncthreads();
-            const double mk = L.M[k * n + k];
-            broke |= !(mk > 0.0 && mk < INFINITY);
-            const double dk = sqrt(mk);
-            double l = 0.0;
-            if (i > k && in_n) { l = L.M[i * n + k] / dk; L.M[i * n + k] = l; }
-            __syncthreads();
-            if (i == k) L.M[k * n + k] = dk;
-            if (i > k && in_n) for (int c = k + 1; c <= i; ++c) L.M[i * n + c] -= l * L.M[c * n + k];
-        }
-        __syncthreads();
-        if (broke && !done) { done = true; st = gap_rel_ok ? 0 : 2; it_done = it; }     // (broke is uniform over the group)
+    };
 
-        // one Newton solve for the complementarity right-hand side rc
-        auto newton = [&](const double rc[4], double& du, double ds[4], double dl[4]) {
-            double w[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) w[r] = valid[r] ? (lam[r] * rp[r] - rc[r]) / s[r] : 0.0;
-            double b = -rd - gtmul(w);
-            for (int k = 0; k < n; ++k) {                // L y = b
-                if (i == k) { b = b / L.M[k * n + k]; L.Y[k] = b; }
-                __syncthreads();
-                if (i > k && in_n) b -= L.M[i * n + k] * L.Y[k];
-            }
-            for (int k = n - 1; k >= 0; --k) {           // L' x = y
-                if (i == k) { b = b / L.M[k * n + k]; L.Y[k] = b; }
-                __syncthreads();
-                if (i < k) b -= L.M[k * n + i] * L.Y[k];
-            }
-            du = in_n ? b : 0.0;
-            double Gd[4];
-            publish(L.U, du);
-            gmul(L.U, du, Gd);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                ds[r] = valid[r] ? -rp[r] - Gd[r] : 0.0;
-                dl[r] = valid[r] ? (-rc[r] - lam[r] * ds[r]) / s[r] : 0.0;
-            }
-        };
-        auto step_max = [&](const double ds[4], const double dl[4]) -> double {
-            double a = 1.0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (valid[r] && ds[r] < 0.0) a = fmin(a, -s[r] / ds[r]);
-                if (valid[r] && dl[r] < 0.0) a = fmin(a, -lam[r] / dl[r]);
-            }
-            return gmin<G>(a);
-        };
-        const double mu = gap / m_rows;
-        double rc[4], du, ds[4], dl[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) rc[r] = valid[r] ? s[r] * lam[r] : 0.0;
-        newton(rc, du, ds, dl);                          // predictor (affine scaling)
-        double a = step_max(ds, dl), gap_aff = 0.0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) gap_aff += valid[r] ? (s[r] + a * ds[r]) * (lam[r] + a * dl[r]) : 0.0;
-        gap_aff = gsum<G>(gap_aff);
-        const double ratio = gap_aff / gap, sigma = ratio * ratio * ratio;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) rc[r] = valid[r] ? s[r] * lam[r] + ds[r] * dl[r] - sigma * mu : 0.0;
-        newton(rc, du, ds, dl);                          // corrector
-        a = fmin(1.0, 0.99 * step_max(ds, dl));
-        if (!done) {
-            u += a * du;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) if (valid[r]) { s[r] += a * ds[r]; lam[r] += a * dl[r]; }
-        }
-    }
+    const double gv[1] = {g};
+    double u[1], lam[4];
+    int it_done;
+    qp_ipm<G, 1, 4>(QpIpmLds{L.H, L.M, L.U, L.Y}, n, i, gv, h, valid, 8.0 * T - 2.0, max_iter, tol, done, st, it_done, u, lam, gmul, gtmul,
+                    newton_rows);
 
     // ---- outputs --------------------------------------------------------------------------------------------------------------------
     if (!ego) return;
     const bool ok = st == 0 || st == 2;
-    publish(L.U, u);
     if (in_n) {
-        if (u_out) u_out[(size_t)e * n + i] = ok ? u : NaN;
-        if (warm_out) warm_out[(size_t)e * n + i] = ok ? u : 0.0;     // a failed solve leaves the reference's oa / od = None: zeros next call
+        if (u_out) u_out[(size_t)e * n + i] = ok ? u[0] : NaN;
+        if (warm_out) warm_out[(size_t)e * n + i] = ok ? u[0] : 0.0;     // a failed solve leaves the reference's oa / od = None: zeros next call
         if (duals) {
             double* du_ = duals + (size_t)e * (8 * T - 2);
             const int R4 = 4 * T, R6 = 6 * T - 2;
@@ -412,19 +275,11 @@ int launch_kmpc_qp(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const 
     const int T = cfg->horizon;
     const int epw = kmpc_qp_pack(ctx, T) == 4 ? 4 : 1;
     const size_t lds = sizeof(double) * (size_t)qp_lds_doubles(T) * epw;
-    const void* kern = epw == 4 ? reinterpret_cast<const void*>(&k_kmpc_qp<16>) : reinterpret_cast<const void*>(&k_kmpc_qp<64>);
-    if (lds > (size_t)ctx->prop.sharedMemPerBlock) {
-        if (lds > (size_t)ctx->prop.maxSharedMemoryPerMultiProcessor)
-            return set_error(ctx, F1P_EINVAL, "kmpc qp: horizon too long for the CU's LDS");
-        F1P_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
-    const dim3 grid((unsigned)((E + epw - 1) / epw));
-    if (epw == 4)
-        hipLaunchKernelGGL(k_kmpc_qp<16>, grid, dim3(64), lds, ctx->stream, d_x0, d_ref, d_pa, d_pd, pstride, E, *cfg, max_iter, tol, d_steer,
-                           d_speed, d_status, d_u, d_xk, d_obj, d_duals, d_iters, d_warm_out);
-    else
-        hipLaunchKernelGGL(k_kmpc_qp<64>, grid, dim3(64), lds, ctx->stream, d_x0, d_ref, d_pa, d_pd, pstride, E, *cfg, max_iter, tol, d_steer,
-                           d_speed, d_status, d_u, d_xk, d_obj, d_duals, d_iters, d_warm_out);
+    const auto kern = epw == 4 ? &k_kmpc_qp<16> : &k_kmpc_qp<64>;
+    const int rc = qp_lds_opt_in(ctx, reinterpret_cast<const void*>(kern), lds, "kmpc qp: horizon too long for the CU's LDS");
+    if (rc) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((E + epw - 1) / epw)), dim3(64), lds, ctx->stream, d_x0, d_ref, d_pa, d_pd, pstride, E, *cfg,
+                       max_iter, tol, d_steer, d_speed, d_status, d_u, d_xk, d_obj, d_duals, d_iters, d_warm_out);
     return check_hip(ctx, hipGetLastError(), "k_kmpc_qp launch");
 }
 

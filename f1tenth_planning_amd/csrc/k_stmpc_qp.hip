@@ -11,43 +11,24 @@
 //      in registers and steps them forward with A_t; each step writes its slab (7 x n) to LDS and every lane adds its two rows of
 //      H = 2 sum_t S_t' Q_t S_t (Qf at T) and of g.  The objective of :616-622 becomes 1/2 u'Hu + g'u + c over
 //      u = vec(u) = (steer_v_0, accel_0, steer_v_1, accel_1, ...), n = 2T.
-//   3. a primal-dual interior-point method (Mehrotra predictor-corrector) on  G u <= h  with the rows of :683-706.  A's rows 2 and 3
+//   3. the interior point of qp_ipm.h on  G u <= h  with the rows of :683-706.  A's rows 2 and 3
 //      are unit rows (B[2, 0] = B[3, 1] = DT, C[2] = C[3] = 0), so delta_t = delta0 + DT sum_{k<t} u0_k and v_t = v0 + DT sum_{k<t} u1_k
 //      exactly, and every row is a unit row, a first difference of u0 or a DT-scaled prefix sum:
 //        steer_v_t upper / lower, accel_t upper / lower (unit rows), delta_{t+1} upper / lower (prefix sums of u0),
 //        v_{t+1} upper / lower (prefix sums of u1), rate_t upper / lower (u0_{t+1} - u0_t, :685: no DT factor)
 //      (the t = 0 rows are constants: feasible iff |delta0| <= MAX_STEER and MIN_SPEED <= v0 <= MAX_SPEED, then u = 0 is feasible).
-//      Newton system (H + G' diag(lambda / s) G) du = rhs: the u0 block gets a diagonal, a tridiagonal (rate rows) and
+//      Newton matrix H + G' diag(lambda / s) G: the u0 block gets a diagonal, a tridiagonal (rate rows) and
 //      DT^2 (suffix sum over max(s, s')) (delta rows); the u1 block a diagonal and the same suffix-sum term (v rows); no u0-u1 term.
-//      G is never formed.  Factored by Cholesky in LDS.  Stopping rule, statuses and breakdown handling are k_kmpc_qp's.
+//      G is never formed.
 //
 // Mapping: one wave per ego; lane tau owns time step tau -- both inputs (rows 2 tau, 2 tau + 1 of H and of the Newton matrix) and the
 // ten inequality rows of step tau -- so T <= 64 on one wave; the LDS of H and the Newton matrix (2 n^2 doubles) bounds T at
 // F1P_STMPC_QP_MAX_T.  An ego's arithmetic depends on nothing outside its own workgroup: results are batch invariant.
-#include "f1p_internal.h"
+#include "qp_ipm.h"
 
 namespace f1p {
 
 namespace {
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ double wmax(double v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {                   // NaN-propagating: a broken-down ego never looks converged
-        const double o = __shfl_xor(v, m, 64);
-        v = (o > v || o != o) ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ double wmin(double v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = fmin(v, __shfl_xor(v, m, 64));
-    return v;
-}
 
 // Jacobian entries per step (get_dynamic_model_matrix :428-535); the unit diagonal of rows 0-4, A[4, 5] = B[2, 0] = B[3, 1] = DT are implicit
 enum { J03, J04, J06, J13, J14, J16, J52, J53, J55, J56, J62, J63, J65, J66, JB51, JB61, JC0, JC1, JC5, JC6, NJ };
@@ -113,7 +94,7 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
         const double d = pd_g ? pd_g[((size_t)e * T + k) * pstride] : 0.0;
         L.pa[k] = a; L.pd[k] = d; bad |= !(isfinite(a) && isfinite(d));
     }
-    bad = wmax(bad ? 1.0 : 0.0) > 0.0;
+    bad = gmax<64>(bad ? 1.0 : 0.0) > 0.0;
     __syncthreads();
     const double d0 = L.x0[2], v0 = L.x0[3];
     int st = bad ? 3 : (fabs(d0) <= cfg.max_steer && v0 >= cfg.min_speed && v0 <= cfg.max_speed) ? 0 : 1;   // 1: a t = 0 row cannot hold
@@ -185,7 +166,7 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
             for (int k = 0; k < 7; ++k) { x[k] = y[k]; L.fr[k * Tp + t + 1] = x[k]; nf |= !isfinite(x[k]); }
         }
     }
-    nf = wmax(nf ? 1.0 : 0.0) > 0.0;
+    nf = gmax<64>(nf ? 1.0 : 0.0) > 0.0;
     if (!done && nf) { st = 3; done = true; }            // non-finite model data (a predicted speed of 0)
     __syncthreads();
 
@@ -239,7 +220,7 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
     }
     __syncthreads();
 
-    // ---- 3. interior point ------------------------------------------------------------------------------------------------------------
+    // ---- 3. interior point (qp_ipm.h) ----------------------------------------------------------------------------------------------------
     const double MSV = cfg.max_steer_v;
     double h[10];
     bool valid[10];
@@ -247,78 +228,33 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
     h[4] = cfg.max_steer - d0; h[5] = cfg.max_steer + d0; h[6] = cfg.max_speed - v0; h[7] = v0 - cfg.min_speed; h[8] = MSV; h[9] = MSV;
 #pragma unroll
     for (int r = 0; r < 10; ++r) valid[r] = in_n && (r < 8 || tau < T - 1);
-    double u0 = 0.0, u1 = 0.0, s[10], lam[10];
-#pragma unroll
-    for (int r = 0; r < 10; ++r) { s[r] = valid[r] ? fmax(h[r], 1.0) : 1.0; lam[r] = valid[r] ? 1.0 : 0.0; }
-    double hmax = 0.0;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) hmax = fmax(hmax, valid[r] ? fabs(h[r]) : 0.0);
-    const double gn = 1.0 + wmax(in_n ? fmax(fabs(g0), fabs(g1)) : 0.0), hn = 1.0 + wmax(hmax);
-    const double m_rows = 10.0 * T - 2.0;
-    int it_done = 0;
 
-    auto publish2 = [&](double* vec, double a, double b) {
-        __syncthreads();
-        if (in_n) { vec[i0] = a; vec[i1] = b; }
-        __syncthreads();
-    };
     // G x for this lane's rows (x published in vec[])
-    auto gmul = [&](const double* vec, double x0v, double x1v, double out[10]) {
+    auto gmul = [&](const double* vec, const double (&x)[2], double (&out)[10]) {
         double p0 = 0.0, p1 = 0.0;
         if (in_n) for (int q = 0; q <= tau; ++q) { p0 += vec[2 * q]; p1 += vec[2 * q + 1]; }
-        const double r = in_n && tau < T - 1 ? vec[i0 + 2] - x0v : 0.0;
-        out[0] = x0v; out[1] = -x0v; out[2] = x1v; out[3] = -x1v;
+        const double r = in_n && tau < T - 1 ? vec[i0 + 2] - x[0] : 0.0;
+        out[0] = x[0]; out[1] = -x[0]; out[2] = x[1]; out[3] = -x[1];
         out[4] = DT * p0; out[5] = -(DT * p0); out[6] = DT * p1; out[7] = -(DT * p1); out[8] = r; out[9] = -r;
 #pragma unroll
         for (int k = 0; k < 10; ++k) out[k] = valid[k] ? out[k] : 0.0;
     };
     // (G' w) at u0_tau, u1_tau: the rows' differences published in Wd[], Wv[], Wr[]
-    auto gtmul = [&](const double w[10], double& o0, double& o1) {
+    auto gtmul = [&](const double (&w)[10], double (&o)[2]) {
         const double wd = valid[4] ? w[4] - w[5] : 0.0, wv = valid[6] ? w[6] - w[7] : 0.0, wr = valid[8] ? w[8] - w[9] : 0.0;
         __syncthreads();
         if (in_n) { L.Wd[tau] = wd; L.Wv[tau] = wv; L.Wr[tau] = wr; }
         __syncthreads();
-        o0 = o1 = 0.0;
+        o[0] = o[1] = 0.0;
         if (in_n) {
             double sd = 0.0, sv = 0.0;
             for (int q = T - 1; q >= tau; --q) { sd += L.Wd[q]; sv += L.Wv[q]; }
-            o0 = (valid[0] ? w[0] - w[1] : 0.0) + DT * sd - wr + (tau > 0 ? L.Wr[tau - 1] : 0.0);
-            o1 = (valid[2] ? w[2] - w[3] : 0.0) + DT * sv;
+            o[0] = (valid[0] ? w[0] - w[1] : 0.0) + DT * sd - wr + (tau > 0 ? L.Wr[tau - 1] : 0.0);
+            o[1] = (valid[2] ? w[2] - w[3] : 0.0) + DT * sv;
         }
     };
-
-    for (int it = 0;; ++it) {
-        // residuals
-        publish2(L.U, u0, u1);
-        double Gu[10], rp[10];
-        gmul(L.U, u0, u1, Gu);
-        double rpmax = 0.0, gap = 0.0;
-#pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            rp[r] = valid[r] ? Gu[r] + s[r] - h[r] : 0.0;
-            rpmax = fmax(rpmax, fabs(rp[r]));
-            gap += valid[r] ? s[r] * lam[r] : 0.0;
-        }
-        double Hu0 = 0.0, Hu1 = 0.0;
-        if (in_n) for (int c = 0; c < n; ++c) { Hu0 += L.H[i0 * n + c] * L.U[c]; Hu1 += L.H[i1 * n + c] * L.U[c]; }
-        double gl0, gl1;
-        gtmul(lam, gl0, gl1);
-        const double rd0 = in_n ? Hu0 + g0 + gl0 : 0.0, rd1 = in_n ? Hu1 + g1 + gl1 : 0.0;
-        const double rdn = wmax(fmax(fabs(rd0), fabs(rd1))) / gn, rpn = wmax(rpmax) / hn;
-        gap = wsum(gap);
-        const double f = wsum(in_n ? u0 * (0.5 * Hu0 + g0) + u1 * (0.5 * Hu1 + g1) : 0.0);
-        const bool res_ok = rdn <= tol && rpn <= tol;
-        const bool gap_rel_ok = res_ok && gap <= tol * (1.0 + fabs(f));
-        if (!done) {
-            if (res_ok && gap <= tol) { done = true; st = 0; it_done = it; }
-            else if (it >= max_iter) { done = true; st = 2; it_done = it; }
-        }
-        if (!__syncthreads_or(!done)) break;
-
-        // Newton matrix M = H + G' diag(lambda / s) G, rows i0 and i1, lower triangle
-        double D[10];
-#pragma unroll
-        for (int r = 0; r < 10; ++r) D[r] = valid[r] ? lam[r] / s[r] : 0.0;
+    // rows i0 and i1 of M = H + G' diag(D) G, lower triangle
+    auto newton_rows = [&](const double (&D)[10]) {
         __syncthreads();
         if (in_n) { L.Wd[tau] = D[4] + D[5]; L.Wv[tau] = D[6] + D[7]; L.Wr[tau] = D[8] + D[9]; }
         __syncthreads();
@@ -342,93 +278,20 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
                 L.M[i1 * n + c] = m1;
             }
         }
-        // Cholesky, in place: lower triangle of M = L
-        bool broke = false;
-        for (int k = 0; k < n; ++k) {
-            __syncthreads();
-            const double mk = L.M[k * n + k];
-            broke |= !(mk > 0.0 && mk < INFINITY);
-            const double dk = sqrt(mk);
-            double l0 = 0.0, l1 = 0.0;
-            if (in_n && i0 > k) { l0 = L.M[i0 * n + k] / dk; L.M[i0 * n + k] = l0; }
-            if (in_n && i1 > k) { l1 = L.M[i1 * n + k] / dk; L.M[i1 * n + k] = l1; }
-            __syncthreads();
-            if (k == i0 || k == i1) L.M[k * n + k] = dk;
-            if (in_n && i0 > k) for (int c = k + 1; c <= i0; ++c) L.M[i0 * n + c] -= l0 * L.M[c * n + k];
-            if (in_n && i1 > k) for (int c = k + 1; c <= i1; ++c) L.M[i1 * n + c] -= l1 * L.M[c * n + k];
-        }
-        __syncthreads();
-        if (broke && !done) { done = true; st = gap_rel_ok ? 0 : 2; it_done = it; }     // (broke is uniform over the wave)
+    };
 
-        // one Newton solve for the complementarity right-hand side rc
-        auto newton = [&](const double rc[10], double& du0, double& du1, double ds[10], double dl[10]) {
-            double w[10];
-#pragma unroll
-            for (int r = 0; r < 10; ++r) w[r] = valid[r] ? (lam[r] * rp[r] - rc[r]) / s[r] : 0.0;
-            double t0, t1;
-            gtmul(w, t0, t1);
-            double b0 = -rd0 - t0, b1 = -rd1 - t1;
-            for (int k = 0; k < n; ++k) {                // L y = b
-                if (k == i0) { b0 = b0 / L.M[k * n + k]; L.Y[k] = b0; }
-                if (k == i1) { b1 = b1 / L.M[k * n + k]; L.Y[k] = b1; }
-                __syncthreads();
-                if (in_n && i0 > k) b0 -= L.M[i0 * n + k] * L.Y[k];
-                if (in_n && i1 > k) b1 -= L.M[i1 * n + k] * L.Y[k];
-            }
-            for (int k = n - 1; k >= 0; --k) {           // L' x = y
-                if (k == i1) { b1 = b1 / L.M[k * n + k]; L.Y[k] = b1; }
-                if (k == i0) { b0 = b0 / L.M[k * n + k]; L.Y[k] = b0; }
-                __syncthreads();
-                if (in_n && i0 < k) b0 -= L.M[k * n + i0] * L.Y[k];
-                if (in_n && i1 < k) b1 -= L.M[k * n + i1] * L.Y[k];
-            }
-            du0 = in_n ? b0 : 0.0; du1 = in_n ? b1 : 0.0;
-            double Gd[10];
-            publish2(L.U, du0, du1);
-            gmul(L.U, du0, du1, Gd);
-#pragma unroll
-            for (int r = 0; r < 10; ++r) {
-                ds[r] = valid[r] ? -rp[r] - Gd[r] : 0.0;
-                dl[r] = valid[r] ? (-rc[r] - lam[r] * ds[r]) / s[r] : 0.0;
-            }
-        };
-        auto step_max = [&](const double ds[10], const double dl[10]) -> double {
-            double a = 1.0;
-#pragma unroll
-            for (int r = 0; r < 10; ++r) {
-                if (valid[r] && ds[r] < 0.0) a = fmin(a, -s[r] / ds[r]);
-                if (valid[r] && dl[r] < 0.0) a = fmin(a, -lam[r] / dl[r]);
-            }
-            return wmin(a);
-        };
-        const double mu = gap / m_rows;
-        double rc[10], du0, du1, ds[10], dl[10];
-#pragma unroll
-        for (int r = 0; r < 10; ++r) rc[r] = valid[r] ? s[r] * lam[r] : 0.0;
-        newton(rc, du0, du1, ds, dl);                    // predictor (affine scaling)
-        double a = step_max(ds, dl), gap_aff = 0.0;
-#pragma unroll
-        for (int r = 0; r < 10; ++r) gap_aff += valid[r] ? (s[r] + a * ds[r]) * (lam[r] + a * dl[r]) : 0.0;
-        gap_aff = wsum(gap_aff);
-        const double ratio = gap_aff / gap, sigma = ratio * ratio * ratio;
-#pragma unroll
-        for (int r = 0; r < 10; ++r) rc[r] = valid[r] ? s[r] * lam[r] + ds[r] * dl[r] - sigma * mu : 0.0;
-        newton(rc, du0, du1, ds, dl);                    // corrector
-        a = fmin(1.0, 0.99 * step_max(ds, dl));
-        if (!done) {
-            u0 += a * du0; u1 += a * du1;
-#pragma unroll
-            for (int r = 0; r < 10; ++r) if (valid[r]) { s[r] += a * ds[r]; lam[r] += a * dl[r]; }
-        }
-    }
+    const double gv[2] = {g0, g1};
+    double u[2], lam[10];
+    int it_done;
+    qp_ipm<64, 2, 10>(QpIpmLds{L.H, L.M, L.U, L.Y}, n, tau, gv, h, valid, 10.0 * T - 2.0, max_iter, tol, done, st, it_done, u, lam, gmul,
+                      gtmul, newton_rows);
 
     // ---- outputs --------------------------------------------------------------------------------------------------------------------
     const bool ok = st == 0 || st == 2;
-    publish2(L.U, u0, u1);
     if (in_n) {
-        if (u_out) { u_out[(size_t)e * n + i0] = ok ? u0 : NaN; u_out[(size_t)e * n + i1] = ok ? u1 : NaN; }
+        if (u_out) { u_out[(size_t)e * n + i0] = ok ? u[0] : NaN; u_out[(size_t)e * n + i1] = ok ? u[1] : NaN; }
         // the reference's (self.oa, self.odelta_v) = (u[1, :], u[0, :]) (:1089-1103); a failed solve leaves None: zeros next call
-        if (warm_out) { warm_out[(size_t)e * n + i0] = ok ? u1 : 0.0; warm_out[(size_t)e * n + i1] = ok ? u0 : 0.0; }
+        if (warm_out) { warm_out[(size_t)e * n + i0] = ok ? u[1] : 0.0; warm_out[(size_t)e * n + i1] = ok ? u[0] : 0.0; }
         if (duals) {
             // rate upper, rate lower (T-1 each), delta_1..T upper, lower, v_1..T upper, lower, steer_v upper, lower, accel upper, lower (T each)
             double* du_ = duals + (size_t)e * (10 * T - 2);
@@ -511,12 +374,8 @@ int launch_stmpc_qp(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const
                     double* d_x, double* d_obj, double* d_duals, int32_t* d_iters, double* d_warm_out) {
     if (E <= 0) return F1P_OK;
     const size_t lds = stmpc_qp_lds_bytes(cfg->horizon);
-    const void* kern = reinterpret_cast<const void*>(&k_stmpc_qp);
-    if (lds > (size_t)ctx->prop.sharedMemPerBlock) {
-        if (lds > (size_t)ctx->prop.maxSharedMemoryPerMultiProcessor)
-            return set_error(ctx, F1P_EINVAL, "stmpc qp: horizon too long for the CU's LDS");
-        F1P_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
+    const int rc = qp_lds_opt_in(ctx, reinterpret_cast<const void*>(&k_stmpc_qp), lds, "stmpc qp: horizon too long for the CU's LDS");
+    if (rc) return rc;
     hipLaunchKernelGGL(k_stmpc_qp, dim3((unsigned)E), dim3(64), lds, ctx->stream, d_x0, d_ref, d_pa, d_pd, pstride, E, *cfg, max_iter, tol,
                        d_steer, d_speed, d_status, d_u, d_x, d_obj, d_duals, d_iters, d_warm_out);
     return check_hip(ctx, hipGetLastError(), "k_stmpc_qp launch");
