@@ -21,8 +21,8 @@ def main():
         if args.solver != "qp":
             raise SystemExit("--tracks plans with STMPCPlanner.plan_batch, which needs --solver qp")
         args.envs = args.tracks
-    if args.envs != 1 and args.tracks == 0:
-        raise SystemExit("STMPCPlanner.plan drives one vehicle; use kinematic_mpc.py --envs N for the batched path")
+    if args.envs != 1 and args.tracks == 0 and args.solver != "shooting":
+        raise SystemExit("--envs N drives N vehicles with the shooting solver's plan_batch; with --solver qp use --tracks N")
     rl = common.raceline(args, centerline=True)
     planner = STMPCPlanner(waypoints=[rl[:, 0], rl[:, 1], rl[:, 3], rl[:, 2]], config=mpc_config(SOLVER=args.solver))
     if args.tracks > 0:
@@ -36,6 +36,9 @@ def main():
     def plan(obs, env):
         if lanes is not None:
             out = planner.plan_batch(env.state, tracks=lanes, track_ids=ids)
+            return np.column_stack([out["steer"], out["speed"]])
+        if args.envs > 1:                                      # one C call per step: controls generated on the GPU, one warm start per vehicle
+            out = planner.plan_batch(env.state, want_u=False)
             return np.column_stack([out["steer"], out["speed"]])
         steer, speed = planner.plan(env.sim.agents[0].state)
         return [[steer, speed]]

@@ -52,6 +52,20 @@ class KmpcSampler(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("call", C.c_uint32), ("use_warm", C.c_int32), ("sigma_accel", C.c_double), ("sigma_steer", C.c_double)]
 
 
+class StmpcSampler(C.Structure):
+    """struct f1p_stmpc_sampler (include/f1p.h)"""
+    _fields_ = [("seed", C.c_uint64), ("call", C.c_uint32), ("use_warm", C.c_int32), ("sigma_steer_v", C.c_double), ("sigma_accel", C.c_double),
+                ("sigma_steer", C.c_double), ("ego_offset", C.c_int32), ("reserved", C.c_int32)]
+
+
+def stmpc_sampler(seed=0, call=0, use_warm=True, sigma_steer_v=1.0, sigma_accel=1.5, sigma_steer=0.15, ego_offset=0):
+    s = StmpcSampler()
+    s.seed, s.call, s.use_warm = int(seed) & (2 ** 64 - 1), int(call) & 0xffffffff, 1 if use_warm else 0
+    s.sigma_steer_v, s.sigma_accel, s.sigma_steer = float(sigma_steer_v), float(sigma_accel), float(sigma_steer)
+    s.ego_offset, s.reserved = int(ego_offset), 0
+    return s
+
+
 def kmpc_sampler(seed=0, call=0, use_warm=True, sigma_accel=1.5, sigma_steer=0.15):
     s = KmpcSampler()
     s.seed, s.call, s.use_warm = int(seed) & (2 ** 64 - 1), int(call) & 0xffffffff, 1 if use_warm else 0
@@ -267,6 +281,13 @@ PROTOTYPES = {
     "f1p_stmpc_ref_batch": (C.c_int, [_P, _P, _I, _I, _D, _D, _P]),
     "f1p_stmpc_shoot_batch": (C.c_int, [_P, _P, _P, _P, _I, C.POINTER(StmpcCfg), _P, _P, _P, _P, _P]),
     "f1p_stmpc_shoot_dev": (C.c_int, [_P, _P, _P, _P, _I, C.POINTER(StmpcCfg), _P, _P, _P, _P, _P]),
+    "f1p_stmpc_gen_controls_dev": (C.c_int, [_P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(StmpcSampler)]),
+    "f1p_stmpc_plan_dev": (C.c_int, [_P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(StmpcSampler), _P, _P, _P, _P, _P]),
+    "f1p_stmpc_plan_batch": (C.c_int, [_P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcCfg), _D, _D, _D, C.POINTER(StmpcSampler), _P, _P, _P, _P,
+                                       _P, _P]),
+    "f1p_stmpc_warm_reset": (C.c_int, [_P]),
+    "f1p_stmpc_warm_get": (C.c_int, [_P, _P, _P, _I, _I, _I]),
+    "f1p_stmpc_warm_set": (C.c_int, [_P, _P, _P, _I, _I, _I]),
     "f1p_comm_unique_id": (C.c_int, [_P, _P]),
     "f1p_comm_init": (C.c_int, [_P, _P, _I, _I]),
     "f1p_comm_destroy": (C.c_int, [_P]),

@@ -108,6 +108,7 @@ class STMPCPlanner:
         self._device = device
         self._ctx = None
         self._calls = 0
+        self._batch_calls = 0
         _check_solver(config)
 
     def _context(self):
@@ -157,8 +158,28 @@ class STMPCPlanner:
         return ctx.stmpc_qp_plan(x0, self._dyn_cfg(), self._kin_cfg(), v_ks=c.V_KS, dl=c.dl, dlk=c.dlk,
                                  opts=_abi.kmpc_qp_opts(max_iter=c.QP_MAX_ITER, tol=c.QP_TOL), want_u=want_u)
 
+    def _shoot(self, ctx, x0, want_u=True):
+        """One C call per plan (f1p_stmpc_plan_batch): per ego the branch (:168), reference extraction (:195-276), R control sequences
+        generated in the kernels around the ego's warm start on the device (call counter = plans since reset()), rollouts through the
+        branch's model, argmin, output map (:1112-1117, :1205-1207), new warm start."""
+        c = self.config
+        smp = _abi.stmpc_sampler(seed=c.SEED, call=self._batch_calls, use_warm=True, sigma_steer_v=c.SIGMA_STEER_V, sigma_accel=c.SIGMA_ACCEL,
+                                 sigma_steer=c.SIGMA_STEER)
+        out = ctx.stmpc_plan(x0, self._dyn_cfg(), self._kin_cfg(), smp, v_ks=c.V_KS, dl=c.dl, dlk=c.dlk, want_seq=want_u)
+        self._batch_calls += 1
+        if want_u:
+            out["u"] = out.pop("best_seq")
+        return out
+
     def plan_batch(self, states, waypoints=None, want_u=True, tracks=None, track_ids=None):
-        """SOLVER == "qp": states [E, 7] -> dict(steer, speed, status, branch (1 dynamic, 0 kinematic), obj[, u [E, max(T, TK), 2] =
+        """SOLVER == "shooting" (the default): states [E, 7] -> dict(steer, speed, best_idx, best_cost, branch (1 dynamic, 0 kinematic)[, u
+        [E, max(T, TK), 2] = the winner's applied sequence, (steering speed, accel) in the dynamic branch and (accel, steer) in the
+        kinematic one, NaN past the branch's horizon]).  One C call: the controls are generated in the kernels (Philox, seeded by
+        mpc_config.SEED and the number of plans since reset()) around each ego's own warm start, which lives on the device -- the previous
+        winner shifted by one step; an ego that crosses V_KS starts its new branch from zeros.  An ego's result depends on that ego's state
+        and history alone, not on the batch around it.  plan() keeps its host-side sampler and has no warm start; a one-ego plan_batch is
+        the warm-started single-vehicle call.  `tracks` needs SOLVER='qp' (below).
+        SOLVER == "qp": states [E, 7] -> dict(steer, speed, status, branch (1 dynamic, 0 kinematic), obj[, u [E, max(T, TK), 2] =
         (oa, odelta_v), NaN past the branch's horizon]) -- per-ego status (0 solved, 1 infeasible, 2 not converged, 3 non-finite input
         or model data), never raised.
         tracks: K courses in the `waypoints` format ([x, y, yaw, v]: four 1-D arrays or an array [4, N]) with track_ids [E]: ego e
@@ -169,7 +190,10 @@ class STMPCPlanner:
         ctx.kmpc_shoot for the kinematic branch."""
         _check_solver(self.config)
         if self.config.SOLVER != "qp":
-            raise ValueError("plan_batch needs SOLVER='qp'")
+            if tracks is not None:
+                raise ValueError("plan_batch with tracks needs SOLVER='qp'")
+            ctx = self._bind(waypoints)
+            return self._shoot(ctx, np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 7), want_u=want_u)
         if tracks is not None:
             cols = self._track_columns(tracks, track_ids)
             ctx = self._context()
@@ -200,9 +224,11 @@ class STMPCPlanner:
     def reset(self):
         """forget the warm start (a new episode)"""
         self._calls = 0
+        self._batch_calls = 0
         self.oa = self.odelta_v = None
         if self._ctx is not None:
             self._ctx.stmpc_qp_warm_reset()
+            self._ctx.stmpc_warm_reset()
 
     def plan(self, states, waypoints=None):
         """states: [x, y, delta, v, yaw, yawrate, beta].  Returns (steering_angle, speed)."""

@@ -322,7 +322,7 @@ void f1p_destroy(f1p_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     f1p_comm_destroy(ctx);
-    void* ptrs[] = {ctx->d_wx, ctx->d_wy, ctx->d_wv, ctx->d_wpsi, ctx->d_wkappa, ctx->d_wbox, ctx->d_tx, ctx->d_ty, ctx->d_tv, ctx->d_tpsi, ctx->d_tkappa, ctx->d_tbox, ctx->d_ttab, ctx->d_bits, ctx->d_bits0, ctx->d_bits_clear, ctx->d_bb_scratch, ctx->d_arena, ctx->d_comm_key, ctx->d_comm_idx, ctx->d_kmpc_warm, ctx->d_kmpc_qp_warm, ctx->d_stmpc_qp_warm, ctx->d_kmpc_scratch, ctx->d_mix_scratch, ctx->d_split_scratch, ctx->d_rec_scratch, ctx->d_st_scratch, ctx->d_audit, ctx->d_audit_buf, ctx->d_cl_theta[0], ctx->d_cl_theta[1], ctx->d_step, ctx->d_comm_rec, ctx->d_order, ctx->d_kmpc_cfg};
+    void* ptrs[] = {ctx->d_wx, ctx->d_wy, ctx->d_wv, ctx->d_wpsi, ctx->d_wkappa, ctx->d_wbox, ctx->d_tx, ctx->d_ty, ctx->d_tv, ctx->d_tpsi, ctx->d_tkappa, ctx->d_tbox, ctx->d_ttab, ctx->d_bits, ctx->d_bits0, ctx->d_bits_clear, ctx->d_bb_scratch, ctx->d_arena, ctx->d_comm_key, ctx->d_comm_idx, ctx->d_kmpc_warm, ctx->d_kmpc_qp_warm, ctx->d_stmpc_qp_warm, ctx->d_stmpc_warm, ctx->d_kmpc_scratch, ctx->d_mix_scratch, ctx->d_split_scratch, ctx->d_rec_scratch, ctx->d_st_scratch, ctx->d_audit, ctx->d_audit_buf, ctx->d_cl_theta[0], ctx->d_cl_theta[1], ctx->d_step, ctx->d_comm_rec, ctx->d_order, ctx->d_kmpc_cfg};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -2292,6 +2292,223 @@ int f1p_stmpc_shoot_batch(f1p_ctx* ctx, const double* x0, const double* ref, con
     double* d_bc = s.out(best_cost, e); double* d_bs = s.out(best_seq, e * T * 2);
     if ((rc = launch_stmpc_shoot(ctx, d_x0, d_ref, d_c, E, cfg, d_steer, d_speed, d_bi, d_bc, d_bs))) return rc;
     return s.finish();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// the dynamic MPC's shooting solver with in-kernel control generation and a per-ego warm start on the device
+// ---------------------------------------------------------------------------------------------------
+static int validate_st_sampler(f1p_ctx* ctx, const f1p_stmpc_sampler* smp) {
+    if (!smp) return set_error(ctx, F1P_EINVAL, "sampler is NULL");
+    const double sg[3] = {smp->sigma_steer_v, smp->sigma_accel, smp->sigma_steer};
+    for (const double v : sg)
+        if (!(v >= 0.0) || !isfinite(v)) return set_error(ctx, F1P_EINVAL, "sampler sigmas must be finite and >= 0");
+    if (smp->ego_offset < 0) return set_error(ctx, F1P_EINVAL, "sampler ego_offset must be >= 0");
+    return F1P_OK;
+}
+
+// the ctx's warm start for (E, T, TK): E + 1 rows of max(T, TK) x 2 floats -- the last row stays zero (the row every ego reads when a
+// call generates without a warm start and must not write one).  A change of shape drops the old contents.
+static int ensure_st_warm(f1p_ctx* ctx, int E, int T, int TK) {
+    if (ctx->d_stmpc_warm && ctx->stmpc_warm_E == E && ctx->stmpc_warm_T == T && ctx->stmpc_warm_TK == TK) return F1P_OK;
+    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->d_stmpc_warm) (void)hipFree(ctx->d_stmpc_warm);
+    ctx->d_stmpc_warm = nullptr; ctx->stmpc_warm_E = ctx->stmpc_warm_T = ctx->stmpc_warm_TK = 0;
+    const size_t bytes = sizeof(float) * 2 * (size_t)(T > TK ? T : TK) * ((size_t)E + 1);
+    ctx->stmpc_warm_tag.assign((size_t)E, 0);
+    F1P_HIP(ctx, hipMalloc((void**)&ctx->d_stmpc_warm, bytes));
+    F1P_HIP(ctx, hipMemsetAsync(ctx->d_stmpc_warm, 0, bytes, ctx->stream));
+    ctx->stmpc_warm_E = E; ctx->stmpc_warm_T = T; ctx->stmpc_warm_TK = TK;
+    return F1P_OK;
+}
+
+// the buffer of a dynamic-only call: whatever TK the ctx's plans use, as long as E and T are the call's
+static int ensure_st_warm_dyn(f1p_ctx* ctx, int E, int T) {
+    if (ctx->d_stmpc_warm && ctx->stmpc_warm_E == E && ctx->stmpc_warm_T == T && ctx->stmpc_warm_TK <= T) return F1P_OK;
+    return ensure_st_warm(ctx, E, T, 0);
+}
+
+int f1p_stmpc_gen_controls_dev(f1p_ctx* ctx, float* d_controls, int32_t E, const f1p_stmpc_cfg* cfg, const f1p_stmpc_sampler* smp) {
+    F1P_ENTER(ctx);
+    int rc = validate_stmpc(ctx, cfg, E); if (rc) return rc;
+    if ((rc = validate_st_sampler(ctx, smp))) return rc;
+    if (E == 0) return F1P_OK;
+    if (!d_controls) return set_error(ctx, F1P_EINVAL, "controls is NULL");
+    const int T = cfg->horizon;
+    if ((rc = ensure_st_warm_dyn(ctx, E, T))) return rc;
+    const int ws = 2 * (ctx->stmpc_warm_T > ctx->stmpc_warm_TK ? ctx->stmpc_warm_T : ctx->stmpc_warm_TK);
+    bool all = smp->use_warm != 0, none = !smp->use_warm;
+    for (int e = 0; e < E && smp->use_warm; ++e) { if (ctx->stmpc_warm_tag[e] != 2) all = false; else none = false; }
+    float* zero_row = ctx->d_stmpc_warm + (size_t)E * ws;
+    if (all) return launch_stmpc_gen_controls(ctx, d_controls, E, cfg, smp, ctx->d_stmpc_warm, ws);
+    if (none) return launch_stmpc_gen_controls(ctx, d_controls, E, cfg, smp, zero_row, 0);
+    // some egos hold a dynamic warm start, the others start from zeros: ego by ego (a mixed state only a plan_batch leaves behind)
+    f1p_stmpc_sampler s1 = *smp;
+    for (int e = 0; e < E; ++e) {
+        s1.ego_offset = smp->ego_offset + e;
+        float* row = ctx->stmpc_warm_tag[e] == 2 ? ctx->d_stmpc_warm + (size_t)e * ws : zero_row;
+        if ((rc = launch_stmpc_gen_controls(ctx, d_controls + (size_t)e * T * 2 * cfg->n_rollouts, 1, cfg, &s1, row, 0))) return rc;
+    }
+    return F1P_OK;
+}
+
+int f1p_stmpc_plan_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, int32_t E, const f1p_stmpc_cfg* cfg,
+                       const f1p_stmpc_sampler* smp, double* d_steer, double* d_speed, int32_t* d_best_idx, double* d_best_cost,
+                       double* d_best_seq) {
+    F1P_ENTER(ctx);
+    int rc = validate_stmpc(ctx, cfg, E); if (rc) return rc;
+    if ((rc = validate_st_sampler(ctx, smp))) return rc;
+    if (E == 0) return F1P_OK;
+    if (!d_x0 || !d_ref || !d_steer || !d_speed || !d_best_idx) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and best_idx are required");
+    if ((rc = ensure_st_warm_dyn(ctx, E, cfg->horizon))) return rc;
+    const size_t ws = 2 * (size_t)(ctx->stmpc_warm_T > ctx->stmpc_warm_TK ? ctx->stmpc_warm_T : ctx->stmpc_warm_TK);
+    // the egos that start over: all of them (one memset), or the few a plan_batch left in the other branch
+    size_t n_restart = 0;
+    for (int e = 0; e < E; ++e) n_restart += !smp->use_warm || ctx->stmpc_warm_tag[e] != 2;
+    if (n_restart == (size_t)E) {
+        F1P_HIP(ctx, hipMemsetAsync(ctx->d_stmpc_warm, 0, sizeof(float) * ws * (size_t)E, ctx->stream));
+    } else if (n_restart) {
+        for (int e = 0; e < E; ++e)
+            if (ctx->stmpc_warm_tag[e] != 2) F1P_HIP(ctx, hipMemsetAsync(ctx->d_stmpc_warm + (size_t)e * ws, 0, sizeof(float) * ws, ctx->stream));
+    }
+    std::fill(ctx->stmpc_warm_tag.begin(), ctx->stmpc_warm_tag.end(), 0);    // (a failed launch leaves no half-written warm start behind as valid)
+    rc = launch_stmpc_plan_gen(ctx, d_x0, d_ref, E, cfg, smp, ctx->d_stmpc_warm, (int)ws, nullptr, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
+    if (rc == F1P_OK) std::fill(ctx->stmpc_warm_tag.begin(), ctx->stmpc_warm_tag.end(), 2);
+    else (void)hipMemsetAsync(ctx->d_stmpc_warm, 0, sizeof(float) * ws * (size_t)E, ctx->stream);
+    return rc;
+}
+
+int f1p_stmpc_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_stmpc_cfg* dcfg, const f1p_kmpc_cfg* kcfg, double v_ks,
+                         double dl, double dlk, const f1p_stmpc_sampler* smp, double* steer, double* speed, int32_t* best_idx,
+                         double* best_cost, int32_t* branch, double* best_seq) {
+    F1P_ENTER(ctx);
+    int rc = validate_stmpc(ctx, dcfg, E); if (rc) return rc;
+    if ((rc = validate_kmpc(ctx, kcfg, E))) return rc;
+    if ((rc = validate_st_sampler(ctx, smp))) return rc;
+    if (kcfg->n_rollouts > 8192) return set_error(ctx, F1P_EINVAL, "at most 8192 rollouts per kinematic plan");
+    if (E > 0 && (!x0 || !steer || !speed || !best_idx)) return set_error(ctx, F1P_EINVAL, "x0, steer, speed and best_idx are required");
+    if (!(dl > 0) || !(dlk > 0)) return set_error(ctx, F1P_EINVAL, "dl and dlk must be > 0");
+    if (ctx->n_wp < 2 || !ctx->has_psi) return set_error(ctx, F1P_ESTATE, "waypoints with a heading column are required");
+    if (E == 0) return F1P_OK;
+    const int T = dcfg->horizon, TK = kcfg->horizon, W = T > TK ? T : TK;
+    if ((rc = ensure_st_warm(ctx, E, T, TK))) return rc;
+    // the model switch (:168) and the restart rule, on the host
+    std::vector<int32_t> idx[2], restart;
+    for (int e = 0; e < E; ++e) {
+        const int dyn = !(x0[(size_t)e * 7 + 3] <= v_ks);
+        idx[dyn].push_back(e);
+        if (!smp->use_warm || ctx->stmpc_warm_tag[e] != (dyn ? 2 : 1)) restart.push_back(e);
+        ctx->stmpc_warm_tag[e] = 0;                                          // until the plan is known to have been issued
+    }
+    const size_t nd = idx[1].size(), nk = idx[0].size(), nr = restart.size();
+    size_t need = al256(4 * nr);
+    for (int b = 0; b < 2; ++b) {
+        const size_t nb = idx[b].size(), Tb = b ? T : TK;
+        need += al256(4 * nb) + al256(8 * 4 * nb) + al256(8 * 7 * (Tb + 1) * nb) + 3 * al256(8 * nb) + al256(4 * nb) + al256(8 * 2 * Tb * nb);
+    }
+    need += al256(8 * 7 * nd) + al256(8 * 4 * (size_t)(TK + 1) * nk);
+    if ((rc = arena_reset(ctx, need))) return rc;
+    // the uploads below read host vectors of this frame: no return before the stream has drained
+    auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->stream); return code; };
+    if (nr) {
+        int32_t* d_rows = (int32_t*)arena_take(ctx, 4 * nr);
+        if (hipError_t e_ = hipMemcpyAsync(d_rows, restart.data(), 4 * nr, hipMemcpyHostToDevice, ctx->stream)) return fail(check_hip(ctx, e_, "stmpc plan upload"));
+        if ((rc = launch_stmpc_warm_zero(ctx, ctx->d_stmpc_warm, d_rows, (int)nr, 2 * W))) return fail(rc);
+    }
+    std::vector<double> hx[2], h7(nd * 7);
+    double *d_steer[2], *d_speed[2], *d_bc[2], *d_bs[2];
+    int32_t* d_bi[2];
+    f1p_kmpc_sampler ks;
+    ks.seed = smp->seed; ks.call = smp->call; ks.use_warm = 1; ks.sigma_accel = smp->sigma_accel; ks.sigma_steer = smp->sigma_steer;
+    for (int b = 0; b < 2; ++b) {                                             // b = 1: dynamic (:181-191), b = 0: kinematic (:168-180)
+        const size_t nb = idx[b].size(), Tb = b ? T : TK;
+        if (nb == 0) continue;
+        int32_t* d_idx = (int32_t*)arena_take(ctx, 4 * nb);
+        double* d_s4 = (double*)arena_take(ctx, 8 * 4 * nb);
+        double* d_ref7 = (double*)arena_take(ctx, 8 * 7 * (Tb + 1) * nb);
+        d_steer[b] = (double*)arena_take(ctx, 8 * nb); d_speed[b] = (double*)arena_take(ctx, 8 * nb); d_bc[b] = (double*)arena_take(ctx, 8 * nb);
+        d_bi[b] = (int32_t*)arena_take(ctx, 4 * nb);
+        d_bs[b] = (double*)arena_take(ctx, 8 * 2 * Tb * nb);
+        hx[b].resize(nb * 4);
+        for (size_t k = 0; k < nb; ++k) {
+            const double* s = x0 + (size_t)idx[b][k] * 7;
+            hx[b][4 * k] = s[0]; hx[b][4 * k + 1] = s[1]; hx[b][4 * k + 2] = s[3]; hx[b][4 * k + 3] = s[4];     // (x, y, v, yaw)
+        }
+        if (hipError_t e_ = hipMemcpyAsync(d_idx, idx[b].data(), 4 * nb, hipMemcpyHostToDevice, ctx->stream)) return fail(check_hip(ctx, e_, "stmpc plan upload"));
+        if (hipError_t e_ = hipMemcpyAsync(d_s4, hx[b].data(), 8 * 4 * nb, hipMemcpyHostToDevice, ctx->stream)) return fail(check_hip(ctx, e_, "stmpc plan upload"));
+        if (b) {
+            double* d_x7 = (double*)arena_take(ctx, 8 * 7 * nb);
+            for (size_t k = 0; k < nb; ++k) memcpy(&h7[7 * k], x0 + (size_t)idx[b][k] * 7, 7 * sizeof(double));
+            if (hipError_t e_ = hipMemcpyAsync(d_x7, h7.data(), 8 * 7 * nb, hipMemcpyHostToDevice, ctx->stream)) return fail(check_hip(ctx, e_, "stmpc plan upload"));
+            if ((rc = launch_stmpc_ref(ctx, d_s4, (int)nb, T, dcfg->dt, dl, d_ref7))) return fail(rc);                                 // :195-233
+            if ((rc = launch_stmpc_plan_gen(ctx, d_x7, d_ref7, (int)nb, dcfg, smp, ctx->d_stmpc_warm, 2 * W, d_idx, d_steer[b], d_speed[b], d_bi[b],
+                                            d_bc[b], d_bs[b]))) return fail(rc);
+        } else {
+            double* d_ref4 = (double*)arena_take(ctx, 8 * 4 * (Tb + 1) * nb);
+            if ((rc = launch_stmpc_ref(ctx, d_s4, (int)nb, TK, kcfg->dt, dlk, d_ref7))) return fail(rc);                               // :195-233 with (TK, DTK, dlk)
+            if ((rc = launch_stmpc_qp_kref(ctx, d_ref7, (int)nb, TK, d_ref4))) return fail(rc);                                        // rows 0, 1, 3, 4
+            if ((rc = launch_kmpc_plan_gen(ctx, d_s4, d_ref4, (int)nb, kcfg, &ks, ctx->d_stmpc_warm, ctx->d_stmpc_warm, d_steer[b], d_speed[b], d_bi[b],
+                                           d_bc[b], d_bs[b], d_idx, 2 * W, (uint32_t)smp->ego_offset))) return fail(rc);
+        }
+    }
+    // results: each branch's compact arrays -> the caller's order
+    std::vector<double> hs[2], hv[2], hc[2], hq[2];
+    std::vector<int32_t> hi[2];
+    for (int b = 0; b < 2; ++b) {
+        const size_t nb = idx[b].size(), Tb = b ? T : TK;
+        if (nb == 0) continue;
+        hs[b].resize(nb); hv[b].resize(nb); hc[b].resize(nb); hi[b].resize(nb);
+        F1P_HIP(ctx, hipMemcpyAsync(hs[b].data(), d_steer[b], 8 * nb, hipMemcpyDeviceToHost, ctx->stream));
+        F1P_HIP(ctx, hipMemcpyAsync(hv[b].data(), d_speed[b], 8 * nb, hipMemcpyDeviceToHost, ctx->stream));
+        F1P_HIP(ctx, hipMemcpyAsync(hi[b].data(), d_bi[b], 4 * nb, hipMemcpyDeviceToHost, ctx->stream));
+        if (best_cost) F1P_HIP(ctx, hipMemcpyAsync(hc[b].data(), d_bc[b], 8 * nb, hipMemcpyDeviceToHost, ctx->stream));
+        if (best_seq) { hq[b].resize(nb * 2 * Tb); F1P_HIP(ctx, hipMemcpyAsync(hq[b].data(), d_bs[b], 8 * 2 * Tb * nb, hipMemcpyDeviceToHost, ctx->stream)); }
+    }
+    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const double NaN = nan("");
+    for (int b = 0; b < 2; ++b) {
+        const size_t Tb = b ? T : TK;
+        for (size_t k = 0; k < idx[b].size(); ++k) {
+            const int e = idx[b][k];
+            steer[e] = hs[b][k]; speed[e] = hv[b][k]; best_idx[e] = hi[b][k];
+            if (best_cost) best_cost[e] = hc[b][k];
+            if (branch) branch[e] = b;
+            ctx->stmpc_warm_tag[e] = b ? 2 : 1;
+            if (best_seq) {
+                double* ue = best_seq + (size_t)e * W * 2;
+                for (size_t j = 0; j < (size_t)W * 2; ++j) ue[j] = j < 2 * Tb ? hq[b][k * 2 * Tb + j] : NaN;
+            }
+        }
+    }
+    return F1P_OK;
+}
+
+int f1p_stmpc_warm_reset(f1p_ctx* ctx) {
+    if (!ctx) return F1P_EINVAL;
+    std::fill(ctx->stmpc_warm_tag.begin(), ctx->stmpc_warm_tag.end(), 0);    // (a row whose tag is not its branch's is zeroed by the plan that reads it)
+    return F1P_OK;
+}
+
+int f1p_stmpc_warm_get(f1p_ctx* ctx, float* warm, int32_t* tag, int32_t E, int32_t T, int32_t TK) {
+    F1P_ENTER(ctx);
+    if (!warm || !tag) return set_error(ctx, F1P_EINVAL, "warm / tag is NULL");
+    if (!ctx->d_stmpc_warm || ctx->stmpc_warm_E != E || ctx->stmpc_warm_T != T || ctx->stmpc_warm_TK != TK)
+        return set_error(ctx, F1P_ESTATE, "no stmpc warm start of this shape is held");
+    F1P_HIP(ctx, hipMemcpyAsync(warm, ctx->d_stmpc_warm, sizeof(float) * 2 * (size_t)E * (T > TK ? T : TK), hipMemcpyDeviceToHost, ctx->stream));
+    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(tag, ctx->stmpc_warm_tag.data(), sizeof(int32_t) * (size_t)E);
+    return F1P_OK;
+}
+
+int f1p_stmpc_warm_set(f1p_ctx* ctx, const float* warm, const int32_t* tag, int32_t E, int32_t T, int32_t TK) {
+    F1P_ENTER(ctx);
+    if (!warm || !tag || E < 1 || T < 1 || TK < 0) return set_error(ctx, F1P_EINVAL, "bad warm / tag / E / T / TK");
+    for (int e = 0; e < E; ++e)
+        if (tag[e] < 0 || tag[e] > 2) return set_error(ctx, F1P_EINVAL, "tag must be 0, 1 or 2");
+    int rc = ensure_st_warm(ctx, E, T, TK); if (rc) return rc;
+    F1P_HIP(ctx, hipMemcpyAsync(ctx->d_stmpc_warm, warm, sizeof(float) * 2 * (size_t)E * (T > TK ? T : TK), hipMemcpyHostToDevice, ctx->stream));
+    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(ctx->stmpc_warm_tag.data(), tag, sizeof(int32_t) * (size_t)E);
+    return F1P_OK;
 }
 
 }  // extern "C"

@@ -90,6 +90,12 @@ struct f1p_ctx {
     double* d_stmpc_qp_warm = nullptr;
     int stmpc_qp_warm_E = 0, stmpc_qp_warm_W = 0;
     std::vector<int32_t> stmpc_qp_len;
+    // the dynamic-MPC shooting plan (f1p_stmpc_plan_*): f32 warm start [E][W][2], W = max(T, TK), keyed by (E, T, TK), and per ego the
+    // branch that wrote its row -- 0: none (zeros are generated around), 1: kinematic ([TK][2] = (accel, steer)), 2: dynamic
+    // ([T][2] = (steering speed, accel)) -- on the host, where the branch split is made.  One allocation, one guard.
+    float* d_stmpc_warm = nullptr;
+    int stmpc_warm_E = 0, stmpc_warm_T = 0, stmpc_warm_TK = 0;
+    std::vector<int32_t> stmpc_warm_tag;
 
     // two-kernel branch and bound of the lattice planner: bounds and clothoids handed from the fit kernel to the evaluation kernel
     char* d_bb_scratch = nullptr;
@@ -213,7 +219,10 @@ int launch_kmpc_shoot(f1p_ctx* ctx, const double* d_x0, const double* d_ref, con
                       double* d_best_cost, double* d_best_seq);
 int launch_kmpc_plan_gen(f1p_ctx* ctx, const double* d_x0, const double* d_ref, int E, const f1p_kmpc_cfg* cfg,
                          const f1p_kmpc_sampler* smp, const float* d_warm_in, float* d_warm_out, double* d_steer, double* d_speed,
-                         int32_t* d_best_idx, double* d_best_cost, double* d_best_seq);
+                         int32_t* d_best_idx, double* d_best_cost, double* d_best_seq,
+                         // d_ids [E] (nullable): the launch is a compacted list, ego e is ego d_ids[e] of the caller's batch -- generator ego word
+                         // d_ids[e] + ego_off, warm rows at d_ids[e] * wstride floats (k_kmpc_plan_gen_idx; the dynamic MPC's kinematic branch)
+                         const int32_t* d_ids = nullptr, int wstride = 0, uint32_t ego_off = 0u);
 int launch_kmpc_gen_controls(f1p_ctx* ctx, float* d_controls, int E, const f1p_kmpc_cfg* cfg, const f1p_kmpc_sampler* smp, const float* d_warm);
 int kmpc_plan_groups(const f1p_ctx* ctx, int E, int R);
 // k_kmpc_qp.hip: prev (oa, od) read at pa[(e T + t) pstride], pd[...] (nullable: zeros); every output but steer / speed nullable
@@ -242,6 +251,13 @@ int launch_stmpc_predict(f1p_ctx* ctx, const double* d_x0, const double* d_oa, c
 int launch_stmpc_shoot(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const float* d_controls, int E, const f1p_stmpc_cfg* cfg,
                        double* d_steer, double* d_speed, int32_t* d_best_idx, double* d_best_cost, double* d_best_seq);
 int launch_stmpc_ref(f1p_ctx* ctx, const double* d_states, int E, int horizon, double dt, double dl, double* d_ref);
+// k_stmpc.hip, generated controls: d_warm rows of wstride floats ([T][2] = (steering speed, accel) used), read as the warm start (zeros =
+// none) and overwritten with the next one; d_ids [E] (nullable): ego e of the launch is ego d_ids[e] of the caller's batch
+int launch_stmpc_plan_gen(f1p_ctx* ctx, const double* d_x0, const double* d_ref, int E, const f1p_stmpc_cfg* cfg, const f1p_stmpc_sampler* smp,
+                          float* d_warm, int wstride, const int32_t* d_ids, double* d_steer, double* d_speed, int32_t* d_best_idx,
+                          double* d_best_cost, double* d_best_seq);
+int launch_stmpc_gen_controls(f1p_ctx* ctx, float* d_controls, int E, const f1p_stmpc_cfg* cfg, const f1p_stmpc_sampler* smp, float* d_warm, int wstride);
+int launch_stmpc_warm_zero(f1p_ctx* ctx, float* d_warm, const int32_t* d_rows, int n, int wstride);
 // k_tracks.hip: the trackers over the ctx's track set, ego e on track d_tid[e]
 struct TrackSetDev {
     const double *x, *y, *v, *psi, *kappa, *box;   // psi / kappa null when the set has no such column

@@ -10,6 +10,7 @@
 // State, cost and the previous applied control stay in registers for the whole horizon.  This is the
 // HBM-streaming kernel of the path: 8 B of controls per rollout-step, fp64 arithmetic on them.
 #include "f1p_internal.h"
+#include "shoot_gen.h"
 
 #ifndef F1P_K4_RING
 #define F1P_K4_RING 3                 // register buffers of the streamed filter's prefetch ring (3: two chunks in flight; 4 measured beside it)
@@ -41,8 +42,7 @@ __device__ __forceinline__ double clampd(double v, double lo, double hi) { retur
 // Rollout 0 is the unperturbed warm start (previous solution shifted by one step, kinematic_mpc.py:491-498), rollout 1 is all
 // zero.  The bounds (:391-401) are applied by the rollout's projection, exactly as for streamed controls.
 // ---------------------------------------------------------------------------------------------------
-#define F1P_IH_MEAN 510.0f                     // 4 bytes x 127.5
-#define F1P_IH_INV_STD 0.0067658765f           // 1 / sqrt(4 (256^2 - 1) / 12) = 1 / 147.80054, rounded to f32 (same literal in the oracle)
+// F1P_IH_MEAN / F1P_IH_INV_STD, philox4x32_10 and SrcGenT: shoot_gen.h (shared with k_stmpc.hip)
 
 struct SrcStream {
     const float* __restrict__ ce;
@@ -61,61 +61,6 @@ struct SrcStream {
         get(FULL || te + 1 < T ? te + 1 : T - 1, r, a1, d1);
     }
 };
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t& o0, uint32_t& o1, uint32_t& o2, uint32_t& o3) {
-    // the 32 x 32 -> 64 products as ONE v_mad_u64_u32 each: the compiler's v_mul_lo_u32 + v_mul_hi_u32 pair costs 1.5x as much
-    // (tools/microbench/intops.hip: 6.5 + 6.4 against 8.5 time units), and Philox is most of this kernel's instructions
-    const uint32_t m0 = 0xD2511F53u, m1 = 0xCD9E8D57u;
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        unsigned long long p0, p1;
-        asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p0) : "s"(m0), "v"(c0) : "vcc");
-        asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p1) : "s"(m1), "v"(c2) : "vcc");
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;          // (gfx950 has no v_xor3_b32: two xors per word)
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o0 = c0; o1 = c1; o2 = c2; o3 = c3;
-}
-
-// WARM_SET: `warm` is never null (k_kmpc_plan_gen's LDS copy, zero-filled without a warm start) -- no null test, hence no branch
-// around each of the filter's warm-start reads (each one used to end a basic block, and with it the scheduler's view)
-template <bool WARM_SET>
-struct SrcGenT {
-    uint32_t k0, k1, call, ego;
-    float sig_a, sig_d;
-    const float* warm;          // [T][2] (accel, steer) of this ego, LDS or global; nullptr = no warm start (zeros)
-    static constexpr int chunk = 6;               // six steps (three Philox calls per rollout) per basic block: 0.0467 ms against 0.048 with 2 or 4
-    __device__ __forceinline__ void one(int t, int r, uint32_t xa, uint32_t xd, float& a, float& d) const {
-        // sum of the word's 4 bytes minus 510, the mean folded into v_sad_u8's accumulator: integers of magnitude <= 510, exact in
-        // f32 either way, so (float)(sum - 510) is the same value as (float)sum - 510.0f without the v_add_f32
-        const float za = (float)(int)__builtin_amdgcn_sad_u8(xa, 0u, (uint32_t)-(int)F1P_IH_MEAN) * F1P_IH_INV_STD;
-        const float zd = (float)(int)__builtin_amdgcn_sad_u8(xd, 0u, (uint32_t)-(int)F1P_IH_MEAN) * F1P_IH_INV_STD;
-        const float wa = WARM_SET || warm ? warm[2 * t] : 0.0f, wd = WARM_SET || warm ? warm[2 * t + 1] : 0.0f;
-        // rollout 0 = the warm start itself, rollout 1 = all zero, as per-lane FACTORS instead of two compares + two selects per
-        // control (r is fixed per lane for the whole rollout, so the factors fold into loop-invariant registers): sigma -> 0 for
-        // r < 2, warm -> 0 for r = 1.  fma(0, z, w) = w and fma(0, z, w * 0) = +-0 exactly: the same controls, bit for bit in value.
-        const float fs = r < 2 ? 0.0f : 1.0f, fw = r == 1 ? 0.0f : 1.0f;
-        a = __builtin_fmaf(sig_a * fs, za, wa * fw);
-        d = __builtin_fmaf(sig_d * fs, zd, wd * fw);
-    }
-    __device__ __forceinline__ void get(int t, int r, float& a, float& d) const {
-        uint32_t x0, x1, x2, x3;
-        philox4x32_10((uint32_t)(t >> 1), (uint32_t)r, ego, call, k0, k1, x0, x1, x2, x3);
-        one(t, r, (t & 1) ? x2 : x0, (t & 1) ? x3 : x1, a, d);
-    }
-    // steps te and te + 1 (te even) from ONE Philox call; steps >= T are generated like any other (and unused).  FULL: te + 1 < T
-    template <bool FULL = false>
-    __device__ __forceinline__ void get2(int te, int T, int r, float& a0, float& d0, float& a1, float& d1) const {
-        uint32_t x0, x1, x2, x3;
-        philox4x32_10((uint32_t)(te >> 1), (uint32_t)r, ego, call, k0, k1, x0, x1, x2, x3);
-        const int tb = FULL || te + 1 < T ? te + 1 : te;              // warm[] has T rows
-        one(FULL || te < T ? te : T - 1, r, x0, x1, a0, d0);
-        one(FULL || tb < T ? tb : T - 1, r, x2, x3, a1, d1);
-    }
-};
-typedef SrcGenT<false> SrcGen;
 
 // fp64 cost of ONE rollout r: running sum in the reference's accumulation order
 template <bool FAST, typename Src>
@@ -798,133 +743,30 @@ struct KmpcGenArgs {
     int G, Rs;
 };
 
-__global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void k_kmpc_plan_gen(const double* __restrict__ x0, const double* __restrict__ ref, int E,
-                                                       f1p_kmpc_cfg cfg, KmpcF32 kf, KmpcGenArgs ga,
-                                                       double* __restrict__ steer, double* __restrict__ speed,
-                                                       int32_t* __restrict__ best_idx, double* __restrict__ best_cost,
-                                                       double* __restrict__ best_seq, int32_t* __restrict__ n_refined,
-                                                       const f1p_kmpc_cfg* __restrict__ dcfg) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int T = cfg.horizon, R = cfg.n_rollouts, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
-    float* sref32 = reinterpret_cast<float*>(lds_raw);                // [4][T+1] relative to the ego state, f32
-    float* warm_s = sref32 + 4 * (T + 1);                             // [T][2] this ego's warm start
-    float* red_f = warm_s + 2 * T;                                    // [4]
-    int* list = reinterpret_cast<int*>(red_f + 4);                    // [F1P_K4_MAX_REFINE]
-    int* cnt = list + F1P_K4_MAX_REFINE;                              // [2]: survivors, "this workgroup is the last one"
-    double* sref = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(cnt + 2) + 7) & ~(uintptr_t)7);   // fp64 refinement scratch
-    float* c32 = reinterpret_cast<float*>(sref + 4 * (T + 1) + 4 + 2);   // [R] filter costs (G == 1: LDS only)
-    const int e = blockIdx.x / ga.G, g = blockIdx.x - e * ga.G;
-    if (e >= E) return;
-#ifdef F1P_K4_PHASES     // shader-clock stamps at the phase boundaries -> n_refined-shaped debug rows in ga.cost32 (tools/kmpc_phases.py)
-    long long tph[8]; int nph = 0;
-#define F1P_KPH() do { tph[nph++] = clock64(); } while (0)
-#define F1P_KPH_OUT() do { F1P_KPH(); if (tid == 0 && ga.cost32 && ga.G == 1) { for (int k_ = 0; k_ + 1 < nph; ++k_) ga.cost32[(size_t)e * R + k_] = (float)(tph[k_ + 1] - tph[k_]); ga.cost32[(size_t)e * R + 7] = (float)(tph[0] & 0xffffff); ga.cost32[(size_t)e * R + 8] = (float)(tph[nph - 1] & 0xffffff); for (int k_ = 0; k_ < 11; ++k_) ga.cost32[(size_t)e * R + 24 + k_] = (float)(f1p_kst[k_ + 1] - f1p_kst[k_]); ga.cost32[(size_t)e * R + 35] = (float)(f1p_kst[0] - tph[nph - 2]); } if (lane == 0 && ga.cost32 && ga.G == 1) { ga.cost32[(size_t)e * R + 10 + wave] = (float)(__builtin_amdgcn_s_getreg(63492) & 0xffff); ga.cost32[(size_t)e * R + 14 + wave] = (float)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xf); ga.cost32[(size_t)e * R + 18 + wave] = (float)(clock64() - tph[0]); } } while (0)
-#else
-#define F1P_KPH() do {} while (0)
-#define F1P_KPH_OUT() do {} while (0)
-#endif
-    F1P_KPH();
-    const double sx = x0[4 * e], sy = x0[4 * e + 1], sv = x0[4 * e + 2], syaw = x0[4 * e + 3];
-    for (int q = tid; q < 2 * T; q += blockDim.x) warm_s[q] = ga.warm_in ? ga.warm_in[(size_t)e * 2 * T + q] : 0.0f;
-    SrcGenT<true> src;
-    src.k0 = ga.k0; src.k1 = ga.k1; src.call = ga.call; src.ego = (uint32_t)e; src.sig_a = ga.sig_a; src.sig_d = ga.sig_d;
-    src.warm = warm_s;
-    float* warm_out = ga.warm_out ? ga.warm_out + (size_t)e * 2 * T : nullptr;
-    const bool in_range = fabs(syaw) <= 1.0e4 && fabs(cfg.max_steer) <= 1.0e4 && kf.w_ok;     // workgroup-uniform: the fast paths' ranges
-    double s0d, c0d;
-    sincos_core(in_range ? syaw : 0.0, &s0d, &c0d);
-    const bool poly = kf.max_steer <= 0.45f;
-    const bool iso = poly && kf.sq[0] == kf.sq[1] && kf.sqf[0] == kf.sqf[1];
-    for (int q = tid; q < 4 * (T + 1); q += blockDim.x) {
-        const double rv = ref[(size_t)e * 4 * (T + 1) + q];
-        sref[q] = rv;                                                 // the fp64 rows the refinement reads (no second trip to memory at the kernel's tail)
-        const int row = q / (T + 1), col = q - row * (T + 1);
-        sref32[q] = kmpc_ref32(kf, row, col == T, kmpc_rel_ref(ref + (size_t)e * 4 * (T + 1), T, row, col, rv, sx, sy, syaw, iso, c0d, s0d));
-    }
-    if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
-    __syncthreads();
-    KmpcF32 k = kf;
-    k.c0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, (float)c0d)));
-    k.s0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, (float)s0d)));
-    k.v0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, (float)sv)));
+// k_kmpc_plan_gen: ego e of the launch is ego e of the batch.  k_kmpc_plan_gen_idx (the kinematic branch of f1p_stmpc_plan_batch): the
+// launch covers a compacted list of egos of a larger batch, ego e of the launch is ego ids[e] of that batch -- the generator's ego
+// word is ids[e] + ego_off and its warm start the row ids[e] of a buffer with wstride floats per ego, so an ego's plan is the one it
+// would get wherever it stands in the list.
+struct KmpcIdxArgs { const int32_t* ids; int wstride; uint32_t ego_off; };
 
-    F1P_KPH();
-    // ---- pass A: f32 filter over this workgroup's slice ---------------------------------------------------------------
-    const int r_lo = g * ga.Rs, r_hi = min(R, r_lo + ga.Rs);
-    float* cost_out = ga.G > 1 ? ga.cost32 + (size_t)e * R : c32;
-    float fmin_ = __builtin_huge_valf();                              // G == 1: this thread's minimum, straight from the filter's registers
-    if (in_range) {
-        const int half = (r_hi - r_lo + 1) >> 1;                      // rollouts r and r + half share the packed lanes
-        for (int q = tid; q < half; q += blockDim.x) {
-            const int r = r_lo + q, r1 = r + half < r_hi ? r + half : r;
-            const f1p_f2 c = iso ? kmpc_rollout_cost_f32x2<true, true>(src, sref32, k, T, r, r1)
-                                 : (poly ? kmpc_rollout_cost_f32x2<true, false>(src, sref32, k, T, r, r1) : kmpc_rollout_cost_f32x2<false, false>(src, sref32, k, T, r, r1));
-            cost_out[r] = c.x;
-            if (r1 != r) cost_out[r1] = c.y;
-            fmin_ = fminf(fmin_, fminf(c.x, c.y));                     // NaN costs are ignored here and caught below (r1 == r: c.y repeats c.x)
-#ifndef F1P_K4_PHASES
-            if (ga.G == 1 && ga.cost32) { ga.cost32[(size_t)e * R + r] = c.x; if (r1 != r) ga.cost32[(size_t)e * R + r1] = c.y; }
-#endif
-        }
-    }
-    F1P_KPH();
-    if (ga.G > 1) {
-        __threadfence();                                              // this workgroup's costs are visible device-wide ...
-        __syncthreads();
-        if (tid == 0) {
-            const unsigned int t_ = atomicAdd(&ga.tickets[e], 1u);    // ... before its ticket is
-            cnt[1] = (t_ == (unsigned int)ga.G - 1u) ? 1 : 0;
-            if (cnt[1]) ga.tickets[e] = 0u;                           // ready for the next launch (stream-ordered)
-        }
-        __syncthreads();
-        if (!cnt[1]) return;
-        __threadfence();
-    } else {
-        __syncthreads();
-    }
-
-    F1P_KPH();
-    // ---- second stage (the ego's last workgroup): minimum -> near-minimum set -> fp64 refinement ------------------------
-    // (round 5: ONE inlined copy of the refinement and one of the emission -- there were three and one; n_eff = -1: every rollout in fp64)
-    int n_eff = -1;
-    if (in_range) {
-        if (ga.G > 1) {
-            fmin_ = __builtin_huge_valf();
-            for (int r = tid; r < R; r += blockDim.x)
-                fmin_ = fminf(fmin_, __builtin_bit_cast(float, __hip_atomic_load(reinterpret_cast<const int*>(cost_out + r), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
-        }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) fmin_ = fminf(fmin_, __shfl_xor(fmin_, m, 64));
-        if (lane == 0) red_f[wave] = fmin_;
-        __syncthreads();
-        fmin_ = red_f[0];
-        for (int w = 1; w < nwaves; ++w) fmin_ = fminf(fmin_, red_f[w]);
-        const float thr = fmin_ + (fabsf(fmin_) * fminf(F1P_K4_MARGIN_REL * (float)T, 0.5f) + F1P_K4_MARGIN_ABS);
-        for (int r = tid; r < R; r += blockDim.x) {
-            float c;
-            if (ga.G > 1) c = __builtin_bit_cast(float, __hip_atomic_load(reinterpret_cast<const int*>(cost_out + r), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            else c = cost_out[r];
-            if (!(c > thr)) {                                              // includes NaN
-                const int pos = atomicAdd(cnt, 1);
-                if (pos < F1P_K4_MAX_REFINE) list[pos] = r;
-            }
-        }
-        __syncthreads();
-        const int n = cnt[0];
-        n_eff = (n > F1P_K4_MAX_REFINE || n < 1 || !isfinite(fmin_)) ? -1 : n;   // pathological inputs, degenerate ties: all rollouts in fp64
-    }
-    F1P_KPH();
-    const f1p_kmpc_cfg& s_cfg = *dcfg;                               // (the device copy: see k_kmpc_shoot_mixed)
-    if (n_eff == 1 && !best_cost) {
-        // a single survivor needs no fp64 cost unless it is asked for
-        kmpc_emit_wave(src, s_cfg, sv, s_cfg.max_dsteer * s_cfg.dt, e, list[0], 0.0, steer, speed, best_idx, nullptr, best_seq, warm_out);
-        if (tid == 0 && n_refined) n_refined[e] = 1;
-    } else {
-        // the survivors in ascending rollout order: the atomic list is in arrival order, the decision (first minimum) is by index
-        kmpc_refine_block(ref, src, s_cfg, sx, sy, sv, syaw, e, n_eff, list, sref, steer, speed, best_idx, best_cost, best_seq, n_refined, warm_out, true);
-    }
-    F1P_KPH_OUT();
-}
+#define F1P_KPG_NAME k_kmpc_plan_gen
+#define F1P_KPG_EXTRA
+#define F1P_KPG_EGO (uint32_t)e
+#define F1P_KPG_WROW (size_t)e * 2 * T
+#include "k_kmpc_plan_gen_text.h"
+#undef F1P_KPG_NAME
+#undef F1P_KPG_EXTRA
+#undef F1P_KPG_EGO
+#undef F1P_KPG_WROW
+#define F1P_KPG_NAME k_kmpc_plan_gen_idx
+#define F1P_KPG_EXTRA KmpcIdxArgs ia,
+#define F1P_KPG_EGO ((uint32_t)ia.ids[e] + ia.ego_off)
+#define F1P_KPG_WROW ((size_t)ia.ids[e] * ia.wstride)
+#include "k_kmpc_plan_gen_text.h"
+#undef F1P_KPG_NAME
+#undef F1P_KPG_EXTRA
+#undef F1P_KPG_EGO
+#undef F1P_KPG_WROW
 
 // materialise SrcGen's controls as the [E][T][2][R] f32 buffer of the streamed entry points (tests: generated == streamed)
 __global__ __launch_bounds__(256) void k_kmpc_gen_controls(float* __restrict__ controls, int E, int T, int R, KmpcGenArgs ga) {
@@ -1189,7 +1031,7 @@ int kmpc_plan_groups(const f1p_ctx* ctx, int E, int R) {
 
 int launch_kmpc_plan_gen(f1p_ctx* ctx, const double* d_x0, const double* d_ref, int E, const f1p_kmpc_cfg* cfg,
                          const f1p_kmpc_sampler* smp, const float* d_warm_in, float* d_warm_out, double* d_steer, double* d_speed,
-                         int32_t* d_best_idx, double* d_best_cost, double* d_best_seq) {
+                         int32_t* d_best_idx, double* d_best_cost, double* d_best_seq, const int32_t* d_ids, int wstride, uint32_t ego_off) {
     if (E <= 0) return F1P_OK;
     const size_t T1 = (size_t)cfg->horizon + 1, T = cfg->horizon, R = cfg->n_rollouts;
     KmpcGenArgs ga = make_gen_args(smp);
@@ -1224,8 +1066,12 @@ int launch_kmpc_plan_gen(f1p_ctx* ctx, const double* d_x0, const double* d_ref, 
     lds = (lds + 15) & ~(size_t)15;
     if (lds > (size_t)ctx->prop.sharedMemPerBlock) return set_error(ctx, F1P_EINVAL, "horizon / n_rollouts need more LDS than a workgroup has: use fewer rollouts per plan");
     if (const int rc = ensure_kmpc_cfg(ctx, cfg)) return rc;
-    hipLaunchKernelGGL(k_kmpc_plan_gen, dim3((unsigned)((size_t)E * ga.G)), dim3(block), lds, ctx->stream, d_x0, d_ref, E, *cfg, make_kf(cfg), ga,
-                       d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_nref, ctx->d_kmpc_cfg_cur);
+    if (d_ids)
+        hipLaunchKernelGGL(k_kmpc_plan_gen_idx, dim3((unsigned)((size_t)E * ga.G)), dim3(block), lds, ctx->stream, d_x0, d_ref, E, *cfg, make_kf(cfg), ga,
+                           KmpcIdxArgs{d_ids, wstride, ego_off}, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_nref, ctx->d_kmpc_cfg_cur);
+    else
+        hipLaunchKernelGGL(k_kmpc_plan_gen, dim3((unsigned)((size_t)E * ga.G)), dim3(block), lds, ctx->stream, d_x0, d_ref, E, *cfg, make_kf(cfg), ga,
+                           d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_nref, ctx->d_kmpc_cfg_cur);
     return check_hip(ctx, hipGetLastError(), "k_kmpc_plan_gen launch");
 }
 

@@ -4,7 +4,9 @@
 // its objective (:616-622), bounds (:685-706) applied as a projection of each sampled control sequence, and the output
 // map (:1112-1117).  Same mapping as K4 (k_kmpc.hip): one 256-thread workgroup per ego, one thread per rollout, f32
 // controls [ego][t][steering speed | accel][rollout] streamed from HBM, the 7-row reference in LDS, fp64 arithmetic.
+// f1p_stmpc_plan_* runs the same kernels' text with the controls GENERATED in registers (the *_gen kernels).
 #include "f1p_internal.h"
+#include "shoot_gen.h"
 
 namespace f1p {
 
@@ -29,78 +31,41 @@ __global__ __launch_bounds__(256) void k_stmpc_predict(const double* __restrict_
     }
 }
 
-// all rollouts of this thread, first-minimum argmin (objective :616-622, bounds :685-706 as a projection)
-template <bool FAST>
-__device__ __forceinline__ void stmpc_rollouts(const float* __restrict__ ce, const double* sref, const f1p_stmpc_cfg& cfg, const DynConst& k,
-                                               const DynState& s0, int tid, double& bc, int& bi) {
-    const int T = cfg.horizon, R = cfg.n_rollouts;
-    for (int r = tid; r < R; r += blockDim.x) {
-        DynState s = s0;
-        double cost = 0.0, pdv = 0.0, pa = 0.0;
-        for (int t = 0; t < T; ++t) {
-            double dv = clampd2((double)ce[((size_t)t * 2 + 0) * R + r], -cfg.max_steer_v, cfg.max_steer_v);   // :701-703
-            double a = clampd2((double)ce[((size_t)t * 2 + 1) * R + r], -cfg.max_accel, cfg.max_accel);        // :704-706
-            if (t > 0) dv = clampd2(dv, pdv - cfg.max_steer_v, pdv + cfg.max_steer_v);                         // :685
-            const double sv[7] = {s.x, s.y, s.delta, s.v, s.yaw, s.yr, s.beta};
-            double q = 0.0;
-#pragma unroll
-            for (int j = 0; j < 7; ++j) { const double er = sv[j] - sref[j * (T + 1) + t]; q += cfg.q[j] * er * er; }   // :619
-            cost += q;
-            cost += cfg.r[0] * dv * dv + cfg.r[1] * a * a;                                                       // :616
-            if (t > 0) { const double d0 = dv - pdv, d1 = a - pa; cost += cfg.rd[0] * d0 * d0 + cfg.rd[1] * d1 * d1; }   // :622
-            dyn_step<FAST>(s, a, dv, cfg, k);
-            pdv = dv; pa = a;
-        }
-        const double sv[7] = {s.x, s.y, s.delta, s.v, s.yaw, s.yr, s.beta};
-        double q = 0.0;
-#pragma unroll
-        for (int j = 0; j < 7; ++j) { const double er = sv[j] - sref[j * (T + 1) + T]; q += cfg.qf[j] * er * er; }
-        cost += q;
-        if (argmin_better(cost, r, bc, bi)) { bc = cost; bi = r; }
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Where a rollout's controls come from (the seam of k_kmpc.hip's SrcStream / SrcGen, for the dynamic model's channels):
+//   streamed : the f32 buffer [t][steering speed | accel][rollout] of one ego in HBM (f1p_stmpc_shoot_*);
+//   generated: in registers from (seed, call, ego, rollout, t) around the ego's warm start (f1p_stmpc_plan_*; shoot_gen.h: channel 0 =
+//              steering speed with sigma sig_dv, channel 1 = accel with sig_a).  The filter, the refinement, the all-fp64 fallback and
+//              the winner's re-emission call the same pure function, so they all see the same controls and no controls buffer exists.
+// The shooting kernels are compiled once per source from k_stmpc_shoot_text.h (below).
+// StCtlGen is the generating kernels' parameter.  ids (nullable): the launch is a compacted list of a larger batch, ego e of the launch
+// is ego ids[e] of that batch.  The generator's ego word is the ego's index in the caller's batch (+ ego_off: the batch is itself a
+// shard of a larger one), its warm start the row of that index in `warm` (wstride floats per ego, [T][2] = (steering speed, accel)
+// used; all zero = none): an ego's plan depends on that ego alone.  The decision kernel overwrites the row with the next warm start.
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct StCtlGen {
+    uint32_t k0, k1, call, ego_off;
+    float sig_dv, sig_a;
+    float* warm;
+    const int32_t* ids;
+    int wstride;
+    __device__ __forceinline__ int row(int e) const { return ids ? ids[e] : e; }
+    __device__ __forceinline__ float* warm_row(int e) const { return warm + (size_t)row(e) * wstride; }
+    __device__ __forceinline__ SrcGenT<true> src(int e, const float* w) const {
+        SrcGenT<true> s;
+        s.k0 = k0; s.k1 = k1; s.call = call; s.ego = (uint32_t)row(e) + ego_off; s.sig_a = sig_dv; s.sig_d = sig_a;   // (SrcGenT calls its channels 0 / 1 "a" / "d")
+        s.warm = w;
+        return s;
     }
-}
-
-__global__ __launch_bounds__(256) void k_stmpc_shoot(const double* __restrict__ x0, const double* __restrict__ ref,
-                                                     const float* __restrict__ controls, int E, f1p_stmpc_cfg cfg,
-                                                     double* __restrict__ steer, double* __restrict__ speed,
-                                                     int32_t* __restrict__ best_idx, double* __restrict__ best_cost,
-                                                     double* __restrict__ best_seq) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    double* sref = reinterpret_cast<double*>(lds_raw);   // [7][T+1]
-    double* red_d = sref + 7 * (cfg.horizon + 1);
-    int* red_i = reinterpret_cast<int*>(red_d + 4);
-    const int e = blockIdx.x;
-    if (e >= E) return;
-    const int T = cfg.horizon, R = cfg.n_rollouts, tid = threadIdx.x;
-    for (int q = tid; q < 7 * (T + 1); q += blockDim.x) sref[q] = ref[(size_t)e * 7 * (T + 1) + q];
-    __syncthreads();
-    const DynConst k = dyn_const(cfg);
-    DynState s0;
-    s0.x = x0[7 * e]; s0.y = x0[7 * e + 1]; s0.delta = x0[7 * e + 2]; s0.v = x0[7 * e + 3]; s0.yaw = x0[7 * e + 4];
-    s0.yr = x0[7 * e + 5]; s0.beta = x0[7 * e + 6];
-    const float* ce = controls + (size_t)e * T * 2 * R;
-    double bc = __builtin_huge_val(); int bi = 0x7fffffff;
-    if (fabs(cfg.max_steer) <= 1.0e4) stmpc_rollouts<true>(ce, sref, cfg, k, s0, tid, bc, bi);     // workgroup-uniform
-    else stmpc_rollouts<false>(ce, sref, cfg, k, s0, tid, bc, bi);
-    block_argmin(bc, bi, red_d, red_i);
-    if (tid == 0) {
-        double pdv = 0.0;
-        for (int t = 0; t < T; ++t) {
-            double dv = clampd2((double)ce[((size_t)t * 2 + 0) * R + bi], -cfg.max_steer_v, cfg.max_steer_v);
-            const double a = clampd2((double)ce[((size_t)t * 2 + 1) * R + bi], -cfg.max_accel, cfg.max_accel);
-            if (t > 0) dv = clampd2(dv, pdv - cfg.max_steer_v, pdv + cfg.max_steer_v);
-            if (t == 0) {
-                steer[e] = s0.delta + dv * cfg.dt;   // :1112
-                speed[e] = s0.v + a * cfg.dt;        // :1117
-            }
-            if (best_seq) { best_seq[((size_t)e * T + t) * 2] = dv; best_seq[((size_t)e * T + t) * 2 + 1] = a; }
-            else if (t == 0) break;
-            pdv = dv;
-        }
-        best_idx[e] = bi;
-        if (best_cost) best_cost[e] = bc;
-    }
-}
+};
+// the generated source of the fp64 paths, read the way the shooting text reads a step: its steering speed, then its accel.  dv(t, r)
+// makes the step's one Philox call and keeps the accel; a() hands it out and must follow dv() of the same step (the text's order).
+struct StGenSrc {
+    SrcGenT<true> g;
+    mutable float a_;
+    __device__ __forceinline__ float dv(int t, int r) const { float v; g.get(t, r, v, a_); return v; }
+    __device__ __forceinline__ float a() const { return a_; }
+};
 
 // ===================================================================================================================
 // Round 3: f32 filter + fp64 decision for the dynamic single-track shooting (the pattern of k_kmpc_shoot_mixed / the lattice
@@ -141,35 +106,6 @@ struct DynF32 {
 // a wave-uniform f32 in a VGPR: VALU instructions with an SGPR operand issue in 4.3 cycles instead of 2.5 (profiles/r03_valu_issue_cycles.txt)
 __device__ __forceinline__ float in_vgpr(float x) { float r; asm("v_mov_b32 %0, %1" : "=v"(r) : "s"(x)); return r; }
 
-// fp64 cost of ONE rollout: the body of stmpc_rollouts for a given r (same operations, same order)
-template <bool FAST>
-__device__ __forceinline__ double stmpc_one_rollout(const float* __restrict__ ce, const double* sref, const f1p_stmpc_cfg& cfg, const DynConst& k,
-                                                    const DynState& s0, int r) {
-    const int T = cfg.horizon, R = cfg.n_rollouts;
-    DynState s = s0;
-    double cost = 0.0, pdv = 0.0, pa = 0.0;
-    for (int t = 0; t < T; ++t) {
-        double dv = clampd2((double)ce[((size_t)t * 2 + 0) * R + r], -cfg.max_steer_v, cfg.max_steer_v);
-        double a = clampd2((double)ce[((size_t)t * 2 + 1) * R + r], -cfg.max_accel, cfg.max_accel);
-        if (t > 0) dv = clampd2(dv, pdv - cfg.max_steer_v, pdv + cfg.max_steer_v);
-        const double sv[7] = {s.x, s.y, s.delta, s.v, s.yaw, s.yr, s.beta};
-        double q = 0.0;
-#pragma unroll
-        for (int j = 0; j < 7; ++j) { const double er = sv[j] - sref[j * (T + 1) + t]; q += cfg.q[j] * er * er; }
-        cost += q;
-        cost += cfg.r[0] * dv * dv + cfg.r[1] * a * a;
-        if (t > 0) { const double d0 = dv - pdv, d1 = a - pa; cost += cfg.rd[0] * d0 * d0 + cfg.rd[1] * d1 * d1; }
-        dyn_step<FAST>(s, a, dv, cfg, k);
-        pdv = dv; pa = a;
-    }
-    const double sv[7] = {s.x, s.y, s.delta, s.v, s.yaw, s.yr, s.beta};
-    double q = 0.0;
-#pragma unroll
-    for (int j = 0; j < 7; ++j) { const double er = sv[j] - sref[j * (T + 1) + T]; q += cfg.qf[j] * er * er; }
-    cost += q;
-    return cost;
-}
-
 // f32 cost of one rollout in ego-relative coordinates; trusted = the speed stayed in the stable range of the reference's integrator.
 // sref8: [T+1][8] floats (x - x0, y - y0, delta, v, yaw - yaw0, yr, beta, -) so one step's reference is two ds_read_b128.
 // NR rollouts of one thread side by side (r, r + stride, ...).  At 4 waves per SIMD one chain per wave leaves a third of the issue slots
@@ -178,6 +114,47 @@ __device__ __forceinline__ double stmpc_one_rollout(const float* __restrict__ ce
 // 0.105 ms per plan against 0.101 for one chain (and 0.090 with the configuration in VGPRs): NR = 1 is what runs.
 // QM: bit j set = row j of the state carries weight in q or qf (compile-time: the reference's own weights leave delta, yr and beta
 // unweighted, three of the seven terms of every step)
+// one step of the f32 filter for rollout slot i, as text: the stage cost of the OLD state, then the step (dynamic_mpc.py:317-404; B_i = dt A_i,
+// the angle in revolutions for the hardware sin / cos).  Expects dv, a (this step's controls after the bounds :701-706; the rate limit :685
+// is applied here), t, r0 / r1 (the step's reference row), k and the state arrays.  A macro so that the streamed and the generating rollout
+// share it while the streamed function's tokens stay exactly what they were.
+#define F1P_ST_F32_STEP(i) \
+            if (t > 0) dv = __builtin_amdgcn_fmed3f(dv, pdv[i] - k.max_steer_v, pdv[i] + k.max_steer_v); \
+            { \
+                const float sv_[7] = {x[i], y[i], delta[i], v[i], yaw[i], yr[i], beta[i]}, rf_[7] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z}; \
+                float qs = 0.f; \
+_Pragma("unroll") \
+                for (int j = 0; j < 7; ++j) if (QM & (1 << j)) { const float er = sv_[j] - rf_[j]; qs += k.q[j] * er * er; } \
+                cost[i] += qs; \
+            } \
+            cost[i] += k.r[0] * dv * dv + k.r[1] * a * a; \
+            if (t > 0) { const float d0 = dv - pdv[i], d1 = a - pa[i]; cost[i] += k.rd[0] * d0 * d0 + k.rd[1] * d1 * d1; } \
+            trusted[i] &= v[i] >= k.v_trust; \
+            const float B1 = k.ap[0] + k.aq[0] * a, B2 = k.ap[1] + k.aq[1] * a, B3 = k.ap[2] + k.aq[2] * a; \
+            const float B4 = k.ap[3] + k.aq[3] * a, B5 = k.ap[4] + k.aq[4] * a, B6 = k.ap[5] + k.aq[5] * a; \
+            const float ang = (yaw[i] + beta[i]) * 0.15915494309189535f; \
+            const float sn_r = __builtin_amdgcn_sinf(ang), cs_r = __builtin_amdgcn_cosf(ang); \
+            const float cs = k.c0 * cs_r - k.s0 * sn_r, sn = k.s0 * cs_r + k.c0 * sn_r; \
+            float tn; \
+            if (POLY) { \
+                const float d2 = delta[i] * delta[i]; \
+                tn = delta[i] * (1.0f + d2 * (0.33333333f + d2 * (0.13333333f + d2 * (0.053968254f + d2 * (0.021869489f + d2 * 0.0088632355f))))); \
+            } else { \
+                const float dr = delta[i] * 0.15915494309189535f; \
+                tn = __builtin_amdgcn_sinf(dr) * __builtin_amdgcn_rcpf(__builtin_amdgcn_cosf(dr)); \
+            } \
+            const float iv = __builtin_amdgcn_rcpf(v[i]); \
+            const float vdt = v[i] * k.dt; \
+            const float x_new = x[i] + vdt * cs, y_new = y[i] + vdt * sn; \
+            const float delta_new = __builtin_amdgcn_fmed3f(delta[i] + dv * k.dt, -k.max_steer, k.max_steer); \
+            const float v_new = __builtin_amdgcn_fmed3f(v[i] + a * k.dt, k.min_speed, k.max_speed); \
+            const float yaw_new = yaw[i] + (v[i] * k.dt_inv_wb) * tn; \
+            const float yri = yr[i] * iv; \
+            const float yr_new = yr[i] + (B1 * delta[i] + B2 * beta[i] - B3 * yri); \
+            const float beta_new = (beta[i] - yr[i] * k.dt) + (B4 * delta[i] - B5 * beta[i] + B6 * yri) * iv; \
+            x[i] = x_new; y[i] = y_new; delta[i] = delta_new; v[i] = v_new; yaw[i] = yaw_new; yr[i] = yr_new; beta[i] = beta_new; \
+            pdv[i] = dv; pa[i] = a;
+
 template <bool POLY, int NR, int QM>
 __device__ __forceinline__ void stmpc_rollout_f32(const float* __restrict__ ce, const float* sref8, const DynF32& k, int T, int R, const int (&rr)[NR],
                                                   float delta0, float v0, float yr0, float beta0, float (&cost_out)[NR], bool (&trusted)[NR]) {
@@ -200,42 +177,50 @@ __device__ __forceinline__ void stmpc_rollout_f32(const float* __restrict__ ce, 
             const float a = __builtin_amdgcn_fmed3f(n_a[i], -k.max_accel, k.max_accel);
             cp[i] += 2 * (size_t)R;
             if (t + 1 < T) { n_dv[i] = cp[i][0]; n_a[i] = cp[i][R]; }   // (two steps ahead measured slower: 0.094 against 0.089 ms per plan)
-            if (t > 0) dv = __builtin_amdgcn_fmed3f(dv, pdv[i] - k.max_steer_v, pdv[i] + k.max_steer_v);
-            {
-                const float sv_[7] = {x[i], y[i], delta[i], v[i], yaw[i], yr[i], beta[i]}, rf_[7] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z};
-                float qs = 0.f;
+            F1P_ST_F32_STEP(i)
+        }
+    }
+    const float4 r0 = sr[2 * T], r1 = sr[2 * T + 1];
 #pragma unroll
-                for (int j = 0; j < 7; ++j) if (QM & (1 << j)) { const float er = sv_[j] - rf_[j]; qs += k.q[j] * er * er; }
-                cost[i] += qs;
+    for (int i = 0; i < NR; ++i) {
+        const float sv_[7] = {x[i], y[i], delta[i], v[i], yaw[i], yr[i], beta[i]}, rf_[7] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z};
+        float qs = 0.f;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) if (QM & (1 << j)) { const float er = sv_[j] - rf_[j]; qs += k.qf[j] * er * er; }
+        cost_out[i] = cost[i] + qs;
+    }
+}
+
+// the same rollout with its controls GENERATED: one Philox4x32-10 call per pair of steps (SrcGenT::get2), nothing fetched but the step's
+// warm-start row (LDS, wave-uniform address).  Same signature as the streamed function; R is unused.
+template <bool POLY, int NR, int QM>
+__device__ __forceinline__ void stmpc_rollout_f32_gen(const SrcGenT<true>& ce, const float* sref8, const DynF32& k, int T, int R, const int (&rr)[NR],
+                                                      float delta0, float v0, float yr0, float beta0, float (&cost_out)[NR], bool (&trusted)[NR]) {
+#pragma clang fp contract(fast)
+    (void)R;
+    float x[NR], y[NR], delta[NR], v[NR], yaw[NR], yr[NR], beta[NR], cost[NR], pdv[NR], pa[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        x[i] = 0.f; y[i] = 0.f; delta[i] = delta0; v[i] = v0; yaw[i] = 0.f; yr[i] = yr0; beta[i] = beta0; cost[i] = 0.f; pdv[i] = 0.f; pa[i] = 0.f;
+        trusted[i] = true;
+    }
+    const float4* sr = reinterpret_cast<const float4*>(sref8);
+    for (int te = 0; te < T; te += 2) {
+        float c_dv[NR][2], c_a[NR][2];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) ce.get2(te, T, rr[i], c_dv[i][0], c_a[i][0], c_dv[i][1], c_a[i][1]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int t = te + h;
+            if (t < T) {
+                const float4 r0 = sr[2 * t], r1 = sr[2 * t + 1];
+#pragma unroll
+                for (int i = 0; i < NR; ++i) {
+                    float dv = __builtin_amdgcn_fmed3f(c_dv[i][h], -k.max_steer_v, k.max_steer_v);
+                    const float a = __builtin_amdgcn_fmed3f(c_a[i][h], -k.max_accel, k.max_accel);
+                    F1P_ST_F32_STEP(i)
+                }
             }
-            cost[i] += k.r[0] * dv * dv + k.r[1] * a * a;
-            if (t > 0) { const float d0 = dv - pdv[i], d1 = a - pa[i]; cost[i] += k.rd[0] * d0 * d0 + k.rd[1] * d1 * d1; }
-            trusted[i] &= v[i] >= k.v_trust;
-            // the step (dynamic_mpc.py:317-404) from the OLD state; B_i = dt A_i
-            const float B1 = k.ap[0] + k.aq[0] * a, B2 = k.ap[1] + k.aq[1] * a, B3 = k.ap[2] + k.aq[2] * a;
-            const float B4 = k.ap[3] + k.aq[3] * a, B5 = k.ap[4] + k.aq[4] * a, B6 = k.ap[5] + k.aq[5] * a;
-            const float ang = (yaw[i] + beta[i]) * 0.15915494309189535f;    // revolutions
-            const float sn_r = __builtin_amdgcn_sinf(ang), cs_r = __builtin_amdgcn_cosf(ang);
-            const float cs = k.c0 * cs_r - k.s0 * sn_r, sn = k.s0 * cs_r + k.c0 * sn_r;
-            float tn;
-            if (POLY) {
-                const float d2 = delta[i] * delta[i];
-                tn = delta[i] * (1.0f + d2 * (0.33333333f + d2 * (0.13333333f + d2 * (0.053968254f + d2 * (0.021869489f + d2 * 0.0088632355f)))));
-            } else {
-                const float dr = delta[i] * 0.15915494309189535f;
-                tn = __builtin_amdgcn_sinf(dr) * __builtin_amdgcn_rcpf(__builtin_amdgcn_cosf(dr));
-            }
-            const float iv = __builtin_amdgcn_rcpf(v[i]);
-            const float vdt = v[i] * k.dt;
-            const float x_new = x[i] + vdt * cs, y_new = y[i] + vdt * sn;
-            const float delta_new = __builtin_amdgcn_fmed3f(delta[i] + dv * k.dt, -k.max_steer, k.max_steer);
-            const float v_new = __builtin_amdgcn_fmed3f(v[i] + a * k.dt, k.min_speed, k.max_speed);
-            const float yaw_new = yaw[i] + (v[i] * k.dt_inv_wb) * tn;
-            const float yri = yr[i] * iv;
-            const float yr_new = yr[i] + (B1 * delta[i] + B2 * beta[i] - B3 * yri);
-            const float beta_new = (beta[i] - yr[i] * k.dt) + (B4 * delta[i] - B5 * beta[i] + B6 * yri) * iv;
-            x[i] = x_new; y[i] = y_new; delta[i] = delta_new; v[i] = v_new; yaw[i] = yaw_new; yr[i] = yr_new; beta[i] = beta_new;
-            pdv[i] = dv; pa[i] = a;
         }
     }
     const float4 r0 = sr[2 * T], r1 = sr[2 * T + 1];
@@ -252,118 +237,8 @@ __device__ __forceinline__ void stmpc_rollout_f32(const float* __restrict__ ce, 
 // ---- K-A: f32 filter, one workgroup per ego; no fp64 rollout code in this kernel (registers for 8 waves per SIMD) ----------------
 // nlist[e] = listed rollouts (<= 64) or -1 (this ego is decided by the all-fp64 loop in k_stmpc_decide); the listed rollouts go to
 // rl[e][slot] and, as (e * 64 + slot, r), onto the global queue that k_stmpc_refine packs into full waves across egos.
+// (The kernels K-A, K-B, K-B' and K-C themselves are in k_stmpc_shoot_text.h; their types and their notes stay here.)
 struct StItem { int es, r; };
-
-template <int QM>
-__global__ __launch_bounds__(256) void k_stmpc_filter(const double* __restrict__ x0, const double* __restrict__ ref,
-                                                      const float* __restrict__ controls, int E, int T, int R, double max_steer_d, DynF32 kf,
-                                                      unsigned int* __restrict__ qcount, StItem* __restrict__ items, int32_t* __restrict__ nlist,
-                                                      int32_t* __restrict__ rl, float* __restrict__ dbg_cost32) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
-    float* sref32 = reinterpret_cast<float*>(lds_raw);               // [T+1][8] relative to the ego state
-    float* c32 = sref32 + 8 * (T + 1);                                // [R] filter costs (-inf = untrusted)
-    float* red_f = c32 + R;                                           // [4]
-    int* list = reinterpret_cast<int*>(red_f + 4);                    // [F1P_ST_MAX_REFINE]
-    int* cnt = list + F1P_ST_MAX_REFINE;                              // [2]: listed, queue base
-    const int e = blockIdx.x;
-    if (e >= E) return;
-    const double sx = x0[7 * e], sy = x0[7 * e + 1], sdelta = x0[7 * e + 2], sv = x0[7 * e + 3], syaw = x0[7 * e + 4], syr = x0[7 * e + 5], sbeta = x0[7 * e + 6];
-    const bool in_range = fabs(syaw) <= 1.0e4 && fabs(max_steer_d) <= 1.0e4 && fabs(sbeta) <= 100.0 && fabs(sdelta) <= 100.0;   // workgroup-uniform
-    if (!in_range) { if (tid == 0) nlist[e] = -1; return; }
-    int bad_ref = 0;                                                 // a non-finite reference in an UNWEIGHTED row makes every fp64 cost NaN (0 * NaN): fp64 decides
-    for (int q = tid; q < 7 * (T + 1); q += blockDim.x) {
-        const double rv = ref[(size_t)e * 7 * (T + 1) + q];
-        const int row = q / (T + 1), t = q - row * (T + 1);
-        sref32[8 * t + row] = (float)(row == 0 ? rv - sx : (row == 1 ? rv - sy : (row == 4 ? rv - syaw : rv)));
-        if (!((QM >> row) & 1) && !(fabs(rv) < __builtin_huge_val())) bad_ref = 1;
-    }
-    if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
-    if (__syncthreads_or(bad_ref | ((QM != 0x7f && !(fabs(syr) < __builtin_huge_val())) ? 1 : 0))) { if (tid == 0) nlist[e] = -1; return; }
-    const float* ce = controls + (size_t)e * T * 2 * R;
-    DynF32 kk;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) { kk.ap[j] = in_vgpr(kf.ap[j]); kk.aq[j] = in_vgpr(kf.aq[j]); }
-#pragma unroll
-    for (int j = 0; j < 7; ++j) { kk.q[j] = in_vgpr(kf.q[j]); kk.qf[j] = kf.qf[j]; }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) { kk.r[j] = in_vgpr(kf.r[j]); kk.rd[j] = in_vgpr(kf.rd[j]); }
-    kk.dt = in_vgpr(kf.dt); kk.dt_inv_wb = in_vgpr(kf.dt_inv_wb);
-    kk.max_steer = in_vgpr(kf.max_steer); kk.max_steer_v = in_vgpr(kf.max_steer_v); kk.max_accel = in_vgpr(kf.max_accel);
-    kk.max_speed = in_vgpr(kf.max_speed); kk.min_speed = in_vgpr(kf.min_speed); kk.v_trust = in_vgpr(kf.v_trust);
-    double s0d, c0d;
-    sincos_core(syaw, &s0d, &c0d);
-    kk.c0 = (float)c0d; kk.s0 = (float)s0d;
-    // the odd polynomial of tan is good for |delta| <= 0.45: every later delta is clamped to max_steer, but step 0 evaluates tan(delta0)
-    // UNCLAMPED (dyn_step does, like the reference) -- an out-of-range initial steering state takes the sin / cos path (workgroup-uniform)
-    const bool poly = kf.max_steer <= 0.45f && fabs(sdelta) <= 0.45;
-    float tmin = __builtin_huge_valf();
-    constexpr int NR = F1P_ST_FILTER_NR;
-    for (int rb = tid; rb < R; rb += NR * blockDim.x) {
-        int rr[NR]; float c[NR]; bool trusted[NR];
-#pragma unroll
-        for (int i = 0; i < NR; ++i) rr[i] = rb + i * (int)blockDim.x < R ? rb + i * (int)blockDim.x : rb;   // past the end: a shadow of the first, not stored
-        if (poly) stmpc_rollout_f32<true, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted);
-        else stmpc_rollout_f32<false, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted);
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            if (i > 0 && rr[i] == rb) continue;
-            float ci = c[i];
-            if (!trusted[i] || !(ci == ci) || !(fabsf(ci) < 1e30f)) ci = -__builtin_huge_valf();      // untrusted / non-finite: fp64 decides
-            else tmin = fminf(tmin, ci);
-            c32[rr[i]] = ci;
-            if (dbg_cost32) dbg_cost32[(size_t)e * R + rr[i]] = ci;
-        }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) tmin = fminf(tmin, __shfl_xor(tmin, m, 64));
-    if (lane == 0) red_f[wave] = tmin;
-    __syncthreads();
-    tmin = red_f[0];
-    for (int w = 1; w < nwaves; ++w) tmin = fminf(tmin, red_f[w]);
-    // (no trusted rollout: tmin = +inf, thr = +inf and every rollout is listed -> fallback)
-    const float thr = tmin + (fabsf(tmin) * fminf(F1P_ST_MARGIN_REL * (float)T, 0.5f) + F1P_ST_MARGIN_ABS);
-    for (int r = tid; r < R; r += blockDim.x) {
-        if (!(c32[r] > thr)) {
-            const int pos = atomicAdd(cnt, 1);
-            if (pos < F1P_ST_MAX_REFINE) list[pos] = r;
-        }
-    }
-    __syncthreads();
-    const int n = cnt[0];
-    const bool fallback = n > F1P_ST_MAX_REFINE || n < 1 || !(tmin < __builtin_huge_valf());
-    if (fallback) { if (tid == 0) nlist[e] = -1; return; }
-    if (tid == 0) { cnt[1] = (int)atomicAdd(qcount, (unsigned int)n); nlist[e] = n; }
-    __syncthreads();
-    if (tid < n) {
-        const int r = list[tid];
-        rl[(size_t)e * F1P_ST_MAX_REFINE + tid] = r;
-        StItem it; it.es = e * F1P_ST_MAX_REFINE + tid; it.r = r;
-        items[(size_t)cnt[1] + tid] = it;
-    }
-}
-
-// ---- K-B: fp64 costs of the queued rollouts, one lane each, packed across egos (stmpc_rollouts' own arithmetic) ----------------
-// ~1 rollout per ego survives the filter, so this kernel is a few dozen waves running 40 sequential fp64 steps: 1.3 us per step (34 us
-// for a single wave of 17 rollouts, 52 us at 1024 egos), latency of the dependent fp64 chain and not throughput.  This kernel now only
-// serves horizons > 63; k_stmpc_refine_tp below is what runs.  Measured and NOT kept
-// (profiles/r03_stmpc_filter.md): splitting the step's independent chains over four waves with an LDS exchange per step, staging the
-// controls in LDS and batching the reference loads -- each left the time where it was.
-__global__ __launch_bounds__(64) void k_stmpc_refine(const double* __restrict__ x0, const double* __restrict__ ref, const float* __restrict__ controls,
-                                                     f1p_stmpc_cfg cfg, const unsigned int* __restrict__ qcount, const StItem* __restrict__ items,
-                                                     double* __restrict__ rc) {
-    const unsigned int count = *qcount;
-    const int T = cfg.horizon, R = cfg.n_rollouts;
-    const DynConst k = dyn_const(cfg);
-    for (unsigned int i = blockIdx.x * 64u + threadIdx.x; i < count; i += gridDim.x * 64u) {
-        const StItem it = items[i];
-        const int e = it.es / F1P_ST_MAX_REFINE;
-        DynState s0;
-        s0.x = x0[7 * e]; s0.y = x0[7 * e + 1]; s0.delta = x0[7 * e + 2]; s0.v = x0[7 * e + 3]; s0.yaw = x0[7 * e + 4];
-        s0.yr = x0[7 * e + 5]; s0.beta = x0[7 * e + 6];
-        rc[it.es] = stmpc_one_rollout<true>(controls + (size_t)e * T * 2 * R, ref + (size_t)e * 7 * (T + 1), cfg, k, s0, it.r);
-    }
-}
 
 // ---- K-B', time-parallel: ONE WAVE per queued rollout, lanes over the time steps (horizon <= 63) ---------------------------------
 // Of the 7 states only (yr, beta) are truly recurrent.  delta and v follow from the controls alone (clamped running sums), yaw from
@@ -387,229 +262,107 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-__global__ __launch_bounds__(256) void k_stmpc_refine_tp(const double* __restrict__ x0, const double* __restrict__ ref, const float* __restrict__ controls,
-                                                        f1p_stmpc_cfg cfg, const unsigned int* __restrict__ qcount, const StItem* __restrict__ items,
-                                                        double* __restrict__ rc, float* __restrict__ dbg_ticks) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#ifdef F1P_ST_PHASES
-    long long ph[12]; int nph = 0;
-#define F1P_STPH() do { ph[nph++] = clock64(); } while (0)
-#else
-#define F1P_STPH() do {} while (0)
-#endif
-    unsigned char* wl = lds_raw + (size_t)wave * F1P_ST_TP_LDS_PER_WAVE;
-    StS1* __restrict__ s1 = reinterpret_cast<StS1*>(wl);
-    StS3* __restrict__ s3 = reinterpret_cast<StS3*>(wl + 64 * sizeof(StS1));
-    StO3* __restrict__ o3 = reinterpret_cast<StO3*>(wl + 64 * (sizeof(StS1) + sizeof(StS3)));
-    StXY* __restrict__ s6 = reinterpret_cast<StXY*>(wl + 64 * (sizeof(StS1) + sizeof(StS3) + sizeof(StO3)));
-    StXY* __restrict__ o6 = reinterpret_cast<StXY*>(wl + 64 * (sizeof(StS1) + sizeof(StS3) + sizeof(StO3) + sizeof(StXY)));
-    StC* __restrict__ cr = reinterpret_cast<StC*>(wl + 64 * (sizeof(StS1) + sizeof(StS3) + sizeof(StO3) + 2 * sizeof(StXY)));
-    const unsigned int count = *qcount;
-    const int T = cfg.horizon, R = cfg.n_rollouts;
-    const DynConst k = dyn_const(cfg);
-    const unsigned int nw = gridDim.x * (blockDim.x >> 6);
-    for (unsigned int i = blockIdx.x * (blockDim.x >> 6) + wave; i < count; i += nw) {   // wave-uniform
-        F1P_STPH();
-        const StItem it = items[i];
-        const int e = it.es / F1P_ST_MAX_REFINE;
-        const int t = lane;
-        const bool act = t < T, act1 = t <= T;
-        const float* cp = controls + (size_t)e * T * 2 * R + it.r;        // [t][2][R]
-        const double* sref = ref + (size_t)e * 7 * (T + 1);
-        const float c_dv = act ? cp[(size_t)t * 2 * R] : 0.0f, c_a = act ? cp[(size_t)t * 2 * R + R] : 0.0f;
-        double rf[7];
-#pragma unroll
-        for (int j = 0; j < 7; ++j) rf[j] = act1 ? sref[j * (T + 1) + t] : 0.0;
-        DynState s0;
-        s0.x = x0[7 * e]; s0.y = x0[7 * e + 1]; s0.delta = x0[7 * e + 2]; s0.v = x0[7 * e + 3]; s0.yaw = x0[7 * e + 4];
-        s0.yr = x0[7 * e + 5]; s0.beta = x0[7 * e + 6];
-        // ---- 1. controls: the bounds in parallel, the rate clamp and the two clamped running sums in sequence ----------------------
-        const double my_a = clampd2((double)c_a, -cfg.max_accel, cfg.max_accel);         // :704-706
-        {
-            StS1 w1; w1.u = clampd2((double)c_dv, -cfg.max_steer_v, cfg.max_steer_v); w1.a = my_a;   // :701-703
-            s1[t] = w1;
-        }
-        wave_lds_sync();
-        F1P_STPH();
-        double my_dv = 0.0, my_delta = 0.0, my_v = 0.0;
-        {
-            double dlt = s0.delta, v = s0.v, pdv = 0.0;
-#pragma unroll 4
-            for (int q = 0; q < T; ++q) {
-                const StS1 cur = s1[q];
-                double dv = cur.u;
-                if (q > 0) dv = clampd2(dv, pdv - cfg.max_steer_v, pdv + cfg.max_steer_v);   // :685
-                if (lane == 0) { StO3 w; w.yr = dv; w.beta = dlt; w.yaw = v; w.pad = 0.0; o3[q] = w; }   // (o3 is free until phase 3: one LDS write instead of six selects)
-                const double delta_new = dlt + dv * cfg.dt;               // :360
-                const double v_new = v + cur.a * cfg.dt;                  // :361
-                v = v_new > cfg.max_speed ? cfg.max_speed : (v_new < cfg.min_speed ? cfg.min_speed : v_new);               // :393-396
-                dlt = delta_new >= cfg.max_steer ? cfg.max_steer : (delta_new <= -cfg.max_steer ? -cfg.max_steer : delta_new);   // :399-402
-                pdv = dv;
-            }
-            if (lane == 0) { StO3 w; w.yr = 0.0; w.beta = dlt; w.yaw = v; w.pad = 0.0; o3[T] = w; }
-        }
-        wave_lds_sync();
-        if (act1) { const StO3 w = o3[t]; my_dv = w.yr; my_delta = w.beta; my_v = w.yaw; }
-        wave_lds_sync();
-        F1P_STPH();
-        // ---- 2. per step: coefficients of the (yr, beta) recurrence and the yaw increment ----------------------------------------
-        if (act) {
-            const double Tz = k.gl_r - (my_a * k.h);                      // :343
-            const double Vz = k.gl_f + (my_a * k.h);                      // :344
-            const double A1 = k.K * k.F * Tz;                             // :350-355
-            const double A2 = k.K * (k.R * Vz - k.F * Tz);
-            const double A3 = k.K * (k.lf2cf * Tz + k.lr2cr * Vz);
-            const double A4 = k.M * Tz;
-            const double A5 = k.N * Vz + k.M * Tz;
-            const double A6 = k.N * Vz * k.l_r - k.M * Tz * k.l_f;
-            double sd, cd;
-            sincos_core(my_delta, &sd, &cd);
-            const double tn = sd / cd;
-            StS3 w3;
-            w3.P1 = A1 * my_delta; w3.A2 = A2; w3.A3 = A3; w3.A4d = A4 * (my_delta / my_v); w3.A5 = A5; w3.A6 = A6;
-            w3.v = my_v; w3.vv = my_v * my_v; w3.w = my_v / cfg.wheelbase * tn * cfg.dt; w3.pad = 0.0;
-            s3[t] = w3;
-        }
-        wave_lds_sync();
-        F1P_STPH();
-        // ---- 3. the recurrence: yr, beta (and yaw's running sum beside them) ------------------------------------------------------
-        {
-            double yr = s0.yr, beta = s0.beta, yaw = s0.yaw;
-#pragma unroll 4
-            for (int q = 0; q < T; ++q) {
-                const StS3 cur = s3[q];
-                if (lane == 0) { StO3 w; w.yr = yr; w.beta = beta; w.yaw = yaw; w.pad = 0.0; o3[q] = w; }
-                const double yr_new = yr + (cur.P1 + cur.A2 * beta - cur.A3 * (yr / cur.v)) * cfg.dt;                       // :367-371
-                const double beta_new = beta + (cur.A4d - cur.A5 * (beta / cur.v) + cur.A6 * (yr / cur.vv) - yr) * cfg.dt;   // :372-381
-                yaw = yaw + cur.w;                                                                                          // :362-365
-                yr = yr_new; beta = beta_new;
-            }
-            if (lane == 0) { StO3 w; w.yr = yr; w.beta = beta; w.yaw = yaw; w.pad = 0.0; o3[T] = w; }
-        }
-        wave_lds_sync();
-        F1P_STPH();
-        double my_yr = 0.0, my_beta = 0.0, my_yaw = 0.0;
-        if (act1) { const StO3 w = o3[t]; my_yr = w.yr; my_beta = w.beta; my_yaw = w.yaw; }
-        // ---- 4. x / y increments --------------------------------------------------------------------------------------------------
-        if (act) {
-            double sn, cs;
-            sincos_fast(my_yaw + my_beta, &sn, &cs);
-            StXY w; w.x = my_v * cs * cfg.dt; w.y = my_v * sn * cfg.dt;   // :358-359
-            s6[t] = w;
-        }
-        wave_lds_sync();
-        F1P_STPH();
-        // ---- 5. x, y ---------------------------------------------------------------------------------------------------------------
-        {
-            double x = s0.x, y = s0.y;
-#pragma unroll 8
-            for (int q = 0; q < T; ++q) {
-                const StXY cur = s6[q];
-                if (lane == 0) { StXY w; w.x = x; w.y = y; o6[q] = w; }
-                x = x + cur.x; y = y + cur.y;
-            }
-            if (lane == 0) { StXY w; w.x = x; w.y = y; o6[T] = w; }
-        }
-        wave_lds_sync();
-        F1P_STPH();
-        // ---- 6. cost rows ----------------------------------------------------------------------------------------------------------
-        {
-            const double p_dv = shfl_d(my_dv, lane > 0 ? lane - 1 : 0), p_a = shfl_d(my_a, lane > 0 ? lane - 1 : 0);
-            StC w; w.q = 0.0; w.r = 0.0; w.rd = 0.0; w.pad = 0.0;
-            if (act1) {
-                const StXY xy = o6[t];
-                const double sv[7] = {xy.x, xy.y, my_delta, my_v, my_yaw, my_yr, my_beta};
-                double q = 0.0;
-                if (act) {
-#pragma unroll
-                    for (int j = 0; j < 7; ++j) { const double er = sv[j] - rf[j]; q += cfg.q[j] * er * er; }    // :619
-                    w.r = cfg.r[0] * my_dv * my_dv + cfg.r[1] * my_a * my_a;                                     // :616
-                    if (t > 0) { const double d0 = my_dv - p_dv, d1 = my_a - p_a; w.rd = cfg.rd[0] * d0 * d0 + cfg.rd[1] * d1 * d1; }   // :622
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 7; ++j) { const double er = sv[j] - rf[j]; q += cfg.qf[j] * er * er; }
-                }
-                w.q = q;
-                cr[t] = w;
-            }
-        }
-        wave_lds_sync();
-        F1P_STPH();
-        // ---- 7. the running sum, in stmpc_rollouts' order ---------------------------------------------------------------------------
-        {
-            double cost = 0.0;
-#pragma unroll 8
-            for (int q = 0; q < T; ++q) {
-                const StC cur = cr[q];
-                cost += cur.q;
-                cost += cur.r;
-                if (q > 0) cost += cur.rd;
-            }
-            cost += cr[T].q;                                              // the terminal row (Qf)
-            if (lane == 0) rc[it.es] = cost;
-        }
-        wave_lds_sync();
-#ifdef F1P_ST_PHASES
-        F1P_STPH();
-        if (dbg_ticks && lane == 0 && i < 4096u) { for (int q = 0; q + 1 < nph; ++q) dbg_ticks[i * 16u + q] = (float)(ph[q + 1] - ph[q]); dbg_ticks[i * 16u + 15] = (float)nph; }
-        nph = 0;
-#endif
-    }
+// ---- the shooting kernels, once per control source (k_stmpc_shoot_text.h) -----------------------------------------------------------
+#define F1P_ST_N(name) name
+#define F1P_ST_CTL_PARAM const float* __restrict__ controls
+#define F1P_ST_SRC_PARAM const float* __restrict__ ce
+#define F1P_ST_SRC_DECL(ce, e) const float* ce = controls + (size_t)e * T * 2 * R
+#define F1P_ST_SRC_DECL_FILTER(ce, e) F1P_ST_SRC_DECL(ce, e)
+#define F1P_ST_SRC_EXPR(e) controls + (size_t)e * T * 2 * R
+#define F1P_ST_SRC_DECL_R(cp, e, r) const float* cp = controls + (size_t)e * T * 2 * R + r
+#define F1P_ST_DV_R(cp, t, r) cp[(size_t)t * 2 * R]
+#define F1P_ST_A_R(cp, t, r) cp[(size_t)t * 2 * R + R]
+#define F1P_ST_DV(ce, t, r) ce[((size_t)t * 2 + 0) * R + r]
+#define F1P_ST_A(ce, t, r) ce[((size_t)t * 2 + 1) * R + r]
+#define F1P_ST_EMIT_PRE(ce, bi)
+#define F1P_ST_EMIT_DV(ce, t, bi) ce[((size_t)t * 2 + 0) * R + bi]
+#define F1P_ST_EMIT_A(ce, t, bi) ce[((size_t)t * 2 + 1) * R + bi]
+#define F1P_ST_EMIT_TAIL(e, t, dv, a) else if (t == 0) break;
+#define F1P_ST_FILTER_WARM(e)
+#include "k_stmpc_shoot_text.h"
+#undef F1P_ST_N
+#undef F1P_ST_CTL_PARAM
+#undef F1P_ST_SRC_PARAM
+#undef F1P_ST_SRC_DECL
+#undef F1P_ST_SRC_DECL_FILTER
+#undef F1P_ST_SRC_EXPR
+#undef F1P_ST_SRC_DECL_R
+#undef F1P_ST_DV_R
+#undef F1P_ST_A_R
+#undef F1P_ST_DV
+#undef F1P_ST_A
+#undef F1P_ST_EMIT_PRE
+#undef F1P_ST_EMIT_DV
+#undef F1P_ST_EMIT_A
+#undef F1P_ST_EMIT_TAIL
+#undef F1P_ST_FILTER_WARM
+
+// generated controls.  The filter keeps the ego's warm start in LDS (read T x R times), behind its other arrays; the fp64 kernels read
+// the global row (a few rollouts).  The emission writes the next warm start: the winner's APPLIED sequence shifted by one step, the
+// last step repeated, rounded to f32 (the rule of kmpc_emit; dynamic_mpc.py:1052-1055 keeps self.oa / self.odelta_v the same way) -- into
+// the row the generator reads; every read of it (F1P_ST_EMIT_PRE, all steps at once) is behind a barrier before the first write.
+#define F1P_ST_N(name) name##_gen
+#define F1P_ST_CTL_PARAM StCtlGen ctl
+#define F1P_ST_SRC_PARAM const StGenSrc& ce
+#define F1P_ST_SRC_DECL(ce, e) const StGenSrc ce = {ctl.src(e, ctl.warm_row(e)), 0.0f}
+#define F1P_ST_SRC_DECL_FILTER(ce, e) const SrcGenT<true> ce = ctl.src(e, reinterpret_cast<const float*>(cnt + 2))
+#define F1P_ST_SRC_EXPR(e) StGenSrc{ctl.src(e, ctl.warm_row(e)), 0.0f}
+#define F1P_ST_SRC_DECL_R(cp, e, r) F1P_ST_SRC_DECL(cp, e)
+#define F1P_ST_DV_R(cp, t, r) cp.dv(t, r)
+#define F1P_ST_A_R(cp, t, r) cp.a()
+#define F1P_ST_DV(ce, t, r) ce.dv(t, r)
+#define F1P_ST_A(ce, t, r) ce.a()
+#define F1P_ST_EMIT_PRE(ce, bi) float* emit_s = reinterpret_cast<float*>(lds_raw); \
+        for (int t_ = tid; t_ < T; t_ += blockDim.x) ce.g.get(t_, bi, emit_s[2 * t_], emit_s[2 * t_ + 1]); \
+        __syncthreads();
+#define F1P_ST_EMIT_DV(ce, t, bi) emit_s[2 * t]
+#define F1P_ST_EMIT_A(ce, t, bi) emit_s[2 * t + 1]
+#define F1P_ST_EMIT_TAIL(e, t, dv, a) { float* wo_ = ctl.warm_row(e); \
+        if (t > 0) { wo_[2 * (t - 1)] = (float)dv; wo_[2 * (t - 1) + 1] = (float)a; } \
+        if (t == T - 1) { wo_[2 * t] = (float)dv; wo_[2 * t + 1] = (float)a; } }
+#define F1P_ST_FILTER_WARM(e) { float* ws_ = reinterpret_cast<float*>(cnt + 2); const float* wg_ = ctl.warm_row(e); \
+        for (int q = tid; q < 2 * T; q += blockDim.x) ws_[q] = wg_[q]; }
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-variable"   // R, where it only addressed the controls buffer
+#include "k_stmpc_shoot_text.h"
+#pragma clang diagnostic pop
+#undef F1P_ST_N
+#undef F1P_ST_CTL_PARAM
+#undef F1P_ST_SRC_PARAM
+#undef F1P_ST_SRC_DECL
+#undef F1P_ST_SRC_DECL_FILTER
+#undef F1P_ST_SRC_EXPR
+#undef F1P_ST_SRC_DECL_R
+#undef F1P_ST_DV_R
+#undef F1P_ST_A_R
+#undef F1P_ST_DV
+#undef F1P_ST_A
+#undef F1P_ST_EMIT_PRE
+#undef F1P_ST_EMIT_DV
+#undef F1P_ST_EMIT_A
+#undef F1P_ST_EMIT_TAIL
+#undef F1P_ST_FILTER_WARM
+
+// materialise the generator's controls as the [E][T][2][R] f32 buffer of the streamed entry points (tests: generated == streamed)
+__global__ __launch_bounds__(256) void k_stmpc_gen_controls(float* __restrict__ controls, int E, int T, int R, StCtlGen ctl) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)E * T * R) return;
+    const size_t et = i / R;
+    const int r = (int)(i - et * R), e = (int)(et / T), t = (int)(et - (size_t)e * T);
+    float dv, a;
+    ctl.src(e, ctl.warm_row(e)).get(t, r, dv, a);
+    controls[(et * 2 + 0) * R + r] = dv;
+    controls[(et * 2 + 1) * R + r] = a;
 }
 
-// ---- K-C: np.argmin's rule over the refined costs (or the all-fp64 loop for the egos the filter gave up on), outputs -------------
-__global__ __launch_bounds__(256) void k_stmpc_decide(const double* __restrict__ x0, const double* __restrict__ ref,
-                                                      const float* __restrict__ controls, int E, f1p_stmpc_cfg cfg,
-                                                      unsigned int* __restrict__ qcount, const int32_t* __restrict__ nlist, const int32_t* __restrict__ rl,
-                                                      const double* __restrict__ rc,
-                                                      double* __restrict__ steer, double* __restrict__ speed,
-                                                      int32_t* __restrict__ best_idx, double* __restrict__ best_cost,
-                                                      double* __restrict__ best_seq, int32_t* __restrict__ dbg_nref) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int T = cfg.horizon, R = cfg.n_rollouts, tid = threadIdx.x;
-    double* sref = reinterpret_cast<double*>(lds_raw);                // [7][T+1] (fallback only)
-    double* red_d = sref + 7 * (T + 1);                               // [4]
-    int* red_i = reinterpret_cast<int*>(red_d + 4);                   // [4]
-    const int e = blockIdx.x;
-    if (e >= E) return;
-    if (e == 0 && tid == 0) *qcount = 0u;                             // re-arm the queue for the next plan (k_stmpc_refine has finished)
-    const int n = nlist[e];
-    DynState s0;
-    s0.x = x0[7 * e]; s0.y = x0[7 * e + 1]; s0.delta = x0[7 * e + 2]; s0.v = x0[7 * e + 3]; s0.yaw = x0[7 * e + 4];
-    s0.yr = x0[7 * e + 5]; s0.beta = x0[7 * e + 6];
-    const float* ce = controls + (size_t)e * T * 2 * R;
-    double bc = __builtin_huge_val(); int bi = 0x7fffffff;
-    if (n < 0) {                                                      // workgroup-uniform
-        for (int q = tid; q < 7 * (T + 1); q += blockDim.x) sref[q] = ref[(size_t)e * 7 * (T + 1) + q];
-        __syncthreads();
-        const DynConst k = dyn_const(cfg);
-        if (fabs(cfg.max_steer) <= 1.0e4) stmpc_rollouts<true>(ce, sref, cfg, k, s0, tid, bc, bi);
-        else stmpc_rollouts<false>(ce, sref, cfg, k, s0, tid, bc, bi);
-    } else if (tid < n) {
-        bc = rc[(size_t)e * F1P_ST_MAX_REFINE + tid];
-        bi = rl[(size_t)e * F1P_ST_MAX_REFINE + tid];
-    }
-    block_argmin(bc, bi, red_d, red_i);
-    if (tid == 0) {
-        double pdv = 0.0;
-        for (int t = 0; t < T; ++t) {
-            double dv = clampd2((double)ce[((size_t)t * 2 + 0) * R + bi], -cfg.max_steer_v, cfg.max_steer_v);
-            const double a = clampd2((double)ce[((size_t)t * 2 + 1) * R + bi], -cfg.max_accel, cfg.max_accel);
-            if (t > 0) dv = clampd2(dv, pdv - cfg.max_steer_v, pdv + cfg.max_steer_v);
-            if (t == 0) {
-                steer[e] = s0.delta + dv * cfg.dt;   // :1112
-                speed[e] = s0.v + a * cfg.dt;        // :1117
-            }
-            if (best_seq) { best_seq[((size_t)e * T + t) * 2] = dv; best_seq[((size_t)e * T + t) * 2 + 1] = a; }
-            else if (t == 0) break;
-            pdv = dv;
-        }
-        best_idx[e] = bi;
-        if (best_cost) best_cost[e] = bc;
-        if (dbg_nref) dbg_nref[e] = n;
-    }
+// rows[k] (k < n) of the warm start <- 0: the egos that start over (no warm start yet, or the other branch's)
+__global__ __launch_bounds__(256) void k_stmpc_warm_zero(float* __restrict__ warm, const int32_t* __restrict__ rows, int n, int wstride) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n * wstride) return;
+    const size_t k = i / wstride;
+    warm[(size_t)rows[k] * wstride + (i - k * wstride)] = 0.0f;
 }
+
 
 // calc_ref_trajectory :195-233; states [E][4] = (x, y, v, yaw); ref [E][7][T+1] rows x, y, 0, v, yaw, 0, 0
 __global__ __launch_bounds__(256) void k_stmpc_ref(const double* __restrict__ states, int E, int T, double dt, double dl,
@@ -675,13 +428,15 @@ static DynF32 make_dyn_f32(const f1p_stmpc_cfg* cfg) {
     return k;
 }
 
-int launch_stmpc_shoot(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const float* d_controls, int E, const f1p_stmpc_cfg* cfg,
-                       double* d_steer, double* d_speed, int32_t* d_best_idx, double* d_best_cost, double* d_best_seq) {
+// the schedule of f1p_stmpc_shoot_* (gen == nullptr: streamed d_controls) and of f1p_stmpc_plan_* (gen: generated controls, d_controls unused)
+static int stmpc_shoot_any(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const float* d_controls, const StCtlGen* gen, int E, const f1p_stmpc_cfg* cfg,
+                           double* d_steer, double* d_speed, int32_t* d_best_idx, double* d_best_cost, double* d_best_seq) {
     if (E <= 0) return F1P_OK;
     const size_t T1 = (size_t)cfg->horizon + 1;
     if (ctx->stmpc_mixed) {
         const DynF32 kf = make_dyn_f32(cfg);
-        const size_t lds_a = sizeof(float) * (8 * T1 + (size_t)cfg->n_rollouts + 4) + sizeof(int) * (F1P_ST_MAX_REFINE + 2);
+        const size_t lds_a = sizeof(float) * (8 * T1 + (size_t)cfg->n_rollouts + 4) + sizeof(int) * (F1P_ST_MAX_REFINE + 2) +
+                             (gen ? sizeof(float) * 2 * (size_t)cfg->horizon : 0);   // + the ego's warm start
         const size_t lds_c = sizeof(double) * (7 * T1 + 4) + sizeof(int) * 4;
         if (lds_a <= (size_t)ctx->prop.sharedMemPerBlock && lds_c <= (size_t)ctx->prop.sharedMemPerBlock && kf.v_trust == kf.v_trust &&
             (size_t)E * F1P_ST_MAX_REFINE < ((size_t)1 << 31)) {
@@ -707,7 +462,13 @@ int launch_stmpc_shoot(f1p_ctx* ctx, const double* d_x0, const double* d_ref, co
             ctx->st_q_dirty = true;
             int qm = 0;                                              // rows that carry weight in the stage or the terminal cost
             for (int j = 0; j < 7; ++j) if (cfg->q[j] != 0.0 || cfg->qf[j] != 0.0) qm |= 1 << j;
-            if (qm == 0x1b)                                         // the reference's weights (x, y, v, yaw): the delta / yr / beta terms are not evaluated
+            if (gen && qm == 0x1b)
+                hipLaunchKernelGGL(k_stmpc_filter_gen<0x1b>, dim3(E), dim3(256), (lds_a + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, cfg->horizon,
+                                   cfg->n_rollouts, cfg->max_steer, kf, qcount, items, nlist, rl, ctx->d_dbg_st_cost32);
+            else if (gen)
+                hipLaunchKernelGGL(k_stmpc_filter_gen<0x7f>, dim3(E), dim3(256), (lds_a + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, cfg->horizon,
+                                   cfg->n_rollouts, cfg->max_steer, kf, qcount, items, nlist, rl, ctx->d_dbg_st_cost32);
+            else if (qm == 0x1b)                                    // the reference's weights (x, y, v, yaw): the delta / yr / beta terms are not evaluated
                 hipLaunchKernelGGL(k_stmpc_filter<0x1b>, dim3(E), dim3(256), (lds_a + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E, cfg->horizon,
                                    cfg->n_rollouts, cfg->max_steer, kf, qcount, items, nlist, rl, ctx->d_dbg_st_cost32);
             else
@@ -717,13 +478,17 @@ int launch_stmpc_shoot(f1p_ctx* ctx, const double* d_x0, const double* d_ref, co
             if (rcode != F1P_OK) return rcode;
             if (cfg->horizon <= 63 && 4 * F1P_ST_TP_LDS_PER_WAVE <= (size_t)ctx->prop.sharedMemPerBlock) {
                 const int nb = E * F1P_ST_MAX_REFINE / 4 < 2 * ctx->prop.multiProcessorCount ? (E * F1P_ST_MAX_REFINE + 3) / 4 : 2 * ctx->prop.multiProcessorCount;
-                hipLaunchKernelGGL(k_stmpc_refine_tp, dim3(nb), dim3(256), 4 * F1P_ST_TP_LDS_PER_WAVE, ctx->stream, d_x0, d_ref, d_controls, *cfg, qcount, items, rc, ctx->d_dbg_st_cost32);
+                if (gen) hipLaunchKernelGGL(k_stmpc_refine_tp_gen, dim3(nb), dim3(256), 4 * F1P_ST_TP_LDS_PER_WAVE, ctx->stream, d_x0, d_ref, *gen, *cfg, qcount, items, rc, ctx->d_dbg_st_cost32);
+                else hipLaunchKernelGGL(k_stmpc_refine_tp, dim3(nb), dim3(256), 4 * F1P_ST_TP_LDS_PER_WAVE, ctx->stream, d_x0, d_ref, d_controls, *cfg, qcount, items, rc, ctx->d_dbg_st_cost32);
             } else {
-                hipLaunchKernelGGL(k_stmpc_refine, dim3(E), dim3(64), 0, ctx->stream, d_x0, d_ref, d_controls, *cfg, qcount, items, rc);
+                if (gen) hipLaunchKernelGGL(k_stmpc_refine_gen, dim3(E), dim3(64), 0, ctx->stream, d_x0, d_ref, *gen, *cfg, qcount, items, rc);
+                else hipLaunchKernelGGL(k_stmpc_refine, dim3(E), dim3(64), 0, ctx->stream, d_x0, d_ref, d_controls, *cfg, qcount, items, rc);
             }
             rcode = check_hip(ctx, hipGetLastError(), "k_stmpc_refine launch");
             if (rcode != F1P_OK) return rcode;
-            hipLaunchKernelGGL(k_stmpc_decide, dim3(E), dim3(256), (lds_c + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E, *cfg, qcount,
+            if (gen) hipLaunchKernelGGL(k_stmpc_decide_gen, dim3(E), dim3(256), (lds_c + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, *cfg, qcount,
+                                        nlist, rl, rc, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_st_nref);
+            else hipLaunchKernelGGL(k_stmpc_decide, dim3(E), dim3(256), (lds_c + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E, *cfg, qcount,
                                nlist, rl, rc, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_st_nref);
             rcode = check_hip(ctx, hipGetLastError(), "k_stmpc_decide launch");
             if (rcode == F1P_OK) ctx->st_q_dirty = false;
@@ -731,9 +496,47 @@ int launch_stmpc_shoot(f1p_ctx* ctx, const double* d_x0, const double* d_ref, co
         }
     }
     const size_t lds = sizeof(double) * (7 * T1 + 4) + sizeof(int) * 4;
-    hipLaunchKernelGGL(k_stmpc_shoot, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E, *cfg,
+    if (gen) hipLaunchKernelGGL(k_stmpc_shoot_gen, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, *cfg,
+                                d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
+    else hipLaunchKernelGGL(k_stmpc_shoot, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E, *cfg,
                        d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
     return check_hip(ctx, hipGetLastError(), "k_stmpc_shoot launch");
+}
+
+int launch_stmpc_shoot(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const float* d_controls, int E, const f1p_stmpc_cfg* cfg,
+                       double* d_steer, double* d_speed, int32_t* d_best_idx, double* d_best_cost, double* d_best_seq) {
+    return stmpc_shoot_any(ctx, d_x0, d_ref, d_controls, nullptr, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
+}
+
+static StCtlGen make_st_gen(const f1p_stmpc_sampler* smp, float* d_warm, int wstride, const int32_t* d_ids) {
+    StCtlGen g;
+    g.k0 = (uint32_t)(smp->seed & 0xffffffffull); g.k1 = (uint32_t)(smp->seed >> 32); g.call = smp->call; g.ego_off = (uint32_t)smp->ego_offset;
+    g.sig_dv = (float)smp->sigma_steer_v; g.sig_a = (float)smp->sigma_accel;
+    g.warm = d_warm; g.ids = d_ids; g.wstride = wstride;
+    return g;
+}
+
+// d_warm: rows of wstride floats, read as this plan's warm start (all zero = none) and overwritten with the next one
+int launch_stmpc_plan_gen(f1p_ctx* ctx, const double* d_x0, const double* d_ref, int E, const f1p_stmpc_cfg* cfg, const f1p_stmpc_sampler* smp,
+                          float* d_warm, int wstride, const int32_t* d_ids, double* d_steer, double* d_speed, int32_t* d_best_idx,
+                          double* d_best_cost, double* d_best_seq) {
+    const StCtlGen g = make_st_gen(smp, d_warm, wstride, d_ids);
+    return stmpc_shoot_any(ctx, d_x0, d_ref, nullptr, &g, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
+}
+
+int launch_stmpc_gen_controls(f1p_ctx* ctx, float* d_controls, int E, const f1p_stmpc_cfg* cfg, const f1p_stmpc_sampler* smp, float* d_warm, int wstride) {
+    const size_t n = (size_t)E * cfg->horizon * cfg->n_rollouts;
+    if (n == 0) return F1P_OK;
+    hipLaunchKernelGGL(k_stmpc_gen_controls, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_controls, E, cfg->horizon, cfg->n_rollouts,
+                       make_st_gen(smp, d_warm, wstride, nullptr));
+    return check_hip(ctx, hipGetLastError(), "k_stmpc_gen_controls launch");
+}
+
+int launch_stmpc_warm_zero(f1p_ctx* ctx, float* d_warm, const int32_t* d_rows, int n, int wstride) {
+    if (n <= 0) return F1P_OK;
+    const size_t m = (size_t)n * wstride;
+    hipLaunchKernelGGL(k_stmpc_warm_zero, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, d_warm, d_rows, n, wstride);
+    return check_hip(ctx, hipGetLastError(), "k_stmpc_warm_zero launch");
 }
 
 int launch_stmpc_ref(f1p_ctx* ctx, const double* d_states, int E, int horizon, double dt, double dl, double* d_ref) {

@@ -917,6 +917,49 @@ class Context:
                                                    _ptr(out.get("best_seq"))))
         return out
 
+    # in-kernel control generation + per-ego device-resident warm start (f1p_stmpc_plan_*)
+    def stmpc_gen_controls_dev(self, d_controls, E, cfg, sampler):
+        """The controls the next stmpc_plan_dev of this shape would evaluate, as the f32 [E][T][2][R] buffer stmpc_shoot_dev takes."""
+        self._check(self.lib.f1p_stmpc_gen_controls_dev(self.h, d_controls.ptr, int(E), C.byref(cfg), C.byref(sampler)))
+
+    def stmpc_plan_dev(self, d_x0, d_ref, E, cfg, sampler, d_steer, d_speed, d_best_idx, d_best_cost=None, d_best_seq=None):
+        """Asynchronous: the dynamic model's shooting plan of E egos on a given reference (x0 [E][7], ref [E][7][T+1]), the controls
+        generated in the kernels around the ctx's warm start, which it updates."""
+        p = lambda b: None if b is None else b.ptr   # noqa: E731
+        self._check(self.lib.f1p_stmpc_plan_dev(self.h, p(d_x0), p(d_ref), int(E), C.byref(cfg), C.byref(sampler), p(d_steer), p(d_speed),
+                                                p(d_best_idx), p(d_best_cost), p(d_best_seq)))
+
+    def stmpc_plan(self, x0, dcfg, kcfg: KmpcCfg, sampler, v_ks=2.0, dl=0.03, dlk=0.03, want_seq=True, want_cost=True):
+        """STMPCPlanner.plan with the shooting solver for E egos in ONE call: x0 [E, 7]; per ego the kinematic model at v <= v_ks, the
+        dynamic one above; reference extraction, generation around the ego's warm start, rollouts, argmin, new warm start ->
+        dict(steer, speed, best_idx, branch (1 dynamic, 0 kinematic)[, best_cost][, best_seq [E, max(T, TK), 2] in the branch's channel
+        order, NaN past its horizon])"""
+        x0 = _f64(x0, (-1, 7)); E = x0.shape[0]; W = max(dcfg.horizon, kcfg.horizon)
+        out = dict(steer=np.empty(E), speed=np.empty(E), best_idx=np.empty(E, np.int32), branch=np.empty(E, np.int32))
+        if want_cost:
+            out["best_cost"] = np.empty(E)
+        if want_seq:
+            out["best_seq"] = np.empty((E, W, 2))
+        self._check(self.lib.f1p_stmpc_plan_batch(self.h, _ptr(x0), E, C.byref(dcfg), C.byref(kcfg), float(v_ks), float(dl), float(dlk),
+                                                  C.byref(sampler), _ptr(out["steer"]), _ptr(out["speed"]), _ptr(out["best_idx"]),
+                                                  _ptr(out.get("best_cost")), _ptr(out["branch"]), _ptr(out.get("best_seq"))))
+        return out
+
+    def stmpc_warm_reset(self):
+        self._check(self.lib.f1p_stmpc_warm_reset(self.h))
+
+    def stmpc_warm_get(self, E, T, TK=0):
+        """-> (warm f32 [E, max(T, TK), 2], tag [E]: 0 none, 1 kinematic (accel, steer), 2 dynamic (steering speed, accel))"""
+        w = np.empty((int(E), max(int(T), int(TK)), 2), np.float32); tag = np.empty(int(E), np.int32)
+        self._check(self.lib.f1p_stmpc_warm_get(self.h, _ptr(w), _ptr(tag), int(E), int(T), int(TK)))
+        return w, tag
+
+    def stmpc_warm_set(self, warm, tags, T, TK=0):
+        w = np.ascontiguousarray(warm, np.float32); tag = np.ascontiguousarray(tags, dtype=np.int32)
+        if w.ndim != 3 or w.shape[1:] != (max(int(T), int(TK)), 2) or tag.shape != (w.shape[0],):
+            raise ValueError("warm must be [E, max(T, TK), 2] and tags [E]")
+        self._check(self.lib.f1p_stmpc_warm_set(self.h, _ptr(w), _ptr(tag), w.shape[0], int(T), int(TK)))
+
     # ---- multi-GPU exchange step -----------------------------------------------------------------------------
     def comm_unique_id(self):
         buf = (C.c_uint8 * _abi.COMM_ID_BYTES)()
@@ -1100,6 +1143,19 @@ class MultiContext:
         x0 = _f64(x0, (-1, 7)); ids = Context._ids(track_ids, x0.shape[0])
         return self._sharded(x0.shape[0], lambda c, lo, hi: c.stmpc_qp_plan_tracks(x0[lo:hi], ids[lo:hi], dcfg, kcfg, v_ks, dl, dlk, opts,
                                                                                    want_u, want_obj))
+
+    def stmpc_plan(self, x0, dcfg, kcfg, sampler, v_ks=2.0, dl=0.03, dlk=0.03, want_seq=True, want_cost=True):
+        """Context.stmpc_plan sharded by ego ranges.  The generator's ego word is the GLOBAL ego index (each range's first index goes
+        down as the sampler's ego offset), so the result equals the single-context call bit for bit.  Each context holds the warm start
+        of its range: E and the device list must stay the same from call to call for the chain to equal the single-context chain."""
+        import copy
+        x0 = _f64(x0, (-1, 7))
+
+        def call(c, lo, hi):
+            s = copy.copy(sampler)
+            s.ego_offset = sampler.ego_offset + lo
+            return c.stmpc_plan(x0[lo:hi], dcfg, kcfg, s, v_ks, dl, dlk, want_seq, want_cost)
+        return self._sharded(x0.shape[0], call)
 
     def kmpc_ref(self, states, horizon, dt=0.1, dl=0.03):
         st = _f64(states, (-1, 4))

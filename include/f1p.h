@@ -714,6 +714,60 @@ int f1p_stmpc_shoot_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, c
                         double* d_best_cost, double* d_best_seq);
 
 /* ------------------------------------------------------------------------------------------------
+ * The dynamic MPC's shooting solver with the controls GENERATED IN THE KERNEL and a per-ego warm start kept on the device
+ * (STMPCPlanner.plan with SOLVER = "shooting", batched; csrc/k_stmpc.hip).  The generator is f1p_kmpc_plan_*'s:
+ * control (rollout r, step t) of ego e = Philox4x32-10(counter (t / 2, r, e, call), key seed) -> standardised Irwin-Hall byte
+ * sums z -> fma(sigma_c, z_c, warm_c[t]) per channel c; rollout 0 = the warm start itself, rollout 1 = all zero (CPU restatement:
+ * oracle/f1p_oracle.c orc_kmpc_gen_controls).  Dynamic model (v > V_KS, MPC_Control :1067-1117): channel 0 = steering speed
+ * (sigma_steer_v), channel 1 = accel (sigma_accel); kinematic model (v <= V_KS, MPC_Control_kinematic :1012-1063): channel 0 = accel
+ * (sigma_accel), channel 1 = steering angle (sigma_steer).  The ego word e is the ego's index in the caller's batch + ego_offset
+ * (a batch that is one shard of a larger one passes its first ego's global index), in both branches: an ego's plan is a function of
+ * that ego alone, wherever it stands in the batch and whatever the others do.
+ * A struct of its own rather than f1p_kmpc_sampler used twice: the two branches share seed, call and use_warm, which two samplers
+ * could set apart by mistake, and the ego offset has no place in the kinematic one.
+ *   f1p_stmpc_gen_controls_dev + f1p_stmpc_shoot_dev  ==  f1p_stmpc_plan_dev   bit for bit (tests/test_gpu_stmpc_plan.py),
+ *   under both settings of f1p_stmpc_set_mode.
+ * Warm start: f32 [E][W][2], W = max(T, TK), plus a tag per ego -- 0: none, 1: written by the kinematic branch ([TK][2] = (accel,
+ * steer)), 2: by the dynamic branch ([T][2] = (steering speed, accel)); rows past the branch's horizon are unspecified.  After a plan
+ * the row is the winner's APPLIED sequence (after the bound projection :685-706 / :391-401) shifted by one step, last step repeated,
+ * rounded to f32 (what :1052-1055 / :1005-1008 keep in self.oa / self.odelta_v).  An ego whose tag is not its branch's starts from
+ * zeros (the channels mean different things), as does every ego with use_warm = 0, after f1p_stmpc_warm_reset and after a change of
+ * E, T or TK.  Separate from f1p_kmpc_warm_* and from the QP's f1p_stmpc_qp_warm_*.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct f1p_stmpc_sampler {
+    uint64_t seed;         /* Philox key */
+    uint32_t call;         /* plan counter: advance per plan */
+    int32_t use_warm;      /* 0: generate around zeros (the warm start is still written) */
+    double sigma_steer_v;  /* dynamic branch, channel 0 [rad/s] */
+    double sigma_accel;    /* both branches [m/s^2] */
+    double sigma_steer;    /* kinematic branch, channel 1 [rad] */
+    int32_t ego_offset;    /* added to the batch index in the generator's ego word (>= 0) */
+    int32_t reserved;      /* 0 */
+} f1p_stmpc_sampler;
+/* the controls the next f1p_stmpc_plan_dev of this shape would evaluate, as the [E][T][2][R] f32 buffer f1p_stmpc_shoot_dev takes
+ * (dynamic_mpc.py:685-706 are applied by the rollouts, not here); asynchronous.  Does not change the warm start. */
+int f1p_stmpc_gen_controls_dev(f1p_ctx* ctx, float* d_controls, int32_t E, const f1p_stmpc_cfg* cfg, const f1p_stmpc_sampler* smp);
+/* MPC_Control (:1067-1117) by shooting on a given reference, dynamic model for every ego: d_x0 [E][7], d_ref [E][7][T+1]
+ * (f1p_stmpc_ref_*_dev); outputs as f1p_stmpc_shoot_dev (d_best_cost, d_best_seq nullable).  Asynchronous on the ctx stream; the
+ * f32 filter / fp64 refinement / decision schedule of f1p_stmpc_shoot_dev with no controls buffer anywhere. */
+int f1p_stmpc_plan_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, int32_t E, const f1p_stmpc_cfg* cfg,
+                       const f1p_stmpc_sampler* smp, double* d_steer, double* d_speed, int32_t* d_best_idx, double* d_best_cost,
+                       double* d_best_seq);
+/* STMPCPlanner.plan (:152-191) by shooting for a batch, host arrays: x0 [E][7]; per ego the model switch of :168 (v <= v_ks:
+ * kinematic model on kcfg, reference rows 0, 1, 3, 4 of calc_ref_trajectory :195-233 with (TK, DTK, dlk); else the dynamic model
+ * on dcfg with (T, DT, dl)), reference extraction from the ctx waypoints, plan, warm-start update.  branch [E] (nullable): 0
+ * kinematic, 1 dynamic.  best_seq [E][W][2] (nullable), W = max(T, TK): the winner's applied sequence in its branch's channel order,
+ * NaN past the branch's horizon.  best_cost nullable. */
+int f1p_stmpc_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_stmpc_cfg* dcfg, const f1p_kmpc_cfg* kcfg, double v_ks,
+                         double dl, double dlk, const f1p_stmpc_sampler* smp, double* steer, double* speed, int32_t* best_idx,
+                         double* best_cost, int32_t* branch, double* best_seq);
+/* the warm start of f1p_stmpc_plan_* (:1052-1055, :1005-1008): warm [E][W][2] f32, tag [E] i32, host arrays, W = max(T, TK)
+ * (TK = 0 for a ctx that only runs f1p_stmpc_plan_dev) */
+int f1p_stmpc_warm_reset(f1p_ctx* ctx);
+int f1p_stmpc_warm_get(f1p_ctx* ctx, float* warm, int32_t* tag, int32_t E, int32_t T, int32_t TK);
+int f1p_stmpc_warm_set(f1p_ctx* ctx, const float* warm, const int32_t* tag, int32_t E, int32_t T, int32_t TK);
+
+/* ------------------------------------------------------------------------------------------------
  * Multi-GPU: egos shard with no communication (one ctx per rank).  Only when ONE ego's candidate set is
  * split over ranks is there an exchange step: all-reduce(min) of the per-ego best cost, then
  * all-reduce(min) of the candidate index among the ranks that hold that cost (np.argmin first-minimum
