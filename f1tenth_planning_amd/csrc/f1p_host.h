@@ -1,0 +1,155 @@
+// f1p_host.h -- what the host-side translation units of libf1p.so (f1p_core / scene / trackers / lattice / kmpc / stmpc / comm .hip) share
+// beyond f1p_internal.h: the entry macro, the staging plan of the *_batch wrappers (Stage), the look-up of page-locked caller arrays, the guard of
+// frames that copy asynchronously from their own vectors (StreamDrain), and the checks used by more than one unit.  Host only: no k_*.hip
+// includes it.  What it declares lives in namespace f1p and stays hidden (-fvisibility=hidden).
+#pragma once
+
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include <new>
+#include <string>
+#include <vector>
+
+// The exported surface is what include/f1p.h declares: its declarations (extern "C") are made with default visibility HERE, before anything else
+// includes it, and the definitions in the units inherit both.  Whatever else a unit defines stays hidden (-fvisibility=hidden).
+#pragma GCC visibility push(default)
+#include "../../include/f1p.h"
+#pragma GCC visibility pop
+#include "f1p_internal.h"
+
+#define F1P_ENTER(ctx)                                              \
+    if (!(ctx)) return F1P_EINVAL;                                  \
+    F1P_HIP((ctx), hipSetDevice((ctx)->device))
+
+namespace f1p {
+
+static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+#define F1P_SMALL_D2H_BYTES ((size_t)64 * 1024)      // calls up to this size: outputs written by the kernels straight into the page-locked block
+#define F1P_BOUNCE_BYTES ((size_t)1024 * 1024)       // the block; results up to this size come back in ONE copy + a host-side scatter
+int ensure_bounce(f1p_ctx* ctx);                     // f1p_core.hip
+
+// staged host<->device transfer plan for the *_batch wrappers
+struct Stage {
+    f1p_ctx* ctx;
+    struct Out { void* host; void* dev; size_t bytes; };
+    std::vector<Out> outs;
+    size_t total = 0, out_total = 0;
+    // Small calls (a single vehicle, a few hundred egos): the outputs -- and inputs of a few hundred bytes, i.e. a pose or two --
+    // live in the context's page-locked, device-visible block: the kernels write their results straight into host memory and no
+    // hipMemcpy is issued at all (each one is ~10-15 us of latency; a single-vehicle plan() is otherwise mostly copies).
+    // Larger inputs still go through a copy: a kernel that re-reads them (previous headings, controls) must find them in HBM.
+    bool zc = false;
+    size_t zc_used = 0;
+    explicit Stage(f1p_ctx* c) : ctx(c) {}
+    void need(size_t bytes, bool used = true) { if (used) total += al256(bytes); }
+    int begin() {
+        zc = total <= F1P_SMALL_D2H_BYTES && ensure_bounce(ctx) == F1P_OK;
+        zc_used = 0;
+        return arena_reset(ctx, total);
+    }
+    void* zc_take(size_t bytes) { void* p = ctx->h_bounce + zc_used; zc_used += al256(bytes); return p; }
+    template <typename T> int in(const T* host, size_t count, const T** dev) {
+        *dev = nullptr;
+        if (!host || count == 0) return F1P_OK;
+        if (zc && count * sizeof(T) <= 512) {
+            T* d = (T*)zc_take(count * sizeof(T));
+            memcpy(d, host, count * sizeof(T));
+            *dev = d;
+            return F1P_OK;
+        }
+        T* d = (T*)arena_take(ctx, count * sizeof(T));
+        F1P_HIP(ctx, hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        *dev = d;
+        return F1P_OK;
+    }
+    template <typename T> T* out(T* host, size_t count) {
+        if (!host || count == 0) return nullptr;
+        T* d = zc ? (T*)zc_take(count * sizeof(T)) : (T*)arena_take(ctx, count * sizeof(T));
+        outs.push_back({(void*)host, (void*)d, count * sizeof(T)});
+        return d;
+    }
+    int finish() {
+        if (zc) {
+            auto in_block = [&](const void* p) { return (const char*)p >= ctx->h_bounce && (const char*)p < ctx->h_bounce + F1P_BOUNCE_BYTES; };
+            for (auto& o : outs)                                  // an in/out buffer that went through the device arena (larger than a pose)
+                if (!in_block(o.dev)) F1P_HIP(ctx, hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, ctx->stream));
+            F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            for (auto& o : outs) if (in_block(o.dev)) memcpy(o.host, o.dev, o.bytes);
+            return F1P_OK;
+        }
+        return gather(nullptr);
+    }
+    // Results to the host: arrays that sit back to back in the arena and together fit the page-locked block come back in ONE copy
+    // and are scattered on the host (a hipMemcpyAsync per array is ~10 us of submission each -- six of them were a third of a
+    // 4096-ego plan()'s latency); anything else (the trajectories) is copied on its own.  `skip`: an output the caller copies itself.
+    int gather(const void* skip) {
+        std::vector<Out*> small;
+        const char *lo = nullptr, *hi = nullptr;
+        for (auto& o : outs) {
+            if (o.host == skip) continue;
+            const char* b = (const char*)o.dev;
+            const char* nlo = lo && lo < b ? lo : b;
+            const char* nhi = hi && hi > b + o.bytes ? hi : b + o.bytes;
+            if ((size_t)(nhi - nlo) <= F1P_BOUNCE_BYTES && o.bytes <= F1P_BOUNCE_BYTES / 4) { small.push_back(&o); lo = nlo; hi = nhi; }
+            else F1P_HIP(ctx, hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        if (small.size() > 1 && ensure_bounce(ctx) == F1P_OK) {
+            F1P_HIP(ctx, hipMemcpyAsync(ctx->h_bounce, lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, ctx->stream));
+            F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            for (Out* o : small) memcpy(o->host, ctx->h_bounce + ((const char*)o->dev - lo), o->bytes);
+            return F1P_OK;
+        }
+        for (Out* o : small) F1P_HIP(ctx, hipMemcpyAsync(o->host, o->dev, o->bytes, hipMemcpyDeviceToHost, ctx->stream));
+        F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return F1P_OK;
+    }
+};
+
+// The device-side address of [p, p + bytes) when the WHOLE range lies in page-locked host memory this device can address (hipHostMalloc /
+// hipHostRegister), else null.  A kernel that stores through it writes straight into the caller's array; a range that is only partly
+// registered would fault, so both ends must be known to HIP as host memory with ONE linear device mapping between them (the
+// first byte alone had been checked, and the host address used instead of attr.devicePointer).
+void* pinned_device_ptr(const void* p, size_t bytes);
+// ... with the context's own page-locked blocks answered from its table (no runtime call)
+void* pinned_device_ptr(const f1p_ctx* ctx, const void* p, size_t bytes);
+
+// A frame whose own host vectors are the source or the destination of asynchronous copies: every way out of it drains the stream first.
+// Declared before the first such copy; the copies go through copy(), the success path ends in finish() (the frame's ONE synchronisation).
+struct StreamDrain {
+    f1p_ctx* ctx;
+    bool armed = true;
+    ~StreamDrain() { if (armed) (void)hipStreamSynchronize(ctx->stream); }
+    int copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+        if (bytes) F1P_HIP(ctx, hipMemcpyAsync(dst, src, bytes, kind, ctx->stream));
+        return F1P_OK;
+    }
+    int finish() { armed = false; F1P_HIP(ctx, hipStreamSynchronize(ctx->stream)); return F1P_OK; }
+};
+
+// checks shared by several units
+int need_tracks(f1p_ctx* ctx, bool psi, bool kappa);                                        // f1p_scene.hip: a track set (with these columns) is loaded
+// the checks both shooting configurations share (f1p_kmpc_cfg, f1p_stmpc_cfg)
+template <typename CFG> int validate_shoot_cfg(f1p_ctx* ctx, const CFG* cfg, int E) {
+    if (!cfg) return set_error(ctx, F1P_EINVAL, "cfg is NULL");
+    if (E < 0) return set_error(ctx, F1P_EINVAL, "E must be >= 0");
+    if (cfg->horizon < 1 || cfg->horizon > 4096) return set_error(ctx, F1P_EINVAL, "horizon must be in [1, 4096]");
+    if (cfg->n_rollouts < 1) return set_error(ctx, F1P_EINVAL, "n_rollouts must be >= 1");
+    if (!(cfg->dt > 0) || !(cfg->wheelbase > 0)) return set_error(ctx, F1P_EINVAL, "dt and wheelbase must be > 0");
+    return F1P_OK;
+}
+inline int validate_kmpc(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, int E) { return validate_shoot_cfg(ctx, cfg, E); }
+inline int validate_stmpc(f1p_ctx* ctx, const f1p_stmpc_cfg* cfg, int E) { return validate_shoot_cfg(ctx, cfg, E); }
+// f1p_kmpc.hip: the QP's cfg checks, and opts (nullable: the defaults) into *o, range-checked
+int validate_kmpc_qp(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, int E, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o);
+int qp_opts(f1p_ctx* ctx, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o, const char* what);
+// f1p_kmpc.hip: the argument checks of the four reference extractions (f1p_{kmpc,stmpc}_ref[_tracks]_{batch,dev}), and the *_batch body behind them:
+// ncol = 4 (kinematic rows) or 7 (dynamic rows); track_id (host) is read when tracks, else every ego follows the raceline
+int validate_ref(f1p_ctx* ctx, const void* states, const int32_t* track_id, bool tracks, int E, int horizon, double dt, double dl, const void* ref);
+int ref_batch_impl(f1p_ctx* ctx, int ncol, const double* states, const int32_t* track_id, bool tracks, int32_t E, int32_t horizon, double dt, double dl,
+                   double* ref);
+
+}  // namespace f1p

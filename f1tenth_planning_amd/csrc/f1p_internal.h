@@ -10,6 +10,17 @@
 #include "f1p_device.h"
 
 #define F1P_KMPC_CFG_SLOTS 8
+
+// One planner's warm start on the device (host-only type; the operations are f1p::warm_* below).  The shape key is the planner's own
+// -- (E, T), (E, W) or (E, T, TK) -- and so is the rule that says whether the contents are valid.
+struct WarmBuf {
+    void* d = nullptr;
+    size_t bytes = 0;
+    int key[3] = {0, 0, 0};
+    bool is(int a, int b, int c = 0) const { return d && key[0] == a && key[1] == b && key[2] == c; }
+    template <typename T> T* as() const { return (T*)d; }
+};
+
 struct f1p_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -73,28 +84,24 @@ struct f1p_ctx {
     f1p_kmpc_cfg* h_kmpc_cfg = nullptr; // ... its pinned host shadow (compared per launch, the stable source of each slot's one copy)
     f1p_kmpc_cfg* d_kmpc_cfg_cur = nullptr; // the slot of the configuration of the launch being issued
     int kmpc_cfg_used = 0;
-    float* d_kmpc_warm = nullptr;      // [E][T][2] f32: previous plan's applied winner shifted by one step
-    int kmpc_warm_E = 0, kmpc_warm_T = 0;
+    WarmBuf kmpc_warm;                 // [E][T][2] f32, key (E, T): previous plan's applied winner shifted by one step
     bool kmpc_warm_valid = false;
     char* d_kmpc_scratch = nullptr;    // split-rollout mode: per-ego tickets [cap_E] | [cap_E][cap_R] filter costs (layout by capacity)
     int kmpc_cap_E = 0, kmpc_cap_R = 0;
     int kmpc_yaw_fixup = 1;            // k_kmpc_ref folds gathered course headings (kinematic_mpc.py:198-203); 0: the caller maintains the array
     int kmpc_groups = 0;               // 0 = automatic number of workgroups per ego; > 0 forces it (tests, A/B runs)
     // the linearised-QP MPC (f1p_kmpc_qp_*): its fp64 warm start [E][T][2], keyed by (E, T) like the shooting one, and the packing knob
-    double* d_kmpc_qp_warm = nullptr;
-    int kmpc_qp_warm_E = 0, kmpc_qp_warm_T = 0;
+    WarmBuf kmpc_qp_warm;
     bool kmpc_qp_warm_valid = false;
     int kmpc_qp_pack = 0;              // egos per wave at T <= 8: 0 = default, 1 or 4 forces it (timing runs)
     // the dynamic-MPC QP plan (f1p_stmpc_qp_plan_batch): fp64 warm start [E][W][2] = (oa, odelta_v), W = max(T, TK), keyed by (E, W);
     // per ego the length of the reference's self.oa (0: None) -- the branch's horizon -- on the host (the branch split is made there)
-    double* d_stmpc_qp_warm = nullptr;
-    int stmpc_qp_warm_E = 0, stmpc_qp_warm_W = 0;
+    WarmBuf stmpc_qp_warm;
     std::vector<int32_t> stmpc_qp_len;
     // the dynamic-MPC shooting plan (f1p_stmpc_plan_*): f32 warm start [E][W][2], W = max(T, TK), keyed by (E, T, TK), and per ego the
     // branch that wrote its row -- 0: none (zeros are generated around), 1: kinematic ([TK][2] = (accel, steer)), 2: dynamic
     // ([T][2] = (steering speed, accel)) -- on the host, where the branch split is made.  One allocation, one guard.
-    float* d_stmpc_warm = nullptr;
-    int stmpc_warm_E = 0, stmpc_warm_T = 0, stmpc_warm_TK = 0;
+    WarmBuf stmpc_warm;
     std::vector<int32_t> stmpc_warm_tag;
 
     // two-kernel branch and bound of the lattice planner: bounds and clothoids handed from the fit kernel to the evaluation kernel
@@ -191,6 +198,13 @@ int arena_reset(f1p_ctx* ctx, size_t need_bytes);
 void* arena_take(f1p_ctx* ctx, size_t bytes);
 
 GridDev grid_dev(const f1p_ctx* ctx);
+
+// warm-start buffers (f1p_core.hip).  warm_ensure: the buffer of `bytes` bytes for shape (a, b, c) -- kept as it is when that shape is held, else the
+// stream is drained and the buffer replaced: the old contents are gone, *fresh is set (also when the allocation then fails and the buffer is left
+// empty), and with `zero` the new one is filled with zeros.  warm_upload / warm_download: one copy of `bytes` bytes and a synchronisation.
+int warm_ensure(f1p_ctx* ctx, WarmBuf* w, size_t bytes, int a, int b, int c, bool zero, bool* fresh);
+int warm_upload(f1p_ctx* ctx, WarmBuf* w, const void* host, size_t bytes);
+int warm_download(f1p_ctx* ctx, const WarmBuf* w, void* host, size_t bytes);
 
 // kernel launchers (k_pursuit.hip / k_lattice.hip / k_kmpc.hip); all asynchronous on ctx->stream
 int launch_nearest(f1p_ctx* ctx, const double* d_pts, int E, double* d_proj, double* d_dist, double* d_t, int32_t* d_idx);

@@ -5,7 +5,7 @@ import numpy as np
 
 from f1tenth_planning_amd.dist import shard_range
 
-# f1p_api.hip lattice_plan_batch_impl: with page-locked rows a batch of >= 8192 egos is planned in K = min(E / 4096, 8) slices [E k / K, E (k + 1) / K)
+# f1p_lattice.hip lattice_plan_batch_impl: with page-locked rows a batch of >= 8192 egos is planned in K = min(E / 4096, 8) slices [E k / K, E (k + 1) / K)
 SLICE_MIN_EGOS, SLICE_EGOS, SLICES_MAX = 8192, 4096, 8
 # k_lattice_mixed.hip: a pipelined plan (f1p_lattice_set_pipeline) runs in at most 8 chunks of ((E + nch - 1) / nch + 3) & ~3 egos (at least 4)
 PIPE_CHUNKS_MAX = 8

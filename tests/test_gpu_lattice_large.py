@@ -1,7 +1,7 @@
 """Lattice batches past 4096 egos: every host / kernel path the library picks by batch size, at the sizes where it cuts a batch, against the
 all-fp64 exhaustive kernel on EVERY ego and against the oracle on the egos around every cut.
 
-Paths (f1p_api.hip lattice_plan_batch_impl, k_lattice_mixed.hip): the staged path with the one-copy gather of the result columns (packed up
+Paths (f1p_lattice.hip lattice_plan_batch_impl, k_lattice_mixed.hip): the staged path with the one-copy gather of the result columns (packed up
 to 1 MB, partly per array above it), page-locked rows planned in min(E / 4096, 8) slices with the rows' D2H on a second stream (fp64 and f32
 rows), page-locked columns without rows, device buffers, the plan pipelined in 2 / 3 / 8 chunks on two streams (two-egos-per-wave prologue
 from 3072 egos a chunk), and f1p_lattice_step_batch.  Sizes: 8192 (2 slices), 12 289 (3, odd split), 20 483 (5, uneven), 32 768 (8:

@@ -176,9 +176,96 @@ def test_oracle_contact(ctx, scene, orc):
             np.testing.assert_array_equal(ref[j], r0)
 
 
+def _rejections():
+    """The argument checks of the raceline / track-set twins: every exported name keeps its own return code and its own error text.
+    A fresh context (no raceline, no track set), then one whose raceline and track set have three columns (no heading, no curvature).
+    Rows: entry point, arguments behind the handle (`p` any valid address, E = 1), code, text."""
+    from f1tenth_planning_amd.runtime import Context
+    EINVAL, ESTATE = _abi.F1P_EINVAL, _abi.F1P_ESTATE
+    c = Context(0)
+    host = np.zeros(64)
+    host[56:60] = (0.999, 0.0, 0.0066, 0.0)
+    dbuf = c.alloc(512)
+    p, q, d = host.ctypes.data, host.ctypes.data + 8 * 56, dbuf.ptr
+    pp, st, lq, rf = (1, L, 0.33, 20.0), (1, 0.33, 5.0), (1, 0.33, 0.01, q, 0.75, 50, 1e-3), (1, T_REF, 0.1, 0.03)
+    wp = "Please set waypoints to track during planner instantiation or when calling plan()"
+    no_set, no_psi = "no track set: call f1p_set_track_set first", "waypoints with a heading column are required"
+    null_arg = [
+        ("nearest_point_batch", (None, 1, p, p, p, p), "bad pts / E"),
+        ("nearest_point_tracks_batch", (None, p, 1, p, p, p, p), "bad pts / track_id / E"),
+        ("nearest_point_tracks_batch", (p, None, 1, p, p, p, p), "bad pts / track_id / E"),
+        ("pure_pursuit_batch", (p, *pp, None, p, p, p, p), "poses, steer and speed are required"),
+        ("pure_pursuit_tracks_batch", (p, None, *pp, p, p, p, p, p), "poses, track_id, steer and speed are required"),
+        ("pure_pursuit_dev", (None, *pp, d, d, d, d, d), "poses, steer and speed are required"),
+        ("pure_pursuit_tracks_dev", (d, None, *pp, d, d, d, d, d), "poses, track_id, steer and speed are required"),
+        ("stanley_batch", (None, *st, p, p, p), "states, steer and speed are required"),
+        ("stanley_tracks_batch", (p, None, *st, p, p, p), "states, track_id, steer and speed are required"),
+        ("lqr_batch", (p, None, *lq, p, p, p), "states, err, q, steer and speed are required"),
+        ("lqr_tracks_batch", (p, None, p, *lq, p, p, p), "states, track_id, err, q, steer and speed are required"),
+        ("lqr_batch", (p, p, 1, 0.33, 0.0, q, 0.75, 50, 1e-3, p, p, p), "timestep and wheelbase must be > 0, max_iter >= 0"),
+        ("lqr_tracks_batch", (p, p, p, 1, 0.33, 0.0, q, 0.75, 50, 1e-3, p, p, p), "timestep and wheelbase must be > 0, max_iter >= 0"),
+        ("kmpc_ref_batch", (p, *rf, None), "bad states / ref / E"),
+        ("kmpc_ref_tracks_batch", (p, None, *rf, p), "bad states / track_id / ref / E"),
+        ("kmpc_ref_tracks_dev", (d, None, *rf, d), "bad states / track_id / ref / E"),
+        ("stmpc_ref_batch", (None, *rf, p), "bad states / ref / E"),
+        ("stmpc_ref_tracks_batch", (p, None, *rf, p), "bad states / track_id / ref / E"),
+        ("stmpc_ref_tracks_dev", (d, None, *rf, d), "bad states / track_id / ref / E"),
+        ("kmpc_ref_batch", (p, 1, 0, 0.1, 0.03, p), "horizon, dt and dl must be positive"),
+        ("stmpc_ref_tracks_batch", (p, p, 1, T_REF, 0.1, 0.0, p), "horizon, dt and dl must be positive"),
+    ]
+    nothing_loaded = [
+        ("nearest_point_batch", (p, 1, p, p, p, p), ESTATE, "waypoints not set"),
+        ("nearest_point_tracks_batch", (p, p, 1, p, p, p, p), ESTATE, no_set),
+        ("pure_pursuit_batch", (p, *pp, p, p, p, p, p), ESTATE, wp),
+        ("pure_pursuit_tracks_batch", (p, p, *pp, p, p, p, p, p), ESTATE, no_set),
+        ("pure_pursuit_dev", (d, *pp, d, d, d, d, d), ESTATE, wp),
+        ("pure_pursuit_tracks_dev", (d, d, *pp, d, d, d, d, d), ESTATE, no_set),
+        ("stanley_batch", (p, *st, p, p, p), ESTATE, wp),
+        ("stanley_tracks_batch", (p, p, *st, p, p, p), ESTATE, no_set),
+        ("lqr_batch", (p, p, *lq, p, p, p), ESTATE, wp),
+        ("lqr_tracks_batch", (p, p, p, *lq, p, p, p), ESTATE, no_set),
+        ("kmpc_ref_batch", (p, *rf, p), ESTATE, no_psi),
+        ("kmpc_ref_tracks_batch", (p, p, *rf, p), ESTATE, no_set),
+        ("kmpc_ref_tracks_dev", (d, d, *rf, d), ESTATE, no_set),
+        ("stmpc_ref_batch", (p, *rf, p), ESTATE, no_psi),
+        ("stmpc_ref_tracks_batch", (p, p, *rf, p), ESTATE, no_set),
+        ("stmpc_ref_tracks_dev", (d, d, *rf, d), ESTATE, no_set),
+    ]
+    no_heading, no_curv = "the track set has no heading column", "the track set has no curvature column"
+    three_columns = [
+        ("stanley_batch", (p, *st, p, p, p), EINVAL, "Waypoints needs to be a (Nxm), m >= 4, numpy array!"),
+        ("stanley_tracks_batch", (p, p, *st, p, p, p), ESTATE, no_heading),
+        ("lqr_batch", (p, p, *lq, p, p, p), EINVAL, "Waypoints needs to be a (Nxm), m >= 5, numpy array!"),
+        ("lqr_tracks_batch", (p, p, p, *lq, p, p, p), ESTATE, no_heading),
+        ("kmpc_ref_batch", (p, *rf, p), ESTATE, no_psi),
+        ("kmpc_ref_tracks_batch", (p, p, *rf, p), ESTATE, no_heading),
+        ("kmpc_ref_tracks_dev", (d, d, *rf, d), ESTATE, no_heading),
+        ("stmpc_ref_batch", (p, *rf, p), ESTATE, no_psi),
+        ("stmpc_ref_tracks_batch", (p, p, *rf, p), ESTATE, no_heading),
+        ("stmpc_ref_tracks_dev", (d, d, *rf, d), ESTATE, no_heading),
+    ]
+
+    def run(rows):
+        for name, args, code, text in rows:
+            rc = getattr(c.lib, "f1p_" + name)(c.h, *args)
+            assert (rc, c.lib.f1p_last_error(c.h).decode()) == (code, text), (name, args)
+
+    try:
+        run([(n, a, EINVAL, t) for n, a, t in null_arg])
+        run(nothing_loaded)
+        arc = _poly(40, seed=3)
+        c.set_waypoints(arc[:, :3]); c.set_tracks([arc[:, :3]])
+        run(three_columns)
+        c.set_tracks([arc[:, :4]])                                  # a heading, no curvature
+        run([("lqr_tracks_batch", (p, p, p, *lq, p, p, p), ESTATE, no_curv)])
+    finally:
+        c.close()
+
+
 def test_edge_cases(ctx, ref_ctx, scene):
     from f1tenth_planning_amd.runtime import F1PError
     tr, ids, st = scene
+    _rejections()
     # a tracks call with no set
     ctx.set_tracks([])
     with pytest.raises(F1PError) as ei:

@@ -80,10 +80,12 @@ def main():
         if r.returncode:
             sys.stderr.write(r.stdout + r.stderr)
             raise SystemExit(r.returncode)
-    res = sorted(glob.glob(os.path.join(CSRC, objdir, "k_*.o.res"))) + [os.path.join(CSRC, objdir, "f1p_api.o.res")]
-    srcs = sorted(glob.glob(os.path.join(CSRC, "k_*.hip")))
-    if len(res) != len(srcs) + 1 or not all(os.path.exists(p) for p in res):
-        raise SystemExit(f"kernel_resources: {objdir}/ holds remarks for {len(res) - 1} of {len(srcs)} kernel files -- rebuild (make clean; make)")
+    srcs = sorted(glob.glob(os.path.join(CSRC, "k_*.hip"))) + sorted(glob.glob(os.path.join(CSRC, "f1p_*.hip")))   # the kernel files, then the host API units
+    res = [os.path.join(CSRC, objdir, os.path.basename(p)[:-len(".hip")] + ".o.res") for p in srcs]
+    missing = [p for p in res if not os.path.exists(p)]
+    if missing:
+        raise SystemExit(f"kernel_resources: {objdir}/ holds remarks for {len(res) - len(missing)} of {len(srcs)} source files "
+                         f"({os.path.basename(missing[0])} missing) -- rebuild (make clean; make)")
     for rf in res:
         rows = resources(rf)
         names = demangle([r["name"] for r in rows])
