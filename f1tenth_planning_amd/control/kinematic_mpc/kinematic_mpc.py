@@ -12,8 +12,12 @@ GPU.
 
 mpc_config.SOLVER = "qp" selects the reference's own solver instead: the linearised QP of :245-450, solved exactly (to QP_TOL) by
 a batched fp64 interior-point kernel (csrc/k_kmpc_qp.hip), warm-started like the reference from the previous solution (unshifted).
+
+mpc_config.COLLISION = True (shooting only) tests every rollout against the occupancy grid installed with set_map / load_map: a rollout
+that touches an occupied cell cannot win (f1p_kmpc_set_collision).
 """
 import os
+import warnings
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -52,6 +56,9 @@ class mpc_config:
     SOLVER: str = "shooting"
     QP_TOL: float = 1e-10  # interior point: scaled KKT residuals and duality gap below this
     QP_MAX_ITER: int = 50  # interior-point iterations at most (status 2 beyond: the last iterate, like cvxpy's OPTIMAL_INACCURATE)
+    # occupancy test on the shooting solver's rollouts (set_map / load_map): a rollout through an occupied cell cannot win
+    COLLISION: bool = False
+    COLLISION_SUBSTEPS: int = 1  # tested points per time step, 1 .. 16 (a step covers up to MAX_SPEED * DTK metres)
 
 
 @dataclass
@@ -87,6 +94,11 @@ def _check_solver(c: mpc_config):
             n = 2 if name in ("Rk", "Rdk") else 4
             if w.shape != (n, n) or np.any(w - np.diag(np.diag(w)) != 0):
                 raise ValueError(f"SOLVER='qp' takes diagonal {n}x{n} weights only; mpc_config.{name} is not")
+    if c.COLLISION:
+        if c.SOLVER == "qp":
+            raise ValueError("mpc_config.COLLISION tests the shooting solver's rollouts; SOLVER='qp' has none")
+        if not 1 <= int(c.COLLISION_SUBSTEPS) <= 16:
+            raise ValueError(f"mpc_config.COLLISION_SUBSTEPS must be in [1, 16], not {c.COLLISION_SUBSTEPS!r}")
 
 
 def _qp_opts(c: mpc_config):
@@ -123,13 +135,59 @@ class KMPCPlanner:
         self._ctx = None
         self._calls = 0
         self._trk_qp_warm = None           # the QP warm start of the track-set path (plan_batch(tracks=...)): u [E, T, 2] fp64
+        self._map = None                   # (img u8, resolution, (ox, oy), occupied_below) of set_map
+        self._inflate = 0.0
         _check_solver(config)
+
+    def set_map(self, image, resolution, origin, occupied_thresh=0.65, negate=0, inflate=0.0):
+        """Occupancy image in the ROS map_server layout, with LatticePlanner.set_map's meaning: u8 [h, w], row 0 at the top, `origin` =
+        world (x, y[, yaw]) of the lower-left pixel; a cell is occupied when its occupancy probability (255 - v)/255 (v/255 if negate)
+        exceeds occupied_thresh.  `inflate` (metres) dilates the occupied set by a disc on the device, which turns the point test of
+        mpc_config.COLLISION into a disc test -- e.g. 0.155 for the half width of the reference's vehicle."""
+        image = np.asarray(image)
+        if image.ndim != 2:
+            raise ValueError("map image must be 2-D")
+        if len(origin) > 2 and abs(origin[2]) > 1e-12:
+            raise ValueError("map origin yaw must be 0")
+        img = image.astype(np.uint8)
+        if negate:
+            img = 255 - img
+        occupied_below = int(np.ceil(255.0 * (1.0 - occupied_thresh)))      # v < 255 (1 - thresh)  <=>  p > thresh
+        self._map = (np.ascontiguousarray(img), float(resolution), (float(origin[0]), float(origin[1])), occupied_below)
+        self._inflate = float(inflate)
+        if self._ctx is not None:
+            self._install_map(self._ctx)
+
+    def load_map(self, yaml_path, inflate=0.0):
+        """Read a ROS map_server YAML + image and install it as the occupancy grid (LatticePlanner.load_map)."""
+        from ...io import load_map
+        m = load_map(yaml_path)
+        self.set_map(m["image"], m["resolution"], m["origin"], occupied_thresh=m["occupied_thresh"], negate=0, inflate=inflate)   # negate already applied
+        return m
+
+    def _install_map(self, ctx):
+        ctx.set_grid(*self._map)
+        if self._inflate > 0.0:
+            ctx.inflate_grid(self._inflate)
+
+    def _check_collision(self):
+        """ValueError before anything touches the GPU: COLLISION without a map (the other COLLISION checks: _check_solver)"""
+        _check_solver(self.config)
+        if self.config.COLLISION and self._map is None:
+            raise ValueError("mpc_config.COLLISION needs an occupancy grid: call set_map / load_map first")
 
     def _context(self):
         if self._ctx is None:
             dev = self._device if self._device is not None else int(os.environ.get("LOCAL_RANK", "0"))
             self._ctx = Context(dev)
+            if self._map is not None:
+                self._install_map(self._ctx)
         return self._ctx
+
+    def _collision_switch(self, ctx):
+        c = self.config
+        if c.SOLVER != "qp":
+            ctx.kmpc_set_collision(bool(c.COLLISION), int(c.COLLISION_SUBSTEPS) if c.COLLISION else 1)
 
     def _bind(self, waypoints, fold_yaw=None):
         """fold_yaw: the vehicle heading of a single-vehicle call -- the course headings are then folded in place on the caller's
@@ -162,8 +220,9 @@ class KMPCPlanner:
         states: [x, y, delta, v, yaw, yawrate, beta] (the 7-state of f110_gym, :139-147).
         Returns (steering_angle, speed).
         """
-        _check_solver(self.config)
+        self._check_collision()
         ctx = self._bind(waypoints, fold_yaw=float(states[4]))
+        self._collision_switch(ctx)
         vehicle_state = State(x=states[0], y=states[1], delta=states[2], v=states[3], yaw=states[4], yawrate=states[5],
                               beta=states[6])
         x0 = np.array([[vehicle_state.x, vehicle_state.y, vehicle_state.v, vehicle_state.yaw]], dtype=np.float64)   # :487
@@ -176,6 +235,11 @@ class KMPCPlanner:
             self.odelta_v = out["u"][0, :, 1]
             return float(out["steer"][0]), float(out["speed"][0])
         out = self._shoot(ctx, x0)
+        if int(out["best_idx"][0]) < 0:        # every rollout runs into an occupied cell: a soft failure like pure pursuit's, (0, 0)
+            warnings.warn("kinematic MPC: every rollout is blocked by the occupancy grid; returning (0.0, 0.0)", RuntimeWarning, stacklevel=2)
+            self.oa = out["best_seq"][0, :, 0]
+            self.odelta_v = out["best_seq"][0, :, 1]
+            return 0.0, 0.0
         self.oa = out["best_seq"][0, :, 0]                 # the reference's attributes (:108-110); the warm start itself lives on the device
         self.odelta_v = out["best_seq"][0, :, 1]
         return float(out["steer"][0]), float(out["speed"][0])
@@ -208,15 +272,17 @@ class KMPCPlanner:
         (f32 [E, T, 2, R]) overrides the in-kernel sampler with a caller-supplied candidate set (streamed from HBM).
         SOLVER == "qp": dict(steer, speed, status, obj[, u [E, T, 2]]) -- per-ego status (0 solved, 1 infeasible, 2 not converged,
         3 non-finite input), never raised.
+        mpc_config.COLLISION: an ego whose rollouts are all blocked has best_idx -1, best_cost +inf, steer 0, speed 0 and a zero sequence.
         tracks: K courses in the `waypoints` format ([x, y, yaw, v]: four 1-D arrays or an array [4, N]) with track_ids [E]: ego e
         follows tracks[track_ids[e]]; `waypoints` is then not used.  The references come from one k_kmpc_ref_tracks launch (an id
         outside [0, K) gives NaN rows, hence NaN outputs and QP status 3 for that ego) and go to the same solvers."""
-        _check_solver(self.config)
+        self._check_collision()
         if self.config.SOLVER == "qp" and controls is not None:
             raise ValueError("controls are candidates of the shooting solver; SOLVER='qp' takes none")
         if tracks is not None:
             return self._plan_tracks(x0, tracks, track_ids, controls, want_seq)
         ctx = self._bind(waypoints)
+        self._collision_switch(ctx)
         x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, 4)
         if self.config.SOLVER == "qp":
             return self._qp(ctx, x0, want_u=want_seq)
@@ -239,6 +305,7 @@ class KMPCPlanner:
             cx, cy, cyaw, sp = (np.asarray(path[k], dtype=np.float64) for k in range(4))             # :479-482
             cols.append(np.column_stack([cx, cy, sp, cyaw]))
         ctx = self._context()
+        self._collision_switch(ctx)
         ctx.kmpc_set_yaw_fixup(True)                           # a batch: per-ego fold of the gathered headings, the courses stay as given
         ctx.set_tracks_cached(cols, cols=(0, 1, 2, 3))
         c = self.config

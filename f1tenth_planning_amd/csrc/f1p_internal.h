@@ -68,6 +68,8 @@ struct f1p_ctx {
 
     // shooting-MPC evaluation mode: f32 filter + fp64 refinement (default) or plain fp64; diagnostics of the filter
     bool kmpc_mixed = true;
+    bool kmpc_collision = false;   // f1p_kmpc_set_collision: rollouts of f1p_kmpc_plan_* / f1p_kmpc_shoot_* are tested against d_bits
+    int kmpc_col_nsub = 1;         // ... at this many points per time step
     float* d_dbg_cost32 = nullptr;     // [E][R] filter costs of the next launch (test hook), or null
     int32_t* d_dbg_nref = nullptr;     // [E] size of the refined set (-1 = fp64 fallback), or null
 

@@ -59,6 +59,25 @@ int ref_batch_impl(f1p_ctx* ctx, int ncol, const double* states, const int32_t* 
 
 }  // namespace f1p
 
+// f1p_kmpc_set_collision's preconditions, checked by every entry point that would launch the tested kernels -- before anything is launched
+static int kmpc_collision_check(f1p_ctx* ctx) {
+    if (!ctx->kmpc_collision) return F1P_OK;
+    if (!ctx->has_grid) return set_error(ctx, F1P_ESTATE, "kmpc collision test is on but no occupancy grid is loaded (f1p_set_grid)");
+    if (ctx->n_disc > 0)
+        return set_error(ctx, F1P_ESTATE, "kmpc collision test is a point / disc test: remove the oriented footprint (f1p_set_footprint) and use f1p_inflate_grid");
+    if (ctx->kmpc_groups > 0) return set_error(ctx, F1P_ESTATE, "kmpc collision test runs one workgroup per ego: f1p_kmpc_set_groups(0)");
+    if (ctx->kmpc_col_nsub < 1 || ctx->kmpc_col_nsub > 16) return set_error(ctx, F1P_EINVAL, "kmpc collision test: n_sub must be in [1, 16]");
+    return F1P_OK;
+}
+
+int f1p_kmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub) {
+    F1P_ENTER(ctx);
+    if (n_sub < 1 || n_sub > 16) return set_error(ctx, F1P_EINVAL, "kmpc collision test: n_sub must be in [1, 16]");
+    ctx->kmpc_collision = on != 0;
+    ctx->kmpc_col_nsub = n_sub;
+    return F1P_OK;
+}
+
 void f1p_kmpc_cfg_default(f1p_kmpc_cfg* cfg) {
     if (!cfg) return;
     memset(cfg, 0, sizeof(*cfg));
@@ -78,6 +97,7 @@ int f1p_kmpc_shoot_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, co
     int rc = validate_kmpc(ctx, cfg, E); if (rc) return rc;
     if (E > 0 && (!d_x0 || !d_ref || !d_controls || !d_steer || !d_speed || !d_best_idx))
         return set_error(ctx, F1P_EINVAL, "x0, ref, controls, steer, speed and best_idx are required");
+    if ((rc = kmpc_collision_check(ctx))) return rc;
     return launch_kmpc_shoot(ctx, d_x0, d_ref, d_controls, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
 }
 
@@ -88,6 +108,7 @@ int f1p_kmpc_shoot_batch(f1p_ctx* ctx, const double* x0, const double* ref, cons
     int rc = validate_kmpc(ctx, cfg, E); if (rc) return rc;
     if (E > 0 && (!x0 || !ref || !controls || !steer || !speed || !best_idx))
         return set_error(ctx, F1P_EINVAL, "x0, ref, controls, steer, speed and best_idx are required");
+    if ((rc = kmpc_collision_check(ctx))) return rc;
     const size_t T = cfg->horizon, R = cfg->n_rollouts, e = E;
     Stage s(ctx);
     s.need(8 * 4 * e); s.need(8 * e * 4 * (T + 1)); s.need(4 * e * T * 2 * R);
@@ -182,6 +203,7 @@ int f1p_kmpc_plan_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, int
     if (E == 0) return F1P_OK;
     if (!d_x0 || !d_ref || !d_steer || !d_speed || !d_best_idx) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and best_idx are required");
     if (cfg->n_rollouts > 8192) return set_error(ctx, F1P_EINVAL, "at most 8192 rollouts per plan");
+    if ((rc = kmpc_collision_check(ctx))) return rc;
     if ((rc = ensure_warm(ctx, E, cfg->horizon))) return rc;
     float* warm = ctx->kmpc_warm.as<float>();
     const float* warm_in = (smp->use_warm && ctx->kmpc_warm_valid) ? warm : nullptr;
@@ -199,6 +221,7 @@ int f1p_kmpc_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_kmp
     if (E > 0 && (!x0 || !steer || !speed || !best_idx)) return set_error(ctx, F1P_EINVAL, "x0, steer, speed and best_idx are required");
     if (!(dl > 0)) return set_error(ctx, F1P_EINVAL, "dl must be > 0");
     if (ctx->n_wp < 2 || !ctx->has_psi) return set_error(ctx, F1P_ESTATE, "waypoints with a heading column are required");
+    if ((rc = kmpc_collision_check(ctx))) return rc;
     const size_t T = cfg->horizon, e = E;
     Stage s(ctx);
     s.need(8 * 4 * e); s.need(8 * e * 4 * (T + 1));

@@ -26,6 +26,44 @@ namespace f1p {
 __device__ __forceinline__ double clampd(double v, double lo, double hi) { return v > hi ? hi : (v < lo ? lo : v); }
 
 // ---------------------------------------------------------------------------------------------------
+// Occupancy test on the rollouts (f1p_kmpc_set_collision).  The states p_0 .. p_T of the applied sequence are tested
+// at  p_t + (p_{t+1} - p_t) * ((double)j / (double)n_sub),  j = 1 .. n_sub (j == n_sub: p_{t+1} itself), t = 0 .. T-1, against the
+// ACTIVE bitmap with the lattice's cell rule (cell_of; outside the image or non-finite = occupied).  A rollout with an occupied
+// tested point is BLOCKED: it takes no part in the argmin.  The fp64 code below finds the test in its control SOURCE: SrcColT<Src> is Src plus
+// the grid, and `if constexpr (kmpc_has_col<Src>::value)` keeps every statement of the test out of the instantiations for a plain source,
+// whose signatures and bodies are what they were (the kernels without the test keep their instructions).
+// ---------------------------------------------------------------------------------------------------
+#define F1P_K4_NONE 0x7fffffff        // argmin index while no unblocked rollout has been seen
+struct KmpcCol {
+    GridDev g;                        // the active bitmap
+    const uint32_t* clear;            // clearance map for the f32 filter (null: the filter proves nothing, every rollout in fp64)
+    int n_sub;                        // tested points per time step, 1 .. 16
+    int force64;                      // f1p_kmpc_set_mode(0): no filter
+    __device__ __forceinline__ bool occupied(double x, double y) const {
+        int gx, gy;
+        if (!cell_of(g, x, y, gx, gy)) return true;
+        return (g.bits[(size_t)gy * g.wwords + (gx >> 5)] >> (gx & 31)) & 1u;
+    }
+    // the tested points of the step p -> q
+    __device__ __forceinline__ bool seg(double px, double py, double qx, double qy) const {
+        bool hit = false;
+        for (int j = 1; j < n_sub; ++j) {
+            const double f = (double)j / (double)n_sub;
+            hit |= occupied(px + (qx - px) * f, py + (qy - py) * f);
+        }
+        return hit | occupied(qx, qy);
+    }
+};
+// a control source with the occupancy test; `blocked`: the verdict on the rollout evaluated last (kmpc_rollout_cost / kmpc_rollout_lanes<true>)
+template <typename Base>
+struct SrcColT : Base {
+    KmpcCol col;
+    mutable bool blocked;
+};
+template <typename S> struct kmpc_has_col { static constexpr bool value = false; };
+template <typename B> struct kmpc_has_col<SrcColT<B>> { static constexpr bool value = true; };
+
+// ---------------------------------------------------------------------------------------------------
 // Where a rollout's controls come from.
 //   SrcStream: the f32 buffer [t][accel|steer][rollout] of one ego in HBM (f1p_kmpc_shoot_*: parity tests, BASELINE configs[4]);
 //   SrcGen   : generated in registers from (seed, call, ego, rollout, t) around the ego's warm start (f1p_kmpc_plan_*): nothing
@@ -63,6 +101,8 @@ struct SrcStream {
 };
 
 // fp64 cost of ONE rollout r: running sum in the reference's accumulation order
+// (SrcColT: the states it visits are tested as it goes and src.blocked is the verdict; a blocked rollout stops at its first occupied point and
+// what it returns is not a cost -- the callers read src.blocked first)
 template <bool FAST, typename Src>
 __device__ __forceinline__ double kmpc_rollout_cost(const Src& src, const double* sref, const f1p_kmpc_cfg& cfg, double sx,
                                                     double sy, double sv, double syaw, double dmax, int r) {
@@ -70,6 +110,7 @@ __device__ __forceinline__ double kmpc_rollout_cost(const Src& src, const double
     KmpcStep s;
     s.x = sx; s.y = sy; s.v = sv; s.yaw = syaw;
     double cost = 0.0, pa = 0.0, pd = 0.0;
+    if constexpr (kmpc_has_col<Src>::value) src.blocked = false;
     for (int t = 0; t < T; ++t) {
         float af, df;
         src.get(t, r, af, df);
@@ -86,7 +127,13 @@ __device__ __forceinline__ double kmpc_rollout_cost(const Src& src, const double
             const double da = a - pa, dd = d - pd;
             cost += cfg.rd[0] * da * da + cfg.rd[1] * dd * dd;                                           // :334
         }
-        kmpc_step<FAST>(s, a, d, cfg);
+        if constexpr (!kmpc_has_col<Src>::value) kmpc_step<FAST>(s, a, d, cfg);
+        else {
+            const double px = s.x, py = s.y;
+            kmpc_step<FAST>(s, a, d, cfg);
+            src.blocked |= src.col.seg(px, py, s.x, s.y);
+            if (src.blocked) break;                                   // its cost is never read (an all-blocked ego stops at the first step: p_1 is every rollout's)
+        }
         pa = a; pd = d;
     }
     const double e0 = s.x - sref[0 * (T + 1) + T], e1 = s.y - sref[1 * (T + 1) + T];
@@ -101,7 +148,11 @@ __device__ __forceinline__ void kmpc_rollouts(const Src& src, const double* sref
                                               double sy, double sv, double syaw, double dmax, int tid, double& bc, int& bi) {
     for (int r = tid; r < cfg.n_rollouts; r += blockDim.x) {
         const double cost = kmpc_rollout_cost<FAST>(src, sref, cfg, sx, sy, sv, syaw, dmax, r);
-        if (argmin_better(cost, r, bc, bi)) { bc = cost; bi = r; }
+        if constexpr (!kmpc_has_col<Src>::value) {
+            if (argmin_better(cost, r, bc, bi)) { bc = cost; bi = r; }
+        } else {
+            if (!src.blocked && argmin_better(cost, r, bc, bi)) { bc = cost; bi = r; }
+        }
     }
 }
 
@@ -255,6 +306,79 @@ __device__ __forceinline__ f1p_f2 kmpc_rollout_cost_f32x2(const Src& src, const 
     const f1p_f2 e2 = k.sqf[2] * s.v + sref32[2 * (T + 1) + T], e3 = k.sqf[3] * s.yaw + sref32[3 * (T + 1) + T];
     s.cost += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
     s.cost -= k.rd[0] * s.pa * s.pa + k.rd[1] * s.pd * s.pd;           // the last step has no successor (see KmpcF32)
+    return s.cost;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The filter's side of the occupancy test (k_kmpc_plan_gen_col).  It looks up every tested point -- the same n_sub points per step as the
+// fp64 test, formed from its own f32 states -- in the CLEARANCE map (k_grid.hip ensure_clear_map: bit 0 = no occupied or off-image cell
+// centre within D cells of this cell's centre) and calls a rollout FREE only when every one of them lands on a 0 bit.  Nothing between
+// tested points is skipped, so D only has to cover the f32 position error: the f32 point and the fp64 point lie less than one cell apart
+// (the launcher checks 1e-4 x reach < resolution; DESIGN.md 5h derives ~2e-5 x reach), so the fp64 point's cell is the f32 point's cell or
+// one of its eight neighbours, whose centres are <= sqrt(2) < D = 2 cells away: FREE implies unblocked.  Everything else -- an occupied
+// or nearly occupied cell, a point outside the image, a NaN -- is UNSURE and decided by the fp64 refinement.
+// Cell coordinates are kept RELATIVE to the ego's cell (ibx, iby: fp64 floor), so the f32 operands stay below reach / resolution cells.
+// ---------------------------------------------------------------------------------------------------
+#define F1P_K4_CLEAR_CELLS 2.0
+#define F1P_K4_POS_ERR_REL 1.0e-4
+struct KmpcColF {
+    const uint32_t* clear;
+    int wwords, n_sub, ibx, iby;
+    float inv_nsub, bx, by, lox, hix, loy, hiy, inv_res, c0, s0;
+    // (x, y): the filter's position -- ego frame (ISO) or world axes relative to the ego
+    template <bool ISO>
+    __device__ __forceinline__ bool unsure(float x, float y) const {
+        const float rx = ISO ? c0 * x - s0 * y : x, ry = ISO ? s0 * x + c0 * y : y;
+        const float fx = floorf(bx + rx * inv_res), fy = floorf(by + ry * inv_res);
+        const bool inside = (fx >= lox) & (fx < hix) & (fy >= loy) & (fy < hiy);      // NaN -> outside
+#ifdef F1P_K4_COL_NOLOOKUP            // A/B build: the cell arithmetic without the map read (where the open-space time goes)
+        return !inside;
+#else
+        const int gx = inside ? ibx + (int)fx : 0, gy = inside ? iby + (int)fy : 0;   // (inside: 0 <= gx < w, 0 <= gy < h)
+        return !inside | (bool)((clear[(size_t)gy * wwords + (gx >> 5)] >> (gx & 31)) & 1u);
+#endif
+    }
+};
+
+// kmpc_rollout_cost_f32x2 step by step, every step's tested points looked up; u0 / u1: rollout r0 / r1 is UNSURE
+template <bool POLY, bool ISO, typename Src>
+__device__ __forceinline__ f1p_f2 kmpc_rollout_cost_f32x2_col(const Src& src, const float* sref32, const KmpcF32& k, int T, int r0, int r1,
+                                                             const KmpcColF& cf, bool& u0, bool& u1) {
+    KmpcState2 s;
+    s.x = 0.f; s.y = 0.f; s.v = k.v0; s.yaw = 0.f; s.cost = 0.f; s.pa = 0.f; s.pd = 0.f;
+    bool h0 = false, h1 = false;
+    for (int te = 0; te < T; te += 2) {
+        f1p_f2 av[2], dv[2];
+        {
+            float a00, d00, a01, d01, a10, d10, a11, d11;
+            src.template get2<false>(te, T, r0, a00, d00, a01, d01);
+            src.template get2<false>(te, T, r1, a10, d10, a11, d11);
+            av[0].x = a00; av[0].y = a10; dv[0].x = d00; dv[0].y = d10;
+            av[1].x = a01; av[1].y = a11; dv[1].x = d01; dv[1].y = d11;
+        }
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) {
+            const int t = te + jj;
+            if (t < T) {
+                const f1p_f2 px = s.x, py = s.y;
+                const f1p_f2 a1[1] = {av[jj]}, d1[1] = {dv[jj]};
+                kmpc_steps2<POLY, ISO, false, false, 1>(s, sref32, k, T, t, a1, d1);
+                for (int j = 1; j < cf.n_sub; ++j) {
+                    const float f = (float)j * cf.inv_nsub;
+                    const f1p_f2 qx = px + (s.x - px) * f, qy = py + (s.y - py) * f;
+                    h0 |= cf.template unsure<ISO>(qx.x, qy.x);
+                    h1 |= cf.template unsure<ISO>(qx.y, qy.y);
+                }
+                h0 |= cf.template unsure<ISO>(s.x.x, s.y.x);
+                h1 |= cf.template unsure<ISO>(s.x.y, s.y.y);
+            }
+        }
+    }
+    const f1p_f2 e0 = k.sqf[0] * s.x + sref32[0 * (T + 1) + T], e1 = k.sqf[1] * s.y + sref32[1 * (T + 1) + T];
+    const f1p_f2 e2 = k.sqf[2] * s.v + sref32[2 * (T + 1) + T], e3 = k.sqf[3] * s.yaw + sref32[3 * (T + 1) + T];
+    s.cost += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
+    s.cost -= k.rd[0] * s.pa * s.pa + k.rd[1] * s.pd * s.pd;           // the last step has no successor (see KmpcF32)
+    u0 = h0; u1 = h1;
     return s.cost;
 }
 
@@ -414,6 +538,8 @@ __device__ __forceinline__ double lane_up1(double v) {                // lane i 
 
 // lane j (0 <= j < group size, j == 0 at the group's first lane) returns the applied controls (a, d) of step j (j < T) and, with
 // COST, the rollout's cost in EVERY lane j >= T ... of which the caller reads lane T.  `sref` as in kmpc_rollout_cost.
+// SrcColT (COST only): lane j (1 <= j <= T) tests the points of the step p_{j-1} -> p_j, lane_up1 supplying p_{j-1}; src.blocked is the
+// OR over the rollout's lane group, in every lane of it.
 template <bool COST, typename Src>
 __device__ __forceinline__ double kmpc_rollout_lanes(const Src& src, const double* sref, const f1p_kmpc_cfg& cfg, double sx, double sy,
                                                      double sv, double syaw, double dmax, int r, int j, double& a, double& d) {
@@ -488,6 +614,13 @@ __device__ __forceinline__ double kmpc_rollout_lanes(const Src& src, const doubl
         x = first ? sx : xn;
         y = first ? sy : yn;
     }
+    if constexpr (kmpc_has_col<Src>::value) {
+        const double qx = lane_up1(x), qy = lane_up1(y);
+        const bool hit = j >= 1 && j <= T && src.col.seg(qx, qy, x, y);
+        const unsigned long long votes = __ballot(hit);             // (the active lanes: the groups that hold a survivor)
+        const unsigned long long mine = T + 1 <= 32 ? 0xffffffffull << (__lane_id() & 32) : ~0ull;
+        src.blocked = (votes & mine) != 0ull;
+    }
     F1P_KST(6);
     // ---- stage terms (all lanes), then the cost in the reference's accumulation order -----------------------------------------
     const int jj = j < T ? j : T;
@@ -555,9 +688,26 @@ __device__ __forceinline__ void kmpc_emit_wave(const Src& src, const f1p_kmpc_cf
     }
 }
 
+// every rollout of the ego is blocked (f1p_kmpc_set_collision): the lattice's ALL_BLOCKED outputs, a zero sequence and a zero warm start.
+// Called by (at least) the whole first wave.
+__device__ __forceinline__ void kmpc_emit_blocked(const f1p_kmpc_cfg& cfg, int e, double* __restrict__ steer, double* __restrict__ speed,
+                                                  int32_t* __restrict__ best_idx, double* __restrict__ best_cost, double* __restrict__ best_seq,
+                                                  float* __restrict__ warm_out) {
+    const int T = cfg.horizon, tid = threadIdx.x;
+    if (tid >= 64) return;
+    if (tid == 0) {
+        steer[e] = 0.0; speed[e] = 0.0; best_idx[e] = -1;
+        if (best_cost) best_cost[e] = __builtin_huge_val();
+    }
+    for (int q = tid; q < 2 * T; q += 64) {
+        if (best_seq) best_seq[(size_t)e * 2 * T + q] = 0.0;
+        if (warm_out) warm_out[q] = 0.0f;
+    }
+}
+
 // fp64 re-evaluation by the whole workgroup (all 256 threads must call it; workgroup-uniform arguments).  n > 0: the listed
 // survivors, one lane each; n < 0: every rollout, one lane per rollout (the code of the plain kernel).  `sref` is LDS scratch
-// of 4 (T+1) + 4 doubles + 4 ints.
+// of 4 (T+1) + 4 doubles + 4 ints.  SrcColT: blocked rollouts leave (bc, bi) at (+inf, F1P_K4_NONE).
 template <typename Src>
 __device__ __forceinline__ void kmpc_refine_block(const double* __restrict__ ref, const Src& ce, const f1p_kmpc_cfg& cfg,
                                                   double sx, double sy, double sv, double syaw, int e, int n, const int* list, double* sref,
@@ -585,7 +735,11 @@ __device__ __forceinline__ void kmpc_refine_block(const double* __restrict__ ref
         if (gid < n) {
             mine = list[gid];
             const double c = kmpc_rollout_lanes<true>(ce, sref, cfg, sx, sy, sv, syaw, dmax, mine, j, a, d);
-            if (j == T) { bc = c; bi = mine; }
+            if constexpr (!kmpc_has_col<Src>::value) {
+                if (j == T) { bc = c; bi = mine; }
+            } else {
+                if (j == T && !ce.blocked) { bc = c; bi = mine; }
+            }
         }
         F1P_KST(9);
         if (one_wave) {
@@ -593,10 +747,12 @@ __device__ __forceinline__ void kmpc_refine_block(const double* __restrict__ ref
             // instead of a butterfly over 64 lanes
             const int clo = __double2loint(bc), chi = __double2hiint(bc);
             bc = __hiloint2double(__builtin_amdgcn_readlane(chi, T), __builtin_amdgcn_readlane(clo, T));
+            int i1 = 0;
+            if constexpr (kmpc_has_col<Src>::value) { if (n > 1) i1 = __builtin_amdgcn_readlane(bi, GL + T); }   // (a blocked survivor: F1P_K4_NONE)
             bi = __builtin_amdgcn_readlane(bi, T);
             if (n > 1) {
                 const double c1 = __hiloint2double(__builtin_amdgcn_readlane(chi, GL + T), __builtin_amdgcn_readlane(clo, GL + T));
-                const int i1 = list[1];
+                if constexpr (!kmpc_has_col<Src>::value) i1 = list[1];
                 if (argmin_better(c1, i1, bc, bi)) { bc = c1; bi = i1; }
             }
         } else {
@@ -604,19 +760,23 @@ __device__ __forceinline__ void kmpc_refine_block(const double* __restrict__ ref
         }
         F1P_KST(10);
         if (mine == bi) kmpc_emit_lanes(cfg, sv, e, j, a, d, bi, bc, steer, speed, best_idx, best_cost, best_seq, warm_out);
+        if constexpr (kmpc_has_col<Src>::value) { if (bi == F1P_K4_NONE) kmpc_emit_blocked(cfg, e, steer, speed, best_idx, best_cost, best_seq, warm_out); }
         F1P_KST(11);
         if (tid == 0 && n_refined) n_refined[e] = n;
         return;
     }
     if (n > 0) {
         if (tid < n) { bi = list[tid]; bc = kmpc_rollout_cost<true>(ce, sref, cfg, sx, sy, sv, syaw, dmax, bi); }
+        if constexpr (kmpc_has_col<Src>::value) { if (tid < n && ce.blocked) { bc = __builtin_huge_val(); bi = F1P_K4_NONE; } }
     } else {
         const bool fast = fabs(syaw) <= 1.0e4 && fabs(cfg.max_steer) <= 1.0e4;   // workgroup-uniform
         if (fast) kmpc_rollouts<true>(ce, sref, cfg, sx, sy, sv, syaw, dmax, tid, bc, bi);
         else kmpc_rollouts<false>(ce, sref, cfg, sx, sy, sv, syaw, dmax, tid, bc, bi);
     }
     block_argmin(bc, bi, red_d, red_i);
-    kmpc_emit_wave(ce, cfg, sv, dmax, e, bi, bc, steer, speed, best_idx, best_cost, best_seq, warm_out);
+    if constexpr (!kmpc_has_col<Src>::value) kmpc_emit_wave(ce, cfg, sv, dmax, e, bi, bc, steer, speed, best_idx, best_cost, best_seq, warm_out);
+    else if (bi == F1P_K4_NONE) kmpc_emit_blocked(cfg, e, steer, speed, best_idx, best_cost, best_seq, warm_out);
+    else kmpc_emit_wave(ce, cfg, sv, dmax, e, bi, bc, steer, speed, best_idx, best_cost, best_seq, warm_out);
     if (tid == 0 && n_refined) n_refined[e] = n;
 }
 
@@ -749,6 +909,7 @@ struct KmpcGenArgs {
 // would get wherever it stands in the list.
 struct KmpcIdxArgs { const int32_t* ids; int wstride; uint32_t ego_off; };
 
+#define F1P_KPG_COL 0
 #define F1P_KPG_NAME k_kmpc_plan_gen
 #define F1P_KPG_EXTRA
 #define F1P_KPG_EGO (uint32_t)e
@@ -767,6 +928,19 @@ struct KmpcIdxArgs { const int32_t* ids; int wstride; uint32_t ego_off; };
 #undef F1P_KPG_EXTRA
 #undef F1P_KPG_EGO
 #undef F1P_KPG_WROW
+#undef F1P_KPG_COL
+// k_kmpc_plan_gen_col: k_kmpc_plan_gen with the occupancy test of f1p_kmpc_set_collision (its own kernel: the test costs the plain one nothing)
+#define F1P_KPG_COL 1
+#define F1P_KPG_NAME k_kmpc_plan_gen_col
+#define F1P_KPG_EXTRA KmpcCol col,
+#define F1P_KPG_EGO (uint32_t)e
+#define F1P_KPG_WROW (size_t)e * 2 * T
+#include "k_kmpc_plan_gen_text.h"
+#undef F1P_KPG_NAME
+#undef F1P_KPG_EXTRA
+#undef F1P_KPG_EGO
+#undef F1P_KPG_WROW
+#undef F1P_KPG_COL
 
 // materialise SrcGen's controls as the [E][T][2][R] f32 buffer of the streamed entry points (tests: generated == streamed)
 __global__ __launch_bounds__(256) void k_kmpc_gen_controls(float* __restrict__ controls, int E, int T, int R, KmpcGenArgs ga) {
@@ -807,6 +981,24 @@ __global__ __launch_bounds__(256, F1P_K4_WAVES) void k_kmpc_shoot(const double* 
     else kmpc_rollouts<false>(ce, sref, cfg, sx, sy, sv, syaw, dmax, tid, bc, bi);
     block_argmin(bc, bi, red_d, red_i);
     kmpc_emit_wave(ce, cfg, sv, dmax, e, bi, bc, steer, speed, best_idx, best_cost, best_seq, nullptr);
+}
+
+// k_kmpc_shoot with the occupancy test: what f1p_kmpc_shoot_* launch in EVERY mode while f1p_kmpc_set_collision is on (the serial fp64
+// rollout tests its points as it goes: the definition of the result, and the parity hook of k_kmpc_plan_gen_col)
+__global__ __launch_bounds__(256, F1P_K4_WAVES) void k_kmpc_shoot_col(const double* __restrict__ x0, const double* __restrict__ ref,
+                                                    const float* __restrict__ controls, int E, f1p_kmpc_cfg cfg, KmpcCol col,
+                                                    double* __restrict__ steer, double* __restrict__ speed,
+                                                    int32_t* __restrict__ best_idx, double* __restrict__ best_cost,
+                                                    double* __restrict__ best_seq) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    double* sref = reinterpret_cast<double*>(lds_raw);   // [4][T+1] + [4] + int [4]
+    const int e = blockIdx.x;
+    if (e >= E) return;
+    const int T = cfg.horizon, R = cfg.n_rollouts;
+    SrcColT<SrcStream> ce;
+    ce.ce = controls + (size_t)e * T * 2 * R; ce.R = R; ce.col = col; ce.blocked = false;
+    kmpc_refine_block(ref, ce, cfg, x0[4 * e], x0[4 * e + 1], x0[4 * e + 2], x0[4 * e + 3], e, -1, nullptr, sref, steer, speed, best_idx, best_cost,
+                      best_seq, nullptr, nullptr, false);
 }
 
 // predict_motion_kinematic :208-221: one thread per ego, T sequential steps, path [E][4][T+1]
@@ -942,6 +1134,17 @@ __global__ void k_argmin_reduce(const uint64_t* __restrict__ recs, int N, int E,
 
 static KmpcF32 make_kf(const f1p_kmpc_cfg* cfg);
 
+// the occupancy test's kernel argument.  filter: the launch runs the f32 filter -- it gets the clearance map when the mode is mixed, the map
+// can be built and the f32 position bound (F1P_K4_POS_ERR_REL x the rollouts' reach) is below one cell; otherwise every rollout is decided in fp64
+static KmpcCol kmpc_col_dev(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, bool filter) {
+    KmpcCol c;
+    c.g = grid_dev(ctx); c.clear = nullptr; c.n_sub = ctx->kmpc_col_nsub; c.force64 = ctx->kmpc_mixed ? 0 : 1;
+    const double reach = fmax(fabs(cfg->max_speed), fabs(cfg->min_speed)) * cfg->horizon * cfg->dt;
+    if (filter && ctx->kmpc_mixed && F1P_K4_POS_ERR_REL * reach * ctx->inv_res < 1.0 && ensure_clear_map(ctx, F1P_K4_CLEAR_CELLS) == F1P_OK)
+        c.clear = ctx->d_bits_clear;
+    return c;
+}
+
 // the device copy of the configuration the shooting kernels' fp64 tails read.  A small write-once table (round 6): every distinct
 // configuration gets its own device slot and its own PINNED host shadow, neither is overwritten while a launch that reads it may be in
 // flight -- two planners alternating configurations on one context hit their slots without any copy; a ninth distinct configuration
@@ -970,6 +1173,12 @@ int launch_kmpc_shoot(f1p_ctx* ctx, const double* d_x0, const double* d_ref, con
                       double* d_best_cost, double* d_best_seq) {
     if (E <= 0) return F1P_OK;
     const size_t T1 = (size_t)cfg->horizon + 1;
+    if (ctx->kmpc_collision) {                                        // (the caller checked the grid: kmpc_collision_check)
+        const size_t lds = sizeof(double) * (4 * T1 + 4) + sizeof(int) * 4;
+        hipLaunchKernelGGL(k_kmpc_shoot_col, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E,
+                           *cfg, kmpc_col_dev(ctx, cfg, false), d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
+        return check_hip(ctx, hipGetLastError(), "k_kmpc_shoot_col launch");
+    }
     if (ctx->kmpc_mixed && cfg->n_rollouts <= 8192) {
         const KmpcF32 kf = make_kf(cfg);
         const size_t lds = sizeof(float) * (4 * T1 + (size_t)cfg->n_rollouts + 4) + sizeof(int) * (F1P_K4_MAX_REFINE + 1) + 8 +
@@ -1063,9 +1272,17 @@ int launch_kmpc_plan_gen(f1p_ctx* ctx, const double* d_x0, const double* d_ref, 
     if (block < 64) block = 64;
     size_t lds = sizeof(float) * (4 * T1 + 2 * T + 4) + sizeof(int) * (F1P_K4_MAX_REFINE + 2) + 8 + sizeof(double) * (4 * T1 + 4 + 2) + sizeof(int) * 4;
     if (ga.G == 1) lds += sizeof(float) * R;
+    const bool collide = ctx->kmpc_collision && !d_ids;              // (f1p_stmpc_plan_*'s kinematic branch: not tested)
     lds = (lds + 15) & ~(size_t)15;
     if (lds > (size_t)ctx->prop.sharedMemPerBlock) return set_error(ctx, F1P_EINVAL, "horizon / n_rollouts need more LDS than a workgroup has: use fewer rollouts per plan");
     if (const int rc = ensure_kmpc_cfg(ctx, cfg)) return rc;
+    if (collide) {
+        if (ga.G != 1) return set_error(ctx, F1P_ESTATE, "kmpc collision test: one workgroup per ego only (f1p_kmpc_set_groups(0))");
+        const KmpcCol col = kmpc_col_dev(ctx, cfg, true);
+        hipLaunchKernelGGL(k_kmpc_plan_gen_col, dim3((unsigned)E), dim3(block), lds, ctx->stream, d_x0, d_ref, E, *cfg, make_kf(cfg), ga, col,
+                           d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_nref, ctx->d_kmpc_cfg_cur);
+        return check_hip(ctx, hipGetLastError(), "k_kmpc_plan_gen_col launch");
+    }
     if (d_ids)
         hipLaunchKernelGGL(k_kmpc_plan_gen_idx, dim3((unsigned)((size_t)E * ga.G)), dim3(block), lds, ctx->stream, d_x0, d_ref, E, *cfg, make_kf(cfg), ga,
                            KmpcIdxArgs{d_ids, wstride, ego_off}, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_nref, ctx->d_kmpc_cfg_cur);

@@ -1,6 +1,9 @@
 // k_kmpc_plan_gen_text.h -- the text of k_kmpc_plan_gen, included by k_kmpc.hip once per kernel it defines:
 //   F1P_KPG_NAME   the kernel's name           F1P_KPG_EXTRA  parameters after `ga` (with their trailing comma), or nothing
 //   F1P_KPG_EGO    the generator's ego word    F1P_KPG_WROW   first float of ego e's row in ga.warm_in / ga.warm_out
+//   F1P_KPG_COL    1: the occupancy test of f1p_kmpc_set_collision (F1P_KPG_EXTRA then declares `KmpcCol col`; one workgroup per ego only).
+//                  The filter marks each rollout FREE or UNSURE next to its f32 cost, the threshold comes from the FREE minimum, the
+//                  FREE and UNSURE rollouts at or below it are refined in fp64 with the exact test.
 // (A kernel text compiled twice, not a shared inlined body: k_kmpc_plan_gen's code object has to stay what it was, instruction for
 // instruction, and the optimiser does not promise that for a __global__ wrapper around an inlined template.)
 __global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void F1P_KPG_NAME(const double* __restrict__ x0, const double* __restrict__ ref, int E,
@@ -31,11 +34,23 @@ __global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void F1P_KPG_NAME(const doub
     F1P_KPH();
     const double sx = x0[4 * e], sy = x0[4 * e + 1], sv = x0[4 * e + 2], syaw = x0[4 * e + 3];
     for (int q = tid; q < 2 * T; q += blockDim.x) warm_s[q] = ga.warm_in ? ga.warm_in[F1P_KPG_WROW + q] : 0.0f;
+#if F1P_KPG_COL
+    SrcColT<SrcGenT<true>> src;
+    src.col = col; src.blocked = false;
+#else
     SrcGenT<true> src;
+#endif
     src.k0 = ga.k0; src.k1 = ga.k1; src.call = ga.call; src.ego = F1P_KPG_EGO; src.sig_a = ga.sig_a; src.sig_d = ga.sig_d;
     src.warm = warm_s;
     float* warm_out = ga.warm_out ? ga.warm_out + F1P_KPG_WROW : nullptr;
+#if F1P_KPG_COL
+    // the ego's cell (fp64) anchors the filter's cell coordinates; an ego without one, no clearance map or f1p_kmpc_set_mode(0): all in fp64
+    const double bxd = (sx - col.g.ox) * col.g.inv_res, byd = (sy - col.g.oy) * col.g.inv_res;
+    const bool col_ok = col.clear && !col.force64 && fabs(bxd) < 1.0e6 && fabs(byd) < 1.0e6;
+    const bool in_range = fabs(syaw) <= 1.0e4 && fabs(cfg.max_steer) <= 1.0e4 && kf.w_ok && col_ok;
+#else
     const bool in_range = fabs(syaw) <= 1.0e4 && fabs(cfg.max_steer) <= 1.0e4 && kf.w_ok;     // workgroup-uniform: the fast paths' ranges
+#endif
     double s0d, c0d;
     sincos_core(in_range ? syaw : 0.0, &s0d, &c0d);
     const bool poly = kf.max_steer <= 0.45f;
@@ -53,6 +68,17 @@ __global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void F1P_KPG_NAME(const doub
     k.s0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, (float)s0d)));
     k.v0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, (float)sv)));
 
+#if F1P_KPG_COL
+    KmpcColF cf;
+    {
+        const double ibx = col_ok ? __builtin_floor(bxd) : 0.0, iby = col_ok ? __builtin_floor(byd) : 0.0;
+        cf.clear = col.clear; cf.wwords = col.g.wwords; cf.n_sub = col.n_sub; cf.inv_nsub = 1.0f / (float)col.n_sub;
+        cf.ibx = __builtin_amdgcn_readfirstlane((int)ibx); cf.iby = __builtin_amdgcn_readfirstlane((int)iby);
+        cf.bx = (float)(bxd - ibx); cf.by = (float)(byd - iby);
+        cf.lox = (float)-cf.ibx; cf.hix = (float)(col.g.w - cf.ibx); cf.loy = (float)-cf.iby; cf.hiy = (float)(col.g.h - cf.iby);
+        cf.inv_res = (float)col.g.inv_res; cf.c0 = k.c0; cf.s0 = k.s0;
+    }
+#endif
     F1P_KPH();
     // ---- pass A: f32 filter over this workgroup's slice ---------------------------------------------------------------
     const int r_lo = g * ga.Rs, r_hi = min(R, r_lo + ga.Rs);
@@ -62,11 +88,22 @@ __global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void F1P_KPG_NAME(const doub
         const int half = (r_hi - r_lo + 1) >> 1;                      // rollouts r and r + half share the packed lanes
         for (int q = tid; q < half; q += blockDim.x) {
             const int r = r_lo + q, r1 = r + half < r_hi ? r + half : r;
+#if F1P_KPG_COL
+            bool u0, u1;
+            const f1p_f2 c = iso ? kmpc_rollout_cost_f32x2_col<true, true>(src, sref32, k, T, r, r1, cf, u0, u1)
+                                 : (poly ? kmpc_rollout_cost_f32x2_col<true, false>(src, sref32, k, T, r, r1, cf, u0, u1)
+                                         : kmpc_rollout_cost_f32x2_col<false, false>(src, sref32, k, T, r, r1, cf, u0, u1));
+            cost_out[r] = c.x;
+            if (r1 != r) cost_out[r1] = c.y;
+            // the minimum over FREE rollouts only; the flags are not kept: the survivors are the FREE and the UNSURE rollouts at or below the threshold alike
+            fmin_ = fminf(fmin_, fminf(u0 ? __builtin_huge_valf() : c.x, u1 ? __builtin_huge_valf() : c.y));
+#else
             const f1p_f2 c = iso ? kmpc_rollout_cost_f32x2<true, true>(src, sref32, k, T, r, r1)
                                  : (poly ? kmpc_rollout_cost_f32x2<true, false>(src, sref32, k, T, r, r1) : kmpc_rollout_cost_f32x2<false, false>(src, sref32, k, T, r, r1));
             cost_out[r] = c.x;
             if (r1 != r) cost_out[r1] = c.y;
             fmin_ = fminf(fmin_, fminf(c.x, c.y));                     // NaN costs are ignored here and caught below (r1 == r: c.y repeats c.x)
+#endif
 #ifndef F1P_K4_PHASES
             if (ga.G == 1 && ga.cost32) { ga.cost32[(size_t)e * R + r] = c.x; if (r1 != r) ga.cost32[(size_t)e * R + r1] = c.y; }
 #endif
@@ -116,12 +153,12 @@ __global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void F1P_KPG_NAME(const doub
         }
         __syncthreads();
         const int n = cnt[0];
-        n_eff = (n > F1P_K4_MAX_REFINE || n < 1 || !isfinite(fmin_)) ? -1 : n;   // pathological inputs, degenerate ties: all rollouts in fp64
+        n_eff = (n > F1P_K4_MAX_REFINE || n < 1 || !isfinite(fmin_)) ? -1 : n;   // pathological inputs, degenerate ties (COL: no FREE rollout): all rollouts in fp64
     }
     F1P_KPH();
     const f1p_kmpc_cfg& s_cfg = *dcfg;                               // (the device copy: see k_kmpc_shoot_mixed)
     if (n_eff == 1 && !best_cost) {
-        // a single survivor needs no fp64 cost unless it is asked for
+        // a single survivor needs no fp64 cost unless it is asked for (COL: it is the FREE minimum, proved free)
         kmpc_emit_wave(src, s_cfg, sv, s_cfg.max_dsteer * s_cfg.dt, e, list[0], 0.0, steer, speed, best_idx, nullptr, best_seq, warm_out);
         if (tid == 0 && n_refined) n_refined[e] = 1;
     } else {

@@ -741,6 +741,11 @@ class Context:
     def kmpc_set_groups(self, groups=0):
         self._check(self.lib.f1p_kmpc_set_groups(self.h, int(groups)))
 
+    def kmpc_set_collision(self, on=True, n_sub=1):
+        """test the shooting solver's rollouts against the occupancy grid at n_sub points per time step (f1p_kmpc_set_collision): a
+        blocked rollout cannot win; an ego whose rollouts are all blocked gets best_idx -1, cost +inf, steer 0, speed 0"""
+        self._check(self.lib.f1p_kmpc_set_collision(self.h, 1 if on else 0, int(n_sub)))
+
     # ---- kinematic MPC, the reference's linearised QP (f1p_kmpc_qp_*) ----------------------------------------------------------------
     def kmpc_qp(self, x0, ref, cfg: KmpcCfg, oa_prev=None, od_prev=None, opts=None, want_u=True, want_xk=False, want_obj=True,
                 want_duals=False, want_iters=True):

@@ -574,6 +574,24 @@ int f1p_kmpc_warm_set(f1p_ctx* ctx, const float* warm, int32_t E, int32_t T);
  * re-emission run with the time steps across lanes); > 0 forces the count -- each workgroup filters a slice of the rollouts, the
  * last one to finish reduces (tests, A/B runs) */
 int f1p_kmpc_set_groups(f1p_ctx* ctx, int32_t groups);
+/* Occupancy test on the rollouts of the shooting solver.
+ * on = 0 (default): rollouts are not tested against the grid.  on = 1: a rollout of f1p_kmpc_plan_* / f1p_kmpc_shoot_* whose
+ * tested points touch an occupied cell costs +inf.  n_sub in [1, 16]: points tested per time step.
+ * Tested points: with p_0 .. p_T the states of the APPLIED sequence (bounds and rate limit) under update_state_kinematic, for
+ * t = 0 .. T-1 and j = 1 .. n_sub the point p_t + (p_{t+1} - p_t) * ((double)j / (double)n_sub), per coordinate in fp64 in that
+ * order; j = n_sub is p_{t+1} itself; p_0, the vehicle's present position, is not tested.
+ * Cell rule: the lattice's, on the ACTIVE bitmap -- f1p_inflate_grid(r) makes it a disc test of radius r; a point outside the
+ * image or a non-finite coordinate is occupied.
+ * Decision: first minimum by rollout index over the unblocked rollouts (NaN costs as without the test).  Every rollout
+ * blocked: best_idx = -1, best_cost = +inf, steer = 0, speed = 0, best_seq all zero, and the ego's warm-start row is set to zero.
+ * f1p_kmpc_plan_* in the mixed mode runs an f32 filter that only decides what cannot win; outputs are bit-identical to mode 0.
+ * f1p_kmpc_shoot_* (streamed controls) with the test on are evaluated in plain fp64 WHATEVER f1p_kmpc_set_mode says; with the
+ * same controls they equal f1p_kmpc_plan_dev bit for bit (f1p_kmpc_gen_controls_dev).
+ * With the test on, the entry points above return an error and launch nothing when no grid is loaded (F1P_ESTATE), when an
+ * oriented footprint is installed (f1p_set_footprint with n_discs > 0: this is a point / disc test, use f1p_inflate_grid;
+ * F1P_ESTATE) or when f1p_kmpc_set_groups(> 0) is in force (F1P_ESTATE).  n_sub outside [1, 16]: F1P_EINVAL, nothing changes.
+ * Not covered: f1p_kmpc_qp_*, f1p_stmpc_* (their kinematic branch included). */
+int f1p_kmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub);
 /* The reference extraction's heading fix-up (calc_ref_trajectory_kinematic, kinematic_mpc.py:198-203: course headings more than
  * 4.5 rad from the vehicle's are folded by abs(. -+ 2 pi), IN PLACE and persistently on the caller's array).  on = 1 (default):
  * applied per ego to the gathered values, the course array is never modified (batches of egos with different headings).
