@@ -218,6 +218,7 @@ int launch_pure_pursuit(f1p_ctx* ctx, const double* d_poses, int E, double looka
 int launch_pack_grid(f1p_ctx* ctx, const uint8_t* d_img, int w, int h, int occupied_below);
 int launch_grid_edt(f1p_ctx* ctx, int cap, uint32_t thr2, float* d_dist_img, uint32_t* d_d2, uint32_t* d_bits_out, const uint32_t* src = nullptr);
 int ensure_clear_map(f1p_ctx* ctx, double dist_cells);
+int launch_grid_occupied(f1p_ctx* ctx, const double* d_pts, int E, uint8_t* d_out);
 
 enum LatticeMode { LATTICE_FULL = 0, LATTICE_EVAL = 1, LATTICE_EMIT = 2 };
 int launch_lattice(f1p_ctx* ctx, int mode, const double* d_poses, const double* d_goals, const double* d_prev_theta,

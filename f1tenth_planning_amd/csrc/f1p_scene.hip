@@ -190,6 +190,48 @@ int f1p_set_footprint(f1p_ctx* ctx, int32_t n_discs, const double* offsets, doub
     return F1P_OK;
 }
 
+// test hooks (read-only): the packed maps cell by cell, and the point test on the active bitmap
+int f1p_grid_debug_read(f1p_ctx* ctx, int32_t which, uint8_t* cells, double* clear_dist_cells, int32_t* padding_all_set) {
+    F1P_ENTER(ctx);
+    if (which < 0 || which > 2) return set_error(ctx, F1P_EINVAL, "which must be 0 (uploaded), 1 (active) or 2 (clearance)");
+    if (!cells) return set_error(ctx, F1P_EINVAL, "cells is NULL");
+    if (!ctx->has_grid) return set_error(ctx, F1P_ESTATE, "occupancy grid not set: call f1p_set_grid first");
+    if (which == 2 && (!ctx->d_bits_clear || ctx->clear_dist == 0.0))
+        return set_error(ctx, F1P_ESTATE, "no clearance map of the active bitmap: none was built yet, or the bitmap changed since (stale)");
+    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int w = ctx->gw, h = ctx->gh, ww = ctx->gwwords;
+    const uint32_t* src = which == 0 ? ctx->d_bits0 : which == 1 ? ctx->d_bits : ctx->d_bits_clear;
+    std::vector<uint32_t> words((size_t)ww * h);
+    F1P_HIP(ctx, hipMemcpy(words.data(), src, sizeof(uint32_t) * words.size(), hipMemcpyDeviceToHost));
+    uint32_t pad_and = 0xffffffffu;
+    const uint32_t pad_mask = (w & 31) ? ~((1u << (w & 31)) - 1u) : 0u;      // the bits of a row's last word beyond column w
+    for (int gy = 0; gy < h; ++gy) {
+        const uint32_t* row = words.data() + (size_t)gy * ww;
+        uint8_t* dst = cells + (size_t)(h - 1 - gy) * w;                     // image row order: row 0 = top
+        for (int gx = 0; gx < w; ++gx) dst[gx] = (uint8_t)((row[gx >> 5] >> (gx & 31)) & 1u);
+        pad_and &= row[ww - 1] | ~pad_mask;
+    }
+    if (padding_all_set) *padding_all_set = pad_and == 0xffffffffu ? 1 : 0;
+    if (clear_dist_cells) *clear_dist_cells = ctx->d_bits_clear ? ctx->clear_dist : 0.0;
+    return F1P_OK;
+}
+
+int f1p_grid_occupied_batch(f1p_ctx* ctx, const double* pts, int32_t E, uint8_t* out) {
+    F1P_ENTER(ctx);
+    if (E < 0) return set_error(ctx, F1P_EINVAL, "E must be >= 0");
+    if (E == 0) return F1P_OK;
+    if (!pts || !out) return set_error(ctx, F1P_EINVAL, "pts or out is NULL");
+    if (!ctx->has_grid) return set_error(ctx, F1P_ESTATE, "occupancy grid not set: call f1p_set_grid first");
+    Stage s(ctx);
+    s.need(sizeof(double) * 2 * (size_t)E); s.need((size_t)E);
+    int rc = s.begin(); if (rc) return rc;
+    const double* d_pts;
+    if ((rc = s.in(pts, (size_t)2 * E, &d_pts))) return rc;
+    uint8_t* d_out = s.out(out, (size_t)E);
+    if ((rc = launch_grid_occupied(ctx, d_pts, E, d_out))) return rc;
+    return s.finish();
+}
+
 // ---------------------------------------------------------------------------------------------------
 // track set: K polylines, each ego follows the one its track id names (k_tracks.hip)
 static void drop_track_set(f1p_ctx* ctx) {

@@ -109,4 +109,22 @@ int ensure_clear_map(f1p_ctx* ctx, double dist_cells) {
     return rc;
 }
 
+// f1p_grid_occupied_batch (test hook): the collision kernels' point test, one thread per point -- cell_of, then the bit of the cell
+// (the two lines of KmpcCol::occupied, k_kmpc.hip, restated: that kernel's code stays what it was)
+__global__ __launch_bounds__(256) void k_grid_occupied(GridDev g, const double* __restrict__ pts, int E, uint8_t* __restrict__ out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    int gx, gy;
+    bool occ = true;                                                // outside the image or non-finite
+    if (cell_of(g, pts[2 * (size_t)e], pts[2 * (size_t)e + 1], gx, gy))
+        occ = (g.bits[(size_t)gy * g.wwords + (gx >> 5)] >> (gx & 31)) & 1u;
+    out[e] = occ ? 1 : 0;
+}
+
+int launch_grid_occupied(f1p_ctx* ctx, const double* d_pts, int E, uint8_t* d_out) {
+    if (E <= 0) return F1P_OK;
+    hipLaunchKernelGGL(k_grid_occupied, dim3((E + 255) / 256), dim3(256), 0, ctx->stream, grid_dev(ctx), d_pts, E, d_out);
+    return check_hip(ctx, hipGetLastError(), "k_grid_occupied launch");
+}
+
 }  // namespace f1p

@@ -297,6 +297,22 @@ class Context:
         off = _f64(list(offsets)).reshape(-1)
         self._check(self.lib.f1p_set_footprint(self.h, int(off.shape[0]), _ptr(off) if off.shape[0] else None, float(radius)))
 
+    def grid_debug_read(self, which):
+        """test hook (f1p_grid_debug_read): one of the packed maps cell by cell -- which = 0 the grid as uploaded, 1 the active bitmap,
+        2 the clearance map -> (cells bool [h, w] in the image's row order, padding_all_set bool, clear_dist_cells float)"""
+        cells = np.empty(self._grid_shape if self.has_grid else (1, 1), dtype=np.uint8)    # (without a grid the call is rejected)
+        dist = C.c_double(); pad = C.c_int32()
+        self._check(self.lib.f1p_grid_debug_read(self.h, int(which), _ptr(cells), C.byref(dist), C.byref(pad)))
+        return cells.astype(bool), bool(pad.value), dist.value
+
+    def grid_occupied(self, pts):
+        """test hook (f1p_grid_occupied_batch): the collision tests' point rule on the active bitmap, pts [E, 2] metres -> bool [E]
+        (occupied, outside the image or not finite)"""
+        pts = _f64(pts, (-1, 2)); E = pts.shape[0]
+        out = np.empty(E, dtype=np.uint8)
+        self._check(self.lib.f1p_grid_occupied_batch(self.h, _ptr(pts), E, _ptr(out)))
+        return out.astype(bool)
+
     # ---- leaf kernels ----------------------------------------------------------------------------------
     def nearest_point(self, pts):
         pts = _f64(pts, (-1, 2)); E = pts.shape[0]

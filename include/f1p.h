@@ -216,6 +216,20 @@ int f1p_inflate_grid(f1p_ctx* ctx, double radius);
  * point-footprint plans, at every batch size, with or without a clearance map); outputs are bit-identical to the all-fp64 kernel. */
 int f1p_set_footprint(f1p_ctx* ctx, int32_t n_discs, const double* offsets, double radius);
 
+/* TEST HOOK, read-only: one of the context's three bit-packed maps, unpacked on the host.  which = 0: the grid as uploaded
+ * (f1p_set_grid), 1: the ACTIVE bitmap every collision test reads (the upload dilated by f1p_inflate_grid + f1p_set_footprint),
+ * 2: the clearance map of the active bitmap the f32 filters use (built by the plans that want one).  cells: u8 [h][w] in the
+ * image's row order (row 0 = top), 1 = bit set.  padding_all_set (nullable): 1 when every bit of the packed rows beyond column w
+ * is set (the packing rule: beyond the right edge is occupied; also 1 when w is a multiple of 32), else 0.  clear_dist_cells
+ * (nullable): the centre distance [cells] the current clearance map was built for, 0 when there is none or it is stale.
+ * F1P_ESTATE without a grid, and for which = 2 while the clearance map is absent or stale; F1P_EINVAL for another `which` or a
+ * NULL cells.  Synchronises the stream; changes nothing. */
+int f1p_grid_debug_read(f1p_ctx* ctx, int32_t which, uint8_t* cells, double* clear_dist_cells, int32_t* padding_all_set);
+/* TEST HOOK, read-only: the point test of the collision checks, one thread per point on the ACTIVE bitmap.  pts [E][2] (x, y) in
+ * metres -> out [E] u8: 1 when the point's cell (f1p_set_grid's rule) is occupied, lies outside the image or a coordinate is not
+ * finite, else 0.  E = 0 is a no-op. */
+int f1p_grid_occupied_batch(f1p_ctx* ctx, const double* pts, int32_t E, uint8_t* out);
+
 /* ------------------------------------------------------------------------------------------------
  * Leaf kernels of utils/utils.py, batched over E query points against the ctx waypoints.
  * ---------------------------------------------------------------------------------------------- */

@@ -20,6 +20,8 @@ def test_header_and_prototypes_agree():
     syms = _declared_symbols()
     assert len(syms) >= 30
     assert sorted(_abi.PROTOTYPES) == syms
+    for name, n_args in (("f1p_grid_debug_read", 5), ("f1p_grid_occupied_batch", 4)):      # the read-only test hooks of the occupancy maps
+        assert name in syms and len(_abi.PROTOTYPES[name][1]) == n_args
 
 
 def test_library_exports_every_declared_symbol():
