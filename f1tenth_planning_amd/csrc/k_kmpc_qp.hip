@@ -5,7 +5,7 @@
 //      NOT shifted -- through kmpc_step<false>, the step of k_kmpc_predict; get_kinematic_model_matrix(v_t, phi_t, 0) (:245-278)
 //   2. condensing: x = S u + s (s: the free response of the linear model, S: one column per input), so the objective of :324-331 becomes
 //      1/2 u'Hu + g'u + c over u = vec(uk) = (a_0, d_0, a_1, d_1, ...), n = 2T
-//   3. the interior point of qp_ipm.h on  G u <= h  with the bounds of :379-389:
+//   3. the interior point of qp_ipm.h (with its refinement step) on  G u <= h  with the bounds of :379-389:
 //        a upper / lower, delta upper / lower (unit rows), rate upper / lower (first differences of delta),
 //        v_1..T upper / lower (DTK x prefix sums of a; v_0 is x0's speed: feasible iff MIN_SPEED <= v0 <= MAX_SPEED)
 //      G is never formed: G'DG in the Newton matrix is O(n^2) from suffix sums.
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
     const double gv[1] = {g};
     double u[1], lam[4];
     int it_done;
-    qp_ipm<G, 1, 4>(QpIpmLds{L.H, L.M, L.U, L.Y}, n, i, gv, h, valid, 8.0 * T - 2.0, max_iter, tol, done, st, it_done, u, lam, gmul, gtmul,
+    qp_ipm<G, 1, 4, true>(QpIpmLds{L.H, L.M, L.U, L.Y}, n, i, gv, h, valid, 8.0 * T - 2.0, max_iter, tol, done, st, it_done, u, lam, gmul, gtmul,
                     newton_rows);
 
     // ---- outputs --------------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,10 @@
 // One ego's  min 1/2 u'Hu + g'u  s.t.  G u <= h  over n inputs, solved by a group of G lanes with a primal-dual interior-point method
 // (Mehrotra predictor-corrector).  Lane l owns inputs P l .. P l + P - 1 (their rows of H and of the Newton matrix) and R inequality
 // rows; a row with valid[r] == false is absent.  Stop: |r_d| <= tol (1 + |g|), |r_p| <= tol (1 + |h|) and s'lambda <= tol (max-norms),
-// or max_iter (status 2: last iterate).  An ego whose Newton matrix stops being numerically positive definite before that (lambda / s
+// or max_iter (status 2: last iterate).  With Refine an ego that meets the rule takes ONE more step before it stops (not counted in
+// it_done, not subject to max_iter): at a degenerate row slack and multiplier both go like the square root of the gap, so the rule
+// alone leaves u up to ~sqrt(tol / curvature) from the optimum; the step is kept only if the iterate still meets the rule with a
+// smaller gap, else the iterate that met it is returned.  An ego whose Newton matrix stops being numerically positive definite before that (lambda / s
 // ~ 1e16 on its active rows) stops there, status 0 when its residuals are below tol and s'lambda <= tol (1 + |objective|), else 2.
 //
 // The model supplies G through three hooks, called by every lane of the workgroup:
@@ -57,7 +60,7 @@ struct QpIpmLds {
 
 // in: g[P] (this lane's entries), h[R], valid[R], m_rows (the number of valid rows of the ego), done (the ego takes no step), st;
 // out: u[P], lam[R], st (0 / 2 unless it came in non-zero), it_done; U holds u on return
-template <int G, int P, int R, class GMul, class GtMul, class NewtonRows>
+template <int G, int P, int R, bool Refine = false, class GMul, class GtMul, class NewtonRows>
 __device__ __forceinline__ void qp_ipm(const QpIpmLds& L, int n, int lane, const double (&g)[P], const double (&h)[R], const bool (&valid)[R],
                                        double m_rows, int max_iter, double tol, bool done, int& st, int& it_done, double (&u)[P],
                                        double (&lam)[R], GMul&& gmul, GtMul&& gtmul, NewtonRows&& newton_rows) {
@@ -72,6 +75,8 @@ __device__ __forceinline__ void qp_ipm(const QpIpmLds& L, int n, int lane, const
 #pragma unroll
     for (int p = 0; p < P; ++p) u[p] = 0.0;
     it_done = 0;
+    bool conv = false;                                   // Refine: the rule is met, the refinement step is under way
+    double u_c[P], s_c[R], lam_c[R], gap_c = 0.0;        // ... and the iterate that met it
 
     // publish x in vec[] (barriers on both sides)
     auto publish = [&](double* vec, const double (&x)[P]) {
@@ -115,8 +120,26 @@ __device__ __forceinline__ void qp_ipm(const QpIpmLds& L, int n, int lane, const
         const bool res_ok = rdn <= tol && rpn <= tol;
         const bool gap_rel_ok = res_ok && gap <= tol * (1.0 + fabs(f));
         if (!done) {
-            if (res_ok && gap <= tol) { done = true; st = 0; it_done = it; }
-            else if (it >= max_iter) { done = true; st = 2; it_done = it; }
+            if (Refine && conv) {                        // after the refinement step: keep it, or go back
+                if (!(res_ok && gap <= gap_c)) {
+#pragma unroll
+                    for (int p = 0; p < P; ++p) u[p] = u_c[p];
+#pragma unroll
+                    for (int r = 0; r < R; ++r) { s[r] = s_c[r]; lam[r] = lam_c[r]; }
+                }
+                done = true;
+            } else if (res_ok && gap <= tol) {
+                st = 0; it_done = it;
+                if (Refine) {
+                    conv = true; gap_c = gap;
+#pragma unroll
+                    for (int p = 0; p < P; ++p) u_c[p] = u[p];
+#pragma unroll
+                    for (int r = 0; r < R; ++r) { s_c[r] = s[r]; lam_c[r] = lam[r]; }
+                } else {
+                    done = true;
+                }
+            } else if (it >= max_iter) { done = true; st = 2; it_done = it; }
         }
         if (!__syncthreads_or(!done)) break;
 
@@ -149,7 +172,10 @@ __device__ __forceinline__ void qp_ipm(const QpIpmLds& L, int n, int lane, const
             }
         }
         __syncthreads();
-        if (broke && !done) { done = true; st = gap_rel_ok ? 0 : 2; it_done = it; }     // (broke is uniform over the group)
+        if (broke && !done) {                            // (broke is uniform over the group)
+            done = true;
+            if (!conv) { st = gap_rel_ok ? 0 : 2; it_done = it; }                      // (conv: no refinement step; the iterate stands)
+        }
 
         // one Newton solve for the complementarity right-hand side rc
         auto newton = [&](const double (&rc)[R], double (&du)[P], double (&ds)[R], double (&dl)[R]) {

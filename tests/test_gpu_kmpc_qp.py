@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import kmpc_qp_ref as Q
+import qp_cases as QC
 from f1tenth_planning_amd import _abi, sim, synth
 from f1tenth_planning_amd.runtime import Context
 from test_kmpc_qp_host import g16_cases
@@ -164,15 +165,21 @@ def test_bad_inputs(ctx):
 
 
 # ---- 5. the plan chain ---------------------------------------------------------------------------------------------------------------
-def test_plan_chain_equals_the_host_chain(ctx):
-    T, E = 8, 64
+def _chain_cfg(case):
+    """None: the defaults at T = 8; (seed, T): an off-default config of tests/qp_cases.py (its own dt, weights and bounds)"""
+    return _cfg(8) if case is None else QC.kmpc_case(*case)[0]
+
+
+@pytest.mark.parametrize("case", [None, (401, 3), (402, 12)], ids=["default-T8", "offdefault-T3", "offdefault-T12"])
+def test_plan_chain_equals_the_host_chain(ctx, case):
+    cfg = _chain_cfg(case)
+    T, E = cfg.horizon, 64
     cl = synth.make_centerline(seed=4)
     rl = np.ascontiguousarray(cl[:, [1, 2, 5, 3, 4]])
     ctx.set_waypoints(rl)
     rng = np.random.default_rng(9)
     k0 = rng.integers(0, len(rl) - 200, E)
-    v = rng.uniform(0.5, 5.5, E)
-    cfg = _cfg(T)
+    v = np.clip(rng.uniform(0.5, 5.5, E), cfg.min_speed, cfg.max_speed)           # (no change at the defaults' [0, 6])
     ctx.kmpc_qp_warm_reset()
     oa = od = None
     first = None
@@ -180,7 +187,7 @@ def test_plan_chain_equals_the_host_chain(ctx):
         k = k0 + 5 * step
         x0 = np.column_stack([rl[k, 0] + 0.1, rl[k, 1] - 0.05, v, rl[k, 3] + 0.05])
         got = ctx.kmpc_qp_plan(x0, cfg, dl=0.03)
-        want = ctx.kmpc_qp(x0, ctx.kmpc_ref(x0, T, 0.1, 0.03), cfg, oa_prev=oa, od_prev=od)
+        want = ctx.kmpc_qp(x0, ctx.kmpc_ref(x0, T, cfg.dt, 0.03), cfg, oa_prev=oa, od_prev=od)
         for key in ("steer", "speed", "status", "u", "obj"):
             assert np.array_equal(got[key], want[key]), (step, key)
         oa, od = want["u"][:, :, 0].copy(), want["u"][:, :, 1].copy()

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import kmpc_qp_ref as KQ
+import qp_cases as QC
 import stmpc_qp_ref as SQ
 from f1tenth_planning_amd import _abi, synth
 from f1tenth_planning_amd.runtime import Context
@@ -219,19 +220,31 @@ def _host_chain_step(ctx, states, warms, p, pk, gpu):
     return steer, speed, br, np.array(degs)
 
 
-def test_plan_chain_equals_the_host_chain(ctx):
-    T, TK, E = 10, 8, 8
+def _chain_case(off_default):
+    """(dcfg, kcfg, p, pk): the defaults at T = 10, TK = 8, or an off-default pair of tests/qp_cases.py at T = 12, TK = 5 (TK <= T) with
+    each branch's own time step and weights; one STMPCPlanner config holds one set of bounds and one wheelbase for both branches"""
+    if not off_default:
+        return _dcfg(10), _kcfg(8), SQ.default_params(10), SQ.kin_params(8)
+    ds, ks = QC.stmpc_spec(403, 12), QC.kmpc_spec(404, 5)
+    shared = dict(WB=0.31, MAX_STEER=0.45, MAX_SPEED=6.5, MIN_SPEED=0.0, MAX_ACCEL=4.0)
+    ds.update(shared, DT=0.025)                          # (DT = 0.05 makes the reference's Euler step of the slip angle unstable: DESIGN.md 5c)
+    ks.update(shared, DTK=0.05)
+    return QC.stmpc_cfg(ds), QC.kmpc_cfg(ks), QC.stmpc_params(ds), QC.kmpc_params(ks)
+
+
+@pytest.mark.parametrize("off_default", [False, True], ids=["default-T10-TK8", "offdefault-T12-TK5"])
+def test_plan_chain_equals_the_host_chain(ctx, off_default):
+    dcfg, kcfg, p, pk = _chain_case(off_default)
+    T, TK, E = p["T"], pk["T"], 8
     rl = _chain_track(ctx)
     n = len(rl)
     k0 = np.array([10, 60, 110, 160, n // 2 + 10, n // 2 + 60, n // 2 + 110, n // 2 + 160])
     v = np.array([1.8, 1.9, 2.6, 3.5, 2.3, 2.15, 1.5, 3.0])
     states = np.column_stack([rl[k0, 0] + 0.05, rl[k0, 1] - 0.05, np.full(E, 0.02), v, rl[k0, 3] + 0.03, np.zeros(E), np.zeros(E)])
-    p, pk = SQ.default_params(T), SQ.kin_params(TK)
-    dcfg, kcfg = _dcfg(T), _kcfg(TK)
     ctx.stmpc_qp_warm_reset()
     warms = [None] * E
     branches = []
-    for step in range(24):
+    for step in range(10 if off_default else 24):            # (the off-default chain has crossed V_KS both ways by then)
         got = ctx.stmpc_qp_plan(states, dcfg, kcfg, v_ks=2.0, dl=0.03, dlk=0.03)
         assert (got["status"] == 0).all(), (step, got["status"])
         steer, speed, br, deg = _host_chain_step(ctx, states, warms, p, pk, got)
