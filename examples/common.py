@@ -76,3 +76,51 @@ def run(args, rl, plan, speed_scale=1.0, report_every=500, avoid_heading_wrap=Fa
     print(f"{args.envs} vehicle(s), {args.steps} steps: travelled {travelled.mean():.1f} m on average, "
           f"max cross-track error {max_cte.max():.3f} m, {1e3 * t_plan / args.steps:.3f} ms per batched plan() call")
     return max_cte, travelled
+
+
+def obstacle_runs(args, rl, waypoints, cfg, make_planner, batch_states, set_substeps, resolution=0.05, cells=900, inflate=0.15):
+    """the synthetic grid of the track + parked obstacles; one closed loop per setting of the occupancy test (mpc_config.COLLISION), the same
+    start poses.  make_planner(waypoints, cfg) -> an MPC planner with set_map / plan / plan_batch; batch_states(env) -> plan_batch's states;
+    set_substeps(cfg, n) sets the tested points per step"""
+    from f1tenth_planning_amd import sim, synth
+    if args.solver == "qp":
+        raise SystemExit("--obstacles needs the shooting solver (the QP has no rollouts to test)")
+    img, origin = synth.make_grid(rl[:, :2], size=(cells, cells), resolution=resolution)
+    length = float(np.hypot(np.diff(rl[:, 0]), np.diff(rl[:, 1])).sum())
+    img, centres = synth.stamp_obstacles(img, origin, resolution, rl, spacing=length / args.obstacles, radius=0.30)
+    occupied = img[::-1] < 128                                          # [gy][gx], the uninflated map: what counts as a hit
+    print(f"{len(centres)} obstacles on {length:.1f} m of track, {args.envs} vehicle(s), {args.steps} steps")
+    poses = start_poses(args, rl, avoid_heading_wrap=True)
+    for p in poses:                                                     # nobody starts inside or right behind an obstacle
+        k = int(np.argmin(np.hypot(rl[:, 0] - p[0], rl[:, 1] - p[1])))
+        while np.hypot(centres[:, 0] - rl[k, 0], centres[:, 1] - rl[k, 1]).min() < 1.5:
+            k = (k + 5) % (len(rl) - 1)
+            p[:] = (rl[k, 0], rl[k, 1], rl[k, 3])
+    hits = {}
+    for on in (False, True):
+        cfg.COLLISION = on
+        set_substeps(cfg, args.substeps)
+        planner = make_planner([w.copy() for w in waypoints], cfg)
+        planner.set_map(img, resolution, (origin[0], origin[1], 0.0), inflate=inflate)
+        env = sim.make("f110_gym:f110-v0", num_agents=args.envs)
+        obs, _, done, _ = env.reset(poses)
+        n_hit = n_stop = 0
+        for it in range(args.steps):
+            if args.envs == 1:
+                import warnings
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore", RuntimeWarning)      # (an all-blocked plan warns and returns (0, 0): the vehicle brakes)
+                    act = np.array([planner.plan(env.sim.agents[0].state)])
+            else:
+                out = planner.plan_batch(batch_states(env))
+                act = np.column_stack([out["steer"], out["speed"]])
+                n_stop += int((out["best_idx"] < 0).sum())
+            obs, dt, done, _ = env.step(act)
+            gx = np.floor((np.asarray(obs["poses_x"]) - origin[0]) / resolution).astype(int)
+            gy = np.floor((np.asarray(obs["poses_y"]) - origin[1]) / resolution).astype(int)
+            inside = (gx >= 0) & (gx < cells) & (gy >= 0) & (gy < cells)
+            n_hit += int((~inside).sum() + occupied[gy[inside], gx[inside]].sum())
+        hits[on] = n_hit
+        print(f"occupancy test {'on ' if on else 'off'}: {n_hit} of {args.steps * args.envs} vehicle-steps ended in an occupied cell"
+              + (f" ({n_stop} plans had every rollout blocked)" if on and args.envs > 1 else ""))
+    return hits

@@ -1,5 +1,8 @@
 """Single-track MPC (random shooting, or with --solver qp the reference's linearised QPs; kinematic model below V_KS, dynamic model above) in closed loop
-(loop shape of the reference's examples/control/dynamic_mpc.py)."""
+(loop shape of the reference's examples/control/dynamic_mpc.py).
+
+--obstacles N parks N obstacles on the line of the synthetic track and drives the loop twice, without and with the occupancy test on the
+rollouts (mpc_config.COLLISION), counting the vehicle-steps that ended in an occupied cell."""
 import os
 import sys
 
@@ -15,6 +18,8 @@ def main():
     ap = common.parser(__doc__, steps=600)
     ap.add_argument("--solver", choices=["shooting", "qp"], default="shooting")
     ap.add_argument("--tracks", type=int, default=0, help="N agents on N lanes offset sideways from the centreline, one track set (--solver qp)")
+    ap.add_argument("--obstacles", type=int, default=0, help="park N obstacles (discs of 0.3 m) on the line and compare the loop with the occupancy test off / on")
+    ap.add_argument("--substeps", type=int, default=1, help="tested points per step of the dynamic model (mpc_config.COLLISION_SUBSTEPS; the kinematic branch tests twice as many)")
     args = ap.parse_args()
     lanes = ids = None
     if args.tracks > 0:
@@ -24,6 +29,15 @@ def main():
     if args.envs != 1 and args.tracks == 0 and args.solver != "shooting":
         raise SystemExit("--envs N drives N vehicles with the shooting solver's plan_batch; with --solver qp use --tracks N")
     rl = common.raceline(args, centerline=True)
+    if args.obstacles > 0:
+        if args.solver == "qp" or args.tracks > 0:
+            raise SystemExit("--obstacles needs the shooting solver on the raceline (the QP has no rollouts to test)")
+
+        def substeps(c, n):
+            c.COLLISION_SUBSTEPS, c.COLLISION_SUBSTEPS_K = n, min(2 * n, 16)
+
+        return common.obstacle_runs(args, rl, [rl[:, 0], rl[:, 1], rl[:, 3], rl[:, 2]], mpc_config(),
+                                    lambda wp, c: STMPCPlanner(waypoints=wp, config=c), lambda env: env.state, substeps)
     planner = STMPCPlanner(waypoints=[rl[:, 0], rl[:, 1], rl[:, 3], rl[:, 2]], config=mpc_config(SOLVER=args.solver))
     if args.tracks > 0:
         normal = rl[:, 3] + np.pi / 2

@@ -9,15 +9,19 @@ csrc/k_stmpc.hip) instead of the reference's cvxpy/OSQP QP (third-party, out of 
 mpc_config.SOLVER = "qp" selects the reference's own solver instead: the linearised QPs of :575-833, solved exactly (to QP_TOL) by
 batched fp64 interior-point kernels -- csrc/k_stmpc_qp.hip for the dynamic branch, csrc/k_kmpc_qp.hip for the kinematic one --
 warm-started like the reference from the previous solution (unshifted, with its reset rules :1005, :1052).
+
+mpc_config.COLLISION = True (shooting only) tests every rollout of both branches against the occupancy grid installed with set_map /
+load_map: a rollout that touches an occupied cell cannot win (f1p_stmpc_set_collision).
 """
 import os
+import warnings
 from dataclasses import dataclass, field
 
 import numpy as np
 
 from ... import _abi
 from ...runtime import Context
-from ..kinematic_mpc.kinematic_mpc import State  # noqa: F401  (same 7-field dataclass, :89-98)
+from ..kinematic_mpc.kinematic_mpc import State, _OccupancyMap  # noqa: F401  (same 7-field dataclass, :89-98; set_map / load_map)
 
 
 @dataclass
@@ -61,6 +65,10 @@ class mpc_config:
     SOLVER: str = "shooting"
     QP_TOL: float = 1e-10  # interior point: scaled KKT residuals and duality gap below this
     QP_MAX_ITER: int = 50  # interior-point iterations at most (status 2 beyond: the last iterate, like cvxpy's OPTIMAL_INACCURATE)
+    # occupancy test on the shooting solver's rollouts (set_map / load_map): a rollout through an occupied cell cannot win
+    COLLISION: bool = False
+    COLLISION_SUBSTEPS: int = 1    # tested points per step of the dynamic model, 1 .. 16 (a step covers up to MAX_SPEED * DT = 0.15 m)
+    COLLISION_SUBSTEPS_K: int = 2  # ... per step of the kinematic branch, 1 .. 16 (up to V_KS * DTK + acceleration)
 
 
 def _diag(m):
@@ -83,9 +91,15 @@ def _check_solver(c: mpc_config):
                 raise ValueError(f"SOLVER='qp' takes diagonal {n}x{n} weights only; mpc_config.{name} is not")
         if c.TK > c.T:
             raise ValueError("SOLVER='qp' needs TK <= T (the reference's kinematic branch would linearise about a cut-short prediction)")
+    if c.COLLISION:
+        if c.SOLVER == "qp":
+            raise ValueError("mpc_config.COLLISION tests the shooting solver's rollouts; SOLVER='qp' has none")
+        for name in ("COLLISION_SUBSTEPS", "COLLISION_SUBSTEPS_K"):
+            if not 1 <= int(getattr(c, name)) <= 16:
+                raise ValueError(f"mpc_config.{name} must be in [1, 16], not {getattr(c, name)!r}")
 
 
-class STMPCPlanner:
+class STMPCPlanner(_OccupancyMap):
     """
     Single-track MPC controller (random shooting on the GPU).  All poses are in the map frame.
 
@@ -109,12 +123,31 @@ class STMPCPlanner:
         self._ctx = None
         self._calls = 0
         self._batch_calls = 0
+        self._map = None                   # (img u8, resolution, (ox, oy), occupied_below) of set_map
+        self._inflate = 0.0
         _check_solver(config)
+
+    def _check_collision(self):
+        """ValueError before anything touches the GPU: the checks of _check_solver, and COLLISION without a map"""
+        _check_solver(self.config)
+        if self.config.COLLISION and self._map is None:
+            raise ValueError("mpc_config.COLLISION needs an occupancy grid: call set_map / load_map first")
 
     def _context(self):
         if self._ctx is None:
             self._ctx = Context(self._device if self._device is not None else int(os.environ.get("LOCAL_RANK", "0")))
+            if self._map is not None:
+                self._install_map(self._ctx)
         return self._ctx
+
+    def _collision_switch(self, ctx):
+        """the planner's context follows mpc_config: the stmpc switch (plan_batch, plan()'s dynamic branch) and, for plan()'s kinematic
+        branch through ctx.kmpc_shoot, the kmpc switch with COLLISION_SUBSTEPS_K"""
+        c = self.config
+        if c.SOLVER != "qp":
+            on = bool(c.COLLISION)
+            ctx.stmpc_set_collision(on, int(c.COLLISION_SUBSTEPS) if on else 1, int(c.COLLISION_SUBSTEPS_K) if on else 2)
+            ctx.kmpc_set_collision(on, int(c.COLLISION_SUBSTEPS_K) if on else 1)
 
     def _bind(self, waypoints):
         if waypoints is not None:
@@ -179,6 +212,8 @@ class STMPCPlanner:
         winner shifted by one step; an ego that crosses V_KS starts its new branch from zeros.  An ego's result depends on that ego's state
         and history alone, not on the batch around it.  plan() keeps its host-side sampler and has no warm start; a one-ego plan_batch is
         the warm-started single-vehicle call.  `tracks` needs SOLVER='qp' (below).
+        mpc_config.COLLISION: every rollout of both branches is tested against the map; an ego whose rollouts are all blocked has best_idx
+        -1, best_cost +inf, steer 0, speed 0, a zero sequence (up to its branch's horizon) and starts its next plan from a zero warm start.
         SOLVER == "qp": states [E, 7] -> dict(steer, speed, status, branch (1 dynamic, 0 kinematic), obj[, u [E, max(T, TK), 2] =
         (oa, odelta_v), NaN past the branch's horizon]) -- per-ego status (0 solved, 1 infeasible, 2 not converged, 3 non-finite input
         or model data), never raised.
@@ -188,11 +223,12 @@ class STMPCPlanner:
         that ego status 4 (F1P_ST_BAD_TRACK), branch -1 and NaN outputs, and leaves its warm start as it was.  The shooting solver on
         tracks is a Context-level chain: ctx.stmpc_ref_tracks -> ctx.stmpc_shoot, or its rows [0, 1, 3, 4] with (TK, DTK, dlk) ->
         ctx.kmpc_shoot for the kinematic branch."""
-        _check_solver(self.config)
+        self._check_collision()
         if self.config.SOLVER != "qp":
             if tracks is not None:
                 raise ValueError("plan_batch with tracks needs SOLVER='qp'")
             ctx = self._bind(waypoints)
+            self._collision_switch(ctx)
             return self._shoot(ctx, np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 7), want_u=want_u)
         if tracks is not None:
             cols = self._track_columns(tracks, track_ids)
@@ -231,9 +267,12 @@ class STMPCPlanner:
             self._ctx.stmpc_warm_reset()
 
     def plan(self, states, waypoints=None):
-        """states: [x, y, delta, v, yaw, yawrate, beta].  Returns (steering_angle, speed)."""
-        _check_solver(self.config)
+        """states: [x, y, delta, v, yaw, yawrate, beta].  Returns (steering_angle, speed).  mpc_config.COLLISION: the rollouts of the
+        branch taken are tested against the map; when every one of them is blocked the call warns and returns (0.0, 0.0) -- a soft failure
+        like KMPCPlanner's -- and oa / odelta_v are the zero sequence."""
+        self._check_collision()
         ctx = self._bind(waypoints)
+        self._collision_switch(ctx)
         c = self.config
         st = np.asarray(states, dtype=np.float64)
         if c.SOLVER == "qp":
@@ -258,6 +297,9 @@ class STMPCPlanner:
             ref = ctx.stmpc_ref(np.array([[st[0], st[1], st[3], st[4]]]), c.T, c.DT, c.dl)
             out = ctx.stmpc_shoot(st[None, :7], ref, self._sample(c.T, c.N_ROLLOUTS, c.SIGMA_STEER_V, c.SIGMA_ACCEL, c.MAX_STEER_V, c.MAX_ACCEL), cfg)
             self.odelta_v, self.oa = out["best_seq"][0, :, 0], out["best_seq"][0, :, 1]
+        if int(out["best_idx"][0]) < 0:        # every rollout runs into an occupied cell
+            warnings.warn("dynamic MPC: every rollout is blocked by the occupancy grid; returning (0.0, 0.0)", RuntimeWarning, stacklevel=2)
+            return 0.0, 0.0
         return float(out["steer"][0]), float(out["speed"][0])
 
     # the reference's helper methods, on the GPU ---------------------------------------------------------------------

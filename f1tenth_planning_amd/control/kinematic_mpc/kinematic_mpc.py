@@ -111,33 +111,11 @@ def _cfg_struct(c: mpc_config, n_rollouts=None):
                          q=np.diag(c.Qk), qf=np.diag(c.Qfk), r=np.diag(c.Rk), rd=np.diag(c.Rdk))
 
 
-class KMPCPlanner:
-    """
-    Kinematic MPC controller (random shooting on the GPU).  All poses are in the map frame.
-
-    Args:
-        waypoints: [x, y, yaw, v] as a list of four 1-D arrays or an array [4, N]
-            (examples/control/kinematic_mpc.py:44-45)
-        config (mpc_config)
-    """
-
-    def __init__(self, waypoints=None, config=mpc_config(),
-                 params=np.array([3.74, 0.15875, 0.17145, 0.074, 4.718, 5.4562, 0.04712, 1.0489]), debug=False, device=None):
-        self.waypoints = waypoints
-        self.config = config
-        self.vehicle_params = params
-        self.odelta_v = None
-        self.oa = None
-        self.odelta = None
-        self.init_flag = 0
-        self.debug = debug
-        self._device = device
-        self._ctx = None
-        self._calls = 0
-        self._trk_qp_warm = None           # the QP warm start of the track-set path (plan_batch(tracks=...)): u [E, T, 2] fp64
-        self._map = None                   # (img u8, resolution, (ox, oy), occupied_below) of set_map
-        self._inflate = 0.0
-        _check_solver(config)
+class _OccupancyMap:
+    """set_map / load_map of the MPC planners (KMPCPlanner, STMPCPlanner): the map is kept on the host and installed on the planner's
+    context when there is one.  The class keeps `_map`, `_inflate` and `_ctx`."""
+    _map = None                            # (img u8, resolution, (ox, oy), occupied_below) of set_map
+    _inflate = 0.0
 
     def set_map(self, image, resolution, origin, occupied_thresh=0.65, negate=0, inflate=0.0):
         """Occupancy image in the ROS map_server layout, with LatticePlanner.set_map's meaning: u8 [h, w], row 0 at the top, `origin` =
@@ -169,6 +147,35 @@ class KMPCPlanner:
         ctx.set_grid(*self._map)
         if self._inflate > 0.0:
             ctx.inflate_grid(self._inflate)
+
+
+class KMPCPlanner(_OccupancyMap):
+    """
+    Kinematic MPC controller (random shooting on the GPU).  All poses are in the map frame.
+
+    Args:
+        waypoints: [x, y, yaw, v] as a list of four 1-D arrays or an array [4, N]
+            (examples/control/kinematic_mpc.py:44-45)
+        config (mpc_config)
+    """
+
+    def __init__(self, waypoints=None, config=mpc_config(),
+                 params=np.array([3.74, 0.15875, 0.17145, 0.074, 4.718, 5.4562, 0.04712, 1.0489]), debug=False, device=None):
+        self.waypoints = waypoints
+        self.config = config
+        self.vehicle_params = params
+        self.odelta_v = None
+        self.oa = None
+        self.odelta = None
+        self.init_flag = 0
+        self.debug = debug
+        self._device = device
+        self._ctx = None
+        self._calls = 0
+        self._trk_qp_warm = None           # the QP warm start of the track-set path (plan_batch(tracks=...)): u [E, T, 2] fp64
+        self._map = None                   # (img u8, resolution, (ox, oy), occupied_below) of set_map
+        self._inflate = 0.0
+        _check_solver(config)
 
     def _check_collision(self):
         """ValueError before anything touches the GPU: COLLISION without a map (the other COLLISION checks: _check_solver)"""

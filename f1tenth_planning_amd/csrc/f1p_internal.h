@@ -75,6 +75,9 @@ struct f1p_ctx {
 
     // dynamic single-track shooting: f32 filter + fp64 refinement (default) or plain fp64 (f1p_stmpc_set_mode); test hooks
     bool stmpc_mixed = true;
+    bool stmpc_collision = false;      // f1p_stmpc_set_collision: rollouts of f1p_stmpc_plan_* / f1p_stmpc_shoot_* are tested against d_bits
+    int stmpc_col_nsub = 1;            // ... at this many points per step of the dynamic model,
+    int stmpc_col_nsub_k = 2;          // ... and at this many per step of f1p_stmpc_plan_batch's kinematic branch
     float* d_dbg_st_cost32 = nullptr;  // [E][R] filter costs (-inf = untrusted) of the next launches, or null
     int32_t* d_dbg_st_nref = nullptr;  // [E] refined rollouts (-1 = all-fp64 fallback), or null
     char* d_st_scratch = nullptr;      // k_stmpc_filter -> refine -> decide: queue counter | per-ego counts | lists | queue | refined costs

@@ -133,11 +133,34 @@ int f1p_stmpc_set_mode(f1p_ctx* ctx, int32_t mixed, float* d_cost32, int32_t* d_
     return F1P_OK;
 }
 
+// f1p_stmpc_set_collision's preconditions, checked by every entry point that would launch the tested kernels -- before anything is launched
+// or any warm-start tag is touched.  kinematic: the call may run f1p_stmpc_plan_batch's kinematic branch (one workgroup per ego with the test)
+static int stmpc_collision_check(f1p_ctx* ctx, bool kinematic) {
+    if (!ctx->stmpc_collision) return F1P_OK;
+    if (!ctx->has_grid) return set_error(ctx, F1P_ESTATE, "stmpc collision test is on but no occupancy grid is loaded (f1p_set_grid)");
+    if (ctx->n_disc > 0)
+        return set_error(ctx, F1P_ESTATE, "stmpc collision test is a point / disc test: remove the oriented footprint (f1p_set_footprint) and use f1p_inflate_grid");
+    if (kinematic && ctx->kmpc_groups > 0) return set_error(ctx, F1P_ESTATE, "stmpc collision test runs one workgroup per ego: f1p_kmpc_set_groups(0)");
+    if (ctx->stmpc_col_nsub < 1 || ctx->stmpc_col_nsub > 16 || ctx->stmpc_col_nsub_k < 1 || ctx->stmpc_col_nsub_k > 16)
+        return set_error(ctx, F1P_EINVAL, "stmpc collision test: n_sub and n_sub_k must be in [1, 16]");
+    return F1P_OK;
+}
+
+int f1p_stmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub, int32_t n_sub_k) {
+    F1P_ENTER(ctx);
+    if (n_sub < 1 || n_sub > 16 || n_sub_k < 1 || n_sub_k > 16)
+        return set_error(ctx, F1P_EINVAL, "stmpc collision test: n_sub and n_sub_k must be in [1, 16]");
+    ctx->stmpc_collision = on != 0;
+    ctx->stmpc_col_nsub = n_sub; ctx->stmpc_col_nsub_k = n_sub_k;
+    return F1P_OK;
+}
+
 int f1p_stmpc_shoot_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const float* d_controls, int32_t E,
                         const f1p_stmpc_cfg* cfg, double* d_steer, double* d_speed, int32_t* d_best_idx,
                         double* d_best_cost, double* d_best_seq) {
     F1P_ENTER(ctx);
     int rc = validate_stmpc(ctx, cfg, E); if (rc) return rc;
+    if ((rc = stmpc_collision_check(ctx, false))) return rc;
     if (E > 0 && (!d_x0 || !d_ref || !d_controls || !d_steer || !d_speed || !d_best_idx))
         return set_error(ctx, F1P_EINVAL, "x0, ref, controls, steer, speed and best_idx are required");
     return launch_stmpc_shoot(ctx, d_x0, d_ref, d_controls, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
@@ -148,6 +171,7 @@ int f1p_stmpc_shoot_batch(f1p_ctx* ctx, const double* x0, const double* ref, con
                           double* best_seq) {
     F1P_ENTER(ctx);
     int rc = validate_stmpc(ctx, cfg, E); if (rc) return rc;
+    if ((rc = stmpc_collision_check(ctx, false))) return rc;
     if (E > 0 && (!x0 || !ref || !controls || !steer || !speed || !best_idx))
         return set_error(ctx, F1P_EINVAL, "x0, ref, controls, steer, speed and best_idx are required");
     const size_t T = cfg->horizon, R = cfg->n_rollouts, e = E;
@@ -423,6 +447,7 @@ int f1p_stmpc_plan_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, in
     F1P_ENTER(ctx);
     int rc = validate_stmpc(ctx, cfg, E); if (rc) return rc;
     if ((rc = validate_st_sampler(ctx, smp))) return rc;
+    if ((rc = stmpc_collision_check(ctx, false))) return rc;
     if (E == 0) return F1P_OK;
     if (!d_x0 || !d_ref || !d_steer || !d_speed || !d_best_idx) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and best_idx are required");
     if ((rc = ensure_st_warm_dyn(ctx, E, cfg->horizon))) return rc;
@@ -451,6 +476,7 @@ int f1p_stmpc_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_st
     int rc = validate_stmpc(ctx, dcfg, E); if (rc) return rc;
     if ((rc = validate_kmpc(ctx, kcfg, E))) return rc;
     if ((rc = validate_st_sampler(ctx, smp))) return rc;
+    if ((rc = stmpc_collision_check(ctx, true))) return rc;
     if (kcfg->n_rollouts > 8192) return set_error(ctx, F1P_EINVAL, "at most 8192 rollouts per kinematic plan");
     if (E > 0 && (!x0 || !steer || !speed || !best_idx)) return set_error(ctx, F1P_EINVAL, "x0, steer, speed and best_idx are required");
     if (!(dl > 0) || !(dlk > 0)) return set_error(ctx, F1P_EINVAL, "dl and dlk must be > 0");

@@ -11,6 +11,7 @@
 // HBM-streaming kernel of the path: 8 B of controls per rollout-step, fp64 arithmetic on them.
 #include "f1p_internal.h"
 #include "shoot_gen.h"
+#include "shoot_col.h"
 
 #ifndef F1P_K4_RING
 #define F1P_K4_RING 3                 // register buffers of the streamed filter's prefetch ring (3: two chunks in flight; 4 measured beside it)
@@ -33,27 +34,7 @@ __device__ __forceinline__ double clampd(double v, double lo, double hi) { retur
 // the grid, and `if constexpr (kmpc_has_col<Src>::value)` keeps every statement of the test out of the instantiations for a plain source,
 // whose signatures and bodies are what they were (the kernels without the test keep their instructions).
 // ---------------------------------------------------------------------------------------------------
-#define F1P_K4_NONE 0x7fffffff        // argmin index while no unblocked rollout has been seen
-struct KmpcCol {
-    GridDev g;                        // the active bitmap
-    const uint32_t* clear;            // clearance map for the f32 filter (null: the filter proves nothing, every rollout in fp64)
-    int n_sub;                        // tested points per time step, 1 .. 16
-    int force64;                      // f1p_kmpc_set_mode(0): no filter
-    __device__ __forceinline__ bool occupied(double x, double y) const {
-        int gx, gy;
-        if (!cell_of(g, x, y, gx, gy)) return true;
-        return (g.bits[(size_t)gy * g.wwords + (gx >> 5)] >> (gx & 31)) & 1u;
-    }
-    // the tested points of the step p -> q
-    __device__ __forceinline__ bool seg(double px, double py, double qx, double qy) const {
-        bool hit = false;
-        for (int j = 1; j < n_sub; ++j) {
-            const double f = (double)j / (double)n_sub;
-            hit |= occupied(px + (qx - px) * f, py + (qy - py) * f);
-        }
-        return hit | occupied(qx, qy);
-    }
-};
+// F1P_K4_NONE, KmpcCol: shoot_col.h (shared with k_stmpc.hip, f1p_stmpc_set_collision)
 // a control source with the occupancy test; `blocked`: the verdict on the rollout evaluated last (kmpc_rollout_cost / kmpc_rollout_lanes<true>)
 template <typename Base>
 struct SrcColT : Base {
@@ -319,26 +300,7 @@ __device__ __forceinline__ f1p_f2 kmpc_rollout_cost_f32x2(const Src& src, const 
 // or nearly occupied cell, a point outside the image, a NaN -- is UNSURE and decided by the fp64 refinement.
 // Cell coordinates are kept RELATIVE to the ego's cell (ibx, iby: fp64 floor), so the f32 operands stay below reach / resolution cells.
 // ---------------------------------------------------------------------------------------------------
-#define F1P_K4_CLEAR_CELLS 2.0
-#define F1P_K4_POS_ERR_REL 1.0e-4
-struct KmpcColF {
-    const uint32_t* clear;
-    int wwords, n_sub, ibx, iby;
-    float inv_nsub, bx, by, lox, hix, loy, hiy, inv_res, c0, s0;
-    // (x, y): the filter's position -- ego frame (ISO) or world axes relative to the ego
-    template <bool ISO>
-    __device__ __forceinline__ bool unsure(float x, float y) const {
-        const float rx = ISO ? c0 * x - s0 * y : x, ry = ISO ? s0 * x + c0 * y : y;
-        const float fx = floorf(bx + rx * inv_res), fy = floorf(by + ry * inv_res);
-        const bool inside = (fx >= lox) & (fx < hix) & (fy >= loy) & (fy < hiy);      // NaN -> outside
-#ifdef F1P_K4_COL_NOLOOKUP            // A/B build: the cell arithmetic without the map read (where the open-space time goes)
-        return !inside;
-#else
-        const int gx = inside ? ibx + (int)fx : 0, gy = inside ? iby + (int)fy : 0;   // (inside: 0 <= gx < w, 0 <= gy < h)
-        return !inside | (bool)((clear[(size_t)gy * wwords + (gx >> 5)] >> (gx & 31)) & 1u);
-#endif
-    }
-};
+// F1P_K4_CLEAR_CELLS, F1P_K4_POS_ERR_REL, KmpcColF: shoot_col.h (shared with k_stmpc.hip)
 
 // kmpc_rollout_cost_f32x2 step by step, every step's tested points looked up; u0 / u1: rollout r0 / r1 is UNSURE
 template <bool POLY, bool ISO, typename Src>
@@ -941,6 +903,19 @@ struct KmpcIdxArgs { const int32_t* ids; int wstride; uint32_t ego_off; };
 #undef F1P_KPG_EGO
 #undef F1P_KPG_WROW
 #undef F1P_KPG_COL
+// k_kmpc_plan_gen_idx_col: k_kmpc_plan_gen_idx with the occupancy test -- the kinematic branch of f1p_stmpc_plan_batch while
+// f1p_stmpc_set_collision is on (its n_sub_k points per step)
+#define F1P_KPG_COL 1
+#define F1P_KPG_NAME k_kmpc_plan_gen_idx_col
+#define F1P_KPG_EXTRA KmpcIdxArgs ia, KmpcCol col,
+#define F1P_KPG_EGO ((uint32_t)ia.ids[e] + ia.ego_off)
+#define F1P_KPG_WROW ((size_t)ia.ids[e] * ia.wstride)
+#include "k_kmpc_plan_gen_text.h"
+#undef F1P_KPG_NAME
+#undef F1P_KPG_EXTRA
+#undef F1P_KPG_EGO
+#undef F1P_KPG_WROW
+#undef F1P_KPG_COL
 
 // materialise SrcGen's controls as the [E][T][2][R] f32 buffer of the streamed entry points (tests: generated == streamed)
 __global__ __launch_bounds__(256) void k_kmpc_gen_controls(float* __restrict__ controls, int E, int T, int R, KmpcGenArgs ga) {
@@ -1136,9 +1111,9 @@ static KmpcF32 make_kf(const f1p_kmpc_cfg* cfg);
 
 // the occupancy test's kernel argument.  filter: the launch runs the f32 filter -- it gets the clearance map when the mode is mixed, the map
 // can be built and the f32 position bound (F1P_K4_POS_ERR_REL x the rollouts' reach) is below one cell; otherwise every rollout is decided in fp64
-static KmpcCol kmpc_col_dev(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, bool filter) {
+static KmpcCol kmpc_col_dev(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, bool filter, int n_sub) {
     KmpcCol c;
-    c.g = grid_dev(ctx); c.clear = nullptr; c.n_sub = ctx->kmpc_col_nsub; c.force64 = ctx->kmpc_mixed ? 0 : 1;
+    c.g = grid_dev(ctx); c.clear = nullptr; c.n_sub = n_sub; c.force64 = ctx->kmpc_mixed ? 0 : 1;
     const double reach = fmax(fabs(cfg->max_speed), fabs(cfg->min_speed)) * cfg->horizon * cfg->dt;
     if (filter && ctx->kmpc_mixed && F1P_K4_POS_ERR_REL * reach * ctx->inv_res < 1.0 && ensure_clear_map(ctx, F1P_K4_CLEAR_CELLS) == F1P_OK)
         c.clear = ctx->d_bits_clear;
@@ -1176,7 +1151,7 @@ int launch_kmpc_shoot(f1p_ctx* ctx, const double* d_x0, const double* d_ref, con
     if (ctx->kmpc_collision) {                                        // (the caller checked the grid: kmpc_collision_check)
         const size_t lds = sizeof(double) * (4 * T1 + 4) + sizeof(int) * 4;
         hipLaunchKernelGGL(k_kmpc_shoot_col, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E,
-                           *cfg, kmpc_col_dev(ctx, cfg, false), d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
+                           *cfg, kmpc_col_dev(ctx, cfg, false, ctx->kmpc_col_nsub), d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
         return check_hip(ctx, hipGetLastError(), "k_kmpc_shoot_col launch");
     }
     if (ctx->kmpc_mixed && cfg->n_rollouts <= 8192) {
@@ -1272,13 +1247,21 @@ int launch_kmpc_plan_gen(f1p_ctx* ctx, const double* d_x0, const double* d_ref, 
     if (block < 64) block = 64;
     size_t lds = sizeof(float) * (4 * T1 + 2 * T + 4) + sizeof(int) * (F1P_K4_MAX_REFINE + 2) + 8 + sizeof(double) * (4 * T1 + 4 + 2) + sizeof(int) * 4;
     if (ga.G == 1) lds += sizeof(float) * R;
-    const bool collide = ctx->kmpc_collision && !d_ids;              // (f1p_stmpc_plan_*'s kinematic branch: not tested)
+    // the raceline / track plans follow f1p_kmpc_set_collision; a list of batch indices is f1p_stmpc_plan_batch's kinematic branch and
+    // follows f1p_stmpc_set_collision, with its own count
+    const bool collide = d_ids ? ctx->stmpc_collision : ctx->kmpc_collision;
     lds = (lds + 15) & ~(size_t)15;
     if (lds > (size_t)ctx->prop.sharedMemPerBlock) return set_error(ctx, F1P_EINVAL, "horizon / n_rollouts need more LDS than a workgroup has: use fewer rollouts per plan");
     if (const int rc = ensure_kmpc_cfg(ctx, cfg)) return rc;
     if (collide) {
         if (ga.G != 1) return set_error(ctx, F1P_ESTATE, "kmpc collision test: one workgroup per ego only (f1p_kmpc_set_groups(0))");
-        const KmpcCol col = kmpc_col_dev(ctx, cfg, true);
+        const KmpcCol col = kmpc_col_dev(ctx, cfg, true, d_ids ? ctx->stmpc_col_nsub_k : ctx->kmpc_col_nsub);
+        if (d_ids) {
+            hipLaunchKernelGGL(k_kmpc_plan_gen_idx_col, dim3((unsigned)E), dim3(block), lds, ctx->stream, d_x0, d_ref, E, *cfg, make_kf(cfg), ga,
+                               KmpcIdxArgs{d_ids, wstride, ego_off}, col, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_nref,
+                               ctx->d_kmpc_cfg_cur);
+            return check_hip(ctx, hipGetLastError(), "k_kmpc_plan_gen_idx_col launch");
+        }
         hipLaunchKernelGGL(k_kmpc_plan_gen_col, dim3((unsigned)E), dim3(block), lds, ctx->stream, d_x0, d_ref, E, *cfg, make_kf(cfg), ga, col,
                            d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_nref, ctx->d_kmpc_cfg_cur);
         return check_hip(ctx, hipGetLastError(), "k_kmpc_plan_gen_col launch");

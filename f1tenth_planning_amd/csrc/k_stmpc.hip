@@ -7,6 +7,7 @@
 // f1p_stmpc_plan_* runs the same kernels' text with the controls GENERATED in registers (the *_gen kernels).
 #include "f1p_internal.h"
 #include "shoot_gen.h"
+#include "shoot_col.h"
 
 namespace f1p {
 
@@ -234,6 +235,64 @@ __device__ __forceinline__ void stmpc_rollout_f32_gen(const SrcGenT<true>& ce, c
     }
 }
 
+// stmpc_rollout_f32_gen with the occupancy test's look-ups (k_stmpc_filter_gen_col): after every step the step's n_sub tested points --
+// formed from the f32 states, relative to the ego with the map's axes -- are looked up in the clearance map; unsure = one of them is near an
+// occupied cell, off the image or NaN, so the rollout is not proved free (shoot_col.h KmpcColF; the position bound: DESIGN.md 5i)
+template <bool POLY, int NR, int QM>
+__device__ __forceinline__ void stmpc_rollout_f32_gen_col(const SrcGenT<true>& ce, const float* sref8, const DynF32& k, int T, int R, const int (&rr)[NR],
+                                                          float delta0, float v0, float yr0, float beta0, float (&cost_out)[NR], bool (&trusted)[NR],
+                                                          const KmpcColF& cf, bool (&unsure)[NR]
+#ifdef F1P_ST_DBG_POS    // variant build (tools/stmpc_pos_error.py): the f32 positions after every step, [t][x | y] planes of pos_stride floats
+                                                          , float* pos_out, size_t pos_stride
+#endif
+                                                          ) {
+#pragma clang fp contract(fast)
+    (void)R;
+    float x[NR], y[NR], delta[NR], v[NR], yaw[NR], yr[NR], beta[NR], cost[NR], pdv[NR], pa[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        x[i] = 0.f; y[i] = 0.f; delta[i] = delta0; v[i] = v0; yaw[i] = 0.f; yr[i] = yr0; beta[i] = beta0; cost[i] = 0.f; pdv[i] = 0.f; pa[i] = 0.f;
+        trusted[i] = true; unsure[i] = false;
+    }
+    const float4* sr = reinterpret_cast<const float4*>(sref8);
+    for (int te = 0; te < T; te += 2) {
+        float c_dv[NR][2], c_a[NR][2];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) ce.get2(te, T, rr[i], c_dv[i][0], c_a[i][0], c_dv[i][1], c_a[i][1]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int t = te + h;
+            if (t < T) {
+                const float4 r0 = sr[2 * t], r1 = sr[2 * t + 1];
+#pragma unroll
+                for (int i = 0; i < NR; ++i) {
+                    float dv = __builtin_amdgcn_fmed3f(c_dv[i][h], -k.max_steer_v, k.max_steer_v);
+                    const float a = __builtin_amdgcn_fmed3f(c_a[i][h], -k.max_accel, k.max_accel);
+                    const float px = x[i], py = y[i];
+                    F1P_ST_F32_STEP(i)
+                    for (int j = 1; j < cf.n_sub; ++j) {
+                        const float f = (float)j * cf.inv_nsub;
+                        unsure[i] |= cf.template unsure<false>(px + (x[i] - px) * f, py + (y[i] - py) * f);
+                    }
+                    unsure[i] |= cf.template unsure<false>(x[i], y[i]);
+#ifdef F1P_ST_DBG_POS
+                    if (pos_out) { pos_out[((size_t)t * 2 + 0) * pos_stride + rr[i]] = x[i]; pos_out[((size_t)t * 2 + 1) * pos_stride + rr[i]] = y[i]; }
+#endif
+                }
+            }
+        }
+    }
+    const float4 r0 = sr[2 * T], r1 = sr[2 * T + 1];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const float sv_[7] = {x[i], y[i], delta[i], v[i], yaw[i], yr[i], beta[i]}, rf_[7] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z};
+        float qs = 0.f;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) if (QM & (1 << j)) { const float er = sv_[j] - rf_[j]; qs += k.qf[j] * er * er; }
+        cost_out[i] = cost[i] + qs;
+    }
+}
+
 // ---- K-A: f32 filter, one workgroup per ego; no fp64 rollout code in this kernel (registers for 8 waves per SIMD) ----------------
 // nlist[e] = listed rollouts (<= 64) or -1 (this ego is decided by the all-fp64 loop in k_stmpc_decide); the listed rollouts go to
 // rl[e][slot] and, as (e * 64 + slot, r), onto the global queue that k_stmpc_refine packs into full waves across egos.
@@ -263,6 +322,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 }
 
 // ---- the shooting kernels, once per control source (k_stmpc_shoot_text.h) -----------------------------------------------------------
+#define F1P_ST_COL 0
 #define F1P_ST_N(name) name
 #define F1P_ST_CTL_PARAM const float* __restrict__ controls
 #define F1P_ST_SRC_PARAM const float* __restrict__ ce
@@ -342,6 +402,97 @@ __device__ __forceinline__ void wave_lds_sync() {
 #undef F1P_ST_EMIT_A
 #undef F1P_ST_EMIT_TAIL
 #undef F1P_ST_FILTER_WARM
+
+// the same text twice more with the occupancy test of f1p_stmpc_set_collision (F1P_ST_COL 1): k_stmpc_shoot_col over streamed
+// controls -- what f1p_stmpc_shoot_* launch in every mode while the test is on -- and k_stmpc_shoot_gen_col over generated ones
+#undef F1P_ST_COL
+#define F1P_ST_COL 1
+#define F1P_ST_COL_MIXED 0
+#define F1P_ST_N(name) name##_col
+#define F1P_ST_CTL_PARAM const float* __restrict__ controls
+#define F1P_ST_SRC_PARAM const float* __restrict__ ce
+#define F1P_ST_SRC_DECL(ce, e) const float* ce = controls + (size_t)e * T * 2 * R
+#define F1P_ST_SRC_DECL_FILTER(ce, e) F1P_ST_SRC_DECL(ce, e)
+#define F1P_ST_SRC_EXPR(e) controls + (size_t)e * T * 2 * R
+#define F1P_ST_SRC_DECL_R(cp, e, r) const float* cp = controls + (size_t)e * T * 2 * R + r
+#define F1P_ST_DV_R(cp, t, r) cp[(size_t)t * 2 * R]
+#define F1P_ST_A_R(cp, t, r) cp[(size_t)t * 2 * R + R]
+#define F1P_ST_DV(ce, t, r) ce[((size_t)t * 2 + 0) * R + r]
+#define F1P_ST_A(ce, t, r) ce[((size_t)t * 2 + 1) * R + r]
+#define F1P_ST_EMIT_PRE(ce, bi)
+#define F1P_ST_EMIT_DV(ce, t, bi) ce[((size_t)t * 2 + 0) * R + bi]
+#define F1P_ST_EMIT_A(ce, t, bi) ce[((size_t)t * 2 + 1) * R + bi]
+#define F1P_ST_EMIT_TAIL(e, t, dv, a) else if (t == 0) break;
+#define F1P_ST_FILTER_WARM(e)
+#define F1P_ST_EMIT_BLOCKED(e, q)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-variable"
+#include "k_stmpc_shoot_text.h"
+#pragma clang diagnostic pop
+#undef F1P_ST_N
+#undef F1P_ST_CTL_PARAM
+#undef F1P_ST_SRC_PARAM
+#undef F1P_ST_SRC_DECL
+#undef F1P_ST_SRC_DECL_FILTER
+#undef F1P_ST_SRC_EXPR
+#undef F1P_ST_SRC_DECL_R
+#undef F1P_ST_DV_R
+#undef F1P_ST_A_R
+#undef F1P_ST_DV
+#undef F1P_ST_A
+#undef F1P_ST_EMIT_PRE
+#undef F1P_ST_EMIT_DV
+#undef F1P_ST_EMIT_A
+#undef F1P_ST_EMIT_TAIL
+#undef F1P_ST_FILTER_WARM
+#undef F1P_ST_EMIT_BLOCKED
+#undef F1P_ST_COL_MIXED
+#define F1P_ST_COL_MIXED 1
+#define F1P_ST_N(name) name##_gen_col
+#define F1P_ST_CTL_PARAM StCtlGen ctl
+#define F1P_ST_SRC_PARAM const StGenSrc& ce
+#define F1P_ST_SRC_DECL(ce, e) const StGenSrc ce = {ctl.src(e, ctl.warm_row(e)), 0.0f}
+#define F1P_ST_SRC_DECL_FILTER(ce, e) const SrcGenT<true> ce = ctl.src(e, reinterpret_cast<const float*>(cnt + 2))
+#define F1P_ST_SRC_EXPR(e) StGenSrc{ctl.src(e, ctl.warm_row(e)), 0.0f}
+#define F1P_ST_SRC_DECL_R(cp, e, r) F1P_ST_SRC_DECL(cp, e)
+#define F1P_ST_DV_R(cp, t, r) cp.dv(t, r)
+#define F1P_ST_A_R(cp, t, r) cp.a()
+#define F1P_ST_DV(ce, t, r) ce.dv(t, r)
+#define F1P_ST_A(ce, t, r) ce.a()
+#define F1P_ST_EMIT_PRE(ce, bi) float* emit_s = reinterpret_cast<float*>(lds_raw); \
+        for (int t_ = tid; t_ < T; t_ += blockDim.x) ce.g.get(t_, bi, emit_s[2 * t_], emit_s[2 * t_ + 1]); \
+        __syncthreads();
+#define F1P_ST_EMIT_DV(ce, t, bi) emit_s[2 * t]
+#define F1P_ST_EMIT_A(ce, t, bi) emit_s[2 * t + 1]
+#define F1P_ST_EMIT_TAIL(e, t, dv, a) { float* wo_ = ctl.warm_row(e); \
+        if (t > 0) { wo_[2 * (t - 1)] = (float)dv; wo_[2 * (t - 1) + 1] = (float)a; } \
+        if (t == T - 1) { wo_[2 * t] = (float)dv; wo_[2 * t + 1] = (float)a; } }
+#define F1P_ST_FILTER_WARM(e) { float* ws_ = reinterpret_cast<float*>(cnt + 2); const float* wg_ = ctl.warm_row(e); \
+        for (int q = tid; q < 2 * T; q += blockDim.x) ws_[q] = wg_[q]; }
+#define F1P_ST_EMIT_BLOCKED(e, q) ctl.warm_row(e)[q] = 0.0f;
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-variable"
+#include "k_stmpc_shoot_text.h"
+#pragma clang diagnostic pop
+#undef F1P_ST_N
+#undef F1P_ST_CTL_PARAM
+#undef F1P_ST_SRC_PARAM
+#undef F1P_ST_SRC_DECL
+#undef F1P_ST_SRC_DECL_FILTER
+#undef F1P_ST_SRC_EXPR
+#undef F1P_ST_SRC_DECL_R
+#undef F1P_ST_DV_R
+#undef F1P_ST_A_R
+#undef F1P_ST_DV
+#undef F1P_ST_A
+#undef F1P_ST_EMIT_PRE
+#undef F1P_ST_EMIT_DV
+#undef F1P_ST_EMIT_A
+#undef F1P_ST_EMIT_TAIL
+#undef F1P_ST_FILTER_WARM
+#undef F1P_ST_EMIT_BLOCKED
+#undef F1P_ST_COL_MIXED
+#undef F1P_ST_COL
 
 // materialise the generator's controls as the [E][T][2][R] f32 buffer of the streamed entry points (tests: generated == streamed)
 __global__ __launch_bounds__(256) void k_stmpc_gen_controls(float* __restrict__ controls, int E, int T, int R, StCtlGen ctl) {
@@ -428,11 +579,102 @@ static DynF32 make_dyn_f32(const f1p_stmpc_cfg* cfg) {
     return k;
 }
 
+// the mixed schedule's scratch for E egos: queue counter (256 B) | nlist [E] | rl [E][64] | items [E][64] | rc [E][64]; the queue counter is
+// zeroed when the scratch is new or a plan failed between its kernels, and st_q_dirty stays set until the caller's last launch succeeded
+struct StScratch { unsigned int* qcount; int32_t *nlist, *rl; StItem* items; double* rc; };
+static int st_scratch(f1p_ctx* ctx, int E, StScratch& sc) {
+    const size_t n_off = 256, rl_off = (n_off + 4 * (size_t)E + 255) & ~(size_t)255;
+    const size_t it_off = (rl_off + 4 * (size_t)E * F1P_ST_MAX_REFINE + 255) & ~(size_t)255;
+    const size_t rc_off = (it_off + sizeof(StItem) * (size_t)E * F1P_ST_MAX_REFINE + 255) & ~(size_t)255;
+    const size_t need = rc_off + 8 * (size_t)E * F1P_ST_MAX_REFINE;
+    if (need > ctx->st_scratch_bytes) {
+        F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->d_st_scratch) (void)hipFree(ctx->d_st_scratch);
+        ctx->d_st_scratch = nullptr; ctx->st_scratch_bytes = 0;
+        F1P_HIP(ctx, hipMalloc((void**)&ctx->d_st_scratch, need));
+        ctx->st_scratch_bytes = need;
+        ctx->st_q_dirty = true;
+    }
+    sc.qcount = reinterpret_cast<unsigned int*>(ctx->d_st_scratch);
+    sc.nlist = reinterpret_cast<int32_t*>(ctx->d_st_scratch + n_off);
+    sc.rl = reinterpret_cast<int32_t*>(ctx->d_st_scratch + rl_off);
+    sc.items = reinterpret_cast<StItem*>(ctx->d_st_scratch + it_off);
+    sc.rc = reinterpret_cast<double*>(ctx->d_st_scratch + rc_off);
+    if (ctx->st_q_dirty) F1P_HIP(ctx, hipMemsetAsync(sc.qcount, 0, 256, ctx->stream));
+    ctx->st_q_dirty = true;
+    return F1P_OK;
+}
+
+// Bound on the f32 filter's position error against the fp64 rollout over the horizon [m], for a TRUSTED rollout (only those can be FREE);
+// DESIGN.md 5i derives the terms.  u = 2^-24.
+static double st_pos_err_bound(const f1p_stmpc_cfg* cfg) {
+    const double u = 5.9604644775390625e-8, T = cfg->horizon;
+    const double vmax = fmax(fabs(cfg->max_speed), fabs(cfg->min_speed)), reach = vmax * T * cfg->dt;
+    const double yr_max = vmax / cfg->wheelbase * tan(fmin(fabs(cfg->max_steer), 1.4));   // steady-state yaw rate at full lock
+    const double yaw_max = yr_max * T * cfg->dt;                                           // the relative heading's range
+    // heading = yaw + beta.  yaw: T accumulations, each rounding u (|yaw| + its increment), + the tan polynomial's 2.5e-7 relative on the
+    // increments; (yr, beta): per-step roundings 8 u max(yr_max, 1) through a contraction of factor <= 0.9 (the trust speed) = x 10;
+    // the hardware sin / cos: 1e-6 absolute
+    const double dth = T * u * (yaw_max + 1.0) + 2.5e-7 * yaw_max + 80.0 * u * fmax(yr_max, 1.0) + 1.0e-6;
+    // positions: the heading error at the reach; T accumulations of u |x|; the increments' 2 u + 1e-6; the speed's T u over the horizon;
+    // the interpolation, the ego-cell offset and the cell conversion 4 u
+    return reach * (dth + T * u + 2.0 * u + 1.0e-6 + T * u + 4.0 * u);
+}
+#define F1P_ST_POS_HEADROOM 5.0        // the filter gets the clearance map only while headroom x bound < one cell (DESIGN.md 5h's factor)
+
 // the schedule of f1p_stmpc_shoot_* (gen == nullptr: streamed d_controls) and of f1p_stmpc_plan_* (gen: generated controls, d_controls unused)
 static int stmpc_shoot_any(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const float* d_controls, const StCtlGen* gen, int E, const f1p_stmpc_cfg* cfg,
                            double* d_steer, double* d_speed, int32_t* d_best_idx, double* d_best_cost, double* d_best_seq) {
     if (E <= 0) return F1P_OK;
     const size_t T1 = (size_t)cfg->horizon + 1;
+    if (ctx->stmpc_collision) {
+        // the occupancy test (the caller checked the grid: stmpc_collision_check).  Streamed controls: plain fp64 in every mode, so that
+        // gen_controls + shoot == plan bit for bit.  Generated controls in the mixed mode: filter -> refinement -> decision with the test, as
+        // long as the f32 position bound (with its headroom) stays below one cell and the clearance map can be built; otherwise plain fp64.
+        KmpcCol col;
+        col.g = grid_dev(ctx); col.clear = nullptr; col.n_sub = ctx->stmpc_col_nsub; col.force64 = 1;
+        const size_t lds = sizeof(double) * (7 * T1 + 4) + sizeof(int) * 4;
+        if (lds > (size_t)ctx->prop.sharedMemPerBlock) return set_error(ctx, F1P_EINVAL, "stmpc: the horizon needs more LDS than a workgroup has");
+        if (gen && ctx->stmpc_mixed) {
+            const DynF32 kf = make_dyn_f32(cfg);
+            const size_t lds_a = sizeof(float) * (8 * T1 + (size_t)cfg->n_rollouts + 4) + sizeof(int) * (F1P_ST_MAX_REFINE + 2) + sizeof(float) * 2 * (size_t)cfg->horizon;
+            if (lds_a <= (size_t)ctx->prop.sharedMemPerBlock && kf.v_trust == kf.v_trust && (size_t)E * F1P_ST_MAX_REFINE < ((size_t)1 << 31) &&
+                F1P_ST_POS_HEADROOM * st_pos_err_bound(cfg) * ctx->inv_res < 1.0 && ensure_clear_map(ctx, F1P_K4_CLEAR_CELLS) == F1P_OK) {
+                col.clear = ctx->d_bits_clear; col.force64 = 0;
+                StScratch sc;
+                if (const int rs = st_scratch(ctx, E, sc)) return rs;
+                int qm = 0;
+                for (int j = 0; j < 7; ++j) if (cfg->q[j] != 0.0 || cfg->qf[j] != 0.0) qm |= 1 << j;
+                if (qm == 0x1b)
+                    hipLaunchKernelGGL(k_stmpc_filter_gen_col<0x1b>, dim3(E), dim3(256), (lds_a + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, cfg->horizon,
+                                       cfg->n_rollouts, cfg->max_steer, kf, col, sc.qcount, sc.items, sc.nlist, sc.rl, ctx->d_dbg_st_cost32);
+                else
+                    hipLaunchKernelGGL(k_stmpc_filter_gen_col<0x7f>, dim3(E), dim3(256), (lds_a + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, cfg->horizon,
+                                       cfg->n_rollouts, cfg->max_steer, kf, col, sc.qcount, sc.items, sc.nlist, sc.rl, ctx->d_dbg_st_cost32);
+                int rcode = check_hip(ctx, hipGetLastError(), "k_stmpc_filter_gen_col launch");
+                if (rcode != F1P_OK) return rcode;
+                if (cfg->horizon <= 63 && 4 * F1P_ST_TP_LDS_PER_WAVE <= (size_t)ctx->prop.sharedMemPerBlock) {
+                    const int nb = E * F1P_ST_MAX_REFINE / 4 < 2 * ctx->prop.multiProcessorCount ? (E * F1P_ST_MAX_REFINE + 3) / 4 : 2 * ctx->prop.multiProcessorCount;
+                    hipLaunchKernelGGL(k_stmpc_refine_tp_gen_col, dim3(nb), dim3(256), 4 * F1P_ST_TP_LDS_PER_WAVE, ctx->stream, d_x0, d_ref, *gen, *cfg, sc.qcount,
+                                       sc.items, col, sc.rl, sc.rc, (float*)nullptr);
+                } else {
+                    hipLaunchKernelGGL(k_stmpc_refine_gen_col, dim3(E), dim3(64), 0, ctx->stream, d_x0, d_ref, *gen, *cfg, sc.qcount, sc.items, col, sc.rl, sc.rc);
+                }
+                rcode = check_hip(ctx, hipGetLastError(), "k_stmpc_refine_gen_col launch");
+                if (rcode != F1P_OK) return rcode;
+                hipLaunchKernelGGL(k_stmpc_decide_gen_col, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, *cfg, sc.qcount,
+                                   sc.nlist, sc.rl, sc.rc, col, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_st_nref);
+                rcode = check_hip(ctx, hipGetLastError(), "k_stmpc_decide_gen_col launch");
+                if (rcode == F1P_OK) ctx->st_q_dirty = false;
+                return rcode;
+            }
+        }
+        if (gen) hipLaunchKernelGGL(k_stmpc_shoot_gen_col, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, *cfg, col,
+                                    d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
+        else hipLaunchKernelGGL(k_stmpc_shoot_col, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E, *cfg, col,
+                                d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
+        return check_hip(ctx, hipGetLastError(), "k_stmpc_shoot_col launch");
+    }
     if (ctx->stmpc_mixed) {
         const DynF32 kf = make_dyn_f32(cfg);
         const size_t lds_a = sizeof(float) * (8 * T1 + (size_t)cfg->n_rollouts + 4) + sizeof(int) * (F1P_ST_MAX_REFINE + 2) +
@@ -440,26 +682,9 @@ static int stmpc_shoot_any(f1p_ctx* ctx, const double* d_x0, const double* d_ref
         const size_t lds_c = sizeof(double) * (7 * T1 + 4) + sizeof(int) * 4;
         if (lds_a <= (size_t)ctx->prop.sharedMemPerBlock && lds_c <= (size_t)ctx->prop.sharedMemPerBlock && kf.v_trust == kf.v_trust &&
             (size_t)E * F1P_ST_MAX_REFINE < ((size_t)1 << 31)) {
-            // scratch: queue counter (256 B) | nlist [E] | rl [E][64] | items [E][64] | rc [E][64]
-            const size_t n_off = 256, rl_off = (n_off + 4 * (size_t)E + 255) & ~(size_t)255;
-            const size_t it_off = (rl_off + 4 * (size_t)E * F1P_ST_MAX_REFINE + 255) & ~(size_t)255;
-            const size_t rc_off = (it_off + sizeof(StItem) * (size_t)E * F1P_ST_MAX_REFINE + 255) & ~(size_t)255;
-            const size_t need = rc_off + 8 * (size_t)E * F1P_ST_MAX_REFINE;
-            if (need > ctx->st_scratch_bytes) {
-                F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                if (ctx->d_st_scratch) (void)hipFree(ctx->d_st_scratch);
-                ctx->d_st_scratch = nullptr; ctx->st_scratch_bytes = 0;
-                F1P_HIP(ctx, hipMalloc((void**)&ctx->d_st_scratch, need));
-                ctx->st_scratch_bytes = need;
-                ctx->st_q_dirty = true;
-            }
-            unsigned int* qcount = reinterpret_cast<unsigned int*>(ctx->d_st_scratch);
-            int32_t* nlist = reinterpret_cast<int32_t*>(ctx->d_st_scratch + n_off);
-            int32_t* rl = reinterpret_cast<int32_t*>(ctx->d_st_scratch + rl_off);
-            StItem* items = reinterpret_cast<StItem*>(ctx->d_st_scratch + it_off);
-            double* rc = reinterpret_cast<double*>(ctx->d_st_scratch + rc_off);
-            if (ctx->st_q_dirty) F1P_HIP(ctx, hipMemsetAsync(qcount, 0, 256, ctx->stream));   // new scratch, or a plan failed between its kernels
-            ctx->st_q_dirty = true;
+            StScratch sc;
+            if (const int rs = st_scratch(ctx, E, sc)) return rs;
+            unsigned int* qcount = sc.qcount; int32_t *nlist = sc.nlist, *rl = sc.rl; StItem* items = sc.items; double* rc = sc.rc;
             int qm = 0;                                              // rows that carry weight in the stage or the terminal cost
             for (int j = 0; j < 7; ++j) if (cfg->q[j] != 0.0 || cfg->qf[j] != 0.0) qm |= 1 << j;
             if (gen && qm == 0x1b)

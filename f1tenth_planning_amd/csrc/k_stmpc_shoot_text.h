@@ -17,14 +17,29 @@
 //   F1P_ST_EMIT_DV / _A(ce, t, bi)   the winner's controls of step t in the emission
 //   F1P_ST_EMIT_TAIL(e, t, dv, a)   after step t of the winner's re-emission: streamed -- stop after step 0 when no best_seq is wanted;
 //                                   generated -- write the next warm start
+//   F1P_ST_COL                  1: the occupancy test of f1p_stmpc_set_collision -- the names get _col, the kernels a `KmpcCol col`
+//                               parameter, the fp64 rollouts test each step as they take it, and F1P_ST_EMIT_BLOCKED(e) zeroes ego e's
+//                               warm start in the "every rollout blocked" emission.  F1P_ST_COL_MIXED 1 also compiles the mixed schedule
+//                               with the test (the generated source only: f1p_stmpc_shoot_* run the plain-fp64 kernel while the test is
+//                               on): the filter looks its tested points up in the clearance map and lists FREE and UNSURE rollouts, the
+//                               refinement marks a blocked item (cost +inf, listed index F1P_K4_NONE), the decision skips those.
+//                               Everything the test adds sits inside #if F1P_ST_COL, so the two inclusions without it keep their
+//                               preprocessed tokens.
 // all rollouts of this thread, first-minimum argmin (objective :616-622, bounds :685-706 as a projection)
 template <bool FAST>
 __device__ __forceinline__ void F1P_ST_N(stmpc_rollouts)(F1P_ST_SRC_PARAM, const double* sref, const f1p_stmpc_cfg& cfg, const DynConst& k,
-                                               const DynState& s0, int tid, double& bc, int& bi) {
+                                               const DynState& s0, int tid, double& bc, int& bi
+#if F1P_ST_COL
+                                               , const KmpcCol& col
+#endif
+                                               ) {
     const int T = cfg.horizon, R = cfg.n_rollouts;
     for (int r = tid; r < R; r += blockDim.x) {
         DynState s = s0;
         double cost = 0.0, pdv = 0.0, pa = 0.0;
+#if F1P_ST_COL
+        bool blocked = false;
+#endif
         for (int t = 0; t < T; ++t) {
             double dv = clampd2((double)F1P_ST_DV(ce, t, r), -cfg.max_steer_v, cfg.max_steer_v);   // :701-703
             double a = clampd2((double)F1P_ST_A(ce, t, r), -cfg.max_accel, cfg.max_accel);        // :704-706
@@ -36,9 +51,18 @@ __device__ __forceinline__ void F1P_ST_N(stmpc_rollouts)(F1P_ST_SRC_PARAM, const
             cost += q;
             cost += cfg.r[0] * dv * dv + cfg.r[1] * a * a;                                                       // :616
             if (t > 0) { const double d0 = dv - pdv, d1 = a - pa; cost += cfg.rd[0] * d0 * d0 + cfg.rd[1] * d1 * d1; }   // :622
+#if F1P_ST_COL
+            const double px = s.x, py = s.y;
+#endif
             dyn_step<FAST>(s, a, dv, cfg, k);
+#if F1P_ST_COL
+            if (col.seg(px, py, s.x, s.y)) { blocked = true; break; }   // the points of step t -> t + 1; a blocked rollout stops at its first occupied point
+#endif
             pdv = dv; pa = a;
         }
+#if F1P_ST_COL
+        if (blocked) continue;                                        // takes no part in the argmin: (bc, bi) stays (+inf, F1P_K4_NONE) while nothing is free
+#endif
         const double sv[7] = {s.x, s.y, s.delta, s.v, s.yaw, s.yr, s.beta};
         double q = 0.0;
 #pragma unroll
@@ -50,6 +74,9 @@ __device__ __forceinline__ void F1P_ST_N(stmpc_rollouts)(F1P_ST_SRC_PARAM, const
 
 __global__ __launch_bounds__(256) void F1P_ST_N(k_stmpc_shoot)(const double* __restrict__ x0, const double* __restrict__ ref,
                                                      F1P_ST_CTL_PARAM, int E, f1p_stmpc_cfg cfg,
+#if F1P_ST_COL
+                                                     KmpcCol col,
+#endif
                                                      double* __restrict__ steer, double* __restrict__ speed,
                                                      int32_t* __restrict__ best_idx, double* __restrict__ best_cost,
                                                      double* __restrict__ best_seq) {
@@ -68,9 +95,26 @@ __global__ __launch_bounds__(256) void F1P_ST_N(k_stmpc_shoot)(const double* __r
     s0.yr = x0[7 * e + 5]; s0.beta = x0[7 * e + 6];
     F1P_ST_SRC_DECL(ce, e);
     double bc = __builtin_huge_val(); int bi = 0x7fffffff;
+#if F1P_ST_COL
+    if (fabs(cfg.max_steer) <= 1.0e4) F1P_ST_N(stmpc_rollouts)<true>(ce, sref, cfg, k, s0, tid, bc, bi, col);     // workgroup-uniform
+    else F1P_ST_N(stmpc_rollouts)<false>(ce, sref, cfg, k, s0, tid, bc, bi, col);
+    block_argmin(bc, bi, red_d, red_i);
+    if (bi == F1P_K4_NONE) {                                          // every rollout blocked (workgroup-uniform): the lattice's ALL_BLOCKED outputs
+        for (int q = tid; q < 2 * T; q += blockDim.x) {
+            if (best_seq) best_seq[(size_t)e * T * 2 + q] = 0.0;
+            F1P_ST_EMIT_BLOCKED(e, q)
+        }
+        if (tid == 0) {
+            steer[e] = 0.0; speed[e] = 0.0; best_idx[e] = -1;
+            if (best_cost) best_cost[e] = __builtin_huge_val();
+        }
+        return;
+    }
+#else
     if (fabs(cfg.max_steer) <= 1.0e4) F1P_ST_N(stmpc_rollouts)<true>(ce, sref, cfg, k, s0, tid, bc, bi);     // workgroup-uniform
     else F1P_ST_N(stmpc_rollouts)<false>(ce, sref, cfg, k, s0, tid, bc, bi);
     block_argmin(bc, bi, red_d, red_i);
+#endif
     F1P_ST_EMIT_PRE(ce, bi)
     if (tid == 0) {
         double pdv = 0.0;
@@ -91,13 +135,21 @@ __global__ __launch_bounds__(256) void F1P_ST_N(k_stmpc_shoot)(const double* __r
     }
 }
 
+#if !F1P_ST_COL || F1P_ST_COL_MIXED
 // fp64 cost of ONE rollout: the body of F1P_ST_N(stmpc_rollouts) for a given r (same operations, same order)
 template <bool FAST>
 __device__ __forceinline__ double F1P_ST_N(stmpc_one_rollout)(F1P_ST_SRC_PARAM, const double* sref, const f1p_stmpc_cfg& cfg, const DynConst& k,
-                                                    const DynState& s0, int r) {
+                                                    const DynState& s0, int r
+#if F1P_ST_COL
+                                                    , const KmpcCol& col, bool& blocked
+#endif
+                                                    ) {
     const int T = cfg.horizon, R = cfg.n_rollouts;
     DynState s = s0;
     double cost = 0.0, pdv = 0.0, pa = 0.0;
+#if F1P_ST_COL
+    blocked = false;
+#endif
     for (int t = 0; t < T; ++t) {
         double dv = clampd2((double)F1P_ST_DV(ce, t, r), -cfg.max_steer_v, cfg.max_steer_v);
         double a = clampd2((double)F1P_ST_A(ce, t, r), -cfg.max_accel, cfg.max_accel);
@@ -109,7 +161,13 @@ __device__ __forceinline__ double F1P_ST_N(stmpc_one_rollout)(F1P_ST_SRC_PARAM, 
         cost += q;
         cost += cfg.r[0] * dv * dv + cfg.r[1] * a * a;
         if (t > 0) { const double d0 = dv - pdv, d1 = a - pa; cost += cfg.rd[0] * d0 * d0 + cfg.rd[1] * d1 * d1; }
+#if F1P_ST_COL
+        const double px = s.x, py = s.y;
+#endif
         dyn_step<FAST>(s, a, dv, cfg, k);
+#if F1P_ST_COL
+        if (col.seg(px, py, s.x, s.y)) { blocked = true; return __builtin_huge_val(); }
+#endif
         pdv = dv; pa = a;
     }
     const double sv[7] = {s.x, s.y, s.delta, s.v, s.yaw, s.yr, s.beta};
@@ -123,6 +181,9 @@ __device__ __forceinline__ double F1P_ST_N(stmpc_one_rollout)(F1P_ST_SRC_PARAM, 
 template <int QM>
 __global__ __launch_bounds__(256) void F1P_ST_N(k_stmpc_filter)(const double* __restrict__ x0, const double* __restrict__ ref,
                                                       F1P_ST_CTL_PARAM, int E, int T, int R, double max_steer_d, DynF32 kf,
+#if F1P_ST_COL
+                                                      KmpcCol col,
+#endif
                                                       unsigned int* __restrict__ qcount, StItem* __restrict__ items, int32_t* __restrict__ nlist,
                                                       int32_t* __restrict__ rl, float* __restrict__ dbg_cost32) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -135,7 +196,14 @@ __global__ __launch_bounds__(256) void F1P_ST_N(k_stmpc_filter)(const double* __
     const int e = blockIdx.x;
     if (e >= E) return;
     const double sx = x0[7 * e], sy = x0[7 * e + 1], sdelta = x0[7 * e + 2], sv = x0[7 * e + 3], syaw = x0[7 * e + 4], syr = x0[7 * e + 5], sbeta = x0[7 * e + 6];
+#if F1P_ST_COL
+    // the ego's cell (fp64) anchors the filter's cell coordinates; an ego without one is decided in fp64
+    const double bxd = (sx - col.g.ox) * col.g.inv_res, byd = (sy - col.g.oy) * col.g.inv_res;
+    const bool in_range = fabs(syaw) <= 1.0e4 && fabs(max_steer_d) <= 1.0e4 && fabs(sbeta) <= 100.0 && fabs(sdelta) <= 100.0 &&
+                          fabs(bxd) < 1.0e6 && fabs(byd) < 1.0e6;   // workgroup-uniform
+#else
     const bool in_range = fabs(syaw) <= 1.0e4 && fabs(max_steer_d) <= 1.0e4 && fabs(sbeta) <= 100.0 && fabs(sdelta) <= 100.0;   // workgroup-uniform
+#endif
     if (!in_range) { if (tid == 0) nlist[e] = -1; return; }
     int bad_ref = 0;                                                 // a non-finite reference in an UNWEIGHTED row makes every fp64 cost NaN (0 * NaN): fp64 decides
     for (int q = tid; q < 7 * (T + 1); q += blockDim.x) {
@@ -161,6 +229,17 @@ __global__ __launch_bounds__(256) void F1P_ST_N(k_stmpc_filter)(const double* __
     double s0d, c0d;
     sincos_core(syaw, &s0d, &c0d);
     kk.c0 = (float)c0d; kk.s0 = (float)s0d;
+#if F1P_ST_COL
+    KmpcColF cf;                                                     // (the filter's positions are relative to the ego with the map's axes: unsure<false>)
+    {
+        const double ibx = __builtin_floor(bxd), iby = __builtin_floor(byd);
+        cf.clear = col.clear; cf.wwords = col.g.wwords; cf.n_sub = col.n_sub; cf.inv_nsub = 1.0f / (float)col.n_sub;
+        cf.ibx = __builtin_amdgcn_readfirstlane((int)ibx); cf.iby = __builtin_amdgcn_readfirstlane((int)iby);
+        cf.bx = (float)(bxd - ibx); cf.by = (float)(byd - iby);
+        cf.lox = (float)-cf.ibx; cf.hix = (float)(col.g.w - cf.ibx); cf.loy = (float)-cf.iby; cf.hiy = (float)(col.g.h - cf.iby);
+        cf.inv_res = (float)col.g.inv_res; cf.c0 = 1.0f; cf.s0 = 0.0f;
+    }
+#endif
     // the odd polynomial of tan is good for |delta| <= 0.45: every later delta is clamped to max_steer, but step 0 evaluates tan(delta0)
     // UNCLAMPED (dyn_step does, like the reference) -- an out-of-range initial steering state takes the sin / cos path (workgroup-uniform)
     const bool poly = kf.max_steer <= 0.45f && fabs(sdelta) <= 0.45;
@@ -170,14 +249,30 @@ __global__ __launch_bounds__(256) void F1P_ST_N(k_stmpc_filter)(const double* __
         int rr[NR]; float c[NR]; bool trusted[NR];
 #pragma unroll
         for (int i = 0; i < NR; ++i) rr[i] = rb + i * (int)blockDim.x < R ? rb + i * (int)blockDim.x : rb;   // past the end: a shadow of the first, not stored
+#if F1P_ST_COL
+        bool unsure[NR];                                             // a tested point near an occupied cell, off the image or NaN: not FREE
+#ifdef F1P_ST_DBG_POS    // variant build: dbg_cost32 is [1 + 2 T][E][R] -- the costs, then the f32 (x, y) after every step (tools/stmpc_pos_error.py)
+#define F1P_ST_POS_ARGS , dbg_cost32 ? dbg_cost32 + ((size_t)E + e) * R : nullptr, (size_t)E * R
+#else
+#define F1P_ST_POS_ARGS
+#endif
+        if (poly) F1P_ST_N(stmpc_rollout_f32)<true, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted, cf, unsure F1P_ST_POS_ARGS);
+        else F1P_ST_N(stmpc_rollout_f32)<false, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted, cf, unsure F1P_ST_POS_ARGS);
+#undef F1P_ST_POS_ARGS
+#else
         if (poly) F1P_ST_N(stmpc_rollout_f32)<true, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted);
         else F1P_ST_N(stmpc_rollout_f32)<false, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted);
+#endif
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
             if (i > 0 && rr[i] == rb) continue;
             float ci = c[i];
             if (!trusted[i] || !(ci == ci) || !(fabsf(ci) < 1e30f)) ci = -__builtin_huge_valf();      // untrusted / non-finite: fp64 decides
+#if F1P_ST_COL
+            else if (!unsure[i]) tmin = fminf(tmin, ci);            // the threshold comes from the FREE rollouts; an UNSURE one keeps its cost and is listed at or below it
+#else
             else tmin = fminf(tmin, ci);
+#endif
             c32[rr[i]] = ci;
             if (dbg_cost32) dbg_cost32[(size_t)e * R + rr[i]] = ci;
         }
@@ -218,6 +313,9 @@ __global__ __launch_bounds__(256) void F1P_ST_N(k_stmpc_filter)(const double* __
 // controls in LDS and batching the reference loads -- each left the time where it was.
 __global__ __launch_bounds__(64) void F1P_ST_N(k_stmpc_refine)(const double* __restrict__ x0, const double* __restrict__ ref, F1P_ST_CTL_PARAM,
                                                      f1p_stmpc_cfg cfg, const unsigned int* __restrict__ qcount, const StItem* __restrict__ items,
+#if F1P_ST_COL
+                                                     KmpcCol col, int32_t* __restrict__ rl,
+#endif
                                                      double* __restrict__ rc) {
     const unsigned int count = *qcount;
     const int T = cfg.horizon, R = cfg.n_rollouts;
@@ -228,12 +326,21 @@ __global__ __launch_bounds__(64) void F1P_ST_N(k_stmpc_refine)(const double* __r
         DynState s0;
         s0.x = x0[7 * e]; s0.y = x0[7 * e + 1]; s0.delta = x0[7 * e + 2]; s0.v = x0[7 * e + 3]; s0.yaw = x0[7 * e + 4];
         s0.yr = x0[7 * e + 5]; s0.beta = x0[7 * e + 6];
+#if F1P_ST_COL
+        bool blocked;
+        rc[it.es] = F1P_ST_N(stmpc_one_rollout)<true>(F1P_ST_SRC_EXPR(e), ref + (size_t)e * 7 * (T + 1), cfg, k, s0, it.r, col, blocked);
+        if (blocked) rl[it.es] = F1P_K4_NONE;                        // (its cost is +inf: the pair loses to every unblocked item)
+#else
         rc[it.es] = F1P_ST_N(stmpc_one_rollout)<true>(F1P_ST_SRC_EXPR(e), ref + (size_t)e * 7 * (T + 1), cfg, k, s0, it.r);
+#endif
     }
 }
 
 __global__ __launch_bounds__(256) void F1P_ST_N(k_stmpc_refine_tp)(const double* __restrict__ x0, const double* __restrict__ ref, F1P_ST_CTL_PARAM,
                                                         f1p_stmpc_cfg cfg, const unsigned int* __restrict__ qcount, const StItem* __restrict__ items,
+#if F1P_ST_COL
+                                                        KmpcCol col, int32_t* __restrict__ rl,
+#endif
                                                         double* __restrict__ rc, float* __restrict__ dbg_ticks) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -358,6 +465,15 @@ __global__ __launch_bounds__(256) void F1P_ST_N(k_stmpc_refine_tp)(const double*
         }
         wave_lds_sync();
         F1P_STPH();
+#if F1P_ST_COL
+        // ---- 5b. lane t tests the points of step t -> t + 1 (x_t, y_t are stmpc_rollouts' own values); a ballot ORs the verdicts --------
+        bool blocked;
+        {
+            bool hit = false;
+            if (act) { const StXY p = o6[t], q = o6[t + 1]; hit = col.seg(p.x, p.y, q.x, q.y); }
+            blocked = __ballot(hit) != 0ull;
+        }
+#endif
         // ---- 6. cost rows ----------------------------------------------------------------------------------------------------------
         {
             const double p_dv = shfl_d(my_dv, lane > 0 ? lane - 1 : 0), p_a = shfl_d(my_a, lane > 0 ? lane - 1 : 0);
@@ -392,7 +508,11 @@ __global__ __launch_bounds__(256) void F1P_ST_N(k_stmpc_refine_tp)(const double*
                 if (q > 0) cost += cur.rd;
             }
             cost += cr[T].q;                                              // the terminal row (Qf)
+#if F1P_ST_COL
+            if (lane == 0) { rc[it.es] = blocked ? __builtin_huge_val() : cost; if (blocked) rl[it.es] = F1P_K4_NONE; }
+#else
             if (lane == 0) rc[it.es] = cost;
+#endif
         }
         wave_lds_sync();
 #ifdef F1P_ST_PHASES
@@ -408,6 +528,9 @@ __global__ __launch_bounds__(256) void F1P_ST_N(k_stmpc_decide)(const double* __
                                                       F1P_ST_CTL_PARAM, int E, f1p_stmpc_cfg cfg,
                                                       unsigned int* __restrict__ qcount, const int32_t* __restrict__ nlist, const int32_t* __restrict__ rl,
                                                       const double* __restrict__ rc,
+#if F1P_ST_COL
+                                                      KmpcCol col,
+#endif
                                                       double* __restrict__ steer, double* __restrict__ speed,
                                                       int32_t* __restrict__ best_idx, double* __restrict__ best_cost,
                                                       double* __restrict__ best_seq, int32_t* __restrict__ dbg_nref) {
@@ -419,12 +542,48 @@ __global__ __launch_bounds__(256) void F1P_ST_N(k_stmpc_decide)(const double* __
     const int e = blockIdx.x;
     if (e >= E) return;
     if (e == 0 && tid == 0) *qcount = 0u;                             // re-arm the queue for the next plan (F1P_ST_N(k_stmpc_refine) has finished)
+#if F1P_ST_COL
+    int n = nlist[e];
+#else
     const int n = nlist[e];
+#endif
     DynState s0;
     s0.x = x0[7 * e]; s0.y = x0[7 * e + 1]; s0.delta = x0[7 * e + 2]; s0.v = x0[7 * e + 3]; s0.yaw = x0[7 * e + 4];
     s0.yr = x0[7 * e + 5]; s0.beta = x0[7 * e + 6];
     F1P_ST_SRC_DECL(ce, e);
     double bc = __builtin_huge_val(); int bi = 0x7fffffff;
+#if F1P_ST_COL
+    if (n >= 0) {                                                     // a blocked item is (+inf, F1P_K4_NONE): it loses to every unblocked one
+        if (tid < n) {
+            bc = rc[(size_t)e * F1P_ST_MAX_REFINE + tid];
+            bi = rl[(size_t)e * F1P_ST_MAX_REFINE + tid];
+        }
+        block_argmin(bc, bi, red_d, red_i);
+        // every listed rollout blocked: the list holds the FREE minimum, which the position bound proves unblocked, so this is not expected --
+        // the ego is decided by the all-fp64 loop rather than declared blocked on the filter's word (workgroup-uniform)
+        if (bi == F1P_K4_NONE) { n = -1; bc = __builtin_huge_val(); __syncthreads(); }
+    }
+    if (n < 0) {
+        for (int q = tid; q < 7 * (T + 1); q += blockDim.x) sref[q] = ref[(size_t)e * 7 * (T + 1) + q];
+        __syncthreads();
+        const DynConst k = dyn_const(cfg);
+        if (fabs(cfg.max_steer) <= 1.0e4) F1P_ST_N(stmpc_rollouts)<true>(ce, sref, cfg, k, s0, tid, bc, bi, col);
+        else F1P_ST_N(stmpc_rollouts)<false>(ce, sref, cfg, k, s0, tid, bc, bi, col);
+        block_argmin(bc, bi, red_d, red_i);
+    }
+    if (bi == F1P_K4_NONE) {                                          // every rollout blocked (workgroup-uniform)
+        for (int q = tid; q < 2 * T; q += blockDim.x) {
+            if (best_seq) best_seq[(size_t)e * T * 2 + q] = 0.0;
+            F1P_ST_EMIT_BLOCKED(e, q)
+        }
+        if (tid == 0) {
+            steer[e] = 0.0; speed[e] = 0.0; best_idx[e] = -1;
+            if (best_cost) best_cost[e] = __builtin_huge_val();
+            if (dbg_nref) dbg_nref[e] = n;
+        }
+        return;
+    }
+#else
     if (n < 0) {                                                      // workgroup-uniform
         for (int q = tid; q < 7 * (T + 1); q += blockDim.x) sref[q] = ref[(size_t)e * 7 * (T + 1) + q];
         __syncthreads();
@@ -436,6 +595,7 @@ __global__ __launch_bounds__(256) void F1P_ST_N(k_stmpc_decide)(const double* __
         bi = rl[(size_t)e * F1P_ST_MAX_REFINE + tid];
     }
     block_argmin(bc, bi, red_d, red_i);
+#endif
     F1P_ST_EMIT_PRE(ce, bi)
     if (tid == 0) {
         double pdv = 0.0;
@@ -456,3 +616,4 @@ __global__ __launch_bounds__(256) void F1P_ST_N(k_stmpc_decide)(const double* __
         if (dbg_nref) dbg_nref[e] = n;
     }
 }
+#endif   // !F1P_ST_COL || F1P_ST_COL_MIXED

@@ -918,6 +918,12 @@ class Context:
         self._check(self.lib.f1p_stmpc_set_mode(self.h, 1 if mixed else 0, None if d_cost32 is None else d_cost32.ptr,
                                                 None if d_n_refined is None else d_n_refined.ptr))
 
+    def stmpc_set_collision(self, on=True, n_sub=1, n_sub_k=2):
+        """test the dynamic MPC's shooting rollouts against the occupancy grid (f1p_stmpc_set_collision): n_sub points per step of the
+        dynamic model, n_sub_k per step of stmpc_plan's kinematic branch; a blocked rollout cannot win; an ego whose rollouts are all
+        blocked gets best_idx -1, cost +inf, steer 0, speed 0, a zero sequence and a zero warm start.  Separate from kmpc_set_collision."""
+        self._check(self.lib.f1p_stmpc_set_collision(self.h, 1 if on else 0, int(n_sub), int(n_sub_k)))
+
     def stmpc_shoot_dev(self, d_x0, d_ref, d_controls, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost=None, d_best_seq=None):
         """Asynchronous launch on HBM-resident buffers: x0 [E][7], ref [E][7][T+1], controls f32 [E][T][2][R]."""
         p = lambda b: None if b is None else b.ptr   # noqa: E731

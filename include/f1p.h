@@ -604,7 +604,7 @@ int f1p_kmpc_set_groups(f1p_ctx* ctx, int32_t groups);
  * With the test on, the entry points above return an error and launch nothing when no grid is loaded (F1P_ESTATE), when an
  * oriented footprint is installed (f1p_set_footprint with n_discs > 0: this is a point / disc test, use f1p_inflate_grid;
  * F1P_ESTATE) or when f1p_kmpc_set_groups(> 0) is in force (F1P_ESTATE).  n_sub outside [1, 16]: F1P_EINVAL, nothing changes.
- * Not covered: f1p_kmpc_qp_*, f1p_stmpc_* (their kinematic branch included). */
+ * Not covered: f1p_kmpc_qp_*.  f1p_stmpc_* has a switch of its own, f1p_stmpc_set_collision; this one does not reach it. */
 int f1p_kmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub);
 /* The reference extraction's heading fix-up (calc_ref_trajectory_kinematic, kinematic_mpc.py:198-203: course headings more than
  * 4.5 rad from the vehicle's are folded by abs(. -+ 2 pi), IN PLACE and persistently on the caller's array).  on = 1 (default):
@@ -738,6 +738,32 @@ int f1p_stmpc_ref_batch(f1p_ctx* ctx, const double* states, int32_t E, int32_t h
  * bit-identical to mixed = 0 (plain fp64).  d_cost32 [E][R] f32 (-inf = untrusted) and d_n_refined [E] i32 (-1 = the ego fell back
  * to all fp64): device pointers, nullable test hooks. */
 int f1p_stmpc_set_mode(f1p_ctx* ctx, int32_t mixed, float* d_cost32, int32_t* d_n_refined);
+/* Occupancy test on the rollouts of the dynamic MPC's shooting solver; f1p_kmpc_set_collision's twin, with a state of
+ * its own: one context may run both planners with different settings.
+ * on = 0 (default): rollouts are not tested, and the launch path selects the kernels it selects without this call.  on = 1: a rollout of
+ * f1p_stmpc_plan_* / f1p_stmpc_shoot_* whose tested points touch an occupied cell cannot win.  n_sub in [1, 16]: points tested per step
+ * of the dynamic model (a step covers at most max_speed * dt = 0.15 m); n_sub_k in [1, 16]: per step of f1p_stmpc_plan_batch's
+ * kinematic branch (TK steps of DTK = 0.1 s).
+ * Tested points (dynamic branch): with p_0 .. p_T the (x, y) of the states the fp64 rollout visits under the APPLIED controls (dv and a
+ * clamped to their bounds, dv to pdv +- max_steer_v for t > 0), for t = 0 .. T-1 and j = 1 .. n_sub the point
+ * p_t + (p_{t+1} - p_t) * ((double)j / (double)n_sub), per coordinate in fp64 in that order; j = n_sub is p_{t+1} itself; p_0 is not
+ * tested.  The kinematic branch: f1p_kmpc_set_collision's rule with n_sub_k.
+ * Cell rule: f1p_kmpc_set_collision's -- the ACTIVE bitmap (f1p_inflate_grid(r) makes it a disc test); outside the image or a
+ * non-finite coordinate is occupied.
+ * Decision: first minimum by rollout index over the unblocked rollouts (NaN costs as without the test).  Every rollout blocked:
+ * best_idx = -1, best_cost = +inf, steer = 0, speed = 0, best_seq all zero, the ego's warm-start row zero; its warm-start tag stays
+ * the branch's own.  A blocked ego has no effect on any other ego.
+ * f1p_stmpc_plan_* in the mixed mode runs an f32 filter that only decides what cannot win (its tested points looked up in the clearance
+ * map; used while the derived f32 position bound, with 5x headroom, stays below one cell -- otherwise plain fp64); outputs are
+ * bit-identical to f1p_stmpc_set_mode(0).  f1p_stmpc_shoot_* (streamed controls) with the test on are evaluated in plain fp64 WHATEVER
+ * f1p_stmpc_set_mode says; with the same controls they equal f1p_stmpc_plan_dev bit for bit (f1p_stmpc_gen_controls_dev).  The
+ * kinematic branch runs f1p_kmpc_plan_*'s schedule with the test (k_kmpc_plan_gen_idx_col) under f1p_kmpc_set_mode.
+ * With the test on, f1p_stmpc_plan_dev, f1p_stmpc_plan_batch, f1p_stmpc_shoot_dev and f1p_stmpc_shoot_batch return an error, launch
+ * nothing and leave the warm-start tags alone when no grid is loaded (F1P_ESTATE), when an oriented footprint is installed
+ * (f1p_set_footprint with n_discs > 0; F1P_ESTATE) or, f1p_stmpc_plan_batch only, when f1p_kmpc_set_groups(> 0) is in force
+ * (F1P_ESTATE).  A count outside [1, 16]: F1P_EINVAL, the switch keeps its state.
+ * Not covered: f1p_stmpc_qp_*. */
+int f1p_stmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub, int32_t n_sub_k);
 int f1p_stmpc_shoot_batch(f1p_ctx* ctx, const double* x0, const double* ref, const float* controls, int32_t E,
                           const f1p_stmpc_cfg* cfg, double* steer, double* speed, int32_t* best_idx, double* best_cost,
                           double* best_seq);
