@@ -1,0 +1,186 @@
+"""What the six drop-in planner classes share: the lazily created context, the reference's waypoint check, the track-set checks, the
+occupancy map of set_map / load_map, and the configuration checks and cfg builders of the two MPC planners."""
+import os
+
+import numpy as np
+
+from . import _abi
+from .runtime import Context
+
+NO_WAYPOINTS = 'Please set waypoints to track during planner instantiation or when calling plan()'
+
+
+class Planner:
+    """Base of the planner classes.  A class keeps `waypoints`, `_device` and `_ctx` (None until the first GPU call)."""
+
+    def _context(self):
+        if self._ctx is None:
+            self._ctx = Context(self._device if self._device is not None else int(os.environ.get("LOCAL_RANK", "0")))
+            self._on_context(self._ctx)
+        return self._ctx
+
+    def _on_context(self, ctx):
+        """called once, with the context just created"""
+
+    def _take_waypoints(self, waypoints, min_cols, message, asarray=False):
+        """The reference's validation (pure_pursuit.py:100-106 and its siblings): a given array is checked and kept, none needs one kept
+        earlier.  asarray: read the shape of np.asarray(waypoints) (the MPC planners, whose courses are lists of columns) instead of
+        waypoints.shape (the trackers)."""
+        if waypoints is not None:
+            shape = np.asarray(waypoints).shape if asarray else waypoints.shape
+            if len(shape) != 2 or shape[1] < min_cols:
+                raise ValueError(message)
+            self.waypoints = waypoints
+        elif self.waypoints is None:
+            raise ValueError(NO_WAYPOINTS)
+
+    def _bind_waypoints(self, waypoints, min_cols, message):
+        """_take_waypoints, then the waypoints on the context (uploaded when they changed) -> the context"""
+        self._take_waypoints(waypoints, min_cols, message)
+        ctx = self._context()
+        ctx.set_waypoints_cached(self.waypoints)
+        return ctx
+
+    def _bind_tracks(self, tracks, track_ids, min_cols):
+        """_check_tracks, then the track set on the context (uploaded when it changed) -> the context"""
+        _check_tracks(tracks, track_ids, min_cols)
+        ctx = self._context()
+        ctx.set_tracks_cached(tracks)
+        return ctx
+
+
+def _check_tracks(tracks, track_ids, min_cols):
+    """the per-vehicle waypoint validation of the reference (pure_pursuit.py:100-102, stanley.py:131-132, lqr.py:195-196) for every track"""
+    if track_ids is None:
+        raise ValueError("tracks needs track_ids: one track index per ego")
+    if len(tracks) == 0:
+        raise ValueError("tracks must hold at least one waypoint array")
+    for t in tracks:
+        if len(np.shape(t)) != 2 or np.shape(t)[1] < min_cols:
+            raise ValueError(f'Waypoints needs to be a (Nxm), m >= {min_cols}, numpy array!')
+
+
+def _course_columns(path):
+    """an MPC course [x, y, yaw, v] (four 1-D arrays or an array [4, N], kinematic_mpc.py:479-482) as (x, y, v, yaw) columns"""
+    cx, cy, cyaw, sp = (np.asarray(path[k], dtype=np.float64) for k in range(4))
+    return np.column_stack([cx, cy, sp, cyaw])
+
+
+def _track_columns(tracks, track_ids):
+    """ValueError before anything touches the GPU; -> the MPC courses as (x, y, v, yaw) columns"""
+    if track_ids is None:
+        raise ValueError("tracks needs track_ids: one track index per ego")
+    if len(tracks) == 0:
+        raise ValueError("tracks must hold at least one course")
+    cols = []
+    for path in tracks:
+        if len(path) < 4:
+            raise ValueError("every track must hold [x, y, yaw, v]")
+        cols.append(_course_columns(path))
+    return cols
+
+
+class OccupancyMap:
+    """set_map / load_map of LatticePlanner, KMPCPlanner and STMPCPlanner: the map is kept on the host and installed on the planner's
+    context when there is one, or when it is created."""
+    _map = None                            # (img u8, resolution, (ox, oy), occupied_below) of set_map
+    _inflate = 0.0
+
+    def set_map(self, image, resolution, origin, occupied_thresh=0.65, negate=0, inflate=0.0):
+        """Occupancy image in the ROS map_server layout (examples/control/Spielberg_map.yaml:1-6): u8 [h, w], row 0 at
+        the top, `origin` = world (x, y[, yaw]) of the lower-left pixel.  A cell is occupied when its occupancy
+        probability (255 - v)/255 (v/255 if negate) exceeds occupied_thresh.  `inflate` (metres) dilates the occupied set by
+        a disc on the device (distance-transform preprocessor), turning the point test -- the lattice's per station, mpc_config.COLLISION's
+        per rollout point -- into a disc test: e.g. 0.155 for the half width of the reference's 0.58 m x 0.31 m vehicle
+        (kinematic_mpc.py:60-61)."""
+        image = np.asarray(image)
+        if image.ndim != 2:
+            raise ValueError("map image must be 2-D")
+        if len(origin) > 2 and abs(origin[2]) > 1e-12:
+            raise ValueError("map origin yaw must be 0")
+        img = image.astype(np.uint8)
+        if negate:
+            img = 255 - img
+        occupied_below = int(np.ceil(255.0 * (1.0 - occupied_thresh)))      # v < 255 (1 - thresh)  <=>  p > thresh
+        self._map = (np.ascontiguousarray(img), float(resolution), (float(origin[0]), float(origin[1])), occupied_below)
+        self._inflate = float(inflate)
+        self._map_changed()
+        if self._ctx is not None:
+            self._install_map(self._ctx)
+
+    def load_map(self, yaml_path, inflate=0.0):
+        """Read a ROS map_server YAML + image (examples/control/Spielberg_map.yaml) and install it as the occupancy grid."""
+        from .io import load_map
+        m = load_map(yaml_path)
+        self.set_map(m["image"], m["resolution"], m["origin"], occupied_thresh=m["occupied_thresh"], negate=0, inflate=inflate)   # negate already applied
+        return m
+
+    def _map_changed(self):
+        """called by set_map once the new map is kept, before it goes to the context"""
+
+    def _install_map(self, ctx):
+        ctx.set_grid(*self._map)
+        if self._inflate > 0.0:
+            ctx.inflate_grid(self._inflate)
+
+    def _on_context(self, ctx):
+        if self._map is not None:
+            self._install_map(ctx)
+
+
+# ---- shared by KMPCPlanner and STMPCPlanner ---------------------------------------------------------------------------------------------
+SOLVERS = ("shooting", "qp")
+
+
+def _diag(m):
+    m = np.asarray(m.todense()) if hasattr(m, "todense") else np.asarray(m)
+    return np.diag(m) if m.ndim == 2 else m
+
+
+def check_solver(c, weights, substeps, tk_within_t=False):
+    """ValueError before anything touches the GPU: an unknown SOLVER, weights the QP path does not take (diagonal only), a COLLISION
+    setting without meaning.  weights: ((mpc_config field, size), ...) of the QP's weight matrices; substeps: the fields that count tested
+    points per step; tk_within_t: the QP also needs TK <= T (STMPCPlanner)."""
+    if c.SOLVER not in SOLVERS:
+        raise ValueError(f"mpc_config.SOLVER must be one of {SOLVERS}, not {c.SOLVER!r}")
+    if c.SOLVER == "qp":
+        for name, n in weights:
+            w = getattr(c, name)
+            w = np.asarray(w.todense() if hasattr(w, "todense") else w, dtype=np.float64)
+            if w.shape != (n, n) or np.any(w - np.diag(np.diag(w)) != 0):
+                raise ValueError(f"SOLVER='qp' takes diagonal {n}x{n} weights only; mpc_config.{name} is not")
+        if tk_within_t and c.TK > c.T:
+            raise ValueError("SOLVER='qp' needs TK <= T (the reference's kinematic branch would linearise about a cut-short prediction)")
+    if c.COLLISION:
+        if c.SOLVER == "qp":
+            raise ValueError("mpc_config.COLLISION tests the shooting solver's rollouts; SOLVER='qp' has none")
+        for name in substeps:
+            if not 1 <= int(getattr(c, name)) <= 16:
+                raise ValueError(f"mpc_config.{name} must be in [1, 16], not {getattr(c, name)!r}")
+
+
+def qp_opts(c):
+    return _abi.kmpc_qp_opts(max_iter=c.QP_MAX_ITER, tol=c.QP_TOL)
+
+
+def kin_cfg_struct(c, n_rollouts=None):
+    """the kinematic model's f1p_kmpc_cfg from either mpc_config (dense, sparse or vector weights)"""
+    return _abi.kmpc_cfg(horizon=c.TK, n_rollouts=n_rollouts or c.N_ROLLOUTS, dt=c.DTK, wheelbase=c.WB, max_steer=c.MAX_STEER,
+                         max_dsteer=c.MAX_DSTEER, max_speed=c.MAX_SPEED, min_speed=c.MIN_SPEED, max_accel=c.MAX_ACCEL,
+                         q=_diag(c.Qk), qf=_diag(c.Qfk), r=_diag(c.Rk), rd=_diag(c.Rdk))
+
+
+class MPCPlanner(OccupancyMap, Planner):
+    """Base of KMPCPlanner and STMPCPlanner.  A class names its mpc_config's QP weights and COLLISION substep fields."""
+    _QP_WEIGHTS = ()                       # ((mpc_config field, size), ...)
+    _SUBSTEPS = ()
+    _TK_WITHIN_T = False
+
+    def _check_solver(self):
+        check_solver(self.config, self._QP_WEIGHTS, self._SUBSTEPS, self._TK_WITHIN_T)
+
+    def _check_collision(self):
+        """ValueError before anything touches the GPU: the checks of check_solver, and COLLISION without a map"""
+        self._check_solver()
+        if self.config.COLLISION and self._map is None:
+            raise ValueError("mpc_config.COLLISION needs an occupancy grid: call set_map / load_map first")

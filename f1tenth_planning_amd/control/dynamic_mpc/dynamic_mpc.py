@@ -13,15 +13,15 @@ warm-started like the reference from the previous solution (unshifted, with its 
 mpc_config.COLLISION = True (shooting only) tests every rollout of both branches against the occupancy grid installed with set_map /
 load_map: a rollout that touches an occupied cell cannot win (f1p_stmpc_set_collision).
 """
-import os
 import warnings
 from dataclasses import dataclass, field
 
 import numpy as np
 
 from ... import _abi
+from ..._planner import MPCPlanner, _course_columns, _diag, _track_columns, kin_cfg_struct, qp_opts
 from ...runtime import Context
-from ..kinematic_mpc.kinematic_mpc import State, _OccupancyMap  # noqa: F401  (same 7-field dataclass, :89-98; set_map / load_map)
+from ..kinematic_mpc.kinematic_mpc import State  # noqa: F401  (same 7-field dataclass, :89-98)
 
 
 @dataclass
@@ -71,35 +71,7 @@ class mpc_config:
     COLLISION_SUBSTEPS_K: int = 2  # ... per step of the kinematic branch, 1 .. 16 (up to V_KS * DTK + acceleration)
 
 
-def _diag(m):
-    m = np.asarray(m.todense()) if hasattr(m, "todense") else np.asarray(m)
-    return np.diag(m) if m.ndim == 2 else m
-
-
-_SOLVERS = ("shooting", "qp")
-
-
-def _check_solver(c: mpc_config):
-    """ValueError before anything touches the GPU: an unknown SOLVER, or weights the QP path does not take (diagonal only)"""
-    if c.SOLVER not in _SOLVERS:
-        raise ValueError(f"mpc_config.SOLVER must be one of {_SOLVERS}, not {c.SOLVER!r}")
-    if c.SOLVER == "qp":
-        for name, n in (("R", 2), ("Rd", 2), ("Q", 7), ("Qf", 7), ("Rk", 2), ("Rdk", 2), ("Qk", 4), ("Qfk", 4)):
-            w = getattr(c, name)
-            w = np.asarray(w.todense() if hasattr(w, "todense") else w, dtype=np.float64)
-            if w.shape != (n, n) or np.any(w - np.diag(np.diag(w)) != 0):
-                raise ValueError(f"SOLVER='qp' takes diagonal {n}x{n} weights only; mpc_config.{name} is not")
-        if c.TK > c.T:
-            raise ValueError("SOLVER='qp' needs TK <= T (the reference's kinematic branch would linearise about a cut-short prediction)")
-    if c.COLLISION:
-        if c.SOLVER == "qp":
-            raise ValueError("mpc_config.COLLISION tests the shooting solver's rollouts; SOLVER='qp' has none")
-        for name in ("COLLISION_SUBSTEPS", "COLLISION_SUBSTEPS_K"):
-            if not 1 <= int(getattr(c, name)) <= 16:
-                raise ValueError(f"mpc_config.{name} must be in [1, 16], not {getattr(c, name)!r}")
-
-
-class STMPCPlanner(_OccupancyMap):
+class STMPCPlanner(MPCPlanner):
     """
     Single-track MPC controller (random shooting on the GPU).  All poses are in the map frame.
 
@@ -108,6 +80,9 @@ class STMPCPlanner(_OccupancyMap):
         config (mpc_config)
         params: mass, l_f, l_r, h_CoG, c_f, c_r, Iz, mu
     """
+    _QP_WEIGHTS = (("R", 2), ("Rd", 2), ("Q", 7), ("Qf", 7), ("Rk", 2), ("Rdk", 2), ("Qk", 4), ("Qfk", 4))
+    _SUBSTEPS = ("COLLISION_SUBSTEPS", "COLLISION_SUBSTEPS_K")
+    _TK_WITHIN_T = True
 
     def __init__(self, waypoints=None, config=mpc_config(),
                  params=np.array([3.74, 0.15875, 0.17145, 0.074, 4.718, 5.4562, 0.04712, 1.0489]), debug=False, device=None):
@@ -125,20 +100,7 @@ class STMPCPlanner(_OccupancyMap):
         self._batch_calls = 0
         self._map = None                   # (img u8, resolution, (ox, oy), occupied_below) of set_map
         self._inflate = 0.0
-        _check_solver(config)
-
-    def _check_collision(self):
-        """ValueError before anything touches the GPU: the checks of _check_solver, and COLLISION without a map"""
-        _check_solver(self.config)
-        if self.config.COLLISION and self._map is None:
-            raise ValueError("mpc_config.COLLISION needs an occupancy grid: call set_map / load_map first")
-
-    def _context(self):
-        if self._ctx is None:
-            self._ctx = Context(self._device if self._device is not None else int(os.environ.get("LOCAL_RANK", "0")))
-            if self._map is not None:
-                self._install_map(self._ctx)
-        return self._ctx
+        self._check_solver()
 
     def _collision_switch(self, ctx):
         """the planner's context follows mpc_config: the stmpc switch (plan_batch, plan()'s dynamic branch) and, for plan()'s kinematic
@@ -150,16 +112,10 @@ class STMPCPlanner(_OccupancyMap):
             ctx.kmpc_set_collision(on, int(c.COLLISION_SUBSTEPS_K) if on else 1)
 
     def _bind(self, waypoints):
-        if waypoints is not None:
-            w = np.asarray(waypoints)
-            if len(w.shape) != 2 or w.shape[1] < 3:
-                raise ValueError("Waypoints needs to be a (Nxm), m >= 3, numpy array!")
-            self.waypoints = waypoints
-        elif self.waypoints is None:
-            raise ValueError("Please set waypoints to track during planner instantiation or when calling plan()")
-        cx, cy, cyaw, sp = (np.asarray(self.waypoints[k], dtype=np.float64) for k in range(4))
+        self._take_waypoints(waypoints, 3, "Waypoints needs to be a (Nxm), m >= 3, numpy array!", asarray=True)
+        cols = _course_columns(self.waypoints)
         ctx = self._context()
-        ctx.set_waypoints_cached(np.column_stack([cx, cy, sp, cyaw]), cols=(0, 1, 2, 3))
+        ctx.set_waypoints_cached(cols, cols=(0, 1, 2, 3))
         return ctx
 
     def _dyn_cfg(self):
@@ -169,10 +125,7 @@ class STMPCPlanner(_OccupancyMap):
                               q=_diag(c.Q), qf=_diag(c.Qf), r=_diag(c.R), rd=_diag(c.Rd), params=self.vehicle_params)
 
     def _kin_cfg(self):
-        c = self.config
-        return _abi.kmpc_cfg(horizon=c.TK, n_rollouts=c.N_ROLLOUTS, dt=c.DTK, wheelbase=c.WB, max_steer=c.MAX_STEER,
-                             max_dsteer=c.MAX_DSTEER, max_speed=c.MAX_SPEED, min_speed=c.MIN_SPEED, max_accel=c.MAX_ACCEL,
-                             q=_diag(c.Qk), qf=_diag(c.Qfk), r=_diag(c.Rk), rd=_diag(c.Rdk))
+        return kin_cfg_struct(self.config)
 
     def _sample(self, T, R, s0, s1, lim0, lim1):
         rng = np.random.default_rng([self.config.SEED, self._calls])
@@ -189,7 +142,7 @@ class STMPCPlanner(_OccupancyMap):
         output map (:1112-1117, :1205-1207), new warm start."""
         c = self.config
         return ctx.stmpc_qp_plan(x0, self._dyn_cfg(), self._kin_cfg(), v_ks=c.V_KS, dl=c.dl, dlk=c.dlk,
-                                 opts=_abi.kmpc_qp_opts(max_iter=c.QP_MAX_ITER, tol=c.QP_TOL), want_u=want_u)
+                                 opts=qp_opts(c), want_u=want_u)
 
     def _shoot(self, ctx, x0, want_u=True):
         """One C call per plan (f1p_stmpc_plan_batch): per ego the branch (:168), reference extraction (:195-276), R control sequences
@@ -231,31 +184,15 @@ class STMPCPlanner(_OccupancyMap):
             self._collision_switch(ctx)
             return self._shoot(ctx, np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 7), want_u=want_u)
         if tracks is not None:
-            cols = self._track_columns(tracks, track_ids)
+            cols = _track_columns(tracks, track_ids)
             ctx = self._context()
             ctx.set_tracks_cached(cols, cols=(0, 1, 2, 3))
             x0 = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 7)
             c = self.config
             return ctx.stmpc_qp_plan_tracks(x0, Context._ids(track_ids, x0.shape[0]), self._dyn_cfg(), self._kin_cfg(), v_ks=c.V_KS,
-                                            dl=c.dl, dlk=c.dlk, opts=_abi.kmpc_qp_opts(max_iter=c.QP_MAX_ITER, tol=c.QP_TOL),
-                                            want_u=want_u)
+                                            dl=c.dl, dlk=c.dlk, opts=qp_opts(c), want_u=want_u)
         ctx = self._bind(waypoints)
         return self._qp(ctx, np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 7), want_u=want_u)
-
-    @staticmethod
-    def _track_columns(tracks, track_ids):
-        """ValueError before anything touches the GPU; -> the courses as (x, y, v, yaw) columns, _bind's order"""
-        if track_ids is None:
-            raise ValueError("tracks needs track_ids: one track index per ego")
-        if len(tracks) == 0:
-            raise ValueError("tracks must hold at least one course")
-        cols = []
-        for path in tracks:
-            if len(path) < 4:
-                raise ValueError("every track must hold [x, y, yaw, v]")
-            cx, cy, cyaw, sp = (np.asarray(path[k], dtype=np.float64) for k in range(4))
-            cols.append(np.column_stack([cx, cy, sp, cyaw]))
-        return cols
 
     def reset(self):
         """forget the warm start (a new episode)"""

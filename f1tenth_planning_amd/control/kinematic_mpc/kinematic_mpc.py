@@ -16,13 +16,14 @@ a batched fp64 interior-point kernel (csrc/k_kmpc_qp.hip), warm-started like the
 mpc_config.COLLISION = True (shooting only) tests every rollout against the occupancy grid installed with set_map / load_map: a rollout
 that touches an occupied cell cannot win (f1p_kmpc_set_collision).
 """
-import os
 import warnings
 from dataclasses import dataclass, field
 
 import numpy as np
 
 from ... import _abi
+from ..._planner import MPCPlanner, _track_columns, qp_opts
+from ..._planner import kin_cfg_struct as _cfg_struct
 from ...runtime import Context
 
 
@@ -81,75 +82,7 @@ def _fold_cyaw_inplace(cyaw, yaw):
     cyaw[m] = np.abs(cyaw[m] + (2 * np.pi))
 
 
-_SOLVERS = ("shooting", "qp")
-
-
-def _check_solver(c: mpc_config):
-    """ValueError before anything touches the GPU: an unknown SOLVER, or weights the QP path does not take (diagonal only)"""
-    if c.SOLVER not in _SOLVERS:
-        raise ValueError(f"mpc_config.SOLVER must be one of {_SOLVERS}, not {c.SOLVER!r}")
-    if c.SOLVER == "qp":
-        for name in ("Rk", "Rdk", "Qk", "Qfk"):
-            w = np.asarray(getattr(c, name), dtype=np.float64)
-            n = 2 if name in ("Rk", "Rdk") else 4
-            if w.shape != (n, n) or np.any(w - np.diag(np.diag(w)) != 0):
-                raise ValueError(f"SOLVER='qp' takes diagonal {n}x{n} weights only; mpc_config.{name} is not")
-    if c.COLLISION:
-        if c.SOLVER == "qp":
-            raise ValueError("mpc_config.COLLISION tests the shooting solver's rollouts; SOLVER='qp' has none")
-        if not 1 <= int(c.COLLISION_SUBSTEPS) <= 16:
-            raise ValueError(f"mpc_config.COLLISION_SUBSTEPS must be in [1, 16], not {c.COLLISION_SUBSTEPS!r}")
-
-
-def _qp_opts(c: mpc_config):
-    return _abi.kmpc_qp_opts(max_iter=c.QP_MAX_ITER, tol=c.QP_TOL)
-
-
-def _cfg_struct(c: mpc_config, n_rollouts=None):
-    return _abi.kmpc_cfg(horizon=c.TK, n_rollouts=n_rollouts or c.N_ROLLOUTS, dt=c.DTK, wheelbase=c.WB, max_steer=c.MAX_STEER,
-                         max_dsteer=c.MAX_DSTEER, max_speed=c.MAX_SPEED, min_speed=c.MIN_SPEED, max_accel=c.MAX_ACCEL,
-                         q=np.diag(c.Qk), qf=np.diag(c.Qfk), r=np.diag(c.Rk), rd=np.diag(c.Rdk))
-
-
-class _OccupancyMap:
-    """set_map / load_map of the MPC planners (KMPCPlanner, STMPCPlanner): the map is kept on the host and installed on the planner's
-    context when there is one.  The class keeps `_map`, `_inflate` and `_ctx`."""
-    _map = None                            # (img u8, resolution, (ox, oy), occupied_below) of set_map
-    _inflate = 0.0
-
-    def set_map(self, image, resolution, origin, occupied_thresh=0.65, negate=0, inflate=0.0):
-        """Occupancy image in the ROS map_server layout, with LatticePlanner.set_map's meaning: u8 [h, w], row 0 at the top, `origin` =
-        world (x, y[, yaw]) of the lower-left pixel; a cell is occupied when its occupancy probability (255 - v)/255 (v/255 if negate)
-        exceeds occupied_thresh.  `inflate` (metres) dilates the occupied set by a disc on the device, which turns the point test of
-        mpc_config.COLLISION into a disc test -- e.g. 0.155 for the half width of the reference's vehicle."""
-        image = np.asarray(image)
-        if image.ndim != 2:
-            raise ValueError("map image must be 2-D")
-        if len(origin) > 2 and abs(origin[2]) > 1e-12:
-            raise ValueError("map origin yaw must be 0")
-        img = image.astype(np.uint8)
-        if negate:
-            img = 255 - img
-        occupied_below = int(np.ceil(255.0 * (1.0 - occupied_thresh)))      # v < 255 (1 - thresh)  <=>  p > thresh
-        self._map = (np.ascontiguousarray(img), float(resolution), (float(origin[0]), float(origin[1])), occupied_below)
-        self._inflate = float(inflate)
-        if self._ctx is not None:
-            self._install_map(self._ctx)
-
-    def load_map(self, yaml_path, inflate=0.0):
-        """Read a ROS map_server YAML + image and install it as the occupancy grid (LatticePlanner.load_map)."""
-        from ...io import load_map
-        m = load_map(yaml_path)
-        self.set_map(m["image"], m["resolution"], m["origin"], occupied_thresh=m["occupied_thresh"], negate=0, inflate=inflate)   # negate already applied
-        return m
-
-    def _install_map(self, ctx):
-        ctx.set_grid(*self._map)
-        if self._inflate > 0.0:
-            ctx.inflate_grid(self._inflate)
-
-
-class KMPCPlanner(_OccupancyMap):
+class KMPCPlanner(MPCPlanner):
     """
     Kinematic MPC controller (random shooting on the GPU).  All poses are in the map frame.
 
@@ -158,6 +91,8 @@ class KMPCPlanner(_OccupancyMap):
             (examples/control/kinematic_mpc.py:44-45)
         config (mpc_config)
     """
+    _QP_WEIGHTS = (("Rk", 2), ("Rdk", 2), ("Qk", 4), ("Qfk", 4))
+    _SUBSTEPS = ("COLLISION_SUBSTEPS",)
 
     def __init__(self, waypoints=None, config=mpc_config(),
                  params=np.array([3.74, 0.15875, 0.17145, 0.074, 4.718, 5.4562, 0.04712, 1.0489]), debug=False, device=None):
@@ -175,21 +110,7 @@ class KMPCPlanner(_OccupancyMap):
         self._trk_qp_warm = None           # the QP warm start of the track-set path (plan_batch(tracks=...)): u [E, T, 2] fp64
         self._map = None                   # (img u8, resolution, (ox, oy), occupied_below) of set_map
         self._inflate = 0.0
-        _check_solver(config)
-
-    def _check_collision(self):
-        """ValueError before anything touches the GPU: COLLISION without a map (the other COLLISION checks: _check_solver)"""
-        _check_solver(self.config)
-        if self.config.COLLISION and self._map is None:
-            raise ValueError("mpc_config.COLLISION needs an occupancy grid: call set_map / load_map first")
-
-    def _context(self):
-        if self._ctx is None:
-            dev = self._device if self._device is not None else int(os.environ.get("LOCAL_RANK", "0"))
-            self._ctx = Context(dev)
-            if self._map is not None:
-                self._install_map(self._ctx)
-        return self._ctx
+        self._check_solver()
 
     def _collision_switch(self, ctx):
         c = self.config
@@ -200,13 +121,7 @@ class KMPCPlanner(_OccupancyMap):
         """fold_yaw: the vehicle heading of a single-vehicle call -- the course headings are then folded in place on the caller's
         array like the reference does (persistent state, :198-203) and the kernel's own stateless per-ego fold is switched off;
         None (batches): the kernel folds the gathered values per ego and the caller's array is left alone."""
-        if waypoints is not None:
-            w = np.asarray(waypoints)
-            if len(w.shape) != 2 or w.shape[1] < 3:
-                raise ValueError("Waypoints needs to be a (Nxm), m >= 3, numpy array!")     # :131-132
-            self.waypoints = waypoints
-        elif self.waypoints is None:
-            raise ValueError("Please set waypoints to track during planner instantiation or when calling plan()")
+        self._take_waypoints(waypoints, 3, "Waypoints needs to be a (Nxm), m >= 3, numpy array!", asarray=True)     # :131-132
         path = self.waypoints
         cx, cy, cyaw, sp = (np.asarray(path[k], dtype=np.float64) for k in range(4))             # :479-482
         ctx = self._context()
@@ -263,7 +178,7 @@ class KMPCPlanner(_OccupancyMap):
         """One C call per plan (f1p_kmpc_qp_plan_batch): reference extraction (:162-206), linearisation about the previous solution held
         on the device (unshifted, :462-468), the QP of :283-450 solved to tolerance, output map (:500-505), new warm start."""
         c = self.config
-        return ctx.kmpc_qp_plan(x0, _cfg_struct(c), dl=c.dlk, opts=_qp_opts(c), want_u=want_u)
+        return ctx.kmpc_qp_plan(x0, _cfg_struct(c), dl=c.dlk, opts=qp_opts(c), want_u=want_u)
 
     def reset(self):
         """forget the warm starts (shooting and QP) and restart the sampler's call counter (a new episode)"""
@@ -301,16 +216,7 @@ class KMPCPlanner(_OccupancyMap):
         return ctx.kmpc_shoot(x0, ref, controls, cfg)
 
     def _plan_tracks(self, x0, tracks, track_ids, controls, want_seq):
-        if track_ids is None:
-            raise ValueError("tracks needs track_ids: one track index per ego")
-        if len(tracks) == 0:
-            raise ValueError("tracks must hold at least one course")
-        cols = []
-        for path in tracks:
-            if len(path) < 4:
-                raise ValueError("every track must hold [x, y, yaw, v]")
-            cx, cy, cyaw, sp = (np.asarray(path[k], dtype=np.float64) for k in range(4))             # :479-482
-            cols.append(np.column_stack([cx, cy, sp, cyaw]))
+        cols = _track_columns(tracks, track_ids)
         ctx = self._context()
         self._collision_switch(ctx)
         ctx.kmpc_set_yaw_fixup(True)                           # a batch: per-ego fold of the gathered headings, the courses stay as given
@@ -334,7 +240,7 @@ class KMPCPlanner(_OccupancyMap):
                 d["oa"].upload(np.ascontiguousarray(warm[:, :, 0]))
                 d["od"].upload(np.ascontiguousarray(warm[:, :, 1]))
             ctx.kmpc_qp_dev(d["x0"], d["ref"], E, _cfg_struct(c), d["steer"], d["speed"], d["status"],
-                            d["oa"] if warm is not None else None, d["od"] if warm is not None else None, opts=_qp_opts(c), d_u=d["u"],
+                            d["oa"] if warm is not None else None, d["od"] if warm is not None else None, opts=qp_opts(c), d_u=d["u"],
                             d_obj=d["obj"])
             out = dict(steer=d["steer"].download(np.float64, E), speed=d["speed"].download(np.float64, E),
                        status=d["status"].download(np.int32, E), obj=d["obj"].download(np.float64, E))

@@ -5,15 +5,12 @@ front-axle nearest-point search, the 4x4 Riccati iteration (solve_lqr, utils/uti
 run in libf1p.so (csrc/k_controllers.hip).  The planner keeps the previous lateral and heading errors like the
 reference does (lqr.py:57-58, 100-101); `plan_batch` carries one such pair per ego.
 """
-import os
-
 import numpy as np
 
-from ...runtime import Context
-from ..pure_pursuit.pure_pursuit import _check_tracks
+from ..._planner import Planner
 
 
-class LQRPlanner():
+class LQRPlanner(Planner):
     """
     Lateral controller using LQR.
 
@@ -32,18 +29,13 @@ class LQRPlanner():
         self._batch_err = None
 
     def _bind(self, waypoints):
-        if waypoints is not None:
-            if len(waypoints.shape) != 2 or waypoints.shape[1] < 5:
-                raise ValueError('Waypoints needs to be a (Nxm), m >= 5, numpy array!')          # lqr.py:195-196
-            self.waypoints = waypoints
-        elif self.waypoints is None:
-            raise ValueError('Please set waypoints to track during planner instantiation or when calling plan()')
-        if np.asarray(self.waypoints).shape[1] < 5:
-            raise ValueError('Waypoints needs to be a (Nxm), m >= 5, numpy array!')
-        if self._ctx is None:
-            self._ctx = Context(self._device if self._device is not None else int(os.environ.get("LOCAL_RANK", "0")))
-        self._ctx.set_waypoints_cached(self.waypoints)
-        return self._ctx
+        message = 'Waypoints needs to be a (Nxm), m >= 5, numpy array!'          # lqr.py:195-196
+        self._take_waypoints(waypoints, 5, message)
+        if np.asarray(self.waypoints).shape[1] < 5:            # (waypoints of the constructor are not checked there)
+            raise ValueError(message)
+        ctx = self._context()
+        ctx.set_waypoints_cached(self.waypoints)
+        return ctx
 
     def plan(self, pose_x, pose_y, pose_theta, velocity, timestep=0.01, matrix_q_1=0.999, matrix_q_2=0.0, matrix_q_3=0.0066,
              matrix_q_4=0.0, matrix_r=0.75, iterations=50, eps=0.001, waypoints=None):
@@ -62,11 +54,7 @@ class LQRPlanner():
         tracks: K waypoint arrays [N_k x m], m >= 5, with track_ids [E]: ego e follows tracks[track_ids[e]] (an id outside [0, K):
         NaN steer / speed, near_idx -1, its error kept); `waypoints` is then not used."""
         if tracks is not None:
-            _check_tracks(tracks, track_ids, 5)
-            if self._ctx is None:
-                self._ctx = Context(self._device if self._device is not None else int(os.environ.get("LOCAL_RANK", "0")))
-            ctx = self._ctx
-            ctx.set_tracks_cached(tracks)
+            ctx = self._bind_tracks(tracks, track_ids, 5)
         else:
             ctx = self._bind(waypoints)
         states = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 4)

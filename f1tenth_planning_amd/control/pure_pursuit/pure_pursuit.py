@@ -10,10 +10,11 @@ import warnings
 import numpy as np
 
 from ... import _abi
-from ...runtime import Context
+from ..._planner import NO_WAYPOINTS, Planner, _check_tracks
+from ...runtime import MultiContext
 
 
-class PurePursuitPlanner():
+class PurePursuitPlanner(Planner):
     """
     Pure pursuit tracking controller (Coulter 1992).  All poses are in the map frame.
 
@@ -33,25 +34,9 @@ class PurePursuitPlanner():
         self._device = device
         self._ctx = None
 
-    def _context(self):
-        if self._ctx is None:
-            import os
-            dev = self._device if self._device is not None else int(os.environ.get("LOCAL_RANK", "0"))
-            self._ctx = Context(dev)
-        return self._ctx
-
-    def _bind_waypoints(self, waypoints):
+    def _bind(self, waypoints):
         # validation and error text of pure_pursuit.py:100-106
-        if waypoints is not None:
-            if len(waypoints.shape) != 2 or waypoints.shape[1] < 3:
-                raise ValueError('Waypoints needs to be a (Nxm), m >= 3, numpy array!')
-            self.waypoints = waypoints
-        else:
-            if self.waypoints is None:
-                raise ValueError('Please set waypoints to track during planner instantiation or when calling plan()')
-        ctx = self._context()
-        ctx.set_waypoints_cached(self.waypoints)
-        return ctx
+        return self._bind_waypoints(waypoints, 3, 'Waypoints needs to be a (Nxm), m >= 3, numpy array!')
 
     def _get_current_waypoint(self, lookahead_distance, position, theta):
         """The waypoint plan() steers towards (pure_pursuit.py:56-83): [x, y of the vertex after the look-ahead circle's first
@@ -59,7 +44,7 @@ class PurePursuitPlanner():
         is within max_reacquire; None otherwise.  One k_pure_pursuit launch: its (nearest index, look-ahead index, branch)
         outputs are exactly the reference's (i, i2, branch); look-ahead index -1 is the last row, as in numpy."""
         if self.waypoints is None:
-            raise ValueError('Please set waypoints to track during planner instantiation or when calling plan()')
+            raise ValueError(NO_WAYPOINTS)
         ctx = self._context()
         ctx.set_waypoints_cached(self.waypoints)
         out = ctx.pure_pursuit(np.array([[position[0], position[1], theta]], dtype=np.float64), lookahead_distance,
@@ -75,7 +60,7 @@ class PurePursuitPlanner():
         """
         Returns (steering_angle, speed) for one vehicle -- the order the reference code returns (:122).
         """
-        ctx = self._bind_waypoints(waypoints)
+        ctx = self._bind(waypoints)
         out = ctx.pure_pursuit(np.array([[pose_x, pose_y, pose_theta]], dtype=np.float64), lookahead_distance,
                                self.wheelbase, self.max_reacquire)
         if out["status"][0] == _abi.ST_NO_LOOKAHEAD:
@@ -99,7 +84,7 @@ class PurePursuitPlanner():
             ctx = self._context()
             ctx.set_tracks_cached(tracks)
             return ctx.pure_pursuit_tracks(poses, track_ids, lookahead_distance, self.wheelbase, self.max_reacquire)
-        ctx = self._bind_waypoints(waypoints)
+        ctx = self._bind(waypoints)
         if devices is not None:
             mc = self._multi(devices)
             mc.set_waypoints_cached(self.waypoints)
@@ -107,21 +92,9 @@ class PurePursuitPlanner():
         return ctx.pure_pursuit(poses, lookahead_distance, self.wheelbase, self.max_reacquire)
 
     def _multi(self, devices):
-        from ...runtime import MultiContext
         key = "all" if isinstance(devices, str) else tuple(int(d) for d in devices)
         if getattr(self, "_mc_key", None) != key:
             if getattr(self, "_mc", None) is not None:
                 self._mc.close()
             self._mc, self._mc_key = MultiContext(None if key == "all" else key), key
         return self._mc
-
-
-def _check_tracks(tracks, track_ids, min_cols):
-    """the per-vehicle waypoint validation of the reference (pure_pursuit.py:100-102, stanley.py:131-132, lqr.py:195-196) for every track"""
-    if track_ids is None:
-        raise ValueError("tracks needs track_ids: one track index per ego")
-    if len(tracks) == 0:
-        raise ValueError("tracks must hold at least one waypoint array")
-    for t in tracks:
-        if len(np.shape(t)) != 2 or np.shape(t)[1] < min_cols:
-            raise ValueError(f'Waypoints needs to be a (Nxm), m >= {min_cols}, numpy array!')

@@ -17,17 +17,17 @@ here is written down in DESIGN.md "Lattice semantics": goals and trajectories li
 tracked from pose (0, 0, 0) with look-ahead 0.8 and the commanded speed is the raceline speed at the nearest
 waypoint.
 """
-import os
 import warnings
 
 import numpy as np
 
 from ... import _abi
-from ...control.pure_pursuit.pure_pursuit import PurePursuitPlanner, _check_tracks
-from ...runtime import Context
+from ..._planner import OccupancyMap, Planner, _check_tracks
+from ...control.pure_pursuit.pure_pursuit import PurePursuitPlanner
+from ...runtime import MultiContext
 
 
-class LatticePlanner():
+class LatticePlanner(OccupancyMap, Planner):
     """
     Sampling-based local planner: goal grid -> G1 clothoids -> cost -> argmin -> pure-pursuit tracking.
     """
@@ -108,29 +108,15 @@ class LatticePlanner():
                 raise ValueError("generator must be 'clothoid' or 'cubic'")
             self.generator = generator
 
-    def set_map(self, image, resolution, origin, occupied_thresh=0.65, negate=0, inflate=0.0):
-        """Occupancy image in the ROS map_server layout (examples/control/Spielberg_map.yaml:1-6): u8 [h, w], row 0 at
-        the top, `origin` = world (x, y[, yaw]) of the lower-left pixel.  A cell is occupied when its occupancy
-        probability (255 - v)/255 (v/255 if negate) exceeds occupied_thresh.  `inflate` (metres) dilates the occupied set by
-        a disc on the device (distance-transform preprocessor), turning the per-station point test into a disc-footprint
-        test -- e.g. 0.155 for the half width of the reference's 0.58 m x 0.31 m vehicle (kinematic_mpc.py:60-61)."""
-        image = np.asarray(image)
-        if image.ndim != 2:
-            raise ValueError("map image must be 2-D")
-        if len(origin) > 2 and abs(origin[2]) > 1e-12:
-            raise ValueError("map origin yaw must be 0")
-        img = image.astype(np.uint8)
-        if negate:
-            img = 255 - img
-        occupied_below = int(np.ceil(255.0 * (1.0 - occupied_thresh)))      # v < 255 (1 - thresh)  <=>  p > thresh
-        self._map = (np.ascontiguousarray(img), float(resolution), (float(origin[0]), float(origin[1])), occupied_below)
-        self._inflate = float(inflate)
+    # set_map / load_map: OccupancyMap
+    def _map_changed(self):
         self._map_gen += 1
         self._foot = None                                    # a new map clears the footprint (f1p_set_grid does)
-        if self._ctx is not None:
-            self._ctx.set_grid(*self._map)
-            if self._inflate > 0.0:
-                self._ctx.inflate_grid(self._inflate)
+
+    def _install_map(self, ctx):
+        super()._install_map(ctx)
+        if self._foot:
+            ctx.set_footprint(*self._foot)
 
     def set_footprint(self, length=0.58, width=0.31, n_discs=3, center_offset=0.0):
         """Oriented footprint collision test: cover the length x width rectangle (the reference's vehicle, kinematic_mpc.py:60-61)
@@ -149,13 +135,6 @@ class LatticePlanner():
             self._mc.set_footprint(*self._foot)              # the multi-GPU replicas follow
             self._mc_map = (self._map_gen, self._inflate, self._foot)
         return self._foot
-
-    def load_map(self, yaml_path, inflate=0.0):
-        """Read a ROS map_server YAML + image (examples/control/Spielberg_map.yaml) and install it as the occupancy grid."""
-        from ...io import load_map
-        m = load_map(yaml_path)
-        self.set_map(m["image"], m["resolution"], m["origin"], occupied_thresh=m["occupied_thresh"], negate=0, inflate=inflate)   # negate already applied
-        return m
 
     # ---- reference methods ------------------------------------------------------------------------------------------
     def sample(self, pose_x, pose_y, pose_theta, velocity, waypoints):
@@ -187,28 +166,8 @@ class LatticePlanner():
         return self.selection_func(all_costs)
 
     # ---- planning ---------------------------------------------------------------------------------------------------
-    def _context(self):
-        if self._ctx is None:
-            dev = self._device if self._device is not None else int(os.environ.get("LOCAL_RANK", "0"))
-            self._ctx = Context(dev)
-            if self._map is not None:
-                self._ctx.set_grid(*self._map)
-                if self._inflate > 0.0:
-                    self._ctx.inflate_grid(self._inflate)
-                if getattr(self, "_foot", None):
-                    self._ctx.set_footprint(*self._foot)
-        return self._ctx
-
     def _bind(self, waypoints):
-        if waypoints is not None:
-            if len(waypoints.shape) != 2 or waypoints.shape[1] < 4:
-                raise ValueError('Waypoints needs to be a (Nxm), m >= 4, numpy array! (x, y, velocity, heading)')
-            self.waypoints = waypoints
-        elif self.waypoints is None:
-            raise ValueError('Please set waypoints to track during planner instantiation or when calling plan()')
-        ctx = self._context()
-        ctx.set_waypoints_cached(self.waypoints)
-        return ctx
+        return self._bind_waypoints(waypoints, 4, 'Waypoints needs to be a (Nxm), m >= 4, numpy array! (x, y, velocity, heading)')
 
     def _cfg(self, n_goals=None):
         if n_goals is None:
@@ -338,12 +297,7 @@ class LatticePlanner():
         until the next step).  Always a link of a closed loop (previous headings stay on the device); nothing but the poses and the
         three result columns touches host memory, and no copy is submitted (f1p_lattice_step_batch).  keep_traj=True keeps the winners'
         rows on the device: fetch_traj() returns them.  tracks / track_ids: as plan_batch (f1p_lattice_step_tracks_batch)."""
-        if tracks is not None:
-            _check_tracks(tracks, track_ids, 4)
-            ctx = self._context()
-            ctx.set_tracks_cached(tracks)
-        else:
-            ctx = self._bind(waypoints)
+        ctx = self._bind_tracks(tracks, track_ids, 4) if tracks is not None else self._bind(waypoints)
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4)
         self._step_shape = (poses.shape[0], self._cfg().n_stations)
         if tracks is not None:
@@ -356,7 +310,6 @@ class LatticePlanner():
         return self._context().lattice_fetch_traj(E, S)
 
     def _multi(self, devices):
-        from ...runtime import MultiContext
         key = "all" if isinstance(devices, str) else tuple(int(d) for d in devices)
         if getattr(self, "_mc_key", None) != key:
             if getattr(self, "_mc", None) is not None:

@@ -1,0 +1,320 @@
+"""Context's kinematic and dynamic MPC: references, rollouts, shooting and the linearised QPs (csrc/f1p_kmpc.hip, csrc/f1p_stmpc.hip)."""
+import ctypes as C
+
+import numpy as np
+
+from .. import _abi
+from .._abi import KmpcCfg
+from .core import _dev, _f64, _pick, _ptr, _ref, _tid
+
+
+class _Mpc:
+    # ---- MPC: the kinematic (kmpc_*, state width 4) and the dynamic (stmpc_*, 7) wrappers share their bodies -----------------------
+    def kmpc_ref(self, states, horizon, dt=0.1, dl=0.03):
+        return self._kmpc_ref(states, horizon, dt, dl)
+
+    def kmpc_ref_tracks(self, states, track_ids, horizon, dt=0.1, dl=0.03):
+        return self._kmpc_ref(states, horizon, dt, dl, _tid(track_ids))
+
+    def stmpc_ref(self, states, horizon, dt=0.025, dl=0.03):
+        return self._stmpc_ref(states, horizon, dt, dl)
+
+    def stmpc_ref_tracks(self, states, track_ids, horizon, dt=0.025, dl=0.03):
+        """stmpc_ref on each ego's track -> ref [E, 7, T+1] (a bad id: NaN rows).  With (TK, DTK, dlk), rows [0, 1, 3, 4] are STMPC's
+        kinematic reference, for kmpc_shoot; the full rows go to stmpc_shoot."""
+        return self._stmpc_ref(states, horizon, dt, dl, _tid(track_ids))
+
+    def _kmpc_ref(self, states, horizon, dt, dl, ids=None):
+        return self._mpc_ref(self.lib.f1p_kmpc_ref_batch, self.lib.f1p_kmpc_ref_tracks_batch, 4, states, horizon, dt, dl, ids)
+
+    def _stmpc_ref(self, states, horizon, dt, dl, ids=None):
+        return self._mpc_ref(self.lib.f1p_stmpc_ref_batch, self.lib.f1p_stmpc_ref_tracks_batch, 7, states, horizon, dt, dl, ids)
+
+    def _mpc_ref(self, plain, tracks, n, states, horizon, dt, dl, ids):
+        st = _f64(states, (-1, 4)); E = st.shape[0]; ids = None if ids is None else self._ids(ids, E)
+        ref = np.empty((E, n, horizon + 1))
+        fn, tid = _pick(plain, tracks, ids)
+        self._check(fn(self.h, _ptr(st), *tid, E, int(horizon), float(dt), float(dl), _ptr(ref)))
+        return ref
+
+    def kmpc_ref_tracks_dev(self, d_states, d_track_ids, E, horizon, d_ref, dt=0.1, dl=0.03):
+        self._mpc_ref_tracks_dev(self.lib.f1p_kmpc_ref_tracks_dev, d_states, d_track_ids, E, horizon, d_ref, dt, dl)
+
+    def stmpc_ref_tracks_dev(self, d_states, d_track_ids, E, horizon, d_ref, dt=0.025, dl=0.03):
+        self._mpc_ref_tracks_dev(self.lib.f1p_stmpc_ref_tracks_dev, d_states, d_track_ids, E, horizon, d_ref, dt, dl)
+
+    def _mpc_ref_tracks_dev(self, fn, d_states, d_track_ids, E, horizon, d_ref, dt, dl):
+        self._check(fn(self.h, _dev(d_states), _dev(d_track_ids), int(E), int(horizon), float(dt), float(dl), _dev(d_ref)))
+
+    def kmpc_set_mode(self, mixed=True, d_cost32=None, d_n_refined=None):
+        """mixed: f32 filter + fp64 refinement (default) or plain fp64; optional device buffers receive the filter diagnostics"""
+        self._check(self.lib.f1p_kmpc_set_mode(self.h, 1 if mixed else 0, None if d_cost32 is None else d_cost32.ptr,
+                                               None if d_n_refined is None else d_n_refined.ptr))
+
+    def stmpc_set_mode(self, mixed=True, d_cost32=None, d_n_refined=None):
+        """f32 filter + fp64 decision (default) or plain fp64 for the dynamic single-track shooting; the buffers are test hooks"""
+        self._check(self.lib.f1p_stmpc_set_mode(self.h, 1 if mixed else 0, None if d_cost32 is None else d_cost32.ptr,
+                                                None if d_n_refined is None else d_n_refined.ptr))
+
+    def kmpc_predict(self, x0, oa, od, cfg: KmpcCfg):
+        """predict_motion_kinematic (kinematic_mpc.py:208-221) for E egos -> path [E, 4, T+1]"""
+        return self._mpc_predict(self.lib.f1p_kmpc_predict_batch, 4, x0, oa, od, cfg)
+
+    def stmpc_predict(self, x0, oa, od_v, cfg):
+        """predict_motion (dynamic_mpc.py:280-300) for E egos -> path [E, 7, T+1]"""
+        return self._mpc_predict(self.lib.f1p_stmpc_predict_batch, 7, x0, oa, od_v, cfg)
+
+    def _mpc_predict(self, fn, n, x0, oa, od, cfg):
+        x0 = _f64(x0, (-1, n)); E = x0.shape[0]; T = cfg.horizon
+        oa = _f64(oa, (E, T)); od = _f64(od, (E, T))
+        path = np.empty((E, n, T + 1))
+        self._check(fn(self.h, _ptr(x0), _ptr(oa), _ptr(od), E, C.byref(cfg), _ptr(path)))
+        return path
+
+    # ---- MPC, random shooting (the dynamic single-track model: SURVEY 8f rank 2) -----------------------------------------------------
+    def kmpc_shoot(self, x0, ref, controls, cfg: KmpcCfg, want_seq=True):
+        return self._mpc_shoot(self.lib.f1p_kmpc_shoot_batch, 4, x0, ref, controls, cfg, want_seq)
+
+    def stmpc_shoot(self, x0, ref, controls, cfg, want_seq=True):
+        return self._mpc_shoot(self.lib.f1p_stmpc_shoot_batch, 7, x0, ref, controls, cfg, want_seq)
+
+    def _mpc_shoot(self, fn, n, x0, ref, controls, cfg, want_seq):
+        x0 = _f64(x0, (-1, n)); E = x0.shape[0]; T = cfg.horizon; R = cfg.n_rollouts
+        ref = _f64(ref, (E, n, T + 1))
+        controls = np.ascontiguousarray(controls, dtype=np.float32)
+        if controls.shape != (E, T, 2, R):
+            raise ValueError(f"controls must be f32 [E={E}, T={T}, 2, R={R}]")
+        out = dict(steer=np.empty(E), speed=np.empty(E), best_idx=np.empty(E, np.int32), best_cost=np.empty(E))
+        if want_seq:
+            out["best_seq"] = np.empty((E, T, 2))
+        self._check(fn(self.h, _ptr(x0), _ptr(ref), _ptr(controls), E, C.byref(cfg), _ptr(out["steer"]), _ptr(out["speed"]),
+                       _ptr(out["best_idx"]), _ptr(out["best_cost"]), _ptr(out.get("best_seq"))))
+        return out
+
+    def kmpc_shoot_dev(self, d_x0, d_ref, d_controls, E, cfg: KmpcCfg, d_steer, d_speed, d_best_idx, d_best_cost=None,
+                       d_best_seq=None):
+        self._mpc_shoot_dev(self.lib.f1p_kmpc_shoot_dev, d_x0, d_ref, d_controls, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq)
+
+    def stmpc_shoot_dev(self, d_x0, d_ref, d_controls, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost=None, d_best_seq=None):
+        """Asynchronous launch on HBM-resident buffers: x0 [E][7], ref [E][7][T+1], controls f32 [E][T][2][R]."""
+        self._mpc_shoot_dev(self.lib.f1p_stmpc_shoot_dev, d_x0, d_ref, d_controls, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq)
+
+    def _mpc_shoot_dev(self, fn, d_x0, d_ref, d_controls, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq):
+        self._check(fn(self.h, _dev(d_x0), _dev(d_ref), _dev(d_controls), int(E), C.byref(cfg), _dev(d_steer), _dev(d_speed),
+                       _dev(d_best_idx), _dev(d_best_cost), _dev(d_best_seq)))
+
+    # in-kernel control generation + device-resident warm start (f1p_kmpc_plan_*)
+    def kmpc_plan(self, x0, cfg: KmpcCfg, sampler, dl=0.03, want_seq=True, want_cost=True):
+        """KMPCPlanner.plan for E egos in ONE call: reference extraction, sampling around the ctx's warm start, rollouts,
+        argmin, new warm start -- nothing but x0 goes up and the winners come down."""
+        x0 = _f64(x0, (-1, 4)); E = x0.shape[0]; T = cfg.horizon
+        out = dict(steer=np.empty(E), speed=np.empty(E), best_idx=np.empty(E, np.int32))
+        if want_cost:
+            out["best_cost"] = np.empty(E)
+        if want_seq:
+            out["best_seq"] = np.empty((E, T, 2))
+        self._check(self.lib.f1p_kmpc_plan_batch(self.h, _ptr(x0), E, C.byref(cfg), float(dl), C.byref(sampler), _ptr(out["steer"]),
+                                                 _ptr(out["speed"]), _ptr(out["best_idx"]), _ptr(out.get("best_cost")), _ptr(out.get("best_seq"))))
+        return out
+
+    def stmpc_plan(self, x0, dcfg, kcfg: KmpcCfg, sampler, v_ks=2.0, dl=0.03, dlk=0.03, want_seq=True, want_cost=True):
+        """STMPCPlanner.plan with the shooting solver for E egos in ONE call: x0 [E, 7]; per ego the kinematic model at v <= v_ks, the
+        dynamic one above; reference extraction, generation around the ego's warm start, rollouts, argmin, new warm start ->
+        dict(steer, speed, best_idx, branch (1 dynamic, 0 kinematic)[, best_cost][, best_seq [E, max(T, TK), 2] in the branch's channel
+        order, NaN past its horizon])"""
+        x0 = _f64(x0, (-1, 7)); E = x0.shape[0]; W = max(dcfg.horizon, kcfg.horizon)
+        out = dict(steer=np.empty(E), speed=np.empty(E), best_idx=np.empty(E, np.int32), branch=np.empty(E, np.int32))
+        if want_cost:
+            out["best_cost"] = np.empty(E)
+        if want_seq:
+            out["best_seq"] = np.empty((E, W, 2))
+        self._check(self.lib.f1p_stmpc_plan_batch(self.h, _ptr(x0), E, C.byref(dcfg), C.byref(kcfg), float(v_ks), float(dl), float(dlk),
+                                                  C.byref(sampler), _ptr(out["steer"]), _ptr(out["speed"]), _ptr(out["best_idx"]),
+                                                  _ptr(out.get("best_cost")), _ptr(out["branch"]), _ptr(out.get("best_seq"))))
+        return out
+
+    def kmpc_plan_dev(self, d_x0, d_ref, E, cfg: KmpcCfg, sampler, d_steer, d_speed, d_best_idx, d_best_cost=None, d_best_seq=None):
+        self._mpc_plan_dev(self.lib.f1p_kmpc_plan_dev, d_x0, d_ref, E, cfg, sampler, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq)
+
+    def stmpc_plan_dev(self, d_x0, d_ref, E, cfg, sampler, d_steer, d_speed, d_best_idx, d_best_cost=None, d_best_seq=None):
+        """Asynchronous: the dynamic model's shooting plan of E egos on a given reference (x0 [E][7], ref [E][7][T+1]), the controls
+        generated in the kernels around the ctx's warm start, which it updates."""
+        self._mpc_plan_dev(self.lib.f1p_stmpc_plan_dev, d_x0, d_ref, E, cfg, sampler, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq)
+
+    def _mpc_plan_dev(self, fn, d_x0, d_ref, E, cfg, sampler, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq):
+        self._check(fn(self.h, _dev(d_x0), _dev(d_ref), int(E), C.byref(cfg), C.byref(sampler), _dev(d_steer), _dev(d_speed),
+                       _dev(d_best_idx), _dev(d_best_cost), _dev(d_best_seq)))
+
+    def kmpc_gen_controls_dev(self, d_controls, E, cfg: KmpcCfg, sampler):
+        self._check(self.lib.f1p_kmpc_gen_controls_dev(self.h, d_controls.ptr, int(E), C.byref(cfg), C.byref(sampler)))
+
+    # in-kernel control generation + per-ego device-resident warm start (f1p_stmpc_plan_*)
+    def stmpc_gen_controls_dev(self, d_controls, E, cfg, sampler):
+        """The controls the next stmpc_plan_dev of this shape would evaluate, as the f32 [E][T][2][R] buffer stmpc_shoot_dev takes."""
+        self._check(self.lib.f1p_stmpc_gen_controls_dev(self.h, d_controls.ptr, int(E), C.byref(cfg), C.byref(sampler)))
+
+    def kmpc_sample_controls_dev(self, d_controls, E, cfg: KmpcCfg, seed, sigma_accel=1.5, sigma_steer=0.15):
+        self._check(self.lib.f1p_kmpc_sample_controls_dev(self.h, d_controls.ptr, int(E), C.byref(cfg),
+                                                          C.c_uint64(int(seed)), float(sigma_accel), float(sigma_steer)))
+
+    def kmpc_warm_reset(self):
+        self._check(self.lib.f1p_kmpc_warm_reset(self.h))
+
+    def kmpc_warm_get(self, E, T):
+        w = np.empty((int(E), int(T), 2), np.float32)
+        self._check(self.lib.f1p_kmpc_warm_get(self.h, _ptr(w), int(E), int(T)))
+        return w
+
+    def kmpc_warm_set(self, warm):
+        w = np.ascontiguousarray(warm, np.float32)
+        self._check(self.lib.f1p_kmpc_warm_set(self.h, _ptr(w), w.shape[0], w.shape[1]))
+
+    def kmpc_set_yaw_fixup(self, on=True):
+        """k_kmpc_ref's per-ego heading fold (kinematic_mpc.py:198-203) on the gathered values; off = the caller maintains the array"""
+        self._check(self.lib.f1p_kmpc_set_yaw_fixup(self.h, 1 if on else 0))
+
+    def kmpc_set_groups(self, groups=0):
+        self._check(self.lib.f1p_kmpc_set_groups(self.h, int(groups)))
+
+    def kmpc_set_collision(self, on=True, n_sub=1):
+        """test the shooting solver's rollouts against the occupancy grid at n_sub points per time step (f1p_kmpc_set_collision): a
+        blocked rollout cannot win; an ego whose rollouts are all blocked gets best_idx -1, cost +inf, steer 0, speed 0"""
+        self._check(self.lib.f1p_kmpc_set_collision(self.h, 1 if on else 0, int(n_sub)))
+
+    def stmpc_set_collision(self, on=True, n_sub=1, n_sub_k=2):
+        """test the dynamic MPC's shooting rollouts against the occupancy grid (f1p_stmpc_set_collision): n_sub points per step of the
+        dynamic model, n_sub_k per step of stmpc_plan's kinematic branch; a blocked rollout cannot win; an ego whose rollouts are all
+        blocked gets best_idx -1, cost +inf, steer 0, speed 0, a zero sequence and a zero warm start.  Separate from kmpc_set_collision."""
+        self._check(self.lib.f1p_stmpc_set_collision(self.h, 1 if on else 0, int(n_sub), int(n_sub_k)))
+
+    def stmpc_warm_reset(self):
+        self._check(self.lib.f1p_stmpc_warm_reset(self.h))
+
+    def stmpc_warm_get(self, E, T, TK=0):
+        """-> (warm f32 [E, max(T, TK), 2], tag [E]: 0 none, 1 kinematic (accel, steer), 2 dynamic (steering speed, accel))"""
+        w = np.empty((int(E), max(int(T), int(TK)), 2), np.float32); tag = np.empty(int(E), np.int32)
+        self._check(self.lib.f1p_stmpc_warm_get(self.h, _ptr(w), _ptr(tag), int(E), int(T), int(TK)))
+        return w, tag
+
+    def stmpc_warm_set(self, warm, tags, T, TK=0):
+        w = np.ascontiguousarray(warm, np.float32); tag = np.ascontiguousarray(tags, dtype=np.int32)
+        if w.ndim != 3 or w.shape[1:] != (max(int(T), int(TK)), 2) or tag.shape != (w.shape[0],):
+            raise ValueError("warm must be [E, max(T, TK), 2] and tags [E]")
+        self._check(self.lib.f1p_stmpc_warm_set(self.h, _ptr(w), _ptr(tag), w.shape[0], int(T), int(TK)))
+
+    # ---- MPC, the reference's linearised QPs (f1p_kmpc_qp_*, f1p_stmpc_qp_*) ---------------------------------------------------------
+    def kmpc_qp(self, x0, ref, cfg: KmpcCfg, oa_prev=None, od_prev=None, opts=None, want_u=True, want_xk=False, want_obj=True,
+                want_duals=False, want_iters=True):
+        """linear_mpc_control_kinematic (kinematic_mpc.py:452-475) solved exactly for E egos: x0 [E, 4], ref [E, 4, T+1], the previous
+        solution oa_prev / od_prev [E, T] (None: zeros) -> dict(steer, speed, status[, u [E, T, 2], xk [E, 4, T+1], obj, duals [E, 8T-2],
+        iters]).  status: 0 solved, 1 infeasible, 2 not converged, 3 non-finite input (1 and 3: NaN outputs)."""
+        return self._mpc_qp(self.lib.f1p_kmpc_qp_batch, 4, "xk", 8, x0, ref, cfg, oa_prev, od_prev, opts, want_u, want_xk, want_obj, want_duals,
+                            want_iters)
+
+    def stmpc_qp(self, x0, ref, cfg: _abi.StmpcCfg, oa_prev=None, od_v_prev=None, opts=None, want_u=True, want_x=False, want_obj=True,
+                 want_duals=False, want_iters=True):
+        """linear_mpc_control (dynamic_mpc.py:995-1040) solved exactly for E egos: x0 [E, 7], ref [E, 7, T+1], the previous solution
+        oa_prev / od_v_prev [E, T] (None: zeros) -> dict(steer, speed, status[, u [E, T, 2] (steering speed, accel), x [E, 7, T+1], obj,
+        duals [E, 10T-2], iters]).  status: 0 solved, 1 infeasible, 2 not converged, 3 non-finite input or model data (1, 3: NaN outputs)."""
+        return self._mpc_qp(self.lib.f1p_stmpc_qp_batch, 7, "x", 10, x0, ref, cfg, oa_prev, od_v_prev, opts, want_u, want_x, want_obj,
+                            want_duals, want_iters)
+
+    def _mpc_qp(self, fn, n, xname, duals_per_step, x0, ref, cfg, oa_prev, od_prev, opts, want_u, want_x, want_obj, want_duals, want_iters):
+        """xname: the key of the predicted states [E, n, T+1]; duals [E, duals_per_step * T - 2]"""
+        x0 = _f64(x0, (-1, n)); E = x0.shape[0]; T = cfg.horizon
+        ref = _f64(ref, (E, n, T + 1))
+        oa = None if oa_prev is None else _f64(oa_prev, (E, T))
+        od = None if od_prev is None else _f64(od_prev, (E, T))
+        out = dict(steer=np.empty(E), speed=np.empty(E), status=np.empty(E, np.int32))
+        for k, want, shape, dt in (("u", want_u, (E, T, 2), np.float64), (xname, want_x, (E, n, T + 1), np.float64), ("obj", want_obj, (E,), np.float64),
+                                   ("duals", want_duals, (E, duals_per_step * T - 2), np.float64), ("iters", want_iters, (E,), np.int32)):
+            if want:
+                out[k] = np.empty(shape, dt)
+        self._check(fn(self.h, _ptr(x0), _ptr(ref), _ptr(oa), _ptr(od), E, C.byref(cfg), _ref(opts), _ptr(out["steer"]), _ptr(out["speed"]),
+                       _ptr(out["status"]), _ptr(out.get("u")), _ptr(out.get(xname)), _ptr(out.get("obj")), _ptr(out.get("duals")),
+                       _ptr(out.get("iters"))))
+        return out
+
+    def kmpc_qp_dev(self, d_x0, d_ref, E, cfg: KmpcCfg, d_steer, d_speed, d_status, d_oa_prev=None, d_od_prev=None, opts=None, d_u=None,
+                    d_xk=None, d_obj=None, d_duals=None, d_iters=None):
+        self._mpc_qp_dev(self.lib.f1p_kmpc_qp_dev, d_x0, d_ref, E, cfg, d_steer, d_speed, d_status, d_oa_prev, d_od_prev, opts, d_u, d_xk,
+                         d_obj, d_duals, d_iters)
+
+    def stmpc_qp_dev(self, d_x0, d_ref, E, cfg: _abi.StmpcCfg, d_steer, d_speed, d_status, d_oa_prev=None, d_od_v_prev=None, opts=None, d_u=None,
+                     d_x=None, d_obj=None, d_duals=None, d_iters=None):
+        self._mpc_qp_dev(self.lib.f1p_stmpc_qp_dev, d_x0, d_ref, E, cfg, d_steer, d_speed, d_status, d_oa_prev, d_od_v_prev, opts, d_u, d_x,
+                         d_obj, d_duals, d_iters)
+
+    def _mpc_qp_dev(self, fn, d_x0, d_ref, E, cfg, d_steer, d_speed, d_status, d_oa_prev, d_od_prev, opts, d_u, d_x, d_obj, d_duals, d_iters):
+        self._check(fn(self.h, _dev(d_x0), _dev(d_ref), _dev(d_oa_prev), _dev(d_od_prev), int(E), C.byref(cfg), _ref(opts), _dev(d_steer),
+                       _dev(d_speed), _dev(d_status), _dev(d_u), _dev(d_x), _dev(d_obj), _dev(d_duals), _dev(d_iters)))
+
+    def kmpc_qp_plan(self, x0, cfg: KmpcCfg, dl=0.03, opts=None, want_u=True, want_obj=True):
+        """KMPCPlanner.plan with the QP solver for E egos in ONE call: reference extraction, linearisation about the ctx's fp64 warm start
+        (the previous call's solution, unshifted), solve, output map, new warm start -> dict(steer, speed, status[, u, obj])"""
+        x0 = _f64(x0, (-1, 4)); E = x0.shape[0]; T = cfg.horizon
+        out = dict(steer=np.empty(E), speed=np.empty(E), status=np.empty(E, np.int32))
+        if want_u:
+            out["u"] = np.empty((E, T, 2))
+        if want_obj:
+            out["obj"] = np.empty(E)
+        self._check(self.lib.f1p_kmpc_qp_plan_batch(self.h, _ptr(x0), E, C.byref(cfg), float(dl), _ref(opts),
+                                                    _ptr(out["steer"]), _ptr(out["speed"]), _ptr(out["status"]), _ptr(out.get("u")),
+                                                    _ptr(out.get("obj"))))
+        return out
+
+    def stmpc_qp_plan(self, x0, dcfg: _abi.StmpcCfg, kcfg: KmpcCfg, v_ks=2.0, dl=0.03, dlk=0.03, opts=None, want_u=True, want_obj=True):
+        """STMPCPlanner.plan with the QP solver for E egos in ONE call: x0 [E, 7]; per ego the kinematic branch at v <= v_ks, the dynamic
+        one above; reference extraction, linearisation about the ctx's warm start (the reference's self.oa / self.odelta_v with its length
+        rules), solve, output map -> dict(steer, speed, status, branch (1 dynamic, 0 kinematic)[, u [E, max(T, TK), 2] = the new
+        (oa, odelta_v), NaN past the branch's horizon][, obj])"""
+        return self._stmpc_qp_plan(x0, dcfg, kcfg, v_ks, dl, dlk, opts, want_u, want_obj)
+
+    def stmpc_qp_plan_tracks(self, x0, track_ids, dcfg: _abi.StmpcCfg, kcfg: KmpcCfg, v_ks=2.0, dl=0.03, dlk=0.03, opts=None, want_u=True,
+                             want_obj=True):
+        """stmpc_qp_plan with ego e's references from track track_ids[e] of set_tracks; the same dict.  The warm start is the one of
+        stmpc_qp_plan (it follows the ego, not the track).  A bad id: status F1P_ST_BAD_TRACK, branch -1, NaN outputs, its warm start
+        untouched."""
+        return self._stmpc_qp_plan(x0, dcfg, kcfg, v_ks, dl, dlk, opts, want_u, want_obj, _tid(track_ids))
+
+    def _stmpc_qp_plan(self, x0, dcfg, kcfg, v_ks, dl, dlk, opts, want_u, want_obj, ids=None):
+        x0 = _f64(x0, (-1, 7)); E = x0.shape[0]; ids = None if ids is None else self._ids(ids, E); W = max(dcfg.horizon, kcfg.horizon)
+        out = dict(steer=np.empty(E), speed=np.empty(E), status=np.empty(E, np.int32), branch=np.empty(E, np.int32))
+        if want_u:
+            out["u"] = np.empty((E, W, 2))
+        if want_obj:
+            out["obj"] = np.empty(E)
+        fn, tid = _pick(self.lib.f1p_stmpc_qp_plan_batch, self.lib.f1p_stmpc_qp_plan_tracks_batch, ids)
+        self._check(fn(self.h, _ptr(x0), *tid, E, C.byref(dcfg), C.byref(kcfg), float(v_ks), float(dl), float(dlk), _ref(opts),
+                       _ptr(out["steer"]), _ptr(out["speed"]), _ptr(out["status"]), _ptr(out["branch"]), _ptr(out.get("u")),
+                       _ptr(out.get("obj"))))
+        return out
+
+    def kmpc_qp_warm_reset(self):
+        self._check(self.lib.f1p_kmpc_qp_warm_reset(self.h))
+
+    def kmpc_qp_warm_get(self, E, T):
+        w = np.empty((int(E), int(T), 2))
+        self._check(self.lib.f1p_kmpc_qp_warm_get(self.h, _ptr(w), int(E), int(T)))
+        return w
+
+    def kmpc_qp_warm_set(self, warm):
+        w = _f64(warm)
+        self._check(self.lib.f1p_kmpc_qp_warm_set(self.h, _ptr(w), w.shape[0], w.shape[1]))
+
+    def kmpc_qp_set_pack(self, egos_per_wave=0):
+        """egos per wave of the QP kernel at T <= 8 (0: default, 1 or 4)"""
+        self._check(self.lib.f1p_kmpc_qp_set_pack(self.h, int(egos_per_wave)))
+
+    def stmpc_qp_warm_reset(self):
+        self._check(self.lib.f1p_stmpc_qp_warm_reset(self.h))
+
+    def stmpc_qp_warm_get(self, E, W):
+        """-> (warm [E, W, 2] = (oa, odelta_v), len [E]: the length of each ego's oa, 0 = None)"""
+        w = np.empty((int(E), int(W), 2)); n = np.empty(int(E), np.int32)
+        self._check(self.lib.f1p_stmpc_qp_warm_get(self.h, _ptr(w), _ptr(n), int(E), int(W)))
+        return w, n
+
+    def stmpc_qp_warm_set(self, warm, lengths):
+        w = _f64(warm); n = np.ascontiguousarray(lengths, dtype=np.int32)
+        self._check(self.lib.f1p_stmpc_qp_warm_set(self.h, _ptr(w), _ptr(n), w.shape[0], w.shape[1]))
