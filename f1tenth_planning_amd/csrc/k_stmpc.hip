@@ -4,7 +4,7 @@
 // its objective (:616-622), bounds (:685-706) applied as a projection of each sampled control sequence, and the output
 // map (:1112-1117).  Same mapping as K4 (k_kmpc.hip): one 256-thread workgroup per ego, one thread per rollout, f32
 // controls [ego][t][steering speed | accel][rollout] streamed from HBM, the 7-row reference in LDS, fp64 arithmetic.
-// f1p_stmpc_plan_* runs the same kernels' text with the controls GENERATED in registers (the *_gen kernels).
+// f1p_stmpc_plan_* runs the same kernel templates with the controls GENERATED in registers (the *_gen kernels).
 #include "f1p_internal.h"
 #include "shoot_gen.h"
 #include "shoot_col.h"
@@ -38,12 +38,20 @@ __global__ __launch_bounds__(256) void k_stmpc_predict(const double* __restrict_
 //   generated: in registers from (seed, call, ego, rollout, t) around the ego's warm start (f1p_stmpc_plan_*; shoot_gen.h: channel 0 =
 //              steering speed with sigma sig_dv, channel 1 = accel with sig_a).  The filter, the refinement, the all-fp64 fallback and
 //              the winner's re-emission call the same pure function, so they all see the same controls and no controls buffer exists.
-// The shooting kernels are compiled once per source from k_stmpc_shoot_text.h (below).
+// The shooting kernels are templates over the source (below).
 // StCtlGen is the generating kernels' parameter.  ids (nullable): the launch is a compacted list of a larger batch, ego e of the launch
 // is ego ids[e] of that batch.  The generator's ego word is the ego's index in the caller's batch (+ ego_off: the batch is itself a
 // shard of a larger one), its warm start the row of that index in `warm` (wstride floats per ego, [T][2] = (steering speed, accel)
 // used; all zero = none): an ego's plan depends on that ego alone.  The decision kernel overwrites the row with the next warm start.
 // ---------------------------------------------------------------------------------------------------------------------------------
+// the generated source of the fp64 paths, read the way the shooting kernels read a step: its steering speed, then its accel.  dv(t, r)
+// makes the step's one Philox call and keeps the accel; a() hands it out and must follow dv() of the same step.
+struct StGenSrc {
+    SrcGenT<true> g;
+    mutable float a_;
+    __device__ __forceinline__ float dv(int t, int r) const { float v; g.get(t, r, v, a_); return v; }
+    __device__ __forceinline__ float a() const { return a_; }
+};
 struct StCtlGen {
     uint32_t k0, k1, call, ego_off;
     float sig_dv, sig_a;
@@ -58,14 +66,6 @@ struct StCtlGen {
         s.warm = w;
         return s;
     }
-};
-// the generated source of the fp64 paths, read the way the shooting text reads a step: its steering speed, then its accel.  dv(t, r)
-// makes the step's one Philox call and keeps the accel; a() hands it out and must follow dv() of the same step (the text's order).
-struct StGenSrc {
-    SrcGenT<true> g;
-    mutable float a_;
-    __device__ __forceinline__ float dv(int t, int r) const { float v; g.get(t, r, v, a_); return v; }
-    __device__ __forceinline__ float a() const { return a_; }
 };
 
 // ===================================================================================================================
@@ -117,7 +117,7 @@ __device__ __forceinline__ float in_vgpr(float x) { float r; asm("v_mov_b32 %0, 
 // unweighted, three of the seven terms of every step)
 // one step of the f32 filter for rollout slot i, as text: the stage cost of the OLD state, then the step (dynamic_mpc.py:317-404; B_i = dt A_i,
 // the angle in revolutions for the hardware sin / cos).  Expects dv, a (this step's controls after the bounds :701-706; the rate limit :685
-// is applied here), t, r0 / r1 (the step's reference row), k and the state arrays.  A macro so that the streamed and the generating rollout
+// is applied here), t, r0 / r1 (the step's reference row), k and the state arrays.  A macro so that the streamed and the generating rollouts
 // share it while the streamed function's tokens stay exactly what they were.
 #define F1P_ST_F32_STEP(i) \
             if (t > 0) dv = __builtin_amdgcn_fmed3f(dv, pdv[i] - k.max_steer_v, pdv[i] + k.max_steer_v); \
@@ -193,9 +193,9 @@ __device__ __forceinline__ void stmpc_rollout_f32(const float* __restrict__ ce, 
 }
 
 // the same rollout with its controls GENERATED: one Philox4x32-10 call per pair of steps (SrcGenT::get2), nothing fetched but the step's
-// warm-start row (LDS, wave-uniform address).  Same signature as the streamed function; R is unused.
+// warm-start row (LDS, wave-uniform address).  An overload on the source type; R is unused.
 template <bool POLY, int NR, int QM>
-__device__ __forceinline__ void stmpc_rollout_f32_gen(const SrcGenT<true>& ce, const float* sref8, const DynF32& k, int T, int R, const int (&rr)[NR],
+__device__ __forceinline__ void stmpc_rollout_f32(const SrcGenT<true>& ce, const float* sref8, const DynF32& k, int T, int R, const int (&rr)[NR],
                                                       float delta0, float v0, float yr0, float beta0, float (&cost_out)[NR], bool (&trusted)[NR]) {
 #pragma clang fp contract(fast)
     (void)R;
@@ -235,11 +235,11 @@ __device__ __forceinline__ void stmpc_rollout_f32_gen(const SrcGenT<true>& ce, c
     }
 }
 
-// stmpc_rollout_f32_gen with the occupancy test's look-ups (k_stmpc_filter_gen_col): after every step the step's n_sub tested points --
+// the generating rollout with the occupancy test's look-ups (k_stmpc_filter_gen_col): after every step the step's n_sub tested points --
 // formed from the f32 states, relative to the ego with the map's axes -- are looked up in the clearance map; unsure = one of them is near an
 // occupied cell, off the image or NaN, so the rollout is not proved free (shoot_col.h KmpcColF; the position bound: DESIGN.md 5i)
 template <bool POLY, int NR, int QM>
-__device__ __forceinline__ void stmpc_rollout_f32_gen_col(const SrcGenT<true>& ce, const float* sref8, const DynF32& k, int T, int R, const int (&rr)[NR],
+__device__ __forceinline__ void stmpc_rollout_f32(const SrcGenT<true>& ce, const float* sref8, const DynF32& k, int T, int R, const int (&rr)[NR],
                                                           float delta0, float v0, float yr0, float beta0, float (&cost_out)[NR], bool (&trusted)[NR],
                                                           const KmpcColF& cf, bool (&unsure)[NR]
 #ifdef F1P_ST_DBG_POS    // variant build (tools/stmpc_pos_error.py): the f32 positions after every step, [t][x | y] planes of pos_stride floats
@@ -296,7 +296,7 @@ __device__ __forceinline__ void stmpc_rollout_f32_gen_col(const SrcGenT<true>& c
 // ---- K-A: f32 filter, one workgroup per ego; no fp64 rollout code in this kernel (registers for 8 waves per SIMD) ----------------
 // nlist[e] = listed rollouts (<= 64) or -1 (this ego is decided by the all-fp64 loop in k_stmpc_decide); the listed rollouts go to
 // rl[e][slot] and, as (e * 64 + slot, r), onto the global queue that k_stmpc_refine packs into full waves across egos.
-// (The kernels K-A, K-B, K-B' and K-C themselves are in k_stmpc_shoot_text.h; their types and their notes stay here.)
+// (The kernels K-A, K-B, K-B' and K-C themselves follow below, as templates; their types and their notes stay here.)
 struct StItem { int es, r; };
 
 // ---- K-B', time-parallel: ONE WAVE per queued rollout, lanes over the time steps (horizon <= 63) ---------------------------------
@@ -321,178 +321,636 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// ---- the shooting kernels, once per control source (k_stmpc_shoot_text.h) -----------------------------------------------------------
-#define F1P_ST_COL 0
-#define F1P_ST_N(name) name
-#define F1P_ST_CTL_PARAM const float* __restrict__ controls
-#define F1P_ST_SRC_PARAM const float* __restrict__ ce
-#define F1P_ST_SRC_DECL(ce, e) const float* ce = controls + (size_t)e * T * 2 * R
-#define F1P_ST_SRC_DECL_FILTER(ce, e) F1P_ST_SRC_DECL(ce, e)
-#define F1P_ST_SRC_EXPR(e) controls + (size_t)e * T * 2 * R
-#define F1P_ST_SRC_DECL_R(cp, e, r) const float* cp = controls + (size_t)e * T * 2 * R + r
-#define F1P_ST_DV_R(cp, t, r) cp[(size_t)t * 2 * R]
-#define F1P_ST_A_R(cp, t, r) cp[(size_t)t * 2 * R + R]
-#define F1P_ST_DV(ce, t, r) ce[((size_t)t * 2 + 0) * R + r]
-#define F1P_ST_A(ce, t, r) ce[((size_t)t * 2 + 1) * R + r]
-#define F1P_ST_EMIT_PRE(ce, bi)
-#define F1P_ST_EMIT_DV(ce, t, bi) ce[((size_t)t * 2 + 0) * R + bi]
-#define F1P_ST_EMIT_A(ce, t, bi) ce[((size_t)t * 2 + 1) * R + bi]
-#define F1P_ST_EMIT_TAIL(e, t, dv, a) else if (t == 0) break;
-#define F1P_ST_FILTER_WARM(e)
-#include "k_stmpc_shoot_text.h"
-#undef F1P_ST_N
-#undef F1P_ST_CTL_PARAM
-#undef F1P_ST_SRC_PARAM
-#undef F1P_ST_SRC_DECL
-#undef F1P_ST_SRC_DECL_FILTER
-#undef F1P_ST_SRC_EXPR
-#undef F1P_ST_SRC_DECL_R
-#undef F1P_ST_DV_R
-#undef F1P_ST_A_R
-#undef F1P_ST_DV
-#undef F1P_ST_A
-#undef F1P_ST_EMIT_PRE
-#undef F1P_ST_EMIT_DV
-#undef F1P_ST_EMIT_A
-#undef F1P_ST_EMIT_TAIL
-#undef F1P_ST_FILTER_WARM
+// ---- the shooting kernels: templates over the control source and the optional occupancy test --------------------------------------
+// Ctl, the kernels' control parameter, is StCtlStream or StCtlGen.  The bodies choose by `if constexpr (st_gen<Ctl>)`; the streamed branch
+// spells the raw pointer and its index arithmetic out at the use site, which is what keeps the streamed kernels' instructions what they
+// were (a wrapper object or an accessor function does not: tools/listing_diff.py is the check after every change here).
+// Col..., nothing or one KmpcCol (StColRef in the two refinement kernels), is the occupancy test of f1p_stmpc_set_collision (DESIGN.md 5i;
+// shoot_col.h has_col / col_of): the fp64 rollouts test each step as they take it, the filter looks its tested points up in the clearance
+// map and lists FREE and UNSURE rollouts, the refinement marks a blocked item (cost +inf, listed index F1P_K4_NONE), the decision skips
+// those.  Filter, refinement and decision with the test exist for generated controls only: f1p_stmpc_shoot_* run the plain-fp64 kernel
+// while the test is on.  The instantiations are the ones named below the kernels -- nothing that is not launched.
+using StCtlStream = const float* __restrict__;
+template <typename Ctl> constexpr bool st_gen = std::is_same_v<Ctl, StCtlGen>;
+// ego e's source: as a value, and as the device functions take it
+template <typename Ctl> using st_ego_t = std::conditional_t<st_gen<Ctl>, StGenSrc, const float*>;
+template <typename Ctl> using st_src_t = std::conditional_t<st_gen<Ctl>, const StGenSrc&, const float* __restrict__>;
+// the refinement kernels' form of the test: they also rewrite the listed index of a blocked item
+struct StColRef : KmpcCol { int32_t* rl; };
 
-// generated controls.  The filter keeps the ego's warm start in LDS (read T x R times), behind its other arrays; the fp64 kernels read
-// the global row (a few rollouts).  The emission writes the next warm start: the winner's APPLIED sequence shifted by one step, the
-// last step repeated, rounded to f32 (the rule of kmpc_emit; dynamic_mpc.py:1052-1055 keeps self.oa / self.odelta_v the same way) -- into
-// the row the generator reads; every read of it (F1P_ST_EMIT_PRE, all steps at once) is behind a barrier before the first write.
-#define F1P_ST_N(name) name##_gen
-#define F1P_ST_CTL_PARAM StCtlGen ctl
-#define F1P_ST_SRC_PARAM const StGenSrc& ce
-#define F1P_ST_SRC_DECL(ce, e) const StGenSrc ce = {ctl.src(e, ctl.warm_row(e)), 0.0f}
-#define F1P_ST_SRC_DECL_FILTER(ce, e) const SrcGenT<true> ce = ctl.src(e, reinterpret_cast<const float*>(cnt + 2))
-#define F1P_ST_SRC_EXPR(e) StGenSrc{ctl.src(e, ctl.warm_row(e)), 0.0f}
-#define F1P_ST_SRC_DECL_R(cp, e, r) F1P_ST_SRC_DECL(cp, e)
-#define F1P_ST_DV_R(cp, t, r) cp.dv(t, r)
-#define F1P_ST_A_R(cp, t, r) cp.a()
-#define F1P_ST_DV(ce, t, r) ce.dv(t, r)
-#define F1P_ST_A(ce, t, r) ce.a()
-#define F1P_ST_EMIT_PRE(ce, bi) float* emit_s = reinterpret_cast<float*>(lds_raw); \
-        for (int t_ = tid; t_ < T; t_ += blockDim.x) ce.g.get(t_, bi, emit_s[2 * t_], emit_s[2 * t_ + 1]); \
-        __syncthreads();
-#define F1P_ST_EMIT_DV(ce, t, bi) emit_s[2 * t]
-#define F1P_ST_EMIT_A(ce, t, bi) emit_s[2 * t + 1]
-#define F1P_ST_EMIT_TAIL(e, t, dv, a) { float* wo_ = ctl.warm_row(e); \
-        if (t > 0) { wo_[2 * (t - 1)] = (float)dv; wo_[2 * (t - 1) + 1] = (float)a; } \
-        if (t == T - 1) { wo_[2 * t] = (float)dv; wo_[2 * t + 1] = (float)a; } }
-#define F1P_ST_FILTER_WARM(e) { float* ws_ = reinterpret_cast<float*>(cnt + 2); const float* wg_ = ctl.warm_row(e); \
-        for (int q = tid; q < 2 * T; q += blockDim.x) ws_[q] = wg_[q]; }
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-variable"   // R, where it only addressed the controls buffer
-#include "k_stmpc_shoot_text.h"
-#pragma clang diagnostic pop
-#undef F1P_ST_N
-#undef F1P_ST_CTL_PARAM
-#undef F1P_ST_SRC_PARAM
-#undef F1P_ST_SRC_DECL
-#undef F1P_ST_SRC_DECL_FILTER
-#undef F1P_ST_SRC_EXPR
-#undef F1P_ST_SRC_DECL_R
-#undef F1P_ST_DV_R
-#undef F1P_ST_A_R
-#undef F1P_ST_DV
-#undef F1P_ST_A
-#undef F1P_ST_EMIT_PRE
-#undef F1P_ST_EMIT_DV
-#undef F1P_ST_EMIT_A
-#undef F1P_ST_EMIT_TAIL
-#undef F1P_ST_FILTER_WARM
+#ifdef F1P_ST_PHASES
+#define F1P_STPH() do { ph[nph++] = clock64(); } while (0)
+#else
+#define F1P_STPH() do {} while (0)
+#endif
 
-// the same text twice more with the occupancy test of f1p_stmpc_set_collision (F1P_ST_COL 1): k_stmpc_shoot_col over streamed
-// controls -- what f1p_stmpc_shoot_* launch in every mode while the test is on -- and k_stmpc_shoot_gen_col over generated ones
-#undef F1P_ST_COL
-#define F1P_ST_COL 1
-#define F1P_ST_COL_MIXED 0
-#define F1P_ST_N(name) name##_col
-#define F1P_ST_CTL_PARAM const float* __restrict__ controls
-#define F1P_ST_SRC_PARAM const float* __restrict__ ce
-#define F1P_ST_SRC_DECL(ce, e) const float* ce = controls + (size_t)e * T * 2 * R
-#define F1P_ST_SRC_DECL_FILTER(ce, e) F1P_ST_SRC_DECL(ce, e)
-#define F1P_ST_SRC_EXPR(e) controls + (size_t)e * T * 2 * R
-#define F1P_ST_SRC_DECL_R(cp, e, r) const float* cp = controls + (size_t)e * T * 2 * R + r
-#define F1P_ST_DV_R(cp, t, r) cp[(size_t)t * 2 * R]
-#define F1P_ST_A_R(cp, t, r) cp[(size_t)t * 2 * R + R]
-#define F1P_ST_DV(ce, t, r) ce[((size_t)t * 2 + 0) * R + r]
-#define F1P_ST_A(ce, t, r) ce[((size_t)t * 2 + 1) * R + r]
-#define F1P_ST_EMIT_PRE(ce, bi)
-#define F1P_ST_EMIT_DV(ce, t, bi) ce[((size_t)t * 2 + 0) * R + bi]
-#define F1P_ST_EMIT_A(ce, t, bi) ce[((size_t)t * 2 + 1) * R + bi]
-#define F1P_ST_EMIT_TAIL(e, t, dv, a) else if (t == 0) break;
-#define F1P_ST_FILTER_WARM(e)
-#define F1P_ST_EMIT_BLOCKED(e, q)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-variable"
-#include "k_stmpc_shoot_text.h"
-#pragma clang diagnostic pop
-#undef F1P_ST_N
-#undef F1P_ST_CTL_PARAM
-#undef F1P_ST_SRC_PARAM
-#undef F1P_ST_SRC_DECL
-#undef F1P_ST_SRC_DECL_FILTER
-#undef F1P_ST_SRC_EXPR
-#undef F1P_ST_SRC_DECL_R
-#undef F1P_ST_DV_R
-#undef F1P_ST_A_R
-#undef F1P_ST_DV
-#undef F1P_ST_A
-#undef F1P_ST_EMIT_PRE
-#undef F1P_ST_EMIT_DV
-#undef F1P_ST_EMIT_A
-#undef F1P_ST_EMIT_TAIL
-#undef F1P_ST_FILTER_WARM
-#undef F1P_ST_EMIT_BLOCKED
-#undef F1P_ST_COL_MIXED
-#define F1P_ST_COL_MIXED 1
-#define F1P_ST_N(name) name##_gen_col
-#define F1P_ST_CTL_PARAM StCtlGen ctl
-#define F1P_ST_SRC_PARAM const StGenSrc& ce
-#define F1P_ST_SRC_DECL(ce, e) const StGenSrc ce = {ctl.src(e, ctl.warm_row(e)), 0.0f}
-#define F1P_ST_SRC_DECL_FILTER(ce, e) const SrcGenT<true> ce = ctl.src(e, reinterpret_cast<const float*>(cnt + 2))
-#define F1P_ST_SRC_EXPR(e) StGenSrc{ctl.src(e, ctl.warm_row(e)), 0.0f}
-#define F1P_ST_SRC_DECL_R(cp, e, r) F1P_ST_SRC_DECL(cp, e)
-#define F1P_ST_DV_R(cp, t, r) cp.dv(t, r)
-#define F1P_ST_A_R(cp, t, r) cp.a()
-#define F1P_ST_DV(ce, t, r) ce.dv(t, r)
-#define F1P_ST_A(ce, t, r) ce.a()
-#define F1P_ST_EMIT_PRE(ce, bi) float* emit_s = reinterpret_cast<float*>(lds_raw); \
-        for (int t_ = tid; t_ < T; t_ += blockDim.x) ce.g.get(t_, bi, emit_s[2 * t_], emit_s[2 * t_ + 1]); \
+// all rollouts of this thread, first-minimum argmin (objective :616-622, bounds :685-706 as a projection)
+template <bool FAST, typename Ctl, typename... Col>
+__device__ __forceinline__ void stmpc_rollouts(st_src_t<Ctl> ce, const double* sref, const f1p_stmpc_cfg& cfg, const DynConst& k,
+                                               const DynState& s0, int tid, double& bc, int& bi, const Col&... col) {
+    const int T = cfg.horizon, R = cfg.n_rollouts;
+    for (int r = tid; r < R; r += blockDim.x) {
+        DynState s = s0;
+        double cost = 0.0, pdv = 0.0, pa = 0.0;
+        [[maybe_unused]] bool blocked = false;
+        for (int t = 0; t < T; ++t) {
+            float c;                                                  // (generated: dv() makes the step's one Philox call, a() hands out its accel)
+            if constexpr (st_gen<Ctl>) c = ce.dv(t, r); else c = ce[((size_t)t * 2 + 0) * R + r];
+            double dv = clampd2((double)c, -cfg.max_steer_v, cfg.max_steer_v);   // :701-703
+            if constexpr (st_gen<Ctl>) c = ce.a(); else c = ce[((size_t)t * 2 + 1) * R + r];
+            double a = clampd2((double)c, -cfg.max_accel, cfg.max_accel);        // :704-706
+            if (t > 0) dv = clampd2(dv, pdv - cfg.max_steer_v, pdv + cfg.max_steer_v);                         // :685
+            const double sv[7] = {s.x, s.y, s.delta, s.v, s.yaw, s.yr, s.beta};
+            double q = 0.0;
+#pragma unroll
+            for (int j = 0; j < 7; ++j) { const double er = sv[j] - sref[j * (T + 1) + t]; q += cfg.q[j] * er * er; }   // :619
+            cost += q;
+            cost += cfg.r[0] * dv * dv + cfg.r[1] * a * a;                                                       // :616
+            if (t > 0) { const double d0 = dv - pdv, d1 = a - pa; cost += cfg.rd[0] * d0 * d0 + cfg.rd[1] * d1 * d1; }   // :622
+            [[maybe_unused]] const double px = s.x, py = s.y;
+            dyn_step<FAST>(s, a, dv, cfg, k);
+            if constexpr (has_col<Col...>) {
+                if (col_of(col...).seg(px, py, s.x, s.y)) { blocked = true; break; }   // the points of step t -> t + 1; a blocked rollout stops at its first occupied point
+            }
+            pdv = dv; pa = a;
+        }
+        if constexpr (has_col<Col...>) { if (blocked) continue; }     // takes no part in the argmin: (bc, bi) stays (+inf, F1P_K4_NONE) while nothing is free
+        const double sv[7] = {s.x, s.y, s.delta, s.v, s.yaw, s.yr, s.beta};
+        double q = 0.0;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) { const double er = sv[j] - sref[j * (T + 1) + T]; q += cfg.qf[j] * er * er; }
+        cost += q;
+        if (argmin_better(cost, r, bc, bi)) { bc = cost; bi = r; }
+    }
+}
+
+// The winner's re-emission (every thread, bi known to all) stands in k_stmpc_shoot_t and in k_stmpc_decide_t, and so does the "every
+// rollout blocked" epilogue: as shared device functions they change the kernels' register allocation (LABNOTES R10).  Streamed controls:
+// thread 0 reads the winner's steps, and stops after step 0 when no best_seq is wanted.  Generated controls: the winner's T steps are
+// regenerated with one thread per step into LDS (the kernels' reference rows are free by then), so that the one emitting thread neither
+// runs T Philox calls in sequence nor waits for a warm-start load per step behind its own warm-start stores; the emission writes the next
+// warm start -- the winner's APPLIED sequence shifted by one step, the last step repeated, rounded to f32 (the rule of kmpc_emit;
+// dynamic_mpc.py:1052-1055 keeps self.oa / self.odelta_v the same way) -- into the row the generator reads: every read of it is behind
+// the barrier, before the first write.  A blocked ego's row is zeroed: no warm start for its next plan.
+template <typename Ctl, typename... Col>
+__global__ __launch_bounds__(256) void k_stmpc_shoot_t(const double* __restrict__ x0, const double* __restrict__ ref,
+                                                     Ctl ctl, int E, f1p_stmpc_cfg cfg, Col... col,
+                                                     double* __restrict__ steer, double* __restrict__ speed,
+                                                     int32_t* __restrict__ best_idx, double* __restrict__ best_cost,
+                                                     double* __restrict__ best_seq) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    double* sref = reinterpret_cast<double*>(lds_raw);   // [7][T+1]
+    double* red_d = sref + 7 * (cfg.horizon + 1);
+    int* red_i = reinterpret_cast<int*>(red_d + 4);
+    const int e = blockIdx.x;
+    if (e >= E) return;
+    const int T = cfg.horizon, R = cfg.n_rollouts, tid = threadIdx.x;
+    for (int q = tid; q < 7 * (T + 1); q += blockDim.x) sref[q] = ref[(size_t)e * 7 * (T + 1) + q];
+    __syncthreads();
+    const DynConst k = dyn_const(cfg);
+    DynState s0;
+    s0.x = x0[7 * e]; s0.y = x0[7 * e + 1]; s0.delta = x0[7 * e + 2]; s0.v = x0[7 * e + 3]; s0.yaw = x0[7 * e + 4];
+    s0.yr = x0[7 * e + 5]; s0.beta = x0[7 * e + 6];
+    st_ego_t<Ctl> ce;
+    if constexpr (st_gen<Ctl>) ce = StGenSrc{ctl.src(e, ctl.warm_row(e)), 0.0f}; else ce = ctl + (size_t)e * T * 2 * R;
+    double bc = __builtin_huge_val(); int bi = 0x7fffffff;
+    if (fabs(cfg.max_steer) <= 1.0e4) stmpc_rollouts<true, Ctl>(ce, sref, cfg, k, s0, tid, bc, bi, col...);     // workgroup-uniform
+    else stmpc_rollouts<false, Ctl>(ce, sref, cfg, k, s0, tid, bc, bi, col...);
+    block_argmin(bc, bi, red_d, red_i);
+    if constexpr (has_col<Col...>) {
+        if (bi == F1P_K4_NONE) {                                      // every rollout blocked (workgroup-uniform): the lattice's ALL_BLOCKED outputs
+            for (int q = tid; q < 2 * T; q += blockDim.x) {
+                if (best_seq) best_seq[(size_t)e * T * 2 + q] = 0.0;
+                if constexpr (st_gen<Ctl>) ctl.warm_row(e)[q] = 0.0f;
+            }
+            if (tid == 0) {
+                steer[e] = 0.0; speed[e] = 0.0; best_idx[e] = -1;
+                if (best_cost) best_cost[e] = __builtin_huge_val();
+            }
+            return;
+        }
+    }
+    [[maybe_unused]] float* emit_s = reinterpret_cast<float*>(lds_raw);
+    if constexpr (st_gen<Ctl>) {
+        for (int t_ = tid; t_ < T; t_ += blockDim.x) ce.g.get(t_, bi, emit_s[2 * t_], emit_s[2 * t_ + 1]);
         __syncthreads();
-#define F1P_ST_EMIT_DV(ce, t, bi) emit_s[2 * t]
-#define F1P_ST_EMIT_A(ce, t, bi) emit_s[2 * t + 1]
-#define F1P_ST_EMIT_TAIL(e, t, dv, a) { float* wo_ = ctl.warm_row(e); \
-        if (t > 0) { wo_[2 * (t - 1)] = (float)dv; wo_[2 * (t - 1) + 1] = (float)a; } \
-        if (t == T - 1) { wo_[2 * t] = (float)dv; wo_[2 * t + 1] = (float)a; } }
-#define F1P_ST_FILTER_WARM(e) { float* ws_ = reinterpret_cast<float*>(cnt + 2); const float* wg_ = ctl.warm_row(e); \
-        for (int q = tid; q < 2 * T; q += blockDim.x) ws_[q] = wg_[q]; }
-#define F1P_ST_EMIT_BLOCKED(e, q) ctl.warm_row(e)[q] = 0.0f;
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-variable"
-#include "k_stmpc_shoot_text.h"
-#pragma clang diagnostic pop
-#undef F1P_ST_N
-#undef F1P_ST_CTL_PARAM
-#undef F1P_ST_SRC_PARAM
-#undef F1P_ST_SRC_DECL
-#undef F1P_ST_SRC_DECL_FILTER
-#undef F1P_ST_SRC_EXPR
-#undef F1P_ST_SRC_DECL_R
-#undef F1P_ST_DV_R
-#undef F1P_ST_A_R
-#undef F1P_ST_DV
-#undef F1P_ST_A
-#undef F1P_ST_EMIT_PRE
-#undef F1P_ST_EMIT_DV
-#undef F1P_ST_EMIT_A
-#undef F1P_ST_EMIT_TAIL
-#undef F1P_ST_FILTER_WARM
-#undef F1P_ST_EMIT_BLOCKED
-#undef F1P_ST_COL_MIXED
-#undef F1P_ST_COL
+    }
+    if (tid == 0) {
+        double pdv = 0.0;
+        for (int t = 0; t < T; ++t) {
+            float c;
+            if constexpr (st_gen<Ctl>) c = emit_s[2 * t]; else c = ce[((size_t)t * 2 + 0) * R + bi];
+            double dv = clampd2((double)c, -cfg.max_steer_v, cfg.max_steer_v);
+            if constexpr (st_gen<Ctl>) c = emit_s[2 * t + 1]; else c = ce[((size_t)t * 2 + 1) * R + bi];
+            const double a = clampd2((double)c, -cfg.max_accel, cfg.max_accel);
+            if (t > 0) dv = clampd2(dv, pdv - cfg.max_steer_v, pdv + cfg.max_steer_v);
+            if (t == 0) {
+                steer[e] = s0.delta + dv * cfg.dt;   // :1112
+                speed[e] = s0.v + a * cfg.dt;        // :1117
+            }
+            if (best_seq) { best_seq[((size_t)e * T + t) * 2] = dv; best_seq[((size_t)e * T + t) * 2 + 1] = a; }
+            else if constexpr (!st_gen<Ctl>) { if (t == 0) break; }
+            if constexpr (st_gen<Ctl>) {
+                float* wo_ = ctl.warm_row(e);
+                if (t > 0) { wo_[2 * (t - 1)] = (float)dv; wo_[2 * (t - 1) + 1] = (float)a; }
+                if (t == T - 1) { wo_[2 * t] = (float)dv; wo_[2 * t + 1] = (float)a; }
+            }
+            pdv = dv;
+        }
+        best_idx[e] = bi;
+        if (best_cost) best_cost[e] = bc;
+    }
+}
+
+// fp64 cost of ONE rollout: the body of stmpc_rollouts for a given r (same operations, same order)
+template <bool FAST, typename Ctl, typename... Col>
+__device__ __forceinline__ double stmpc_one_rollout(st_src_t<Ctl> ce, const double* sref, const f1p_stmpc_cfg& cfg, const DynConst& k,
+                                                    const DynState& s0, int r, bool& blocked, const Col&... col) {
+    const int T = cfg.horizon, R = cfg.n_rollouts;
+    DynState s = s0;
+    double cost = 0.0, pdv = 0.0, pa = 0.0;
+    blocked = false;
+    for (int t = 0; t < T; ++t) {
+        float c;
+        if constexpr (st_gen<Ctl>) c = ce.dv(t, r); else c = ce[((size_t)t * 2 + 0) * R + r];
+        double dv = clampd2((double)c, -cfg.max_steer_v, cfg.max_steer_v);
+        if constexpr (st_gen<Ctl>) c = ce.a(); else c = ce[((size_t)t * 2 + 1) * R + r];
+        double a = clampd2((double)c, -cfg.max_accel, cfg.max_accel);
+        if (t > 0) dv = clampd2(dv, pdv - cfg.max_steer_v, pdv + cfg.max_steer_v);
+        const double sv[7] = {s.x, s.y, s.delta, s.v, s.yaw, s.yr, s.beta};
+        double q = 0.0;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) { const double er = sv[j] - sref[j * (T + 1) + t]; q += cfg.q[j] * er * er; }
+        cost += q;
+        cost += cfg.r[0] * dv * dv + cfg.r[1] * a * a;
+        if (t > 0) { const double d0 = dv - pdv, d1 = a - pa; cost += cfg.rd[0] * d0 * d0 + cfg.rd[1] * d1 * d1; }
+        [[maybe_unused]] const double px = s.x, py = s.y;
+        dyn_step<FAST>(s, a, dv, cfg, k);
+        if constexpr (has_col<Col...>) {
+            if (col_of(col...).seg(px, py, s.x, s.y)) { blocked = true; return __builtin_huge_val(); }
+        }
+        pdv = dv; pa = a;
+    }
+    const double sv[7] = {s.x, s.y, s.delta, s.v, s.yaw, s.yr, s.beta};
+    double q = 0.0;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) { const double er = sv[j] - sref[j * (T + 1) + T]; q += cfg.qf[j] * er * er; }
+    cost += q;
+    return cost;
+}
+
+template <int QM, typename Ctl, typename... Col>
+__global__ __launch_bounds__(256) void k_stmpc_filter_t(const double* __restrict__ x0, const double* __restrict__ ref,
+                                                      Ctl ctl, int E, int T, int R, double max_steer_d, DynF32 kf, Col... col,
+                                                      unsigned int* __restrict__ qcount, StItem* __restrict__ items, int32_t* __restrict__ nlist,
+                                                      int32_t* __restrict__ rl, float* __restrict__ dbg_cost32) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+    float* sref32 = reinterpret_cast<float*>(lds_raw);               // [T+1][8] relative to the ego state
+    float* c32 = sref32 + 8 * (T + 1);                                // [R] filter costs (-inf = untrusted)
+    float* red_f = c32 + R;                                           // [4]
+    int* list = reinterpret_cast<int*>(red_f + 4);                    // [F1P_ST_MAX_REFINE]
+    int* cnt = list + F1P_ST_MAX_REFINE;                              // [2]: listed, queue base
+    const int e = blockIdx.x;
+    if (e >= E) return;
+    const double sx = x0[7 * e], sy = x0[7 * e + 1], sdelta = x0[7 * e + 2], sv = x0[7 * e + 3], syaw = x0[7 * e + 4], syr = x0[7 * e + 5], sbeta = x0[7 * e + 6];
+    constexpr bool COL = has_col<Col...>;
+    [[maybe_unused]] double bxd = 0.0, byd = 0.0;
+    bool in_range;                                                   // workgroup-uniform
+    if constexpr (COL) {
+        // the ego's cell (fp64) anchors the filter's cell coordinates; an ego without one is decided in fp64
+        const KmpcCol& c_ = col_of(col...);
+        bxd = (sx - c_.g.ox) * c_.g.inv_res; byd = (sy - c_.g.oy) * c_.g.inv_res;
+        in_range = fabs(syaw) <= 1.0e4 && fabs(max_steer_d) <= 1.0e4 && fabs(sbeta) <= 100.0 && fabs(sdelta) <= 100.0 &&
+                   fabs(bxd) < 1.0e6 && fabs(byd) < 1.0e6;
+    } else {
+        in_range = fabs(syaw) <= 1.0e4 && fabs(max_steer_d) <= 1.0e4 && fabs(sbeta) <= 100.0 && fabs(sdelta) <= 100.0;
+    }
+    if (!in_range) { if (tid == 0) nlist[e] = -1; return; }
+    int bad_ref = 0;                                                 // a non-finite reference in an UNWEIGHTED row makes every fp64 cost NaN (0 * NaN): fp64 decides
+    for (int q = tid; q < 7 * (T + 1); q += blockDim.x) {
+        const double rv = ref[(size_t)e * 7 * (T + 1) + q];
+        const int row = q / (T + 1), t = q - row * (T + 1);
+        sref32[8 * t + row] = (float)(row == 0 ? rv - sx : (row == 1 ? rv - sy : (row == 4 ? rv - syaw : rv)));
+        if (!((QM >> row) & 1) && !(fabs(rv) < __builtin_huge_val())) bad_ref = 1;
+    }
+    if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
+    if constexpr (st_gen<Ctl>) {                                     // the ego's warm start: read T x R times, so from LDS, behind the other arrays
+        float* ws_ = reinterpret_cast<float*>(cnt + 2); const float* wg_ = ctl.warm_row(e);
+        for (int q = tid; q < 2 * T; q += blockDim.x) ws_[q] = wg_[q];
+    }
+    if (__syncthreads_or(bad_ref | ((QM != 0x7f && !(fabs(syr) < __builtin_huge_val())) ? 1 : 0))) { if (tid == 0) nlist[e] = -1; return; }
+    std::conditional_t<st_gen<Ctl>, SrcGenT<true>, const float*> ce;
+    if constexpr (st_gen<Ctl>) ce = ctl.src(e, reinterpret_cast<const float*>(cnt + 2)); else ce = ctl + (size_t)e * T * 2 * R;
+    DynF32 kk;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) { kk.ap[j] = in_vgpr(kf.ap[j]); kk.aq[j] = in_vgpr(kf.aq[j]); }
+#pragma unroll
+    for (int j = 0; j < 7; ++j) { kk.q[j] = in_vgpr(kf.q[j]); kk.qf[j] = kf.qf[j]; }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { kk.r[j] = in_vgpr(kf.r[j]); kk.rd[j] = in_vgpr(kf.rd[j]); }
+    kk.dt = in_vgpr(kf.dt); kk.dt_inv_wb = in_vgpr(kf.dt_inv_wb);
+    kk.max_steer = in_vgpr(kf.max_steer); kk.max_steer_v = in_vgpr(kf.max_steer_v); kk.max_accel = in_vgpr(kf.max_accel);
+    kk.max_speed = in_vgpr(kf.max_speed); kk.min_speed = in_vgpr(kf.min_speed); kk.v_trust = in_vgpr(kf.v_trust);
+    double s0d, c0d;
+    sincos_core(syaw, &s0d, &c0d);
+    kk.c0 = (float)c0d; kk.s0 = (float)s0d;
+    [[maybe_unused]] KmpcColF cf;                                    // (the filter's positions are relative to the ego with the map's axes: unsure<false>)
+    if constexpr (COL) {
+        const KmpcCol& c_ = col_of(col...);
+        const double ibx = __builtin_floor(bxd), iby = __builtin_floor(byd);
+        cf.clear = c_.clear; cf.wwords = c_.g.wwords; cf.n_sub = c_.n_sub; cf.inv_nsub = 1.0f / (float)c_.n_sub;
+        cf.ibx = __builtin_amdgcn_readfirstlane((int)ibx); cf.iby = __builtin_amdgcn_readfirstlane((int)iby);
+        cf.bx = (float)(bxd - ibx); cf.by = (float)(byd - iby);
+        cf.lox = (float)-cf.ibx; cf.hix = (float)(c_.g.w - cf.ibx); cf.loy = (float)-cf.iby; cf.hiy = (float)(c_.g.h - cf.iby);
+        cf.inv_res = (float)c_.g.inv_res; cf.c0 = 1.0f; cf.s0 = 0.0f;
+    }
+    // the odd polynomial of tan is good for |delta| <= 0.45: every later delta is clamped to max_steer, but step 0 evaluates tan(delta0)
+    // UNCLAMPED (dyn_step does, like the reference) -- an out-of-range initial steering state takes the sin / cos path (workgroup-uniform)
+    const bool poly = kf.max_steer <= 0.45f && fabs(sdelta) <= 0.45;
+    float tmin = __builtin_huge_valf();
+    constexpr int NR = F1P_ST_FILTER_NR;
+    for (int rb = tid; rb < R; rb += NR * blockDim.x) {
+        int rr[NR]; float c[NR]; bool trusted[NR];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) rr[i] = rb + i * (int)blockDim.x < R ? rb + i * (int)blockDim.x : rb;   // past the end: a shadow of the first, not stored
+        [[maybe_unused]] bool unsure[NR];                            // a tested point near an occupied cell, off the image or NaN: not FREE
+        if constexpr (COL) {
+#ifdef F1P_ST_DBG_POS    // variant build: dbg_cost32 is [1 + 2 T][E][R] -- the costs, then the f32 (x, y) after every step (tools/stmpc_pos_error.py)
+#define F1P_ST_POS_ARGS , dbg_cost32 ? dbg_cost32 + ((size_t)E + e) * R : nullptr, (size_t)E * R
+#else
+#define F1P_ST_POS_ARGS
+#endif
+            if (poly) stmpc_rollout_f32<true, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted, cf, unsure F1P_ST_POS_ARGS);
+            else stmpc_rollout_f32<false, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted, cf, unsure F1P_ST_POS_ARGS);
+#undef F1P_ST_POS_ARGS
+        } else {
+            if (poly) stmpc_rollout_f32<true, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted);
+            else stmpc_rollout_f32<false, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted);
+        }
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            if (i > 0 && rr[i] == rb) continue;
+            float ci = c[i];
+            if (!trusted[i] || !(ci == ci) || !(fabsf(ci) < 1e30f)) ci = -__builtin_huge_valf();      // untrusted / non-finite: fp64 decides
+            else if constexpr (COL) { if (!unsure[i]) tmin = fminf(tmin, ci); }   // the threshold comes from the FREE rollouts; an UNSURE one keeps its cost and is listed at or below it
+            else tmin = fminf(tmin, ci);
+            c32[rr[i]] = ci;
+            if (dbg_cost32) dbg_cost32[(size_t)e * R + rr[i]] = ci;
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) tmin = fminf(tmin, __shfl_xor(tmin, m, 64));
+    if (lane == 0) red_f[wave] = tmin;
+    __syncthreads();
+    tmin = red_f[0];
+    for (int w = 1; w < nwaves; ++w) tmin = fminf(tmin, red_f[w]);
+    // (no trusted rollout: tmin = +inf, thr = +inf and every rollout is listed -> fallback)
+    const float thr = tmin + (fabsf(tmin) * fminf(F1P_ST_MARGIN_REL * (float)T, 0.5f) + F1P_ST_MARGIN_ABS);
+    for (int r = tid; r < R; r += blockDim.x) {
+        if (!(c32[r] > thr)) {
+            const int pos = atomicAdd(cnt, 1);
+            if (pos < F1P_ST_MAX_REFINE) list[pos] = r;
+        }
+    }
+    __syncthreads();
+    const int n = cnt[0];
+    const bool fallback = n > F1P_ST_MAX_REFINE || n < 1 || !(tmin < __builtin_huge_valf());
+    if (fallback) { if (tid == 0) nlist[e] = -1; return; }
+    if (tid == 0) { cnt[1] = (int)atomicAdd(qcount, (unsigned int)n); nlist[e] = n; }
+    __syncthreads();
+    if (tid < n) {
+        const int r = list[tid];
+        rl[(size_t)e * F1P_ST_MAX_REFINE + tid] = r;
+        StItem it; it.es = e * F1P_ST_MAX_REFINE + tid; it.r = r;
+        items[(size_t)cnt[1] + tid] = it;
+    }
+}
+
+// ---- K-B: fp64 costs of the queued rollouts, one lane each, packed across egos (stmpc_rollouts' own arithmetic) ----------------
+// ~1 rollout per ego survives the filter, so this kernel is a few dozen waves running 40 sequential fp64 steps: 1.3 us per step (34 us
+// for a single wave of 17 rollouts, 52 us at 1024 egos), latency of the dependent fp64 chain and not throughput.  This kernel now only
+// serves horizons > 63; k_stmpc_refine_tp below is what runs.  Measured and NOT kept
+// (profiles/r03_stmpc_filter.md): splitting the step's independent chains over four waves with an LDS exchange per step, staging the
+// controls in LDS and batching the reference loads -- each left the time where it was.
+template <typename Ctl, typename... Col>
+__global__ __launch_bounds__(64) void k_stmpc_refine_t(const double* __restrict__ x0, const double* __restrict__ ref, Ctl ctl,
+                                                     f1p_stmpc_cfg cfg, const unsigned int* __restrict__ qcount, const StItem* __restrict__ items,
+                                                     Col... col, double* __restrict__ rc) {
+    const unsigned int count = *qcount;
+    const int T = cfg.horizon, R = cfg.n_rollouts;
+    const DynConst k = dyn_const(cfg);
+    for (unsigned int i = blockIdx.x * 64u + threadIdx.x; i < count; i += gridDim.x * 64u) {
+        const StItem it = items[i];
+        const int e = it.es / F1P_ST_MAX_REFINE;
+        DynState s0;
+        s0.x = x0[7 * e]; s0.y = x0[7 * e + 1]; s0.delta = x0[7 * e + 2]; s0.v = x0[7 * e + 3]; s0.yaw = x0[7 * e + 4];
+        s0.yr = x0[7 * e + 5]; s0.beta = x0[7 * e + 6];
+        st_ego_t<Ctl> ce;
+        if constexpr (st_gen<Ctl>) ce = StGenSrc{ctl.src(e, ctl.warm_row(e)), 0.0f}; else ce = ctl + (size_t)e * T * 2 * R;
+        bool blocked;
+        rc[it.es] = stmpc_one_rollout<true, Ctl>(ce, ref + (size_t)e * 7 * (T + 1), cfg, k, s0, it.r, blocked, col...);
+        if constexpr (has_col<Col...>) { if (blocked) col_of(col...).rl[it.es] = F1P_K4_NONE; }   // (its cost is +inf: the pair loses to every unblocked item)
+    }
+}
+
+template <typename Ctl, typename... Col>
+__global__ __launch_bounds__(256) void k_stmpc_refine_tp_t(const double* __restrict__ x0, const double* __restrict__ ref, Ctl ctl,
+                                                        f1p_stmpc_cfg cfg, const unsigned int* __restrict__ qcount, const StItem* __restrict__ items,
+                                                        Col... col, double* __restrict__ rc, float* __restrict__ dbg_ticks) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#ifdef F1P_ST_PHASES
+    long long ph[12]; int nph = 0;
+#endif
+    unsigned char* wl = lds_raw + (size_t)wave * F1P_ST_TP_LDS_PER_WAVE;
+    StS1* __restrict__ s1 = reinterpret_cast<StS1*>(wl);
+    StS3* __restrict__ s3 = reinterpret_cast<StS3*>(wl + 64 * sizeof(StS1));
+    StO3* __restrict__ o3 = reinterpret_cast<StO3*>(wl + 64 * (sizeof(StS1) + sizeof(StS3)));
+    StXY* __restrict__ s6 = reinterpret_cast<StXY*>(wl + 64 * (sizeof(StS1) + sizeof(StS3) + sizeof(StO3)));
+    StXY* __restrict__ o6 = reinterpret_cast<StXY*>(wl + 64 * (sizeof(StS1) + sizeof(StS3) + sizeof(StO3) + sizeof(StXY)));
+    StC* __restrict__ cr = reinterpret_cast<StC*>(wl + 64 * (sizeof(StS1) + sizeof(StS3) + sizeof(StO3) + 2 * sizeof(StXY)));
+    const unsigned int count = *qcount;
+    const int T = cfg.horizon, R = cfg.n_rollouts;
+    const DynConst k = dyn_const(cfg);
+    const unsigned int nw = gridDim.x * (blockDim.x >> 6);
+    for (unsigned int i = blockIdx.x * (blockDim.x >> 6) + wave; i < count; i += nw) {   // wave-uniform
+        F1P_STPH();
+        const StItem it = items[i];
+        const int e = it.es / F1P_ST_MAX_REFINE;
+        const int t = lane;
+        const bool act = t < T, act1 = t <= T;
+        st_ego_t<Ctl> cp;                                                 // [t][2][R], or regenerated: step t of rollout r is a pure function of (e, r, t)
+        if constexpr (st_gen<Ctl>) cp = StGenSrc{ctl.src(e, ctl.warm_row(e)), 0.0f}; else cp = ctl + (size_t)e * T * 2 * R + it.r;
+        const double* sref = ref + (size_t)e * 7 * (T + 1);
+        float c_dv, c_a;
+        if constexpr (st_gen<Ctl>) { c_dv = act ? cp.dv(t, it.r) : 0.0f; c_a = act ? cp.a() : 0.0f; }
+        else { c_dv = act ? cp[(size_t)t * 2 * R] : 0.0f; c_a = act ? cp[(size_t)t * 2 * R + R] : 0.0f; }
+        double rf[7];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) rf[j] = act1 ? sref[j * (T + 1) + t] : 0.0;
+        DynState s0;
+        s0.x = x0[7 * e]; s0.y = x0[7 * e + 1]; s0.delta = x0[7 * e + 2]; s0.v = x0[7 * e + 3]; s0.yaw = x0[7 * e + 4];
+        s0.yr = x0[7 * e + 5]; s0.beta = x0[7 * e + 6];
+        // ---- 1. controls: the bounds in parallel, the rate clamp and the two clamped running sums in sequence ----------------------
+        const double my_a = clampd2((double)c_a, -cfg.max_accel, cfg.max_accel);         // :704-706
+        {
+            StS1 w1; w1.u = clampd2((double)c_dv, -cfg.max_steer_v, cfg.max_steer_v); w1.a = my_a;   // :701-703
+            s1[t] = w1;
+        }
+        wave_lds_sync();
+        F1P_STPH();
+        double my_dv = 0.0, my_delta = 0.0, my_v = 0.0;
+        {
+            double dlt = s0.delta, v = s0.v, pdv = 0.0;
+#pragma unroll 4
+            for (int q = 0; q < T; ++q) {
+                const StS1 cur = s1[q];
+                double dv = cur.u;
+                if (q > 0) dv = clampd2(dv, pdv - cfg.max_steer_v, pdv + cfg.max_steer_v);   // :685
+                if (lane == 0) { StO3 w; w.yr = dv; w.beta = dlt; w.yaw = v; w.pad = 0.0; o3[q] = w; }   // (o3 is free until phase 3: one LDS write instead of six selects)
+                const double delta_new = dlt + dv * cfg.dt;               // :360
+                const double v_new = v + cur.a * cfg.dt;                  // :361
+                v = v_new > cfg.max_speed ? cfg.max_speed : (v_new < cfg.min_speed ? cfg.min_speed : v_new);               // :393-396
+                dlt = delta_new >= cfg.max_steer ? cfg.max_steer : (delta_new <= -cfg.max_steer ? -cfg.max_steer : delta_new);   // :399-402
+                pdv = dv;
+            }
+            if (lane == 0) { StO3 w; w.yr = 0.0; w.beta = dlt; w.yaw = v; w.pad = 0.0; o3[T] = w; }
+        }
+        wave_lds_sync();
+        if (act1) { const StO3 w = o3[t]; my_dv = w.yr; my_delta = w.beta; my_v = w.yaw; }
+        wave_lds_sync();
+        F1P_STPH();
+        // ---- 2. per step: coefficients of the (yr, beta) recurrence and the yaw increment ----------------------------------------
+        if (act) {
+            const double Tz = k.gl_r - (my_a * k.h);                      // :343
+            const double Vz = k.gl_f + (my_a * k.h);                      // :344
+            const double A1 = k.K * k.F * Tz;                             // :350-355
+            const double A2 = k.K * (k.R * Vz - k.F * Tz);
+            const double A3 = k.K * (k.lf2cf * Tz + k.lr2cr * Vz);
+            const double A4 = k.M * Tz;
+            const double A5 = k.N * Vz + k.M * Tz;
+            const double A6 = k.N * Vz * k.l_r - k.M * Tz * k.l_f;
+            double sd, cd;
+            sincos_core(my_delta, &sd, &cd);
+            const double tn = sd / cd;
+            StS3 w3;
+            w3.P1 = A1 * my_delta; w3.A2 = A2; w3.A3 = A3; w3.A4d = A4 * (my_delta / my_v); w3.A5 = A5; w3.A6 = A6;
+            w3.v = my_v; w3.vv = my_v * my_v; w3.w = my_v / cfg.wheelbase * tn * cfg.dt; w3.pad = 0.0;
+            s3[t] = w3;
+        }
+        wave_lds_sync();
+        F1P_STPH();
+        // ---- 3. the recurrence: yr, beta (and yaw's running sum beside them) ------------------------------------------------------
+        {
+            double yr = s0.yr, beta = s0.beta, yaw = s0.yaw;
+#pragma unroll 4
+            for (int q = 0; q < T; ++q) {
+                const StS3 cur = s3[q];
+                if (lane == 0) { StO3 w; w.yr = yr; w.beta = beta; w.yaw = yaw; w.pad = 0.0; o3[q] = w; }
+                const double yr_new = yr + (cur.P1 + cur.A2 * beta - cur.A3 * (yr / cur.v)) * cfg.dt;                       // :367-371
+                const double beta_new = beta + (cur.A4d - cur.A5 * (beta / cur.v) + cur.A6 * (yr / cur.vv) - yr) * cfg.dt;   // :372-381
+                yaw = yaw + cur.w;                                                                                          // :362-365
+                yr = yr_new; beta = beta_new;
+            }
+            if (lane == 0) { StO3 w; w.yr = yr; w.beta = beta; w.yaw = yaw; w.pad = 0.0; o3[T] = w; }
+        }
+        wave_lds_sync();
+        F1P_STPH();
+        double my_yr = 0.0, my_beta = 0.0, my_yaw = 0.0;
+        if (act1) { const StO3 w = o3[t]; my_yr = w.yr; my_beta = w.beta; my_yaw = w.yaw; }
+        // ---- 4. x / y increments --------------------------------------------------------------------------------------------------
+        if (act) {
+            double sn, cs;
+            sincos_fast(my_yaw + my_beta, &sn, &cs);
+            StXY w; w.x = my_v * cs * cfg.dt; w.y = my_v * sn * cfg.dt;   // :358-359
+            s6[t] = w;
+        }
+        wave_lds_sync();
+        F1P_STPH();
+        // ---- 5. x, y ---------------------------------------------------------------------------------------------------------------
+        {
+            double x = s0.x, y = s0.y;
+#pragma unroll 8
+            for (int q = 0; q < T; ++q) {
+                const StXY cur = s6[q];
+                if (lane == 0) { StXY w; w.x = x; w.y = y; o6[q] = w; }
+                x = x + cur.x; y = y + cur.y;
+            }
+            if (lane == 0) { StXY w; w.x = x; w.y = y; o6[T] = w; }
+        }
+        wave_lds_sync();
+        F1P_STPH();
+        // ---- 5b. lane t tests the points of step t -> t + 1 (x_t, y_t are stmpc_rollouts' own values); a ballot ORs the verdicts --------
+        [[maybe_unused]] bool blocked = false;
+        if constexpr (has_col<Col...>) {
+            bool hit = false;
+            if (act) { const StXY p = o6[t], q = o6[t + 1]; hit = col_of(col...).seg(p.x, p.y, q.x, q.y); }
+            blocked = __ballot(hit) != 0ull;
+        }
+        // ---- 6. cost rows ----------------------------------------------------------------------------------------------------------
+        {
+            const double p_dv = shfl_d(my_dv, lane > 0 ? lane - 1 : 0), p_a = shfl_d(my_a, lane > 0 ? lane - 1 : 0);
+            StC w; w.q = 0.0; w.r = 0.0; w.rd = 0.0; w.pad = 0.0;
+            if (act1) {
+                const StXY xy = o6[t];
+                const double sv[7] = {xy.x, xy.y, my_delta, my_v, my_yaw, my_yr, my_beta};
+                double q = 0.0;
+                if (act) {
+#pragma unroll
+                    for (int j = 0; j < 7; ++j) { const double er = sv[j] - rf[j]; q += cfg.q[j] * er * er; }    // :619
+                    w.r = cfg.r[0] * my_dv * my_dv + cfg.r[1] * my_a * my_a;                                     // :616
+                    if (t > 0) { const double d0 = my_dv - p_dv, d1 = my_a - p_a; w.rd = cfg.rd[0] * d0 * d0 + cfg.rd[1] * d1 * d1; }   // :622
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 7; ++j) { const double er = sv[j] - rf[j]; q += cfg.qf[j] * er * er; }
+                }
+                w.q = q;
+                cr[t] = w;
+            }
+        }
+        wave_lds_sync();
+        F1P_STPH();
+        // ---- 7. the running sum, in stmpc_rollouts' order ---------------------------------------------------------------------------
+        {
+            double cost = 0.0;
+#pragma unroll 8
+            for (int q = 0; q < T; ++q) {
+                const StC cur = cr[q];
+                cost += cur.q;
+                cost += cur.r;
+                if (q > 0) cost += cur.rd;
+            }
+            cost += cr[T].q;                                              // the terminal row (Qf)
+            if constexpr (has_col<Col...>) { if (lane == 0) { rc[it.es] = blocked ? __builtin_huge_val() : cost; if (blocked) col_of(col...).rl[it.es] = F1P_K4_NONE; } }
+            else if (lane == 0) rc[it.es] = cost;
+        }
+        wave_lds_sync();
+#ifdef F1P_ST_PHASES
+        F1P_STPH();
+        if (dbg_ticks && lane == 0 && i < 4096u) { for (int q = 0; q + 1 < nph; ++q) dbg_ticks[i * 16u + q] = (float)(ph[q + 1] - ph[q]); dbg_ticks[i * 16u + 15] = (float)nph; }
+        nph = 0;
+#endif
+    }
+}
+
+// ---- K-C: np.argmin's rule over the refined costs (or the all-fp64 loop for the egos the filter gave up on), outputs -------------
+template <typename Ctl, typename... Col>
+__global__ __launch_bounds__(256) void k_stmpc_decide_t(const double* __restrict__ x0, const double* __restrict__ ref,
+                                                      Ctl ctl, int E, f1p_stmpc_cfg cfg,
+                                                      unsigned int* __restrict__ qcount, const int32_t* __restrict__ nlist, const int32_t* __restrict__ rl,
+                                                      const double* __restrict__ rc, Col... col,
+                                                      double* __restrict__ steer, double* __restrict__ speed,
+                                                      int32_t* __restrict__ best_idx, double* __restrict__ best_cost,
+                                                      double* __restrict__ best_seq, int32_t* __restrict__ dbg_nref) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const int T = cfg.horizon, R = cfg.n_rollouts, tid = threadIdx.x;
+    double* sref = reinterpret_cast<double*>(lds_raw);                // [7][T+1] (fallback only)
+    double* red_d = sref + 7 * (T + 1);                               // [4]
+    int* red_i = reinterpret_cast<int*>(red_d + 4);                   // [4]
+    const int e = blockIdx.x;
+    if (e >= E) return;
+    if (e == 0 && tid == 0) *qcount = 0u;                             // re-arm the queue for the next plan (k_stmpc_refine has finished)
+    int n = nlist[e];
+    DynState s0;
+    s0.x = x0[7 * e]; s0.y = x0[7 * e + 1]; s0.delta = x0[7 * e + 2]; s0.v = x0[7 * e + 3]; s0.yaw = x0[7 * e + 4];
+    s0.yr = x0[7 * e + 5]; s0.beta = x0[7 * e + 6];
+    st_ego_t<Ctl> ce;
+    if constexpr (st_gen<Ctl>) ce = StGenSrc{ctl.src(e, ctl.warm_row(e)), 0.0f}; else ce = ctl + (size_t)e * T * 2 * R;
+    double bc = __builtin_huge_val(); int bi = 0x7fffffff;
+    if constexpr (has_col<Col...>) {
+        if (n >= 0) {                                                 // a blocked item is (+inf, F1P_K4_NONE): it loses to every unblocked one
+            if (tid < n) {
+                bc = rc[(size_t)e * F1P_ST_MAX_REFINE + tid];
+                bi = rl[(size_t)e * F1P_ST_MAX_REFINE + tid];
+            }
+            block_argmin(bc, bi, red_d, red_i);
+            // every listed rollout blocked: the list holds the FREE minimum, which the position bound proves unblocked, so this is not expected --
+            // the ego is decided by the all-fp64 loop rather than declared blocked on the filter's word (workgroup-uniform)
+            if (bi == F1P_K4_NONE) { n = -1; bc = __builtin_huge_val(); __syncthreads(); }
+        }
+    }
+    if (n < 0) {                                                      // workgroup-uniform
+        for (int q = tid; q < 7 * (T + 1); q += blockDim.x) sref[q] = ref[(size_t)e * 7 * (T + 1) + q];
+        __syncthreads();
+        const DynConst k = dyn_const(cfg);
+        if (fabs(cfg.max_steer) <= 1.0e4) stmpc_rollouts<true, Ctl>(ce, sref, cfg, k, s0, tid, bc, bi, col...);
+        else stmpc_rollouts<false, Ctl>(ce, sref, cfg, k, s0, tid, bc, bi, col...);
+        if constexpr (has_col<Col...>) block_argmin(bc, bi, red_d, red_i);
+    } else if constexpr (!has_col<Col...>) {
+        if (tid < n) {
+            bc = rc[(size_t)e * F1P_ST_MAX_REFINE + tid];
+            bi = rl[(size_t)e * F1P_ST_MAX_REFINE + tid];
+        }
+    }
+    if constexpr (has_col<Col...>) {
+        if (bi == F1P_K4_NONE) {                                      // every rollout blocked (workgroup-uniform): the lattice's ALL_BLOCKED outputs
+            for (int q = tid; q < 2 * T; q += blockDim.x) {
+                if (best_seq) best_seq[(size_t)e * T * 2 + q] = 0.0;
+                if constexpr (st_gen<Ctl>) ctl.warm_row(e)[q] = 0.0f;
+            }
+            if (tid == 0) {
+                steer[e] = 0.0; speed[e] = 0.0; best_idx[e] = -1;
+                if (best_cost) best_cost[e] = __builtin_huge_val();
+                if (dbg_nref) dbg_nref[e] = n;
+            }
+            return;
+        }
+    } else {
+        block_argmin(bc, bi, red_d, red_i);
+    }
+    [[maybe_unused]] float* emit_s = reinterpret_cast<float*>(lds_raw);
+    if constexpr (st_gen<Ctl>) {
+        for (int t_ = tid; t_ < T; t_ += blockDim.x) ce.g.get(t_, bi, emit_s[2 * t_], emit_s[2 * t_ + 1]);
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double pdv = 0.0;
+        for (int t = 0; t < T; ++t) {
+            float c;
+            if constexpr (st_gen<Ctl>) c = emit_s[2 * t]; else c = ce[((size_t)t * 2 + 0) * R + bi];
+            double dv = clampd2((double)c, -cfg.max_steer_v, cfg.max_steer_v);
+            if constexpr (st_gen<Ctl>) c = emit_s[2 * t + 1]; else c = ce[((size_t)t * 2 + 1) * R + bi];
+            const double a = clampd2((double)c, -cfg.max_accel, cfg.max_accel);
+            if (t > 0) dv = clampd2(dv, pdv - cfg.max_steer_v, pdv + cfg.max_steer_v);
+            if (t == 0) {
+                steer[e] = s0.delta + dv * cfg.dt;   // :1112
+                speed[e] = s0.v + a * cfg.dt;        // :1117
+            }
+            if (best_seq) { best_seq[((size_t)e * T + t) * 2] = dv; best_seq[((size_t)e * T + t) * 2 + 1] = a; }
+            else if constexpr (!st_gen<Ctl>) { if (t == 0) break; }
+            if constexpr (st_gen<Ctl>) {
+                float* wo_ = ctl.warm_row(e);
+                if (t > 0) { wo_[2 * (t - 1)] = (float)dv; wo_[2 * (t - 1) + 1] = (float)a; }
+                if (t == T - 1) { wo_[2 * t] = (float)dv; wo_[2 * t + 1] = (float)a; }
+            }
+            pdv = dv;
+        }
+        best_idx[e] = bi;
+        if (best_cost) best_cost[e] = bc;
+        if (dbg_nref) dbg_nref[e] = n;
+    }
+}
+
+// the kernels under the names their launches, the profiles and bench.py's labels know them by: streamed controls (f1p_stmpc_shoot_*),
+// generated controls (_gen: f1p_stmpc_plan_*), and with the occupancy test (_col).  (The launches below go through the templates: one helper per
+// schedule over the source and the test.)
+[[maybe_unused]] static constexpr auto k_stmpc_shoot = k_stmpc_shoot_t<StCtlStream>;
+[[maybe_unused]] static constexpr auto k_stmpc_shoot_gen = k_stmpc_shoot_t<StCtlGen>;
+[[maybe_unused]] static constexpr auto k_stmpc_shoot_col = k_stmpc_shoot_t<StCtlStream, KmpcCol>;
+[[maybe_unused]] static constexpr auto k_stmpc_shoot_gen_col = k_stmpc_shoot_t<StCtlGen, KmpcCol>;
+template <int QM> [[maybe_unused]] static constexpr auto k_stmpc_filter = k_stmpc_filter_t<QM, StCtlStream>;
+template <int QM> [[maybe_unused]] static constexpr auto k_stmpc_filter_gen = k_stmpc_filter_t<QM, StCtlGen>;
+template <int QM> [[maybe_unused]] static constexpr auto k_stmpc_filter_gen_col = k_stmpc_filter_t<QM, StCtlGen, KmpcCol>;
+[[maybe_unused]] static constexpr auto k_stmpc_refine = k_stmpc_refine_t<StCtlStream>;
+[[maybe_unused]] static constexpr auto k_stmpc_refine_gen = k_stmpc_refine_t<StCtlGen>;
+[[maybe_unused]] static constexpr auto k_stmpc_refine_gen_col = k_stmpc_refine_t<StCtlGen, StColRef>;
+[[maybe_unused]] static constexpr auto k_stmpc_refine_tp = k_stmpc_refine_tp_t<StCtlStream>;
+[[maybe_unused]] static constexpr auto k_stmpc_refine_tp_gen = k_stmpc_refine_tp_t<StCtlGen>;
+[[maybe_unused]] static constexpr auto k_stmpc_refine_tp_gen_col = k_stmpc_refine_tp_t<StCtlGen, StColRef>;
+[[maybe_unused]] static constexpr auto k_stmpc_decide = k_stmpc_decide_t<StCtlStream>;
+[[maybe_unused]] static constexpr auto k_stmpc_decide_gen = k_stmpc_decide_t<StCtlGen>;
+[[maybe_unused]] static constexpr auto k_stmpc_decide_gen_col = k_stmpc_decide_t<StCtlGen, KmpcCol>;
 
 // materialise the generator's controls as the [E][T][2][R] f32 buffer of the streamed entry points (tests: generated == streamed)
 __global__ __launch_bounds__(256) void k_stmpc_gen_controls(float* __restrict__ controls, int E, int T, int R, StCtlGen ctl) {
@@ -622,18 +1080,57 @@ static double st_pos_err_bound(const f1p_stmpc_cfg* cfg) {
 }
 #define F1P_ST_POS_HEADROOM 5.0        // the filter gets the clearance map only while headroom x bound < one cell (DESIGN.md 5h's factor)
 
+// the mixed schedule, filter -> refinement -> decision, over the control source and the optional occupancy test
+template <typename Ctl, typename... Col>
+static int stmpc_mixed(f1p_ctx* ctx, const double* d_x0, const double* d_ref, Ctl ctl, int E, const f1p_stmpc_cfg* cfg, const DynF32& kf, size_t lds_a, size_t lds_c,
+                       double* d_steer, double* d_speed, int32_t* d_best_idx, double* d_best_cost, double* d_best_seq, Col... col) {
+    constexpr bool COL = sizeof...(Col) > 0;                         // (the error strings name the kernels as they always did)
+    StScratch sc;
+    if (const int rs = st_scratch(ctx, E, sc)) return rs;
+    int qm = 0;                                                      // rows that carry weight in the stage or the terminal cost
+    for (int j = 0; j < 7; ++j) if (cfg->q[j] != 0.0 || cfg->qf[j] != 0.0) qm |= 1 << j;
+    // 0x1b: the reference's weights (x, y, v, yaw): the delta / yr / beta terms are not evaluated
+    hipLaunchKernelGGL(qm == 0x1b ? (k_stmpc_filter_t<0x1b, Ctl, Col...>) : (k_stmpc_filter_t<0x7f, Ctl, Col...>), dim3(E), dim3(256), (lds_a + 15) & ~(size_t)15,
+                       ctx->stream, d_x0, d_ref, ctl, E, cfg->horizon, cfg->n_rollouts, cfg->max_steer, kf, col..., sc.qcount, sc.items, sc.nlist, sc.rl, ctx->d_dbg_st_cost32);
+    int rcode = check_hip(ctx, hipGetLastError(), COL ? "k_stmpc_filter_gen_col launch" : "k_stmpc_filter launch");
+    if (rcode != F1P_OK) return rcode;
+    if (cfg->horizon <= 63 && 4 * F1P_ST_TP_LDS_PER_WAVE <= (size_t)ctx->prop.sharedMemPerBlock) {
+        const int nb = E * F1P_ST_MAX_REFINE / 4 < 2 * ctx->prop.multiProcessorCount ? (E * F1P_ST_MAX_REFINE + 3) / 4 : 2 * ctx->prop.multiProcessorCount;
+        hipLaunchKernelGGL((k_stmpc_refine_tp_t<Ctl, decltype(StColRef{col, sc.rl})...>), dim3(nb), dim3(256), 4 * F1P_ST_TP_LDS_PER_WAVE, ctx->stream, d_x0, d_ref, ctl,
+                           *cfg, sc.qcount, sc.items, StColRef{col, sc.rl}..., sc.rc, COL ? (float*)nullptr : ctx->d_dbg_st_cost32);
+    } else {
+        hipLaunchKernelGGL((k_stmpc_refine_t<Ctl, decltype(StColRef{col, sc.rl})...>), dim3(E), dim3(64), 0, ctx->stream, d_x0, d_ref, ctl, *cfg, sc.qcount, sc.items,
+                           StColRef{col, sc.rl}..., sc.rc);
+    }
+    rcode = check_hip(ctx, hipGetLastError(), COL ? "k_stmpc_refine_gen_col launch" : "k_stmpc_refine launch");
+    if (rcode != F1P_OK) return rcode;
+    hipLaunchKernelGGL((k_stmpc_decide_t<Ctl, Col...>), dim3(E), dim3(256), (lds_c + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, ctl, E, *cfg, sc.qcount,
+                       sc.nlist, sc.rl, sc.rc, col..., d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_st_nref);
+    rcode = check_hip(ctx, hipGetLastError(), COL ? "k_stmpc_decide_gen_col launch" : "k_stmpc_decide launch");
+    if (rcode == F1P_OK) ctx->st_q_dirty = false;
+    return rcode;
+}
+
 // the schedule of f1p_stmpc_shoot_* (gen == nullptr: streamed d_controls) and of f1p_stmpc_plan_* (gen: generated controls, d_controls unused)
 static int stmpc_shoot_any(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const float* d_controls, const StCtlGen* gen, int E, const f1p_stmpc_cfg* cfg,
                            double* d_steer, double* d_speed, int32_t* d_best_idx, double* d_best_cost, double* d_best_seq) {
     if (E <= 0) return F1P_OK;
     const size_t T1 = (size_t)cfg->horizon + 1;
+    const size_t lds = sizeof(double) * (7 * T1 + 4) + sizeof(int) * 4;   // the plain-fp64 kernel's, and the decision's
+    // the plain-fp64 evaluation, over the control source and the optional occupancy test
+    auto shoot = [&](const char* what, auto... col) {
+        if (gen) hipLaunchKernelGGL((k_stmpc_shoot_t<StCtlGen, decltype(col)...>), dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, *cfg, col...,
+                                    d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
+        else hipLaunchKernelGGL((k_stmpc_shoot_t<StCtlStream, decltype(col)...>), dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E, *cfg, col...,
+                                d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
+        return check_hip(ctx, hipGetLastError(), what);
+    };
     if (ctx->stmpc_collision) {
         // the occupancy test (the caller checked the grid: stmpc_collision_check).  Streamed controls: plain fp64 in every mode, so that
         // gen_controls + shoot == plan bit for bit.  Generated controls in the mixed mode: filter -> refinement -> decision with the test, as
         // long as the f32 position bound (with its headroom) stays below one cell and the clearance map can be built; otherwise plain fp64.
         KmpcCol col;
         col.g = grid_dev(ctx); col.clear = nullptr; col.n_sub = ctx->stmpc_col_nsub; col.force64 = 1;
-        const size_t lds = sizeof(double) * (7 * T1 + 4) + sizeof(int) * 4;
         if (lds > (size_t)ctx->prop.sharedMemPerBlock) return set_error(ctx, F1P_EINVAL, "stmpc: the horizon needs more LDS than a workgroup has");
         if (gen && ctx->stmpc_mixed) {
             const DynF32 kf = make_dyn_f32(cfg);
@@ -641,91 +1138,21 @@ static int stmpc_shoot_any(f1p_ctx* ctx, const double* d_x0, const double* d_ref
             if (lds_a <= (size_t)ctx->prop.sharedMemPerBlock && kf.v_trust == kf.v_trust && (size_t)E * F1P_ST_MAX_REFINE < ((size_t)1 << 31) &&
                 F1P_ST_POS_HEADROOM * st_pos_err_bound(cfg) * ctx->inv_res < 1.0 && ensure_clear_map(ctx, F1P_K4_CLEAR_CELLS) == F1P_OK) {
                 col.clear = ctx->d_bits_clear; col.force64 = 0;
-                StScratch sc;
-                if (const int rs = st_scratch(ctx, E, sc)) return rs;
-                int qm = 0;
-                for (int j = 0; j < 7; ++j) if (cfg->q[j] != 0.0 || cfg->qf[j] != 0.0) qm |= 1 << j;
-                if (qm == 0x1b)
-                    hipLaunchKernelGGL(k_stmpc_filter_gen_col<0x1b>, dim3(E), dim3(256), (lds_a + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, cfg->horizon,
-                                       cfg->n_rollouts, cfg->max_steer, kf, col, sc.qcount, sc.items, sc.nlist, sc.rl, ctx->d_dbg_st_cost32);
-                else
-                    hipLaunchKernelGGL(k_stmpc_filter_gen_col<0x7f>, dim3(E), dim3(256), (lds_a + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, cfg->horizon,
-                                       cfg->n_rollouts, cfg->max_steer, kf, col, sc.qcount, sc.items, sc.nlist, sc.rl, ctx->d_dbg_st_cost32);
-                int rcode = check_hip(ctx, hipGetLastError(), "k_stmpc_filter_gen_col launch");
-                if (rcode != F1P_OK) return rcode;
-                if (cfg->horizon <= 63 && 4 * F1P_ST_TP_LDS_PER_WAVE <= (size_t)ctx->prop.sharedMemPerBlock) {
-                    const int nb = E * F1P_ST_MAX_REFINE / 4 < 2 * ctx->prop.multiProcessorCount ? (E * F1P_ST_MAX_REFINE + 3) / 4 : 2 * ctx->prop.multiProcessorCount;
-                    hipLaunchKernelGGL(k_stmpc_refine_tp_gen_col, dim3(nb), dim3(256), 4 * F1P_ST_TP_LDS_PER_WAVE, ctx->stream, d_x0, d_ref, *gen, *cfg, sc.qcount,
-                                       sc.items, col, sc.rl, sc.rc, (float*)nullptr);
-                } else {
-                    hipLaunchKernelGGL(k_stmpc_refine_gen_col, dim3(E), dim3(64), 0, ctx->stream, d_x0, d_ref, *gen, *cfg, sc.qcount, sc.items, col, sc.rl, sc.rc);
-                }
-                rcode = check_hip(ctx, hipGetLastError(), "k_stmpc_refine_gen_col launch");
-                if (rcode != F1P_OK) return rcode;
-                hipLaunchKernelGGL(k_stmpc_decide_gen_col, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, *cfg, sc.qcount,
-                                   sc.nlist, sc.rl, sc.rc, col, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_st_nref);
-                rcode = check_hip(ctx, hipGetLastError(), "k_stmpc_decide_gen_col launch");
-                if (rcode == F1P_OK) ctx->st_q_dirty = false;
-                return rcode;
+                return stmpc_mixed(ctx, d_x0, d_ref, *gen, E, cfg, kf, lds_a, lds, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, col);
             }
         }
-        if (gen) hipLaunchKernelGGL(k_stmpc_shoot_gen_col, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, *cfg, col,
-                                    d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
-        else hipLaunchKernelGGL(k_stmpc_shoot_col, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E, *cfg, col,
-                                d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
-        return check_hip(ctx, hipGetLastError(), "k_stmpc_shoot_col launch");
+        return shoot("k_stmpc_shoot_col launch", col);
     }
     if (ctx->stmpc_mixed) {
         const DynF32 kf = make_dyn_f32(cfg);
         const size_t lds_a = sizeof(float) * (8 * T1 + (size_t)cfg->n_rollouts + 4) + sizeof(int) * (F1P_ST_MAX_REFINE + 2) +
                              (gen ? sizeof(float) * 2 * (size_t)cfg->horizon : 0);   // + the ego's warm start
-        const size_t lds_c = sizeof(double) * (7 * T1 + 4) + sizeof(int) * 4;
-        if (lds_a <= (size_t)ctx->prop.sharedMemPerBlock && lds_c <= (size_t)ctx->prop.sharedMemPerBlock && kf.v_trust == kf.v_trust &&
-            (size_t)E * F1P_ST_MAX_REFINE < ((size_t)1 << 31)) {
-            StScratch sc;
-            if (const int rs = st_scratch(ctx, E, sc)) return rs;
-            unsigned int* qcount = sc.qcount; int32_t *nlist = sc.nlist, *rl = sc.rl; StItem* items = sc.items; double* rc = sc.rc;
-            int qm = 0;                                              // rows that carry weight in the stage or the terminal cost
-            for (int j = 0; j < 7; ++j) if (cfg->q[j] != 0.0 || cfg->qf[j] != 0.0) qm |= 1 << j;
-            if (gen && qm == 0x1b)
-                hipLaunchKernelGGL(k_stmpc_filter_gen<0x1b>, dim3(E), dim3(256), (lds_a + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, cfg->horizon,
-                                   cfg->n_rollouts, cfg->max_steer, kf, qcount, items, nlist, rl, ctx->d_dbg_st_cost32);
-            else if (gen)
-                hipLaunchKernelGGL(k_stmpc_filter_gen<0x7f>, dim3(E), dim3(256), (lds_a + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, cfg->horizon,
-                                   cfg->n_rollouts, cfg->max_steer, kf, qcount, items, nlist, rl, ctx->d_dbg_st_cost32);
-            else if (qm == 0x1b)                                    // the reference's weights (x, y, v, yaw): the delta / yr / beta terms are not evaluated
-                hipLaunchKernelGGL(k_stmpc_filter<0x1b>, dim3(E), dim3(256), (lds_a + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E, cfg->horizon,
-                                   cfg->n_rollouts, cfg->max_steer, kf, qcount, items, nlist, rl, ctx->d_dbg_st_cost32);
-            else
-                hipLaunchKernelGGL(k_stmpc_filter<0x7f>, dim3(E), dim3(256), (lds_a + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E, cfg->horizon,
-                                   cfg->n_rollouts, cfg->max_steer, kf, qcount, items, nlist, rl, ctx->d_dbg_st_cost32);
-            int rcode = check_hip(ctx, hipGetLastError(), "k_stmpc_filter launch");
-            if (rcode != F1P_OK) return rcode;
-            if (cfg->horizon <= 63 && 4 * F1P_ST_TP_LDS_PER_WAVE <= (size_t)ctx->prop.sharedMemPerBlock) {
-                const int nb = E * F1P_ST_MAX_REFINE / 4 < 2 * ctx->prop.multiProcessorCount ? (E * F1P_ST_MAX_REFINE + 3) / 4 : 2 * ctx->prop.multiProcessorCount;
-                if (gen) hipLaunchKernelGGL(k_stmpc_refine_tp_gen, dim3(nb), dim3(256), 4 * F1P_ST_TP_LDS_PER_WAVE, ctx->stream, d_x0, d_ref, *gen, *cfg, qcount, items, rc, ctx->d_dbg_st_cost32);
-                else hipLaunchKernelGGL(k_stmpc_refine_tp, dim3(nb), dim3(256), 4 * F1P_ST_TP_LDS_PER_WAVE, ctx->stream, d_x0, d_ref, d_controls, *cfg, qcount, items, rc, ctx->d_dbg_st_cost32);
-            } else {
-                if (gen) hipLaunchKernelGGL(k_stmpc_refine_gen, dim3(E), dim3(64), 0, ctx->stream, d_x0, d_ref, *gen, *cfg, qcount, items, rc);
-                else hipLaunchKernelGGL(k_stmpc_refine, dim3(E), dim3(64), 0, ctx->stream, d_x0, d_ref, d_controls, *cfg, qcount, items, rc);
-            }
-            rcode = check_hip(ctx, hipGetLastError(), "k_stmpc_refine launch");
-            if (rcode != F1P_OK) return rcode;
-            if (gen) hipLaunchKernelGGL(k_stmpc_decide_gen, dim3(E), dim3(256), (lds_c + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, *cfg, qcount,
-                                        nlist, rl, rc, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_st_nref);
-            else hipLaunchKernelGGL(k_stmpc_decide, dim3(E), dim3(256), (lds_c + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E, *cfg, qcount,
-                               nlist, rl, rc, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_st_nref);
-            rcode = check_hip(ctx, hipGetLastError(), "k_stmpc_decide launch");
-            if (rcode == F1P_OK) ctx->st_q_dirty = false;
-            return rcode;
-        }
+        if (lds_a <= (size_t)ctx->prop.sharedMemPerBlock && lds <= (size_t)ctx->prop.sharedMemPerBlock && kf.v_trust == kf.v_trust &&
+            (size_t)E * F1P_ST_MAX_REFINE < ((size_t)1 << 31))
+            return gen ? stmpc_mixed(ctx, d_x0, d_ref, *gen, E, cfg, kf, lds_a, lds, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq)
+                       : stmpc_mixed<StCtlStream>(ctx, d_x0, d_ref, d_controls, E, cfg, kf, lds_a, lds, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
     }
-    const size_t lds = sizeof(double) * (7 * T1 + 4) + sizeof(int) * 4;
-    if (gen) hipLaunchKernelGGL(k_stmpc_shoot_gen, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, *cfg,
-                                d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
-    else hipLaunchKernelGGL(k_stmpc_shoot, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E, *cfg,
-                       d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
-    return check_hip(ctx, hipGetLastError(), "k_stmpc_shoot launch");
+    return shoot("k_stmpc_shoot launch");
 }
 
 int launch_stmpc_shoot(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const float* d_controls, int E, const f1p_stmpc_cfg* cfg,

@@ -1,6 +1,7 @@
 // shoot_col.h -- the occupancy test of the shooting MPCs' rollouts (f1p_kmpc_set_collision, f1p_stmpc_set_collision):
 // one struct, one point test and one segment rule for k_kmpc.hip and k_stmpc.hip.
 #pragma once
+#include <type_traits>
 #include "f1p_device.h"
 
 namespace f1p {
@@ -26,10 +27,15 @@ struct KmpcCol {
         return hit | occupied(qx, qy);
     }
 };
-
+// The test is an OPTIONAL kernel argument: the shooting kernels are templates over a pack of optional arguments, a KmpcCol (or a struct
+// derived from it) the last of them, and `if constexpr (has_col<Extra...>)` keeps every statement of the test out of an instantiation
+// without it -- whose kernarg layout and instructions are those of a kernel written without the argument.
+template <typename... X> constexpr bool has_col = (std::is_base_of_v<KmpcCol, X> || ...);
+template <typename A> __device__ __forceinline__ const A& col_of(const A& c) { return c; }
+template <typename A, typename B, typename... X> __device__ __forceinline__ const auto& col_of(const A&, const B& b, const X&... x) { return col_of(b, x...); }
 
 // the f32 filters' side of the test: the tested points looked up in the CLEARANCE map, cell coordinates relative to the ego's cell
-// (k_kmpc.hip kmpc_rollout_cost_f32x2_col, k_stmpc.hip stmpc_rollout_f32_gen_col)
+// (k_kmpc.hip kmpc_rollout_cost_f32x2_col, k_stmpc.hip stmpc_rollout_f32 with `cf`)
 #define F1P_K4_CLEAR_CELLS 2.0
 #define F1P_K4_POS_ERR_REL 1.0e-4
 struct KmpcColF {

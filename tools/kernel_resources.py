@@ -30,12 +30,14 @@ CSRC = os.path.join(ROOT, "f1tenth_planning_amd", "csrc")
 #                       goals (<CR, true, true>), cubic + footprint and footprint + host goals -- production plan shapes of the add_sample_function
 #                       path -- so those shapes carry this budget (8-24 B of scratch); the spill-free claim holds for the device-goal shapes
 #                       (<CR, false, false, GEN, FOOT = false>: 0 scratch, asserted below by the default budget of 0)
-#   k_kmpc_plan_gen_idx the same kernel text with the ego indirection of f1p_stmpc_plan_batch's kinematic branch: 14 VGPRs (52 B) spilled in the
-#                       same once-per-workgroup blocks, none in the three filter loops (tools/isa_loops.py)
-#   k_stmpc_shoot_gen   the PLAIN-fp64 evaluation of f1p_stmpc_plan_* (f1p_stmpc_set_mode(0): the parity mode, not the default schedule): 36 B of
+#   k_kmpc_plan_gen_t<> / <KmpcIdxArgs>   (IJEE / IJNS_11KmpcIdxArgsEEE) the planning kernel and its instantiation with the ego indirection of
+#                       f1p_stmpc_plan_batch's kinematic branch: 7 / 14 VGPRs (32 / 52 B) spilled in the same once-per-workgroup blocks, none in
+#                       the three filter loops (tools/isa_loops.py).  The two instantiations with the occupancy test carry none; the keys are
+#                       whole template argument lists, so they match nothing else
+#   k_stmpc_shoot_t<StCtlGen>   (INS_8StCtlGenEJEE: k_stmpc_shoot_gen, not its _col form) the PLAIN-fp64 evaluation of f1p_stmpc_plan_* (f1p_stmpc_set_mode(0): the parity mode, not the default schedule): 36 B of
 #                       SGPR spill slots around the all-fp64 rollout loop's set-up.  The default schedule's kernels (k_stmpc_filter_gen,
 #                       _refine_gen, _refine_tp_gen, _decide_gen) carry none
-BUDGET = {"ILb1E": 56, "k_kmpc_plan_gen": 32, "k_kmpc_plan_gen_idx": 52, "k_stmpc_shoot_gen": 36, "k_kmpc_shoot_mixed": 0, "k_clothoid_g1": 8, "9k_latticeILb0E": 8,
+BUDGET = {"ILb1E": 56, "k_kmpc_plan_gen_tIJEE": 32, "k_kmpc_plan_gen_tIJNS_11KmpcIdxArgsEEE": 52, "k_stmpc_shoot_tINS_8StCtlGenEJEE": 36, "k_kmpc_shoot_mixed": 0, "k_clothoid_g1": 8, "9k_latticeILb0E": 8,
           "k_lattice_filter3ILi1ELb1E": 24, "k_lattice_filter3ILi2ELb1E": 24,
           "k_lattice_filter3ILi1ELb0ELb0ELi0ELb1E": 8, "k_lattice_filter3ILi2ELb0ELb0ELi0ELb1E": 8,
           "9k_latticeILb0ELi0ELb1ELb0ELb1E": 24}   # (the instantiations WITH test hooks -- incl. the host-goal shapes; device goals, point footprint: 0)
