@@ -93,6 +93,8 @@ struct f1p_ctx {
     int kmpc_cfg_used = 0;
     WarmBuf kmpc_warm;                 // [E][T][2] f32, key (E, T): previous plan's applied winner shifted by one step
     bool kmpc_warm_valid = false;
+    bool kmpc_warm_nonfinite = false;  // f1p_kmpc_warm_set uploaded a NaN / inf: generated plans are evaluated in fp64 until the next set / reset (k_kmpc.hip "NaN controls")
+    bool stmpc_warm_nonfinite = false; // the same for f1p_stmpc_warm_set (both branches of f1p_stmpc_plan_batch read that buffer)
     char* d_kmpc_scratch = nullptr;    // split-rollout mode: per-ego tickets [cap_E] | [cap_E][cap_R] filter costs (layout by capacity)
     int kmpc_cap_E = 0, kmpc_cap_R = 0;
     int kmpc_yaw_fixup = 1;            // k_kmpc_ref folds gathered course headings (kinematic_mpc.py:198-203); 0: the caller maintains the array

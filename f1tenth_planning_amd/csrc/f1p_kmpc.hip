@@ -249,6 +249,7 @@ int f1p_kmpc_gen_controls_dev(f1p_ctx* ctx, float* d_controls, int32_t E, const 
 int f1p_kmpc_warm_reset(f1p_ctx* ctx) {
     if (!ctx) return F1P_EINVAL;
     ctx->kmpc_warm_valid = false;
+    ctx->kmpc_warm_nonfinite = false;
     return F1P_OK;
 }
 
@@ -265,6 +266,9 @@ int f1p_kmpc_warm_set(f1p_ctx* ctx, const float* warm, int32_t E, int32_t T) {
     int rc = ensure_warm(ctx, E, T); if (rc) return rc;
     if ((rc = warm_upload(ctx, &ctx->kmpc_warm, warm, sizeof(float) * 2 * (size_t)E * T))) return rc;
     ctx->kmpc_warm_valid = true;
+    // the only way a non-finite value enters a warm start (the kernels write clamped controls, or a NaN they were handed here)
+    ctx->kmpc_warm_nonfinite = false;
+    for (size_t q = 0; q < 2 * (size_t)E * T; ++q) if (!isfinite(warm[q])) { ctx->kmpc_warm_nonfinite = true; break; }
     return F1P_OK;
 }
 

@@ -551,6 +551,7 @@ int f1p_stmpc_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_st
 int f1p_stmpc_warm_reset(f1p_ctx* ctx) {
     if (!ctx) return F1P_EINVAL;
     std::fill(ctx->stmpc_warm_tag.begin(), ctx->stmpc_warm_tag.end(), 0);    // (a row whose tag is not its branch's is zeroed by the plan that reads it)
+    ctx->stmpc_warm_nonfinite = false;
     return F1P_OK;
 }
 
@@ -571,5 +572,8 @@ int f1p_stmpc_warm_set(f1p_ctx* ctx, const float* warm, const int32_t* tag, int3
     int rc = ensure_st_warm(ctx, E, T, TK); if (rc) return rc;
     if ((rc = warm_upload(ctx, &ctx->stmpc_warm, warm, sizeof(float) * 2 * (size_t)E * (T > TK ? T : TK)))) return rc;
     memcpy(ctx->stmpc_warm_tag.data(), tag, sizeof(int32_t) * (size_t)E);
+    // the only way a non-finite value enters a warm start (the kernels write clamped controls, or a NaN they were handed here)
+    ctx->stmpc_warm_nonfinite = false;
+    for (size_t q = 0; q < 2 * (size_t)E * (T > TK ? T : TK); ++q) if (!isfinite(warm[q])) { ctx->stmpc_warm_nonfinite = true; break; }
     return F1P_OK;
 }

@@ -144,6 +144,15 @@ __device__ __forceinline__ void kmpc_rollouts(const Src& src, const double* sref
 // above, and the decision is taken on those fp64 costs -- so the result is the fp64 argmin as long as the f32 error is below
 // half the margin (measured at T = 30: f32 error = 2.5 % of the margin of 1e-4 relative + 0.02 absolute; tests/test_gpu_kmpc.py
 // checks both the error against the margin and the bit-identity of the results with the plain fp64 kernel).
+// NaN controls: the fp64 bounds (clampd) keep a NaN, the rollout's fp64 cost is NaN and np.argmin's rule makes the first such rollout the
+// winner -- while v_med3_f32 with a NaN operand returns the smaller of the other two, so the f32 rollout would carry on with -max and a finite
+// cost.  RULE: a rollout with a NaN among its raw controls gets a NaN filter cost, and NaN costs are listed (fp64 decides).  Streamed
+// controls: raw = fma(accel_raw, steer_raw, raw) per step (kmpc_raw2; inf x 0 or an overflow make it NaN too, which only hands a finite
+// rollout to fp64), tested once after the loop.  Generated controls are fma(sigma z, warm[t]) with sigma validated finite by the entry
+// points: a NaN needs a non-finite warm-start entry (inf x 0 in rollout 1 included), and only f1p_kmpc_warm_set / f1p_stmpc_warm_set can
+// put one there (the emission writes clamped controls).  They scan what they upload, and while the flag stands the launcher hands the
+// kernel w_ok = 0: every rollout in fp64, no device code for it.
+// The f32 arithmetic of a finite rollout is what it was.
 // ---------------------------------------------------------------------------------------------------
 // sq / sqf: square roots of the stage / terminal state weights (f32).  The filter's reference rows hold -sq[i] * ref_i (the fp64 product of
 // the ROUNDED root and the relative reference, so both halves of the error carry the same scale), and a state term is
@@ -366,8 +375,16 @@ __device__ __forceinline__ void kmpc_load_chunk_adj(const SrcStream& src, int T,
 // (ADJ is a template parameter and the prefetches are unconditional -- past the horizon's end they re-read its last whole chunk -- so that the
 // loop body is straight-line code: with a branch around every load the compiler's wait-count pass put an s_waitcnt vmcnt(0) in front of every
 // chunk and the ring bought nothing, measured)
+// NaN controls (the rule is in the filter's header above): raw = fma(accel_raw, steer_raw, raw) over the steps a chunk CONSUMES, one packed
+// FMA per step for both channels of both rollouts, beside the steps' chain
+__device__ __forceinline__ void kmpc_raw2(f1p_f2& raw, const f1p_f2 (&av)[2], const f1p_f2 (&dv)[2], bool both = true) {
+#pragma clang fp contract(fast)
+    raw = av[0] * dv[0] + raw;
+    if (both) raw = av[1] * dv[1] + raw;
+}
 template <bool POLY, bool ISO, bool ADJ>
 __device__ __forceinline__ f1p_f2 kmpc_rollout_cost_stream(const SrcStream& src, const float* sref32, const KmpcF32& k, int T, int r0, int r1) {
+    f1p_f2 raw = 0.f;
     KmpcState2 s;
     s.x = 0.f; s.y = 0.f; s.v = k.v0; s.yaw = 0.f; s.cost = 0.f; s.pa = 0.f; s.pd = 0.f;
     constexpr int CH = 2;
@@ -384,36 +401,36 @@ __device__ __forceinline__ f1p_f2 kmpc_rollout_cost_stream(const SrcStream& src,
         kmpc_load_chunk_adj<true, ADJ>(src, T, r0, at(2), r1, a2, d2);
 #if F1P_K4_RING == 4
         kmpc_load_chunk_adj<true, ADJ>(src, T, r0, at(3), r1, a3, d3);
-        kmpc_steps2<POLY, ISO, true, true, CH>(s, sref32, k, T, 0, a0, d0);
+        kmpc_steps2<POLY, ISO, true, true, CH>(s, sref32, k, T, 0, a0, d0); kmpc_raw2(raw, a0, d0);
         kmpc_load_chunk_adj<true, ADJ>(src, T, r0, at(4), r1, a0, d0);
         int c = 1;                                                     // chunk c sits in buffer 1, c + 1 in 2, c + 2 in 3, c + 3 in 0
         for (; c + 4 <= nch; c += 4) {
-            kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, c * CH, a1, d1);
+            kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, c * CH, a1, d1); kmpc_raw2(raw, a1, d1);
             kmpc_load_chunk_adj<true, ADJ>(src, T, r0, at(c + 4), r1, a1, d1);
-            kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 1) * CH, a2, d2);
+            kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 1) * CH, a2, d2); kmpc_raw2(raw, a2, d2);
             kmpc_load_chunk_adj<true, ADJ>(src, T, r0, at(c + 5), r1, a2, d2);
-            kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 2) * CH, a3, d3);
+            kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 2) * CH, a3, d3); kmpc_raw2(raw, a3, d3);
             kmpc_load_chunk_adj<true, ADJ>(src, T, r0, at(c + 6), r1, a3, d3);
-            kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 3) * CH, a0, d0);
+            kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 3) * CH, a0, d0); kmpc_raw2(raw, a0, d0);
             kmpc_load_chunk_adj<true, ADJ>(src, T, r0, at(c + 7), r1, a0, d0);
         }
-        if (c < nch) kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, c * CH, a1, d1);
-        if (c + 1 < nch) kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 1) * CH, a2, d2);
-        if (c + 2 < nch) kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 2) * CH, a3, d3);
+        if (c < nch) { kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, c * CH, a1, d1); kmpc_raw2(raw, a1, d1); }
+        if (c + 1 < nch) { kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 1) * CH, a2, d2); kmpc_raw2(raw, a2, d2); }
+        if (c + 2 < nch) { kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 2) * CH, a3, d3); kmpc_raw2(raw, a3, d3); }
 #else
-        kmpc_steps2<POLY, ISO, true, true, CH>(s, sref32, k, T, 0, a0, d0);
+        kmpc_steps2<POLY, ISO, true, true, CH>(s, sref32, k, T, 0, a0, d0); kmpc_raw2(raw, a0, d0);
         kmpc_load_chunk_adj<true, ADJ>(src, T, r0, at(3), r1, a0, d0);
         int c = 1;                                                     // chunk c sits in buffer 1, c + 1 in buffer 2, c + 2 in buffer 0
         for (; c + 3 <= nch; c += 3) {
-            kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, c * CH, a1, d1);
+            kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, c * CH, a1, d1); kmpc_raw2(raw, a1, d1);
             kmpc_load_chunk_adj<true, ADJ>(src, T, r0, at(c + 3), r1, a1, d1);
-            kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 1) * CH, a2, d2);
+            kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 1) * CH, a2, d2); kmpc_raw2(raw, a2, d2);
             kmpc_load_chunk_adj<true, ADJ>(src, T, r0, at(c + 4), r1, a2, d2);
-            kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 2) * CH, a0, d0);
+            kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 2) * CH, a0, d0); kmpc_raw2(raw, a0, d0);
             kmpc_load_chunk_adj<true, ADJ>(src, T, r0, at(c + 5), r1, a0, d0);
         }
-        if (c < nch) kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, c * CH, a1, d1);
-        if (c + 1 < nch) kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 1) * CH, a2, d2);
+        if (c < nch) { kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, c * CH, a1, d1); kmpc_raw2(raw, a1, d1); }
+        if (c + 1 < nch) { kmpc_steps2<POLY, ISO, true, false, CH>(s, sref32, k, T, (c + 1) * CH, a2, d2); kmpc_raw2(raw, a2, d2); }
 #endif
     }
     const int t0 = nch * CH;
@@ -421,11 +438,14 @@ __device__ __forceinline__ f1p_f2 kmpc_rollout_cost_stream(const SrcStream& src,
         kmpc_load_chunk_adj<false, ADJ>(src, T, r0, t0, r1, a0, d0);
         if (t0 == 0) kmpc_steps2<POLY, ISO, false, true, CH>(s, sref32, k, T, 0, a0, d0);
         else kmpc_steps2<POLY, ISO, false, false, CH>(s, sref32, k, T, t0, a0, d0);
+        kmpc_raw2(raw, a0, d0, false);
     }
     const f1p_f2 e0 = k.sqf[0] * s.x + sref32[0 * (T + 1) + T], e1 = k.sqf[1] * s.y + sref32[1 * (T + 1) + T];
     const f1p_f2 e2 = k.sqf[2] * s.v + sref32[2 * (T + 1) + T], e3 = k.sqf[3] * s.yaw + sref32[3 * (T + 1) + T];
     s.cost += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
     s.cost -= k.rd[0] * s.pa * s.pa + k.rd[1] * s.pd * s.pd;           // the last step has no successor (see KmpcF32)
+    if (!(raw.x == raw.x)) s.cost.x = raw.x;                           // a NaN control: a NaN filter cost, which the caller lists for fp64
+    if (!(raw.y == raw.y)) s.cost.y = raw.y;
     return s.cost;
 }
 
@@ -1390,8 +1410,12 @@ int launch_kmpc_plan_gen(f1p_ctx* ctx, const double* d_x0, const double* d_ref, 
     if (lds > (size_t)ctx->prop.sharedMemPerBlock) return set_error(ctx, F1P_EINVAL, "horizon / n_rollouts need more LDS than a workgroup has: use fewer rollouts per plan");
     if (const int rc = ensure_kmpc_cfg(ctx, cfg)) return rc;
     // one launch over the kernel's optional arguments (the test's kernels run one workgroup per ego: ga.G == 1)
+    // NaN controls (the filter's header): a warm start that was SET with a non-finite entry takes the filter out of the plan -- w_ok = 0 is the
+    // kernel's existing "every rollout in fp64" route -- until the next f1p_*_warm_set / _reset
+    KmpcF32 kf = make_kf(cfg);
+    if (d_warm_in && (d_ids ? ctx->stmpc_warm_nonfinite : ctx->kmpc_warm_nonfinite)) kf.w_ok = 0;
     auto launch = [&](auto kern, const char* what, auto... ex) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)E * ga.G)), dim3(block), lds, ctx->stream, d_x0, d_ref, E, *cfg, make_kf(cfg), ga, ex...,
+        hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)E * ga.G)), dim3(block), lds, ctx->stream, d_x0, d_ref, E, *cfg, kf, ga, ex...,
                            d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_nref, ctx->d_kmpc_cfg_cur);
         return check_hip(ctx, hipGetLastError(), what);
     };

@@ -84,6 +84,14 @@ struct StCtlGen {
 //     trusted) -> the ego falls back to the all-fp64 loop.
 //   pass B (fp64): the listed rollouts by stmpc_rollouts' own arithmetic (k_stmpc_refine_tp: one wave each, lanes over the time steps),
 //     np.argmin's rule over THOSE costs (k_stmpc_decide).
+//   NaN controls: the fp64 bounds (clampd2) keep a NaN, the rollout's fp64 cost is NaN and np.argmin's rule makes the first such rollout the
+//     winner -- while v_med3_f32 with a NaN operand returns the smaller of the other two, so the f32 rollout would carry on with -max and a
+//     finite cost.  RULE: a rollout with a NaN among its raw controls is UNTRUSTED (listed, fp64 decides).  Streamed controls: each
+//     step's two raw controls go through one unordered compare (v_cmp_u_f32 dv_raw, a_raw: true iff either is a NaN; exact, +-inf is not
+//     flagged) that ANDs into `trusted` beside the speed test -- scalar registers, no VGPR.  Generated controls are fma(sigma z, warm[t]) with sigma validated finite by
+//     the entry points: a NaN needs a non-finite warm-start entry (inf x 0 in rollout 1 included), and only f1p_stmpc_warm_set can put one
+//     there (the emission writes clamped controls).  It scans what it uploads, and while the flag stands stmpc_shoot_any runs the generated
+//     plan through the all-fp64 kernel: no device code for it.  The f32 arithmetic of a finite rollout is what it was.
 // Exactness: the fp64 minimiser r* has cost64(r*) <= cost64(r32), so if trusted cost32(r*) <= cost32(r32) + 2 err <= min32 + margin
 // (margin >= 2 err, measured by tools/stmpc_filter_error.py and sized 40x above it); untrusted r* is listed by construction.
 // ===================================================================================================================
@@ -176,6 +184,7 @@ __device__ __forceinline__ void stmpc_rollout_f32(const float* __restrict__ ce, 
         for (int i = 0; i < NR; ++i) {
             float dv = __builtin_amdgcn_fmed3f(n_dv[i], -k.max_steer_v, k.max_steer_v);
             const float a = __builtin_amdgcn_fmed3f(n_a[i], -k.max_accel, k.max_accel);
+            trusted[i] &= !__builtin_isunordered(n_dv[i], n_a[i]);      // NaN controls (the filter's header): ONE compare takes both raw channels, its result in scalar registers
             cp[i] += 2 * (size_t)R;
             if (t + 1 < T) { n_dv[i] = cp[i][0]; n_a[i] = cp[i][R]; }   // (two steps ahead measured slower: 0.094 against 0.089 ms per plan)
             F1P_ST_F32_STEP(i)
@@ -1132,7 +1141,7 @@ static int stmpc_shoot_any(f1p_ctx* ctx, const double* d_x0, const double* d_ref
         KmpcCol col;
         col.g = grid_dev(ctx); col.clear = nullptr; col.n_sub = ctx->stmpc_col_nsub; col.force64 = 1;
         if (lds > (size_t)ctx->prop.sharedMemPerBlock) return set_error(ctx, F1P_EINVAL, "stmpc: the horizon needs more LDS than a workgroup has");
-        if (gen && ctx->stmpc_mixed) {
+        if (gen && ctx->stmpc_mixed && !ctx->stmpc_warm_nonfinite) {
             const DynF32 kf = make_dyn_f32(cfg);
             const size_t lds_a = sizeof(float) * (8 * T1 + (size_t)cfg->n_rollouts + 4) + sizeof(int) * (F1P_ST_MAX_REFINE + 2) + sizeof(float) * 2 * (size_t)cfg->horizon;
             if (lds_a <= (size_t)ctx->prop.sharedMemPerBlock && kf.v_trust == kf.v_trust && (size_t)E * F1P_ST_MAX_REFINE < ((size_t)1 << 31) &&
@@ -1143,7 +1152,7 @@ static int stmpc_shoot_any(f1p_ctx* ctx, const double* d_x0, const double* d_ref
         }
         return shoot("k_stmpc_shoot_col launch", col);
     }
-    if (ctx->stmpc_mixed) {
+    if (ctx->stmpc_mixed && !(gen && ctx->stmpc_warm_nonfinite)) {      // (NaN controls: a warm start set with a non-finite entry -> plain fp64)
         const DynF32 kf = make_dyn_f32(cfg);
         const size_t lds_a = sizeof(float) * (8 * T1 + (size_t)cfg->n_rollouts + 4) + sizeof(int) * (F1P_ST_MAX_REFINE + 2) +
                              (gen ? sizeof(float) * 2 * (size_t)cfg->horizon : 0);   // + the ego's warm start

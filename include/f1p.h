@@ -520,7 +520,12 @@ int f1p_clothoid_sample_batch(f1p_ctx* ctx, const double* params, int32_t n, int
  * the objective of :324-334 evaluated on the nonlinear rollout, argmin, output map of :506-508.
  *   x0       [E][4]          (x, y, v, yaw)                       fp64
  *   ref      [E][4][T+1]     calc_ref_trajectory_kinematic output (:162-206), rows x, y, v, yaw   fp64
- *   controls [E][T][2][R]    f32, (accel, steer) candidates, rollout index fastest (coalesced)
+ *   controls [E][T][2][R]    f32, (accel, steer) candidates, rollout index fastest (coalesced).  +-inf is clamped to the bound.  A NaN
+ *                            stays a NaN through the bounds: that rollout's cost is NaN and, by np.argmin's rule, the first such rollout of
+ *                            an ego wins (best_cost NaN) -- in both evaluation modes: the f32 filter hands a rollout with a NaN control
+ *                            to the fp64 decision.  The same holds for generated controls: f1p_kmpc_warm_set / f1p_stmpc_warm_set note a
+ *                            non-finite entry, and until the next set / reset the generated plans are evaluated in fp64 throughout
+ *                            (non-finite sigmas are rejected with F1P_EINVAL).
  * Outputs: steer [E] = delta_0 of the winner, speed [E] = v + a_0*DTK, best_idx [E], best_cost [E],
  *   best_seq [E][T][2] (the winner's applied accel/steer after bound projection; may be NULL).
  * ---------------------------------------------------------------------------------------------- */
@@ -731,7 +736,8 @@ int f1p_stmpc_qp_plan_tracks_batch(f1p_ctx* ctx, const double* x0, const int32_t
  * (control/dynamic_mpc/dynamic_mpc.py): predict_motion / update_state (:280-404), calc_ref_trajectory (:195-233),
  * objective :616-622, bounds :685-706, output map :1112-1117.
  *   x0 [E][7]; oa / od_v [E][T] fp64; path [E][7][T+1]; states [E][4] = (x, y, v, yaw); ref [E][7][T+1];
- *   controls [E][T][2][R] f32 = (steering speed, accel), rollout index fastest.
+ *   controls [E][T][2][R] f32 = (steering speed, accel), rollout index fastest.  +-inf is clamped to the bound; a NaN stays a NaN (the rule of
+ *   f1p_kmpc_shoot_*'s controls: the first rollout with a NaN control wins with a NaN cost, in both evaluation modes).
  * ---------------------------------------------------------------------------------------------- */
 int f1p_stmpc_predict_batch(f1p_ctx* ctx, const double* x0, const double* oa, const double* od_v, int32_t E,
                             const f1p_stmpc_cfg* cfg, double* path);
