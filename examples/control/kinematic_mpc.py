@@ -2,7 +2,11 @@
 examples/control/kinematic_mpc.py:35-67): the planner gets the simulator's 7-state and the waypoints as [x, y, yaw, v].
 
 --obstacles N parks N obstacles on the line of the synthetic track and drives the loop twice, without and with the occupancy test on the
-rollouts (mpc_config.COLLISION), counting the vehicle-steps that ended in an occupied cell."""
+rollouts (mpc_config.COLLISION), counting the vehicle-steps that ended in an occupied cell.
+
+--opponents M (with --envs E >= 2) starts the E vehicles as a pack on one course, the fast ones behind the slow ones, and drives the loop
+twice: each vehicle planning as if it were alone, then with its M nearest other vehicles as moving obstacles, predicted at constant
+velocity (planner.obstacles).  It reports the smallest distance between two vehicles over each run."""
 import os
 import sys
 
@@ -19,11 +23,51 @@ def obstacle_runs(args, rl, waypoints, cfg):
                                 lambda env: env.state[:, [0, 1, 3, 4]], lambda c, n: setattr(c, "COLLISION_SUBSTEPS", n))
 
 
+def opponent_runs(args, rl, waypoints, cfg, gap=1.5, radius=0.45):
+    """radius: the two vehicles' radii folded into the obstacle's (a point-against-disc test)"""
+    from f1tenth_planning_amd import sim
+    E, M = args.envs, min(args.opponents, args.envs - 1, 16)
+    if args.solver == "qp" or E < 2:
+        raise SystemExit("--opponents needs the shooting solver and --envs >= 2")
+    seg = np.hypot(np.diff(rl[:, 0]), np.diff(rl[:, 1]))
+    k0 = int(np.argmin(np.abs(rl[:, 3])))                                # start where the heading is far from the +-pi seam
+    k = k0 + np.searchsorted(np.cumsum(np.concatenate([seg[k0:], seg[:k0]])), gap * np.arange(E))
+    k %= len(rl) - 1
+    poses = np.column_stack([rl[k, 0], rl[k, 1], rl[k, 3]])
+    scale = np.linspace(1.0, 0.5, E)                                    # vehicle 0 is last in line and the fastest
+    cfg.COLLISION_SUBSTEPS = args.substeps
+    print(f"{E} vehicles {gap} m apart on one course, speed scales 1.0 (rear) .. 0.5 (front), {args.steps} steps, {M} opponents each")
+    closest = {}
+    for on in (False, True):
+        planner = KMPCPlanner(waypoints=[w.copy() for w in waypoints], config=cfg)
+        env = sim.make("f110_gym:f110-v0", num_agents=E)
+        env.reset(poses)
+        d_min, n_stop = np.inf, 0
+        for it in range(args.steps):
+            st = env.state[:, [0, 1, 3, 4]]                             # (x, y, v, yaw)
+            d = np.hypot(st[:, None, 0] - st[None, :, 0], st[:, None, 1] - st[None, :, 1]) + np.diag(np.full(E, np.inf))
+            d_min = min(d_min, float(d.min()))
+            obs = None
+            if on:
+                near = np.argsort(d, axis=1)[:, :M]                     # [E, M] the nearest other vehicles
+                o = st[near]
+                obs = np.stack([o[:, :, 0], o[:, :, 1], o[:, :, 2] * np.cos(o[:, :, 3]), o[:, :, 2] * np.sin(o[:, :, 3]), np.full((E, M), radius)], 2)
+            planner.obstacles = obs
+            out = planner.plan_batch(st)
+            n_stop += int((out["best_idx"] < 0).sum())
+            env.step(np.column_stack([out["steer"], out["speed"] * scale]))
+        closest[on] = d_min
+        print(f"obstacle test {'on ' if on else 'off'}: smallest distance between two vehicles {d_min:.3f} m"
+              + (f" ({n_stop} plans had every rollout blocked)" if on else ""))
+    return closest
+
+
 def main():
     ap = common.parser(__doc__, steps=600)
     ap.add_argument("--rollouts", type=int, default=512)
     ap.add_argument("--solver", choices=["shooting", "qp"], default="shooting")
     ap.add_argument("--obstacles", type=int, default=0, help="park N obstacles (discs of 0.3 m) on the line and compare the loop with the occupancy test off / on")
+    ap.add_argument("--opponents", type=int, default=0, help="with --envs E: each vehicle's M nearest other vehicles are moving obstacles of its rollouts; compares the pack with the test off / on")
     ap.add_argument("--substeps", type=int, default=4, help="tested points per time step of a rollout (mpc_config.COLLISION_SUBSTEPS)")
     args = ap.parse_args()
     rl = common.raceline(args, centerline=True)
@@ -33,6 +77,8 @@ def main():
     cfg.SOLVER = args.solver
     if args.obstacles > 0:
         return obstacle_runs(args, rl, waypoints, cfg)
+    if args.opponents > 0:
+        return opponent_runs(args, rl, waypoints, cfg)
     planner = KMPCPlanner(waypoints=waypoints, config=cfg)
 
     def plan(obs, env):

@@ -15,6 +15,13 @@ a batched fp64 interior-point kernel (csrc/k_kmpc_qp.hip), warm-started like the
 
 mpc_config.COLLISION = True (shooting only) tests every rollout against the occupancy grid installed with set_map / load_map: a rollout
 that touches an occupied cell cannot win (f1p_kmpc_set_collision).
+
+planner.obstacles = [M, 5] before plan() / [E, M, 5] before plan_batch() (shooting only) tests every rollout of THAT call against moving
+discs, rows (x, y, vx, vy, r) in the map frame at constant velocity, M <= 16, r < 0 or NaN = an empty slot: a rollout that is inside a
+disc at the time it gets there cannot win (f1p_kmpc_set_obstacles).  The next plan / plan_batch call TAKES the attribute:
+it is None again afterwards, so obstacles are given per call, as a keyword argument would be, and a call without them plans without any.
+The caller folds the vehicle's own radius into r.  (An attribute, not a keyword: the signatures of plan and plan_batch are the
+reference's and a pinned record, tests/test_runtime_calls.py.)
 """
 import warnings
 from dataclasses import dataclass, field
@@ -24,7 +31,7 @@ import numpy as np
 from ... import _abi
 from ..._planner import MPCPlanner, _track_columns, qp_opts
 from ..._planner import kin_cfg_struct as _cfg_struct
-from ...runtime import Context
+from ...runtime import Context, kmpc_set_obstacles
 
 
 @dataclass
@@ -110,12 +117,34 @@ class KMPCPlanner(MPCPlanner):
         self._trk_qp_warm = None           # the QP warm start of the track-set path (plan_batch(tracks=...)): u [E, T, 2] fp64
         self._map = None                   # (img u8, resolution, (ox, oy), occupied_below) of set_map
         self._inflate = 0.0
+        self.obstacles = None              # moving discs of the NEXT plan, which takes them: [M, 5] for plan(), [E, M, 5] for plan_batch()
+        self._obstacles_set = False        # the context holds obstacles of an earlier plan
         self._check_solver()
 
-    def _collision_switch(self, ctx):
+    def _collision_switch(self, ctx, obstacles=None):
+        """the occupancy switch and the obstacles of this plan (None clears them); COLLISION_SUBSTEPS serves both tests"""
         c = self.config
         if c.SOLVER != "qp":
-            ctx.kmpc_set_collision(bool(c.COLLISION), int(c.COLLISION_SUBSTEPS) if c.COLLISION else 1)
+            ctx.kmpc_set_collision(bool(c.COLLISION), int(c.COLLISION_SUBSTEPS) if (c.COLLISION or obstacles is not None) else 1)
+            if obstacles is not None or self._obstacles_set:       # (a plan without any, after plans without any: nothing to clear)
+                kmpc_set_obstacles(ctx, obstacles)
+                self._obstacles_set = obstacles is not None
+
+    def _check_obstacles(self, obstacles, E):
+        """-> None or obstacles as fp64 [E, M, 5]; ValueError before anything touches the GPU"""
+        if obstacles is None:
+            return None
+        c = self.config
+        if c.SOLVER == "qp":
+            raise ValueError("obstacles are tested on the shooting solver's rollouts; SOLVER='qp' takes none")
+        o = np.ascontiguousarray(obstacles, dtype=np.float64)
+        if o.ndim != 3 or o.shape[0] != E or o.shape[2] != 5 or o.shape[1] < 1:
+            raise ValueError(f"obstacles must be [E={E}, M, 5] = (x, y, vx, vy, r) with 1 <= M <= 16")
+        if o.shape[1] > 16:
+            raise ValueError("at most 16 obstacles per ego (M <= 16)")
+        if not 1 <= int(c.COLLISION_SUBSTEPS) <= 16:
+            raise ValueError("COLLISION_SUBSTEPS must be in [1, 16]")
+        return o
 
     def _bind(self, waypoints, fold_yaw=None):
         """fold_yaw: the vehicle heading of a single-vehicle call -- the course headings are then folded in place on the caller's
@@ -140,11 +169,18 @@ class KMPCPlanner(MPCPlanner):
     def plan(self, states, waypoints=None):
         """
         states: [x, y, delta, v, yaw, yawrate, beta] (the 7-state of f110_gym, :139-147).
+        self.obstacles: [M, 5] rows (x, y, vx, vy, r) of moving discs for this call (taken: None afterwards), or None.
         Returns (steering_angle, speed).
         """
         self._check_collision()
+        obstacles, self.obstacles = self.obstacles, None
+        if obstacles is not None:
+            o = np.asarray(obstacles, dtype=np.float64)
+            if o.ndim != 2:
+                raise ValueError("obstacles must be [M, 5] = (x, y, vx, vy, r)")
+            obstacles = self._check_obstacles(o[None], 1)
         ctx = self._bind(waypoints, fold_yaw=float(states[4]))
-        self._collision_switch(ctx)
+        self._collision_switch(ctx, obstacles)
         vehicle_state = State(x=states[0], y=states[1], delta=states[2], v=states[3], yaw=states[4], yawrate=states[5],
                               beta=states[6])
         x0 = np.array([[vehicle_state.x, vehicle_state.y, vehicle_state.v, vehicle_state.yaw]], dtype=np.float64)   # :487
@@ -197,14 +233,19 @@ class KMPCPlanner(MPCPlanner):
         mpc_config.COLLISION: an ego whose rollouts are all blocked has best_idx -1, best_cost +inf, steer 0, speed 0 and a zero sequence.
         tracks: K courses in the `waypoints` format ([x, y, yaw, v]: four 1-D arrays or an array [4, N]) with track_ids [E]: ego e
         follows tracks[track_ids[e]]; `waypoints` is then not used.  The references come from one k_kmpc_ref_tracks launch (an id
-        outside [0, K) gives NaN rows, hence NaN outputs and QP status 3 for that ego) and go to the same solvers."""
+        outside [0, K) gives NaN rows, hence NaN outputs and QP status 3 for that ego) and go to the same solvers.
+        self.obstacles (taken by this call: None afterwards): [E, M, 5] rows (x, y, vx, vy, r) of moving discs per ego (M <= 16, r < 0 or NaN: empty), tested at COLLISION_SUBSTEPS
+        points per step whether COLLISION is on or not; None: none.  All-blocked egos as with COLLISION."""
         self._check_collision()
         if self.config.SOLVER == "qp" and controls is not None:
             raise ValueError("controls are candidates of the shooting solver; SOLVER='qp' takes none")
+        obstacles, self.obstacles = self.obstacles, None
+        if obstacles is not None:
+            obstacles = self._check_obstacles(obstacles, np.asarray(x0).reshape(-1, 4).shape[0])
         if tracks is not None:
-            return self._plan_tracks(x0, tracks, track_ids, controls, want_seq)
+            return self._plan_tracks(x0, tracks, track_ids, controls, want_seq, obstacles)
         ctx = self._bind(waypoints)
-        self._collision_switch(ctx)
+        self._collision_switch(ctx, obstacles)
         x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, 4)
         if self.config.SOLVER == "qp":
             return self._qp(ctx, x0, want_u=want_seq)
@@ -215,10 +256,10 @@ class KMPCPlanner(MPCPlanner):
         ref = ctx.kmpc_ref(x0, c.TK, c.DTK, c.dlk)
         return ctx.kmpc_shoot(x0, ref, controls, cfg)
 
-    def _plan_tracks(self, x0, tracks, track_ids, controls, want_seq):
+    def _plan_tracks(self, x0, tracks, track_ids, controls, want_seq, obstacles=None):
         cols = _track_columns(tracks, track_ids)
         ctx = self._context()
-        self._collision_switch(ctx)
+        self._collision_switch(ctx, obstacles)
         ctx.kmpc_set_yaw_fixup(True)                           # a batch: per-ego fold of the gathered headings, the courses stay as given
         ctx.set_tracks_cached(cols, cols=(0, 1, 2, 3))
         c = self.config

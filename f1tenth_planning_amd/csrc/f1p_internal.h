@@ -72,6 +72,11 @@ struct f1p_ctx {
     bool kmpc_mixed = true;
     bool kmpc_collision = false;   // f1p_kmpc_set_collision: rollouts of f1p_kmpc_plan_* / f1p_kmpc_shoot_* are tested against d_bits
     int kmpc_col_nsub = 1;         // ... at this many points per time step
+    // f1p_kmpc_set_obstacles: moving discs per ego, [E][M][5] fp64 rows (x, y, vx, vy, r), tested at the same points
+    double* d_kmpc_obs = nullptr;        // the context's own copy (f1p_kmpc_set_obstacles), kept across sets when large enough
+    size_t kmpc_obs_bytes = 0;
+    const double* kmpc_obs_cur = nullptr;   // the array in force: d_kmpc_obs or the caller's (f1p_kmpc_set_obstacles_dev); null: none
+    int kmpc_obs_E = 0, kmpc_obs_M = 0;
     float* d_dbg_cost32 = nullptr;     // [E][R] filter costs of the next launch (test hook), or null
     int32_t* d_dbg_nref = nullptr;     // [E] size of the refined set (-1 = fp64 fallback), or null
 

@@ -60,7 +60,13 @@ int ref_batch_impl(f1p_ctx* ctx, int ncol, const double* states, const int32_t* 
 }  // namespace f1p
 
 // f1p_kmpc_set_collision's preconditions, checked by every entry point that would launch the tested kernels -- before anything is launched
-static int kmpc_collision_check(f1p_ctx* ctx) {
+static int kmpc_collision_check(f1p_ctx* ctx, int E) {
+    if (ctx->kmpc_obs_cur) {                                          // f1p_kmpc_set_obstacles: with or without the grid
+        if (E != ctx->kmpc_obs_E)
+            return set_error(ctx, F1P_ESTATE, "kmpc obstacles were set for " + std::to_string(ctx->kmpc_obs_E) + " egos, this plan has " + std::to_string(E) +
+                                              " (f1p_kmpc_set_obstacles)");
+        if (ctx->kmpc_groups > 0) return set_error(ctx, F1P_ESTATE, "kmpc obstacle test runs one workgroup per ego: f1p_kmpc_set_groups(0)");
+    }
     if (!ctx->kmpc_collision) return F1P_OK;
     if (!ctx->has_grid) return set_error(ctx, F1P_ESTATE, "kmpc collision test is on but no occupancy grid is loaded (f1p_set_grid)");
     if (ctx->n_disc > 0)
@@ -77,6 +83,32 @@ int f1p_kmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub) {
     ctx->kmpc_col_nsub = n_sub;
     return F1P_OK;
 }
+
+// obs (host or device, by `dev`) -> the discs in force; null or M == 0 clears
+static int kmpc_set_obstacles(f1p_ctx* ctx, const double* obs, int32_t E, int32_t M, bool dev) {
+    F1P_ENTER(ctx);
+    if (!obs || M == 0) { ctx->kmpc_obs_cur = nullptr; ctx->kmpc_obs_E = 0; ctx->kmpc_obs_M = 0; return F1P_OK; }
+    if (M < 1 || M > F1P_KMPC_MAX_OBS) return set_error(ctx, F1P_EINVAL, "kmpc obstacles: M must be in [1, 16]");
+    if (E < 1) return set_error(ctx, F1P_EINVAL, "kmpc obstacles: E must be >= 1");
+    if (ctx->kmpc_groups > 0) return set_error(ctx, F1P_ESTATE, "kmpc obstacle test runs one workgroup per ego: f1p_kmpc_set_groups(0)");
+    if (dev) { ctx->kmpc_obs_cur = obs; ctx->kmpc_obs_E = E; ctx->kmpc_obs_M = M; return F1P_OK; }
+    const size_t bytes = sizeof(double) * 5 * (size_t)E * M;
+    if (bytes > ctx->kmpc_obs_bytes) {
+        ctx->kmpc_obs_cur = nullptr; ctx->kmpc_obs_E = 0; ctx->kmpc_obs_M = 0;
+        F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));              // no launch in flight reads the old copy
+        if (ctx->d_kmpc_obs) (void)hipFree(ctx->d_kmpc_obs);
+        ctx->d_kmpc_obs = nullptr; ctx->kmpc_obs_bytes = 0;
+        F1P_HIP(ctx, hipMalloc((void**)&ctx->d_kmpc_obs, bytes));
+        ctx->kmpc_obs_bytes = bytes;
+    }
+    // (pageable host memory: the copy has left the caller's array when this returns; stream order puts it after the plans already queued)
+    F1P_HIP(ctx, hipMemcpyAsync(ctx->d_kmpc_obs, obs, bytes, hipMemcpyHostToDevice, ctx->stream));
+    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->kmpc_obs_cur = ctx->d_kmpc_obs; ctx->kmpc_obs_E = E; ctx->kmpc_obs_M = M;
+    return F1P_OK;
+}
+int f1p_kmpc_set_obstacles(f1p_ctx* ctx, const double* obs, int32_t E, int32_t M) { return kmpc_set_obstacles(ctx, obs, E, M, false); }
+int f1p_kmpc_set_obstacles_dev(f1p_ctx* ctx, const double* d_obs, int32_t E, int32_t M) { return kmpc_set_obstacles(ctx, d_obs, E, M, true); }
 
 void f1p_kmpc_cfg_default(f1p_kmpc_cfg* cfg) {
     if (!cfg) return;
@@ -97,7 +129,7 @@ int f1p_kmpc_shoot_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, co
     int rc = validate_kmpc(ctx, cfg, E); if (rc) return rc;
     if (E > 0 && (!d_x0 || !d_ref || !d_controls || !d_steer || !d_speed || !d_best_idx))
         return set_error(ctx, F1P_EINVAL, "x0, ref, controls, steer, speed and best_idx are required");
-    if ((rc = kmpc_collision_check(ctx))) return rc;
+    if ((rc = kmpc_collision_check(ctx, E))) return rc;
     return launch_kmpc_shoot(ctx, d_x0, d_ref, d_controls, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
 }
 
@@ -108,7 +140,7 @@ int f1p_kmpc_shoot_batch(f1p_ctx* ctx, const double* x0, const double* ref, cons
     int rc = validate_kmpc(ctx, cfg, E); if (rc) return rc;
     if (E > 0 && (!x0 || !ref || !controls || !steer || !speed || !best_idx))
         return set_error(ctx, F1P_EINVAL, "x0, ref, controls, steer, speed and best_idx are required");
-    if ((rc = kmpc_collision_check(ctx))) return rc;
+    if ((rc = kmpc_collision_check(ctx, E))) return rc;
     const size_t T = cfg->horizon, R = cfg->n_rollouts, e = E;
     Stage s(ctx);
     s.need(8 * 4 * e); s.need(8 * e * 4 * (T + 1)); s.need(4 * e * T * 2 * R);
@@ -203,7 +235,7 @@ int f1p_kmpc_plan_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, int
     if (E == 0) return F1P_OK;
     if (!d_x0 || !d_ref || !d_steer || !d_speed || !d_best_idx) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and best_idx are required");
     if (cfg->n_rollouts > 8192) return set_error(ctx, F1P_EINVAL, "at most 8192 rollouts per plan");
-    if ((rc = kmpc_collision_check(ctx))) return rc;
+    if ((rc = kmpc_collision_check(ctx, E))) return rc;
     if ((rc = ensure_warm(ctx, E, cfg->horizon))) return rc;
     float* warm = ctx->kmpc_warm.as<float>();
     const float* warm_in = (smp->use_warm && ctx->kmpc_warm_valid) ? warm : nullptr;
@@ -221,7 +253,7 @@ int f1p_kmpc_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_kmp
     if (E > 0 && (!x0 || !steer || !speed || !best_idx)) return set_error(ctx, F1P_EINVAL, "x0, steer, speed and best_idx are required");
     if (!(dl > 0)) return set_error(ctx, F1P_EINVAL, "dl must be > 0");
     if (ctx->n_wp < 2 || !ctx->has_psi) return set_error(ctx, F1P_ESTATE, "waypoints with a heading column are required");
-    if ((rc = kmpc_collision_check(ctx))) return rc;
+    if ((rc = kmpc_collision_check(ctx, E))) return rc;
     const size_t T = cfg->horizon, e = E;
     Stage s(ctx);
     s.need(8 * 4 * e); s.need(8 * e * 4 * (T + 1));
@@ -281,6 +313,7 @@ int f1p_kmpc_set_yaw_fixup(f1p_ctx* ctx, int32_t on) {
 int f1p_kmpc_set_groups(f1p_ctx* ctx, int32_t groups) {
     if (!ctx) return F1P_EINVAL;
     if (groups < 0 || groups > 64) return set_error(ctx, F1P_EINVAL, "groups must be in [0, 64]");
+    if (groups > 0 && ctx->kmpc_obs_cur) return set_error(ctx, F1P_ESTATE, "kmpc obstacles are set and run one workgroup per ego: clear them first (f1p_kmpc_set_obstacles)");
     ctx->kmpc_groups = groups;
     return F1P_OK;
 }

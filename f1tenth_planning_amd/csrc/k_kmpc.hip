@@ -36,13 +36,14 @@ __device__ __forceinline__ double clampd(double v, double lo, double hi) { retur
 // ---------------------------------------------------------------------------------------------------
 // F1P_K4_NONE, KmpcCol: shoot_col.h (shared with k_stmpc.hip, f1p_stmpc_set_collision)
 // a control source with the occupancy test; `blocked`: the verdict on the rollout evaluated last (kmpc_rollout_cost / kmpc_rollout_lanes<true>)
-template <typename Base>
+// (Col: KmpcCol, or KmpcObs -- the moving discs of f1p_kmpc_set_obstacles with or without the grid; col_seg picks the rule)
+template <typename Base, typename Col = KmpcCol>
 struct SrcColT : Base {
-    KmpcCol col;
+    Col col;
     mutable bool blocked;
 };
 template <typename S> struct kmpc_has_col { static constexpr bool value = false; };
-template <typename B> struct kmpc_has_col<SrcColT<B>> { static constexpr bool value = true; };
+template <typename B, typename C> struct kmpc_has_col<SrcColT<B, C>> { static constexpr bool value = true; };
 
 // ---------------------------------------------------------------------------------------------------
 // Where a rollout's controls come from.
@@ -112,7 +113,7 @@ __device__ __forceinline__ double kmpc_rollout_cost(const Src& src, const double
         else {
             const double px = s.x, py = s.y;
             kmpc_step<FAST>(s, a, d, cfg);
-            src.blocked |= src.col.seg(px, py, s.x, s.y);
+            src.blocked |= col_seg(src.col, t, cfg.dt, px, py, s.x, s.y);
             if (src.blocked) break;                                   // its cost is never read (an all-blocked ego stops at the first step: p_1 is every rollout's)
         }
         pa = a; pd = d;
@@ -342,6 +343,62 @@ __device__ __forceinline__ f1p_f2 kmpc_rollout_cost_f32x2_col(const Src& src, co
                 }
                 h0 |= cf.template unsure<ISO>(s.x.x, s.y.x);
                 h1 |= cf.template unsure<ISO>(s.x.y, s.y.y);
+            }
+        }
+    }
+    const f1p_f2 e0 = k.sqf[0] * s.x + sref32[0 * (T + 1) + T], e1 = k.sqf[1] * s.y + sref32[1 * (T + 1) + T];
+    const f1p_f2 e2 = k.sqf[2] * s.v + sref32[2 * (T + 1) + T], e3 = k.sqf[3] * s.yaw + sref32[3 * (T + 1) + T];
+    s.cost += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
+    s.cost -= k.rd[0] * s.pa * s.pa + k.rd[1] * s.pd * s.pd;           // the last step has no successor (see KmpcF32)
+    u0 = h0; u1 = h1;
+    return s.cost;
+}
+
+// kmpc_rollout_cost_f32x2_col with the moving discs of f1p_kmpc_set_obstacles (k_kmpc_plan_gen_obs): every tested point is
+// compared with every live slot of the ego's LDS table at the point's time, and looked up in the clearance map as well while the
+// occupancy test is on (of.grid).  FREE needs both proofs at every point.
+template <bool POLY, bool ISO, typename Src>
+__device__ __forceinline__ f1p_f2 kmpc_rollout_cost_f32x2_obs(const Src& src, const float* sref32, const KmpcF32& k, int T, int r0, int r1,
+                                                             const KmpcColF& cf, const KmpcObsF& of, bool& u0, bool& u1) {
+    KmpcState2 s;
+    s.x = 0.f; s.y = 0.f; s.v = k.v0; s.yaw = 0.f; s.cost = 0.f; s.pa = 0.f; s.pd = 0.f;
+    bool h0 = false, h1 = false;
+    const bool test = of.grid | (of.n_live > 0);                      // (every slot empty and no grid: the plain filter, step by step)
+    for (int te = 0; te < T; te += 2) {
+        f1p_f2 av[2], dv[2];
+        {
+            float a00, d00, a01, d01, a10, d10, a11, d11;
+            src.template get2<false>(te, T, r0, a00, d00, a01, d01);
+            src.template get2<false>(te, T, r1, a10, d10, a11, d11);
+            av[0].x = a00; av[0].y = a10; dv[0].x = d00; dv[0].y = d10;
+            av[1].x = a01; av[1].y = a11; dv[1].x = d01; dv[1].y = d11;
+        }
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) {
+            const int t = te + jj;
+            if (t < T) {
+                const f1p_f2 px = s.x, py = s.y;
+                const f1p_f2 a1[1] = {av[jj]}, d1[1] = {dv[jj]};
+                kmpc_steps2<POLY, ISO, false, false, 1>(s, sref32, k, T, t, a1, d1);
+                if (test) {
+                    for (int j = 1; j <= cf.n_sub; ++j) {
+                        const bool end = j == cf.n_sub;
+                        const float f = end ? 1.0f : (float)j * cf.inv_nsub;
+                        const f1p_f2 qx = end ? s.x : px + (s.x - px) * f, qy = end ? s.y : py + (s.y - py) * f;
+                        if (of.grid) {
+                            h0 |= cf.template unsure<ISO>(qx.x, qy.x);
+                            h1 |= cf.template unsure<ISO>(qx.y, qy.y);
+                        }
+                        const float tau = ((float)t + f) * of.dt;
+                        for (int m = 0; m < of.n_live; ++m) {
+                            const float* o = of.live + 5 * m;
+                            const float cx = o[0] + o[2] * tau, cy = o[1] + o[3] * tau;
+                            const f1p_f2 dx = qx - cx, dy = qy - cy, d2 = dx * dx + dy * dy;
+                            h0 |= !(d2.x > o[4]);
+                            h1 |= !(d2.y > o[4]);
+                        }
+                    }
+                }
             }
         }
     }
@@ -598,7 +655,7 @@ __device__ __forceinline__ double kmpc_rollout_lanes(const Src& src, const doubl
     }
     if constexpr (kmpc_has_col<Src>::value) {
         const double qx = lane_up1(x), qy = lane_up1(y);
-        const bool hit = j >= 1 && j <= T && src.col.seg(qx, qy, x, y);
+        const bool hit = j >= 1 && j <= T && col_seg(src.col, j - 1, cfg.dt, qx, qy, x, y);   // (lane j holds p_j: step j - 1)
         const unsigned long long votes = __ballot(hit);             // (the active lanes: the groups that hold a survivor)
         const unsigned long long mine = T + 1 <= 32 ? 0xffffffffull << (__lane_id() & 32) : ~0ull;
         src.blocked = (votes & mine) != 0ull;
@@ -932,7 +989,8 @@ __global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void k_kmpc_plan_gen_t(const
     const double sx = x0[4 * e], sy = x0[4 * e + 1], sv = x0[4 * e + 2], syaw = x0[4 * e + 3];
     for (int q = tid; q < 2 * T; q += blockDim.x) warm_s[q] = ga.warm_in ? ga.warm_in[kpg_wrow(e, T, ex...) + q] : 0.0f;
     constexpr bool COL = has_col<Extra...>;                           // the occupancy test: a KmpcCol among the optional arguments
-    std::conditional_t<COL, SrcColT<SrcGenT<true>>, SrcGenT<true>> src;
+    constexpr bool OBS = has_obs<Extra...>;                           // ... a KmpcObs: moving discs, with the grid (a bitmap) or without (null)
+    std::conditional_t<COL, SrcColT<SrcGenT<true>, typename col_arg<Extra...>::type>, SrcGenT<true>> src;
     if constexpr (COL) { src.col = col_of(ex...); src.blocked = false; }
     src.k0 = ga.k0; src.k1 = ga.k1; src.call = ga.call; src.ego = kpg_ego(e, ex...); src.sig_a = ga.sig_a; src.sig_d = ga.sig_d;
     src.warm = warm_s;
@@ -941,7 +999,17 @@ __global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void k_kmpc_plan_gen_t(const
     [[maybe_unused]] double bxd = 0.0, byd = 0.0;
     [[maybe_unused]] bool col_ok = true;
     bool in_range;                                                    // workgroup-uniform: the fast paths' ranges
-    if constexpr (COL) {
+    if constexpr (OBS) {
+        // without a grid the discs need no cell: their FREE threshold carries the filter's position bound itself (obs_compact)
+        const KmpcObs& col = col_of(ex...);
+        if (col.g.bits) {
+            bxd = (sx - col.g.ox) * col.g.inv_res; byd = (sy - col.g.oy) * col.g.inv_res;
+            col_ok = col.clear && !col.force64 && fabs(bxd) < 1.0e6 && fabs(byd) < 1.0e6;
+        } else {
+            col_ok = !col.force64;
+        }
+        in_range = fabs(syaw) <= 1.0e4 && fabs(cfg.max_steer) <= 1.0e4 && kf.w_ok && col_ok;
+    } else if constexpr (COL) {
         const KmpcCol& col = col_of(ex...);
         bxd = (sx - col.g.ox) * col.g.inv_res; byd = (sy - col.g.oy) * col.g.inv_res;
         col_ok = col.clear && !col.force64 && fabs(bxd) < 1.0e6 && fabs(byd) < 1.0e6;
@@ -960,6 +1028,16 @@ __global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void k_kmpc_plan_gen_t(const
         sref32[q] = kmpc_ref32(kf, row, col == T, kmpc_rel_ref(ref + (size_t)e * 4 * (T + 1), T, row, col, rv, sx, sy, syaw, iso, c0d, s0d));
     }
     if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
+    // the ego's live discs -> LDS behind the filter costs (G == 1): fp64 rows, the filter's f32 rows, the count
+    [[maybe_unused]] double* olive = nullptr;
+    [[maybe_unused]] float* olive32 = nullptr;
+    [[maybe_unused]] int* on_live = nullptr;
+    if constexpr (OBS) {
+        olive = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(c32 + R) + 7) & ~(uintptr_t)7);
+        olive32 = reinterpret_cast<float*>(olive + 5 * F1P_KMPC_MAX_OBS);
+        on_live = reinterpret_cast<int*>(olive32 + 5 * F1P_KMPC_MAX_OBS);
+        if (tid < 64) obs_compact(col_of(ex...), e, sx, sy, sv, syaw, T, cfg.dt, cfg.max_speed, cfg.min_speed, iso, c0d, s0d, olive, olive32, on_live);
+    }
     __syncthreads();
     KmpcF32 k = kf;
     k.c0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, (float)c0d)));
@@ -967,6 +1045,11 @@ __global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void k_kmpc_plan_gen_t(const
     k.v0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, (float)sv)));
 
     [[maybe_unused]] KmpcColF cf;
+    [[maybe_unused]] KmpcObsF of;
+    if constexpr (OBS) {
+        src.col.live = olive; src.col.n_live = __builtin_amdgcn_readfirstlane(*on_live);
+        of.live = olive32; of.n_live = src.col.n_live; of.grid = src.col.g.bits != nullptr; of.dt = kf.dt;
+    }
     if constexpr (COL) {
         const KmpcCol& col = col_of(ex...);
         const double ibx = col_ok ? __builtin_floor(bxd) : 0.0, iby = col_ok ? __builtin_floor(byd) : 0.0;
@@ -988,6 +1071,11 @@ __global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void k_kmpc_plan_gen_t(const
             f1p_f2 c;
             if constexpr (COL) {
                 bool u0, u1;
+                if constexpr (OBS)
+                    c = iso ? kmpc_rollout_cost_f32x2_obs<true, true>(src, sref32, k, T, r, r1, cf, of, u0, u1)
+                            : (poly ? kmpc_rollout_cost_f32x2_obs<true, false>(src, sref32, k, T, r, r1, cf, of, u0, u1)
+                                    : kmpc_rollout_cost_f32x2_obs<false, false>(src, sref32, k, T, r, r1, cf, of, u0, u1));
+                else
                 c = iso ? kmpc_rollout_cost_f32x2_col<true, true>(src, sref32, k, T, r, r1, cf, u0, u1)
                         : (poly ? kmpc_rollout_cost_f32x2_col<true, false>(src, sref32, k, T, r, r1, cf, u0, u1)
                                 : kmpc_rollout_cost_f32x2_col<false, false>(src, sref32, k, T, r, r1, cf, u0, u1));
@@ -1072,6 +1160,8 @@ static constexpr auto k_kmpc_plan_gen = k_kmpc_plan_gen_t<>;
 static constexpr auto k_kmpc_plan_gen_idx = k_kmpc_plan_gen_t<KmpcIdxArgs>;
 static constexpr auto k_kmpc_plan_gen_col = k_kmpc_plan_gen_t<KmpcCol>;
 static constexpr auto k_kmpc_plan_gen_idx_col = k_kmpc_plan_gen_t<KmpcIdxArgs, KmpcCol>;
+// the moving discs of f1p_kmpc_set_obstacles, alone or with the occupancy test (the bitmap of its KmpcCol part: null = no grid)
+static constexpr auto k_kmpc_plan_gen_obs = k_kmpc_plan_gen_t<KmpcObs>;
 
 // materialise SrcGen's controls as the [E][T][2][R] f32 buffer of the streamed entry points (tests: generated == streamed)
 __global__ __launch_bounds__(256) void k_kmpc_gen_controls(float* __restrict__ controls, int E, int T, int R, KmpcGenArgs ga) {
@@ -1130,6 +1220,29 @@ __global__ __launch_bounds__(256, F1P_K4_WAVES) void k_kmpc_shoot_col(const doub
     ce.ce = controls + (size_t)e * T * 2 * R; ce.R = R; ce.col = col; ce.blocked = false;
     kmpc_refine_block(ref, ce, cfg, x0[4 * e], x0[4 * e + 1], x0[4 * e + 2], x0[4 * e + 3], e, -1, nullptr, sref, steer, speed, best_idx, best_cost,
                       best_seq, nullptr, nullptr, false);
+}
+
+// k_kmpc_shoot_col with the moving discs: what f1p_kmpc_shoot_* launch in EVERY mode while obstacles are set, with the grid (a bitmap in
+// `obs`) or without; the definition of the result and the parity hook of k_kmpc_plan_gen_obs
+__global__ __launch_bounds__(256, F1P_K4_WAVES) void k_kmpc_shoot_obs(const double* __restrict__ x0, const double* __restrict__ ref,
+                                                    const float* __restrict__ controls, int E, f1p_kmpc_cfg cfg, KmpcObs obs,
+                                                    double* __restrict__ steer, double* __restrict__ speed,
+                                                    int32_t* __restrict__ best_idx, double* __restrict__ best_cost,
+                                                    double* __restrict__ best_seq) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    double* sref = reinterpret_cast<double*>(lds_raw);   // [4][T+1] + [4] + int [4], then the live discs [F1P_KMPC_MAX_OBS][5] and their count
+    const int e = blockIdx.x;
+    if (e >= E) return;
+    const int T = cfg.horizon, R = cfg.n_rollouts;
+    double* olive = sref + 4 * (T + 1) + 4 + 2;
+    int* on_live = reinterpret_cast<int*>(olive + 5 * F1P_KMPC_MAX_OBS);
+    const double sx = x0[4 * e], sy = x0[4 * e + 1], sv = x0[4 * e + 2], syaw = x0[4 * e + 3];
+    if (threadIdx.x < 64) obs_compact(obs, e, sx, sy, sv, syaw, T, cfg.dt, cfg.max_speed, cfg.min_speed, false, 1.0, 0.0, olive, nullptr, on_live);
+    __syncthreads();
+    SrcColT<SrcStream, KmpcObs> ce;
+    ce.ce = controls + (size_t)e * T * 2 * R; ce.R = R; ce.col = obs; ce.blocked = false;
+    ce.col.live = olive; ce.col.n_live = __builtin_amdgcn_readfirstlane(*on_live);
+    kmpc_refine_block(ref, ce, cfg, sx, sy, sv, syaw, e, -1, nullptr, sref, steer, speed, best_idx, best_cost, best_seq, nullptr, nullptr, false);
 }
 
 // predict_motion_kinematic :208-221: one thread per ego, T sequential steps, path [E][4][T+1]
@@ -1276,13 +1389,29 @@ static KmpcCol kmpc_col_dev(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, bool filter, 
     return c;
 }
 
+// the obstacle test's kernel argument: the discs in force, and the occupancy test's argument while f1p_kmpc_set_collision is on too (else a
+// null bitmap: no grid)
+static KmpcObs kmpc_obs_dev(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, bool filter) {
+    KmpcObs o;
+    if (ctx->kmpc_collision) static_cast<KmpcCol&>(o) = kmpc_col_dev(ctx, cfg, filter, ctx->kmpc_col_nsub);
+    else {
+        o.g = GridDev{nullptr, 0, 0, 0, 0.0, 0.0, 0.0}; o.clear = nullptr; o.n_sub = ctx->kmpc_col_nsub; o.force64 = ctx->kmpc_mixed ? 0 : 1;
+    }
+    o.obs = ctx->kmpc_obs_cur; o.M = ctx->kmpc_obs_M; o.live = nullptr; o.n_live = 0;
+    return o;
+}
+
 // the device copy of the configuration the shooting kernels' fp64 tails read.  A small write-once table (round 6): every distinct
 // configuration gets its own device slot and its own PINNED host shadow, neither is overwritten while a launch that reads it may be in
 // flight -- two planners alternating configurations on one context hit their slots without any copy; a ninth distinct configuration
 // drains the stream and starts the table over.  (The struct has no padding: int32 x 2 then doubles, tests/test_abi.py checks the layout.)
 static int ensure_kmpc_cfg(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg) {
+    // (each under its own guard: a failed host allocation leaves the device table for the next call to complete, never a null shadow behind it)
     if (!ctx->d_kmpc_cfg) {
         F1P_HIP(ctx, hipMalloc((void**)&ctx->d_kmpc_cfg, sizeof(f1p_kmpc_cfg) * F1P_KMPC_CFG_SLOTS));
+        ctx->kmpc_cfg_used = 0;
+    }
+    if (!ctx->h_kmpc_cfg) {
         F1P_HIP(ctx, hipHostMalloc((void**)&ctx->h_kmpc_cfg, sizeof(f1p_kmpc_cfg) * F1P_KMPC_CFG_SLOTS, hipHostMallocDefault));
         ctx->kmpc_cfg_used = 0;
     }
@@ -1304,6 +1433,12 @@ int launch_kmpc_shoot(f1p_ctx* ctx, const double* d_x0, const double* d_ref, con
                       double* d_best_cost, double* d_best_seq) {
     if (E <= 0) return F1P_OK;
     const size_t T1 = (size_t)cfg->horizon + 1;
+    if (ctx->kmpc_obs_cur) {                                          // (the caller checked E, the grid and the groups: kmpc_collision_check)
+        const size_t lds = sizeof(double) * (4 * T1 + 4) + sizeof(int) * 4 + sizeof(double) * 5 * F1P_KMPC_MAX_OBS + sizeof(int) * 4;
+        hipLaunchKernelGGL(k_kmpc_shoot_obs, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E,
+                           *cfg, kmpc_obs_dev(ctx, cfg, false), d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
+        return check_hip(ctx, hipGetLastError(), "k_kmpc_shoot_obs launch");
+    }
     if (ctx->kmpc_collision) {                                        // (the caller checked the grid: kmpc_collision_check)
         const size_t lds = sizeof(double) * (4 * T1 + 4) + sizeof(int) * 4;
         hipLaunchKernelGGL(k_kmpc_shoot_col, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E,
@@ -1406,6 +1541,8 @@ int launch_kmpc_plan_gen(f1p_ctx* ctx, const double* d_x0, const double* d_ref, 
     // the raceline / track plans follow f1p_kmpc_set_collision; a list of batch indices is f1p_stmpc_plan_batch's kinematic branch and
     // follows f1p_stmpc_set_collision, with its own count
     const bool collide = d_ids ? ctx->stmpc_collision : ctx->kmpc_collision;
+    const bool discs = !d_ids && ctx->kmpc_obs_cur;                   // f1p_kmpc_set_obstacles: the raceline / track plans only
+    if (discs) lds += 8 + (sizeof(double) + sizeof(float)) * 5 * F1P_KMPC_MAX_OBS + sizeof(int) * 4;
     lds = (lds + 15) & ~(size_t)15;
     if (lds > (size_t)ctx->prop.sharedMemPerBlock) return set_error(ctx, F1P_EINVAL, "horizon / n_rollouts need more LDS than a workgroup has: use fewer rollouts per plan");
     if (const int rc = ensure_kmpc_cfg(ctx, cfg)) return rc;
@@ -1420,6 +1557,10 @@ int launch_kmpc_plan_gen(f1p_ctx* ctx, const double* d_x0, const double* d_ref, 
         return check_hip(ctx, hipGetLastError(), what);
     };
     const KmpcIdxArgs ia{d_ids, wstride, ego_off};
+    if (discs) {
+        if (ga.G != 1) return set_error(ctx, F1P_ESTATE, "kmpc obstacle test: one workgroup per ego only (f1p_kmpc_set_groups(0))");
+        return launch(k_kmpc_plan_gen_obs, "k_kmpc_plan_gen_obs launch", kmpc_obs_dev(ctx, cfg, true));
+    }
     if (collide) {
         if (ga.G != 1) return set_error(ctx, F1P_ESTATE, "kmpc collision test: one workgroup per ego only (f1p_kmpc_set_groups(0))");
         const KmpcCol col = kmpc_col_dev(ctx, cfg, true, d_ids ? ctx->stmpc_col_nsub_k : ctx->kmpc_col_nsub);

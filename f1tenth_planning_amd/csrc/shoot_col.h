@@ -57,4 +57,99 @@ struct KmpcColF {
     }
 };
 
+// ---------------------------------------------------------------------------------------------------
+// Moving obstacles (f1p_kmpc_set_obstacles): discs (x, y, vx, vy, r) per ego, map frame, at constant velocity.  The tested
+// points are the occupancy test's; the point of step t at fraction f = j / n_sub has the time  tau = ((double)t + f) * dt,  a live slot's
+// centre is there  c = (x + vx tau, y + vy tau),  and the point is blocked when  !(|P - c|^2 > r r)  -- touching blocks, a NaN blocks.
+// KmpcObs IS a KmpcCol (has_col finds it, every decision path of the occupancy test serves it): a null bitmap means "no grid", with one
+// the point is tested against both.  `obs` / `M` come from the launcher; `live` / `n_live` are filled in by the kernel, once per
+// workgroup: the ego's live slots (r >= 0) that can be reached within the horizon, compacted into LDS as (x, y, vx, vy, r r).
+// ---------------------------------------------------------------------------------------------------
+struct KmpcObs : KmpcCol {
+    const double* obs;                // [E][M][5]
+    int M;
+    const double* live;               // LDS [n_live][5]
+    int n_live;
+    __device__ __forceinline__ bool disc(double x, double y, double tau) const {
+        bool hit = false;
+        for (int m = 0; m < n_live; ++m) {
+            const double* o = live + 5 * m;
+            const double cx = o[0] + o[2] * tau, cy = o[1] + o[3] * tau;
+            const double dx = x - cx, dy = y - cy, d2 = dx * dx + dy * dy;
+            hit |= !(d2 > o[4]);
+        }
+        return hit;
+    }
+    // the tested points of step t, p -> q
+    __device__ __forceinline__ bool seg_t(int t, double dt, double px, double py, double qx, double qy) const {
+        bool hit = false;
+        for (int j = 1; j <= n_sub; ++j) {
+            const double f = (double)j / (double)n_sub;
+            const bool end = j == n_sub;                              // (p_{t+1} itself, not p + (q - p) * 1.0)
+            const double x = end ? qx : px + (qx - px) * f, y = end ? qy : py + (qy - py) * f;
+            if (g.bits) hit |= occupied(x, y);
+            hit |= disc(x, y, ((double)t + f) * dt);
+        }
+        return hit;
+    }
+};
+template <typename... X> constexpr bool has_obs = (std::is_base_of_v<KmpcObs, X> || ...);
+// the test's argument type in a pack of optional arguments (the last of them; KmpcCol when there is none)
+template <typename... X> struct col_arg { using type = KmpcCol; };
+template <typename A> struct col_arg<A> { using type = A; };
+template <typename A, typename B, typename... X> struct col_arg<A, B, X...> : col_arg<B, X...> {};
+// the points of step t, p -> q, against whichever test `c` is (the grid has no time axis)
+__device__ __forceinline__ bool col_seg(const KmpcCol& c, int, double, double px, double py, double qx, double qy) { return c.seg(px, py, qx, qy); }
+__device__ __forceinline__ bool col_seg(const KmpcObs& c, int t, double dt, double px, double py, double qx, double qy) { return c.seg_t(t, dt, px, py, qx, qy); }
+
+// The ego's live slots -> LDS, by the workgroup's first wave (all of its lanes call; M <= 64).  A slot is dropped when even the
+// fastest ego and the disc heading straight for each other cannot meet within the horizon:  |o - p_0| - r - |v_o| T dt > reach,  reach =
+// max(|v_0|, |max_speed|, |min_speed|) T dt  (the first step runs at v_0, every later one inside the speed bounds; 1e-9 of slack for the
+// roundings).  Only for tame operands: with a non-finite or beyond-1e100 value in the slot or in the ego's state (x, y, v, yaw: a NaN speed or
+// heading makes every tested point NaN, which any live slot blocks) every live slot is kept.  live64: (x, y, vx, vy, r r).  live32 (nullable, the f32 filter's table): the centre relative to the ego and the
+// velocity, in the filter's frame (iso: rotated by -yaw0), and the FREE threshold (r + eps)^2 rounded up, eps as DESIGN.md 5j derives it:
+// F1P_K4_POS_ERR_REL x reach for the filter's position + 16 x 2^-24 x (|o_rel|_1 + |v|_1 T dt + r + reach) for the roundings of the
+// obstacle's side.  Returns nothing: *n_out holds the count after the caller's barrier.
+__device__ __forceinline__ void obs_compact(const KmpcObs& ob, int e, double sx, double sy, double sv, double syaw, int T, double dt, double max_speed,
+                                            double min_speed, bool iso, double c0, double s0, double* live64, float* live32, int* n_out) {
+    const int lane = threadIdx.x;
+    bool keep = false;
+    double x = 0.0, y = 0.0, vx = 0.0, vy = 0.0, r = 0.0;
+    const double Tdt = (double)T * dt, reach = fmax(fabs(sv), fmax(fabs(max_speed), fabs(min_speed))) * Tdt;
+    if (lane < ob.M) {
+        const double* o = ob.obs + ((size_t)e * ob.M + lane) * 5;
+        x = o[0]; y = o[1]; vx = o[2]; vy = o[3]; r = o[4];
+        if (r >= 0.0) {
+            const double dx = x - sx, dy = y - sy;
+            const bool tame = fabs(x) < 1.0e100 && fabs(y) < 1.0e100 && fabs(vx) < 1.0e100 && fabs(vy) < 1.0e100 && r < 1.0e100 && fabs(sx) < 1.0e100 && fabs(sy) < 1.0e100 &&
+                              fabs(sv) < 1.0e100 && fabs(syaw) < 1.0e100;      // (a NaN fails every one of these)
+            const bool far = tame && sqrt(dx * dx + dy * dy) - r - sqrt(vx * vx + vy * vy) * Tdt > reach * (1.0 + 1.0e-9) + 1.0e-9;
+            keep = !far;
+        }
+    }
+    const unsigned long long votes = __ballot(keep);
+    if (keep) {
+        const int pos = __popcll(votes & ((1ull << lane) - 1ull));
+        live64[5 * pos] = x; live64[5 * pos + 1] = y; live64[5 * pos + 2] = vx; live64[5 * pos + 3] = vy; live64[5 * pos + 4] = r * r;
+        if (live32) {
+            const double dx = x - sx, dy = y - sy;
+            const double rx = iso ? c0 * dx + s0 * dy : dx, ry = iso ? c0 * dy - s0 * dx : dy;
+            const double wx = iso ? c0 * vx + s0 * vy : vx, wy = iso ? c0 * vy - s0 * vx : vy;
+            const double S = (fabs(rx) + fabs(ry)) + (fabs(wx) + fabs(wy)) * Tdt + r + reach;
+            const double rr = r + (F1P_K4_POS_ERR_REL * reach + 1.0e-6 * S);       // (1e-6 >= 16 x 2^-24)
+            live32[5 * pos] = (float)rx; live32[5 * pos + 1] = (float)ry; live32[5 * pos + 2] = (float)wx; live32[5 * pos + 3] = (float)wy;
+            live32[5 * pos + 4] = (float)(rr * rr * (1.0 + 1.0e-6));               // (the rounding to f32 is inside the factor; NaN / inf: never FREE)
+        }
+    }
+    if (lane == 0) *n_out = __popcll(votes);
+}
+
+// the f32 filter's side: a point is FREE against a slot only when its f32 distance from the f32 centre exceeds r + eps
+struct KmpcObsF {
+    const float* live;                // LDS [n_live][5] (obs_compact)
+    int n_live;
+    int grid;                         // the occupancy test too (KmpcColF)
+    float dt;
+};
+
 }  // namespace f1p

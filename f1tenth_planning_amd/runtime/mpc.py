@@ -8,6 +8,19 @@ from .._abi import KmpcCfg
 from .core import _dev, _f64, _pick, _ptr, _ref, _tid
 
 
+def kmpc_set_obstacles(ctx, obs):
+    """moving discs for the shooting solver's rollouts (f1p_kmpc_set_obstacles) on Context `ctx`: obs [E, M, 5] fp64 rows (x, y, vx, vy, r),
+    map frame, M <= 16, a row with r < 0 or NaN is empty; they stay in force for kmpc_plan* / kmpc_shoot* of E egos until the next set.
+    None clears.  (The public face of Context._kmpc_set_obstacles: Context's public methods are a pinned record, tests/test_runtime_calls.py.)"""
+    ctx._kmpc_set_obstacles(obs)
+
+
+def kmpc_set_obstacles_dev(ctx, d_obs, E=None, M=None):
+    """kmpc_set_obstacles on a device buffer [E][M][5] fp64 that the context BORROWS: keep it alive, rewrite it in place between plans.
+    E and M are required with a buffer; d_obs None clears."""
+    ctx._kmpc_set_obstacles_dev(d_obs, E, M)
+
+
 class _Mpc:
     # ---- MPC: the kinematic (kmpc_*, state width 4) and the dynamic (stmpc_*, 7) wrappers share their bodies -----------------------
     def kmpc_ref(self, states, horizon, dt=0.1, dl=0.03):
@@ -180,6 +193,23 @@ class _Mpc:
         """test the shooting solver's rollouts against the occupancy grid at n_sub points per time step (f1p_kmpc_set_collision): a
         blocked rollout cannot win; an ego whose rollouts are all blocked gets best_idx -1, cost +inf, steer 0, speed 0"""
         self._check(self.lib.f1p_kmpc_set_collision(self.h, 1 if on else 0, int(n_sub)))
+
+    def _kmpc_set_obstacles(self, obs):
+        if obs is None:
+            self._check(self.lib.f1p_kmpc_set_obstacles(self.h, None, 0, 0))
+            return
+        o = _f64(obs)
+        if o.ndim != 3 or o.shape[2] != 5:
+            raise ValueError("obstacles must be [E, M, 5] = (x, y, vx, vy, r)")
+        self._check(self.lib.f1p_kmpc_set_obstacles(self.h, _ptr(o), o.shape[0], o.shape[1]))
+
+    def _kmpc_set_obstacles_dev(self, d_obs, E=None, M=None):
+        if d_obs is None:
+            self._check(self.lib.f1p_kmpc_set_obstacles_dev(self.h, None, 0, 0))
+            return
+        if E is None or M is None:
+            raise ValueError("a device array of obstacles needs its E and M")
+        self._check(self.lib.f1p_kmpc_set_obstacles_dev(self.h, _dev(d_obs), int(E), int(M)))
 
     def stmpc_set_collision(self, on=True, n_sub=1, n_sub_k=2):
         """test the dynamic MPC's shooting rollouts against the occupancy grid (f1p_stmpc_set_collision): n_sub points per step of the

@@ -615,6 +615,26 @@ int f1p_kmpc_set_groups(f1p_ctx* ctx, int32_t groups);
  * F1P_ESTATE) or when f1p_kmpc_set_groups(> 0) is in force (F1P_ESTATE).  n_sub outside [1, 16]: F1P_EINVAL, nothing changes.
  * Not covered: f1p_kmpc_qp_*.  f1p_stmpc_* has a switch of its own, f1p_stmpc_set_collision; this one does not reach it. */
 int f1p_kmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub);
+/* Moving obstacles on the rollouts of the shooting solver: per ego up to F1P_KMPC_MAX_OBS discs at constant
+ * velocity, obs [E][M][5] fp64 rows (x, y, vx, vy, r) in the map frame.  A slot with !(r >= 0) -- r negative or NaN -- is EMPTY;
+ * empty slots may sit anywhere.  The caller folds the ego's own radius into r (a point-against-disc test, like f1p_inflate_grid).
+ * Tested points: f1p_kmpc_set_collision's, with its n_sub (the context keeps the number while `on` is 0; default 1).  The point of
+ * step t at f = (double)j / (double)n_sub has the time tau = ((double)t + f) * dt; against a live slot, in fp64 and in this order,
+ *   cx = x + vx * tau; cy = y + vy * tau; dx = Px - cx; dy = Py - cy; d2 = dx*dx + dy*dy;   blocked when !(d2 > r*r)
+ * -- touching blocks, a NaN anywhere blocks.  A rollout is blocked when a tested point is blocked by a live slot, or by the grid
+ * while f1p_kmpc_set_collision is on as well; the decision, the NaN-cost rule and the all-blocked outputs are that test's.  An
+ * ego without a live slot gets the bits of a plan without obstacles.
+ * f1p_kmpc_set_obstacles copies the array into a buffer of the context on its stream; obs == NULL or M == 0 clears.
+ * f1p_kmpc_set_obstacles_dev BORROWS a device array: the caller keeps it alive and may rewrite it in place between plans (in
+ * stream order).  The obstacles stay until the next set or clear and apply to f1p_kmpc_plan_batch / _dev and
+ * f1p_kmpc_shoot_batch / _dev (raceline and track-set references alike), with or without a grid; the streamed entry points are
+ * then evaluated in plain fp64 whatever the mode and equal f1p_kmpc_plan_dev bit for bit.
+ * Errors, nothing launched: M outside [1, 16]: F1P_EINVAL; a plan whose E is not the E the obstacles were set for: F1P_ESTATE;
+ * f1p_kmpc_set_groups(> 0) while obstacles are set (and setting obstacles while groups are forced): F1P_ESTATE.
+ * Not covered: f1p_stmpc_* (its kinematic branch included), f1p_kmpc_qp_*, and a MultiContext's sharded plans. */
+#define F1P_KMPC_MAX_OBS 16
+int f1p_kmpc_set_obstacles(f1p_ctx* ctx, const double* obs, int32_t E, int32_t M);
+int f1p_kmpc_set_obstacles_dev(f1p_ctx* ctx, const double* d_obs, int32_t E, int32_t M);
 /* The reference extraction's heading fix-up (calc_ref_trajectory_kinematic, kinematic_mpc.py:198-203: course headings more than
  * 4.5 rad from the vehicle's are folded by abs(. -+ 2 pi), IN PLACE and persistently on the caller's array).  on = 1 (default):
  * applied per ego to the gathered values, the course array is never modified (batches of egos with different headings).
