@@ -2,7 +2,11 @@
 (loop shape of the reference's examples/control/dynamic_mpc.py).
 
 --obstacles N parks N obstacles on the line of the synthetic track and drives the loop twice, without and with the occupancy test on the
-rollouts (mpc_config.COLLISION), counting the vehicle-steps that ended in an occupied cell."""
+rollouts (mpc_config.COLLISION), counting the vehicle-steps that ended in an occupied cell.
+
+--opponents M (with --envs E >= 2) starts the E vehicles as a pack on one course, the fast ones behind the slow ones, and drives the loop
+twice: each vehicle planning as if it were alone, then with its M nearest other vehicles as moving obstacles, predicted at constant
+velocity (planner.obstacles; both branches of the model test them).  It reports the smallest distance between two vehicles over each run."""
 import os
 import sys
 
@@ -19,6 +23,7 @@ def main():
     ap.add_argument("--solver", choices=["shooting", "qp"], default="shooting")
     ap.add_argument("--tracks", type=int, default=0, help="N agents on N lanes offset sideways from the centreline, one track set (--solver qp)")
     ap.add_argument("--obstacles", type=int, default=0, help="park N obstacles (discs of 0.3 m) on the line and compare the loop with the occupancy test off / on")
+    ap.add_argument("--opponents", type=int, default=0, help="with --envs E: each vehicle's M nearest other vehicles are moving obstacles of its rollouts; compares the pack with the test off / on")
     ap.add_argument("--substeps", type=int, default=1, help="tested points per step of the dynamic model (mpc_config.COLLISION_SUBSTEPS; the kinematic branch tests twice as many)")
     args = ap.parse_args()
     lanes = ids = None
@@ -38,6 +43,13 @@ def main():
 
         return common.obstacle_runs(args, rl, [rl[:, 0], rl[:, 1], rl[:, 3], rl[:, 2]], mpc_config(),
                                     lambda wp, c: STMPCPlanner(waypoints=wp, config=c), lambda env: env.state, substeps)
+    if args.opponents > 0:
+        if args.tracks > 0:
+            raise SystemExit("--opponents drives the pack on the raceline with the shooting solver")
+        cfg = mpc_config(SOLVER=args.solver)
+        cfg.COLLISION_SUBSTEPS, cfg.COLLISION_SUBSTEPS_K = args.substeps, min(2 * args.substeps, 16)
+        return common.opponent_runs(args, rl, [rl[:, 0], rl[:, 1], rl[:, 3], rl[:, 2]], cfg, lambda wp, c: STMPCPlanner(waypoints=wp, config=c),
+                                    lambda env: env.state)
     planner = STMPCPlanner(waypoints=[rl[:, 0], rl[:, 1], rl[:, 3], rl[:, 2]], config=mpc_config(SOLVER=args.solver))
     if args.tracks > 0:
         normal = rl[:, 3] + np.pi / 2

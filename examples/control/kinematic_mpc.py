@@ -23,43 +23,9 @@ def obstacle_runs(args, rl, waypoints, cfg):
                                 lambda env: env.state[:, [0, 1, 3, 4]], lambda c, n: setattr(c, "COLLISION_SUBSTEPS", n))
 
 
-def opponent_runs(args, rl, waypoints, cfg, gap=1.5, radius=0.45):
-    """radius: the two vehicles' radii folded into the obstacle's (a point-against-disc test)"""
-    from f1tenth_planning_amd import sim
-    E, M = args.envs, min(args.opponents, args.envs - 1, 16)
-    if args.solver == "qp" or E < 2:
-        raise SystemExit("--opponents needs the shooting solver and --envs >= 2")
-    seg = np.hypot(np.diff(rl[:, 0]), np.diff(rl[:, 1]))
-    k0 = int(np.argmin(np.abs(rl[:, 3])))                                # start where the heading is far from the +-pi seam
-    k = k0 + np.searchsorted(np.cumsum(np.concatenate([seg[k0:], seg[:k0]])), gap * np.arange(E))
-    k %= len(rl) - 1
-    poses = np.column_stack([rl[k, 0], rl[k, 1], rl[k, 3]])
-    scale = np.linspace(1.0, 0.5, E)                                    # vehicle 0 is last in line and the fastest
+def opponent_runs(args, rl, waypoints, cfg):
     cfg.COLLISION_SUBSTEPS = args.substeps
-    print(f"{E} vehicles {gap} m apart on one course, speed scales 1.0 (rear) .. 0.5 (front), {args.steps} steps, {M} opponents each")
-    closest = {}
-    for on in (False, True):
-        planner = KMPCPlanner(waypoints=[w.copy() for w in waypoints], config=cfg)
-        env = sim.make("f110_gym:f110-v0", num_agents=E)
-        env.reset(poses)
-        d_min, n_stop = np.inf, 0
-        for it in range(args.steps):
-            st = env.state[:, [0, 1, 3, 4]]                             # (x, y, v, yaw)
-            d = np.hypot(st[:, None, 0] - st[None, :, 0], st[:, None, 1] - st[None, :, 1]) + np.diag(np.full(E, np.inf))
-            d_min = min(d_min, float(d.min()))
-            obs = None
-            if on:
-                near = np.argsort(d, axis=1)[:, :M]                     # [E, M] the nearest other vehicles
-                o = st[near]
-                obs = np.stack([o[:, :, 0], o[:, :, 1], o[:, :, 2] * np.cos(o[:, :, 3]), o[:, :, 2] * np.sin(o[:, :, 3]), np.full((E, M), radius)], 2)
-            planner.obstacles = obs
-            out = planner.plan_batch(st)
-            n_stop += int((out["best_idx"] < 0).sum())
-            env.step(np.column_stack([out["steer"], out["speed"] * scale]))
-        closest[on] = d_min
-        print(f"obstacle test {'on ' if on else 'off'}: smallest distance between two vehicles {d_min:.3f} m"
-              + (f" ({n_stop} plans had every rollout blocked)" if on else ""))
-    return closest
+    return common.opponent_runs(args, rl, waypoints, cfg, lambda wp, c: KMPCPlanner(waypoints=wp, config=c), lambda env: env.state[:, [0, 1, 3, 4]])
 
 
 def main():

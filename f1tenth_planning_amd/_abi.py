@@ -265,6 +265,8 @@ PROTOTYPES = {
     "f1p_kmpc_set_obstacles_dev": (C.c_int, [_P, _P, _I, _I]),
     "f1p_stmpc_set_mode": (C.c_int, [_P, _I, _P, _P]),
     "f1p_stmpc_set_collision": (C.c_int, [_P, _I, _I, _I]),
+    "f1p_stmpc_set_obstacles": (C.c_int, [_P, _P, _I, _I]),
+    "f1p_stmpc_set_obstacles_dev": (C.c_int, [_P, _P, _I, _I]),
     "f1p_kmpc_set_yaw_fixup": (C.c_int, [_P, _I]),
     "f1p_kmpc_qp_opts_default": (None, [C.POINTER(KmpcQpOpts)]),
     "f1p_kmpc_qp_batch": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(KmpcCfg), C.POINTER(KmpcQpOpts), _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -184,3 +184,30 @@ class MPCPlanner(OccupancyMap, Planner):
         self._check_solver()
         if self.config.COLLISION and self._map is None:
             raise ValueError("mpc_config.COLLISION needs an occupancy grid: call set_map / load_map first")
+
+    # the attribute `obstacles` (moving discs): the next plan / plan_batch call TAKES it -- None again afterwards, also
+    # when the call raises -- so obstacles are given per call, as a keyword argument would be
+    def _take_obstacles(self):
+        obstacles, self.obstacles = self.obstacles, None
+        return obstacles
+
+    def _check_obstacles(self, obstacles, E, single=False):
+        """-> None or obstacles as fp64 [E, M, 5]; ValueError before anything touches the GPU.  single: plan()'s [M, 5] for its one ego"""
+        if obstacles is None:
+            return None
+        c = self.config
+        if c.SOLVER == "qp":
+            raise ValueError("obstacles are tested on the shooting solver's rollouts; SOLVER='qp' takes none")
+        o = np.ascontiguousarray(obstacles, dtype=np.float64)
+        if single:
+            if o.ndim != 2:
+                raise ValueError("obstacles must be [M, 5] = (x, y, vx, vy, r)")
+            o = o[None]
+        if o.ndim != 3 or o.shape[0] != E or o.shape[2] != 5 or o.shape[1] < 1:
+            raise ValueError(f"obstacles must be [E={E}, M, 5] = (x, y, vx, vy, r) with 1 <= M <= 16")
+        if o.shape[1] > 16:
+            raise ValueError("at most 16 obstacles per ego (M <= 16)")
+        for name in self._SUBSTEPS:
+            if not 1 <= int(getattr(c, name)) <= 16:
+                raise ValueError(f"{name} must be in [1, 16]")
+        return o

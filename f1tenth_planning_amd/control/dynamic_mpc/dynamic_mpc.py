@@ -12,6 +12,11 @@ warm-started like the reference from the previous solution (unshifted, with its 
 
 mpc_config.COLLISION = True (shooting only) tests every rollout of both branches against the occupancy grid installed with set_map /
 load_map: a rollout that touches an occupied cell cannot win (f1p_stmpc_set_collision).
+
+planner.obstacles = [M, 5] before plan() / [E, M, 5] before plan_batch() (shooting only) tests every rollout of THAT call, whichever branch
+an ego takes, against moving discs: rows (x, y, vx, vy, r) in the map frame at constant velocity, M <= 16, r < 0 or NaN = an empty slot,
+row e of a batch for ego e of `states`.  A rollout that is inside a disc at the time it gets there cannot win (f1p_stmpc_set_obstacles,
+DESIGN.md 5k).  The next plan / plan_batch call TAKES the attribute: it is None again afterwards -- KMPCPlanner's contract.
 """
 import warnings
 from dataclasses import dataclass, field
@@ -20,7 +25,7 @@ import numpy as np
 
 from ... import _abi
 from ..._planner import MPCPlanner, _course_columns, _diag, _track_columns, kin_cfg_struct, qp_opts
-from ...runtime import Context
+from ...runtime import Context, kmpc_set_obstacles, stmpc_set_obstacles
 from ..kinematic_mpc.kinematic_mpc import State  # noqa: F401  (same 7-field dataclass, :89-98)
 
 
@@ -100,16 +105,25 @@ class STMPCPlanner(MPCPlanner):
         self._batch_calls = 0
         self._map = None                   # (img u8, resolution, (ox, oy), occupied_below) of set_map
         self._inflate = 0.0
+        self.obstacles = None              # moving discs of the NEXT plan, which takes them: [M, 5] for plan(), [E, M, 5] for plan_batch()
+        self._obstacles_set = [False, False]   # the context holds obstacles of an earlier plan: the kmpc state, the stmpc state
         self._check_solver()
 
-    def _collision_switch(self, ctx):
+    def _collision_switch(self, ctx, obstacles=None, kinematic=False):
         """the planner's context follows mpc_config: the stmpc switch (plan_batch, plan()'s dynamic branch) and, for plan()'s kinematic
-        branch through ctx.kmpc_shoot, the kmpc switch with COLLISION_SUBSTEPS_K"""
+        branch through ctx.kmpc_shoot, the kmpc switch with COLLISION_SUBSTEPS_K.  The obstacles of this plan (None clears them) go to
+        the stmpc state, or (kinematic: plan()'s kinematic branch) to the kmpc state; the substep counts serve both tests"""
         c = self.config
         if c.SOLVER != "qp":
             on = bool(c.COLLISION)
-            ctx.stmpc_set_collision(on, int(c.COLLISION_SUBSTEPS) if on else 1, int(c.COLLISION_SUBSTEPS_K) if on else 2)
-            ctx.kmpc_set_collision(on, int(c.COLLISION_SUBSTEPS_K) if on else 1)
+            sub = on or obstacles is not None
+            ctx.stmpc_set_collision(on, int(c.COLLISION_SUBSTEPS) if sub else 1, int(c.COLLISION_SUBSTEPS_K) if sub else 2)
+            ctx.kmpc_set_collision(on, int(c.COLLISION_SUBSTEPS_K) if sub else 1)
+            for k, setter in ((0, kmpc_set_obstacles), (1, stmpc_set_obstacles)):
+                o = obstacles if k == (0 if kinematic else 1) else None
+                if o is not None or self._obstacles_set[k]:       # (a plan without any, after plans without any: nothing to clear)
+                    setter(ctx, o)
+                    self._obstacles_set[k] = o is not None
 
     def _bind(self, waypoints):
         self._take_waypoints(waypoints, 3, "Waypoints needs to be a (Nxm), m >= 3, numpy array!", asarray=True)
@@ -167,6 +181,9 @@ class STMPCPlanner(MPCPlanner):
         the warm-started single-vehicle call.  `tracks` needs SOLVER='qp' (below).
         mpc_config.COLLISION: every rollout of both branches is tested against the map; an ego whose rollouts are all blocked has best_idx
         -1, best_cost +inf, steer 0, speed 0, a zero sequence (up to its branch's horizon) and starts its next plan from a zero warm start.
+        self.obstacles (taken by this call: None afterwards): [E, M, 5] rows (x, y, vx, vy, r) of moving discs, row e for ego e of `states`
+        whichever branch it takes (M <= 16, r < 0 or NaN: empty), tested at COLLISION_SUBSTEPS / COLLISION_SUBSTEPS_K points per step
+        whether COLLISION is on or not; None: none.  All-blocked egos as with COLLISION.
         SOLVER == "qp": states [E, 7] -> dict(steer, speed, status, branch (1 dynamic, 0 kinematic), obj[, u [E, max(T, TK), 2] =
         (oa, odelta_v), NaN past the branch's horizon]) -- per-ego status (0 solved, 1 infeasible, 2 not converged, 3 non-finite input
         or model data), never raised.
@@ -177,11 +194,14 @@ class STMPCPlanner(MPCPlanner):
         tracks is a Context-level chain: ctx.stmpc_ref_tracks -> ctx.stmpc_shoot, or its rows [0, 1, 3, 4] with (TK, DTK, dlk) ->
         ctx.kmpc_shoot for the kinematic branch."""
         self._check_collision()
+        obstacles = self._take_obstacles()
+        if obstacles is not None:
+            obstacles = self._check_obstacles(obstacles, np.asarray(states).reshape(-1, 7).shape[0])
         if self.config.SOLVER != "qp":
             if tracks is not None:
                 raise ValueError("plan_batch with tracks needs SOLVER='qp'")
             ctx = self._bind(waypoints)
-            self._collision_switch(ctx)
+            self._collision_switch(ctx, obstacles)
             return self._shoot(ctx, np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 7), want_u=want_u)
         if tracks is not None:
             cols = _track_columns(tracks, track_ids)
@@ -206,12 +226,15 @@ class STMPCPlanner(MPCPlanner):
     def plan(self, states, waypoints=None):
         """states: [x, y, delta, v, yaw, yawrate, beta].  Returns (steering_angle, speed).  mpc_config.COLLISION: the rollouts of the
         branch taken are tested against the map; when every one of them is blocked the call warns and returns (0.0, 0.0) -- a soft failure
-        like KMPCPlanner's -- and oa / odelta_v are the zero sequence."""
+        like KMPCPlanner's -- and oa / odelta_v are the zero sequence.
+        self.obstacles: [M, 5] rows (x, y, vx, vy, r) of moving discs for this call (taken: None afterwards), or None; tested in the branch
+        taken, an all-blocked plan warns and returns (0.0, 0.0) likewise."""
         self._check_collision()
+        obstacles = self._check_obstacles(self._take_obstacles(), 1, single=True)
         ctx = self._bind(waypoints)
-        self._collision_switch(ctx)
         c = self.config
         st = np.asarray(states, dtype=np.float64)
+        self._collision_switch(ctx, obstacles, kinematic=bool(st[3] <= c.V_KS))
         if c.SOLVER == "qp":
             out = self._qp(ctx, st[None, :7])
             s = int(out["status"][0])
@@ -234,8 +257,9 @@ class STMPCPlanner(MPCPlanner):
             ref = ctx.stmpc_ref(np.array([[st[0], st[1], st[3], st[4]]]), c.T, c.DT, c.dl)
             out = ctx.stmpc_shoot(st[None, :7], ref, self._sample(c.T, c.N_ROLLOUTS, c.SIGMA_STEER_V, c.SIGMA_ACCEL, c.MAX_STEER_V, c.MAX_ACCEL), cfg)
             self.odelta_v, self.oa = out["best_seq"][0, :, 0], out["best_seq"][0, :, 1]
-        if int(out["best_idx"][0]) < 0:        # every rollout runs into an occupied cell
-            warnings.warn("dynamic MPC: every rollout is blocked by the occupancy grid; returning (0.0, 0.0)", RuntimeWarning, stacklevel=2)
+        if int(out["best_idx"][0]) < 0:        # every rollout runs into an occupied cell or a disc
+            warnings.warn("dynamic MPC: every rollout is blocked by the " + ("occupancy grid" if obstacles is None else "obstacles or the occupancy grid") +
+                          "; returning (0.0, 0.0)", RuntimeWarning, stacklevel=2)
             return 0.0, 0.0
         return float(out["steer"][0]), float(out["speed"][0])
 

@@ -130,22 +130,6 @@ class KMPCPlanner(MPCPlanner):
                 kmpc_set_obstacles(ctx, obstacles)
                 self._obstacles_set = obstacles is not None
 
-    def _check_obstacles(self, obstacles, E):
-        """-> None or obstacles as fp64 [E, M, 5]; ValueError before anything touches the GPU"""
-        if obstacles is None:
-            return None
-        c = self.config
-        if c.SOLVER == "qp":
-            raise ValueError("obstacles are tested on the shooting solver's rollouts; SOLVER='qp' takes none")
-        o = np.ascontiguousarray(obstacles, dtype=np.float64)
-        if o.ndim != 3 or o.shape[0] != E or o.shape[2] != 5 or o.shape[1] < 1:
-            raise ValueError(f"obstacles must be [E={E}, M, 5] = (x, y, vx, vy, r) with 1 <= M <= 16")
-        if o.shape[1] > 16:
-            raise ValueError("at most 16 obstacles per ego (M <= 16)")
-        if not 1 <= int(c.COLLISION_SUBSTEPS) <= 16:
-            raise ValueError("COLLISION_SUBSTEPS must be in [1, 16]")
-        return o
-
     def _bind(self, waypoints, fold_yaw=None):
         """fold_yaw: the vehicle heading of a single-vehicle call -- the course headings are then folded in place on the caller's
         array like the reference does (persistent state, :198-203) and the kernel's own stateless per-ego fold is switched off;
@@ -173,12 +157,7 @@ class KMPCPlanner(MPCPlanner):
         Returns (steering_angle, speed).
         """
         self._check_collision()
-        obstacles, self.obstacles = self.obstacles, None
-        if obstacles is not None:
-            o = np.asarray(obstacles, dtype=np.float64)
-            if o.ndim != 2:
-                raise ValueError("obstacles must be [M, 5] = (x, y, vx, vy, r)")
-            obstacles = self._check_obstacles(o[None], 1)
+        obstacles = self._check_obstacles(self._take_obstacles(), 1, single=True)
         ctx = self._bind(waypoints, fold_yaw=float(states[4]))
         self._collision_switch(ctx, obstacles)
         vehicle_state = State(x=states[0], y=states[1], delta=states[2], v=states[3], yaw=states[4], yawrate=states[5],
@@ -239,7 +218,7 @@ class KMPCPlanner(MPCPlanner):
         self._check_collision()
         if self.config.SOLVER == "qp" and controls is not None:
             raise ValueError("controls are candidates of the shooting solver; SOLVER='qp' takes none")
-        obstacles, self.obstacles = self.obstacles, None
+        obstacles = self._take_obstacles()
         if obstacles is not None:
             obstacles = self._check_obstacles(obstacles, np.asarray(x0).reshape(-1, 4).shape[0])
         if tracks is not None:

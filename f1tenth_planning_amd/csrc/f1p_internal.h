@@ -85,6 +85,11 @@ struct f1p_ctx {
     bool stmpc_collision = false;      // f1p_stmpc_set_collision: rollouts of f1p_stmpc_plan_* / f1p_stmpc_shoot_* are tested against d_bits
     int stmpc_col_nsub = 1;            // ... at this many points per step of the dynamic model,
     int stmpc_col_nsub_k = 2;          // ... and at this many per step of f1p_stmpc_plan_batch's kinematic branch
+    // f1p_stmpc_set_obstacles: the dynamic MPC's own moving discs, [E][M][5] fp64 rows in the caller's ego order
+    double* d_stmpc_obs = nullptr;          // the context's own copy, kept across sets when large enough
+    size_t stmpc_obs_bytes = 0;
+    const double* stmpc_obs_cur = nullptr;  // the array in force: d_stmpc_obs or the caller's (f1p_stmpc_set_obstacles_dev); null: none
+    int stmpc_obs_E = 0, stmpc_obs_M = 0;
     float* d_dbg_st_cost32 = nullptr;  // [E][R] filter costs (-inf = untrusted) of the next launches, or null
     int32_t* d_dbg_st_nref = nullptr;  // [E] refined rollouts (-1 = all-fp64 fallback), or null
     char* d_st_scratch = nullptr;      // k_stmpc_filter -> refine -> decide: queue counter | per-ego counts | lists | queue | refined costs

@@ -135,7 +135,14 @@ int f1p_stmpc_set_mode(f1p_ctx* ctx, int32_t mixed, float* d_cost32, int32_t* d_
 
 // f1p_stmpc_set_collision's preconditions, checked by every entry point that would launch the tested kernels -- before anything is launched
 // or any warm-start tag is touched.  kinematic: the call may run f1p_stmpc_plan_batch's kinematic branch (one workgroup per ego with the test)
-static int stmpc_collision_check(f1p_ctx* ctx, bool kinematic) {
+// E: the caller's ego count (f1p_stmpc_set_obstacles' rows are in the caller's order: for plan_batch the batch's E, not a branch's)
+static int stmpc_collision_check(f1p_ctx* ctx, bool kinematic, int E) {
+    if (ctx->stmpc_obs_cur) {                                         // f1p_stmpc_set_obstacles: with or without the grid
+        if (E != ctx->stmpc_obs_E)
+            return set_error(ctx, F1P_ESTATE, "stmpc obstacles were set for " + std::to_string(ctx->stmpc_obs_E) + " egos, this plan has " + std::to_string(E) +
+                                              " (f1p_stmpc_set_obstacles)");
+        if (kinematic && ctx->kmpc_groups > 0) return set_error(ctx, F1P_ESTATE, "stmpc obstacle test runs one workgroup per ego: f1p_kmpc_set_groups(0)");
+    }
     if (!ctx->stmpc_collision) return F1P_OK;
     if (!ctx->has_grid) return set_error(ctx, F1P_ESTATE, "stmpc collision test is on but no occupancy grid is loaded (f1p_set_grid)");
     if (ctx->n_disc > 0)
@@ -155,12 +162,37 @@ int f1p_stmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub, int32_t n_s
     return F1P_OK;
 }
 
+// obs (host or device, by `dev`) -> the discs in force; null or M == 0 clears.  A state of its own beside f1p_kmpc_set_obstacles'.
+static int stmpc_set_obstacles(f1p_ctx* ctx, const double* obs, int32_t E, int32_t M, bool dev) {
+    F1P_ENTER(ctx);
+    if (!obs || M == 0) { ctx->stmpc_obs_cur = nullptr; ctx->stmpc_obs_E = 0; ctx->stmpc_obs_M = 0; return F1P_OK; }
+    if (M < 1 || M > F1P_KMPC_MAX_OBS) return set_error(ctx, F1P_EINVAL, "stmpc obstacles: M must be in [1, 16]");
+    if (E < 1) return set_error(ctx, F1P_EINVAL, "stmpc obstacles: E must be >= 1");
+    if (dev) { ctx->stmpc_obs_cur = obs; ctx->stmpc_obs_E = E; ctx->stmpc_obs_M = M; return F1P_OK; }
+    const size_t bytes = sizeof(double) * 5 * (size_t)E * M;
+    if (bytes > ctx->stmpc_obs_bytes) {
+        ctx->stmpc_obs_cur = nullptr; ctx->stmpc_obs_E = 0; ctx->stmpc_obs_M = 0;
+        F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));              // no launch in flight reads the old copy
+        if (ctx->d_stmpc_obs) (void)hipFree(ctx->d_stmpc_obs);
+        ctx->d_stmpc_obs = nullptr; ctx->stmpc_obs_bytes = 0;
+        F1P_HIP(ctx, hipMalloc((void**)&ctx->d_stmpc_obs, bytes));
+        ctx->stmpc_obs_bytes = bytes;
+    }
+    // (pageable host memory: the copy has left the caller's array when this returns; stream order puts it after the plans already queued)
+    F1P_HIP(ctx, hipMemcpyAsync(ctx->d_stmpc_obs, obs, bytes, hipMemcpyHostToDevice, ctx->stream));
+    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->stmpc_obs_cur = ctx->d_stmpc_obs; ctx->stmpc_obs_E = E; ctx->stmpc_obs_M = M;
+    return F1P_OK;
+}
+int f1p_stmpc_set_obstacles(f1p_ctx* ctx, const double* obs, int32_t E, int32_t M) { return stmpc_set_obstacles(ctx, obs, E, M, false); }
+int f1p_stmpc_set_obstacles_dev(f1p_ctx* ctx, const double* d_obs, int32_t E, int32_t M) { return stmpc_set_obstacles(ctx, d_obs, E, M, true); }
+
 int f1p_stmpc_shoot_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const float* d_controls, int32_t E,
                         const f1p_stmpc_cfg* cfg, double* d_steer, double* d_speed, int32_t* d_best_idx,
                         double* d_best_cost, double* d_best_seq) {
     F1P_ENTER(ctx);
     int rc = validate_stmpc(ctx, cfg, E); if (rc) return rc;
-    if ((rc = stmpc_collision_check(ctx, false))) return rc;
+    if ((rc = stmpc_collision_check(ctx, false, E))) return rc;
     if (E > 0 && (!d_x0 || !d_ref || !d_controls || !d_steer || !d_speed || !d_best_idx))
         return set_error(ctx, F1P_EINVAL, "x0, ref, controls, steer, speed and best_idx are required");
     return launch_stmpc_shoot(ctx, d_x0, d_ref, d_controls, E, cfg, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
@@ -171,7 +203,7 @@ int f1p_stmpc_shoot_batch(f1p_ctx* ctx, const double* x0, const double* ref, con
                           double* best_seq) {
     F1P_ENTER(ctx);
     int rc = validate_stmpc(ctx, cfg, E); if (rc) return rc;
-    if ((rc = stmpc_collision_check(ctx, false))) return rc;
+    if ((rc = stmpc_collision_check(ctx, false, E))) return rc;
     if (E > 0 && (!x0 || !ref || !controls || !steer || !speed || !best_idx))
         return set_error(ctx, F1P_EINVAL, "x0, ref, controls, steer, speed and best_idx are required");
     const size_t T = cfg->horizon, R = cfg->n_rollouts, e = E;
@@ -447,7 +479,7 @@ int f1p_stmpc_plan_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, in
     F1P_ENTER(ctx);
     int rc = validate_stmpc(ctx, cfg, E); if (rc) return rc;
     if ((rc = validate_st_sampler(ctx, smp))) return rc;
-    if ((rc = stmpc_collision_check(ctx, false))) return rc;
+    if ((rc = stmpc_collision_check(ctx, false, E))) return rc;
     if (E == 0) return F1P_OK;
     if (!d_x0 || !d_ref || !d_steer || !d_speed || !d_best_idx) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and best_idx are required");
     if ((rc = ensure_st_warm_dyn(ctx, E, cfg->horizon))) return rc;
@@ -476,7 +508,7 @@ int f1p_stmpc_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_st
     int rc = validate_stmpc(ctx, dcfg, E); if (rc) return rc;
     if ((rc = validate_kmpc(ctx, kcfg, E))) return rc;
     if ((rc = validate_st_sampler(ctx, smp))) return rc;
-    if ((rc = stmpc_collision_check(ctx, true))) return rc;
+    if ((rc = stmpc_collision_check(ctx, true, E))) return rc;
     if (kcfg->n_rollouts > 8192) return set_error(ctx, F1P_EINVAL, "at most 8192 rollouts per kinematic plan");
     if (E > 0 && (!x0 || !steer || !speed || !best_idx)) return set_error(ctx, F1P_EINVAL, "x0, steer, speed and best_idx are required");
     if (!(dl > 0) || !(dlk > 0)) return set_error(ctx, F1P_EINVAL, "dl and dlk must be > 0");

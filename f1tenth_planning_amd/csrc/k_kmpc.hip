@@ -958,6 +958,9 @@ template <typename... X> __device__ __forceinline__ uint32_t kpg_ego(int e, cons
 // first float of ego e's row in ga.warm_in / ga.warm_out
 template <typename... X> __device__ __forceinline__ size_t kpg_wrow(int e, int T, const X&...) { return (size_t)e * 2 * T; }
 template <typename... X> __device__ __forceinline__ size_t kpg_wrow(int e, int T, const KmpcIdxArgs& ia, const X&...) { return ((size_t)ia.ids[e] * ia.wstride); }
+// ego e's row of the obstacle array: the array is indexed by the CALLER's ego order, a compacted launch goes through its index list
+template <typename... X> __device__ __forceinline__ int kpg_orow(int e, const X&...) { return e; }
+template <typename... X> __device__ __forceinline__ int kpg_orow(int e, const KmpcIdxArgs& ia, const X&...) { return ia.ids[e]; }
 
 template <typename... Extra>
 __global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void k_kmpc_plan_gen_t(const double* __restrict__ x0, const double* __restrict__ ref, int E,
@@ -1036,7 +1039,7 @@ __global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void k_kmpc_plan_gen_t(const
         olive = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(c32 + R) + 7) & ~(uintptr_t)7);
         olive32 = reinterpret_cast<float*>(olive + 5 * F1P_KMPC_MAX_OBS);
         on_live = reinterpret_cast<int*>(olive32 + 5 * F1P_KMPC_MAX_OBS);
-        if (tid < 64) obs_compact(col_of(ex...), e, sx, sy, sv, syaw, T, cfg.dt, cfg.max_speed, cfg.min_speed, iso, c0d, s0d, olive, olive32, on_live);
+        if (tid < 64) obs_compact(col_of(ex...), kpg_orow(e, ex...), sx, sy, sv, syaw, T, cfg.dt, cfg.max_speed, cfg.min_speed, iso, c0d, s0d, olive, olive32, on_live);
     }
     __syncthreads();
     KmpcF32 k = kf;
@@ -1162,6 +1165,8 @@ static constexpr auto k_kmpc_plan_gen_col = k_kmpc_plan_gen_t<KmpcCol>;
 static constexpr auto k_kmpc_plan_gen_idx_col = k_kmpc_plan_gen_t<KmpcIdxArgs, KmpcCol>;
 // the moving discs of f1p_kmpc_set_obstacles, alone or with the occupancy test (the bitmap of its KmpcCol part: null = no grid)
 static constexpr auto k_kmpc_plan_gen_obs = k_kmpc_plan_gen_t<KmpcObs>;
+// ... of f1p_stmpc_set_obstacles in f1p_stmpc_plan_batch's kinematic branch: the obstacle row of ego e is ids[e]
+static constexpr auto k_kmpc_plan_gen_idx_obs = k_kmpc_plan_gen_t<KmpcIdxArgs, KmpcObs>;
 
 // materialise SrcGen's controls as the [E][T][2][R] f32 buffer of the streamed entry points (tests: generated == streamed)
 __global__ __launch_bounds__(256) void k_kmpc_gen_controls(float* __restrict__ controls, int E, int T, int R, KmpcGenArgs ga) {
@@ -1391,13 +1396,15 @@ static KmpcCol kmpc_col_dev(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, bool filter, 
 
 // the obstacle test's kernel argument: the discs in force, and the occupancy test's argument while f1p_kmpc_set_collision is on too (else a
 // null bitmap: no grid)
-static KmpcObs kmpc_obs_dev(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, bool filter) {
+// (st: f1p_stmpc_plan_batch's kinematic branch -- the stmpc switch, its n_sub_k and the stmpc obstacles)
+static KmpcObs kmpc_obs_dev(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, bool filter, bool st = false) {
     KmpcObs o;
-    if (ctx->kmpc_collision) static_cast<KmpcCol&>(o) = kmpc_col_dev(ctx, cfg, filter, ctx->kmpc_col_nsub);
+    const int n_sub = st ? ctx->stmpc_col_nsub_k : ctx->kmpc_col_nsub;
+    if (st ? ctx->stmpc_collision : ctx->kmpc_collision) static_cast<KmpcCol&>(o) = kmpc_col_dev(ctx, cfg, filter, n_sub);
     else {
-        o.g = GridDev{nullptr, 0, 0, 0, 0.0, 0.0, 0.0}; o.clear = nullptr; o.n_sub = ctx->kmpc_col_nsub; o.force64 = ctx->kmpc_mixed ? 0 : 1;
+        o.g = GridDev{nullptr, 0, 0, 0, 0.0, 0.0, 0.0}; o.clear = nullptr; o.n_sub = n_sub; o.force64 = ctx->kmpc_mixed ? 0 : 1;
     }
-    o.obs = ctx->kmpc_obs_cur; o.M = ctx->kmpc_obs_M; o.live = nullptr; o.n_live = 0;
+    o.obs = st ? ctx->stmpc_obs_cur : ctx->kmpc_obs_cur; o.M = st ? ctx->stmpc_obs_M : ctx->kmpc_obs_M; o.live = nullptr; o.n_live = 0;
     return o;
 }
 
@@ -1541,7 +1548,7 @@ int launch_kmpc_plan_gen(f1p_ctx* ctx, const double* d_x0, const double* d_ref, 
     // the raceline / track plans follow f1p_kmpc_set_collision; a list of batch indices is f1p_stmpc_plan_batch's kinematic branch and
     // follows f1p_stmpc_set_collision, with its own count
     const bool collide = d_ids ? ctx->stmpc_collision : ctx->kmpc_collision;
-    const bool discs = !d_ids && ctx->kmpc_obs_cur;                   // f1p_kmpc_set_obstacles: the raceline / track plans only
+    const bool discs = d_ids ? ctx->stmpc_obs_cur != nullptr : ctx->kmpc_obs_cur != nullptr;   // f1p_kmpc_set_obstacles / f1p_stmpc_set_obstacles, likewise
     if (discs) lds += 8 + (sizeof(double) + sizeof(float)) * 5 * F1P_KMPC_MAX_OBS + sizeof(int) * 4;
     lds = (lds + 15) & ~(size_t)15;
     if (lds > (size_t)ctx->prop.sharedMemPerBlock) return set_error(ctx, F1P_EINVAL, "horizon / n_rollouts need more LDS than a workgroup has: use fewer rollouts per plan");
@@ -1559,7 +1566,8 @@ int launch_kmpc_plan_gen(f1p_ctx* ctx, const double* d_x0, const double* d_ref, 
     const KmpcIdxArgs ia{d_ids, wstride, ego_off};
     if (discs) {
         if (ga.G != 1) return set_error(ctx, F1P_ESTATE, "kmpc obstacle test: one workgroup per ego only (f1p_kmpc_set_groups(0))");
-        return launch(k_kmpc_plan_gen_obs, "k_kmpc_plan_gen_obs launch", kmpc_obs_dev(ctx, cfg, true));
+        return d_ids ? launch(k_kmpc_plan_gen_idx_obs, "k_kmpc_plan_gen_idx_obs launch", ia, kmpc_obs_dev(ctx, cfg, true, true))
+                     : launch(k_kmpc_plan_gen_obs, "k_kmpc_plan_gen_obs launch", kmpc_obs_dev(ctx, cfg, true));
     }
     if (collide) {
         if (ga.G != 1) return set_error(ctx, F1P_ESTATE, "kmpc collision test: one workgroup per ego only (f1p_kmpc_set_groups(0))");

@@ -302,6 +302,69 @@ __device__ __forceinline__ void stmpc_rollout_f32(const SrcGenT<true>& ce, const
     }
 }
 
+// the generating rollout with the moving discs of f1p_stmpc_set_obstacles (k_stmpc_filter_gen_obs): every tested point is
+// compared with every live slot of the ego's LDS table at the point's own time, and looked up in the clearance map as well while the
+// occupancy test is on (of.grid); FREE needs both proofs at every point.  cf.n_sub / cf.inv_nsub are set with or without a grid.  Without
+// a live slot and without a grid nothing is tested: the plain filter, step by step.
+template <bool POLY, int NR, int QM>
+__device__ __forceinline__ void stmpc_rollout_f32(const SrcGenT<true>& ce, const float* sref8, const DynF32& k, int T, int R, const int (&rr)[NR],
+                                                          float delta0, float v0, float yr0, float beta0, float (&cost_out)[NR], bool (&trusted)[NR],
+                                                          const KmpcColF& cf, const KmpcObsF& of, bool (&unsure)[NR]) {
+#pragma clang fp contract(fast)
+    (void)R;
+    float x[NR], y[NR], delta[NR], v[NR], yaw[NR], yr[NR], beta[NR], cost[NR], pdv[NR], pa[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        x[i] = 0.f; y[i] = 0.f; delta[i] = delta0; v[i] = v0; yaw[i] = 0.f; yr[i] = yr0; beta[i] = beta0; cost[i] = 0.f; pdv[i] = 0.f; pa[i] = 0.f;
+        trusted[i] = true; unsure[i] = false;
+    }
+    const bool test = of.grid | (of.n_live > 0);
+    const float4* sr = reinterpret_cast<const float4*>(sref8);
+    for (int te = 0; te < T; te += 2) {
+        float c_dv[NR][2], c_a[NR][2];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) ce.get2(te, T, rr[i], c_dv[i][0], c_a[i][0], c_dv[i][1], c_a[i][1]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int t = te + h;
+            if (t < T) {
+                const float4 r0 = sr[2 * t], r1 = sr[2 * t + 1];
+#pragma unroll
+                for (int i = 0; i < NR; ++i) {
+                    float dv = __builtin_amdgcn_fmed3f(c_dv[i][h], -k.max_steer_v, k.max_steer_v);
+                    const float a = __builtin_amdgcn_fmed3f(c_a[i][h], -k.max_accel, k.max_accel);
+                    const float px = x[i], py = y[i];
+                    F1P_ST_F32_STEP(i)
+                    if (test) {
+                        for (int j = 1; j <= cf.n_sub; ++j) {
+                            const bool end = j == cf.n_sub;
+                            const float f = end ? 1.0f : (float)j * cf.inv_nsub;
+                            const float qx = end ? x[i] : px + (x[i] - px) * f, qy = end ? y[i] : py + (y[i] - py) * f;
+                            if (of.grid) unsure[i] |= cf.template unsure<false>(qx, qy);
+                            const float tau = ((float)t + f) * of.dt;
+                            for (int m = 0; m < of.n_live; ++m) {
+                                const float* o = of.live + 5 * m;
+                                const float cx = o[0] + o[2] * tau, cy = o[1] + o[3] * tau;
+                                const float dx = qx - cx, dy = qy - cy, d2 = dx * dx + dy * dy;
+                                unsure[i] |= !(d2 > o[4]);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+    const float4 r0 = sr[2 * T], r1 = sr[2 * T + 1];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const float sv_[7] = {x[i], y[i], delta[i], v[i], yaw[i], yr[i], beta[i]}, rf_[7] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z};
+        float qs = 0.f;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) if (QM & (1 << j)) { const float er = sv_[j] - rf_[j]; qs += k.qf[j] * er * er; }
+        cost_out[i] = cost[i] + qs;
+    }
+}
+
 // ---- K-A: f32 filter, one workgroup per ego; no fp64 rollout code in this kernel (registers for 8 waves per SIMD) ----------------
 // nlist[e] = listed rollouts (<= 64) or -1 (this ego is decided by the all-fp64 loop in k_stmpc_decide); the listed rollouts go to
 // rl[e][slot] and, as (e * 64 + slot, r), onto the global queue that k_stmpc_refine packs into full waves across egos.
@@ -339,6 +402,8 @@ __device__ __forceinline__ void wave_lds_sync() {
 // map and lists FREE and UNSURE rollouts, the refinement marks a blocked item (cost +inf, listed index F1P_K4_NONE), the decision skips
 // those.  Filter, refinement and decision with the test exist for generated controls only: f1p_stmpc_shoot_* run the plain-fp64 kernel
 // while the test is on.  The instantiations are the ones named below the kernels -- nothing that is not launched.
+// Col can also be StObs (StObsRef in the refinement), the moving discs of f1p_stmpc_set_obstacles with the grid or without:
+// a KmpcCol too, so the same statements serve it; has_obs marks what the discs add, col_seg(col, t, dt, ...) picks the segment rule.
 using StCtlStream = const float* __restrict__;
 template <typename Ctl> constexpr bool st_gen = std::is_same_v<Ctl, StCtlGen>;
 // ego e's source: as a value, and as the device functions take it
@@ -346,6 +411,57 @@ template <typename Ctl> using st_ego_t = std::conditional_t<st_gen<Ctl>, StGenSr
 template <typename Ctl> using st_src_t = std::conditional_t<st_gen<Ctl>, const StGenSrc&, const float* __restrict__>;
 // the refinement kernels' form of the test: they also rewrite the listed index of a blocked item
 struct StColRef : KmpcCol { int32_t* rl; };
+
+// The moving discs of f1p_stmpc_set_obstacles: KmpcObs with what the dynamic model's kernels need beside it.  The drop rule of
+// obs_compact takes its operands in fp64 from here (the filter kernel has the configuration in f32 only).  The ego's obstacle row is
+// ids ? ids[e] : e -- the array is in the CALLER's ego order, a plan_batch branch is a compacted list.  The kernels that own an ego per workgroup
+// (shoot, filter, decide) compact the live slots into LDS (st_obs_setup / st_obs_bind); the filter also copies its table to tab / ntab, where
+// the refinement -- whose items come from many egos -- reads it with wave-uniform addresses.
+// nan_all: the ego has a live slot (before the drop).  Against a live slot a tested point with a NaN coordinate is blocked wherever the slot
+// is (!(NaN > r r)), and the dynamic model makes NaN positions out of finite states (yr / v and beta / v at v = 0), so a dropped slot must
+// still block those: seg_t tests the point itself.  An infinite coordinate is free against every tame slot, dropped or not.
+#define F1P_ST_OBS_LDS64 (sizeof(double) * 5 * F1P_KMPC_MAX_OBS + sizeof(int) * 4)                    // fp64 rows, the two counts
+#define F1P_ST_OBS_LDS32 (8 + F1P_ST_OBS_LDS64 + sizeof(float) * 5 * F1P_KMPC_MAX_OBS)                 // (+ alignment) + the filter's f32 rows
+struct StObs : KmpcObs {
+    double dt, max_speed, min_speed, pos_err;
+    const int32_t* ids;
+    double* tab;                      // [E][F1P_KMPC_MAX_OBS][5]
+    int32_t* ntab;                    // [E]: n_live | nan_all << 8
+    int nan_all;
+    __device__ __forceinline__ bool seg_t(int t, double dt_, double px, double py, double qx, double qy) const {
+        bool hit = false;
+        for (int j = 1; j <= n_sub; ++j) {
+            const double f = (double)j / (double)n_sub;
+            const bool end = j == n_sub;
+            const double x = end ? qx : px + (qx - px) * f, y = end ? qy : py + (qy - py) * f;
+            if (g.bits) hit |= occupied(x, y);
+            hit |= disc(x, y, ((double)t + f) * dt_);
+            hit |= (nan_all != 0) & !((x == x) & (y == y));
+        }
+        return hit;
+    }
+};
+struct StObsRef : StObs { int32_t* rl; };
+__device__ __forceinline__ bool col_seg(const StObs& c, int t, double dt, double px, double py, double qx, double qy) { return c.seg_t(t, dt, px, py, qx, qy); }
+// the workgroup's first wave (all its lanes): ego e's live slots -> live64 (and live32), the counts -> n2[0] (kept), n2[1] (any live slot)
+__device__ __forceinline__ void st_obs_setup(const StObs& ob, int e, double sx, double sy, double sv, double syaw, int T, double* live64, float* live32, int* n2) {
+    const int row = ob.ids ? ob.ids[e] : e;
+    const bool live = (int)threadIdx.x < ob.M && ob.obs[((size_t)row * ob.M + threadIdx.x) * 5 + 4] >= 0.0;
+    const unsigned long long any = __ballot(live);
+    if (threadIdx.x == 0) n2[1] = any != 0ull;
+    obs_compact(ob, row, sx, sy, sv, syaw, T, ob.dt, ob.max_speed, ob.min_speed, false, 1.0, 0.0, live64, live32, n2, ob.pos_err);
+}
+// behind the barrier
+__device__ __forceinline__ void st_obs_bind(StObs& ob, const double* live64, const int* n2) {
+    ob.live = live64; ob.n_live = __builtin_amdgcn_readfirstlane(n2[0]); ob.nan_all = __builtin_amdgcn_readfirstlane(n2[1]);
+}
+// the refinement's: ego e's table as the filter left it
+template <typename O> __device__ __forceinline__ O st_obs_of_ego(const O& ob, int e) {
+    O o = ob;
+    const int w = ob.ntab[e];
+    o.live = ob.tab + (size_t)e * 5 * F1P_KMPC_MAX_OBS; o.n_live = w & 0xff; o.nan_all = w >> 8;
+    return o;
+}
 
 #ifdef F1P_ST_PHASES
 #define F1P_STPH() do { ph[nph++] = clock64(); } while (0)
@@ -379,7 +495,7 @@ __device__ __forceinline__ void stmpc_rollouts(st_src_t<Ctl> ce, const double* s
             [[maybe_unused]] const double px = s.x, py = s.y;
             dyn_step<FAST>(s, a, dv, cfg, k);
             if constexpr (has_col<Col...>) {
-                if (col_of(col...).seg(px, py, s.x, s.y)) { blocked = true; break; }   // the points of step t -> t + 1; a blocked rollout stops at its first occupied point
+                if (col_seg(col_of(col...), t, cfg.dt, px, py, s.x, s.y)) { blocked = true; break; }   // the points of step t -> t + 1; a blocked rollout stops at its first occupied point
             }
             pdv = dv; pa = a;
         }
@@ -423,6 +539,16 @@ __global__ __launch_bounds__(256) void k_stmpc_shoot_t(const double* __restrict_
     st_ego_t<Ctl> ce;
     if constexpr (st_gen<Ctl>) ce = StGenSrc{ctl.src(e, ctl.warm_row(e)), 0.0f}; else ce = ctl + (size_t)e * T * 2 * R;
     double bc = __builtin_huge_val(); int bi = 0x7fffffff;
+    if constexpr (has_obs<Col...>) {                                  // the ego's live discs -> LDS behind the reduction's words
+        double* olive = reinterpret_cast<double*>(red_i + 4);
+        int* on2 = reinterpret_cast<int*>(olive + 5 * F1P_KMPC_MAX_OBS);
+        if (tid < 64) st_obs_setup(col_of(col...), e, s0.x, s0.y, s0.v, s0.yaw, T, olive, nullptr, on2);
+        __syncthreads();
+        auto ob = col_of(col...);
+        st_obs_bind(ob, olive, on2);
+        if (fabs(cfg.max_steer) <= 1.0e4) stmpc_rollouts<true, Ctl>(ce, sref, cfg, k, s0, tid, bc, bi, ob);
+        else stmpc_rollouts<false, Ctl>(ce, sref, cfg, k, s0, tid, bc, bi, ob);
+    } else
     if (fabs(cfg.max_steer) <= 1.0e4) stmpc_rollouts<true, Ctl>(ce, sref, cfg, k, s0, tid, bc, bi, col...);     // workgroup-uniform
     else stmpc_rollouts<false, Ctl>(ce, sref, cfg, k, s0, tid, bc, bi, col...);
     block_argmin(bc, bi, red_d, red_i);
@@ -496,7 +622,7 @@ __device__ __forceinline__ double stmpc_one_rollout(st_src_t<Ctl> ce, const doub
         [[maybe_unused]] const double px = s.x, py = s.y;
         dyn_step<FAST>(s, a, dv, cfg, k);
         if constexpr (has_col<Col...>) {
-            if (col_of(col...).seg(px, py, s.x, s.y)) { blocked = true; return __builtin_huge_val(); }
+            if (col_seg(col_of(col...), t, cfg.dt, px, py, s.x, s.y)) { blocked = true; return __builtin_huge_val(); }
         }
         pdv = dv; pa = a;
     }
@@ -524,9 +650,16 @@ __global__ __launch_bounds__(256) void k_stmpc_filter_t(const double* __restrict
     if (e >= E) return;
     const double sx = x0[7 * e], sy = x0[7 * e + 1], sdelta = x0[7 * e + 2], sv = x0[7 * e + 3], syaw = x0[7 * e + 4], syr = x0[7 * e + 5], sbeta = x0[7 * e + 6];
     constexpr bool COL = has_col<Col...>;
+    constexpr bool OBS = has_obs<Col...>;                            // moving discs, with the grid (a bitmap) or without (null)
     [[maybe_unused]] double bxd = 0.0, byd = 0.0;
     bool in_range;                                                   // workgroup-uniform
-    if constexpr (COL) {
+    if constexpr (OBS) {
+        // without a grid the discs need no cell: their FREE threshold carries the filter's position bound itself (obs_compact)
+        const KmpcCol& c_ = col_of(col...);
+        if (c_.g.bits) { bxd = (sx - c_.g.ox) * c_.g.inv_res; byd = (sy - c_.g.oy) * c_.g.inv_res; }
+        in_range = fabs(syaw) <= 1.0e4 && fabs(max_steer_d) <= 1.0e4 && fabs(sbeta) <= 100.0 && fabs(sdelta) <= 100.0 &&
+                   fabs(bxd) < 1.0e6 && fabs(byd) < 1.0e6;
+    } else if constexpr (COL) {
         // the ego's cell (fp64) anchors the filter's cell coordinates; an ego without one is decided in fp64
         const KmpcCol& c_ = col_of(col...);
         bxd = (sx - c_.g.ox) * c_.g.inv_res; byd = (sy - c_.g.oy) * c_.g.inv_res;
@@ -548,6 +681,16 @@ __global__ __launch_bounds__(256) void k_stmpc_filter_t(const double* __restrict
         float* ws_ = reinterpret_cast<float*>(cnt + 2); const float* wg_ = ctl.warm_row(e);
         for (int q = tid; q < 2 * T; q += blockDim.x) ws_[q] = wg_[q];
     }
+    // the ego's live discs -> LDS behind the warm start: fp64 rows (for the refinement's table), the filter's f32 rows, the counts
+    [[maybe_unused]] double* olive = nullptr;
+    [[maybe_unused]] float* olive32 = nullptr;
+    [[maybe_unused]] int* on2 = nullptr;
+    if constexpr (OBS) {
+        olive = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(reinterpret_cast<float*>(cnt + 2) + 2 * T) + 7) & ~(uintptr_t)7);
+        on2 = reinterpret_cast<int*>(olive + 5 * F1P_KMPC_MAX_OBS);
+        olive32 = reinterpret_cast<float*>(on2 + 4);
+        if (tid < 64) st_obs_setup(col_of(col...), e, sx, sy, sv, syaw, T, olive, olive32, on2);
+    }
     if (__syncthreads_or(bad_ref | ((QM != 0x7f && !(fabs(syr) < __builtin_huge_val())) ? 1 : 0))) { if (tid == 0) nlist[e] = -1; return; }
     std::conditional_t<st_gen<Ctl>, SrcGenT<true>, const float*> ce;
     if constexpr (st_gen<Ctl>) ce = ctl.src(e, reinterpret_cast<const float*>(cnt + 2)); else ce = ctl + (size_t)e * T * 2 * R;
@@ -565,6 +708,14 @@ __global__ __launch_bounds__(256) void k_stmpc_filter_t(const double* __restrict
     sincos_core(syaw, &s0d, &c0d);
     kk.c0 = (float)c0d; kk.s0 = (float)s0d;
     [[maybe_unused]] KmpcColF cf;                                    // (the filter's positions are relative to the ego with the map's axes: unsure<false>)
+    [[maybe_unused]] KmpcObsF of;
+    if constexpr (OBS) {
+        const auto& o_ = col_of(col...);
+        of.live = olive32; of.n_live = __builtin_amdgcn_readfirstlane(on2[0]); of.grid = o_.g.bits != nullptr; of.dt = kf.dt;
+        // the refinement's copy of the table (it cannot compact per workgroup: its items come from many egos)
+        if (tid < 5 * of.n_live) o_.tab[(size_t)e * 5 * F1P_KMPC_MAX_OBS + tid] = olive[tid];
+        if (tid == 0) o_.ntab[e] = on2[0] | (on2[1] << 8);
+    }
     if constexpr (COL) {
         const KmpcCol& c_ = col_of(col...);
         const double ibx = __builtin_floor(bxd), iby = __builtin_floor(byd);
@@ -584,7 +735,10 @@ __global__ __launch_bounds__(256) void k_stmpc_filter_t(const double* __restrict
 #pragma unroll
         for (int i = 0; i < NR; ++i) rr[i] = rb + i * (int)blockDim.x < R ? rb + i * (int)blockDim.x : rb;   // past the end: a shadow of the first, not stored
         [[maybe_unused]] bool unsure[NR];                            // a tested point near an occupied cell, off the image or NaN: not FREE
-        if constexpr (COL) {
+        if constexpr (OBS) {
+            if (poly) stmpc_rollout_f32<true, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted, cf, of, unsure);
+            else stmpc_rollout_f32<false, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted, cf, of, unsure);
+        } else if constexpr (COL) {
 #ifdef F1P_ST_DBG_POS    // variant build: dbg_cost32 is [1 + 2 T][E][R] -- the costs, then the f32 (x, y) after every step (tools/stmpc_pos_error.py)
 #define F1P_ST_POS_ARGS , dbg_cost32 ? dbg_cost32 + ((size_t)E + e) * R : nullptr, (size_t)E * R
 #else
@@ -658,6 +812,8 @@ __global__ __launch_bounds__(64) void k_stmpc_refine_t(const double* __restrict_
         st_ego_t<Ctl> ce;
         if constexpr (st_gen<Ctl>) ce = StGenSrc{ctl.src(e, ctl.warm_row(e)), 0.0f}; else ce = ctl + (size_t)e * T * 2 * R;
         bool blocked;
+        if constexpr (has_obs<Col...>) rc[it.es] = stmpc_one_rollout<true, Ctl>(ce, ref + (size_t)e * 7 * (T + 1), cfg, k, s0, it.r, blocked, st_obs_of_ego(col_of(col...), e));
+        else
         rc[it.es] = stmpc_one_rollout<true, Ctl>(ce, ref + (size_t)e * 7 * (T + 1), cfg, k, s0, it.r, blocked, col...);
         if constexpr (has_col<Col...>) { if (blocked) col_of(col...).rl[it.es] = F1P_K4_NONE; }   // (its cost is +inf: the pair loses to every unblocked item)
     }
@@ -794,6 +950,9 @@ __global__ __launch_bounds__(256) void k_stmpc_refine_tp_t(const double* __restr
         [[maybe_unused]] bool blocked = false;
         if constexpr (has_col<Col...>) {
             bool hit = false;
+            if constexpr (has_obs<Col...>) {                              // ego e's table, at wave-uniform addresses; lane t has the step's own t
+                if (act) { const StXY p = o6[t], q = o6[t + 1]; hit = col_seg(st_obs_of_ego(col_of(col...), e), t, cfg.dt, p.x, p.y, q.x, q.y); }
+            } else
             if (act) { const StXY p = o6[t], q = o6[t + 1]; hit = col_of(col...).seg(p.x, p.y, q.x, q.y); }
             blocked = __ballot(hit) != 0ull;
         }
@@ -867,6 +1026,13 @@ __global__ __launch_bounds__(256) void k_stmpc_decide_t(const double* __restrict
     st_ego_t<Ctl> ce;
     if constexpr (st_gen<Ctl>) ce = StGenSrc{ctl.src(e, ctl.warm_row(e)), 0.0f}; else ce = ctl + (size_t)e * T * 2 * R;
     double bc = __builtin_huge_val(); int bi = 0x7fffffff;
+    [[maybe_unused]] double* olive = nullptr;
+    [[maybe_unused]] int* on2 = nullptr;
+    if constexpr (has_obs<Col...>) {                                  // the ego's live discs -> LDS (the all-fp64 loop's), behind the reduction's words
+        olive = reinterpret_cast<double*>(red_i + 4);
+        on2 = reinterpret_cast<int*>(olive + 5 * F1P_KMPC_MAX_OBS);
+        if (n < 0 && tid < 64) st_obs_setup(col_of(col...), e, s0.x, s0.y, s0.v, s0.yaw, T, olive, nullptr, on2);
+    }
     if constexpr (has_col<Col...>) {
         if (n >= 0) {                                                 // a blocked item is (+inf, F1P_K4_NONE): it loses to every unblocked one
             if (tid < n) {
@@ -876,13 +1042,22 @@ __global__ __launch_bounds__(256) void k_stmpc_decide_t(const double* __restrict
             block_argmin(bc, bi, red_d, red_i);
             // every listed rollout blocked: the list holds the FREE minimum, which the position bound proves unblocked, so this is not expected --
             // the ego is decided by the all-fp64 loop rather than declared blocked on the filter's word (workgroup-uniform)
-            if (bi == F1P_K4_NONE) { n = -1; bc = __builtin_huge_val(); __syncthreads(); }
+            if (bi == F1P_K4_NONE) {
+                n = -1; bc = __builtin_huge_val(); __syncthreads();
+                if constexpr (has_obs<Col...>) { if (tid < 64) st_obs_setup(col_of(col...), e, s0.x, s0.y, s0.v, s0.yaw, T, olive, nullptr, on2); }
+            }
         }
     }
     if (n < 0) {                                                      // workgroup-uniform
         for (int q = tid; q < 7 * (T + 1); q += blockDim.x) sref[q] = ref[(size_t)e * 7 * (T + 1) + q];
         __syncthreads();
         const DynConst k = dyn_const(cfg);
+        if constexpr (has_obs<Col...>) {                              // (the barrier above is behind st_obs_setup)
+            auto ob = col_of(col...);
+            st_obs_bind(ob, olive, on2);
+            if (fabs(cfg.max_steer) <= 1.0e4) stmpc_rollouts<true, Ctl>(ce, sref, cfg, k, s0, tid, bc, bi, ob);
+            else stmpc_rollouts<false, Ctl>(ce, sref, cfg, k, s0, tid, bc, bi, ob);
+        } else
         if (fabs(cfg.max_steer) <= 1.0e4) stmpc_rollouts<true, Ctl>(ce, sref, cfg, k, s0, tid, bc, bi, col...);
         else stmpc_rollouts<false, Ctl>(ce, sref, cfg, k, s0, tid, bc, bi, col...);
         if constexpr (has_col<Col...>) block_argmin(bc, bi, red_d, red_i);
@@ -960,6 +1135,13 @@ template <int QM> [[maybe_unused]] static constexpr auto k_stmpc_filter_gen_col 
 [[maybe_unused]] static constexpr auto k_stmpc_decide = k_stmpc_decide_t<StCtlStream>;
 [[maybe_unused]] static constexpr auto k_stmpc_decide_gen = k_stmpc_decide_t<StCtlGen>;
 [[maybe_unused]] static constexpr auto k_stmpc_decide_gen_col = k_stmpc_decide_t<StCtlGen, KmpcCol>;
+// with the moving discs of f1p_stmpc_set_obstacles (_obs), alone or with the occupancy test (the bitmap of the KmpcCol part: null = no grid)
+[[maybe_unused]] static constexpr auto k_stmpc_shoot_obs = k_stmpc_shoot_t<StCtlStream, StObs>;
+[[maybe_unused]] static constexpr auto k_stmpc_shoot_gen_obs = k_stmpc_shoot_t<StCtlGen, StObs>;
+template <int QM> [[maybe_unused]] static constexpr auto k_stmpc_filter_gen_obs = k_stmpc_filter_t<QM, StCtlGen, StObs>;
+[[maybe_unused]] static constexpr auto k_stmpc_refine_gen_obs = k_stmpc_refine_t<StCtlGen, StObsRef>;
+[[maybe_unused]] static constexpr auto k_stmpc_refine_tp_gen_obs = k_stmpc_refine_tp_t<StCtlGen, StObsRef>;
+[[maybe_unused]] static constexpr auto k_stmpc_decide_gen_obs = k_stmpc_decide_t<StCtlGen, StObs>;
 
 // materialise the generator's controls as the [E][T][2][R] f32 buffer of the streamed entry points (tests: generated == streamed)
 __global__ __launch_bounds__(256) void k_stmpc_gen_controls(float* __restrict__ controls, int E, int T, int R, StCtlGen ctl) {
@@ -1048,12 +1230,15 @@ static DynF32 make_dyn_f32(const f1p_stmpc_cfg* cfg) {
 
 // the mixed schedule's scratch for E egos: queue counter (256 B) | nlist [E] | rl [E][64] | items [E][64] | rc [E][64]; the queue counter is
 // zeroed when the scratch is new or a plan failed between its kernels, and st_q_dirty stays set until the caller's last launch succeeded
-struct StScratch { unsigned int* qcount; int32_t *nlist, *rl; StItem* items; double* rc; };
+// | the discs' tables otab [E][16][5] fp64 | their counts ontab [E] (the filter writes them for the refinement while obstacles are set)
+struct StScratch { unsigned int* qcount; int32_t *nlist, *rl; StItem* items; double* rc; double* otab; int32_t* ontab; };
 static int st_scratch(f1p_ctx* ctx, int E, StScratch& sc) {
     const size_t n_off = 256, rl_off = (n_off + 4 * (size_t)E + 255) & ~(size_t)255;
     const size_t it_off = (rl_off + 4 * (size_t)E * F1P_ST_MAX_REFINE + 255) & ~(size_t)255;
     const size_t rc_off = (it_off + sizeof(StItem) * (size_t)E * F1P_ST_MAX_REFINE + 255) & ~(size_t)255;
-    const size_t need = rc_off + 8 * (size_t)E * F1P_ST_MAX_REFINE;
+    const size_t ot_off = (rc_off + 8 * (size_t)E * F1P_ST_MAX_REFINE + 255) & ~(size_t)255;
+    const size_t on_off = (ot_off + sizeof(double) * 5 * F1P_KMPC_MAX_OBS * (size_t)E + 255) & ~(size_t)255;
+    const size_t need = on_off + 4 * (size_t)E;
     if (need > ctx->st_scratch_bytes) {
         F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (ctx->d_st_scratch) (void)hipFree(ctx->d_st_scratch);
@@ -1067,6 +1252,8 @@ static int st_scratch(f1p_ctx* ctx, int E, StScratch& sc) {
     sc.rl = reinterpret_cast<int32_t*>(ctx->d_st_scratch + rl_off);
     sc.items = reinterpret_cast<StItem*>(ctx->d_st_scratch + it_off);
     sc.rc = reinterpret_cast<double*>(ctx->d_st_scratch + rc_off);
+    sc.otab = reinterpret_cast<double*>(ctx->d_st_scratch + ot_off);
+    sc.ontab = reinterpret_cast<int32_t*>(ctx->d_st_scratch + on_off);
     if (ctx->st_q_dirty) F1P_HIP(ctx, hipMemsetAsync(sc.qcount, 0, 256, ctx->stream));
     ctx->st_q_dirty = true;
     return F1P_OK;
@@ -1089,6 +1276,15 @@ static double st_pos_err_bound(const f1p_stmpc_cfg* cfg) {
 }
 #define F1P_ST_POS_HEADROOM 5.0        // the filter gets the clearance map only while headroom x bound < one cell (DESIGN.md 5h's factor)
 
+// the refinement kernels' form of the test, and the scratch the obstacle test keeps its tables in
+static StColRef st_ref(const KmpcCol& c, int32_t* rl) { return StColRef{c, rl}; }
+static StObsRef st_ref(const StObs& c, int32_t* rl) { return StObsRef{c, rl}; }
+static void st_bind_scratch(KmpcCol&, const StScratch&) {}
+static void st_bind_scratch(StObs& o, const StScratch& sc) { o.tab = sc.otab; o.ntab = sc.ontab; }
+template <typename... Col> static const char* st_what(const char* plain, const char* col, const char* obs) {
+    if constexpr (has_obs<Col...>) return obs; else if constexpr (sizeof...(Col) > 0) return col; else return plain;
+}
+
 // the mixed schedule, filter -> refinement -> decision, over the control source and the optional occupancy test
 template <typename Ctl, typename... Col>
 static int stmpc_mixed(f1p_ctx* ctx, const double* d_x0, const double* d_ref, Ctl ctl, int E, const f1p_stmpc_cfg* cfg, const DynF32& kf, size_t lds_a, size_t lds_c,
@@ -1096,26 +1292,27 @@ static int stmpc_mixed(f1p_ctx* ctx, const double* d_x0, const double* d_ref, Ct
     constexpr bool COL = sizeof...(Col) > 0;                         // (the error strings name the kernels as they always did)
     StScratch sc;
     if (const int rs = st_scratch(ctx, E, sc)) return rs;
+    (st_bind_scratch(col, sc), ...);
     int qm = 0;                                                      // rows that carry weight in the stage or the terminal cost
     for (int j = 0; j < 7; ++j) if (cfg->q[j] != 0.0 || cfg->qf[j] != 0.0) qm |= 1 << j;
     // 0x1b: the reference's weights (x, y, v, yaw): the delta / yr / beta terms are not evaluated
     hipLaunchKernelGGL(qm == 0x1b ? (k_stmpc_filter_t<0x1b, Ctl, Col...>) : (k_stmpc_filter_t<0x7f, Ctl, Col...>), dim3(E), dim3(256), (lds_a + 15) & ~(size_t)15,
                        ctx->stream, d_x0, d_ref, ctl, E, cfg->horizon, cfg->n_rollouts, cfg->max_steer, kf, col..., sc.qcount, sc.items, sc.nlist, sc.rl, ctx->d_dbg_st_cost32);
-    int rcode = check_hip(ctx, hipGetLastError(), COL ? "k_stmpc_filter_gen_col launch" : "k_stmpc_filter launch");
+    int rcode = check_hip(ctx, hipGetLastError(), st_what<Col...>("k_stmpc_filter launch", "k_stmpc_filter_gen_col launch", "k_stmpc_filter_gen_obs launch"));
     if (rcode != F1P_OK) return rcode;
     if (cfg->horizon <= 63 && 4 * F1P_ST_TP_LDS_PER_WAVE <= (size_t)ctx->prop.sharedMemPerBlock) {
         const int nb = E * F1P_ST_MAX_REFINE / 4 < 2 * ctx->prop.multiProcessorCount ? (E * F1P_ST_MAX_REFINE + 3) / 4 : 2 * ctx->prop.multiProcessorCount;
-        hipLaunchKernelGGL((k_stmpc_refine_tp_t<Ctl, decltype(StColRef{col, sc.rl})...>), dim3(nb), dim3(256), 4 * F1P_ST_TP_LDS_PER_WAVE, ctx->stream, d_x0, d_ref, ctl,
-                           *cfg, sc.qcount, sc.items, StColRef{col, sc.rl}..., sc.rc, COL ? (float*)nullptr : ctx->d_dbg_st_cost32);
+        hipLaunchKernelGGL((k_stmpc_refine_tp_t<Ctl, decltype(st_ref(col, sc.rl))...>), dim3(nb), dim3(256), 4 * F1P_ST_TP_LDS_PER_WAVE, ctx->stream, d_x0, d_ref, ctl,
+                           *cfg, sc.qcount, sc.items, st_ref(col, sc.rl)..., sc.rc, COL ? (float*)nullptr : ctx->d_dbg_st_cost32);
     } else {
-        hipLaunchKernelGGL((k_stmpc_refine_t<Ctl, decltype(StColRef{col, sc.rl})...>), dim3(E), dim3(64), 0, ctx->stream, d_x0, d_ref, ctl, *cfg, sc.qcount, sc.items,
-                           StColRef{col, sc.rl}..., sc.rc);
+        hipLaunchKernelGGL((k_stmpc_refine_t<Ctl, decltype(st_ref(col, sc.rl))...>), dim3(E), dim3(64), 0, ctx->stream, d_x0, d_ref, ctl, *cfg, sc.qcount, sc.items,
+                           st_ref(col, sc.rl)..., sc.rc);
     }
-    rcode = check_hip(ctx, hipGetLastError(), COL ? "k_stmpc_refine_gen_col launch" : "k_stmpc_refine launch");
+    rcode = check_hip(ctx, hipGetLastError(), st_what<Col...>("k_stmpc_refine launch", "k_stmpc_refine_gen_col launch", "k_stmpc_refine_gen_obs launch"));
     if (rcode != F1P_OK) return rcode;
     hipLaunchKernelGGL((k_stmpc_decide_t<Ctl, Col...>), dim3(E), dim3(256), (lds_c + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, ctl, E, *cfg, sc.qcount,
                        sc.nlist, sc.rl, sc.rc, col..., d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ctx->d_dbg_st_nref);
-    rcode = check_hip(ctx, hipGetLastError(), COL ? "k_stmpc_decide_gen_col launch" : "k_stmpc_decide launch");
+    rcode = check_hip(ctx, hipGetLastError(), st_what<Col...>("k_stmpc_decide launch", "k_stmpc_decide_gen_col launch", "k_stmpc_decide_gen_obs launch"));
     if (rcode == F1P_OK) ctx->st_q_dirty = false;
     return rcode;
 }
@@ -1125,7 +1322,8 @@ static int stmpc_shoot_any(f1p_ctx* ctx, const double* d_x0, const double* d_ref
                            double* d_steer, double* d_speed, int32_t* d_best_idx, double* d_best_cost, double* d_best_seq) {
     if (E <= 0) return F1P_OK;
     const size_t T1 = (size_t)cfg->horizon + 1;
-    const size_t lds = sizeof(double) * (7 * T1 + 4) + sizeof(int) * 4;   // the plain-fp64 kernel's, and the decision's
+    const bool discs = ctx->stmpc_obs_cur != nullptr;                      // f1p_stmpc_set_obstacles (the caller checked E: stmpc_collision_check)
+    const size_t lds = sizeof(double) * (7 * T1 + 4) + sizeof(int) * 4 + (discs ? F1P_ST_OBS_LDS64 : 0);   // the plain-fp64 kernel's, and the decision's
     // the plain-fp64 evaluation, over the control source and the optional occupancy test
     auto shoot = [&](const char* what, auto... col) {
         if (gen) hipLaunchKernelGGL((k_stmpc_shoot_t<StCtlGen, decltype(col)...>), dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, *gen, E, *cfg, col...,
@@ -1134,6 +1332,30 @@ static int stmpc_shoot_any(f1p_ctx* ctx, const double* d_x0, const double* d_ref
                                 d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
         return check_hip(ctx, hipGetLastError(), what);
     };
+    if (discs) {
+        // the moving discs, with the occupancy test (a bitmap) or without (null).  Streamed controls: plain fp64 in every mode, as with the grid.
+        // Generated controls in the mixed mode: filter -> refinement -> decision; with the grid under the occupancy test's own guard (the
+        // position bound below one cell and a clearance map), without one no cell guard applies -- the discs' FREE threshold carries the bound.
+        StObs ob;
+        ob.g = ctx->stmpc_collision ? grid_dev(ctx) : GridDev{nullptr, 0, 0, 0, 0.0, 0.0, 0.0};
+        ob.clear = nullptr; ob.n_sub = ctx->stmpc_col_nsub; ob.force64 = 1;
+        ob.obs = ctx->stmpc_obs_cur; ob.M = ctx->stmpc_obs_M; ob.live = nullptr; ob.n_live = 0;
+        ob.dt = cfg->dt; ob.max_speed = cfg->max_speed; ob.min_speed = cfg->min_speed; ob.pos_err = st_pos_err_bound(cfg);
+        ob.ids = gen ? gen->ids : nullptr; ob.tab = nullptr; ob.ntab = nullptr; ob.nan_all = 0;
+        if (lds > (size_t)ctx->prop.sharedMemPerBlock) return set_error(ctx, F1P_EINVAL, "stmpc: the horizon needs more LDS than a workgroup has");
+        if (gen && ctx->stmpc_mixed && !ctx->stmpc_warm_nonfinite) {
+            const DynF32 kf = make_dyn_f32(cfg);
+            const size_t lds_a = sizeof(float) * (8 * T1 + (size_t)cfg->n_rollouts + 4) + sizeof(int) * (F1P_ST_MAX_REFINE + 2) + sizeof(float) * 2 * (size_t)cfg->horizon +
+                                 F1P_ST_OBS_LDS32;
+            if (lds_a <= (size_t)ctx->prop.sharedMemPerBlock && kf.v_trust == kf.v_trust && (size_t)E * F1P_ST_MAX_REFINE < ((size_t)1 << 31) &&
+                (!ctx->stmpc_collision || (F1P_ST_POS_HEADROOM * st_pos_err_bound(cfg) * ctx->inv_res < 1.0 && ensure_clear_map(ctx, F1P_K4_CLEAR_CELLS) == F1P_OK))) {
+                if (ctx->stmpc_collision) ob.clear = ctx->d_bits_clear;
+                ob.force64 = 0;
+                return stmpc_mixed(ctx, d_x0, d_ref, *gen, E, cfg, kf, lds_a, lds, d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq, ob);
+            }
+        }
+        return shoot("k_stmpc_shoot_obs launch", ob);
+    }
     if (ctx->stmpc_collision) {
         // the occupancy test (the caller checked the grid: stmpc_collision_check).  Streamed controls: plain fp64 in every mode, so that
         // gen_controls + shoot == plan bit for bit.  Generated controls in the mixed mode: filter -> refinement -> decision with the test, as

@@ -109,9 +109,10 @@ __device__ __forceinline__ bool col_seg(const KmpcObs& c, int t, double dt, doub
 // heading makes every tested point NaN, which any live slot blocks) every live slot is kept.  live64: (x, y, vx, vy, r r).  live32 (nullable, the f32 filter's table): the centre relative to the ego and the
 // velocity, in the filter's frame (iso: rotated by -yaw0), and the FREE threshold (r + eps)^2 rounded up, eps as DESIGN.md 5j derives it:
 // F1P_K4_POS_ERR_REL x reach for the filter's position + 16 x 2^-24 x (|o_rel|_1 + |v|_1 T dt + r + reach) for the roundings of the
-// obstacle's side.  Returns nothing: *n_out holds the count after the caller's barrier.
+// obstacle's side.  pos_err >= 0 replaces the first term by an absolute bound [m]: the dynamic model's grows with T^2 (k_stmpc.hip
+// st_pos_err_bound).  Returns nothing: *n_out holds the count after the caller's barrier.
 __device__ __forceinline__ void obs_compact(const KmpcObs& ob, int e, double sx, double sy, double sv, double syaw, int T, double dt, double max_speed,
-                                            double min_speed, bool iso, double c0, double s0, double* live64, float* live32, int* n_out) {
+                                            double min_speed, bool iso, double c0, double s0, double* live64, float* live32, int* n_out, double pos_err = -1.0) {
     const int lane = threadIdx.x;
     bool keep = false;
     double x = 0.0, y = 0.0, vx = 0.0, vy = 0.0, r = 0.0;
@@ -136,7 +137,7 @@ __device__ __forceinline__ void obs_compact(const KmpcObs& ob, int e, double sx,
             const double rx = iso ? c0 * dx + s0 * dy : dx, ry = iso ? c0 * dy - s0 * dx : dy;
             const double wx = iso ? c0 * vx + s0 * vy : vx, wy = iso ? c0 * vy - s0 * vx : vy;
             const double S = (fabs(rx) + fabs(ry)) + (fabs(wx) + fabs(wy)) * Tdt + r + reach;
-            const double rr = r + (F1P_K4_POS_ERR_REL * reach + 1.0e-6 * S);       // (1e-6 >= 16 x 2^-24)
+            const double rr = r + ((pos_err >= 0.0 ? pos_err : F1P_K4_POS_ERR_REL * reach) + 1.0e-6 * S);       // (1e-6 >= 16 x 2^-24)
             live32[5 * pos] = (float)rx; live32[5 * pos + 1] = (float)ry; live32[5 * pos + 2] = (float)wx; live32[5 * pos + 3] = (float)wy;
             live32[5 * pos + 4] = (float)(rr * rr * (1.0 + 1.0e-6));               // (the rounding to f32 is inside the factor; NaN / inf: never FREE)
         }
@@ -145,6 +146,7 @@ __device__ __forceinline__ void obs_compact(const KmpcObs& ob, int e, double sx,
 }
 
 // the f32 filter's side: a point is FREE against a slot only when its f32 distance from the f32 centre exceeds r + eps
+// (k_kmpc.hip kmpc_rollout_cost_f32x2_obs, k_stmpc.hip stmpc_rollout_f32 with `of`)
 struct KmpcObsF {
     const float* live;                // LDS [n_live][5] (obs_compact)
     int n_live;

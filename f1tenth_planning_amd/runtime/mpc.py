@@ -21,6 +21,18 @@ def kmpc_set_obstacles_dev(ctx, d_obs, E=None, M=None):
     ctx._kmpc_set_obstacles_dev(d_obs, E, M)
 
 
+def stmpc_set_obstacles(ctx, obs):
+    """kmpc_set_obstacles for the dynamic MPC's shooting solver (f1p_stmpc_set_obstacles), a state of its own: obs [E, M, 5] fp64 rows in the
+    CALLER's ego order; in force for stmpc_plan / stmpc_plan_dev / stmpc_shoot* of E egos until the next set.  None clears."""
+    ctx._stmpc_set_obstacles(obs)
+
+
+def stmpc_set_obstacles_dev(ctx, d_obs, E=None, M=None):
+    """stmpc_set_obstacles on a device buffer [E][M][5] fp64 that the context BORROWS: keep it alive, rewrite it in place between plans.
+    E and M are required with a buffer; d_obs None clears."""
+    ctx._stmpc_set_obstacles_dev(d_obs, E, M)
+
+
 class _Mpc:
     # ---- MPC: the kinematic (kmpc_*, state width 4) and the dynamic (stmpc_*, 7) wrappers share their bodies -----------------------
     def kmpc_ref(self, states, horizon, dt=0.1, dl=0.03):
@@ -194,22 +206,36 @@ class _Mpc:
         blocked rollout cannot win; an ego whose rollouts are all blocked gets best_idx -1, cost +inf, steer 0, speed 0"""
         self._check(self.lib.f1p_kmpc_set_collision(self.h, 1 if on else 0, int(n_sub)))
 
-    def _kmpc_set_obstacles(self, obs):
+    def _set_obstacles(self, name, obs):
+        fn = getattr(self.lib, name)
         if obs is None:
-            self._check(self.lib.f1p_kmpc_set_obstacles(self.h, None, 0, 0))
+            self._check(fn(self.h, None, 0, 0))
             return
         o = _f64(obs)
         if o.ndim != 3 or o.shape[2] != 5:
             raise ValueError("obstacles must be [E, M, 5] = (x, y, vx, vy, r)")
-        self._check(self.lib.f1p_kmpc_set_obstacles(self.h, _ptr(o), o.shape[0], o.shape[1]))
+        self._check(fn(self.h, _ptr(o), o.shape[0], o.shape[1]))
+
+    def _set_obstacles_dev(self, name, d_obs, E, M):
+        if d_obs is not None and (E is None or M is None):
+            raise ValueError("a device array of obstacles needs its E and M")
+        fn = getattr(self.lib, name)
+        if d_obs is None:
+            self._check(fn(self.h, None, 0, 0))
+            return
+        self._check(fn(self.h, _dev(d_obs), int(E), int(M)))
+
+    def _kmpc_set_obstacles(self, obs):
+        _Mpc._set_obstacles(self, "f1p_kmpc_set_obstacles", obs)
 
     def _kmpc_set_obstacles_dev(self, d_obs, E=None, M=None):
-        if d_obs is None:
-            self._check(self.lib.f1p_kmpc_set_obstacles_dev(self.h, None, 0, 0))
-            return
-        if E is None or M is None:
-            raise ValueError("a device array of obstacles needs its E and M")
-        self._check(self.lib.f1p_kmpc_set_obstacles_dev(self.h, _dev(d_obs), int(E), int(M)))
+        _Mpc._set_obstacles_dev(self, "f1p_kmpc_set_obstacles_dev", d_obs, E, M)
+
+    def _stmpc_set_obstacles(self, obs):
+        _Mpc._set_obstacles(self, "f1p_stmpc_set_obstacles", obs)
+
+    def _stmpc_set_obstacles_dev(self, d_obs, E=None, M=None):
+        _Mpc._set_obstacles_dev(self, "f1p_stmpc_set_obstacles_dev", d_obs, E, M)
 
     def stmpc_set_collision(self, on=True, n_sub=1, n_sub_k=2):
         """test the dynamic MPC's shooting rollouts against the occupancy grid (f1p_stmpc_set_collision): n_sub points per step of the

@@ -631,7 +631,7 @@ int f1p_kmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub);
  * then evaluated in plain fp64 whatever the mode and equal f1p_kmpc_plan_dev bit for bit.
  * Errors, nothing launched: M outside [1, 16]: F1P_EINVAL; a plan whose E is not the E the obstacles were set for: F1P_ESTATE;
  * f1p_kmpc_set_groups(> 0) while obstacles are set (and setting obstacles while groups are forced): F1P_ESTATE.
- * Not covered: f1p_stmpc_* (its kinematic branch included), f1p_kmpc_qp_*, and a MultiContext's sharded plans. */
+ * Not covered: f1p_stmpc_* (f1p_stmpc_set_obstacles is its own), f1p_kmpc_qp_*, and a MultiContext's sharded plans. */
 #define F1P_KMPC_MAX_OBS 16
 int f1p_kmpc_set_obstacles(f1p_ctx* ctx, const double* obs, int32_t E, int32_t M);
 int f1p_kmpc_set_obstacles_dev(f1p_ctx* ctx, const double* d_obs, int32_t E, int32_t M);
@@ -794,6 +794,26 @@ int f1p_stmpc_set_mode(f1p_ctx* ctx, int32_t mixed, float* d_cost32, int32_t* d_
  * (F1P_ESTATE).  A count outside [1, 16]: F1P_EINVAL, the switch keeps its state.
  * Not covered: f1p_stmpc_qp_*. */
 int f1p_stmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub, int32_t n_sub_k);
+/* Moving obstacles on the rollouts of the dynamic MPC's shooting solver: f1p_kmpc_set_obstacles' discs and rule
+ * for f1p_stmpc_*.  obs [E][M][5] fp64 rows (x, y, vx, vy, r) in the map frame, M <= F1P_KMPC_MAX_OBS, INDEXED BY THE CALLER'S EGO
+ * ORDER (for f1p_stmpc_plan_batch the batch's, whatever branch an ego takes); a slot with !(r >= 0) is empty.
+ * Tested points: f1p_stmpc_set_collision's, n_sub per step of the dynamic model and n_sub_k per step of plan_batch's kinematic
+ * branch (the context keeps both numbers while `on` is 0; defaults 1 and 2).  The point of step t at f = (double)j / (double)n_sub
+ * has the time tau = ((double)t + f) * dt with the BRANCH's dt; against a live slot, in fp64 and in this order,
+ *   cx = x + vx * tau; cy = y + vy * tau; dx = Px - cx; dy = Py - cy; d2 = dx*dx + dy*dy;   blocked when !(d2 > r*r)
+ * -- touching blocks, a NaN anywhere blocks.  With f1p_stmpc_set_collision on as well a point is tested against both rules.  The
+ * decision, the NaN-cost rule and the all-blocked outputs (best_idx -1, best_cost +inf, steer 0, speed 0, zero best_seq, zero warm
+ * row, the warm tag the branch's own) are that test's.  An ego without a live slot gets the bits of the plan without obstacles.
+ * f1p_stmpc_set_obstacles copies the array on the context's stream; obs == NULL or M == 0 clears.  f1p_stmpc_set_obstacles_dev
+ * BORROWS a device array: the caller keeps it alive and may rewrite it in place between plans (in stream order).  The obstacles
+ * are a state of their own beside f1p_kmpc_set_obstacles' (f1p_kmpc_* follows that one only, f1p_stmpc_* this one only) and
+ * apply to f1p_stmpc_plan_dev / _plan_batch / _shoot_dev / _shoot_batch with or without a grid; the streamed entry points are then
+ * evaluated in plain fp64 whatever the mode and equal f1p_stmpc_plan_dev bit for bit.
+ * Errors, nothing launched and no warm tag touched: M outside [1, 16]: F1P_EINVAL; a plan whose E is not the obstacles' E (for
+ * plan_batch the caller's E): F1P_ESTATE; f1p_stmpc_plan_batch under f1p_kmpc_set_groups(> 0) with obstacles set: F1P_ESTATE.
+ * Not covered: f1p_stmpc_qp_*, a MultiContext's sharded plans, f1p_kmpc_*. */
+int f1p_stmpc_set_obstacles(f1p_ctx* ctx, const double* obs, int32_t E, int32_t M);
+int f1p_stmpc_set_obstacles_dev(f1p_ctx* ctx, const double* d_obs, int32_t E, int32_t M);
 int f1p_stmpc_shoot_batch(f1p_ctx* ctx, const double* x0, const double* ref, const float* controls, int32_t E,
                           const f1p_stmpc_cfg* cfg, double* steer, double* speed, int32_t* best_idx, double* best_cost,
                           double* best_seq);

@@ -37,7 +37,10 @@ CSRC = os.path.join(ROOT, "f1tenth_planning_amd", "csrc")
 #   k_stmpc_shoot_t<StCtlGen>   (INS_8StCtlGenEJEE: k_stmpc_shoot_gen, not its _col form) the PLAIN-fp64 evaluation of f1p_stmpc_plan_* (f1p_stmpc_set_mode(0): the parity mode, not the default schedule): 36 B of
 #                       SGPR spill slots around the all-fp64 rollout loop's set-up.  The default schedule's kernels (k_stmpc_filter_gen,
 #                       _refine_gen, _refine_tp_gen, _decide_gen) carry none
-BUDGET = {"ILb1E": 56, "k_kmpc_plan_gen_tIJEE": 32, "k_kmpc_plan_gen_tIJNS_11KmpcIdxArgsEEE": 52, "k_stmpc_shoot_tINS_8StCtlGenEJEE": 36, "k_kmpc_shoot_mixed": 0, "k_clothoid_g1": 8, "9k_latticeILb0E": 8,
+#   k_kmpc_plan_gen_t<KmpcIdxArgs, KmpcObs>   the kinematic branch of f1p_stmpc_plan_batch with f1p_stmpc_set_obstacles' discs: 4 VGPRs (12 B), reloaded in the
+#                       fp64 tails (the refinement's time-parallel disc test and the serial fp64 fallback), none in the three f32 filter loops; the
+#                       same kernel without the indirection (k_kmpc_plan_gen_obs) carries none
+BUDGET = {"ILb1E": 56, "k_kmpc_plan_gen_tIJEE": 32, "k_kmpc_plan_gen_tIJNS_11KmpcIdxArgsEEE": 52, "k_kmpc_plan_gen_tIJNS_11KmpcIdxArgsENS_7KmpcObsEEE": 12, "k_stmpc_shoot_tINS_8StCtlGenEJEE": 36, "k_kmpc_shoot_mixed": 0, "k_clothoid_g1": 8, "9k_latticeILb0E": 8,
           "k_lattice_filter3ILi1ELb1E": 24, "k_lattice_filter3ILi2ELb1E": 24,
           "k_lattice_filter3ILi1ELb0ELb0ELi0ELb1E": 8, "k_lattice_filter3ILi2ELb0ELb0ELi0ELb1E": 8,
           "9k_latticeILb0ELi0ELb1ELb0ELb1E": 24}   # (the instantiations WITH test hooks -- incl. the host-goal shapes; device goals, point footprint: 0)
