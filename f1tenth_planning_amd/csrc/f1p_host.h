@@ -151,5 +151,14 @@ int qp_opts(f1p_ctx* ctx, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o, con
 int validate_ref(f1p_ctx* ctx, const void* states, const int32_t* track_id, bool tracks, int E, int horizon, double dt, double dl, const void* ref);
 int ref_batch_impl(f1p_ctx* ctx, int ncol, const double* states, const int32_t* track_id, bool tracks, int32_t E, int32_t horizon, double dt, double dl,
                    double* ref);
+// f1p_kmpc.hip: what the two shooting planners' rollout tests share on the host.  who: "kmpc" / "stmpc", the prefix of every message.
+// set_obstacles: obs (host or device, by `dev`) -> the discs in force of `st`; null or M == 0 clears.  groups_matter: the planner's tested
+// kernels run one workgroup per ego, so f1p_kmpc_set_groups(> 0) refuses the set.
+int set_obstacles(f1p_ctx* ctx, ObsState& st, const char* who, bool groups_matter, const double* obs, int32_t E, int32_t M, bool dev);
+// the preconditions of the tests of a plan over E egos, checked before anything is launched: the discs of `st` (set for E egos), and -- while
+// `on` -- the occupancy test with its n_sub points per step (n_sub_k: the second count of f1p_stmpc_set_collision, F1P_NO_NSUB_K: there is none).
+// kinematic: the call may run the kinematic filter (one workgroup per ego with a test)
+#define F1P_NO_NSUB_K (-1)
+int collision_check(f1p_ctx* ctx, const ObsState& st, bool on, int n_sub, int n_sub_k, const char* who, bool kinematic, int E);
 
 }  // namespace f1p

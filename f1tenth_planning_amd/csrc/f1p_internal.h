@@ -21,6 +21,15 @@ struct WarmBuf {
     template <typename T> T* as() const { return (T*)d; }
 };
 
+// One shooting planner's moving discs (f1p_kmpc_set_obstacles, f1p_stmpc_set_obstacles; f1p::set_obstacles): [E][M][5] fp64 rows
+// (x, y, vx, vy, r) in the caller's ego order, tested at the occupancy test's points
+struct ObsState {
+    double* d = nullptr;           // the context's own copy, kept across sets when large enough
+    size_t bytes = 0;
+    const double* cur = nullptr;   // the array in force: d or the caller's (f1p_*_set_obstacles_dev); null: none
+    int E = 0, M = 0;
+};
+
 struct f1p_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -72,11 +81,7 @@ struct f1p_ctx {
     bool kmpc_mixed = true;
     bool kmpc_collision = false;   // f1p_kmpc_set_collision: rollouts of f1p_kmpc_plan_* / f1p_kmpc_shoot_* are tested against d_bits
     int kmpc_col_nsub = 1;         // ... at this many points per time step
-    // f1p_kmpc_set_obstacles: moving discs per ego, [E][M][5] fp64 rows (x, y, vx, vy, r), tested at the same points
-    double* d_kmpc_obs = nullptr;        // the context's own copy (f1p_kmpc_set_obstacles), kept across sets when large enough
-    size_t kmpc_obs_bytes = 0;
-    const double* kmpc_obs_cur = nullptr;   // the array in force: d_kmpc_obs or the caller's (f1p_kmpc_set_obstacles_dev); null: none
-    int kmpc_obs_E = 0, kmpc_obs_M = 0;
+    ObsState kmpc_obs;             // f1p_kmpc_set_obstacles
     float* d_dbg_cost32 = nullptr;     // [E][R] filter costs of the next launch (test hook), or null
     int32_t* d_dbg_nref = nullptr;     // [E] size of the refined set (-1 = fp64 fallback), or null
 
@@ -85,11 +90,7 @@ struct f1p_ctx {
     bool stmpc_collision = false;      // f1p_stmpc_set_collision: rollouts of f1p_stmpc_plan_* / f1p_stmpc_shoot_* are tested against d_bits
     int stmpc_col_nsub = 1;            // ... at this many points per step of the dynamic model,
     int stmpc_col_nsub_k = 2;          // ... and at this many per step of f1p_stmpc_plan_batch's kinematic branch
-    // f1p_stmpc_set_obstacles: the dynamic MPC's own moving discs, [E][M][5] fp64 rows in the caller's ego order
-    double* d_stmpc_obs = nullptr;          // the context's own copy, kept across sets when large enough
-    size_t stmpc_obs_bytes = 0;
-    const double* stmpc_obs_cur = nullptr;  // the array in force: d_stmpc_obs or the caller's (f1p_stmpc_set_obstacles_dev); null: none
-    int stmpc_obs_E = 0, stmpc_obs_M = 0;
+    ObsState stmpc_obs;                // f1p_stmpc_set_obstacles: the dynamic MPC's own discs, a state of its own beside kmpc_obs
     float* d_dbg_st_cost32 = nullptr;  // [E][R] filter costs (-inf = untrusted) of the next launches, or null
     int32_t* d_dbg_st_nref = nullptr;  // [E] refined rollouts (-1 = all-fp64 fallback), or null
     char* d_st_scratch = nullptr;      // k_stmpc_filter -> refine -> decide: queue counter | per-ego counts | lists | queue | refined costs

@@ -57,24 +57,54 @@ int ref_batch_impl(f1p_ctx* ctx, int ncol, const double* states, const int32_t* 
     return s.finish();
 }
 
-}  // namespace f1p
-
-// f1p_kmpc_set_collision's preconditions, checked by every entry point that would launch the tested kernels -- before anything is launched
-static int kmpc_collision_check(f1p_ctx* ctx, int E) {
-    if (ctx->kmpc_obs_cur) {                                          // f1p_kmpc_set_obstacles: with or without the grid
-        if (E != ctx->kmpc_obs_E)
-            return set_error(ctx, F1P_ESTATE, "kmpc obstacles were set for " + std::to_string(ctx->kmpc_obs_E) + " egos, this plan has " + std::to_string(E) +
-                                              " (f1p_kmpc_set_obstacles)");
-        if (ctx->kmpc_groups > 0) return set_error(ctx, F1P_ESTATE, "kmpc obstacle test runs one workgroup per ego: f1p_kmpc_set_groups(0)");
+int collision_check(f1p_ctx* ctx, const ObsState& st, bool on, int n_sub, int n_sub_k, const char* who, bool kinematic, int E) {
+    const std::string w = who;
+    const bool split = kinematic && ctx->kmpc_groups > 0;
+    if (st.cur) {                                                     // the discs: with or without the grid
+        if (E != st.E)
+            return set_error(ctx, F1P_ESTATE, w + " obstacles were set for " + std::to_string(st.E) + " egos, this plan has " + std::to_string(E) + " (f1p_" + w + "_set_obstacles)");
+        if (split) return set_error(ctx, F1P_ESTATE, w + " obstacle test runs one workgroup per ego: f1p_kmpc_set_groups(0)");
     }
-    if (!ctx->kmpc_collision) return F1P_OK;
-    if (!ctx->has_grid) return set_error(ctx, F1P_ESTATE, "kmpc collision test is on but no occupancy grid is loaded (f1p_set_grid)");
+    if (!on) return F1P_OK;
+    if (!ctx->has_grid) return set_error(ctx, F1P_ESTATE, w + " collision test is on but no occupancy grid is loaded (f1p_set_grid)");
     if (ctx->n_disc > 0)
-        return set_error(ctx, F1P_ESTATE, "kmpc collision test is a point / disc test: remove the oriented footprint (f1p_set_footprint) and use f1p_inflate_grid");
-    if (ctx->kmpc_groups > 0) return set_error(ctx, F1P_ESTATE, "kmpc collision test runs one workgroup per ego: f1p_kmpc_set_groups(0)");
-    if (ctx->kmpc_col_nsub < 1 || ctx->kmpc_col_nsub > 16) return set_error(ctx, F1P_EINVAL, "kmpc collision test: n_sub must be in [1, 16]");
+        return set_error(ctx, F1P_ESTATE, w + " collision test is a point / disc test: remove the oriented footprint (f1p_set_footprint) and use f1p_inflate_grid");
+    if (split) return set_error(ctx, F1P_ESTATE, w + " collision test runs one workgroup per ego: f1p_kmpc_set_groups(0)");
+    const auto bad = [](int n) { return n < 1 || n > 16; };
+    const bool two = n_sub_k != F1P_NO_NSUB_K;
+    if (bad(n_sub) || (two && bad(n_sub_k)))
+        return set_error(ctx, F1P_EINVAL, w + (two ? " collision test: n_sub and n_sub_k must be in [1, 16]" : " collision test: n_sub must be in [1, 16]"));
     return F1P_OK;
 }
+
+int set_obstacles(f1p_ctx* ctx, ObsState& st, const char* who, bool groups_matter, const double* obs, int32_t E, int32_t M, bool dev) {
+    F1P_ENTER(ctx);
+    const std::string w = who;
+    if (!obs || M == 0) { st.cur = nullptr; st.E = 0; st.M = 0; return F1P_OK; }
+    if (M < 1 || M > F1P_KMPC_MAX_OBS) return set_error(ctx, F1P_EINVAL, w + " obstacles: M must be in [1, 16]");
+    if (E < 1) return set_error(ctx, F1P_EINVAL, w + " obstacles: E must be >= 1");
+    if (groups_matter && ctx->kmpc_groups > 0) return set_error(ctx, F1P_ESTATE, w + " obstacle test runs one workgroup per ego: f1p_kmpc_set_groups(0)");
+    if (dev) { st.cur = obs; st.E = E; st.M = M; return F1P_OK; }
+    const size_t bytes = sizeof(double) * 5 * (size_t)E * M;
+    if (bytes > st.bytes) {
+        st.cur = nullptr; st.E = 0; st.M = 0;
+        F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));              // no launch in flight reads the old copy
+        if (st.d) (void)hipFree(st.d);
+        st.d = nullptr; st.bytes = 0;
+        F1P_HIP(ctx, hipMalloc((void**)&st.d, bytes));
+        st.bytes = bytes;
+    }
+    // (pageable host memory: the copy has left the caller's array when this returns; stream order puts it after the plans already queued)
+    F1P_HIP(ctx, hipMemcpyAsync(st.d, obs, bytes, hipMemcpyHostToDevice, ctx->stream));
+    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    st.cur = st.d; st.E = E; st.M = M;
+    return F1P_OK;
+}
+
+}  // namespace f1p
+
+// f1p_kmpc_set_collision's / f1p_kmpc_set_obstacles' preconditions, checked by every entry point that would launch the tested kernels
+static int kmpc_collision_check(f1p_ctx* ctx, int E) { return collision_check(ctx, ctx->kmpc_obs, ctx->kmpc_collision, ctx->kmpc_col_nsub, F1P_NO_NSUB_K, "kmpc", true, E); }
 
 int f1p_kmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub) {
     F1P_ENTER(ctx);
@@ -84,31 +114,8 @@ int f1p_kmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub) {
     return F1P_OK;
 }
 
-// obs (host or device, by `dev`) -> the discs in force; null or M == 0 clears
-static int kmpc_set_obstacles(f1p_ctx* ctx, const double* obs, int32_t E, int32_t M, bool dev) {
-    F1P_ENTER(ctx);
-    if (!obs || M == 0) { ctx->kmpc_obs_cur = nullptr; ctx->kmpc_obs_E = 0; ctx->kmpc_obs_M = 0; return F1P_OK; }
-    if (M < 1 || M > F1P_KMPC_MAX_OBS) return set_error(ctx, F1P_EINVAL, "kmpc obstacles: M must be in [1, 16]");
-    if (E < 1) return set_error(ctx, F1P_EINVAL, "kmpc obstacles: E must be >= 1");
-    if (ctx->kmpc_groups > 0) return set_error(ctx, F1P_ESTATE, "kmpc obstacle test runs one workgroup per ego: f1p_kmpc_set_groups(0)");
-    if (dev) { ctx->kmpc_obs_cur = obs; ctx->kmpc_obs_E = E; ctx->kmpc_obs_M = M; return F1P_OK; }
-    const size_t bytes = sizeof(double) * 5 * (size_t)E * M;
-    if (bytes > ctx->kmpc_obs_bytes) {
-        ctx->kmpc_obs_cur = nullptr; ctx->kmpc_obs_E = 0; ctx->kmpc_obs_M = 0;
-        F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));              // no launch in flight reads the old copy
-        if (ctx->d_kmpc_obs) (void)hipFree(ctx->d_kmpc_obs);
-        ctx->d_kmpc_obs = nullptr; ctx->kmpc_obs_bytes = 0;
-        F1P_HIP(ctx, hipMalloc((void**)&ctx->d_kmpc_obs, bytes));
-        ctx->kmpc_obs_bytes = bytes;
-    }
-    // (pageable host memory: the copy has left the caller's array when this returns; stream order puts it after the plans already queued)
-    F1P_HIP(ctx, hipMemcpyAsync(ctx->d_kmpc_obs, obs, bytes, hipMemcpyHostToDevice, ctx->stream));
-    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->kmpc_obs_cur = ctx->d_kmpc_obs; ctx->kmpc_obs_E = E; ctx->kmpc_obs_M = M;
-    return F1P_OK;
-}
-int f1p_kmpc_set_obstacles(f1p_ctx* ctx, const double* obs, int32_t E, int32_t M) { return kmpc_set_obstacles(ctx, obs, E, M, false); }
-int f1p_kmpc_set_obstacles_dev(f1p_ctx* ctx, const double* d_obs, int32_t E, int32_t M) { return kmpc_set_obstacles(ctx, d_obs, E, M, true); }
+int f1p_kmpc_set_obstacles(f1p_ctx* ctx, const double* obs, int32_t E, int32_t M) { return set_obstacles(ctx, ctx->kmpc_obs, "kmpc", true, obs, E, M, false); }
+int f1p_kmpc_set_obstacles_dev(f1p_ctx* ctx, const double* d_obs, int32_t E, int32_t M) { return set_obstacles(ctx, ctx->kmpc_obs, "kmpc", true, d_obs, E, M, true); }
 
 void f1p_kmpc_cfg_default(f1p_kmpc_cfg* cfg) {
     if (!cfg) return;
@@ -313,7 +320,7 @@ int f1p_kmpc_set_yaw_fixup(f1p_ctx* ctx, int32_t on) {
 int f1p_kmpc_set_groups(f1p_ctx* ctx, int32_t groups) {
     if (!ctx) return F1P_EINVAL;
     if (groups < 0 || groups > 64) return set_error(ctx, F1P_EINVAL, "groups must be in [0, 64]");
-    if (groups > 0 && ctx->kmpc_obs_cur) return set_error(ctx, F1P_ESTATE, "kmpc obstacles are set and run one workgroup per ego: clear them first (f1p_kmpc_set_obstacles)");
+    if (groups > 0 && ctx->kmpc_obs.cur) return set_error(ctx, F1P_ESTATE, "kmpc obstacles are set and run one workgroup per ego: clear them first (f1p_kmpc_set_obstacles)");
     ctx->kmpc_groups = groups;
     return F1P_OK;
 }

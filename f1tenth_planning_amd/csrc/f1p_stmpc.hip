@@ -136,21 +136,9 @@ int f1p_stmpc_set_mode(f1p_ctx* ctx, int32_t mixed, float* d_cost32, int32_t* d_
 // f1p_stmpc_set_collision's preconditions, checked by every entry point that would launch the tested kernels -- before anything is launched
 // or any warm-start tag is touched.  kinematic: the call may run f1p_stmpc_plan_batch's kinematic branch (one workgroup per ego with the test)
 // E: the caller's ego count (f1p_stmpc_set_obstacles' rows are in the caller's order: for plan_batch the batch's E, not a branch's)
+// (collision_check and set_obstacles, which both planners share, are defined in f1p_kmpc.hip and declared in f1p_host.h)
 static int stmpc_collision_check(f1p_ctx* ctx, bool kinematic, int E) {
-    if (ctx->stmpc_obs_cur) {                                         // f1p_stmpc_set_obstacles: with or without the grid
-        if (E != ctx->stmpc_obs_E)
-            return set_error(ctx, F1P_ESTATE, "stmpc obstacles were set for " + std::to_string(ctx->stmpc_obs_E) + " egos, this plan has " + std::to_string(E) +
-                                              " (f1p_stmpc_set_obstacles)");
-        if (kinematic && ctx->kmpc_groups > 0) return set_error(ctx, F1P_ESTATE, "stmpc obstacle test runs one workgroup per ego: f1p_kmpc_set_groups(0)");
-    }
-    if (!ctx->stmpc_collision) return F1P_OK;
-    if (!ctx->has_grid) return set_error(ctx, F1P_ESTATE, "stmpc collision test is on but no occupancy grid is loaded (f1p_set_grid)");
-    if (ctx->n_disc > 0)
-        return set_error(ctx, F1P_ESTATE, "stmpc collision test is a point / disc test: remove the oriented footprint (f1p_set_footprint) and use f1p_inflate_grid");
-    if (kinematic && ctx->kmpc_groups > 0) return set_error(ctx, F1P_ESTATE, "stmpc collision test runs one workgroup per ego: f1p_kmpc_set_groups(0)");
-    if (ctx->stmpc_col_nsub < 1 || ctx->stmpc_col_nsub > 16 || ctx->stmpc_col_nsub_k < 1 || ctx->stmpc_col_nsub_k > 16)
-        return set_error(ctx, F1P_EINVAL, "stmpc collision test: n_sub and n_sub_k must be in [1, 16]");
-    return F1P_OK;
+    return collision_check(ctx, ctx->stmpc_obs, ctx->stmpc_collision, ctx->stmpc_col_nsub, ctx->stmpc_col_nsub_k, "stmpc", kinematic, E);
 }
 
 int f1p_stmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub, int32_t n_sub_k) {
@@ -162,30 +150,9 @@ int f1p_stmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub, int32_t n_s
     return F1P_OK;
 }
 
-// obs (host or device, by `dev`) -> the discs in force; null or M == 0 clears.  A state of its own beside f1p_kmpc_set_obstacles'.
-static int stmpc_set_obstacles(f1p_ctx* ctx, const double* obs, int32_t E, int32_t M, bool dev) {
-    F1P_ENTER(ctx);
-    if (!obs || M == 0) { ctx->stmpc_obs_cur = nullptr; ctx->stmpc_obs_E = 0; ctx->stmpc_obs_M = 0; return F1P_OK; }
-    if (M < 1 || M > F1P_KMPC_MAX_OBS) return set_error(ctx, F1P_EINVAL, "stmpc obstacles: M must be in [1, 16]");
-    if (E < 1) return set_error(ctx, F1P_EINVAL, "stmpc obstacles: E must be >= 1");
-    if (dev) { ctx->stmpc_obs_cur = obs; ctx->stmpc_obs_E = E; ctx->stmpc_obs_M = M; return F1P_OK; }
-    const size_t bytes = sizeof(double) * 5 * (size_t)E * M;
-    if (bytes > ctx->stmpc_obs_bytes) {
-        ctx->stmpc_obs_cur = nullptr; ctx->stmpc_obs_E = 0; ctx->stmpc_obs_M = 0;
-        F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));              // no launch in flight reads the old copy
-        if (ctx->d_stmpc_obs) (void)hipFree(ctx->d_stmpc_obs);
-        ctx->d_stmpc_obs = nullptr; ctx->stmpc_obs_bytes = 0;
-        F1P_HIP(ctx, hipMalloc((void**)&ctx->d_stmpc_obs, bytes));
-        ctx->stmpc_obs_bytes = bytes;
-    }
-    // (pageable host memory: the copy has left the caller's array when this returns; stream order puts it after the plans already queued)
-    F1P_HIP(ctx, hipMemcpyAsync(ctx->d_stmpc_obs, obs, bytes, hipMemcpyHostToDevice, ctx->stream));
-    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->stmpc_obs_cur = ctx->d_stmpc_obs; ctx->stmpc_obs_E = E; ctx->stmpc_obs_M = M;
-    return F1P_OK;
-}
-int f1p_stmpc_set_obstacles(f1p_ctx* ctx, const double* obs, int32_t E, int32_t M) { return stmpc_set_obstacles(ctx, obs, E, M, false); }
-int f1p_stmpc_set_obstacles_dev(f1p_ctx* ctx, const double* d_obs, int32_t E, int32_t M) { return stmpc_set_obstacles(ctx, d_obs, E, M, true); }
+// (a state of its own beside f1p_kmpc_set_obstacles'; f1p_kmpc_set_groups does not bear on the dynamic filter)
+int f1p_stmpc_set_obstacles(f1p_ctx* ctx, const double* obs, int32_t E, int32_t M) { return set_obstacles(ctx, ctx->stmpc_obs, "stmpc", false, obs, E, M, false); }
+int f1p_stmpc_set_obstacles_dev(f1p_ctx* ctx, const double* d_obs, int32_t E, int32_t M) { return set_obstacles(ctx, ctx->stmpc_obs, "stmpc", false, d_obs, E, M, true); }
 
 int f1p_stmpc_shoot_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const float* d_controls, int32_t E,
                         const f1p_stmpc_cfg* cfg, double* d_steer, double* d_speed, int32_t* d_best_idx,

@@ -187,7 +187,7 @@ __device__ __forceinline__ float kmpc_ref32(const KmpcF32& kf, int row, bool ter
 // Two rollouts per thread in the lanes of packed-f32 instructions: plain f32 VALU ops issue 16 lanes per clock on CDNA4 and
 // only v_pk_{fma,mul,add}_f32 reach the 32-lane f32 rate, so the filter -- which is VALU-bound once the control stream is
 // prefetched -- evaluates rollouts r0 and r1 as the two halves of <2 x float> values.  Clamps are single v_med3_f32.
-typedef float f1p_f2 __attribute__((ext_vector_type(2)));
+// (f1p_f2: shoot_col.h, with the tested points of both filters)
 __device__ __forceinline__ f1p_f2 med3x2(f1p_f2 x, float lo, float hi) {
     f1p_f2 r;
     r.x = __builtin_amdgcn_fmed3f(x.x, lo, hi);
@@ -195,6 +195,20 @@ __device__ __forceinline__ f1p_f2 med3x2(f1p_f2 x, float lo, float hi) {
     return r;
 }
 struct KmpcState2 { f1p_f2 x, y, v, yaw, cost, pa, pd; };
+// every f32 rollout starts at the origin of the ego's frame with the ego's speed ...
+__device__ __forceinline__ KmpcState2 kmpc_state2_start(const KmpcF32& k) {
+    KmpcState2 s;
+    s.x = 0.f; s.y = 0.f; s.v = k.v0; s.yaw = 0.f; s.cost = 0.f; s.pa = 0.f; s.pd = 0.f;
+    return s;
+}
+// ... and ends with the terminal state's term (column T of the reference rows: the terminal weights) and the control terms' closing
+__device__ __forceinline__ f1p_f2 kmpc_terminal2(KmpcState2& s, const float* sref32, const KmpcF32& k, int T) {
+    const f1p_f2 e0 = k.sqf[0] * s.x + sref32[0 * (T + 1) + T], e1 = k.sqf[1] * s.y + sref32[1 * (T + 1) + T];
+    const f1p_f2 e2 = k.sqf[2] * s.v + sref32[2 * (T + 1) + T], e3 = k.sqf[3] * s.yaw + sref32[3 * (T + 1) + T];
+    s.cost += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
+    s.cost -= k.rd[0] * s.pa * s.pa + k.rd[1] * s.pd * s.pd;           // the last step has no successor (see KmpcF32)
+    return s.cost;
+}
 
 template <bool FULL, typename Src>
 __device__ __forceinline__ void kmpc_load_chunk2(const Src& src, int T, int r0, int r1, int t0,
@@ -273,8 +287,7 @@ __device__ __forceinline__ void kmpc_steps2(KmpcState2& s, const float* sref32, 
 template <bool POLY, bool ISO, typename Src>
 __device__ __forceinline__ f1p_f2 kmpc_rollout_cost_f32x2(const Src& src, const float* sref32, const KmpcF32& k, int T,
                                                          int r0, int r1) {
-    KmpcState2 s;
-    s.x = 0.f; s.y = 0.f; s.v = k.v0; s.yaw = 0.f; s.cost = 0.f; s.pa = 0.f; s.pd = 0.f;
+    KmpcState2 s = kmpc_state2_start(k);
     constexpr int CH = Src::chunk;
     int t0 = 0;
     if (T >= CH) {                                                     // the first chunk, whole
@@ -293,11 +306,7 @@ __device__ __forceinline__ f1p_f2 kmpc_rollout_cost_f32x2(const Src& src, const 
         if (t0 == 0) kmpc_steps2<POLY, ISO, false, true, CH>(s, sref32, k, T, 0, a0, d0);
         else kmpc_steps2<POLY, ISO, false, false, CH>(s, sref32, k, T, t0, a0, d0);
     }
-    const f1p_f2 e0 = k.sqf[0] * s.x + sref32[0 * (T + 1) + T], e1 = k.sqf[1] * s.y + sref32[1 * (T + 1) + T];
-    const f1p_f2 e2 = k.sqf[2] * s.v + sref32[2 * (T + 1) + T], e3 = k.sqf[3] * s.yaw + sref32[3 * (T + 1) + T];
-    s.cost += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
-    s.cost -= k.rd[0] * s.pa * s.pa + k.rd[1] * s.pd * s.pd;           // the last step has no successor (see KmpcF32)
-    return s.cost;
+    return kmpc_terminal2(s, sref32, k, T);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -312,13 +321,20 @@ __device__ __forceinline__ f1p_f2 kmpc_rollout_cost_f32x2(const Src& src, const 
 // ---------------------------------------------------------------------------------------------------
 // F1P_K4_CLEAR_CELLS, F1P_K4_POS_ERR_REL, KmpcColF: shoot_col.h (shared with k_stmpc.hip)
 
-// kmpc_rollout_cost_f32x2 step by step, every step's tested points looked up; u0 / u1: rollout r0 / r1 is UNSURE
-template <bool POLY, bool ISO, typename Src>
-__device__ __forceinline__ f1p_f2 kmpc_rollout_cost_f32x2_col(const Src& src, const float* sref32, const KmpcF32& k, int T, int r0, int r1,
-                                                             const KmpcColF& cf, bool& u0, bool& u1) {
-    KmpcState2 s;
-    s.x = 0.f; s.y = 0.f; s.v = k.v0; s.yaw = 0.f; s.cost = 0.f; s.pa = 0.f; s.pd = 0.f;
+// kmpc_rollout_cost_f32x2 step by step, every step's tested points tested as `test` says (shoot_col.h).  ColTestGrid (k_kmpc_plan_gen_col):
+// looked up in the clearance map.  ColTestObs (k_kmpc_plan_gen_obs, the moving discs of f1p_kmpc_set_obstacles): compared
+// with every live slot of the ego's LDS table at the point's time, and looked up as well while the occupancy test is on (of.grid).
+// u0 / u1: rollout r0 / r1 is UNSURE -- FREE needs every proof at every point.
+template <bool POLY, bool ISO, typename Test, typename Src>
+__device__ __forceinline__ f1p_f2 kmpc_rollout_cost_f32x2_test(const Src& src, const float* sref32, const KmpcF32& k, int T, int r0, int r1,
+                                                              const Test& test, bool& u0, bool& u1) {
+    constexpr bool OBS = std::is_same_v<Test, ColTestObs>;
+    static_assert(OBS || std::is_same_v<Test, ColTestGrid>, "the plain filter is kmpc_rollout_cost_f32x2: its steps run in chunks, not one by one");
+    const KmpcColF& cf = test.cf;
+    KmpcState2 s = kmpc_state2_start(k);
     bool h0 = false, h1 = false;
+    [[maybe_unused]] bool testing = true;                             // (the discs: every slot empty and no grid -> the plain filter, step by step)
+    if constexpr (OBS) testing = test.of.grid | (test.of.n_live > 0);
     for (int te = 0; te < T; te += 2) {
         f1p_f2 av[2], dv[2];
         {
@@ -335,52 +351,17 @@ __device__ __forceinline__ f1p_f2 kmpc_rollout_cost_f32x2_col(const Src& src, co
                 const f1p_f2 px = s.x, py = s.y;
                 const f1p_f2 a1[1] = {av[jj]}, d1[1] = {dv[jj]};
                 kmpc_steps2<POLY, ISO, false, false, 1>(s, sref32, k, T, t, a1, d1);
-                for (int j = 1; j < cf.n_sub; ++j) {
-                    const float f = (float)j * cf.inv_nsub;
-                    const f1p_f2 qx = px + (s.x - px) * f, qy = py + (s.y - py) * f;
-                    h0 |= cf.template unsure<ISO>(qx.x, qy.x);
-                    h1 |= cf.template unsure<ISO>(qx.y, qy.y);
-                }
-                h0 |= cf.template unsure<ISO>(s.x.x, s.y.x);
-                h1 |= cf.template unsure<ISO>(s.x.y, s.y.y);
-            }
-        }
-    }
-    const f1p_f2 e0 = k.sqf[0] * s.x + sref32[0 * (T + 1) + T], e1 = k.sqf[1] * s.y + sref32[1 * (T + 1) + T];
-    const f1p_f2 e2 = k.sqf[2] * s.v + sref32[2 * (T + 1) + T], e3 = k.sqf[3] * s.yaw + sref32[3 * (T + 1) + T];
-    s.cost += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
-    s.cost -= k.rd[0] * s.pa * s.pa + k.rd[1] * s.pd * s.pd;           // the last step has no successor (see KmpcF32)
-    u0 = h0; u1 = h1;
-    return s.cost;
-}
-
-// kmpc_rollout_cost_f32x2_col with the moving discs of f1p_kmpc_set_obstacles (k_kmpc_plan_gen_obs): every tested point is
-// compared with every live slot of the ego's LDS table at the point's time, and looked up in the clearance map as well while the
-// occupancy test is on (of.grid).  FREE needs both proofs at every point.
-template <bool POLY, bool ISO, typename Src>
-__device__ __forceinline__ f1p_f2 kmpc_rollout_cost_f32x2_obs(const Src& src, const float* sref32, const KmpcF32& k, int T, int r0, int r1,
-                                                             const KmpcColF& cf, const KmpcObsF& of, bool& u0, bool& u1) {
-    KmpcState2 s;
-    s.x = 0.f; s.y = 0.f; s.v = k.v0; s.yaw = 0.f; s.cost = 0.f; s.pa = 0.f; s.pd = 0.f;
-    bool h0 = false, h1 = false;
-    const bool test = of.grid | (of.n_live > 0);                      // (every slot empty and no grid: the plain filter, step by step)
-    for (int te = 0; te < T; te += 2) {
-        f1p_f2 av[2], dv[2];
-        {
-            float a00, d00, a01, d01, a10, d10, a11, d11;
-            src.template get2<false>(te, T, r0, a00, d00, a01, d01);
-            src.template get2<false>(te, T, r1, a10, d10, a11, d11);
-            av[0].x = a00; av[0].y = a10; dv[0].x = d00; dv[0].y = d10;
-            av[1].x = a01; av[1].y = a11; dv[1].x = d01; dv[1].y = d11;
-        }
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            const int t = te + jj;
-            if (t < T) {
-                const f1p_f2 px = s.x, py = s.y;
-                const f1p_f2 a1[1] = {av[jj]}, d1[1] = {dv[jj]};
-                kmpc_steps2<POLY, ISO, false, false, 1>(s, sref32, k, T, t, a1, d1);
-                if (test) {
+                if constexpr (!OBS) {                                 // j = 1 .. n_sub - 1, then p_{t+1} itself
+                    for (int j = 1; j < cf.n_sub; ++j) {
+                        const float f = (float)j * cf.inv_nsub;
+                        const f1p_f2 qx = px + (s.x - px) * f, qy = py + (s.y - py) * f;
+                        h0 |= cf.template unsure<ISO>(qx.x, qy.x);
+                        h1 |= cf.template unsure<ISO>(qx.y, qy.y);
+                    }
+                    h0 |= cf.template unsure<ISO>(s.x.x, s.y.x);
+                    h1 |= cf.template unsure<ISO>(s.x.y, s.y.y);
+                } else if (testing) {                                 // j = 1 .. n_sub, every point at its own time
+                    const KmpcObsF& of = test.of;
                     for (int j = 1; j <= cf.n_sub; ++j) {
                         const bool end = j == cf.n_sub;
                         const float f = end ? 1.0f : (float)j * cf.inv_nsub;
@@ -402,12 +383,8 @@ __device__ __forceinline__ f1p_f2 kmpc_rollout_cost_f32x2_obs(const Src& src, co
             }
         }
     }
-    const f1p_f2 e0 = k.sqf[0] * s.x + sref32[0 * (T + 1) + T], e1 = k.sqf[1] * s.y + sref32[1 * (T + 1) + T];
-    const f1p_f2 e2 = k.sqf[2] * s.v + sref32[2 * (T + 1) + T], e3 = k.sqf[3] * s.yaw + sref32[3 * (T + 1) + T];
-    s.cost += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
-    s.cost -= k.rd[0] * s.pa * s.pa + k.rd[1] * s.pd * s.pd;           // the last step has no successor (see KmpcF32)
     u0 = h0; u1 = h1;
-    return s.cost;
+    return kmpc_terminal2(s, sref32, k, T);
 }
 
 // The STREAMED filter (round 5): the same steps, fed differently.  (i) A thread's two rollouts are NEIGHBOURS (r, r + 1) when R is even, so
@@ -442,8 +419,7 @@ __device__ __forceinline__ void kmpc_raw2(f1p_f2& raw, const f1p_f2 (&av)[2], co
 template <bool POLY, bool ISO, bool ADJ>
 __device__ __forceinline__ f1p_f2 kmpc_rollout_cost_stream(const SrcStream& src, const float* sref32, const KmpcF32& k, int T, int r0, int r1) {
     f1p_f2 raw = 0.f;
-    KmpcState2 s;
-    s.x = 0.f; s.y = 0.f; s.v = k.v0; s.yaw = 0.f; s.cost = 0.f; s.pa = 0.f; s.pd = 0.f;
+    KmpcState2 s = kmpc_state2_start(k);
     constexpr int CH = 2;
     const int nch = T / CH;                                            // whole chunks
     f1p_f2 a0[CH], d0[CH], a1[CH], d1[CH], a2[CH], d2[CH];
@@ -497,10 +473,7 @@ __device__ __forceinline__ f1p_f2 kmpc_rollout_cost_stream(const SrcStream& src,
         else kmpc_steps2<POLY, ISO, false, false, CH>(s, sref32, k, T, t0, a0, d0);
         kmpc_raw2(raw, a0, d0, false);
     }
-    const f1p_f2 e0 = k.sqf[0] * s.x + sref32[0 * (T + 1) + T], e1 = k.sqf[1] * s.y + sref32[1 * (T + 1) + T];
-    const f1p_f2 e2 = k.sqf[2] * s.v + sref32[2 * (T + 1) + T], e3 = k.sqf[3] * s.yaw + sref32[3 * (T + 1) + T];
-    s.cost += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
-    s.cost -= k.rd[0] * s.pa * s.pa + k.rd[1] * s.pd * s.pd;           // the last step has no successor (see KmpcF32)
+    kmpc_terminal2(s, sref32, k, T);
     if (!(raw.x == raw.x)) s.cost.x = raw.x;                           // a NaN control: a NaN filter cost, which the caller lists for fp64
     if (!(raw.y == raw.y)) s.cost.y = raw.y;
     return s.cost;
@@ -1001,25 +974,22 @@ __global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void k_kmpc_plan_gen_t(const
     // the ego's cell (fp64) anchors the filter's cell coordinates; an ego without one, no clearance map or f1p_kmpc_set_mode(0): all in fp64
     [[maybe_unused]] double bxd = 0.0, byd = 0.0;
     [[maybe_unused]] bool col_ok = true;
-    bool in_range;                                                    // workgroup-uniform: the fast paths' ranges
-    if constexpr (OBS) {
-        // without a grid the discs need no cell: their FREE threshold carries the filter's position bound itself (obs_compact)
-        const KmpcObs& col = col_of(ex...);
-        if (col.g.bits) {
+    if constexpr (COL) {
+        const KmpcCol& col = col_of(ex...);
+        bool grid = true;                                             // (the discs may come without one: a null bitmap)
+        if constexpr (OBS) grid = col.g.bits != nullptr;
+        if (grid) {
             bxd = (sx - col.g.ox) * col.g.inv_res; byd = (sy - col.g.oy) * col.g.inv_res;
             col_ok = col.clear && !col.force64 && fabs(bxd) < 1.0e6 && fabs(byd) < 1.0e6;
         } else {
-            col_ok = !col.force64;
+            col_ok = !col.force64;                                    // the discs need no cell: their FREE threshold carries the filter's position bound itself (obs_compact)
         }
-        in_range = fabs(syaw) <= 1.0e4 && fabs(cfg.max_steer) <= 1.0e4 && kf.w_ok && col_ok;
-    } else if constexpr (COL) {
-        const KmpcCol& col = col_of(ex...);
-        bxd = (sx - col.g.ox) * col.g.inv_res; byd = (sy - col.g.oy) * col.g.inv_res;
-        col_ok = col.clear && !col.force64 && fabs(bxd) < 1.0e6 && fabs(byd) < 1.0e6;
-        in_range = fabs(syaw) <= 1.0e4 && fabs(cfg.max_steer) <= 1.0e4 && kf.w_ok && col_ok;
-    } else {
-        in_range = fabs(syaw) <= 1.0e4 && fabs(cfg.max_steer) <= 1.0e4 && kf.w_ok;
     }
+    // workgroup-uniform: the fast paths' ranges.  (Two spellings: `&& col_ok` with a constant true, or behind a compile-time guard, moves
+    // instructions in the kernels without the test -- LABNOTES.md R15)
+    bool in_range;
+    if constexpr (COL) in_range = fabs(syaw) <= 1.0e4 && fabs(cfg.max_steer) <= 1.0e4 && kf.w_ok && col_ok;
+    else in_range = fabs(syaw) <= 1.0e4 && fabs(cfg.max_steer) <= 1.0e4 && kf.w_ok;
     double s0d, c0d;
     sincos_core(in_range ? syaw : 0.0, &s0d, &c0d);
     const bool poly = kf.max_steer <= 0.45f;
@@ -1047,21 +1017,13 @@ __global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void k_kmpc_plan_gen_t(const
     k.s0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, (float)s0d)));
     k.v0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, (float)sv)));
 
-    [[maybe_unused]] KmpcColF cf;
-    [[maybe_unused]] KmpcObsF of;
+    // what the filter tests after every step (shoot_col.h): nothing, the clearance look-ups, or the look-ups and the discs
+    [[maybe_unused]] std::conditional_t<OBS, ColTestObs, std::conditional_t<COL, ColTestGrid, ColTestNone>> test;
     if constexpr (OBS) {
         src.col.live = olive; src.col.n_live = __builtin_amdgcn_readfirstlane(*on_live);
-        of.live = olive32; of.n_live = src.col.n_live; of.grid = src.col.g.bits != nullptr; of.dt = kf.dt;
+        test.of.live = olive32; test.of.n_live = src.col.n_live; test.of.grid = src.col.g.bits != nullptr; test.of.dt = kf.dt;
     }
-    if constexpr (COL) {
-        const KmpcCol& col = col_of(ex...);
-        const double ibx = col_ok ? __builtin_floor(bxd) : 0.0, iby = col_ok ? __builtin_floor(byd) : 0.0;
-        cf.clear = col.clear; cf.wwords = col.g.wwords; cf.n_sub = col.n_sub; cf.inv_nsub = 1.0f / (float)col.n_sub;
-        cf.ibx = __builtin_amdgcn_readfirstlane((int)ibx); cf.iby = __builtin_amdgcn_readfirstlane((int)iby);
-        cf.bx = (float)(bxd - ibx); cf.by = (float)(byd - iby);
-        cf.lox = (float)-cf.ibx; cf.hix = (float)(col.g.w - cf.ibx); cf.loy = (float)-cf.iby; cf.hiy = (float)(col.g.h - cf.iby);
-        cf.inv_res = (float)col.g.inv_res; cf.c0 = k.c0; cf.s0 = k.s0;
-    }
+    if constexpr (COL) test.cf = col_filter(col_of(ex...), bxd, byd, col_ok, k.c0, k.s0);
     F1P_KPH();
     // ---- pass A: f32 filter over this workgroup's slice ---------------------------------------------------------------
     const int r_lo = g * ga.Rs, r_hi = min(R, r_lo + ga.Rs);
@@ -1074,14 +1036,9 @@ __global__ __launch_bounds__(256, F1P_K4_WAVES_GEN) void k_kmpc_plan_gen_t(const
             f1p_f2 c;
             if constexpr (COL) {
                 bool u0, u1;
-                if constexpr (OBS)
-                    c = iso ? kmpc_rollout_cost_f32x2_obs<true, true>(src, sref32, k, T, r, r1, cf, of, u0, u1)
-                            : (poly ? kmpc_rollout_cost_f32x2_obs<true, false>(src, sref32, k, T, r, r1, cf, of, u0, u1)
-                                    : kmpc_rollout_cost_f32x2_obs<false, false>(src, sref32, k, T, r, r1, cf, of, u0, u1));
-                else
-                c = iso ? kmpc_rollout_cost_f32x2_col<true, true>(src, sref32, k, T, r, r1, cf, u0, u1)
-                        : (poly ? kmpc_rollout_cost_f32x2_col<true, false>(src, sref32, k, T, r, r1, cf, u0, u1)
-                                : kmpc_rollout_cost_f32x2_col<false, false>(src, sref32, k, T, r, r1, cf, u0, u1));
+                c = iso ? kmpc_rollout_cost_f32x2_test<true, true>(src, sref32, k, T, r, r1, test, u0, u1)
+                        : (poly ? kmpc_rollout_cost_f32x2_test<true, false>(src, sref32, k, T, r, r1, test, u0, u1)
+                                : kmpc_rollout_cost_f32x2_test<false, false>(src, sref32, k, T, r, r1, test, u0, u1));
                 cost_out[r] = c.x;
                 if (r1 != r) cost_out[r1] = c.y;
                 // the minimum over FREE rollouts only; the flags are not kept: the survivors are the FREE and the UNSURE rollouts at or below the threshold alike
@@ -1404,7 +1361,8 @@ static KmpcObs kmpc_obs_dev(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, bool filter, 
     else {
         o.g = GridDev{nullptr, 0, 0, 0, 0.0, 0.0, 0.0}; o.clear = nullptr; o.n_sub = n_sub; o.force64 = ctx->kmpc_mixed ? 0 : 1;
     }
-    o.obs = st ? ctx->stmpc_obs_cur : ctx->kmpc_obs_cur; o.M = st ? ctx->stmpc_obs_M : ctx->kmpc_obs_M; o.live = nullptr; o.n_live = 0;
+    const ObsState& os = st ? ctx->stmpc_obs : ctx->kmpc_obs;
+    o.obs = os.cur; o.M = os.M; o.live = nullptr; o.n_live = 0;
     return o;
 }
 
@@ -1440,7 +1398,7 @@ int launch_kmpc_shoot(f1p_ctx* ctx, const double* d_x0, const double* d_ref, con
                       double* d_best_cost, double* d_best_seq) {
     if (E <= 0) return F1P_OK;
     const size_t T1 = (size_t)cfg->horizon + 1;
-    if (ctx->kmpc_obs_cur) {                                          // (the caller checked E, the grid and the groups: kmpc_collision_check)
+    if (ctx->kmpc_obs.cur) {                                          // (the caller checked E, the grid and the groups: kmpc_collision_check)
         const size_t lds = sizeof(double) * (4 * T1 + 4) + sizeof(int) * 4 + sizeof(double) * 5 * F1P_KMPC_MAX_OBS + sizeof(int) * 4;
         hipLaunchKernelGGL(k_kmpc_shoot_obs, dim3(E), dim3(256), (lds + 15) & ~(size_t)15, ctx->stream, d_x0, d_ref, d_controls, E,
                            *cfg, kmpc_obs_dev(ctx, cfg, false), d_steer, d_speed, d_best_idx, d_best_cost, d_best_seq);
@@ -1548,7 +1506,7 @@ int launch_kmpc_plan_gen(f1p_ctx* ctx, const double* d_x0, const double* d_ref, 
     // the raceline / track plans follow f1p_kmpc_set_collision; a list of batch indices is f1p_stmpc_plan_batch's kinematic branch and
     // follows f1p_stmpc_set_collision, with its own count
     const bool collide = d_ids ? ctx->stmpc_collision : ctx->kmpc_collision;
-    const bool discs = d_ids ? ctx->stmpc_obs_cur != nullptr : ctx->kmpc_obs_cur != nullptr;   // f1p_kmpc_set_obstacles / f1p_stmpc_set_obstacles, likewise
+    const bool discs = (d_ids ? ctx->stmpc_obs : ctx->kmpc_obs).cur != nullptr;   // f1p_kmpc_set_obstacles / f1p_stmpc_set_obstacles, likewise
     if (discs) lds += 8 + (sizeof(double) + sizeof(float)) * 5 * F1P_KMPC_MAX_OBS + sizeof(int) * 4;
     lds = (lds + 15) & ~(size_t)15;
     if (lds > (size_t)ctx->prop.sharedMemPerBlock) return set_error(ctx, F1P_EINVAL, "horizon / n_rollouts need more LDS than a workgroup has: use fewer rollouts per plan");

@@ -202,59 +202,20 @@ __device__ __forceinline__ void stmpc_rollout_f32(const float* __restrict__ ce, 
 }
 
 // the same rollout with its controls GENERATED: one Philox4x32-10 call per pair of steps (SrcGenT::get2), nothing fetched but the step's
-// warm-start row (LDS, wave-uniform address).  An overload on the source type; R is unused.
-template <bool POLY, int NR, int QM>
+// warm-start row (LDS, wave-uniform address).  An overload on the source type; R is unused.  After every step the step's n_sub tested
+// points -- formed from the f32 states, relative to the ego with the map's axes (unsure<false>) -- are tested as `test` says (shoot_col.h):
+// ColTestNone: not at all, the plain filter; ColTestGrid: looked up in the clearance map (f1p_stmpc_set_collision, k_stmpc_filter_gen_col;
+// the position bound: DESIGN.md 5i); ColTestObs: compared with every live slot of the ego's LDS table at the point's own time, and looked
+// up as well while the occupancy test is on (f1p_stmpc_set_obstacles, k_stmpc_filter_gen_obs).
+// unsure = a point is near an occupied cell, off the image, NaN or not clear of a disc: the rollout is not proved FREE.
+template <bool POLY, int NR, int QM, typename Test>
 __device__ __forceinline__ void stmpc_rollout_f32(const SrcGenT<true>& ce, const float* sref8, const DynF32& k, int T, int R, const int (&rr)[NR],
-                                                      float delta0, float v0, float yr0, float beta0, float (&cost_out)[NR], bool (&trusted)[NR]) {
-#pragma clang fp contract(fast)
-    (void)R;
-    float x[NR], y[NR], delta[NR], v[NR], yaw[NR], yr[NR], beta[NR], cost[NR], pdv[NR], pa[NR];
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        x[i] = 0.f; y[i] = 0.f; delta[i] = delta0; v[i] = v0; yaw[i] = 0.f; yr[i] = yr0; beta[i] = beta0; cost[i] = 0.f; pdv[i] = 0.f; pa[i] = 0.f;
-        trusted[i] = true;
-    }
-    const float4* sr = reinterpret_cast<const float4*>(sref8);
-    for (int te = 0; te < T; te += 2) {
-        float c_dv[NR][2], c_a[NR][2];
-#pragma unroll
-        for (int i = 0; i < NR; ++i) ce.get2(te, T, rr[i], c_dv[i][0], c_a[i][0], c_dv[i][1], c_a[i][1]);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int t = te + h;
-            if (t < T) {
-                const float4 r0 = sr[2 * t], r1 = sr[2 * t + 1];
-#pragma unroll
-                for (int i = 0; i < NR; ++i) {
-                    float dv = __builtin_amdgcn_fmed3f(c_dv[i][h], -k.max_steer_v, k.max_steer_v);
-                    const float a = __builtin_amdgcn_fmed3f(c_a[i][h], -k.max_accel, k.max_accel);
-                    F1P_ST_F32_STEP(i)
-                }
-            }
-        }
-    }
-    const float4 r0 = sr[2 * T], r1 = sr[2 * T + 1];
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const float sv_[7] = {x[i], y[i], delta[i], v[i], yaw[i], yr[i], beta[i]}, rf_[7] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z};
-        float qs = 0.f;
-#pragma unroll
-        for (int j = 0; j < 7; ++j) if (QM & (1 << j)) { const float er = sv_[j] - rf_[j]; qs += k.qf[j] * er * er; }
-        cost_out[i] = cost[i] + qs;
-    }
-}
-
-// the generating rollout with the occupancy test's look-ups (k_stmpc_filter_gen_col): after every step the step's n_sub tested points --
-// formed from the f32 states, relative to the ego with the map's axes -- are looked up in the clearance map; unsure = one of them is near an
-// occupied cell, off the image or NaN, so the rollout is not proved free (shoot_col.h KmpcColF; the position bound: DESIGN.md 5i)
-template <bool POLY, int NR, int QM>
-__device__ __forceinline__ void stmpc_rollout_f32(const SrcGenT<true>& ce, const float* sref8, const DynF32& k, int T, int R, const int (&rr)[NR],
-                                                          float delta0, float v0, float yr0, float beta0, float (&cost_out)[NR], bool (&trusted)[NR],
-                                                          const KmpcColF& cf, bool (&unsure)[NR]
+                                                  float delta0, float v0, float yr0, float beta0, float (&cost_out)[NR], bool (&trusted)[NR],
+                                                  const Test& test, bool (&unsure)[NR]
 #ifdef F1P_ST_DBG_POS    // variant build (tools/stmpc_pos_error.py): the f32 positions after every step, [t][x | y] planes of pos_stride floats
-                                                          , float* pos_out, size_t pos_stride
+                                                  , float* pos_out, size_t pos_stride
 #endif
-                                                          ) {
+                                                  ) {
 #pragma clang fp contract(fast)
     (void)R;
     float x[NR], y[NR], delta[NR], v[NR], yaw[NR], yr[NR], beta[NR], cost[NR], pdv[NR], pa[NR];
@@ -263,6 +224,8 @@ __device__ __forceinline__ void stmpc_rollout_f32(const SrcGenT<true>& ce, const
         x[i] = 0.f; y[i] = 0.f; delta[i] = delta0; v[i] = v0; yaw[i] = 0.f; yr[i] = yr0; beta[i] = beta0; cost[i] = 0.f; pdv[i] = 0.f; pa[i] = 0.f;
         trusted[i] = true; unsure[i] = false;
     }
+    [[maybe_unused]] bool testing = true;                              // (the discs: every slot empty and no grid -> the plain filter, step by step)
+    if constexpr (std::is_same_v<Test, ColTestObs>) testing = test.of.grid | (test.of.n_live > 0);
     const float4* sr = reinterpret_cast<const float4*>(sref8);
     for (int te = 0; te < T; te += 2) {
         float c_dv[NR][2], c_a[NR][2];
@@ -277,79 +240,38 @@ __device__ __forceinline__ void stmpc_rollout_f32(const SrcGenT<true>& ce, const
                 for (int i = 0; i < NR; ++i) {
                     float dv = __builtin_amdgcn_fmed3f(c_dv[i][h], -k.max_steer_v, k.max_steer_v);
                     const float a = __builtin_amdgcn_fmed3f(c_a[i][h], -k.max_accel, k.max_accel);
-                    const float px = x[i], py = y[i];
+                    [[maybe_unused]] const float px = x[i], py = y[i];
                     F1P_ST_F32_STEP(i)
-                    for (int j = 1; j < cf.n_sub; ++j) {
-                        const float f = (float)j * cf.inv_nsub;
-                        unsure[i] |= cf.template unsure<false>(px + (x[i] - px) * f, py + (y[i] - py) * f);
+                    if constexpr (std::is_same_v<Test, ColTestGrid>) {          // j = 1 .. n_sub - 1, then p_{t+1} itself
+                        const KmpcColF& cf = test.cf;
+                        for (int j = 1; j < cf.n_sub; ++j) {
+                            const float f = (float)j * cf.inv_nsub;
+                            unsure[i] |= cf.template unsure<false>(px + (x[i] - px) * f, py + (y[i] - py) * f);
+                        }
+                        unsure[i] |= cf.template unsure<false>(x[i], y[i]);
                     }
-                    unsure[i] |= cf.template unsure<false>(x[i], y[i]);
-#ifdef F1P_ST_DBG_POS
-                    if (pos_out) { pos_out[((size_t)t * 2 + 0) * pos_stride + rr[i]] = x[i]; pos_out[((size_t)t * 2 + 1) * pos_stride + rr[i]] = y[i]; }
-#endif
-                }
-            }
-        }
-    }
-    const float4 r0 = sr[2 * T], r1 = sr[2 * T + 1];
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const float sv_[7] = {x[i], y[i], delta[i], v[i], yaw[i], yr[i], beta[i]}, rf_[7] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z};
-        float qs = 0.f;
-#pragma unroll
-        for (int j = 0; j < 7; ++j) if (QM & (1 << j)) { const float er = sv_[j] - rf_[j]; qs += k.qf[j] * er * er; }
-        cost_out[i] = cost[i] + qs;
-    }
-}
-
-// the generating rollout with the moving discs of f1p_stmpc_set_obstacles (k_stmpc_filter_gen_obs): every tested point is
-// compared with every live slot of the ego's LDS table at the point's own time, and looked up in the clearance map as well while the
-// occupancy test is on (of.grid); FREE needs both proofs at every point.  cf.n_sub / cf.inv_nsub are set with or without a grid.  Without
-// a live slot and without a grid nothing is tested: the plain filter, step by step.
-template <bool POLY, int NR, int QM>
-__device__ __forceinline__ void stmpc_rollout_f32(const SrcGenT<true>& ce, const float* sref8, const DynF32& k, int T, int R, const int (&rr)[NR],
-                                                          float delta0, float v0, float yr0, float beta0, float (&cost_out)[NR], bool (&trusted)[NR],
-                                                          const KmpcColF& cf, const KmpcObsF& of, bool (&unsure)[NR]) {
-#pragma clang fp contract(fast)
-    (void)R;
-    float x[NR], y[NR], delta[NR], v[NR], yaw[NR], yr[NR], beta[NR], cost[NR], pdv[NR], pa[NR];
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        x[i] = 0.f; y[i] = 0.f; delta[i] = delta0; v[i] = v0; yaw[i] = 0.f; yr[i] = yr0; beta[i] = beta0; cost[i] = 0.f; pdv[i] = 0.f; pa[i] = 0.f;
-        trusted[i] = true; unsure[i] = false;
-    }
-    const bool test = of.grid | (of.n_live > 0);
-    const float4* sr = reinterpret_cast<const float4*>(sref8);
-    for (int te = 0; te < T; te += 2) {
-        float c_dv[NR][2], c_a[NR][2];
-#pragma unroll
-        for (int i = 0; i < NR; ++i) ce.get2(te, T, rr[i], c_dv[i][0], c_a[i][0], c_dv[i][1], c_a[i][1]);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int t = te + h;
-            if (t < T) {
-                const float4 r0 = sr[2 * t], r1 = sr[2 * t + 1];
-#pragma unroll
-                for (int i = 0; i < NR; ++i) {
-                    float dv = __builtin_amdgcn_fmed3f(c_dv[i][h], -k.max_steer_v, k.max_steer_v);
-                    const float a = __builtin_amdgcn_fmed3f(c_a[i][h], -k.max_accel, k.max_accel);
-                    const float px = x[i], py = y[i];
-                    F1P_ST_F32_STEP(i)
-                    if (test) {
-                        for (int j = 1; j <= cf.n_sub; ++j) {
-                            const bool end = j == cf.n_sub;
-                            const float f = end ? 1.0f : (float)j * cf.inv_nsub;
-                            const float qx = end ? x[i] : px + (x[i] - px) * f, qy = end ? y[i] : py + (y[i] - py) * f;
-                            if (of.grid) unsure[i] |= cf.template unsure<false>(qx, qy);
-                            const float tau = ((float)t + f) * of.dt;
-                            for (int m = 0; m < of.n_live; ++m) {
-                                const float* o = of.live + 5 * m;
-                                const float cx = o[0] + o[2] * tau, cy = o[1] + o[3] * tau;
-                                const float dx = qx - cx, dy = qy - cy, d2 = dx * dx + dy * dy;
-                                unsure[i] |= !(d2 > o[4]);
+                    if constexpr (std::is_same_v<Test, ColTestObs>) {           // j = 1 .. n_sub, every point at its own time
+                        const KmpcColF& cf = test.cf;
+                        const KmpcObsF& of = test.of;
+                        if (testing) {
+                            for (int j = 1; j <= cf.n_sub; ++j) {
+                                const bool end = j == cf.n_sub;
+                                const float f = end ? 1.0f : (float)j * cf.inv_nsub;
+                                const float qx = end ? x[i] : px + (x[i] - px) * f, qy = end ? y[i] : py + (y[i] - py) * f;
+                                if (of.grid) unsure[i] |= cf.template unsure<false>(qx, qy);
+                                const float tau = ((float)t + f) * of.dt;
+                                for (int m = 0; m < of.n_live; ++m) {
+                                    const float* o = of.live + 5 * m;
+                                    const float cx = o[0] + o[2] * tau, cy = o[1] + o[3] * tau;
+                                    const float dx = qx - cx, dy = qy - cy, d2 = dx * dx + dy * dy;
+                                    unsure[i] |= !(d2 > o[4]);
+                                }
                             }
                         }
                     }
+#ifdef F1P_ST_DBG_POS
+                    if (pos_out) { pos_out[((size_t)t * 2 + 0) * pos_stride + rr[i]] = x[i]; pos_out[((size_t)t * 2 + 1) * pos_stride + rr[i]] = y[i]; }
+#endif
                 }
             }
         }
@@ -652,22 +574,14 @@ __global__ __launch_bounds__(256) void k_stmpc_filter_t(const double* __restrict
     constexpr bool COL = has_col<Col...>;
     constexpr bool OBS = has_obs<Col...>;                            // moving discs, with the grid (a bitmap) or without (null)
     [[maybe_unused]] double bxd = 0.0, byd = 0.0;
-    bool in_range;                                                   // workgroup-uniform
-    if constexpr (OBS) {
-        // without a grid the discs need no cell: their FREE threshold carries the filter's position bound itself (obs_compact)
+    if constexpr (COL) {
+        // the ego's cell (fp64) anchors the filter's cell coordinates; an ego without one is decided in fp64.  Without a grid (the discs
+        // alone: a null bitmap) there is no cell: the discs' FREE threshold carries the filter's position bound itself (obs_compact)
         const KmpcCol& c_ = col_of(col...);
-        if (c_.g.bits) { bxd = (sx - c_.g.ox) * c_.g.inv_res; byd = (sy - c_.g.oy) * c_.g.inv_res; }
-        in_range = fabs(syaw) <= 1.0e4 && fabs(max_steer_d) <= 1.0e4 && fabs(sbeta) <= 100.0 && fabs(sdelta) <= 100.0 &&
-                   fabs(bxd) < 1.0e6 && fabs(byd) < 1.0e6;
-    } else if constexpr (COL) {
-        // the ego's cell (fp64) anchors the filter's cell coordinates; an ego without one is decided in fp64
-        const KmpcCol& c_ = col_of(col...);
-        bxd = (sx - c_.g.ox) * c_.g.inv_res; byd = (sy - c_.g.oy) * c_.g.inv_res;
-        in_range = fabs(syaw) <= 1.0e4 && fabs(max_steer_d) <= 1.0e4 && fabs(sbeta) <= 100.0 && fabs(sdelta) <= 100.0 &&
-                   fabs(bxd) < 1.0e6 && fabs(byd) < 1.0e6;
-    } else {
-        in_range = fabs(syaw) <= 1.0e4 && fabs(max_steer_d) <= 1.0e4 && fabs(sbeta) <= 100.0 && fabs(sdelta) <= 100.0;
+        if (!OBS || c_.g.bits) { bxd = (sx - c_.g.ox) * c_.g.inv_res; byd = (sy - c_.g.oy) * c_.g.inv_res; }
     }
+    const bool in_range = fabs(syaw) <= 1.0e4 && fabs(max_steer_d) <= 1.0e4 && fabs(sbeta) <= 100.0 && fabs(sdelta) <= 100.0 &&
+                          (!COL || (fabs(bxd) < 1.0e6 && fabs(byd) < 1.0e6));   // workgroup-uniform
     if (!in_range) { if (tid == 0) nlist[e] = -1; return; }
     int bad_ref = 0;                                                 // a non-finite reference in an UNWEIGHTED row makes every fp64 cost NaN (0 * NaN): fp64 decides
     for (int q = tid; q < 7 * (T + 1); q += blockDim.x) {
@@ -707,24 +621,17 @@ __global__ __launch_bounds__(256) void k_stmpc_filter_t(const double* __restrict
     double s0d, c0d;
     sincos_core(syaw, &s0d, &c0d);
     kk.c0 = (float)c0d; kk.s0 = (float)s0d;
-    [[maybe_unused]] KmpcColF cf;                                    // (the filter's positions are relative to the ego with the map's axes: unsure<false>)
-    [[maybe_unused]] KmpcObsF of;
+    // the filter's test of a step's points (shoot_col.h): none, the clearance look-ups, or the look-ups and the discs
+    [[maybe_unused]] std::conditional_t<OBS, ColTestObs, std::conditional_t<COL, ColTestGrid, ColTestNone>> test;
     if constexpr (OBS) {
         const auto& o_ = col_of(col...);
+        KmpcObsF& of = test.of;
         of.live = olive32; of.n_live = __builtin_amdgcn_readfirstlane(on2[0]); of.grid = o_.g.bits != nullptr; of.dt = kf.dt;
         // the refinement's copy of the table (it cannot compact per workgroup: its items come from many egos)
         if (tid < 5 * of.n_live) o_.tab[(size_t)e * 5 * F1P_KMPC_MAX_OBS + tid] = olive[tid];
         if (tid == 0) o_.ntab[e] = on2[0] | (on2[1] << 8);
     }
-    if constexpr (COL) {
-        const KmpcCol& c_ = col_of(col...);
-        const double ibx = __builtin_floor(bxd), iby = __builtin_floor(byd);
-        cf.clear = c_.clear; cf.wwords = c_.g.wwords; cf.n_sub = c_.n_sub; cf.inv_nsub = 1.0f / (float)c_.n_sub;
-        cf.ibx = __builtin_amdgcn_readfirstlane((int)ibx); cf.iby = __builtin_amdgcn_readfirstlane((int)iby);
-        cf.bx = (float)(bxd - ibx); cf.by = (float)(byd - iby);
-        cf.lox = (float)-cf.ibx; cf.hix = (float)(c_.g.w - cf.ibx); cf.loy = (float)-cf.iby; cf.hiy = (float)(c_.g.h - cf.iby);
-        cf.inv_res = (float)c_.g.inv_res; cf.c0 = 1.0f; cf.s0 = 0.0f;
-    }
+    if constexpr (COL) test.cf = col_filter(col_of(col...), bxd, byd, true, 1.0f, 0.0f);   // (the filter's positions are relative to the ego with the map's axes)
     // the odd polynomial of tan is good for |delta| <= 0.45: every later delta is clamped to max_steer, but step 0 evaluates tan(delta0)
     // UNCLAMPED (dyn_step does, like the reference) -- an out-of-range initial steering state takes the sin / cos path (workgroup-uniform)
     const bool poly = kf.max_steer <= 0.45f && fabs(sdelta) <= 0.45;
@@ -735,17 +642,14 @@ __global__ __launch_bounds__(256) void k_stmpc_filter_t(const double* __restrict
 #pragma unroll
         for (int i = 0; i < NR; ++i) rr[i] = rb + i * (int)blockDim.x < R ? rb + i * (int)blockDim.x : rb;   // past the end: a shadow of the first, not stored
         [[maybe_unused]] bool unsure[NR];                            // a tested point near an occupied cell, off the image or NaN: not FREE
-        if constexpr (OBS) {
-            if (poly) stmpc_rollout_f32<true, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted, cf, of, unsure);
-            else stmpc_rollout_f32<false, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted, cf, of, unsure);
-        } else if constexpr (COL) {
+        if constexpr (st_gen<Ctl>) {
 #ifdef F1P_ST_DBG_POS    // variant build: dbg_cost32 is [1 + 2 T][E][R] -- the costs, then the f32 (x, y) after every step (tools/stmpc_pos_error.py)
-#define F1P_ST_POS_ARGS , dbg_cost32 ? dbg_cost32 + ((size_t)E + e) * R : nullptr, (size_t)E * R
+#define F1P_ST_POS_ARGS , COL && !OBS && dbg_cost32 ? dbg_cost32 + ((size_t)E + e) * R : nullptr, (size_t)E * R
 #else
 #define F1P_ST_POS_ARGS
 #endif
-            if (poly) stmpc_rollout_f32<true, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted, cf, unsure F1P_ST_POS_ARGS);
-            else stmpc_rollout_f32<false, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted, cf, unsure F1P_ST_POS_ARGS);
+            if (poly) stmpc_rollout_f32<true, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted, test, unsure F1P_ST_POS_ARGS);
+            else stmpc_rollout_f32<false, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted, test, unsure F1P_ST_POS_ARGS);
 #undef F1P_ST_POS_ARGS
         } else {
             if (poly) stmpc_rollout_f32<true, NR, QM>(ce, sref32, kk, T, R, rr, (float)sdelta, (float)sv, (float)syr, (float)sbeta, c, trusted);
@@ -1322,7 +1226,7 @@ static int stmpc_shoot_any(f1p_ctx* ctx, const double* d_x0, const double* d_ref
                            double* d_steer, double* d_speed, int32_t* d_best_idx, double* d_best_cost, double* d_best_seq) {
     if (E <= 0) return F1P_OK;
     const size_t T1 = (size_t)cfg->horizon + 1;
-    const bool discs = ctx->stmpc_obs_cur != nullptr;                      // f1p_stmpc_set_obstacles (the caller checked E: stmpc_collision_check)
+    const bool discs = ctx->stmpc_obs.cur != nullptr;                      // f1p_stmpc_set_obstacles (the caller checked E: stmpc_collision_check)
     const size_t lds = sizeof(double) * (7 * T1 + 4) + sizeof(int) * 4 + (discs ? F1P_ST_OBS_LDS64 : 0);   // the plain-fp64 kernel's, and the decision's
     // the plain-fp64 evaluation, over the control source and the optional occupancy test
     auto shoot = [&](const char* what, auto... col) {
@@ -1339,7 +1243,7 @@ static int stmpc_shoot_any(f1p_ctx* ctx, const double* d_x0, const double* d_ref
         StObs ob;
         ob.g = ctx->stmpc_collision ? grid_dev(ctx) : GridDev{nullptr, 0, 0, 0, 0.0, 0.0, 0.0};
         ob.clear = nullptr; ob.n_sub = ctx->stmpc_col_nsub; ob.force64 = 1;
-        ob.obs = ctx->stmpc_obs_cur; ob.M = ctx->stmpc_obs_M; ob.live = nullptr; ob.n_live = 0;
+        ob.obs = ctx->stmpc_obs.cur; ob.M = ctx->stmpc_obs.M; ob.live = nullptr; ob.n_live = 0;
         ob.dt = cfg->dt; ob.max_speed = cfg->max_speed; ob.min_speed = cfg->min_speed; ob.pos_err = st_pos_err_bound(cfg);
         ob.ids = gen ? gen->ids : nullptr; ob.tab = nullptr; ob.ntab = nullptr; ob.nan_all = 0;
         if (lds > (size_t)ctx->prop.sharedMemPerBlock) return set_error(ctx, F1P_EINVAL, "stmpc: the horizon needs more LDS than a workgroup has");

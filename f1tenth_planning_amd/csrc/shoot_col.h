@@ -1,5 +1,9 @@
-// shoot_col.h -- the occupancy test of the shooting MPCs' rollouts (f1p_kmpc_set_collision, f1p_stmpc_set_collision):
-// one struct, one point test and one segment rule for k_kmpc.hip and k_stmpc.hip.
+// shoot_col.h -- the rollout tests of the shooting MPCs (f1p_kmpc_set_collision / _set_obstacles, f1p_stmpc_set_collision / _set_obstacles;
+// DESIGN.md 5h - 5k), once for k_kmpc.hip and k_stmpc.hip.  fp64 side: KmpcCol (the occupancy bitmap, its point test and segment rule), KmpcObs
+// (the moving discs on top of it), col_seg, obs_compact.  f32 filters' side: KmpcColF (the clearance look-up) and its set-up col_filter,
+// KmpcObsF (the discs' f32 table), the packed-pair type f1p_f2, and ColTestNone / ColTestGrid / ColTestObs: what a filter's rollout tests
+// after every step, the type both planners' tested f32 rollouts are templated on (ColTestNone: k_stmpc.hip only, whose plain generating
+// rollout has the tested ones' shape; k_kmpc.hip's plain rollout runs in chunks and stays a function of its own).
 #pragma once
 #include <type_traits>
 #include "f1p_device.h"
@@ -35,7 +39,7 @@ template <typename A> __device__ __forceinline__ const A& col_of(const A& c) { r
 template <typename A, typename B, typename... X> __device__ __forceinline__ const auto& col_of(const A&, const B& b, const X&... x) { return col_of(b, x...); }
 
 // the f32 filters' side of the test: the tested points looked up in the CLEARANCE map, cell coordinates relative to the ego's cell
-// (k_kmpc.hip kmpc_rollout_cost_f32x2_col, k_stmpc.hip stmpc_rollout_f32 with `cf`)
+// (used through ColTestGrid / ColTestObs below)
 #define F1P_K4_CLEAR_CELLS 2.0
 #define F1P_K4_POS_ERR_REL 1.0e-4
 struct KmpcColF {
@@ -56,6 +60,22 @@ struct KmpcColF {
 #endif
     }
 };
+// the filter's view of `col` for an ego whose position is cell (bxd, byd) of the map (fp64, fractional); ok: the ego has a cell (else the
+// anchor is cell 0 and the launch's `in_range` keeps the filter from running).  (c0, s0): the rotation from the filter's frame to the
+// map's axes (unsure<ISO = true>)
+__device__ __forceinline__ KmpcColF col_filter(const KmpcCol& col, double bxd, double byd, bool ok, float c0, float s0) {
+    KmpcColF cf;
+    const double ibx = ok ? __builtin_floor(bxd) : 0.0, iby = ok ? __builtin_floor(byd) : 0.0;
+    cf.clear = col.clear; cf.wwords = col.g.wwords; cf.n_sub = col.n_sub; cf.inv_nsub = 1.0f / (float)col.n_sub;
+    cf.ibx = __builtin_amdgcn_readfirstlane((int)ibx); cf.iby = __builtin_amdgcn_readfirstlane((int)iby);
+    cf.bx = (float)(bxd - ibx); cf.by = (float)(byd - iby);
+    cf.lox = (float)-cf.ibx; cf.hix = (float)(col.g.w - cf.ibx); cf.loy = (float)-cf.iby; cf.hiy = (float)(col.g.h - cf.iby);
+    cf.inv_res = (float)col.g.inv_res; cf.c0 = c0; cf.s0 = s0;
+    return cf;
+}
+
+// two rollouts in the halves of one packed-f32 value (k_kmpc.hip's filter)
+typedef float f1p_f2 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------------
 // Moving obstacles (f1p_kmpc_set_obstacles): discs (x, y, vx, vy, r) per ego, map frame, at constant velocity.  The tested
@@ -146,12 +166,20 @@ __device__ __forceinline__ void obs_compact(const KmpcObs& ob, int e, double sx,
 }
 
 // the f32 filter's side: a point is FREE against a slot only when its f32 distance from the f32 centre exceeds r + eps
-// (k_kmpc.hip kmpc_rollout_cost_f32x2_obs, k_stmpc.hip stmpc_rollout_f32 with `of`)
+// (used through ColTestObs below)
 struct KmpcObsF {
     const float* live;                // LDS [n_live][5] (obs_compact)
     int n_live;
     int grid;                         // the occupancy test too (KmpcColF)
     float dt;
 };
+
+// What an f32 filter's rollout tests after every step (k_kmpc.hip kmpc_rollout_cost_f32x2_test, k_stmpc.hip stmpc_rollout_f32): nothing,
+// the step's points in the clearance map, or the points against the discs and -- while of.grid -- in the map too.  The rollouts are
+// templates over these; the two loops over a step's points stay in the rollouts' own text, once per value type (float / f1p_f2): handed
+// to a function of these structs they come out with other instructions (LABNOTES.md R15).
+struct ColTestNone {};
+struct ColTestGrid { KmpcColF cf; };
+struct ColTestObs { KmpcColF cf; KmpcObsF of; };       // (cf.n_sub / cf.inv_nsub are set with or without a grid)
 
 }  // namespace f1p

@@ -2,7 +2,7 @@
 the oracle and the numpy disc rule (tests/stmpc_obstacle_ref.py), mixed against plain fp64 (bit for bit, all three regimes of the filter,
 with and without the grid), streamed against generated controls, nothing live against nothing set, both rules together, plan_batch with
 both branches (and permuted), a chain with moving discs, independence of the batch, the borrowed device array, the hand cases on the rule,
-the two obstacle states kept apart, the rejections and the class."""
+the two obstacle states kept apart (also when one of them is cleared), the rejections and the class."""
 import warnings
 
 import numpy as np
@@ -468,6 +468,33 @@ def test_the_two_obstacle_states_do_not_reach_each_other(ctx, orc):
     kin = off["branch"] == 0
     assert (son["best_idx"][kin] != off["best_idx"][kin]).any() and (son["best_idx"][~kin] != off["best_idx"][~kin]).any()
     _same(ctx.kmpc_plan(xk, kcfg, ksmp), koff, keys=KEYS, msg="stmpc obstacles, kmpc plan")
+
+
+def test_clearing_one_obstacle_state_leaves_the_other_in_force(ctx, orc):
+    """the two states are set and cleared by one function: kmpc discs for (E 2, M 1), OTHER discs for the dynamic MPC with (E 3, M 2), the
+    kmpc ones cleared -- the stmpc plan is the expected one with its own discs and its own shape, the kmpc plan the unobstructed one"""
+    T, R, n_sub = 4, 64, 2
+    s = dict(_scene(orc, "t", 3, 40))                                    # (the traffic scene needs a longer horizon; only its egos and course are used)
+    s["ref"] = O.oracle_ref(orc, s["x0"], s["wp"], T)
+    cfg, kcfg = _abi.stmpc_cfg(horizon=T, n_rollouts=R), _abi.kmpc_cfg(horizon=T, n_rollouts=R)
+    ksmp = _abi.kmpc_sampler(seed=SEED, call=CALL, use_warm=False, sigma_accel=1.5, sigma_steer=0.15)
+    _install(ctx, s, grid=False)
+    ctx.stmpc_set_collision(False, n_sub)
+    xk = O.xy4(s["x0"][:2])
+    obs = np.empty((3, 2, 5)); obs[:] = O.EMPTY
+    obs[0, 1] = (s["x0"][0, 0], s["x0"][0, 1], 0.0, 0.0, 0.5)            # parked on ego 0: every rollout of it is blocked
+    obs[2, 0] = (s["x0"][2, 0] + 50.0, s["x0"][2, 1], 0.0, 0.0, 0.3)     # out of ego 2's reach
+    kobs = np.array([[(xk[0, 0], xk[0, 1], 0.0, 0.0, 0.5)], [O.EMPTY]])  # [2, 1, 5]: parked on the kinematic ego 0
+    koff = ctx.kmpc_plan(xk, kcfg, ksmp)
+    kmpc_set_obstacles(ctx, kobs)
+    kon = ctx.kmpc_plan(xk, kcfg, ksmp)
+    assert kon["best_idx"][0] == -1 and koff["best_idx"][0] >= 0
+    stmpc_set_obstacles(ctx, obs)
+    kmpc_set_obstacles(ctx, None)
+    want = O.expected(orc, s["x0"], s["ref"], cfg, obs, n_sub, SEED, CALL, warm=O.warm_start(3, T))
+    assert want["all_blocked"][0] and not want["all_blocked"][1:].any()
+    _check_against(_plan(ctx, s["x0"], s["ref"], cfg, O.warm_start(3, T)), want)
+    _same(ctx.kmpc_plan(xk, kcfg, ksmp), koff, keys=KEYS, msg="kmpc obstacles cleared")
 
 
 def test_the_rejections(ctx, orc):
