@@ -233,6 +233,8 @@ PROTOTYPES = {
     "f1p_lattice_step_tracks_batch": (C.c_int, [_P, _P, _P, _I, C.POINTER(LatticeCfg), _P, _P, _P, _I]),
     "f1p_lattice_set_mode": (C.c_int, [_P, _I, _P, _P]),
     "f1p_lattice_set_split": (C.c_int, [_P, _I]),
+    "f1p_lattice_set_obstacles": (C.c_int, [_P, _P, _P, _I, _I]),
+    "f1p_lattice_set_obstacles_dev": (C.c_int, [_P, _P, _P, _I, _I]),
     "f1p_lattice_set_clearance": (C.c_int, [_P, _I]),
     "f1p_lattice_set_pipeline": (C.c_int, [_P, _I]),
     "f1p_lattice_set_audit": (C.c_int, [_P, _I, _I]),

@@ -170,6 +170,26 @@ def kin_cfg_struct(c, n_rollouts=None):
                          q=_diag(c.Qk), qf=_diag(c.Qfk), r=_diag(c.Rk), rd=_diag(c.Rdk))
 
 
+def take_obstacles(planner):
+    """the attribute `obstacles` of a planner: the next plan / plan_batch call TAKES it -- None again afterwards, also when the call raises"""
+    obstacles, planner.obstacles = planner.obstacles, None
+    return obstacles
+
+
+def check_obstacle_shape(obstacles, E, single=False):
+    """obstacles as fp64 [E, M, 5] with 1 <= M <= 16; ValueError before anything touches the GPU.  single: plan()'s [M, 5] for its one ego"""
+    o = np.ascontiguousarray(obstacles, dtype=np.float64)
+    if single:
+        if o.ndim != 2:
+            raise ValueError("obstacles must be [M, 5] = (x, y, vx, vy, r)")
+        o = o[None]
+    if o.ndim != 3 or o.shape[0] != E or o.shape[2] != 5 or o.shape[1] < 1:
+        raise ValueError(f"obstacles must be [E={E}, M, 5] = (x, y, vx, vy, r) with 1 <= M <= 16")
+    if o.shape[1] > 16:
+        raise ValueError("at most 16 obstacles per ego (M <= 16)")
+    return o
+
+
 class MPCPlanner(OccupancyMap, Planner):
     """Base of KMPCPlanner and STMPCPlanner.  A class names its mpc_config's QP weights and COLLISION substep fields."""
     _QP_WEIGHTS = ()                       # ((mpc_config field, size), ...)
@@ -188,8 +208,7 @@ class MPCPlanner(OccupancyMap, Planner):
     # the attribute `obstacles` (moving discs): the next plan / plan_batch call TAKES it -- None again afterwards, also
     # when the call raises -- so obstacles are given per call, as a keyword argument would be
     def _take_obstacles(self):
-        obstacles, self.obstacles = self.obstacles, None
-        return obstacles
+        return take_obstacles(self)
 
     def _check_obstacles(self, obstacles, E, single=False):
         """-> None or obstacles as fp64 [E, M, 5]; ValueError before anything touches the GPU.  single: plan()'s [M, 5] for its one ego"""
@@ -198,15 +217,7 @@ class MPCPlanner(OccupancyMap, Planner):
         c = self.config
         if c.SOLVER == "qp":
             raise ValueError("obstacles are tested on the shooting solver's rollouts; SOLVER='qp' takes none")
-        o = np.ascontiguousarray(obstacles, dtype=np.float64)
-        if single:
-            if o.ndim != 2:
-                raise ValueError("obstacles must be [M, 5] = (x, y, vx, vy, r)")
-            o = o[None]
-        if o.ndim != 3 or o.shape[0] != E or o.shape[2] != 5 or o.shape[1] < 1:
-            raise ValueError(f"obstacles must be [E={E}, M, 5] = (x, y, vx, vy, r) with 1 <= M <= 16")
-        if o.shape[1] > 16:
-            raise ValueError("at most 16 obstacles per ego (M <= 16)")
+        o = check_obstacle_shape(obstacles, E, single)
         for name in self._SUBSTEPS:
             if not 1 <= int(getattr(c, name)) <= 16:
                 raise ValueError(f"{name} must be in [1, 16]")

@@ -164,6 +164,15 @@ struct f1p_ctx {
     int32_t* d_dbg_lat_state = nullptr;// [E][C] filter states
     int32_t* d_dbg_lat_pass = nullptr; // [E][4] station-pass statistics of k_lattice_filter3 (f1p_lattice_debug_pass), or null
 
+    // moving discs of the lattice planner (f1p_lattice_set_obstacles): the slots [E][M][5] and the paces [E], the context's own copies
+    // or the caller's device arrays; per-ego arrays are indexed by the ABSOLUTE ego, so a slice of a large batch and the audit's window plan
+    // with lat_obs_e0 set to their first ego
+    ObsState lat_obs;
+    double* d_lat_pace = nullptr; size_t lat_pace_bytes = 0;
+    const double* lat_pace_cur = nullptr;
+    int lat_obs_e0 = 0;
+    char* d_lat_obs_xf = nullptr; size_t lat_obs_xf_bytes = 0;   // mixed schedule: transformed live slots [E][16][5] fp64 | live counts [E] (k_lattice_filter3 -> k_lattice_refine)
+
     // closed-loop mode (f1p_lattice_set_closed_loop): the heading column of every plan's winners stays on the device and is the next
     // plan's prev_theta (get_similarity_cost's previous path, lattice_planner.py:287-296) -- two buffers used alternately
     bool lattice_closed_loop = false;

@@ -47,6 +47,57 @@ static int validate_lattice(f1p_ctx* ctx, const f1p_lattice_cfg* cfg, int E, boo
     return F1P_OK;
 }
 
+// f1p_lattice_set_obstacles' preconditions, checked by every entry point that plans: the batch size the discs were set for, whole egos
+static int lattice_obs_check(f1p_ctx* ctx, const f1p_lattice_cfg* cfg, int E) {
+    if (!ctx->lat_obs.cur) return F1P_OK;
+    if (E != ctx->lat_obs.E)
+        return set_error(ctx, F1P_ESTATE, "lattice obstacles were set for " + std::to_string(ctx->lat_obs.E) + " egos, this plan has " + std::to_string(E) + ": set them again or clear them (f1p_lattice_set_obstacles)");
+    if (cfg->cand_count > 0) return set_error(ctx, F1P_ESTATE, "lattice obstacles are set and cover whole egos: a candidate shard (cfg.cand_count > 0) is not tested, clear them first");
+    return F1P_OK;
+}
+
+// a slice of a batch (or the audit's window) plans with the per-ego obstacle arrays offset to its first ego; back to 0 on every way out
+struct LatObsSlice {
+    f1p_ctx* c;
+    explicit LatObsSlice(f1p_ctx* ctx, size_t e0) : c(ctx) { c->lat_obs_e0 = (int)e0; }
+    ~LatObsSlice() { c->lat_obs_e0 = 0; }
+};
+
+int f1p_lattice_set_obstacles(f1p_ctx* ctx, const double* obs, const double* pace, int32_t E, int32_t M) {
+    F1P_ENTER(ctx);
+    if (!obs || M == 0) { ctx->lat_pace_cur = nullptr; return set_obstacles(ctx, ctx->lat_obs, "lattice", false, nullptr, 0, 0, false); }
+    if (!pace) return set_error(ctx, F1P_EINVAL, "lattice obstacles: pace is NULL");
+    if (ctx->lattice_split > 0) return set_error(ctx, F1P_ESTATE, "lattice obstacle test runs one workgroup per ego: f1p_lattice_set_split(0)");
+    int rc = set_obstacles(ctx, ctx->lat_obs, "lattice", false, obs, E, M, false);
+    if (rc) return rc;
+    const size_t bytes = sizeof(double) * (size_t)E;
+    auto fail = [&]() { ctx->lat_obs.cur = nullptr; ctx->lat_obs.E = 0; ctx->lat_obs.M = 0; ctx->lat_pace_cur = nullptr; };
+    if (bytes > ctx->lat_pace_bytes) {
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess) { fail(); return check_hip(ctx, hipGetLastError(), "hipStreamSynchronize"); }
+        if (ctx->d_lat_pace) (void)hipFree(ctx->d_lat_pace);
+        ctx->d_lat_pace = nullptr; ctx->lat_pace_bytes = 0;
+        const hipError_t er = hipMalloc((void**)&ctx->d_lat_pace, bytes);
+        if (er != hipSuccess) { fail(); return check_hip(ctx, er, "hipMalloc (lattice paces)"); }
+        ctx->lat_pace_bytes = bytes;
+    }
+    hipError_t er = hipMemcpyAsync(ctx->d_lat_pace, pace, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (er == hipSuccess) er = hipStreamSynchronize(ctx->stream);
+    if (er != hipSuccess) { fail(); return check_hip(ctx, er, "copy of the lattice paces"); }
+    ctx->lat_pace_cur = ctx->d_lat_pace;
+    return F1P_OK;
+}
+
+int f1p_lattice_set_obstacles_dev(f1p_ctx* ctx, const double* d_obs, const double* d_pace, int32_t E, int32_t M) {
+    F1P_ENTER(ctx);
+    if (!d_obs || M == 0) { ctx->lat_pace_cur = nullptr; return set_obstacles(ctx, ctx->lat_obs, "lattice", false, nullptr, 0, 0, true); }
+    if (!d_pace) return set_error(ctx, F1P_EINVAL, "lattice obstacles: pace is NULL");
+    if (ctx->lattice_split > 0) return set_error(ctx, F1P_ESTATE, "lattice obstacle test runs one workgroup per ego: f1p_lattice_set_split(0)");
+    const int rc = set_obstacles(ctx, ctx->lat_obs, "lattice", false, d_obs, E, M, true);
+    if (rc) return rc;
+    ctx->lat_pace_cur = d_pace;
+    return F1P_OK;
+}
+
 void f1p_lattice_cfg_default(f1p_lattice_cfg* cfg) {
     if (!cfg) return;
     memset(cfg, 0, sizeof(*cfg));
@@ -129,6 +180,7 @@ static int lattice_plan_dev_cl(f1p_ctx* ctx, const double* d_poses, const double
     // them and fail in hipMalloc instead of returning F1P_EINVAL); lattice_plan_dev_impl validates again, with the output pointers
     if (const int rcv = validate_lattice(ctx, cfg, E, d_goals == nullptr, true, tracks)) return rcv;
     if (tracks && E > 0 && !d_track_id) return set_error(ctx, F1P_EINVAL, "track_id is NULL");
+    if (const int rco = lattice_obs_check(ctx, cfg, E)) return rco;
     if (cfg && E > 0 && cfg->n_stations >= 2) {
         const int rc0 = cl_begin(ctx, d_prev_theta, E, cfg->n_stations, cfg->cand_count == 0, &cl);
         if (rc0) return rc0;
@@ -171,6 +223,7 @@ int f1p_lattice_emit_dev(f1p_ctx* ctx, const double* d_poses, const double* d_go
     F1P_ENTER(ctx);
     int rc = validate_lattice(ctx, cfg, E, d_goals == nullptr, E == 0 || (d_poses && d_cand_idx && d_steer && d_speed));
     if (rc) return rc;
+    if (ctx->lat_obs.cur) return set_error(ctx, F1P_ESTATE, "lattice obstacles are set: the emit half of a sharded plan is not tested against them, clear them first (f1p_lattice_set_obstacles)");
     ClosedLoop cl;                                                 // the emitted winners are this plan's previous path for the next one
     if (E > 0 && (rc = cl_begin(ctx, nullptr, E, cfg->n_stations, true, &cl))) return rc;
     rc = launch_lattice(ctx, LATTICE_EMIT, d_poses, d_goals, nullptr, E, cfg, d_cand_idx, d_cand_cost, d_steer, d_speed,
@@ -207,6 +260,7 @@ static int lattice_plan_batch_impl(f1p_ctx* ctx, const double* poses, const doub
     int rc = validate_lattice(ctx, cfg, E, goals == nullptr, E == 0 || (poses && best_idx && ((cfg && cfg->cand_count > 0) || (steer && speed))), tracks);
     if (rc) return rc;
     if (tracks && E > 0 && !track_id) return set_error(ctx, F1P_EINVAL, "track_id is NULL");
+    if ((rc = lattice_obs_check(ctx, cfg, E))) return rc;
     if (cfg->cand_count > 0 && (steer || speed || status || best_traj))
         return set_error(ctx, F1P_EINVAL, "a candidate shard (cfg.cand_count > 0) only evaluates: it produces best_idx, best_cost and near_idx; "
                                           "pass NULL for steer / speed / status / best_traj and emit the global winner with f1p_lattice_emit_dev");
@@ -280,6 +334,7 @@ static int lattice_plan_batch_impl(f1p_ctx* ctx, const double* poses, const doub
     ctx->traj_dst_host = zero_copy_traj;
     double* d_ac = s.out(all_cost, e * C); double* d_at = s.out(all_traj, e * C * S * 4);
     auto plan = [&](size_t e0, size_t n) {
+        LatObsSlice obs_slice(ctx, e0);                             // (the moving discs' per-ego arrays: from this slice's first ego)
         double* bt64 = nullptr; float* bt32 = nullptr;
         if (d_bt) { if (F32) bt32 = reinterpret_cast<float*>(d_bt) + e0 * S * 4; else bt64 = reinterpret_cast<double*>(d_bt) + e0 * S * 4; }
         return lattice_plan_dev_impl(ctx, d_poses + 4 * e0, d_goals ? d_goals + e0 * C * 3 : nullptr, d_prev ? d_prev + e0 * S : nullptr,
@@ -376,6 +431,7 @@ static int lattice_step_impl(f1p_ctx* ctx, const double* poses, int32_t E, const
     if (rc) return rc;
     if (cfg->cand_count > 0) return set_error(ctx, F1P_EINVAL, "f1p_lattice_step_batch plans whole egos: cfg.cand_count must be 0");
     if (tracks && E > 0 && !track_id) return set_error(ctx, F1P_EINVAL, "track_id is NULL");
+    if ((rc = lattice_obs_check(ctx, cfg, E))) return rc;
     if (E == 0) return F1P_OK;
     const int S = cfg->n_stations;
     const size_t e = (size_t)E;
@@ -463,6 +519,7 @@ int f1p_lattice_set_mode(f1p_ctx* ctx, int32_t mixed, float* d_cost32, int32_t* 
 int f1p_lattice_set_split(f1p_ctx* ctx, int32_t groups) {
     if (!ctx) return F1P_EINVAL;
     if (groups < 0 || groups > 16) return set_error(ctx, F1P_EINVAL, "groups must be in [0, 16]");
+    if (groups > 0 && ctx->lat_obs.cur) return set_error(ctx, F1P_ESTATE, "lattice obstacles are set and run one workgroup per ego: clear them first (f1p_lattice_set_obstacles)");
     ctx->lattice_split = groups;
     return F1P_OK;
 }

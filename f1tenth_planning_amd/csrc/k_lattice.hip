@@ -65,9 +65,12 @@ __device__ __forceinline__ bool split_merge(const LatticeArgs& a, int e, int g, 
 // (round 6: the materialised clothoid instantiation with the footprint is held to TWO waves per SIMD -- at three it carried 23 spilled VGPRs / 104 B of scratch;
 // spill-free it is 1 % faster, tools/time_mat_footprint.py 0.2373 -> 0.2349 ms at 1024 egos.  The cubic one, 12 spills at three waves, measured 4 % SLOWER at two and stays.)
 // TRK = a track plan (LatticeArgs::track_id): the workgroup's ego plans along its own track of the set; the other instantiations keep their code.
-template <bool STAGING, int GEN, bool PRUNE = false, bool FOOT = false, bool TRK = false>
-__global__ __launch_bounds__(256, (STAGING && GEN != F1P_GEN_CLOTHOID && !FOOT) ? F1P_K3_WAVES_STAGE2 : ((STAGING && FOOT && GEN == F1P_GEN_CLOTHOID) ? 2 : ((STAGING || FOOT) ? F1P_K3_WAVES_STAGE : F1P_K3_WAVES))) void k_lattice(LatticeArgs a, f1p_lattice_cfg cfg) {
+// OB = LatObs (f1p_lattice_set_obstacles: one more kernel argument, the moving discs) or nothing: the instantiations without obstacles keep their
+// signature and their code.  This kernel's disc test is the DEFINITION the mixed schedule has to equal bit for bit.
+template <bool STAGING, int GEN, bool PRUNE = false, bool FOOT = false, bool TRK = false, typename... OB>
+__global__ __launch_bounds__(256, (STAGING && GEN != F1P_GEN_CLOTHOID && !FOOT) ? F1P_K3_WAVES_STAGE2 : ((STAGING && FOOT && GEN == F1P_GEN_CLOTHOID) ? 2 : ((STAGING || FOOT) ? F1P_K3_WAVES_STAGE : F1P_K3_WAVES))) void k_lattice(LatticeArgs a, f1p_lattice_cfg cfg, OB... obx) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
+    constexpr bool OBS = sizeof...(OB) > 0;
     // ---- LDS carve-up (all offsets multiples of 8) -------------------------------------------------
     double* red_d = reinterpret_cast<double*>(lds_raw);          // [4]
     double* cen_x = red_d + 4;                                   // [64]
@@ -178,6 +181,24 @@ __global__ __launch_bounds__(256, (STAGING && GEN != F1P_GEN_CLOTHOID && !FOOT) 
     }
     __syncthreads();
 
+    // ---- 3'. moving discs: the ego's live slots, transformed once per workgroup and compacted into LDS ----------
+    [[maybe_unused]] const double* obl = nullptr;
+    if constexpr (OBS) {
+        __shared__ double s_obs[F1P_LATOBS_DOUBLES];
+        const LatObs& ob = lat_obs_arg(obx...);
+        if (wave == 0) {
+            bool live; int k; double v[5];
+            const int nl = lat_obs_transform(ob, e, px, py, egp->ct, egp->st, lane, live, k, v);
+            if (live) {
+#pragma unroll
+                for (int q = 0; q < 5; ++q) s_obs[5 * k + q] = v[q];
+            }
+            if (lane == 0) { s_obs[F1P_LATOBS_PACE] = ob.pace[e]; *reinterpret_cast<int*>(s_obs + F1P_LATOBS_NLIVE) = nl; }
+        }
+        __syncthreads();
+        obl = s_obs;
+    }
+
     double bc; int bi;
     if (PRUNE && a.mode != LATTICE_EMIT) {
         // ---- 4'. branch and bound: fit every candidate, bound its cost from below, evaluate in order of the bound ----------
@@ -254,8 +275,9 @@ __global__ __launch_bounds__(256, (STAGING && GEN != F1P_GEN_CLOTHOID && !FOOT) 
                     double cost = __builtin_huge_val();
                     if ((lbj <= bc || bc != bc) && lbj < __builtin_huge_val()) {
                         const double k0 = slot[4 * j], dk = slot[4 * j + 1], L = slot[4 * j + 2];
-                        const StationResult sr = station_loop<false, F1P_GEN_CLOTHOID>(k0, dk, L, (const F1P_LDS(EgoParams)*)egp,
-                                                                                     (const F1P_LDS(uint32_t)*)tile, nullptr, nullptr, 0);
+                        const StationResult sr = station_loop<false, F1P_GEN_CLOTHOID, false, OBS>(k0, dk, L, (const F1P_LDS(EgoParams)*)egp,
+                                                                                     (const F1P_LDS(uint32_t)*)tile, nullptr, nullptr, 0,
+                                                                                     (const F1P_LDS(double)*)obl);
                         cost = 0.0;                               // eval(): cost = 0.; cost += w_i * f_i
                         cost += cfg.w_length * (1.0 / sr.len);
                         cost += cfg.w_max_kappa * sr.maxk;
@@ -310,8 +332,9 @@ __global__ __launch_bounds__(256, (STAGING && GEN != F1P_GEN_CLOTHOID && !FOOT) 
                 F1P_LDS(f1p_d2)* stage = staging ? (F1P_LDS(f1p_d2)*)(stage_all + wave * 64 * F1P_STAGE_PITCH) : nullptr;
                 double* wave_out = staging ? a.all_traj + ((size_t)e * C + wave_c0) * (size_t)S * 4 : nullptr;
                 const double sk0 = cl.ok ? cl.k0 : 0.0, sdk = cl.ok ? cl.dk : 0.0, sL = cl.ok ? cl.L : 0.0;   // zero rows when infeasible
-                const StationResult sr = station_loop<STAGING, GEN, FOOT>(sk0, sdk, sL, (const F1P_LDS(EgoParams)*)egp,
-                                                      (const F1P_LDS(uint32_t)*)tile, stage, wave_out, n_valid);
+                const StationResult sr = station_loop<STAGING, GEN, FOOT, OBS>(sk0, sdk, sL, (const F1P_LDS(EgoParams)*)egp,
+                                                      (const F1P_LDS(uint32_t)*)tile, stage, wave_out, n_valid,
+                                                      (const F1P_LDS(double)*)obl);
                 if (cl.ok) {
                     const double maxk = sr.maxk, sumk = sr.sumk, sim = sr.sim;
                     const bool hit = sr.hit != 0;
@@ -513,24 +536,35 @@ int launch_clothoid_sample(f1p_ctx* ctx, const double* d_params, int n, int S, d
     return check_hip(ctx, hipGetLastError(), "k_clothoid_sample launch");
 }
 
-// the all-fp64 kernel's launch (every instantiation the plan shape may take): TRK = a track plan
+// one instantiation of the all-fp64 kernel, with the moving discs' argument (ob) or without
+template <bool STAGING, int GEN, bool PRUNE, bool FOOT, bool TRK>
+static bool k_lattice_fits(f1p_ctx* ctx, size_t lds, const LatObs* ob) {
+    return ob ? lds_fits(ctx, k_lattice<STAGING, GEN, PRUNE, FOOT, TRK, LatObs>, lds) : lds_fits(ctx, k_lattice<STAGING, GEN, PRUNE, FOOT, TRK>, lds);
+}
+template <bool STAGING, int GEN, bool PRUNE, bool FOOT, bool TRK>
+static void k_lattice_go(f1p_ctx* ctx, unsigned grid, size_t lds, const LatticeArgs& a, const f1p_lattice_cfg* cfg, const LatObs* ob) {
+    if (ob) hipLaunchKernelGGL((k_lattice<STAGING, GEN, PRUNE, FOOT, TRK, LatObs>), dim3(grid), dim3(256), lds, ctx->stream, a, *cfg, *ob);
+    else hipLaunchKernelGGL((k_lattice<STAGING, GEN, PRUNE, FOOT, TRK>), dim3(grid), dim3(256), lds, ctx->stream, a, *cfg);
+}
+
+// the all-fp64 kernel's launch (every instantiation the plan shape may take): TRK = a track plan; ob: the plan's moving discs or null
 template <bool TRK>
 static int launch_k_lattice(f1p_ctx* ctx, LatticeArgs& a, const f1p_lattice_cfg* cfg, int E, size_t lds, bool all_traj, bool all_cost, int mode,
-                            bool foot, bool cubic, bool prune, int n_cand) {
+                            bool foot, bool cubic, bool prune, int n_cand, const LatObs* ob) {
     {
         bool fits;
-        if (all_traj) fits = cubic ? lds_fits(ctx, k_lattice<true, F1P_GEN_CUBIC, false, false, TRK>, lds) : lds_fits(ctx, k_lattice<true, F1P_GEN_CLOTHOID, false, false, TRK>, lds);
-        else if (cubic) fits = lds_fits(ctx, k_lattice<false, F1P_GEN_CUBIC, false, false, TRK>, lds);
-        else if (prune) fits = lds_fits(ctx, k_lattice<false, F1P_GEN_CLOTHOID, true, false, TRK>, lds);
-        else fits = lds_fits(ctx, k_lattice<false, F1P_GEN_CLOTHOID, false, false, TRK>, lds);
+        if (all_traj) fits = cubic ? k_lattice_fits<true, F1P_GEN_CUBIC, false, false, TRK>(ctx, lds, ob) : k_lattice_fits<true, F1P_GEN_CLOTHOID, false, false, TRK>(ctx, lds, ob);
+        else if (cubic) fits = k_lattice_fits<false, F1P_GEN_CUBIC, false, false, TRK>(ctx, lds, ob);
+        else if (prune) fits = k_lattice_fits<false, F1P_GEN_CLOTHOID, true, false, TRK>(ctx, lds, ob);
+        else fits = k_lattice_fits<false, F1P_GEN_CLOTHOID, false, false, TRK>(ctx, lds, ob);
         if (!fits)
             return set_error(ctx, F1P_EINVAL, "n_stations / occupancy tile need " + std::to_string(lds) + " B of LDS per workgroup, more than this device offers (" +
                                                   std::to_string((size_t)ctx->prop.maxSharedMemoryPerMultiProcessor) + " B): reduce n_stations");
     }
     // BASELINE configs[1] (one ego, 512 candidates): fewer egos than half the CUs and more candidates than one workgroup holds ->
-    // one workgroup per 256 candidates, merged by the last one to finish (split_merge)
+    // one workgroup per 256 candidates, merged by the last one to finish (split_merge).  (Moving discs: one workgroup per ego, f1p_lattice_set_obstacles.)
     unsigned grid = (unsigned)E;
-    {
+    if (!ob) {
         const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
         int G = ctx->lattice_split > 0 ? ctx->lattice_split : ((2 * E < cus && n_cand > 256) ? (n_cand + 255) / 256 : 1);
         if (G > 16) G = 16;
@@ -555,19 +589,19 @@ static int launch_k_lattice(f1p_ctx* ctx, LatticeArgs& a, const f1p_lattice_cfg*
     }
     if (foot) {
         if (all_traj) {
-            if (cubic) hipLaunchKernelGGL((k_lattice<true, F1P_GEN_CUBIC, false, true, TRK>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
-            else hipLaunchKernelGGL((k_lattice<true, F1P_GEN_CLOTHOID, false, true, TRK>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
+            if (cubic) k_lattice_go<true, F1P_GEN_CUBIC, false, true, TRK>(ctx, E, lds, a, cfg, ob);
+            else k_lattice_go<true, F1P_GEN_CLOTHOID, false, true, TRK>(ctx, E, lds, a, cfg, ob);
         } else {
-            if (cubic) hipLaunchKernelGGL((k_lattice<false, F1P_GEN_CUBIC, false, true, TRK>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
-            else hipLaunchKernelGGL((k_lattice<false, F1P_GEN_CLOTHOID, false, true, TRK>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
+            if (cubic) k_lattice_go<false, F1P_GEN_CUBIC, false, true, TRK>(ctx, E, lds, a, cfg, ob);
+            else k_lattice_go<false, F1P_GEN_CLOTHOID, false, true, TRK>(ctx, E, lds, a, cfg, ob);
         }
     } else if (all_traj) {
-        if (cubic) hipLaunchKernelGGL((k_lattice<true, F1P_GEN_CUBIC, false, false, TRK>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
-        else hipLaunchKernelGGL((k_lattice<true, F1P_GEN_CLOTHOID, false, false, TRK>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
+        if (cubic) k_lattice_go<true, F1P_GEN_CUBIC, false, false, TRK>(ctx, E, lds, a, cfg, ob);
+        else k_lattice_go<true, F1P_GEN_CLOTHOID, false, false, TRK>(ctx, E, lds, a, cfg, ob);
     } else {
-        if (cubic) hipLaunchKernelGGL((k_lattice<false, F1P_GEN_CUBIC, false, false, TRK>), dim3(E), dim3(256), lds, ctx->stream, a, *cfg);
-        else if (prune) hipLaunchKernelGGL((k_lattice<false, F1P_GEN_CLOTHOID, true, false, TRK>), dim3(grid), dim3(256), lds, ctx->stream, a, *cfg);
-        else hipLaunchKernelGGL((k_lattice<false, F1P_GEN_CLOTHOID, false, false, TRK>), dim3(grid), dim3(256), lds, ctx->stream, a, *cfg);
+        if (cubic) k_lattice_go<false, F1P_GEN_CUBIC, false, false, TRK>(ctx, E, lds, a, cfg, ob);
+        else if (prune) k_lattice_go<false, F1P_GEN_CLOTHOID, true, false, TRK>(ctx, grid, lds, a, cfg, ob);
+        else k_lattice_go<false, F1P_GEN_CLOTHOID, false, false, TRK>(ctx, grid, lds, a, cfg, ob);
     }
     return check_hip(ctx, hipGetLastError(), TRK ? "k_lattice (tracks) launch" : "k_lattice launch");
 }
@@ -640,10 +674,21 @@ int launch_lattice(f1p_ctx* ctx, int mode, const double* d_poses, const double* 
     a.fit_only = 0; a.bb_keys = nullptr; a.bb_cloth = nullptr; a.bb_ni = nullptr; a.wave_lds_bytes = 0;
     a.split_g = 1; a.split_part = nullptr; a.split_tickets = nullptr;
     const int n_cand = cfg->cand_count > 0 ? cfg->cand_count : cfg->n_lookahead * cfg->n_width;
+    // moving discs (f1p_lattice_set_obstacles): the plan's slots and paces from its first ego on (a slice, the audit's window: lat_obs_e0).  The
+    // entry points have checked the batch size and refused what the discs do not cover (candidate shards, the emit half)
+    LatObs obs_arg;
+    const LatObs* ob = nullptr;
+    if (ctx->lat_obs.cur && mode == LATTICE_FULL) {
+        obs_arg.M = ctx->lat_obs.M;
+        obs_arg.obs = ctx->lat_obs.cur + (size_t)ctx->lat_obs_e0 * 5 * (size_t)obs_arg.M;
+        obs_arg.pace = ctx->lat_pace_cur + ctx->lat_obs_e0;
+        obs_arg.xf = nullptr; obs_arg.n_live = nullptr;
+        ob = &obs_arg;
+    }
     // ---- mixed-precision schedule: f32 filter + fp64 decision (k_lattice_mixed.hip), where it applies ---------------------------------
     {
         bool handled = false;
-        const int rc = launch_lattice_mixed(ctx, a, cfg, mode, E, foot, cubic, d_pose_copy, &handled);
+        const int rc = launch_lattice_mixed(ctx, a, cfg, mode, E, foot, cubic, d_pose_copy, &handled, ob);
         if (rc != F1P_OK || handled) return rc;
     }
     // The plan stays here (all fp64): every thread of an ego's workgroup reads the pose, so poses that live in page-locked HOST memory (d_pose_copy given:
@@ -658,7 +703,8 @@ int launch_lattice(f1p_ctx* ctx, int mode, const double* d_poses, const double* 
     // the single-kernel branch and bound below
     const bool split_fits = lds_fits(ctx, k_lattice_eval, 4 * wl) && lds_fits(ctx, k_lattice<false, F1P_GEN_CLOTHOID, true>, lds);
     // (a track plan takes the single-kernel branch and bound: the same winners, bit for bit, without a track path in k_lattice_eval)
-    if (prune && n_cand <= 256 && E >= F1P_BB_SPLIT_MIN_EGOS && split_fits && !tracks) {
+    // (... and so does a plan with moving discs: k_lattice_eval has no disc test)
+    if (prune && n_cand <= 256 && E >= F1P_BB_SPLIT_MIN_EGOS && split_fits && !tracks && !ob) {
         // two kernels: fit + bound + sort with every wave busy, then one wave per ego for the station rounds
         const size_t need = (size_t)E * (256 * 8 + 256 * 32 + 4) + 64;
         if (need > ctx->bb_scratch_bytes) {
@@ -681,8 +727,8 @@ int launch_lattice(f1p_ctx* ctx, int mode, const double* d_poses, const double* 
         hipLaunchKernelGGL(k_lattice_eval, dim3((E + 3) / 4), dim3(256), 4 * wl, ctx->stream, a, *cfg);
         return check_hip(ctx, hipGetLastError(), "k_lattice_eval launch");
     }
-    return tracks ? launch_k_lattice<true>(ctx, a, cfg, E, lds, d_all_traj != nullptr, d_all_cost != nullptr, mode, foot, cubic, prune, n_cand)
-                  : launch_k_lattice<false>(ctx, a, cfg, E, lds, d_all_traj != nullptr, d_all_cost != nullptr, mode, foot, cubic, prune, n_cand);
+    return tracks ? launch_k_lattice<true>(ctx, a, cfg, E, lds, d_all_traj != nullptr, d_all_cost != nullptr, mode, foot, cubic, prune, n_cand, ob)
+                  : launch_k_lattice<false>(ctx, a, cfg, E, lds, d_all_traj != nullptr, d_all_cost != nullptr, mode, foot, cubic, prune, n_cand, ob);
 }
 
 int launch_clothoid_g1(f1p_ctx* ctx, const double* d_goals, int n, double* d_k0, double* d_dk, double* d_len, int32_t* d_ok) {

@@ -878,10 +878,21 @@ __device__ __forceinline__ bool candidate_goal_rec(const f1p_lattice_cfg& cfg, i
 // HG: host-supplied goals (the caller's [E][C][3] rows instead of the prologue's goal frames) -- an instantiation of its own, so that the
 // headline kernel carries neither the pointer nor the branches (as runtime branches they cost it 12 more spilled SGPRs and 1.5 us)
 // GEN: the candidate generator (F1P_GEN_CLOTHOID; F1P_GEN_CUBIC: bracket_cubic_f32 and the table-driven station passes, round 5)
-template <int CR, bool DBG = false, bool HG = false, int GEN = F1P_GEN_CLOTHOID, bool FOOT = false>
-__global__ __launch_bounds__(256, F1P_MIX_FILTER_WAVES) void k_lattice_filter3(LatticeArgs a, f1p_lattice_cfg cfg, MixArgs mx, const unsigned char* __restrict__ recs) {
+// OB = LatObs (moving discs, f1p_lattice_set_obstacles) or nothing.  With discs the filter must never call a candidate FREE that a disc
+// could block: phase 1 flags (state bit 6) every candidate that is not PROVABLY clear of every live slot, and a flagged candidate ends HIT (by the
+// grid) or UNSURE, never FREE -- so it never bounds T and goes to fp64 when its lo <= T; without a map a trusted bracket is FREE only unflagged.
+// The proof: every point P of a candidate of length L from the origin to its goal g has |P| + |P - g| <= L; a disc of radius r whose centre starts
+// at a and moves at u for at most L |pace| seconds stays within |u| L |pace| of a; so it cannot touch the candidate when
+//     |a| + |a - g| - 2 |u| L |pace|  >  L + 2 r + eps
+// with L the f32 fit's upper bound on the length and eps the f32 roundings of the operands (derived in DESIGN.md 5l).  This workgroup also does the
+// slot transform in fp64 (the ego's frame is in its record) and leaves the live slots for k_lattice_refine (LatObs::xf, n_live).
+// The instantiations without obstacles keep their signature and their code.
+template <int CR, bool DBG = false, bool HG = false, int GEN = F1P_GEN_CLOTHOID, bool FOOT = false, typename... OB>
+__global__ __launch_bounds__(256, F1P_MIX_FILTER_WAVES) void k_lattice_filter3(LatticeArgs a, f1p_lattice_cfg cfg, MixArgs mx, const unsigned char* __restrict__ recs, OB... obx) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    warm_kernargs<sizeof(LatticeArgs) + sizeof(f1p_lattice_cfg) + sizeof(MixArgs) + 8>();
+    constexpr bool OBS = sizeof...(OB) > 0;
+    constexpr int STM = OBS ? 0x3f : 0x7f;                        // the state proper (bit 7: can no longer turn out FREE by the first look; OBS, bit 6: nor by any look -- a disc may block it)
+    warm_kernargs<sizeof(LatticeArgs) + sizeof(f1p_lattice_cfg) + sizeof(MixArgs) + 8 + (sizeof(OB) + ... + 0)>();
     const int pitch = a.tile_words + 1;
     const unsigned tile_bytes = (unsigned)(a.tile_rows + 1) * (unsigned)pitch * 4u;
     uint32_t* tile = reinterpret_cast<uint32_t*>(lds_raw);       // (clearance word, bitmap word) pairs: (tile_rows + 1) x pitch, the last row / column the guard
@@ -926,6 +937,33 @@ __global__ __launch_bounds__(256, F1P_MIX_FILTER_WAVES) void k_lattice_filter3(L
     }
     if (tid >= 128 && tid < 128 + F1P_MAX_WIDTHS) wtab[tid - 128] = tid - 128 < cfg.n_width ? cfg.width[tid - 128] : 0.0;
     if (tid == 0) cnt[0] = 0;
+    // moving discs: wave 3 transforms the ego's slots (fp64, the frame straight from the record in global memory: no barrier to wait for), leaves the
+    // live ones for the refinement and, rounded OUTWARDS to f32, in LDS for phase 1: (ax, ay, |a| rounded down, 2 |u| |pace| and 2 r rounded up)
+    [[maybe_unused]] const F1P_LDS(float)* dsl = nullptr;
+    [[maybe_unused]] const F1P_LDS(int)* dnl = nullptr;
+    if constexpr (OBS) {
+        __shared__ float s_dsl[5 * F1P_LATTICE_MAX_OBS];
+        __shared__ int s_dnl;
+        const LatObs& ob = lat_obs_arg(obx...);
+        if (wave == 3) {
+            const EgoRecHdr* gh = reinterpret_cast<const EgoRecHdr*>(recs + (size_t)e * rec_bytes);
+            bool live; int k; double v[5];
+            const int nl = lat_obs_transform(ob, e, gh->px, gh->py, gh->ct, gh->st, lane, live, k, v);
+            if (live) {
+                double* o = ob.xf + ((size_t)e * F1P_LATTICE_MAX_OBS + k) * 5;
+#pragma unroll
+                for (int q = 0; q < 5; ++q) o[q] = v[q];
+                const double pc = __builtin_fabs(ob.pace[e]);
+                const double na = __builtin_sqrt(v[0] * v[0] + v[1] * v[1]), nu = __builtin_sqrt(v[2] * v[2] + v[3] * v[3]);
+                s_dsl[5 * k] = (float)v[0]; s_dsl[5 * k + 1] = (float)v[1];
+                s_dsl[5 * k + 2] = (float)na * 0.9999998f;                       // (NaN stays NaN: nothing is provably clear of such a slot)
+                s_dsl[5 * k + 3] = (float)(2.0 * nu * pc) * 1.0000002f;
+                s_dsl[5 * k + 4] = (float)(2.0 * __builtin_sqrt(v[4])) * 1.0000002f;
+            }
+            if (lane == 0) { s_dnl = nl; ob.n_live[e] = nl; }
+        }
+        dsl = (const F1P_LDS(float)*)s_dsl; dnl = (const F1P_LDS(int)*)&s_dnl;
+    }
     if (GEN == F1P_GEN_CUBIC) {
         const int S_ = cfg.n_stations, den_ = S_ - 1 > 1 ? S_ - 1 : 1, sim_m_ = S_ - cfg.n_shift - cfg.n_cull;
         for (int i = tid; i < S_; i += blockDim.x) {
@@ -1020,14 +1058,32 @@ __global__ __launch_bounds__(256, F1P_MIX_FILTER_WAVES) void k_lattice_filter3(L
         if (c >= c1) continue;
         float lo, hi, gx, gy; Brk32 o; int dbg_code;
         float f_k0, f_dk, f_L, f_ek0, f_edk, f_eL;
-        const int st = bracket_of(c, f_k0, f_dk, f_L, f_ek0, f_edk, f_eL, lo, hi, gx, gy, o, dbg_code);
+        int st = bracket_of(c, f_k0, f_dk, f_L, f_ek0, f_edk, f_eL, lo, hi, gx, gy, o, dbg_code);
+        if constexpr (OBS) {
+            // not provably clear of every live slot (see the top of the kernel; a NaN anywhere: not proved): never FREE
+            const int nl = __builtin_amdgcn_readfirstlane(*dnl);
+            const float Lu = f_L * (1.0f + 2.0f * f_eL + 1.0e-6f);           // upper bound of the fp64 length (trusted fits: the others are UNSURE already)
+            const float gn = __builtin_sqrtf(gx * gx + gy * gy);
+            bool flagged = false;
+            for (int k = 0; k < nl; ++k) {
+                const float ddx = dsl[5 * k] - gx, ddy = dsl[5 * k + 1] - gy;
+                const float lhs = dsl[5 * k + 2] + __builtin_sqrtf(ddx * ddx + ddy * ddy);
+                const float rhs = Lu * (1.0f + dsl[5 * k + 3]) + dsl[5 * k + 4];
+                const float eps = 1.0e-6f * (dsl[5 * k + 2] + gn + rhs) + 1.0e-6f;
+                flagged |= !(lhs - rhs > eps);
+            }
+            if (flagged) {
+                if (st == F1P_ST_FREE) { st = F1P_ST_UNSURE; hi = INF; }      // (no collision check: FREE straight from the bracket)
+                else if ((st & STM) == F1P_ST_PENDING || (st & STM) == F1P_ST_PENDING2) st |= 0x40;
+            }
+        }
         c_lo[c - c0] = lo; c_hi[c - c0] = hi;
         if (one_pass) {
             float* q = c_fit + (c - c0);
             q[0] = f_k0; q[nc] = f_dk; q[2 * nc] = f_L; q[3 * nc] = f_ek0; q[4 * nc] = f_edk; q[5 * nc] = f_eL;
         }
         c_st[c - c0] = (unsigned char)st;
-        if ((st & 0x7f) == F1P_ST_PENDING || (st & 0x7f) == F1P_ST_PENDING2) my_hi_p = fminf(my_hi_p, hi);
+        if ((st & STM) == F1P_ST_PENDING || (st & STM) == F1P_ST_PENDING2) my_hi_p = fminf(my_hi_p, hi);
         if (st == F1P_ST_FREE) t_free = fminf(t_free, hi);           // (only without a collision check)
 #if !defined(F1P_MIX_DEBUG_END) && !defined(F1P_PRO_PHASES) && !defined(F1P_PRO2_PHASES)
         if (DBG && mx.dbg_cost32) mx.dbg_cost32[(size_t)e * C + c] = o.cost;
@@ -1036,7 +1092,7 @@ __global__ __launch_bounds__(256, F1P_MIX_FILTER_WAVES) void k_lattice_filter3(L
         if (DBG && mx.dbg_cost32) mx.dbg_cost32[(size_t)e * C + c] = 0.0f;
         if (DBG && mx.dbg_bound) mx.dbg_bound[(size_t)e * C + c] = o.ebound;
 #endif
-        if (DBG && mx.dbg_state && (st & 0x7f) != F1P_ST_PENDING && (st & 0x7f) != F1P_ST_PENDING2) mx.dbg_state[(size_t)e * C + c] = dbg_code >= 0 ? dbg_code : ((st & 0x7f) == F1P_ST_UNSURE && lo == -INF ? 5 : (st & 0x7f));
+        if (DBG && mx.dbg_state && (st & STM) != F1P_ST_PENDING && (st & STM) != F1P_ST_PENDING2) mx.dbg_state[(size_t)e * C + c] = dbg_code >= 0 ? dbg_code : ((st & STM) == F1P_ST_UNSURE && lo == -INF ? 5 : (st & STM));
     }
 #if defined(F1P_F3_ABLATE) && F1P_F3_ABLATE == 1                  // measurement builds (tools/pmc_ablate.sh, profiles/r06_filter3_ablation.txt): the kernel ends behind phase 1 -- NOT a plan
     if (tid == 0) { mx.ego_base[e] = 0; mx.ego_n[e] = 0; }
@@ -1117,7 +1173,7 @@ __global__ __launch_bounds__(256, F1P_MIX_FILTER_WAVES) void k_lattice_filter3(L
             const int c = cand_of(cb);
             const int st = c < c1 ? (int)c_st[c - c0] : F1P_ST_BAD;
             const float lo = c < c1 ? c_lo[c - c0] : INF;
-            const int st7 = st & 0x7f;
+            const int st7 = st & STM;
             const bool pend = (st7 == F1P_ST_PENDING) | (st7 == F1P_ST_PENDING2);
             const bool sel = pend && (all_states || !(lo > thr));
             const bool sel1 = sel && st7 == F1P_ST_PENDING;
@@ -1147,6 +1203,7 @@ __global__ __launch_bounds__(256, F1P_MIX_FILTER_WAVES) void k_lattice_filter3(L
                     // the selected candidates' cell-edge band, and what it says about their positions (a band of 0.8 cells: they decide nothing)
                     float edge = 2.0f;
                     bool nfree = look == 0 && (st & 0x80) != 0;
+                    if constexpr (OBS) nfree |= (st & 0x40) != 0;         // a disc may block it: no look can call it FREE
                     if (mine) { edge = GEN == F1P_GEN_CUBIC ? edge_cubic(edk, ep, ft.omax) : edge_f2<CR>(k0, dk, L, ek0, edk, eL, ep, ex, nullptr, ft.omax); nfree |= !(edge < 0.8f); }
                     const int nt = ex ? plan_x.nt : plan.nt;
                     bool coop = false;
@@ -1211,7 +1268,7 @@ __global__ __launch_bounds__(256, F1P_MIX_FILTER_WAVES) void k_lattice_filter3(L
                     }
                 }
                 if (ns != st7) {                                  // (only lanes that took a pass)
-                    c_st[c - c0] = (unsigned char)ns;
+                    c_st[c - c0] = (unsigned char)(OBS ? (ns | (st & 0x40)) : ns);
                     if (ns == F1P_ST_FREE) t_free = fminf(t_free, c_hi[c - c0]);
                     if (DBG && mx.dbg_state) mx.dbg_state[(size_t)e * C + c] = ns;
 #ifdef F1P_MIX_DEBUG_END
@@ -1251,7 +1308,7 @@ __global__ __launch_bounds__(256, F1P_MIX_FILTER_WAVES) void k_lattice_filter3(L
     for (int cb = c0; cb < c1; cb += blockDim.x) {
         const int c = cand_of(cb);
         if (c >= c1) continue;
-        const int st = c_st[c - c0] & 0x7f;
+        const int st = c_st[c - c0] & STM;
         const bool need = ((st == F1P_ST_FREE) | (st == F1P_ST_UNSURE) | (st == F1P_ST_PENDING2)) & !(c_lo[c - c0] > t_min);
         mine += (need | (none_free & (c == c0))) ? 1 : 0;
     }
@@ -1277,7 +1334,7 @@ __global__ __launch_bounds__(256, F1P_MIX_FILTER_WAVES) void k_lattice_filter3(L
         const int c = cand_of(c0);
         need1 = mine != 0;                                           // (one candidate per thread: what the count above found)
         if (need1) {
-            const int st = c_st[c - c0] & 0x7f;
+            const int st = c_st[c - c0] & STM;
             const bool gok = HG ? candidate_goal_host(a.goals, e, C, c, g1x, g1y, g1th) : candidate_goal_rec(cfg, c, hdr, cen, nl, gfr, g1x, g1y, g1th);
             ok1 = gok ? (st == F1P_ST_FREE ? -2 : -1) : 0;
         }
@@ -1296,7 +1353,7 @@ __global__ __launch_bounds__(256, F1P_MIX_FILTER_WAVES) void k_lattice_filter3(L
     for (int cb = c0; cb < c1; cb += blockDim.x) {
         const int c = cand_of(cb);
         if (c >= c1) continue;
-        const int st = c_st[c - c0] & 0x7f;
+        const int st = c_st[c - c0] & STM;
         const bool need = ((st == F1P_ST_FREE) | (st == F1P_ST_UNSURE) | (st == F1P_ST_PENDING2)) & !(c_lo[c - c0] > t_min);
         if (need | (none_free & (c == c0))) {
             double gx = 0.0, gy = 0.0, gth = 0.0;
@@ -1329,7 +1386,10 @@ __global__ __launch_bounds__(256, F1P_MIX_FILTER_WAVES) void k_lattice_filter3(L
 // The instantiations a plan shape may launch: <CR, hooks, host goals, generator, footprint>.  The headline shape (device goals, clothoids, point footprint) and the
 // host-goal shape exist with and without the test hooks; the others carry the hooks where the table below says so.
 template <int CR>
-static bool filter3_fits(f1p_ctx* ctx, bool foot, bool cubic, size_t lds) {
+static bool filter3_fits(f1p_ctx* ctx, bool foot, bool cubic, size_t lds, bool obs) {
+    if (obs)                                                     // moving discs: clothoids with the point footprint, device or host goals, with and without the hooks
+        return lds_fits(ctx, (k_lattice_filter3<CR, false, false, F1P_GEN_CLOTHOID, false, LatObs>), lds) && lds_fits(ctx, (k_lattice_filter3<CR, true, false, F1P_GEN_CLOTHOID, false, LatObs>), lds) &&
+               lds_fits(ctx, (k_lattice_filter3<CR, false, true, F1P_GEN_CLOTHOID, false, LatObs>), lds) && lds_fits(ctx, (k_lattice_filter3<CR, true, true, F1P_GEN_CLOTHOID, false, LatObs>), lds);
     bool ok = lds_fits(ctx, k_lattice_filter3<CR>, lds) && lds_fits(ctx, (k_lattice_filter3<CR, true>), lds) && lds_fits(ctx, (k_lattice_filter3<CR, true, true>), lds) &&
               lds_fits(ctx, (k_lattice_filter3<CR, false, true>), lds);
     if (foot)                                                    // oriented footprint: its own instantiations (hooks included)
@@ -1342,14 +1402,21 @@ static bool filter3_fits(f1p_ctx* ctx, bool foot, bool cubic, size_t lds) {
     return ok;
 }
 
-bool mixed_filter3_fits(f1p_ctx* ctx, int cr, bool foot, bool cubic, size_t lds) {
-    return cr == 1 ? filter3_fits<1>(ctx, foot, cubic, lds) : filter3_fits<2>(ctx, foot, cubic, lds);
+bool mixed_filter3_fits(f1p_ctx* ctx, int cr, bool foot, bool cubic, size_t lds, bool obs) {
+    return cr == 1 ? filter3_fits<1>(ctx, foot, cubic, lds, obs) : filter3_fits<2>(ctx, foot, cubic, lds, obs);
 }
 
 template <int CR>
 static void filter3_launch(bool hooks, bool host_goals, bool cubic, bool foot, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a,
-                           const f1p_lattice_cfg& cfg, const MixArgs& mx, const unsigned char* recs) {
+                           const f1p_lattice_cfg& cfg, const MixArgs& mx, const unsigned char* recs, const LatObs* ob) {
     const dim3 g(grid), fb(F1P_MIX_FILTER_BLOCK);
+    if (ob) {                                                    // (the schedule sends only clothoids with the point footprint here while discs are set)
+        if (host_goals && hooks) hipLaunchKernelGGL((k_lattice_filter3<CR, true, true, F1P_GEN_CLOTHOID, false, LatObs>), g, fb, lds, st, a, cfg, mx, recs, *ob);
+        else if (host_goals) hipLaunchKernelGGL((k_lattice_filter3<CR, false, true, F1P_GEN_CLOTHOID, false, LatObs>), g, fb, lds, st, a, cfg, mx, recs, *ob);
+        else if (hooks) hipLaunchKernelGGL((k_lattice_filter3<CR, true, false, F1P_GEN_CLOTHOID, false, LatObs>), g, fb, lds, st, a, cfg, mx, recs, *ob);
+        else hipLaunchKernelGGL((k_lattice_filter3<CR, false, false, F1P_GEN_CLOTHOID, false, LatObs>), g, fb, lds, st, a, cfg, mx, recs, *ob);
+        return;
+    }
     if (cubic && foot && host_goals) hipLaunchKernelGGL((k_lattice_filter3<CR, true, true, F1P_GEN_CUBIC, true>), g, fb, lds, st, a, cfg, mx, recs);   // (oriented footprint: one instantiation per goal source, hooks included)
     else if (cubic && foot) hipLaunchKernelGGL((k_lattice_filter3<CR, true, false, F1P_GEN_CUBIC, true>), g, fb, lds, st, a, cfg, mx, recs);
     else if (cubic && host_goals) hipLaunchKernelGGL((k_lattice_filter3<CR, true, true, F1P_GEN_CUBIC>), g, fb, lds, st, a, cfg, mx, recs);             // (host goals: hooks included)
@@ -1370,9 +1437,9 @@ static void filter3_launch(bool hooks, bool host_goals, bool cubic, bool foot, u
 }
 
 void mixed_launch_filter3(int cr, bool hooks, bool host_goals, bool cubic, bool foot, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a,
-                          const f1p_lattice_cfg& cfg, const MixArgs& mx, const unsigned char* recs) {
-    if (cr == 1) filter3_launch<1>(hooks, host_goals, cubic, foot, grid, lds, st, a, cfg, mx, recs);
-    else filter3_launch<2>(hooks, host_goals, cubic, foot, grid, lds, st, a, cfg, mx, recs);
+                          const f1p_lattice_cfg& cfg, const MixArgs& mx, const unsigned char* recs, const LatObs* ob) {
+    if (cr == 1) filter3_launch<1>(hooks, host_goals, cubic, foot, grid, lds, st, a, cfg, mx, recs, ob);
+    else filter3_launch<2>(hooks, host_goals, cubic, foot, grid, lds, st, a, cfg, mx, recs, ob);
 }
 
 }  // namespace f1p

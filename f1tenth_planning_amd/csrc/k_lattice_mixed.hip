@@ -64,11 +64,13 @@ static int lattice_audit(f1p_ctx* ctx, const double* d_poses, const double* d_pr
     f1p_lattice_cfg ref_cfg = *cfg;
     ref_cfg.prune = 0;                                              // the plain exhaustive loop
     const int mixed = ctx->lattice_mixed;
+    const int obs_e0 = ctx->lat_obs_e0;
+    ctx->lat_obs_e0 = obs_e0 + w0;                                  // (the window sees the same moving discs: per-ego arrays from its first ego)
     ctx->lattice_mixed = 0; ctx->auditing = true;
     const int rc = launch_lattice(ctx, LATTICE_FULL, d_poses + 4 * (size_t)w0, nullptr, d_prev_theta ? d_prev_theta + (size_t)w0 * S : nullptr, n, &ref_cfg,
                                   nullptr, nullptr, r_steer, r_speed, r_idx, r_cost, r_status, r_near, r_traj, nullptr, nullptr, nullptr, nullptr, nullptr,
                                   d_track_id ? d_track_id + w0 : nullptr);   // (a track plan's window: re-planned with the same track ids)
-    ctx->lattice_mixed = mixed; ctx->auditing = false;
+    ctx->lattice_mixed = mixed; ctx->auditing = false; ctx->lat_obs_e0 = obs_e0;
     if (rc) return rc;
     hipLaunchKernelGGL(k_lattice_audit_compare, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, S,
                        d_steer ? d_steer + w0 : nullptr, d_speed ? d_speed + w0 : nullptr, d_best_idx + w0, d_best_cost ? d_best_cost + w0 : nullptr,
@@ -106,8 +108,11 @@ void lookahead_slack(const f1p_lattice_cfg* cfg, double absmax, double* slack, f
 // The mixed-precision schedule of one plan: decides whether it applies (*handled), sizes the scratch, launches prologue -> filter ->
 // refinement -> selection (and the runtime audit).  Called by launch_lattice (k_lattice.hip) with the plan's LatticeArgs filled in.
 int launch_lattice_mixed(f1p_ctx* ctx, LatticeArgs& a, const f1p_lattice_cfg* cfg, int mode, int E, bool foot, bool cubic,
-                         double* d_pose_copy, bool* handled) {
+                         double* d_pose_copy, bool* handled, const LatObs* ob) {
     *handled = false;
+    // moving discs (f1p_lattice_set_obstacles): clothoid candidates with the point footprint -- device or host goals, raceline or track set,
+    // plan or step -- stay on this schedule; cubic candidates and the oriented footprint run all fp64 while discs are set (not handled)
+    if (ob && (cubic || foot)) return F1P_OK;
     const int S = cfg->n_stations;
     const int n_cand = cfg->cand_count > 0 ? cfg->cand_count : cfg->n_lookahead * cfg->n_width;
     const double *d_poses = a.poses, *d_prev_theta = a.prev_theta;
@@ -162,8 +167,8 @@ int launch_lattice_mixed(f1p_ctx* ctx, LatticeArgs& a, const f1p_lattice_cfg* cf
         // every instantiation that may be launched below is checked (and configured for > 64 KB of dynamic LDS) by lds_fits -- the
         // footprint variants included (only refine<64> had been, so a FOOT plan with > 496 stations could fail between the
         // filter and the selection kernel and leave the queue counter armed)
-        const bool groups16 = mixed_refine_fits(ctx, 16, foot, lds_r16 + lds_r_static);
-        const bool refine_fits = groups16 || mixed_refine_fits(ctx, 64, foot, lds_r64 + lds_r_static);
+        const bool groups16 = mixed_refine_fits(ctx, 16, foot, lds_r16 + lds_r_static, ob != nullptr);
+        const bool refine_fits = groups16 || mixed_refine_fits(ctx, 64, foot, lds_r64 + lds_r_static, ob != nullptr);
         const bool tracks = a.track_id != nullptr;
         if (refine_fits && mixed_select_fits(ctx, false, lds_s, tracks)) {
             MixArgs mx;
@@ -200,7 +205,7 @@ int launch_lattice_mixed(f1p_ctx* ctx, LatticeArgs& a, const f1p_lattice_cfg* cf
             // (clearance 0 -- no map -- runs the r = 1 instantiations: every look of theirs is the every-station one then)
             const int cr = mx.clear_r == 2 ? 2 : 1;
             // (every instantiation the plan shape may launch: checked -- and configured for > 64 KB of dynamic LDS -- in the kernels' own translation units)
-            bool v3 = mixed_filter3_fits(ctx, cr, mx.n_disc > 0, cubic, lds_f3);
+            bool v3 = mixed_filter3_fits(ctx, cr, mx.n_disc > 0, cubic, lds_f3, ob != nullptr);
             if (cubic) v3 = v3 && S <= 256 && mixed_refine_cubic_fits(ctx, lds_rc) && mixed_select_fits(ctx, true, lds_s, tracks);
             if (!v3) return F1P_OK;                                  // (not handled: the all-fp64 kernel takes the plan)
             // ---- pipeline: the batch in chunks of egos, chunk k on internal stream k % 2, the second stream one stage behind the
@@ -232,6 +237,23 @@ int launch_lattice_mixed(f1p_ctx* ctx, LatticeArgs& a, const f1p_lattice_cfg* cf
                 ctx->d_mix_scratch = nullptr; ctx->mix_scratch_bytes = 0;
                 F1P_HIP(ctx, hipMalloc((void**)&ctx->d_mix_scratch, need));
                 ctx->mix_scratch_bytes = need;
+            }
+            // the moving discs' hand-over from the candidate kernel (it holds the ego's frame) to the refinement: transformed live slots and their number per ego
+            LatObs obm;
+            if (ob) {
+                const size_t xf_bytes = (sizeof(double) * 5 * F1P_LATTICE_MAX_OBS * (size_t)E + 255) & ~(size_t)255;
+                const size_t need_xf = xf_bytes + sizeof(int32_t) * (size_t)E;
+                if (need_xf > ctx->lat_obs_xf_bytes) {
+                    F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                    if (ctx->d_lat_obs_xf) (void)hipFree(ctx->d_lat_obs_xf);
+                    ctx->d_lat_obs_xf = nullptr; ctx->lat_obs_xf_bytes = 0;
+                    F1P_HIP(ctx, hipMalloc((void**)&ctx->d_lat_obs_xf, need_xf));
+                    ctx->lat_obs_xf_bytes = need_xf;
+                }
+                obm = *ob;
+                obm.xf = reinterpret_cast<double*>(ctx->d_lat_obs_xf);
+                obm.n_live = reinterpret_cast<int32_t*>(ctx->d_lat_obs_xf + xf_bytes);
+                ob = &obm;
             }
             ctx->mix_last_E = E; ctx->mix_ego_n_off = qc_bytes + sizeof(int32_t) * (size_t)E;   // (f1p_lattice_debug_queue)
             mx.qcount = reinterpret_cast<unsigned int*>(ctx->d_mix_scratch);
@@ -322,7 +344,7 @@ int launch_lattice_mixed(f1p_ctx* ctx, LatticeArgs& a, const f1p_lattice_cfg* cf
                     const bool dbg = mk.dbg_cost32 || mk.dbg_state || mk.dbg_bound || mk.dbg_pass;      // (test hooks: their own instantiation)
                     const unsigned char* recs = (const unsigned char*)ctx->d_rec_scratch;
                     // (one instantiation per plan shape <clearance mode, hooks, host goals, generator, footprint>: k_lattice_filter3.hip)
-                    mixed_launch_filter3(cr, dbg, ak.goals != nullptr, cubic, mk.n_disc > 0, f3_grid, lds_f3, st, ak, *cfg, mk, recs);
+                    mixed_launch_filter3(cr, dbg, ak.goals != nullptr, cubic, mk.n_disc > 0, f3_grid, lds_f3, st, ak, *cfg, mk, recs, ob);
                 }
                 if ((rc = check_hip(ctx, hipGetLastError(), "k_lattice_filter3 launch"))) break;
                 if (prof) F1P_HIP(ctx, hipEventRecord(ctx->ev_prof[2], st));
@@ -332,7 +354,7 @@ int launch_lattice_mixed(f1p_ctx* ctx, LatticeArgs& a, const f1p_lattice_cfg* cf
                 if (rb > rb_max) rb = rb_max;
                 rb = rb & ~(size_t)15;
                 if (rb < 16) rb = 16;
-                mixed_launch_refine(cubic, groups16 ? 16 : 64, mk.n_disc > 0, (unsigned)rb, cubic ? lds_rc : (groups16 ? lds_r16 : lds_r64), st, ak, *cfg, mk);
+                mixed_launch_refine(cubic, groups16 ? 16 : 64, mk.n_disc > 0, (unsigned)rb, cubic ? lds_rc : (groups16 ? lds_r16 : lds_r64), st, ak, *cfg, mk, ob);
                 if ((rc = check_hip(ctx, hipGetLastError(), "k_lattice_refine launch"))) break;
                 if (prof) F1P_HIP(ctx, hipEventRecord(ctx->ev_prof[3], st));
                 mixed_launch_select(cubic, tracks, (unsigned)((Ek + 3) / 4 + (mk.perm_fill ? (Ek + 255) / 256 : 0)), lds_s, st, ak, *cfg, mk);

@@ -30,10 +30,14 @@ __device__ __forceinline__ double group_shr1(double v) {
     return __longlong_as_double(((long long)shi << 32) | (long long)(unsigned int)slo);
 }
 
-template <int GS, bool FOOT = false>
-__global__ __launch_bounds__(256, 2) void k_lattice_refine(LatticeArgs a, f1p_lattice_cfg cfg, MixArgs mx) {
+// OB = LatObs (moving discs, f1p_lattice_set_obstacles) or nothing: the disc test of station_loop<.., OBS> on the same station points, at the same
+// times, against the slots the candidate kernel transformed (LatObs::xf) -- for every entry it did not prove clear of every disc (ok != -2).  The
+// instantiations without obstacles keep their signature and their code.
+template <int GS, bool FOOT = false, typename... OB>
+__global__ __launch_bounds__(256, 2) void k_lattice_refine(LatticeArgs a, f1p_lattice_cfg cfg, MixArgs mx, OB... obx) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    warm_kernargs<sizeof(LatticeArgs) + sizeof(f1p_lattice_cfg) + sizeof(MixArgs)>();
+    constexpr bool OBS = sizeof...(OB) > 0;
+    warm_kernargs<sizeof(LatticeArgs) + sizeof(f1p_lattice_cfg) + sizeof(MixArgs) + (sizeof(OB) + ... + 0)>();
     constexpr int GPW = 64 / GS;                                 // groups (entries) per wave
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int gl = lane & (GS - 1), grp = lane / GS, gbase = lane & ~(GS - 1);
@@ -110,6 +114,18 @@ __global__ __launch_bounds__(256, 2) void k_lattice_refine(LatticeArgs a, f1p_la
         // what the station phases need from memory is requested now, behind the entry, and arrives while the fit runs
         EgoXform xf = {};
         if (work && check_occ) xf = mx.xf[e];                        // the ego -> tile-relative cell transform of the filter's setup thread (fp64)
+        // moving discs: an entry the filter proved FREE (-2) is clear of the grid AND of every disc; any other takes the disc test -- with or without a grid
+        [[maybe_unused]] bool check_disc = false;
+        [[maybe_unused]] int n_live = 0;
+        [[maybe_unused]] double pace = 0.0;
+        [[maybe_unused]] const double* slots = nullptr;
+        if constexpr (OBS) {
+            const LatObs& ob = lat_obs_arg(obx...);
+            if (work && r.ok != -2) {
+                n_live = ob.n_live[e]; pace = ob.pace[e]; slots = ob.xf + (size_t)e * (5 * F1P_LATTICE_MAX_OBS);
+                check_disc = n_live > 0;
+            }
+        }
         const double* prev = a.prev_theta ? a.prev_theta + (size_t)e * S : nullptr;
         double pv[4] = {0.0, 0.0, 0.0, 0.0};                         // previous headings of this lane's first four stations
         if (work && prev) {
@@ -236,7 +252,7 @@ __global__ __launch_bounds__(256, 2) void k_lattice_refine(LatticeArgs a, f1p_la
         const double k0 = cl.k0, dk = cl.dk, L = run ? cl.L : 1.0;
         const double ds = L / (double)den;
         bool hit = false;
-        const bool occ_pass = run && check_occ;
+        const bool occ_pass = run && (check_occ || (OBS && check_disc));
         // the station increments: needed here by the occupancy pass, and by k_lattice_select for whichever entry wins -- handed over
         // through mx.inc (the selection's own interval_setup + piece_state_at + interval_increment was 41 % of its wave's lifetime);
         // an entry the filter proved collision-free computes them only for that hand-over, beside the other groups' occupancy passes
@@ -355,6 +371,16 @@ __global__ __launch_bounds__(256, 2) void k_lattice_refine(LatticeArgs a, f1p_la
                         for (int k = 0; k < NSL; ++k) { const int q = qb + k * GS + gl; if (q < S) { __builtin_nontemporal_store(xs[k], gp + q); __builtin_nontemporal_store(ys[k], gp + S + q); } }
                     }
                     if (!occ_pass) continue;
+                    if constexpr (OBS) {
+                        if (check_disc) {
+#pragma unroll
+                            for (int k = 0; k < NSL; ++k) {
+                                const int q = qb + k * GS + gl;
+                                if (q < S) hit |= lat_disc_blocked(slots, n_live, xs[k], ys[k], ((double)q * ds) * pace);   // tau_q = s_q * pace, s_q = (double)q * ds
+                            }
+                        }
+                        if (!check_occ) continue;
+                    }
                     if (!FOOT || mx.n_disc == 0) {
                         uint32_t word[NSL]; int bit[NSL]; bool have[NSL];
 #pragma unroll
@@ -585,7 +611,8 @@ __global__ __launch_bounds__(256, 2) void k_lattice_refine_cubic(LatticeArgs a, 
 }
 
 // ---- launch wrappers (host) --------------------------------------------------------------------------------------------------------------
-bool mixed_refine_fits(f1p_ctx* ctx, int lanes, bool foot, size_t lds) {
+bool mixed_refine_fits(f1p_ctx* ctx, int lanes, bool foot, size_t lds, bool obs) {
+    if (obs) return lanes == 16 ? lds_fits(ctx, (k_lattice_refine<16, false, LatObs>), lds) : lds_fits(ctx, (k_lattice_refine<64, false, LatObs>), lds);   // (moving discs: point footprint only)
     if (lanes == 16) return foot ? lds_fits(ctx, (k_lattice_refine<16, true>), lds) : lds_fits(ctx, k_lattice_refine<16>, lds);
     return foot ? lds_fits(ctx, (k_lattice_refine<64, true>), lds) : lds_fits(ctx, k_lattice_refine<64>, lds);
 }
@@ -594,9 +621,13 @@ bool mixed_refine_cubic_fits(f1p_ctx* ctx, size_t lds) {
     return lds_fits(ctx, k_lattice_refine_cubic<16>, lds) && lds_fits(ctx, (k_lattice_refine_cubic<16, true>), lds);
 }
 
-void mixed_launch_refine(bool cubic, int lanes, bool foot, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx) {
+void mixed_launch_refine(bool cubic, int lanes, bool foot, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx,
+                         const LatObs* ob) {
     const dim3 g(grid), b(256);
-    if (cubic && foot) hipLaunchKernelGGL((k_lattice_refine_cubic<16, true>), g, b, lds, st, a, cfg, mx);
+    if (ob) {                                                    // (the schedule sends only clothoids with the point footprint here while discs are set)
+        if (lanes == 16) hipLaunchKernelGGL((k_lattice_refine<16, false, LatObs>), g, b, lds, st, a, cfg, mx, *ob);
+        else hipLaunchKernelGGL((k_lattice_refine<64, false, LatObs>), g, b, lds, st, a, cfg, mx, *ob);
+    } else if (cubic && foot) hipLaunchKernelGGL((k_lattice_refine_cubic<16, true>), g, b, lds, st, a, cfg, mx);
     else if (cubic) hipLaunchKernelGGL(k_lattice_refine_cubic<16>, g, b, lds, st, a, cfg, mx);
     else if (lanes == 16) {
         if (foot) hipLaunchKernelGGL((k_lattice_refine<16, true>), g, b, lds, st, a, cfg, mx);

@@ -250,13 +250,15 @@ __host__ __device__ inline size_t ego_rec_stride(int nl) { return (sizeof(EgoRec
 void mixed_launch_prologue(bool two_per_wave, bool tracks, int egos, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx, unsigned char* recs);
 // k_lattice_filter3.hip: cr = clearance mode (1 | 2), hooks = the instantiation with the test hooks; *_fits: every instantiation the plan shape may launch
 // fits the device's LDS (and is configured for > 64 KB where needed)
-bool mixed_filter3_fits(f1p_ctx* ctx, int cr, bool foot, bool cubic, size_t lds);
+// (obs / ob: the plan has moving discs -- f1p_lattice_set_obstacles -- and takes the instantiations with the LatObs argument: clothoids, point footprint)
+bool mixed_filter3_fits(f1p_ctx* ctx, int cr, bool foot, bool cubic, size_t lds, bool obs = false);
 void mixed_launch_filter3(int cr, bool hooks, bool host_goals, bool cubic, bool foot, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a,
-                          const f1p_lattice_cfg& cfg, const MixArgs& mx, const unsigned char* recs);
+                          const f1p_lattice_cfg& cfg, const MixArgs& mx, const unsigned char* recs, const LatObs* ob = nullptr);
 // k_lattice_refine.hip: lanes = 16 | 64 lanes per queue entry (clothoids); the cubic generator has one form
-bool mixed_refine_fits(f1p_ctx* ctx, int lanes, bool foot, size_t lds);
+bool mixed_refine_fits(f1p_ctx* ctx, int lanes, bool foot, size_t lds, bool obs = false);
 bool mixed_refine_cubic_fits(f1p_ctx* ctx, size_t lds);
-void mixed_launch_refine(bool cubic, int lanes, bool foot, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx);
+void mixed_launch_refine(bool cubic, int lanes, bool foot, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx,
+                         const LatObs* ob = nullptr);
 // k_lattice_select.hip
 bool mixed_select_fits(f1p_ctx* ctx, bool cubic, size_t lds, bool tracks = false);
 void mixed_launch_select(bool cubic, bool tracks, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx);

@@ -16,15 +16,21 @@ the tracker is handed an ego-frame path with a map-frame pose and reads theta as
 here is written down in DESIGN.md "Lattice semantics": goals and trajectories live in the ego frame, the winner is
 tracked from pose (0, 0, 0) with look-ahead 0.8 and the commanded speed is the raceline speed at the nearest
 waypoint.
+
+Moving obstacles: `planner.obstacles = [M, 5]` before plan() / `[E, M, 5]` before plan_batch() / step_batch() tests every candidate of THAT call
+against discs (x, y, vx, vy, r) -- map frame, constant velocity, the vehicle's own radius folded into r, r < 0 or NaN: an empty row -- at the
+stations the occupancy test tests; station j is reached at s_j / max(|v|, obstacle_min_speed) with v the call's velocity column.  A candidate that is
+inside a disc at the time it gets there cannot win (f1p_lattice_set_obstacles).  The call TAKES the attribute: it is None again
+afterwards, and a call without obstacles plans without any.  Multi-GPU plans (devices=...) take none.
 """
 import warnings
 
 import numpy as np
 
 from ... import _abi
-from ..._planner import OccupancyMap, Planner, _check_tracks
+from ..._planner import OccupancyMap, Planner, _check_tracks, check_obstacle_shape, take_obstacles
 from ...control.pure_pursuit.pure_pursuit import PurePursuitPlanner
-from ...runtime import MultiContext
+from ...runtime import MultiContext, lattice_set_obstacles
 
 
 class LatticePlanner(OccupancyMap, Planner):
@@ -55,6 +61,9 @@ class LatticePlanner(OccupancyMap, Planner):
         self.check_collision = True
         self.generator = "clothoid"          # "clothoid" (the reference's G1 clothoid, :196) or "cubic" (cubic Hermite spline)
         self.prev_traj = None
+        self.obstacles = None                # moving discs of the NEXT plan / plan_batch / step_batch, which takes them: [M, 5] for plan(), [E, M, 5] for a batch
+        self.obstacle_min_speed = 0.5        # pace of ego e = 1 / max(|v_e|, obstacle_min_speed) [s/m], v_e from the call's velocity column
+        self._obstacles_set = False          # the context holds obstacles of an earlier plan
 
         self._device = device
         self._ctx = None
@@ -169,6 +178,16 @@ class LatticePlanner(OccupancyMap, Planner):
     def _bind(self, waypoints):
         return self._bind_waypoints(waypoints, 4, 'Waypoints needs to be a (Nxm), m >= 4, numpy array! (x, y, velocity, heading)')
 
+    def _obstacle_switch(self, ctx, obstacles, poses=None):
+        """the obstacles of this plan on the context (None clears what an earlier plan left there); pace from the poses' velocity column"""
+        if obstacles is not None:
+            v = np.abs(np.asarray(poses, dtype=np.float64).reshape(-1, 4)[:, 3])
+            lattice_set_obstacles(ctx, obstacles, 1.0 / np.maximum(v, float(self.obstacle_min_speed)))
+            self._obstacles_set = True
+        elif self._obstacles_set:                            # (a plan without any, after plans without any: nothing to clear)
+            lattice_set_obstacles(ctx, None)
+            self._obstacles_set = False
+
     def _cfg(self, n_goals=None):
         if n_goals is None:
             la, wd = self.lookahead_distances, self.widths
@@ -199,8 +218,12 @@ class LatticePlanner(OccupancyMap, Planner):
         Plan for one vehicle.  Returns (steering_angle, speed, selected_traj [S, 4]) like the reference (:214);
         selected_traj rows are (x, y, theta, |kappa|) in the ego frame.
         """
+        obstacles = take_obstacles(self)
+        if obstacles is not None:
+            obstacles = check_obstacle_shape(obstacles, 1, single=True)
         ctx = self._bind(waypoints)
         pose = np.array([[pose_x, pose_y, pose_theta, velocity]], dtype=np.float64)
+        self._obstacle_switch(ctx, obstacles, pose)
         plugin = self.sample_func is not None or len(self.cost_funcs) > 0 or self.selection_func not in (None, np.argmin)
         if not plugin:
             prev = None if self.prev_traj is None else self.prev_traj[None, :, 2]
@@ -231,6 +254,7 @@ class LatticePlanner(OccupancyMap, Planner):
             else:
                 all_costs = list(gen["all_cost"][0])
             best = int(self.select(all_costs))
+            self._obstacle_switch(ctx, None)                 # (the candidates are tested; tracking the selected one is the emit half, which takes no discs)
             steer, speed, status, traj = self._track(ctx, pose, cfg, goals, best, float(all_costs[best]))
         self.prev_traj = traj
         if status == _abi.ST_NO_LOOKAHEAD:
@@ -266,18 +290,26 @@ class LatticePlanner(OccupancyMap, Planner):
         tracks: K waypoint arrays [N_k x m], m >= 4 (x, y, velocity, heading), all with the same columns, and track_ids [E]: ego e
         plans along tracks[track_ids[e]] (the reference's plan(..., waypoints) per vehicle), bit-identical to a plan whose waypoints
         are that track; near_idx is the row within it.  An id outside [0, K) gives NaN steer / speed / best_cost, best_idx and
-        near_idx -1, status 4 and zero rows.  `waypoints` is then not used."""
+        near_idx -1, status 4 and zero rows.  `waypoints` is then not used.
+        self.obstacles (taken by this call: None afterwards): [E, M, 5] rows (x, y, vx, vy, r) of moving discs per ego (see the module's text); single-GPU plans only."""
+        obstacles = take_obstacles(self)
+        if obstacles is not None:
+            if devices is not None:
+                raise ValueError("obstacles are per-ego arrays of one context: multi-GPU plans (devices=...) take none")
+            obstacles = check_obstacle_shape(obstacles, np.asarray(poses).reshape(-1, 4).shape[0])
         if tracks is not None:
             _check_tracks(tracks, track_ids, 4)
             if devices is None:
                 ctx = self._context()
                 ctx.set_tracks_cached(tracks)
+                self._obstacle_switch(ctx, obstacles, poses)
                 return ctx.lattice_plan_tracks(poses, track_ids, self._cfg(), prev_theta=prev_theta, want_traj=want_traj, traj_dtype=traj_dtype)
             mc = self._multi(devices)
             mc.set_tracks_cached(tracks)
             return mc.lattice_plan_tracks(poses, track_ids, self._cfg(), prev_theta=prev_theta, want_traj=want_traj, traj_dtype=traj_dtype)
         ctx = self._bind(waypoints)
         if devices is None:
+            self._obstacle_switch(ctx, obstacles, poses)
             return ctx.lattice_plan(poses, self._cfg(), prev_theta=prev_theta, want_traj=want_traj, traj_dtype=traj_dtype)
         mc = self._multi(devices)
         mc.set_waypoints_cached(self.waypoints)
@@ -296,9 +328,13 @@ class LatticePlanner(OccupancyMap, Planner):
         """One control step for E vehicles: poses [E, 4] -> dict(steer, speed, status) (page-locked arrays owned by the context, valid
         until the next step).  Always a link of a closed loop (previous headings stay on the device); nothing but the poses and the
         three result columns touches host memory, and no copy is submitted (f1p_lattice_step_batch).  keep_traj=True keeps the winners'
-        rows on the device: fetch_traj() returns them.  tracks / track_ids: as plan_batch (f1p_lattice_step_tracks_batch)."""
-        ctx = self._bind_tracks(tracks, track_ids, 4) if tracks is not None else self._bind(waypoints)
+        rows on the device: fetch_traj() returns them.  tracks / track_ids: as plan_batch (f1p_lattice_step_tracks_batch).  self.obstacles: as plan_batch."""
+        obstacles = take_obstacles(self)
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4)
+        if obstacles is not None:
+            obstacles = check_obstacle_shape(obstacles, poses.shape[0])
+        ctx = self._bind_tracks(tracks, track_ids, 4) if tracks is not None else self._bind(waypoints)
+        self._obstacle_switch(ctx, obstacles, poses)
         self._step_shape = (poses.shape[0], self._cfg().n_stations)
         if tracks is not None:
             return ctx.lattice_step_tracks(poses, track_ids, self._cfg(), keep_traj=keep_traj)

@@ -48,7 +48,7 @@ def _content_signature(a):
 
 from .core import DeviceBuffer, F1PError, _Core, _f64, _ptr  # noqa: E402, F401
 from .comm import _Comm  # noqa: E402
-from .lattice import _Lattice  # noqa: E402
+from .lattice import _Lattice, lattice_set_obstacles, lattice_set_obstacles_dev  # noqa: E402, F401
 from .mpc import _Mpc, kmpc_set_obstacles, kmpc_set_obstacles_dev, stmpc_set_obstacles, stmpc_set_obstacles_dev  # noqa: E402, F401
 from .scene import _Scene  # noqa: E402
 from .trackers import _Trackers  # noqa: E402

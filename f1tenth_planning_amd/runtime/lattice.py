@@ -7,7 +7,43 @@ from .._abi import LatticeCfg
 from .core import _dev, _f64, _pick, _ptr, _tid
 
 
+def lattice_set_obstacles(ctx, obs, pace=None):
+    """moving discs for the lattice planner's candidates (f1p_lattice_set_obstacles) on Context `ctx`: obs [E, M, 5] fp64 rows
+    (x, y, vx, vy, r), map frame, constant velocity, M <= 16, a row with r < 0 or NaN is empty; pace [E] in s/m (seconds per metre of path: station j
+    of a candidate is reached at s_j * pace).  They stay until the next set; None clears.  (The public face of Context._lattice_set_obstacles:
+    Context's public methods are a pinned record, tests/test_runtime_calls.py.)"""
+    ctx._lattice_set_obstacles(obs, pace)
+
+
+def lattice_set_obstacles_dev(ctx, d_obs, d_pace=None, E=None, M=None):
+    """lattice_set_obstacles on device buffers [E][M][5] and [E] fp64 that the context BORROWS: keep them alive, rewrite them in place between
+    plans.  None clears."""
+    ctx._lattice_set_obstacles_dev(d_obs, d_pace, E, M)
+
+
 class _Lattice:
+    def _lattice_set_obstacles(self, obs, pace):
+        if obs is None:
+            self._check(self.lib.f1p_lattice_set_obstacles(self.h, None, None, 0, 0))
+            return
+        o = _f64(obs)
+        if o.ndim != 3 or o.shape[2] != 5:
+            raise ValueError("obstacles must be [E, M, 5] = (x, y, vx, vy, r)")
+        if pace is None:
+            raise ValueError("lattice obstacles need a pace [E] in s/m")
+        p = _f64(pace).reshape(-1)
+        if p.shape[0] != o.shape[0]:
+            raise ValueError(f"pace must be [E={o.shape[0]}]")
+        self._check(self.lib.f1p_lattice_set_obstacles(self.h, _ptr(o), _ptr(p), o.shape[0], o.shape[1]))
+
+    def _lattice_set_obstacles_dev(self, d_obs, d_pace, E, M):
+        if d_obs is None:
+            self._check(self.lib.f1p_lattice_set_obstacles_dev(self.h, None, None, 0, 0))
+            return
+        if d_pace is None or E is None or M is None:
+            raise ValueError("device arrays of obstacles need their paces, E and M")
+        self._check(self.lib.f1p_lattice_set_obstacles_dev(self.h, _dev(d_obs), _dev(d_pace), int(E), int(M)))
+
     # ---- lattice -------------------------------------------------------------------------------------------
     def lattice_plan(self, poses, cfg: LatticeCfg, goals=None, prev_theta=None, want_traj=True, want_all=False,
                      reuse_outputs=False, traj_dtype=np.float64):

@@ -436,6 +436,45 @@ int f1p_lattice_set_mode(f1p_ctx* ctx, int32_t mixed, float* d_cost32, int32_t* 
  * one to finish merges the partial winners, re-emits and tracks: no second launch); n > 0 forces n slices (tests, A/B runs). */
 int f1p_lattice_set_split(f1p_ctx* ctx, int32_t groups);
 
+/* Moving obstacles on the lattice planner's candidates.
+ * Inputs, per ego e:
+ *   - up to F1P_LATTICE_MAX_OBS = 16 slots obs[e][m] = (x, y, vx, vy, r): fp64, map frame, constant velocity;
+ *   - a slot with !(r >= 0) is empty; empty slots may sit anywhere;
+ *   - the caller folds the vehicle's own radius into r; with an oriented footprint installed, that is the footprint's disc radius;
+ *   - a pace pace[e] in s/m, meaning seconds per metre of path.
+ * Time of a station: station j has the time tau_j = s_j * pace[e].
+ *   - clothoid: s_j = (double)j * ds, with ds exactly as station_loop forms it (L / (double)max(S - 1, 1));
+ *   - cubic: s_j is the chord sum that station_loop accumulates in len up to station j, with 0 at j = 0;
+ *   - pace = 0 makes every disc a parked one.
+ * Tested points: exactly the points the occupancy test tests: every station j = 0 .. S-1, as the station point (qx, qy) in the ego
+ * frame; with an oriented footprint (and the occupancy test running: a grid loaded, cfg.check_collision on) the footprint's disc centres instead.
+ * Slot transform, once per ego and live slot, in fp64 and in this order, with (ct, st) the cos / sin of the pose heading the kernels already hold:
+ *   dx0 = x - px; dy0 = y - py
+ *   ax = ct*dx0 + st*dy0; ay = ct*dy0 - st*dx0
+ *   ux = ct*vx + st*vy; uy = ct*vy - st*vx
+ *   rr = r*r
+ * Point test, per tested point and live slot:
+ *   cx = ax + ux*tau; cy = ay + uy*tau
+ *   dx = qx - cx; dy = qy - cy; d2 = dx*dx + dy*dy
+ *   the point is blocked when !(d2 > rr)
+ * -- touching blocks; a NaN anywhere blocks: a NaN pace or slot value blocks every candidate of that ego; no contraction, as everywhere
+ * else in the library (-ffp-contract=off).
+ * Decision: a candidate with a blocked point costs +inf, exactly like one through an occupied cell; the decision, all_cost,
+ * F1P_ST_ALL_BLOCKED and the all-blocked outputs are the occupancy test's.  The disc test applies with or without a grid, and with
+ * cfg.check_collision on or off.  An ego without a live slot gets the bits of a plan without obstacles.
+ * f1p_lattice_set_obstacles copies both arrays into buffers of the context on its stream; obs == NULL or M == 0 clears.
+ * f1p_lattice_set_obstacles_dev BORROWS device arrays: the caller keeps them alive and may rewrite them in place between plans (in
+ * stream order).  The obstacles stay until the next set or clear and apply to f1p_lattice_plan_batch / _dev / _batch_f32 / _dev_f32, the
+ * four f1p_lattice_plan_tracks_*, f1p_lattice_step_batch and f1p_lattice_step_tracks_batch, with and without all_cost / all_traj (a blocked
+ * candidate's all_cost is +inf, its rows are unchanged), under every f1p_lattice_set_mode (every mode equals mode 0 bit for bit), slices
+ * and pipelined chunks (the per-ego arrays are indexed by the absolute ego), the closed-loop chain, cfg.prune and the runtime audit.
+ * Errors, nothing launched: M outside [1, 16] or a NULL pace: F1P_EINVAL; a plan whose E differs from the E the obstacles were set for:
+ * F1P_ESTATE; while obstacles are set, a candidate shard (cfg.cand_count > 0), f1p_lattice_emit_dev and f1p_lattice_set_split(> 0)
+ * (and setting obstacles while a split is forced): F1P_ESTATE.  Not covered: a MultiContext's sharded plans. */
+#define F1P_LATTICE_MAX_OBS 16
+int f1p_lattice_set_obstacles(f1p_ctx* ctx, const double* obs, const double* pace, int32_t E, int32_t M);
+int f1p_lattice_set_obstacles_dev(f1p_ctx* ctx, const double* d_obs, const double* d_pace, int32_t E, int32_t M);
+
 /* Occupancy test of the f32 filter (mixed schedule).  stations_each_side = r > 0 (default 2; a smaller r is taken when the clearance zone of r would not fit the ego's tile): the filter
  * looks up one station in 2 r + 1 in a CLEARANCE map of the active bitmap (cells whose centre is within
  * r * ds_cap + (sqrt 2 + 1) cells of an occupied or off-map cell, ds_cap = 1.2 * hypot(max look-ahead, max width) / (S - 1);

@@ -40,7 +40,12 @@ CSRC = os.path.join(ROOT, "f1tenth_planning_amd", "csrc")
 #   k_kmpc_plan_gen_t<KmpcIdxArgs, KmpcObs>   the kinematic branch of f1p_stmpc_plan_batch with f1p_stmpc_set_obstacles' discs: 4 VGPRs (12 B), reloaded in the
 #                       fp64 tails (the refinement's time-parallel disc test and the serial fp64 fallback), none in the three f32 filter loops; the
 #                       same kernel without the indirection (k_kmpc_plan_gen_obs) carries none
-BUDGET = {"ILb1E": 56, "k_kmpc_plan_gen_tIJEE": 32, "k_kmpc_plan_gen_tIJNS_11KmpcIdxArgsEEE": 52, "k_kmpc_plan_gen_tIJNS_11KmpcIdxArgsENS_7KmpcObsEEE": 12, "k_stmpc_shoot_tINS_8StCtlGenEJEE": 36, "k_kmpc_shoot_mixed": 0, "k_clothoid_g1": 8, "9k_latticeILb0E": 8,
+#   k_lattice<.., cubic, .., LatObs>   the all-fp64 kernel's cubic instantiations WITH the moving discs' argument (f1p_lattice_set_obstacles): 2 VGPRs (12 B) in
+#                       the point-footprint ones, 28 (60 B) in materialised + footprint, whose instantiation without discs carries 52 B.  While discs are set
+#                       cubic plans run here; the clothoid ones stay inside the budgets of their instantiations without discs
+BUDGET = {"9k_latticeILb0ELi1ELb0ELb0ELb0EJNS_6LatObs": 12, "9k_latticeILb0ELi1ELb0ELb0ELb1EJNS_6LatObs": 12,
+          "9k_latticeILb1ELi1ELb0ELb1ELb0EJNS_6LatObs": 60, "9k_latticeILb1ELi1ELb0ELb1ELb1EJNS_6LatObs": 60,
+          "ILb1E": 56, "k_kmpc_plan_gen_tIJEE": 32, "k_kmpc_plan_gen_tIJNS_11KmpcIdxArgsEEE": 52, "k_kmpc_plan_gen_tIJNS_11KmpcIdxArgsENS_7KmpcObsEEE": 12, "k_stmpc_shoot_tINS_8StCtlGenEJEE": 36, "k_kmpc_shoot_mixed": 0, "k_clothoid_g1": 8, "9k_latticeILb0E": 8,
           "k_lattice_filter3ILi1ELb1E": 24, "k_lattice_filter3ILi2ELb1E": 24,
           "k_lattice_filter3ILi1ELb0ELb0ELi0ELb1E": 8, "k_lattice_filter3ILi2ELb0ELb0ELi0ELb1E": 8,
           "9k_latticeILb0ELi0ELb1ELb0ELb1E": 24}   # (the instantiations WITH test hooks -- incl. the host-goal shapes; device goals, point footprint: 0)
