@@ -41,7 +41,13 @@ template <typename A, typename B, typename... X> __device__ __forceinline__ cons
 // the f32 filters' side of the test: the tested points looked up in the CLEARANCE map, cell coordinates relative to the ego's cell
 // (used through ColTestGrid / ColTestObs below)
 #define F1P_K4_CLEAR_CELLS 2.0
+// (guarded: the no-allowance variant build that shows tests/test_gpu_shoot_graze.py bites sets both to 0.0, DESIGN.md 5j "Tests")
+#ifndef F1P_K4_POS_ERR_REL
 #define F1P_K4_POS_ERR_REL 1.0e-4
+#endif
+#ifndef F1P_K4_OBS_ERR_REL
+#define F1P_K4_OBS_ERR_REL 1.0e-6     // the roundings of the obstacle's side in obs_compact's FREE threshold, relative to S (>= 16 x 2^-24)
+#endif
 struct KmpcColF {
     const uint32_t* clear;
     int wwords, n_sub, ibx, iby;
@@ -157,7 +163,7 @@ __device__ __forceinline__ void obs_compact(const KmpcObs& ob, int e, double sx,
             const double rx = iso ? c0 * dx + s0 * dy : dx, ry = iso ? c0 * dy - s0 * dx : dy;
             const double wx = iso ? c0 * vx + s0 * vy : vx, wy = iso ? c0 * vy - s0 * vx : vy;
             const double S = (fabs(rx) + fabs(ry)) + (fabs(wx) + fabs(wy)) * Tdt + r + reach;
-            const double rr = r + ((pos_err >= 0.0 ? pos_err : F1P_K4_POS_ERR_REL * reach) + 1.0e-6 * S);       // (1e-6 >= 16 x 2^-24)
+            const double rr = r + ((pos_err >= 0.0 ? pos_err : F1P_K4_POS_ERR_REL * reach) + F1P_K4_OBS_ERR_REL * S);
             live32[5 * pos] = (float)rx; live32[5 * pos + 1] = (float)ry; live32[5 * pos + 2] = (float)wx; live32[5 * pos + 3] = (float)wy;
             live32[5 * pos + 4] = (float)(rr * rr * (1.0 + 1.0e-6));               // (the rounding to f32 is inside the factor; NaN / inf: never FREE)
         }

@@ -142,6 +142,11 @@ def test_mixed_is_bit_identical_to_plain_fp64_in_all_three_regimes(ctx, orc):
                     outs.append(_plan(ctx, s["x0"], s["ref"], cfg, K.warm_start(E, T), mixed=mixed))
                 for k in KEYS + ("warm",):
                     np.testing.assert_array_equal(outs[0][k], outs[1][k], err_msg=f"{k} T={T} scene={name} n_sub={n_sub}")
+                # best_cost == NULL: a single survivor is emitted on the filter's word, unrefined
+                bare = _plan(ctx, s["x0"], s["ref"], cfg, K.warm_start(E, T), want_cost=False)
+                for k in KEYS + ("warm",):
+                    if k != "best_cost":
+                        np.testing.assert_array_equal(bare[k], outs[1][k], err_msg=f"{k} without best_cost T={T} scene={name} n_sub={n_sub}")
                 n = outs[0]["n_refined"]
                 assert (n != -99).all() and (outs[1]["n_refined"] == -1).all()
                 seen |= {"refined" if v > 1 else ("single" if v == 1 else "fallback") for v in n}

@@ -174,6 +174,10 @@ def test_mixed_is_bit_identical_to_plain_fp64_in_all_three_regimes(ctx, orc):
                     kmpc_set_obstacles(ctx, np.ascontiguousarray(obs))
                     outs = [_plan(ctx, s["x0"], s["ref"], cfg, O.warm_start(E, T), mixed=mixed) for mixed in (True, False)]
                     _same(outs[0], outs[1], msg=f"T={T} scene={name} grid={grid} M={M} n_sub={n_sub}")
+                    # best_cost == NULL: a single survivor is emitted on the filter's word, unrefined
+                    bare = _plan(ctx, s["x0"], s["ref"], cfg, O.warm_start(E, T), want_cost=False)
+                    _same(bare, outs[1], keys=tuple(k for k in KEYS + ("warm",) if k != "best_cost"),
+                          msg=f"without best_cost T={T} scene={name} grid={grid} M={M} n_sub={n_sub}")
                     n = outs[0]["n_refined"]
                     assert (n != -99).all() and (outs[1]["n_refined"] == -1).all()
                     seen |= {"refined" if v > 1 else ("single" if v == 1 else "fallback") for v in n}
