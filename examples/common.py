@@ -126,16 +126,34 @@ def obstacle_runs(args, rl, waypoints, cfg, make_planner, batch_states, set_subs
     return hits
 
 
+def add_rival_flags(ap):
+    ap.add_argument("--rivals", action="store_true", help="with --opponents M: the M opponents are found on the device from each call's states "
+                    "(planner.rivals) instead of built on the host")
+    ap.add_argument("--groups", type=int, default=0, help="with --rivals: split the pack into G independent races (vehicle e in race e %% G)")
+
+
+def rival_groups(args, E):
+    """-> (group id per vehicle or None, [E, E] +inf where two vehicles are not each other's business -- the diagonal, another race -- else 0)"""
+    if args.groups > 0 and not args.rivals:
+        raise SystemExit("--groups needs --rivals (the host construction of --opponents knows one race of all)")
+    if args.groups <= 0:
+        return None, np.diag(np.full(E, np.inf))
+    groups = (np.arange(E) % args.groups).astype(np.int32)
+    return groups, np.where((groups[:, None] != groups[None, :]) | np.eye(E, dtype=bool), np.inf, 0.0)
+
+
 def opponent_runs(args, rl, waypoints, cfg, make_planner, batch_states, gap=1.5, radius=0.45):
     """E vehicles as a pack on one course, the fast ones behind the slow ones; one closed loop with each vehicle planning as if it were alone,
     one with its M nearest other vehicles as moving obstacles predicted at constant velocity (planner.obstacles), the same start poses.
     make_planner(waypoints, cfg) -> an MPC planner with the attribute `obstacles` and plan_batch; batch_states(env) -> plan_batch's states.
     radius: the two vehicles' radii folded into the obstacle's (a point-against-disc test).  -> the smallest distance between two vehicles
-    over each run"""
-    from f1tenth_planning_amd import sim
+    over each run.  args.rivals: the opponents are found on the device from the call's own states (planner.rivals) instead of built here;
+    with args.groups = G the pack is G independent races (vehicle e in race e % G) and distances count within a race."""
+    from f1tenth_planning_amd import Rivals, sim
     E, M = args.envs, min(args.opponents, args.envs - 1, 16)
     if args.solver == "qp" or E < 2:
         raise SystemExit("--opponents needs the shooting solver and --envs >= 2")
+    groups, apart = rival_groups(args, E)
     seg = np.hypot(np.diff(rl[:, 0]), np.diff(rl[:, 1]))
     k0 = int(np.argmin(np.abs(rl[:, 3])))                                # start where the heading is far from the +-pi seam
     k = k0 + np.searchsorted(np.cumsum(np.concatenate([seg[k0:], seg[:k0]])), gap * np.arange(E))
@@ -146,15 +164,17 @@ def opponent_runs(args, rl, waypoints, cfg, make_planner, batch_states, gap=1.5,
     closest = {}
     for on in (False, True):
         planner = make_planner([w.copy() for w in waypoints], cfg)
+        if on and args.rivals:
+            planner.rivals = Rivals(count=M, radius=radius, groups=groups)      # every plan_batch finds them itself, on the device
         env = sim.make("f110_gym:f110-v0", num_agents=E)
         env.reset(poses)
         d_min, n_stop = np.inf, 0
         for it in range(args.steps):
             st = env.state[:, [0, 1, 3, 4]]                             # (x, y, v, yaw)
-            d = np.hypot(st[:, None, 0] - st[None, :, 0], st[:, None, 1] - st[None, :, 1]) + np.diag(np.full(E, np.inf))
+            d = np.hypot(st[:, None, 0] - st[None, :, 0], st[:, None, 1] - st[None, :, 1]) + apart
             d_min = min(d_min, float(d.min()))
             obs = None
-            if on:
+            if on and not args.rivals:
                 near = np.argsort(d, axis=1)[:, :M]                     # [E, M] the nearest other vehicles
                 o = st[near]
                 obs = np.stack([o[:, :, 0], o[:, :, 1], o[:, :, 2] * np.cos(o[:, :, 3]), o[:, :, 2] * np.sin(o[:, :, 3]), np.full((E, M), radius)], 2)

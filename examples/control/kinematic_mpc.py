@@ -6,7 +6,9 @@ rollouts (mpc_config.COLLISION), counting the vehicle-steps that ended in an occ
 
 --opponents M (with --envs E >= 2) starts the E vehicles as a pack on one course, the fast ones behind the slow ones, and drives the loop
 twice: each vehicle planning as if it were alone, then with its M nearest other vehicles as moving obstacles, predicted at constant
-velocity (planner.obstacles).  It reports the smallest distance between two vehicles over each run."""
+velocity (planner.obstacles).  It reports the smallest distance between two vehicles over each run.  With --rivals the opponents are not
+built here but found on the device by every plan (planner.rivals = Rivals(count=M, radius=...)); --groups G then splits the pack into G
+independent races."""
 import os
 import sys
 
@@ -34,6 +36,7 @@ def main():
     ap.add_argument("--solver", choices=["shooting", "qp"], default="shooting")
     ap.add_argument("--obstacles", type=int, default=0, help="park N obstacles (discs of 0.3 m) on the line and compare the loop with the occupancy test off / on")
     ap.add_argument("--opponents", type=int, default=0, help="with --envs E: each vehicle's M nearest other vehicles are moving obstacles of its rollouts; compares the pack with the test off / on")
+    common.add_rival_flags(ap)
     ap.add_argument("--substeps", type=int, default=4, help="tested points per time step of a rollout (mpc_config.COLLISION_SUBSTEPS)")
     args = ap.parse_args()
     rl = common.raceline(args, centerline=True)

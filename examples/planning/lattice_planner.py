@@ -3,7 +3,9 @@ pursuit on the winner (the flow LatticePlanner.plan intends, planning/lattice_pl
 
 --opponents M (with --envs E >= 2) starts the E vehicles as a pack on one course, the fast ones behind the slow ones, and drives the loop twice:
 each vehicle planning as if it were alone, then with its M nearest other vehicles as moving discs of its candidates (LatticePlanner.obstacles,
-predicted at constant velocity; f1p_lattice_set_obstacles) -- and prints the smallest distance between two vehicles over each run."""
+predicted at constant velocity; f1p_lattice_set_obstacles) -- and prints the smallest distance between two vehicles over each run.  With --rivals
+the opponents are not built here but found on the device by every plan (LatticePlanner.rivals = Rivals(count=M, radius=...)); --groups G then
+splits the pack into G independent races."""
 import os
 import sys
 
@@ -27,10 +29,11 @@ def make_planner(args, waypoints):
 
 def opponent_runs(args, waypoints, gap=1.5, radius=0.45):
     """E vehicles as a pack on one course (examples/common.py opponent_runs, for the lattice planner): radius folds both vehicles' radii into the disc's"""
-    from f1tenth_planning_amd import sim
+    from f1tenth_planning_amd import Rivals, sim
     E, M = args.envs, min(args.opponents, args.envs - 1, 16)
     if E < 2:
         raise SystemExit("--opponents needs --envs >= 2")
+    groups, apart = common.rival_groups(args, E)
     seg = np.hypot(np.diff(waypoints[:, 0]), np.diff(waypoints[:, 1]))
     k0 = int(np.argmin(np.abs(waypoints[:, 3])))
     k = (k0 + np.searchsorted(np.cumsum(np.concatenate([seg[k0:], seg[:k0]])), gap * np.arange(E))) % (len(waypoints) - 1)
@@ -40,14 +43,16 @@ def opponent_runs(args, waypoints, gap=1.5, radius=0.45):
     closest = {}
     for on in (False, True):
         planner = make_planner(args, waypoints)
+        if on and args.rivals:
+            planner.rivals = Rivals(count=M, radius=radius, groups=groups)     # every plan_batch finds them itself, on the device
         env = sim.make("f110_gym:f110-v0", num_agents=E)
         env.reset(poses0)
         d_min, n_stop = np.inf, 0
         for it in range(args.steps):
             st = env.state[:, [0, 1, 3, 4]]                            # (x, y, v, yaw)
-            d = np.hypot(st[:, None, 0] - st[None, :, 0], st[:, None, 1] - st[None, :, 1]) + np.diag(np.full(E, np.inf))
+            d = np.hypot(st[:, None, 0] - st[None, :, 0], st[:, None, 1] - st[None, :, 1]) + apart
             d_min = min(d_min, float(d.min()))
-            if on:
+            if on and not args.rivals:
                 o = st[np.argsort(d, axis=1)[:, :M]]                   # [E, M] the nearest other vehicles
                 planner.obstacles = np.stack([o[:, :, 0], o[:, :, 1], o[:, :, 2] * np.cos(o[:, :, 3]), o[:, :, 2] * np.sin(o[:, :, 3]), np.full((E, M), radius)], 2)
             out = planner.plan_batch(np.column_stack([st[:, 0], st[:, 1], st[:, 3], st[:, 2]]), want_traj=False)
@@ -65,6 +70,7 @@ def main():
     ap.add_argument("--generator", choices=["clothoid", "cubic"], default="clothoid")
     ap.add_argument("--tracks", type=int, default=0, help="N agents on N lanes offset sideways from the raceline, one track set")
     ap.add_argument("--opponents", type=int, default=0, help="with --envs E: each vehicle's M nearest other vehicles are moving obstacles of its candidates; compares the pack with the test off / on")
+    common.add_rival_flags(ap)
     args = ap.parse_args()
     waypoints = common.raceline(args)
     if args.opponents > 0:

@@ -11,3 +11,5 @@ planner classes kept as thin ctypes shims:
 There is no CPU fallback: the HIP library and a GPU are required.
 """
 __version__ = "0.1.0"
+
+from ._rivals import Rivals  # noqa: E402, F401  (planner.rivals = Rivals(count=M, radius=r): DESIGN.md 5m)

@@ -18,6 +18,7 @@ MAX_WIDTHS = 64
 COMM_ID_BYTES = 128
 LA_IDX_NONE = -(2 ** 31)
 GEN_CLOTHOID, GEN_CUBIC = 0, 1
+RIVALS_XYVYAW, RIVALS_POSE, RIVALS_ST7 = 0, 1, 2      # state layouts of f1p_rivals_*: (x, y, v, yaw), (x, y, theta, v), the dynamic MPC's 7-state
 
 
 class LatticeCfg(C.Structure):
@@ -299,6 +300,9 @@ PROTOTYPES = {
     "f1p_stmpc_warm_reset": (C.c_int, [_P]),
     "f1p_stmpc_warm_get": (C.c_int, [_P, _P, _P, _I, _I, _I]),
     "f1p_stmpc_warm_set": (C.c_int, [_P, _P, _P, _I, _I, _I]),
+    "f1p_rivals_set_groups": (C.c_int, [_P, _P, _I]),
+    "f1p_rivals_dev": (C.c_int, [_P, _P, _I, _I, _I, _D, _D, _D, _P, _P, _P]),
+    "f1p_rivals_batch": (C.c_int, [_P, _P, _I, _I, _I, _D, _D, _D, _P, _P, _P]),
     "f1p_comm_unique_id": (C.c_int, [_P, _P]),
     "f1p_comm_init": (C.c_int, [_P, _P, _I, _I]),
     "f1p_comm_destroy": (C.c_int, [_P]),

@@ -5,6 +5,7 @@ import os
 import numpy as np
 
 from . import _abi
+from ._rivals import check_rivals
 from .runtime import Context
 
 NO_WAYPOINTS = 'Please set waypoints to track during planner instantiation or when calling plan()'
@@ -222,3 +223,10 @@ class MPCPlanner(OccupancyMap, Planner):
             if not 1 <= int(getattr(c, name)) <= 16:
                 raise ValueError(f"{name} must be in [1, 16]")
         return o
+
+    def _check_rivals(self, rivals, E, obstacles):
+        """the attribute `rivals` of a plan_batch over E egos; ValueError before anything touches the GPU"""
+        check_rivals(rivals, E, obstacles, self.config.SOLVER)
+        for name in self._SUBSTEPS:
+            if not 1 <= int(getattr(self.config, name)) <= 16:
+                raise ValueError(f"{name} must be in [1, 16]")

@@ -1,0 +1,72 @@
+"""planner.rivals: the vehicles of a batch as each other's moving obstacles, found on the device (include/f1p.h "Rivals").
+
+`Rivals` is what a user assigns to the attribute `rivals` of KMPCPlanner, STMPCPlanner or LatticePlanner; `RivalFeed` is the device side one
+planner keeps for it: the state, slot and pace buffers per (context, E, M) and the races on the context."""
+from dataclasses import dataclass
+
+import numpy as np
+
+from .runtime import rivals_dev, rivals_set_groups
+
+
+@dataclass(frozen=True, eq=False)
+class Rivals:
+    """planner.rivals = Rivals(count=M, radius=r): while set, every plan_batch (and the lattice's step_batch) tests each ego against its
+    `count` nearest other vehicles of the call's own states, as discs of `radius` (both vehicles' radii folded in) at constant velocity.
+    reach: vehicles farther than this [m] are left out.  groups: int [E], egos with the same id >= 0 are one race, an ego with a negative id
+    has no rivals and is nobody's rival; None: one race of all.  Persistent, unlike `obstacles`: it stays until set to None."""
+    count: int
+    radius: float
+    reach: float = float("inf")
+    groups: object = None
+
+
+SINGLE_EGO = "plan() drives one ego, which has no rivals: set planner.rivals = None, or use plan_batch()"
+
+
+def check_rivals(rivals, E, obstacles=None, solver=None, devices=None):
+    """ValueError before anything touches the GPU"""
+    if obstacles is not None:
+        raise ValueError("planner.rivals and planner.obstacles in one call: the rivals fill the obstacle slots, set one of them to None")
+    if solver == "qp":
+        raise ValueError("rivals are tested on the shooting solver's rollouts; SOLVER='qp' takes none")
+    if devices is not None:
+        raise ValueError("rivals are per-ego arrays of one context: multi-GPU plans (devices=...) take none")
+    if not 1 <= int(rivals.count) <= 16:
+        raise ValueError(f"Rivals.count must be in [1, 16], not {rivals.count!r}")
+    if not float(rivals.radius) >= 0.0 or not float(rivals.reach) >= 0.0:
+        raise ValueError("Rivals.radius and Rivals.reach must be >= 0")
+    if rivals.groups is not None and np.asarray(rivals.groups).reshape(-1).shape[0] != E:
+        raise ValueError(f"Rivals.groups must hold one id per ego ({E}), not {np.asarray(rivals.groups).reshape(-1).shape[0]}")
+
+
+class RivalFeed:
+    """layout: the planner's state layout ("xyvyaw", "pose", "st7"); clear(ctx): the planner's *_set_obstacles_dev(ctx, None) -- the context
+    must stop borrowing the slot buffer before it is freed"""
+
+    def __init__(self, layout, clear):
+        self.layout, self.clear = layout, clear
+        self.ncol = 7 if layout == "st7" else 4
+        self._key, self._bufs, self._groups = None, None, None
+
+    def run(self, ctx, rivals, states, min_speed=0.5):
+        """upload the call's states [E, ncol] and fill the slots (and paces) from them, asynchronously -> (d_obs, d_pace, E, M)"""
+        E, M = states.shape[0], int(rivals.count)
+        key = (id(ctx), E, M)
+        if self._key != key:
+            if self._bufs is not None:
+                if self._bufs[0].ctx is ctx:
+                    self.clear(ctx)                          # first: the context borrows d_obs / d_pace
+                for b in self._bufs:
+                    b.free()
+            self._bufs = (ctx.alloc(8 * self.ncol * E), ctx.alloc(40 * E * M), ctx.alloc(8 * E))
+            self._key, self._groups = key, None
+        g = None if rivals.groups is None else np.ascontiguousarray(rivals.groups, dtype=np.int32).reshape(-1)
+        gkey = (id(ctx), None if g is None else g.tobytes())
+        if self._groups != gkey:
+            rivals_set_groups(ctx, g)
+            self._groups = gkey
+        d_states, d_obs, d_pace = self._bufs
+        d_states.upload(states)
+        rivals_dev(ctx, d_states, self.layout, E, M, float(rivals.radius), d_obs, d_pace, None, float(rivals.reach), float(min_speed))
+        return d_obs, d_pace, E, M

@@ -17,6 +17,10 @@ planner.obstacles = [M, 5] before plan() / [E, M, 5] before plan_batch() (shooti
 an ego takes, against moving discs: rows (x, y, vx, vy, r) in the map frame at constant velocity, M <= 16, r < 0 or NaN = an empty slot,
 row e of a batch for ego e of `states`.  A rollout that is inside a disc at the time it gets there cannot win (f1p_stmpc_set_obstacles,
 DESIGN.md 5k).  The next plan / plan_batch call TAKES the attribute: it is None again afterwards -- KMPCPlanner's contract.
+
+planner.rivals = Rivals(count=M, radius=r[, reach, groups]) (shooting only, plan_batch only): while it is set, every plan_batch finds each
+ego's M nearest other vehicles of its race among the call's own states on the device (heading yaw + beta; f1p_rivals_dev) and
+tests the rollouts of both branches against them.  Persistent until set to None; not together with `obstacles`.
 """
 import warnings
 from dataclasses import dataclass, field
@@ -25,7 +29,8 @@ import numpy as np
 
 from ... import _abi
 from ..._planner import MPCPlanner, _course_columns, _diag, _track_columns, kin_cfg_struct, qp_opts
-from ...runtime import Context, kmpc_set_obstacles, stmpc_set_obstacles
+from ..._rivals import SINGLE_EGO, RivalFeed
+from ...runtime import Context, kmpc_set_obstacles, stmpc_set_obstacles, stmpc_set_obstacles_dev
 from ..kinematic_mpc.kinematic_mpc import State  # noqa: F401  (same 7-field dataclass, :89-98)
 
 
@@ -107,19 +112,26 @@ class STMPCPlanner(MPCPlanner):
         self._inflate = 0.0
         self.obstacles = None              # moving discs of the NEXT plan, which takes them: [M, 5] for plan(), [E, M, 5] for plan_batch()
         self._obstacles_set = [False, False]   # the context holds obstacles of an earlier plan: the kmpc state, the stmpc state
+        self.rivals = None                 # Rivals(...): every plan_batch tests each ego against its nearest other vehicles; persistent
+        self._rival_feed = RivalFeed("st7", lambda ctx: stmpc_set_obstacles_dev(ctx, None))
         self._check_solver()
 
-    def _collision_switch(self, ctx, obstacles=None, kinematic=False):
+    def _collision_switch(self, ctx, obstacles=None, kinematic=False, rivals=None, states=None):
         """the planner's context follows mpc_config: the stmpc switch (plan_batch, plan()'s dynamic branch) and, for plan()'s kinematic
         branch through ctx.kmpc_shoot, the kmpc switch with COLLISION_SUBSTEPS_K.  The obstacles of this plan (None clears them) go to
         the stmpc state, or (kinematic: plan()'s kinematic branch) to the kmpc state; the substep counts serve both tests"""
         c = self.config
         if c.SOLVER != "qp":
             on = bool(c.COLLISION)
-            sub = on or obstacles is not None
+            sub = on or obstacles is not None or rivals is not None
             ctx.stmpc_set_collision(on, int(c.COLLISION_SUBSTEPS) if sub else 1, int(c.COLLISION_SUBSTEPS_K) if sub else 2)
             ctx.kmpc_set_collision(on, int(c.COLLISION_SUBSTEPS_K) if sub else 1)
             for k, setter in ((0, kmpc_set_obstacles), (1, stmpc_set_obstacles)):
+                if k == 1 and rivals is not None:                 # (plan_batch: the stmpc state; the slots are filled on the device from the call's states)
+                    d_obs, _, E, M = self._rival_feed.run(ctx, rivals, states)
+                    stmpc_set_obstacles_dev(ctx, d_obs, E, M)
+                    self._obstacles_set[k] = True
+                    continue
                 o = obstacles if k == (0 if kinematic else 1) else None
                 if o is not None or self._obstacles_set[k]:       # (a plan without any, after plans without any: nothing to clear)
                     setter(ctx, o)
@@ -197,12 +209,16 @@ class STMPCPlanner(MPCPlanner):
         obstacles = self._take_obstacles()
         if obstacles is not None:
             obstacles = self._check_obstacles(obstacles, np.asarray(states).reshape(-1, 7).shape[0])
+        rivals = self.rivals
+        if rivals is not None:
+            self._check_rivals(rivals, np.asarray(states).reshape(-1, 7).shape[0], obstacles)
         if self.config.SOLVER != "qp":
             if tracks is not None:
                 raise ValueError("plan_batch with tracks needs SOLVER='qp'")
             ctx = self._bind(waypoints)
-            self._collision_switch(ctx, obstacles)
-            return self._shoot(ctx, np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 7), want_u=want_u)
+            x0 = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 7)
+            self._collision_switch(ctx, obstacles, rivals=rivals, states=x0)
+            return self._shoot(ctx, x0, want_u=want_u)
         if tracks is not None:
             cols = _track_columns(tracks, track_ids)
             ctx = self._context()
@@ -231,6 +247,8 @@ class STMPCPlanner(MPCPlanner):
         taken, an all-blocked plan warns and returns (0.0, 0.0) likewise."""
         self._check_collision()
         obstacles = self._check_obstacles(self._take_obstacles(), 1, single=True)
+        if self.rivals is not None:
+            raise ValueError(SINGLE_EGO)
         ctx = self._bind(waypoints)
         c = self.config
         st = np.asarray(states, dtype=np.float64)

@@ -22,6 +22,10 @@ disc at the time it gets there cannot win (f1p_kmpc_set_obstacles)
 it is None again afterwards, so obstacles are given per call, as a keyword argument would be, and a call without them plans without any.
 The caller folds the vehicle's own radius into r.  (An attribute, not a keyword: the signatures of plan and plan_batch are the
 reference's and a pinned record, tests/test_runtime_calls.py.)
+
+planner.rivals = Rivals(count=M, radius=r[, reach, groups]) (shooting only, plan_batch only) makes the vehicles of a batch each other's
+obstacles: while it is set, every plan_batch finds each ego's M nearest other vehicles of its race among the call's own x0 ON THE DEVICE
+(f1p_rivals_dev) and tests the rollouts against them as above.  Persistent until set to None; not together with `obstacles`.
 """
 import warnings
 from dataclasses import dataclass, field
@@ -31,7 +35,8 @@ import numpy as np
 from ... import _abi
 from ..._planner import MPCPlanner, _track_columns, qp_opts
 from ..._planner import kin_cfg_struct as _cfg_struct
-from ...runtime import Context, kmpc_set_obstacles
+from ..._rivals import SINGLE_EGO, RivalFeed
+from ...runtime import Context, kmpc_set_obstacles, kmpc_set_obstacles_dev
 
 
 @dataclass
@@ -119,14 +124,22 @@ class KMPCPlanner(MPCPlanner):
         self._inflate = 0.0
         self.obstacles = None              # moving discs of the NEXT plan, which takes them: [M, 5] for plan(), [E, M, 5] for plan_batch()
         self._obstacles_set = False        # the context holds obstacles of an earlier plan
+        self.rivals = None                 # Rivals(...): every plan_batch tests each ego against its nearest other vehicles; persistent
+        self._rival_feed = RivalFeed("xyvyaw", lambda ctx: kmpc_set_obstacles_dev(ctx, None))
         self._check_solver()
 
-    def _collision_switch(self, ctx, obstacles=None):
-        """the occupancy switch and the obstacles of this plan (None clears them); COLLISION_SUBSTEPS serves both tests"""
+    def _collision_switch(self, ctx, obstacles=None, rivals=None, x0=None):
+        """the occupancy switch and the obstacles of this plan (None clears them); COLLISION_SUBSTEPS serves both tests.  rivals: the slots
+        are filled on the device from the call's x0 and the context borrows them"""
         c = self.config
         if c.SOLVER != "qp":
-            ctx.kmpc_set_collision(bool(c.COLLISION), int(c.COLLISION_SUBSTEPS) if (c.COLLISION or obstacles is not None) else 1)
-            if obstacles is not None or self._obstacles_set:       # (a plan without any, after plans without any: nothing to clear)
+            tested = obstacles is not None or rivals is not None
+            ctx.kmpc_set_collision(bool(c.COLLISION), int(c.COLLISION_SUBSTEPS) if (c.COLLISION or tested) else 1)
+            if rivals is not None:
+                d_obs, _, E, M = self._rival_feed.run(ctx, rivals, x0)
+                kmpc_set_obstacles_dev(ctx, d_obs, E, M)
+                self._obstacles_set = True
+            elif obstacles is not None or self._obstacles_set:     # (a plan without any, after plans without any: nothing to clear)
                 kmpc_set_obstacles(ctx, obstacles)
                 self._obstacles_set = obstacles is not None
 
@@ -158,6 +171,8 @@ class KMPCPlanner(MPCPlanner):
         """
         self._check_collision()
         obstacles = self._check_obstacles(self._take_obstacles(), 1, single=True)
+        if self.rivals is not None:
+            raise ValueError(SINGLE_EGO)
         ctx = self._bind(waypoints, fold_yaw=float(states[4]))
         self._collision_switch(ctx, obstacles)
         vehicle_state = State(x=states[0], y=states[1], delta=states[2], v=states[3], yaw=states[4], yawrate=states[5],
@@ -214,18 +229,22 @@ class KMPCPlanner(MPCPlanner):
         follows tracks[track_ids[e]]; `waypoints` is then not used.  The references come from one k_kmpc_ref_tracks launch (an id
         outside [0, K) gives NaN rows, hence NaN outputs and QP status 3 for that ego) and go to the same solvers.
         self.obstacles (taken by this call: None afterwards): [E, M, 5] rows (x, y, vx, vy, r) of moving discs per ego (M <= 16, r < 0 or NaN: empty), tested at COLLISION_SUBSTEPS
-        points per step whether COLLISION is on or not; None: none.  All-blocked egos as with COLLISION."""
+        points per step whether COLLISION is on or not; None: none.  All-blocked egos as with COLLISION.
+        self.rivals (persistent): Rivals(count, radius[, reach, groups]): each ego's nearest other vehicles of x0 take the obstacle slots."""
         self._check_collision()
         if self.config.SOLVER == "qp" and controls is not None:
             raise ValueError("controls are candidates of the shooting solver; SOLVER='qp' takes none")
         obstacles = self._take_obstacles()
         if obstacles is not None:
             obstacles = self._check_obstacles(obstacles, np.asarray(x0).reshape(-1, 4).shape[0])
+        rivals = self.rivals
+        if rivals is not None:
+            self._check_rivals(rivals, np.asarray(x0).reshape(-1, 4).shape[0], obstacles)
         if tracks is not None:
-            return self._plan_tracks(x0, tracks, track_ids, controls, want_seq, obstacles)
+            return self._plan_tracks(x0, tracks, track_ids, controls, want_seq, obstacles, rivals)
         ctx = self._bind(waypoints)
-        self._collision_switch(ctx, obstacles)
         x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, 4)
+        self._collision_switch(ctx, obstacles, rivals, x0)
         if self.config.SOLVER == "qp":
             return self._qp(ctx, x0, want_u=want_seq)
         if controls is None:
@@ -235,14 +254,14 @@ class KMPCPlanner(MPCPlanner):
         ref = ctx.kmpc_ref(x0, c.TK, c.DTK, c.dlk)
         return ctx.kmpc_shoot(x0, ref, controls, cfg)
 
-    def _plan_tracks(self, x0, tracks, track_ids, controls, want_seq, obstacles=None):
+    def _plan_tracks(self, x0, tracks, track_ids, controls, want_seq, obstacles=None, rivals=None):
         cols = _track_columns(tracks, track_ids)
         ctx = self._context()
-        self._collision_switch(ctx, obstacles)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, 4)
+        self._collision_switch(ctx, obstacles, rivals, x0)
         ctx.kmpc_set_yaw_fixup(True)                           # a batch: per-ego fold of the gathered headings, the courses stay as given
         ctx.set_tracks_cached(cols, cols=(0, 1, 2, 3))
         c = self.config
-        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, 4)
         E, T = x0.shape[0], c.TK
         ids = Context._ids(track_ids, E)
         if controls is not None:

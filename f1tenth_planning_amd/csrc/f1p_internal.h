@@ -173,6 +173,12 @@ struct f1p_ctx {
     int lat_obs_e0 = 0;
     char* d_lat_obs_xf = nullptr; size_t lat_obs_xf_bytes = 0;   // mixed schedule: transformed live slots [E][16][5] fp64 | live counts [E] (k_lattice_filter3 -> k_lattice_refine)
 
+    // rivals (f1p_rivals_set_groups): the races' members sorted by (group, ego) and each ego's [begin, end) in that list; riv_E == 0:
+    // no groups, one race of all
+    int32_t* d_riv_mem = nullptr;      // [riv_cap]
+    int32_t* d_riv_rng = nullptr;      // [riv_cap][2]
+    int riv_E = 0, riv_cap = 0;
+
     // closed-loop mode (f1p_lattice_set_closed_loop): the heading column of every plan's winners stays on the device and is the next
     // plan's prev_theta (get_similarity_cost's previous path, lattice_planner.py:287-296) -- two buffers used alternately
     bool lattice_closed_loop = false;
@@ -321,6 +327,9 @@ int launch_lqr_tracks(f1p_ctx* ctx, const double* d_states, const int32_t* d_tid
                       const double* q, double r, int max_iter, double eps, double* d_steer, double* d_speed, int32_t* d_near);
 int launch_kmpc_ref_tracks(f1p_ctx* ctx, const double* d_states, const int32_t* d_tid, int E, int horizon, double dt, double dl, double* d_ref);
 int launch_stmpc_ref_tracks(f1p_ctx* ctx, const double* d_states, const int32_t* d_tid, int E, int horizon, double dt, double dl, double* d_ref);
+// k_rivals.hip: d_mem / d_rng null: one race of all E
+int launch_rivals(f1p_ctx* ctx, const double* d_states, int layout, int E, int M, double radius, double reach2, double min_speed,
+                  const int32_t* d_mem, const int32_t* d_rng, double* d_obs, double* d_pace, int32_t* d_idx);
 int launch_argmin_key(f1p_ctx* ctx, const double* d_cost, uint64_t* d_key, int E);
 int launch_argmin_mask(f1p_ctx* ctx, const uint64_t* d_own, const uint64_t* d_min, const int32_t* d_idx, int32_t* d_masked,
                        double* d_cost_out, int E);

@@ -22,6 +22,11 @@ against discs (x, y, vx, vy, r) -- map frame, constant velocity, the vehicle's o
 stations the occupancy test tests; station j is reached at s_j / max(|v|, obstacle_min_speed) with v the call's velocity column.  A candidate that is
 inside a disc at the time it gets there cannot win (f1p_lattice_set_obstacles).  The call TAKES the attribute: it is None again
 afterwards, and a call without obstacles plans without any.  Multi-GPU plans (devices=...) take none.
+
+Rivals: `planner.rivals = Rivals(count=M, radius=r[, reach, groups])` makes the vehicles of a batch each other's obstacles: while it is set,
+every plan_batch() / step_batch() finds each ego's M nearest other vehicles of its race among the call's own poses ON THE DEVICE, with the pace
+1 / max(|v|, obstacle_min_speed) (f1p_rivals_dev, DESIGN.md 5m), and tests the candidates against them as above.  Persistent until set to None;
+not together with `obstacles`, not for plan() (one ego has no rivals), not for multi-GPU plans.
 """
 import warnings
 
@@ -30,7 +35,8 @@ import numpy as np
 from ... import _abi
 from ..._planner import OccupancyMap, Planner, _check_tracks, check_obstacle_shape, take_obstacles
 from ...control.pure_pursuit.pure_pursuit import PurePursuitPlanner
-from ...runtime import MultiContext, lattice_set_obstacles
+from ..._rivals import SINGLE_EGO, RivalFeed, check_rivals
+from ...runtime import MultiContext, lattice_set_obstacles, lattice_set_obstacles_dev
 
 
 class LatticePlanner(OccupancyMap, Planner):
@@ -64,6 +70,8 @@ class LatticePlanner(OccupancyMap, Planner):
         self.obstacles = None                # moving discs of the NEXT plan / plan_batch / step_batch, which takes them: [M, 5] for plan(), [E, M, 5] for a batch
         self.obstacle_min_speed = 0.5        # pace of ego e = 1 / max(|v_e|, obstacle_min_speed) [s/m], v_e from the call's velocity column
         self._obstacles_set = False          # the context holds obstacles of an earlier plan
+        self.rivals = None                   # Rivals(...): every plan_batch / step_batch tests each ego against its nearest other vehicles; persistent
+        self._rival_feed = RivalFeed("pose", lambda ctx: lattice_set_obstacles_dev(ctx, None))
 
         self._device = device
         self._ctx = None
@@ -178,9 +186,15 @@ class LatticePlanner(OccupancyMap, Planner):
     def _bind(self, waypoints):
         return self._bind_waypoints(waypoints, 4, 'Waypoints needs to be a (Nxm), m >= 4, numpy array! (x, y, velocity, heading)')
 
-    def _obstacle_switch(self, ctx, obstacles, poses=None):
-        """the obstacles of this plan on the context (None clears what an earlier plan left there); pace from the poses' velocity column"""
-        if obstacles is not None:
+    def _obstacle_switch(self, ctx, obstacles, poses=None, rivals=None):
+        """the obstacles of this plan on the context (None clears what an earlier plan left there); pace from the poses' velocity column.
+        rivals: slots and paces are filled on the device from the call's poses and the context borrows them"""
+        if rivals is not None:
+            d_obs, d_pace, E, M = self._rival_feed.run(ctx, rivals, np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4),
+                                                       min_speed=float(self.obstacle_min_speed))
+            lattice_set_obstacles_dev(ctx, d_obs, d_pace, E, M)
+            self._obstacles_set = True
+        elif obstacles is not None:
             v = np.abs(np.asarray(poses, dtype=np.float64).reshape(-1, 4)[:, 3])
             lattice_set_obstacles(ctx, obstacles, 1.0 / np.maximum(v, float(self.obstacle_min_speed)))
             self._obstacles_set = True
@@ -221,6 +235,8 @@ class LatticePlanner(OccupancyMap, Planner):
         obstacles = take_obstacles(self)
         if obstacles is not None:
             obstacles = check_obstacle_shape(obstacles, 1, single=True)
+        if self.rivals is not None:
+            raise ValueError(SINGLE_EGO)
         ctx = self._bind(waypoints)
         pose = np.array([[pose_x, pose_y, pose_theta, velocity]], dtype=np.float64)
         self._obstacle_switch(ctx, obstacles, pose)
@@ -297,19 +313,22 @@ class LatticePlanner(OccupancyMap, Planner):
             if devices is not None:
                 raise ValueError("obstacles are per-ego arrays of one context: multi-GPU plans (devices=...) take none")
             obstacles = check_obstacle_shape(obstacles, np.asarray(poses).reshape(-1, 4).shape[0])
+        rivals = self.rivals
+        if rivals is not None:
+            check_rivals(rivals, np.asarray(poses).reshape(-1, 4).shape[0], obstacles, devices=devices)
         if tracks is not None:
             _check_tracks(tracks, track_ids, 4)
             if devices is None:
                 ctx = self._context()
                 ctx.set_tracks_cached(tracks)
-                self._obstacle_switch(ctx, obstacles, poses)
+                self._obstacle_switch(ctx, obstacles, poses, rivals)
                 return ctx.lattice_plan_tracks(poses, track_ids, self._cfg(), prev_theta=prev_theta, want_traj=want_traj, traj_dtype=traj_dtype)
             mc = self._multi(devices)
             mc.set_tracks_cached(tracks)
             return mc.lattice_plan_tracks(poses, track_ids, self._cfg(), prev_theta=prev_theta, want_traj=want_traj, traj_dtype=traj_dtype)
         ctx = self._bind(waypoints)
         if devices is None:
-            self._obstacle_switch(ctx, obstacles, poses)
+            self._obstacle_switch(ctx, obstacles, poses, rivals)
             return ctx.lattice_plan(poses, self._cfg(), prev_theta=prev_theta, want_traj=want_traj, traj_dtype=traj_dtype)
         mc = self._multi(devices)
         mc.set_waypoints_cached(self.waypoints)
@@ -333,8 +352,11 @@ class LatticePlanner(OccupancyMap, Planner):
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4)
         if obstacles is not None:
             obstacles = check_obstacle_shape(obstacles, poses.shape[0])
+        rivals = self.rivals
+        if rivals is not None:
+            check_rivals(rivals, poses.shape[0], obstacles)
         ctx = self._bind_tracks(tracks, track_ids, 4) if tracks is not None else self._bind(waypoints)
-        self._obstacle_switch(ctx, obstacles, poses)
+        self._obstacle_switch(ctx, obstacles, poses, rivals)
         self._step_shape = (poses.shape[0], self._cfg().n_stations)
         if tracks is not None:
             return ctx.lattice_step_tracks(poses, track_ids, self._cfg(), keep_traj=keep_traj)

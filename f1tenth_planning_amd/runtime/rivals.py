@@ -1,0 +1,54 @@
+"""Context's rivals: each ego's nearest other vehicles of its race as the moving discs the three sampling planners test
+(csrc/f1p_rivals.hip, csrc/k_rivals.hip; the rule: include/f1p.h "Rivals")."""
+import numpy as np
+
+from .. import _abi
+from .core import _dev, _f64, _ptr
+
+LAYOUTS = {"xyvyaw": _abi.RIVALS_XYVYAW, "pose": _abi.RIVALS_POSE, "st7": _abi.RIVALS_ST7}
+
+
+def rivals_set_groups(ctx, groups):
+    """the races of the following rivals calls on Context `ctx` (f1p_rivals_set_groups): groups int32 [E], egos with the same id >= 0 are one
+    race, an ego with a negative id has no rivals and is nobody's rival; None: one race of all.  (The public face of
+    Context._rivals_set_groups: Context's public methods are a pinned record, tests/test_runtime_calls.py.)"""
+    ctx._rivals_set_groups(groups)
+
+
+def rivals(ctx, states, layout, M, radius, reach=np.inf, min_speed=0.5):
+    """each ego's M nearest other vehicles of its race within `reach`, as discs of `radius` moving at constant velocity (f1p_rivals_batch):
+    states [E, 4] = (x, y, v, yaw) for layout "xyvyaw" / RIVALS_XYVYAW, (x, y, theta, v) for "pose", [E, 7] for "st7" ->
+    dict(obs [E, M, 5] = (x, y, vx, vy, r) with (0, 0, 0, 0, -1) in the empty slots, pace [E] = 1 / max(|v|, min_speed), idx int32 [E, M] = the
+    chosen vehicles, -1 in the empty slots)"""
+    return ctx._rivals(states, layout, M, radius, reach, min_speed)
+
+
+def rivals_dev(ctx, d_states, layout, E, M, radius, d_obs, d_pace=None, d_idx=None, reach=np.inf, min_speed=0.5):
+    """rivals on device buffers, asynchronous on the context's stream (f1p_rivals_dev): d_obs [E][M][5] fp64 (and d_pace [E]) may be the very
+    arrays kmpc_set_obstacles_dev / stmpc_set_obstacles_dev / lattice_set_obstacles_dev borrow"""
+    ctx._rivals_dev(d_states, layout, E, M, radius, d_obs, d_pace, d_idx, reach, min_speed)
+
+
+def _layout(layout):
+    return LAYOUTS[layout] if isinstance(layout, str) else int(layout)
+
+
+class _Rivals:
+    def _rivals_set_groups(self, groups):
+        if groups is None:
+            self._check(self.lib.f1p_rivals_set_groups(self.h, None, 0))
+            return
+        g = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+        self._check(self.lib.f1p_rivals_set_groups(self.h, _ptr(g), g.shape[0]))
+
+    def _rivals(self, states, layout, M, radius, reach, min_speed):
+        layout = _layout(layout)
+        st = _f64(states, (-1, 7 if layout == _abi.RIVALS_ST7 else 4)); E = st.shape[0]; M = int(M)
+        out = dict(obs=np.empty((E, max(M, 0), 5)), pace=np.empty(E), idx=np.empty((E, max(M, 0)), np.int32))
+        self._check(self.lib.f1p_rivals_batch(self.h, _ptr(st), layout, E, M, float(radius), float(reach), float(min_speed), _ptr(out["obs"]),
+                                              _ptr(out["pace"]), _ptr(out["idx"])))
+        return out
+
+    def _rivals_dev(self, d_states, layout, E, M, radius, d_obs, d_pace, d_idx, reach, min_speed):
+        self._check(self.lib.f1p_rivals_dev(self.h, _dev(d_states), _layout(layout), int(E), int(M), float(radius), float(reach), float(min_speed),
+                                            _dev(d_obs), _dev(d_pace), _dev(d_idx)))

@@ -915,6 +915,62 @@ int f1p_stmpc_warm_get(f1p_ctx* ctx, float* warm, int32_t* tag, int32_t E, int32
 int f1p_stmpc_warm_set(f1p_ctx* ctx, const float* warm, const int32_t* tag, int32_t E, int32_t T, int32_t TK);
 
 /* ------------------------------------------------------------------------------------------------
+ * Rivals: each ego's nearest other vehicles as moving discs, on the device (csrc/k_rivals.hip).  The output is the
+ * [E][M][5] array (and, for the lattice, the pace [E]) that f1p_kmpc_set_obstacles_dev, f1p_stmpc_set_obstacles_dev and
+ * f1p_lattice_set_obstacles_dev borrow.
+ * Inputs.
+ *   - E vehicle states in one of three layouts:
+ *       F1P_RIVALS_XYVYAW = 0: [E][4] = (x, y, v, yaw), the kinematic MPC's x0; heading h = yaw.
+ *       F1P_RIVALS_POSE = 1: [E][4] = (x, y, theta, v), the lattice poses; h = theta.
+ *       F1P_RIVALS_ST7 = 2: [E][7] = (x, y, delta, v, yaw, yaw_rate, beta), the dynamic MPC's x0; h = yaw + beta, one fp64 add.
+ *   - An optional group id per ego, group[e] int32, any values (f1p_rivals_set_groups).
+ *       Egos with the same id >= 0 are one race.
+ *       An ego with a negative id has no rivals and is nobody's rival.
+ *       No groups means one race of all E.
+ *   - M in [1, 16], radius >= 0, reach >= 0 (+inf allowed), min_speed > 0.
+ * Selection, for ego i with group[i] >= 0, over every j != i with group[j] == group[i].
+ *   - dx = x_j - x_i; dy = y_j - y_i; d2 = dx*dx + dy*dy, in fp64, no contraction.
+ *   - j is a candidate unless d2 > reach*reach.
+ *       reach*reach is formed once on the host in fp64.
+ *       A NaN d2 is a candidate.
+ *   - Candidates are ordered by the project's np.argmin rule, applied repeatedly: NaN d2 first, then ascending d2, then ascending j
+ *     on equal bits.
+ *       Coincident vehicles (d2 == 0) are ordinary candidates.
+ *   - The first min(M, #candidates) become slots 0, 1, ... in that order.
+ *   - The remaining slots are empty.
+ * Slot values.
+ *   - Live slot: (x_j, y_j, v_j*cos(h_j), v_j*sin(h_j), radius).
+ *       x, y and r are bit copies.
+ *       The trig is the full-range device sincos, not sincos_core, because a heading is unbounded here.
+ *   - Empty slot: (0, 0, 0, 0, -1.0).
+ * Other outputs.
+ *   - idx[e][m] int32: the chosen j, or -1.
+ *   - pace[e]: m = fabs(v_e); if !(m >= min_speed) then m = (m != m) ? m : min_speed; pace = 1.0 / m.
+ *       Bit-equal to 1.0 / np.maximum(np.abs(v), min_speed), which is what LatticePlanner forms on the host for explicit obstacles.
+ *       A NaN speed gives a NaN pace, which blocks that ego's candidates.
+ * NaN policy: NaN sorts first and therefore blocks, the library's rule everywhere ("a NaN anywhere blocks").  A vehicle with a NaN
+ * position has a NaN d2 to every member of its race (its own rivals included), so it takes slot 0 of each of them and its NaN slot
+ * values block every rollout / candidate there: ONE vehicle with a NaN position blocks its WHOLE race, and only its race.
+ *
+ * f1p_rivals_set_groups builds the member list sorted by (group, ego) and each ego's [begin, end) in it on the host and keeps them in
+ * device buffers of the context (synchronous); group == NULL returns to one race of all (any E).
+ * f1p_rivals_dev is asynchronous on the context's stream and owns nothing: it can write straight into the arrays the three
+ * *_set_obstacles_dev borrow.  d_pace and d_idx are nullable.  f1p_rivals_batch: the same on host arrays, synchronous.
+ * Errors, nothing launched: a bad layout, M outside [1, 16], !(radius >= 0), !(reach >= 0), !(min_speed > 0), E < 1 or a NULL states /
+ * obs array (for set_groups: E < 1 with a group array): F1P_EINVAL; E different from the E the groups were set for: F1P_ESTATE.
+ * E == 1 is valid: every slot is empty.
+ * ---------------------------------------------------------------------------------------------- */
+#define F1P_RIVALS_XYVYAW 0
+#define F1P_RIVALS_POSE 1
+#define F1P_RIVALS_ST7 2
+#define F1P_RIVALS_MAX 16
+int f1p_rivals_set_groups(f1p_ctx* ctx, const int32_t* group, int32_t E);
+int f1p_rivals_dev(f1p_ctx* ctx, const double* d_states, int32_t layout, int32_t E, int32_t M, double radius, double reach,
+                   double min_speed, double* d_obs, double* d_pace, int32_t* d_idx);
+int f1p_rivals_batch(f1p_ctx* ctx, const double* states, int32_t layout, int32_t E, int32_t M, double radius, double reach,
+                     double min_speed, double* obs, double* pace, int32_t* idx);
+
+/* ------------------------------------------------------------------------------------------------
  * Multi-GPU: egos shard with no communication (one ctx per rank).  Only when ONE ego's candidate set is
  * split over ranks is there an exchange step: all-reduce(min) of the per-ego best cost, then
  * all-reduce(min) of the candidate index among the ranks that hold that cost (np.argmin first-minimum

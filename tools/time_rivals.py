@@ -1,0 +1,113 @@
+#!/usr/bin/env python3
+"""What it costs to make the vehicles of a batch each other's obstacles, E = 4096 egos, M = 4, as one race of all and as 512
+races of 8, all rows from this one process:
+    device   state upload + f1p_rivals_dev + f1p_kmpc_set_obstacles_dev        (what planner.rivals does per plan)
+    host     the numpy construction of examples/common.py opponent_runs (distance matrix, argsort, gather, trig, stack; for the races a
+             +inf mask between different groups) + f1p_kmpc_set_obstacles      (what a user had to do before)
+    kernel   k_rivals alone, device events around `--calls` chained launches
+device and host: a host clock around the work and a final synchronise, the two ALTERNATED block by block after a warm-up, `--repeats` blocks
+of `--dev-calls` / `--host-calls` calls, ms per call, median and spread (min, max) over the blocks.  The two paths' slots are compared first
+(same vehicles; vx, vy to 1e-12).  THE EXPECTATION: device faster than host by more than the host path's own block-to-block spread, in both
+shapes; "expected" in the record says whether it held.  Prints one JSON object; --out also writes it."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+from f1tenth_planning_amd.runtime import Context, kmpc_set_obstacles, kmpc_set_obstacles_dev, rivals_dev, rivals_set_groups  # noqa: E402
+from time_kmpc_qp import _time  # noqa: E402
+
+RADIUS = 0.45
+
+
+def host_obstacles(st, M, groups):
+    """examples/common.py:153-160, with the races kept apart by a +inf mask"""
+    E = st.shape[0]
+    d = np.hypot(st[:, None, 0] - st[None, :, 0], st[:, None, 1] - st[None, :, 1]) + np.diag(np.full(E, np.inf))
+    if groups is not None:
+        d = d + np.where(groups[:, None] != groups[None, :], np.inf, 0.0)
+    near = np.argsort(d, axis=1)[:, :M]
+    o = st[near]
+    return np.stack([o[:, :, 0], o[:, :, 1], o[:, :, 2] * np.cos(o[:, :, 3]), o[:, :, 2] * np.sin(o[:, :, 3]), np.full((E, M), RADIUS)], 2), near
+
+
+def _blocks(per):
+    per = np.array(per)
+    return dict(ms_median=float(np.median(per)), ms_min=float(per.min()), ms_max=float(per.max()), blocks=per.round(5).tolist())
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--egos", type=int, default=4096)
+    ap.add_argument("--slots", type=int, default=4)
+    ap.add_argument("--race", type=int, default=8, help="vehicles per race of the grouped shape")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--dev-calls", type=int, default=50)
+    ap.add_argument("--host-calls", type=int, default=1)
+    ap.add_argument("--calls", type=int, default=50, help="chained launches per block of the kernel-only row")
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    E, M = args.egos, args.slots
+    rng = np.random.default_rng(0)
+    res = {"tool": "tools/time_rivals.py", "egos": E, "slots": M, "repeats": args.repeats, "dev_calls": args.dev_calls, "host_calls": args.host_calls,
+           "kernel_calls": args.calls, "rows": []}
+    ok = True
+    with Context(0) as ctx:
+        res["device"] = ctx.device_info()
+        d_st, d_obs, d_idx = ctx.alloc(32 * E), ctx.alloc(40 * E * M), ctx.alloc(4 * E * M)
+        for name, groups in (("one race", None), (f"{E // args.race} races of {args.race}", (np.arange(E) % (E // args.race)).astype(np.int32))):
+            # one race: a field of 100 m x 100 m; the races: every race a pack of its own 20 m x 20 m, the packs on top of each other
+            side = 100.0 if groups is None else 20.0
+            st = np.column_stack([rng.uniform(0.0, side, (E, 2)), rng.uniform(0.5, 6.0, E), rng.uniform(-3.0, 3.0, E)])
+            rivals_set_groups(ctx, groups)
+
+            def device():
+                d_st.upload(st)
+                rivals_dev(ctx, d_st, "xyvyaw", E, M, RADIUS, d_obs)
+                kmpc_set_obstacles_dev(ctx, d_obs, E, M)
+                ctx.sync()
+
+            def host():
+                kmpc_set_obstacles(ctx, host_obstacles(st, M, groups)[0])
+                ctx.sync()
+
+            # the same slots both ways
+            want, near = host_obstacles(st, M, groups)
+            rivals_dev(ctx, d_st.upload(st), "xyvyaw", E, M, RADIUS, d_obs, None, d_idx)
+            got, idx = d_obs.download(np.float64, (E, M, 5)), d_idx.download(np.int32, (E, M))
+            same = bool((idx == near).all() and np.abs(got - want).max() <= 1e-12 * 6.0)
+            device(); host(); device()                                              # warm-up of both
+            per = {"device": [], "host": []}
+            for _ in range(args.repeats):
+                for key, fn, n in (("device", device, args.dev_calls), ("host", host, args.host_calls)):
+                    t0 = time.perf_counter()
+                    for _ in range(n):
+                        fn()
+                    per[key].append(1e3 * (time.perf_counter() - t0) / n)
+            row = {"shape": name, "same_slots": same, "device": _blocks(per["device"]), "host": _blocks(per["host"]),
+                   "kernel": _time(ctx, lambda: rivals_dev(ctx, d_st, "xyvyaw", E, M, RADIUS, d_obs), args.calls, args.repeats, 3)}
+            row["host_over_device"] = row["host"]["ms_median"] / row["device"]["ms_median"]
+            row["expected"] = bool(same and row["device"]["ms_median"] < row["host"]["ms_median"] - (row["host"]["ms_max"] - row["host"]["ms_min"]))
+            ok &= row["expected"]
+            res["rows"].append(row)
+            print(json.dumps(row), flush=True)
+            kmpc_set_obstacles_dev(ctx, None)
+        rivals_set_groups(ctx, None)
+        for b in (d_st, d_obs, d_idx):
+            b.free()
+    res["expected"] = bool(ok)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    sys.exit(0 if ok else 1)
+
+
+if __name__ == "__main__":
+    main()
