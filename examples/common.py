@@ -130,12 +130,16 @@ def add_rival_flags(ap):
     ap.add_argument("--rivals", action="store_true", help="with --opponents M: the M opponents are found on the device from each call's states "
                     "(planner.rivals) instead of built on the host")
     ap.add_argument("--groups", type=int, default=0, help="with --rivals: split the pack into G independent races (vehicle e in race e %% G)")
+    ap.add_argument("--predict", choices=("velocity", "track"), default="velocity", help="with --rivals: 'track' predicts each rival along the raceline "
+                    "over the planner's horizon instead of at constant velocity (Rivals(predict='track'))")
 
 
 def rival_groups(args, E):
     """-> (group id per vehicle or None, [E, E] +inf where two vehicles are not each other's business -- the diagonal, another race -- else 0)"""
     if args.groups > 0 and not args.rivals:
         raise SystemExit("--groups needs --rivals (the host construction of --opponents knows one race of all)")
+    if args.predict != "velocity" and not args.rivals:
+        raise SystemExit("--predict needs --rivals (the host construction of --opponents moves every opponent at constant velocity)")
     if args.groups <= 0:
         return None, np.diag(np.full(E, np.inf))
     groups = (np.arange(E) % args.groups).astype(np.int32)
@@ -165,7 +169,7 @@ def opponent_runs(args, rl, waypoints, cfg, make_planner, batch_states, gap=1.5,
     for on in (False, True):
         planner = make_planner([w.copy() for w in waypoints], cfg)
         if on and args.rivals:
-            planner.rivals = Rivals(count=M, radius=radius, groups=groups)      # every plan_batch finds them itself, on the device
+            planner.rivals = Rivals(count=M, radius=radius, groups=groups, predict=args.predict)      # every plan_batch finds them itself, on the device
         env = sim.make("f110_gym:f110-v0", num_agents=E)
         env.reset(poses)
         d_min, n_stop = np.inf, 0

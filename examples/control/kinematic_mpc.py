@@ -8,7 +8,8 @@ rollouts (mpc_config.COLLISION), counting the vehicle-steps that ended in an occ
 twice: each vehicle planning as if it were alone, then with its M nearest other vehicles as moving obstacles, predicted at constant
 velocity (planner.obstacles).  It reports the smallest distance between two vehicles over each run.  With --rivals the opponents are not
 built here but found on the device by every plan (planner.rivals = Rivals(count=M, radius=...)); --groups G then splits the pack into G
-independent races."""
+independent races.  --predict track predicts each rival along the raceline over the planner's
+horizon instead of at constant velocity (Rivals(predict="track"))."""
 import os
 import sys
 

@@ -53,6 +53,18 @@ class KmpcSampler(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("call", C.c_uint32), ("use_warm", C.c_int32), ("sigma_accel", C.c_double), ("sigma_steer", C.c_double)]
 
 
+class RivalsPredict(C.Structure):
+    """struct f1p_rivals_predict (include/f1p.h)"""
+    _fields_ = [("horizon_s", C.c_double), ("horizon_m", C.c_double), ("knots", C.c_int32), ("inflate", C.c_int32), ("wrap", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+def rivals_predict(horizon_s, horizon_m=0.0, knots=8, inflate=True, wrap=True):
+    p = RivalsPredict()
+    p.horizon_s, p.horizon_m, p.knots, p.inflate, p.wrap = float(horizon_s), float(horizon_m), int(knots), 1 if inflate else 0, 1 if wrap else 0
+    return p
+
+
 class StmpcSampler(C.Structure):
     """struct f1p_stmpc_sampler (include/f1p.h)"""
     _fields_ = [("seed", C.c_uint64), ("call", C.c_uint32), ("use_warm", C.c_int32), ("sigma_steer_v", C.c_double), ("sigma_accel", C.c_double),
@@ -303,6 +315,9 @@ PROTOTYPES = {
     "f1p_rivals_set_groups": (C.c_int, [_P, _P, _I]),
     "f1p_rivals_dev": (C.c_int, [_P, _P, _I, _I, _I, _D, _D, _D, _P, _P, _P]),
     "f1p_rivals_batch": (C.c_int, [_P, _P, _I, _I, _I, _D, _D, _D, _P, _P, _P]),
+    "f1p_rivals_set_course": (C.c_int, [_P, _P, _I]),
+    "f1p_rivals_predict_dev": (C.c_int, [_P, _P, _I, _I, _I, _D, _D, _D, C.POINTER(RivalsPredict), _P, _P, _P, _P]),
+    "f1p_rivals_predict_batch": (C.c_int, [_P, _P, _I, _I, _I, _D, _D, _D, C.POINTER(RivalsPredict), _P, _P, _P, _P]),
     "f1p_comm_unique_id": (C.c_int, [_P, _P]),
     "f1p_comm_init": (C.c_int, [_P, _P, _I, _I]),
     "f1p_comm_destroy": (C.c_int, [_P]),

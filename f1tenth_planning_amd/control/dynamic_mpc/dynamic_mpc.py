@@ -21,6 +21,8 @@ DESIGN.md 5k).  The next plan / plan_batch call TAKES the attribute: it is None 
 planner.rivals = Rivals(count=M, radius=r[, reach, groups]) (shooting only, plan_batch only): while it is set, every plan_batch finds each
 ego's M nearest other vehicles of its race among the call's own states on the device (heading yaw + beta; f1p_rivals_dev) and
 tests the rollouts of both branches against them.  Persistent until set to None; not together with `obstacles`.
+predict="track" predicts each rival along the planner's raceline over max(T * DT, TK * DTK) seconds, one value for both branches
+(f1p_rivals_predict_dev).
 """
 import warnings
 from dataclasses import dataclass, field
@@ -128,7 +130,7 @@ class STMPCPlanner(MPCPlanner):
             ctx.kmpc_set_collision(on, int(c.COLLISION_SUBSTEPS_K) if sub else 1)
             for k, setter in ((0, kmpc_set_obstacles), (1, stmpc_set_obstacles)):
                 if k == 1 and rivals is not None:                 # (plan_batch: the stmpc state; the slots are filled on the device from the call's states)
-                    d_obs, _, E, M = self._rival_feed.run(ctx, rivals, states)
+                    d_obs, _, E, M = self._rival_feed.run(ctx, rivals, states, horizon=(max(float(c.T) * float(c.DT), float(c.TK) * float(c.DTK)), 0.0))
                     stmpc_set_obstacles_dev(ctx, d_obs, E, M)
                     self._obstacles_set[k] = True
                     continue

@@ -23,9 +23,11 @@ it is None again afterwards, so obstacles are given per call, as a keyword argum
 The caller folds the vehicle's own radius into r.  (An attribute, not a keyword: the signatures of plan and plan_batch are the
 reference's and a pinned record, tests/test_runtime_calls.py.)
 
-planner.rivals = Rivals(count=M, radius=r[, reach, groups]) (shooting only, plan_batch only) makes the vehicles of a batch each other's
+planner.rivals = Rivals(count=M, radius=r[, reach, groups, predict, horizon, knots, inflate, wrap]) (shooting only, plan_batch only) makes the vehicles of a batch each other's
 obstacles: while it is set, every plan_batch finds each ego's M nearest other vehicles of its race among the call's own x0 ON THE DEVICE
 (f1p_rivals_dev) and tests the rollouts against them as above.  Persistent until set to None; not together with `obstacles`.
+predict="track" predicts each rival along the course it follows (the call's tracks / track_ids, else the raceline) over TK * DTK seconds
+(f1p_rivals_predict_dev).
 """
 import warnings
 from dataclasses import dataclass, field
@@ -128,7 +130,7 @@ class KMPCPlanner(MPCPlanner):
         self._rival_feed = RivalFeed("xyvyaw", lambda ctx: kmpc_set_obstacles_dev(ctx, None))
         self._check_solver()
 
-    def _collision_switch(self, ctx, obstacles=None, rivals=None, x0=None):
+    def _collision_switch(self, ctx, obstacles=None, rivals=None, x0=None, track_ids=None):
         """the occupancy switch and the obstacles of this plan (None clears them); COLLISION_SUBSTEPS serves both tests.  rivals: the slots
         are filled on the device from the call's x0 and the context borrows them"""
         c = self.config
@@ -136,7 +138,7 @@ class KMPCPlanner(MPCPlanner):
             tested = obstacles is not None or rivals is not None
             ctx.kmpc_set_collision(bool(c.COLLISION), int(c.COLLISION_SUBSTEPS) if (c.COLLISION or tested) else 1)
             if rivals is not None:
-                d_obs, _, E, M = self._rival_feed.run(ctx, rivals, x0)
+                d_obs, _, E, M = self._rival_feed.run(ctx, rivals, x0, horizon=(float(c.TK) * float(c.DTK), 0.0), track_ids=track_ids)
                 kmpc_set_obstacles_dev(ctx, d_obs, E, M)
                 self._obstacles_set = True
             elif obstacles is not None or self._obstacles_set:     # (a plan without any, after plans without any: nothing to clear)
@@ -258,7 +260,9 @@ class KMPCPlanner(MPCPlanner):
         cols = _track_columns(tracks, track_ids)
         ctx = self._context()
         x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, 4)
-        self._collision_switch(ctx, obstacles, rivals, x0)
+        if rivals is not None and rivals.predict == "track":   # the rivals are predicted along the call's tracks: the set is on the context first
+            ctx.set_tracks_cached(cols, cols=(0, 1, 2, 3))
+        self._collision_switch(ctx, obstacles, rivals, x0, track_ids)
         ctx.kmpc_set_yaw_fixup(True)                           # a batch: per-ego fold of the gathered headings, the courses stay as given
         ctx.set_tracks_cached(cols, cols=(0, 1, 2, 3))
         c = self.config

@@ -178,6 +178,17 @@ struct f1p_ctx {
     int32_t* d_riv_mem = nullptr;      // [riv_cap]
     int32_t* d_riv_rng = nullptr;      // [riv_cap][2]
     int riv_E = 0, riv_cap = 0;
+    // rivals predicted along their courses (f1p_rivals_predict_*): the arc tables of the raceline and of the track set, each built by
+    // k_course_arc for the generation of its course (wp_gen / trk_gen count the f1p_set_waypoints* / f1p_set_track_set calls), the vehicles' track ids
+    // (f1p_rivals_set_course; riv_course_E == 0: every vehicle on the raceline) and the per-call scratch: the Frenet records [cap][4], the indices [cap][16]
+    struct ArcTab { double* cum = nullptr; int32_t* ok = nullptr; size_t rows = 0; int K = 0; unsigned long long gen = 0; };
+    unsigned long long wp_gen = 1, trk_gen = 1;
+    ArcTab arc_wp, arc_trk;
+    int32_t* d_riv_tid = nullptr;      // [riv_tid_cap]
+    int riv_course_E = 0, riv_tid_cap = 0;
+    double* d_riv_rec = nullptr;
+    int32_t* d_riv_idx = nullptr;
+    int riv_scr_cap = 0;
 
     // closed-loop mode (f1p_lattice_set_closed_loop): the heading column of every plan's winners stays on the device and is the next
     // plan's prev_theta (get_similarity_cost's previous path, lattice_planner.py:287-296) -- two buffers used alternately
@@ -330,6 +341,12 @@ int launch_stmpc_ref_tracks(f1p_ctx* ctx, const double* d_states, const int32_t*
 // k_rivals.hip: d_mem / d_rng null: one race of all E
 int launch_rivals(f1p_ctx* ctx, const double* d_states, int layout, int E, int M, double radius, double reach2, double min_speed,
                   const int32_t* d_mem, const int32_t* d_rng, double* d_obs, double* d_pace, int32_t* d_idx);
+// k_rivals_predict.hip: the arc table of the track set (tracks) or of the raceline; the Frenet records and the predicted (vx, vy, r) of the live
+// slots k_rivals wrote.  d_tid null: every vehicle on the raceline
+int launch_course_arc(f1p_ctx* ctx, bool tracks, double* d_cum, int32_t* d_ok);
+int launch_rivals_predict(f1p_ctx* ctx, const double* d_states, int layout, int E, int M, double radius, double min_speed,
+                          const f1p_rivals_predict* pr, const int32_t* d_tid, const double* d_cum, const int32_t* d_ok, double* d_rec,
+                          const int32_t* d_idx, double* d_obs, double* d_frenet);
 int launch_argmin_key(f1p_ctx* ctx, const double* d_cost, uint64_t* d_key, int E);
 int launch_argmin_mask(f1p_ctx* ctx, const uint64_t* d_own, const uint64_t* d_min, const int32_t* d_idx, int32_t* d_masked,
                        double* d_cost_out, int E);

@@ -79,6 +79,7 @@ int f1p_set_waypoints_ex(f1p_ctx* ctx, const double* wp, int32_t n, int32_t ncol
     std::vector<double> box((size_t)4 * nchunk);
     chunk_boxes(soa.data(), soa.data() + n, n, box.data());
     F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->wp_gen++;                                                  // (the arc table of the rivals' prediction is the old raceline's)
     if (n != ctx->n_wp) {
         double** ps[] = {&ctx->d_wx, &ctx->d_wy, &ctx->d_wv, &ctx->d_wpsi, &ctx->d_wkappa, &ctx->d_wbox};
         for (double** p : ps) { if (*p) (void)hipFree(*p); *p = nullptr; }
@@ -260,6 +261,7 @@ int f1p_set_track_set(f1p_ctx* ctx, const double* wp, const int64_t* row_offsets
     if (K < 0) return set_error(ctx, F1P_EINVAL, "K must be >= 0");
     if (K == 0) {                                                   // clear
         F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->trk_gen++;
         drop_track_set(ctx);
         return F1P_OK;
     }
@@ -315,6 +317,7 @@ int f1p_set_track_set(f1p_ctx* ctx, const double* wp, const int64_t* row_offsets
     if (rc == F1P_OK) rc = check_hip(ctx, hipMemcpy(d_tab, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice), "hipMemcpy(track table)");
     if (rc == F1P_OK) rc = check_hip(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");   // no launch still reads the old set
     if (rc != F1P_OK) { release(); return rc; }
+    ctx->trk_gen++;                                                 // (the arc tables of the rivals' prediction are the old set's)
     drop_track_set(ctx);
     ctx->d_tx = d[0]; ctx->d_ty = d[1]; ctx->d_tv = d[2]; ctx->d_tpsi = d[3]; ctx->d_tkappa = d[4]; ctx->d_tbox = d[5]; ctx->d_ttab = d_tab;
     ctx->trk_K = K; ctx->trk_rows = (int)rows; ctx->trk_chunks = (int)nchunk_all;

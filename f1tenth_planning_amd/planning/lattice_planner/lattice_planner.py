@@ -27,6 +27,8 @@ Rivals: `planner.rivals = Rivals(count=M, radius=r[, reach, groups])` makes the 
 every plan_batch() / step_batch() finds each ego's M nearest other vehicles of its race among the call's own poses ON THE DEVICE, with the pace
 1 / max(|v|, obstacle_min_speed) (f1p_rivals_dev, DESIGN.md 5m), and tests the candidates against them as above.  Persistent until set to None;
 not together with `obstacles`, not for plan() (one ego has no rivals), not for multi-GPU plans.
+predict="track" predicts each rival along the course it follows (the call's tracks / track_ids, else the raceline) over the time ego e needs for
+its longest look-ahead, max(lookahead_distances) * pace_e (f1p_rivals_predict_dev).
 """
 import warnings
 
@@ -186,12 +188,13 @@ class LatticePlanner(OccupancyMap, Planner):
     def _bind(self, waypoints):
         return self._bind_waypoints(waypoints, 4, 'Waypoints needs to be a (Nxm), m >= 4, numpy array! (x, y, velocity, heading)')
 
-    def _obstacle_switch(self, ctx, obstacles, poses=None, rivals=None):
+    def _obstacle_switch(self, ctx, obstacles, poses=None, rivals=None, track_ids=None):
         """the obstacles of this plan on the context (None clears what an earlier plan left there); pace from the poses' velocity column.
         rivals: slots and paces are filled on the device from the call's poses and the context borrows them"""
         if rivals is not None:
             d_obs, d_pace, E, M = self._rival_feed.run(ctx, rivals, np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4),
-                                                       min_speed=float(self.obstacle_min_speed))
+                                                       min_speed=float(self.obstacle_min_speed),
+                                                       horizon=(0.0, float(max(self.lookahead_distances))), track_ids=track_ids)
             lattice_set_obstacles_dev(ctx, d_obs, d_pace, E, M)
             self._obstacles_set = True
         elif obstacles is not None:
@@ -321,7 +324,7 @@ class LatticePlanner(OccupancyMap, Planner):
             if devices is None:
                 ctx = self._context()
                 ctx.set_tracks_cached(tracks)
-                self._obstacle_switch(ctx, obstacles, poses, rivals)
+                self._obstacle_switch(ctx, obstacles, poses, rivals, track_ids)
                 return ctx.lattice_plan_tracks(poses, track_ids, self._cfg(), prev_theta=prev_theta, want_traj=want_traj, traj_dtype=traj_dtype)
             mc = self._multi(devices)
             mc.set_tracks_cached(tracks)
@@ -356,7 +359,7 @@ class LatticePlanner(OccupancyMap, Planner):
         if rivals is not None:
             check_rivals(rivals, poses.shape[0], obstacles)
         ctx = self._bind_tracks(tracks, track_ids, 4) if tracks is not None else self._bind(waypoints)
-        self._obstacle_switch(ctx, obstacles, poses, rivals)
+        self._obstacle_switch(ctx, obstacles, poses, rivals, track_ids if tracks is not None else None)
         self._step_shape = (poses.shape[0], self._cfg().n_stations)
         if tracks is not None:
             return ctx.lattice_step_tracks(poses, track_ids, self._cfg(), keep_traj=keep_traj)

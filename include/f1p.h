@@ -971,6 +971,61 @@ int f1p_rivals_batch(f1p_ctx* ctx, const double* states, int32_t layout, int32_t
                      double min_speed, double* obs, double* pace, int32_t* idx);
 
 /* ------------------------------------------------------------------------------------------------
+ * Rivals, predicted along the course (csrc/k_rivals_predict.hip).  A rival that follows a raceline stays on it: instead of
+ * the constant-velocity (vx, vy) above, a live slot carries the CHORD of the rival's path along its course over the ego's horizon, and a
+ * radius optionally widened by the largest distance between that path and the chord.  Selection, slot order, idx, pace, empty slots,
+ * groups, reach and the NaN ordering are exactly those above; only vx, vy, r of a LIVE slot change.
+ * Course of vehicle j: the polyline p_0 .. p_{n-1} (x and y columns) of the context's raceline, or of track track_id[j] of the context's
+ * track set (f1p_rivals_set_course).  All in fp64, no contraction:
+ *   - len_k = sqrt(dx*dx + dy*dy); cum_0 = 0; cum_{k+1} = cum_k + len_k, added one by one in index order; L = cum_{n-1}.
+ *   - u_k = (p_{k+1} - p_k) / len_k (each component divided); left normal n_k = (-u_k.y, u_k.x).
+ * Frenet record of vehicle j, once per vehicle per call:
+ *   - (b, t, q): segment index, parameter and projection that f1p_nearest_point_batch / f1p_nearest_point_tracks_batch return for
+ *     (x_j, y_j) on that course -- the same device functions, the same bits.
+ *   - s0 = cum_b + t * len_b;  d = (x_j - q.x) * n_b.x + (y_j - q.y) * n_b.y.
+ *   - dir = (v_j * (cos h_j * u_b.x + sin h_j * u_b.y) >= 0) ? +1 : -1, h_j the layout's heading as above (full-range sincos).
+ * Position at time tau:
+ *   - s = s0 + (dir * |v_j|) * tau;  with wrap: s = s - L * floor(s / L);  in both modes s is then clamped into [0, L].
+ *   - k = the largest index <= n - 2 with cum_k <= s (a binary search).
+ *   - P(tau) = p_k + u_k * (s - cum_k) + n_k * d, per component, left to right.
+ *     wrap jumps from p_{n-1} to p_0 without a closing segment (the reference's single index wrap, kinematic_mpc.py:194).
+ * Slot of ego i that holds vehicle j:
+ *   - H_i = horizon_s + horizon_m * pace_i, pace_i as above;  knots c_k = P((H_i * k) / K), k = 0 .. K, K = knots.
+ *   - x, y: bit copies of x_j, y_j, as above.
+ *   - vx = (c_K.x - c_0.x) / H_i, vy likewise.
+ *   - dev = max over 0 < k < K of sqrt(ex*ex + ey*ey), e = (c_k - c_0) - (c_K - c_0) * (k / K);  0 for K = 1.
+ *   - r = radius + dev with inflate, else radius (a bit copy).
+ * The slot keeps the constant-velocity bits above when x_j, y_j, v_j, h_j or H_i is not finite, !(H_i > 0), !(|v_j| * H_i < 1e9),
+ * track_id[j] is outside [0, K_tracks), or the course has a zero-length segment or an L that is not finite and positive -- so the NaN
+ * policy ("a NaN anywhere blocks") is exactly the one above.
+ *
+ * f1p_rivals_set_course: track_id host [E], vehicle j follows track track_id[j] of the track set in force at the following calls
+ * (synchronous, kept in a device buffer of the context); NULL (any E): every vehicle follows the context's raceline, the default.
+ * f1p_rivals_predict_dev: asynchronous on the context's stream; d_pace, d_idx and d_frenet are nullable.  d_frenet [E][3] =
+ * (s0, d, dir) per vehicle, a NaN row for a vehicle that falls back for a cause of its own (state, track id, course).  The arc tables
+ * live in buffers of the context and are rebuilt, by one launch, when f1p_set_waypoints* / f1p_set_track_set has been called since.
+ * f1p_rivals_predict_batch: the same on host arrays, synchronous.
+ * Errors, nothing launched: everything f1p_rivals_dev rejects, knots outside [1, 16], a negative or NaN horizon_s / horizon_m, both
+ * zero, a NULL pr (set_course: E < 1 with an id array): F1P_EINVAL; E different from the E the courses were set for, or no track set
+ * (ids set) / no raceline (no ids): F1P_ESTATE.
+ * ---------------------------------------------------------------------------------------------- */
+#define F1P_RIVALS_KNOTS_MAX 16
+typedef struct f1p_rivals_predict {
+    double horizon_s;              /* H_i = horizon_s [s] + horizon_m [m] * pace_i */
+    double horizon_m;
+    int32_t knots;                 /* K in [1, 16] */
+    int32_t inflate;               /* != 0: r = radius + dev */
+    int32_t wrap;                  /* != 0: the course is a loop */
+    int32_t reserved;
+} f1p_rivals_predict;
+int f1p_rivals_set_course(f1p_ctx* ctx, const int32_t* track_id, int32_t E);
+int f1p_rivals_predict_dev(f1p_ctx* ctx, const double* d_states, int32_t layout, int32_t E, int32_t M, double radius, double reach,
+                           double min_speed, const f1p_rivals_predict* pr, double* d_obs, double* d_pace, int32_t* d_idx,
+                           double* d_frenet);
+int f1p_rivals_predict_batch(f1p_ctx* ctx, const double* states, int32_t layout, int32_t E, int32_t M, double radius, double reach,
+                             double min_speed, const f1p_rivals_predict* pr, double* obs, double* pace, int32_t* idx, double* frenet);
+
+/* ------------------------------------------------------------------------------------------------
  * Multi-GPU: egos shard with no communication (one ctx per rank).  Only when ONE ego's candidate set is
  * split over ranks is there an exchange step: all-reduce(min) of the per-ego best cost, then
  * all-reduce(min) of the candidate index among the ranks that hold that cost (np.argmin first-minimum

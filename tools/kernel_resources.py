@@ -45,7 +45,7 @@ CSRC = os.path.join(ROOT, "f1tenth_planning_amd", "csrc")
 #                       cubic plans run here; the clothoid ones stay inside the budgets of their instantiations without discs
 BUDGET = {"9k_latticeILb0ELi1ELb0ELb0ELb0EJNS_6LatObs": 12, "9k_latticeILb0ELi1ELb0ELb0ELb1EJNS_6LatObs": 12,
           "9k_latticeILb1ELi1ELb0ELb1ELb0EJNS_6LatObs": 60, "9k_latticeILb1ELi1ELb0ELb1ELb1EJNS_6LatObs": 60,
-          "ILb1E": 56, "k_kmpc_plan_gen_tIJEE": 32, "k_kmpc_plan_gen_tIJNS_11KmpcIdxArgsEEE": 52, "k_kmpc_plan_gen_tIJNS_11KmpcIdxArgsENS_7KmpcObsEEE": 12, "k_stmpc_shoot_tINS_8StCtlGenEJEE": 36, "k_kmpc_shoot_mixed": 0, "k_rivals": 0, "k_clothoid_g1": 8, "9k_latticeILb0E": 8,
+          "ILb1E": 56, "k_kmpc_plan_gen_tIJEE": 32, "k_kmpc_plan_gen_tIJNS_11KmpcIdxArgsEEE": 52, "k_kmpc_plan_gen_tIJNS_11KmpcIdxArgsENS_7KmpcObsEEE": 12, "k_stmpc_shoot_tINS_8StCtlGenEJEE": 36, "k_kmpc_shoot_mixed": 0, "k_rivals": 0, "k_course_arc": 0, "k_rivals_frenet": 0, "k_rivals_predict": 0, "k_clothoid_g1": 8, "9k_latticeILb0E": 8,
           "k_lattice_filter3ILi1ELb1E": 24, "k_lattice_filter3ILi2ELb1E": 24,
           "k_lattice_filter3ILi1ELb0ELb0ELi0ELb1E": 8, "k_lattice_filter3ILi2ELb0ELb0ELi0ELb1E": 8,
           "9k_latticeILb0ELi0ELb1ELb0ELb1E": 24}   # (the instantiations WITH test hooks -- incl. the host-goal shapes; device goals, point footprint: 0)

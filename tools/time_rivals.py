@@ -8,8 +8,18 @@ races of 8, all rows from this one process:
 device and host: a host clock around the work and a final synchronise, the two ALTERNATED block by block after a warm-up, `--repeats` blocks
 of `--dev-calls` / `--host-calls` calls, ms per call, median and spread (min, max) over the blocks.  The two paths' slots are compared first
 (same vehicles; vx, vy to 1e-12).  THE EXPECTATION: device faster than host by more than the host path's own block-to-block spread, in both
-shapes; "expected" in the record says whether it held.  Prints one JSON object; --out also writes it."""
+shapes; "expected" in the record says whether it held.  Prints one JSON object; --out also writes it.
+
+--predict: the rivals predicted along the raceline, same shapes, same protocol, the vehicles on a synthetic raceline:
+    predict  state upload + f1p_rivals_predict_dev + f1p_kmpc_set_obstacles_dev  (what Rivals(predict="track") does per plan)
+    device   the constant-velocity path above, same run
+    parent   (--parent-lib PATH: libf1p.so of the parent commit) the constant-velocity path through THAT library, on a context of its own
+    kernels  device events around chained launches: k_rivals alone, and k_rivals + k_rivals_frenet + k_rivals_predict; "new_kernels_ms" is the difference
+The paths are ALTERNATED block by block.  Compared first: the constant-velocity slots of both libraries bit for bit, and idx, x, y of the predicted
+slots against them.  THE EXPECTATION: the constant-velocity path's median stays inside the parent's own block-to-block band (its kernel is unchanged,
+only the launch path gained a branch).  The prediction's own cost is reported, not judged."""
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -19,7 +29,9 @@ import numpy as np
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
-from f1tenth_planning_amd.runtime import Context, kmpc_set_obstacles, kmpc_set_obstacles_dev, rivals_dev, rivals_set_groups  # noqa: E402
+from f1tenth_planning_amd import _abi, synth  # noqa: E402
+from f1tenth_planning_amd.runtime import (Context, kmpc_set_obstacles, kmpc_set_obstacles_dev, rivals_dev, rivals_predict_dev,  # noqa: E402
+                                          rivals_set_groups)
 from time_kmpc_qp import _time  # noqa: E402
 
 RADIUS = 0.45
@@ -41,6 +53,103 @@ def _blocks(per):
     return dict(ms_median=float(np.median(per)), ms_min=float(per.min()), ms_max=float(per.max()), blocks=per.round(5).tolist())
 
 
+def other_library_context(path):
+    """a Context on another build of the library (the parent commit's: it exports fewer symbols)"""
+    lib = C.CDLL(path, mode=os.RTLD_NOW | os.RTLD_LOCAL | getattr(os, "RTLD_DEEPBIND", 0))
+    for name, (res, args) in _abi.PROTOTYPES.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
+    mine, _abi._lib = _abi.load_library(), lib
+    try:
+        return Context(0)
+    finally:
+        _abi._lib = mine
+
+
+def predict_main(args):
+    E, M, H, K = args.egos, args.slots, 0.8, 8
+    rng = np.random.default_rng(0)
+    rl = synth.make_raceline(seed=0)
+    res = {"tool": "tools/time_rivals.py --predict", "egos": E, "slots": M, "horizon_s": H, "knots": K, "raceline_points": int(rl.shape[0]),
+           "repeats": args.repeats, "dev_calls": args.dev_calls, "kernel_calls": args.calls, "parent_lib": bool(args.parent_lib), "rows": []}
+    ok = True
+    with Context(0) as ctx:
+        res["device"] = ctx.device_info()
+        ctxs = [ctx] + ([other_library_context(args.parent_lib)] if args.parent_lib else [])
+        bufs = [(c.alloc(32 * E), c.alloc(40 * E * M), c.alloc(4 * E * M)) for c in ctxs]
+        for c in ctxs:
+            c.set_waypoints(rl)
+        for name, groups in (("one race", None), (f"{E // args.race} races of {args.race}", (np.arange(E) % (E // args.race)).astype(np.int32))):
+            k = rng.integers(0, rl.shape[0] - 1, E)                 # on the raceline, up to 0.4 m to either side, roughly along it
+            lat = rng.uniform(-0.4, 0.4, E)
+            st = np.column_stack([rl[k, 0] - lat * np.sin(rl[k, 3]), rl[k, 1] + lat * np.cos(rl[k, 3]), rng.uniform(0.5, 6.0, E),
+                                  rl[k, 3] + rng.uniform(-0.2, 0.2, E)])
+            for c in ctxs:
+                rivals_set_groups(c, groups)
+
+            def velocity(c, b):
+                b[0].upload(st)
+                rivals_dev(c, b[0], "xyvyaw", E, M, RADIUS, b[1])
+                kmpc_set_obstacles_dev(c, b[1], E, M)
+                c.sync()
+
+            def predict():
+                d_st, d_obs, _ = bufs[0]
+                d_st.upload(st)
+                rivals_predict_dev(ctx, d_st, "xyvyaw", E, M, RADIUS, d_obs, H, 0.0, K)
+                kmpc_set_obstacles_dev(ctx, d_obs, E, M)
+                ctx.sync()
+
+            outs = []
+            for c, b in zip(ctxs, bufs):
+                rivals_dev(c, b[0].upload(st), "xyvyaw", E, M, RADIUS, b[1], None, b[2])
+                outs.append((b[1].download(np.float64, (E, M, 5)), b[2].download(np.int32, (E, M))))
+            d_st, d_obs, d_idx = bufs[0]
+            rivals_predict_dev(ctx, d_st, "xyvyaw", E, M, RADIUS, d_obs, H, 0.0, K, d_idx=d_idx)
+            pobs, pidx = d_obs.download(np.float64, (E, M, 5)), d_idx.download(np.int32, (E, M))
+            same = bool(all(o.tobytes() == outs[0][0].tobytes() and i.tobytes() == outs[0][1].tobytes() for o, i in outs)
+                        and (pidx == outs[0][1]).all() and pobs[..., :2].tobytes() == outs[0][0][..., :2].tobytes())
+            moved = float((np.abs(pobs[..., 2:4] - outs[0][0][..., 2:4]).max(axis=2)[pidx >= 0] > 0.05).mean())
+            paths = [("predict", predict), ("device", lambda: velocity(ctx, bufs[0]))] + ([("parent", lambda: velocity(ctxs[1], bufs[1]))] if args.parent_lib else [])
+            for _, fn in paths * 2:                                  # warm-up of every path
+                fn()
+            per = {key: [] for key, _ in paths}
+            for _ in range(args.repeats):
+                for key, fn in paths:
+                    t0 = time.perf_counter()
+                    for _ in range(args.dev_calls):
+                        fn()
+                    per[key].append(1e3 * (time.perf_counter() - t0) / args.dev_calls)
+            row = {"shape": name, "same_slots": same, "slots_moved_by_prediction": moved}
+            row.update({key: _blocks(v) for key, v in per.items()})
+            row["kernel_velocity"] = _time(ctx, lambda: rivals_dev(ctx, d_st, "xyvyaw", E, M, RADIUS, d_obs), args.calls, args.repeats, 3)
+            row["kernel_predict"] = _time(ctx, lambda: rivals_predict_dev(ctx, d_st, "xyvyaw", E, M, RADIUS, d_obs, H, 0.0, K), args.calls, args.repeats, 3)
+            row["new_kernels_ms"] = row["kernel_predict"]["ms_median"] - row["kernel_velocity"]["ms_median"]
+            row["prediction_ms"] = row["predict"]["ms_median"] - row["device"]["ms_median"]
+            row["expected"] = same
+            if args.parent_lib:
+                row["expected"] = bool(same and row["device"]["ms_median"] <= row["parent"]["ms_max"])
+            ok &= row["expected"]
+            res["rows"].append(row)
+            print(json.dumps(row), flush=True)
+            for c in ctxs:
+                kmpc_set_obstacles_dev(c, None)
+                rivals_set_groups(c, None)
+        for c, b in zip(ctxs, bufs):
+            for x in b:
+                x.free()
+        for c in ctxs[1:]:
+            c.close()
+    res["expected"] = bool(ok)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    sys.exit(0 if ok else 1)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--egos", type=int, default=4096)
@@ -51,7 +160,11 @@ def main():
     ap.add_argument("--host-calls", type=int, default=1)
     ap.add_argument("--calls", type=int, default=50, help="chained launches per block of the kernel-only row")
     ap.add_argument("--out")
+    ap.add_argument("--predict", action="store_true", help="time the prediction along the raceline (DESIGN.md 5n) instead")
+    ap.add_argument("--parent-lib", help="--predict: libf1p.so of the parent commit, its constant-velocity path alternated with this tree's")
     args = ap.parse_args()
+    if args.predict:
+        predict_main(args)
     E, M = args.egos, args.slots
     rng = np.random.default_rng(0)
     res = {"tool": "tools/time_rivals.py", "egos": E, "slots": M, "repeats": args.repeats, "dev_calls": args.dev_calls, "host_calls": args.host_calls,
