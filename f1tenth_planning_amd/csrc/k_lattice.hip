@@ -504,14 +504,32 @@ __global__ __launch_bounds__(256) void k_clothoid_g1(const double* __restrict__ 
     if (ok) ok[i] = cl.ok ? 1 : 0;
 }
 
+// a + b c as an unevaluated sum hi + lo, exact up to the rounding of lo (TwoProduct by fma, TwoSum); finite operands
+__device__ __forceinline__ double sum_prod(double a, double b, double c, double& lo) {
+    const double p = b * c, pe = __builtin_fma(b, c, -p);
+    const double t = a + p, bb = t - a;
+    lo = ((a - (t - bb)) + (p - bb)) + pe;
+    return t;
+}
+
 // sample_traj (utils/utils.py:286-295) of clothoids given by their parameters (k0, dk, L) in their own start frame: the station
-// loop's arithmetic (interval_setup / interval_increment), one thread per clothoid, rows (x, y, theta, |kappa|)
+// loop's arithmetic (interval_setup / interval_increment), one thread per clothoid, rows (x, y, theta, |kappa|).
+// A clothoid outside the premises of that arithmetic -- a parameter that is not finite, or more than 4096 pieces per station interval
+// by interval_setup's two rules, where its cap would leave |a| > 0.15 or |b| > 0.02 and the truncated series no longer hold -- gets
+// NaN in every row; the other clothoids of the call are untouched and the call succeeds.  A G1 fit never gets there.
 __global__ __launch_bounds__(256) void k_clothoid_sample(const double* __restrict__ params, int n, int S, double* __restrict__ rows) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n) return;
     const double k0 = params[3 * c], dk = params[3 * c + 1], L = params[3 * c + 2];
     const int den = S - 1 > 1 ? S - 1 : 1;
     const double ds = L / (double)den;
+    const double kmax = fmax(fabs(k0), fabs(__builtin_fma(dk, L, k0)));
+    const double n1 = kmax * ds * (1.0 / 0.3), n2 = ds * __builtin_sqrt(fabs(dk) * 6.25);   // interval_setup's piece counts before ceil and cap
+    if (!(isfinite(k0) && isfinite(dk) && isfinite(L)) || !(__builtin_ceil(n1) <= 4096.0) || !(__builtin_ceil(n2) <= 4096.0)) {
+        double* bad = rows + (size_t)c * S * 4;
+        for (int i = 0; i < 4 * S; ++i) bad[i] = __builtin_nan("");
+        return;
+    }
     const IntervalCoef ic = interval_setup(k0, dk, L, ds);
     PieceState st;
     st.er = 1.0; st.ei = 0.0; st.rr = 1.0; st.ri = 0.0;
@@ -520,8 +538,11 @@ __global__ __launch_bounds__(256) void k_clothoid_sample(const double* __restric
     for (int i = 0; i < S; ++i) {
         const double s = (double)i * ds;
         out[4 * i] = x; out[4 * i + 1] = y;
-        out[4 * i + 2] = s * (k0 + 0.5 * s * dk);
-        out[4 * i + 3] = fabs(k0 + dk * s);
+        double lo, hi = sum_prod(k0, 0.5 * s, dk, lo);               // theta = s (k0 + s dk / 2), |kappa| = |k0 + dk s|: where the terms cancel the plain
+        const double th = s * hi;                                     // sums of the station loop keep the rounding of the TERMS; here of the result
+        out[4 * i + 2] = th + (__builtin_fma(s, hi, -th) + s * lo);
+        hi = sum_prod(k0, dk, s, lo);
+        out[4 * i + 3] = fabs(hi + lo);
         if (i + 1 < S) {
             double dx, dy;
             interval_increment(k0, dk, s, i * ic.nsub, ic, st, dx, dy);

@@ -550,7 +550,9 @@ int f1p_clothoid_g1_batch(f1p_ctx* ctx, const double* goals, int32_t n, double* 
 
 /* sample_traj (utils/utils.py:286-295) for n clothoids given by their parameters: params [n][3] = (kappa0, dkappa, length) in
  * each clothoid's own start frame (start pose (0, 0, 0)) -> rows [n][npts][4] = (X(s_i), Y(s_i), Theta(s_i), |kappa(s_i)|) at
- * s_i = i * length / max(npts - 1, 1), the arithmetic of the planner's station loop. */
+ * s_i = i * length / max(npts - 1, 1), the arithmetic of the planner's station loop.  That arithmetic holds up to 4096 pieces per
+ * station interval (ceil(max|kappa| ds / 0.3) and ceil(2.5 ds sqrt|dkappa|), ds = length / max(npts - 1, 1)): a clothoid beyond that, or
+ * with a parameter that is not finite, gets NaN in all its rows; the others are unaffected and the call succeeds.  A G1 fit stays below 60. */
 int f1p_clothoid_sample_batch(f1p_ctx* ctx, const double* params, int32_t n, int32_t npts, double* rows);
 
 /* ------------------------------------------------------------------------------------------------

@@ -286,11 +286,25 @@ ORC_API int orc_clothoid_g1(double x1, double y1, double th1, double* kappa0, do
 
 /* pose of the clothoid (start (0,0,0), kappa0, dkappa) at arc length s: X(s), Y(s), Theta(s), and
  * sqrt(XDD^2 + YDD^2) exactly as sample_traj combines them (utils/utils.py:290-293) */
+/* a + b c as an unevaluated sum hi + lo, exact up to the rounding of lo (TwoProduct by fma, TwoSum): where the two terms cancel -- an
+ * S-curve back at heading 0, the curvature at an inflection -- the plain sum keeps the rounding of its TERMS, a relative error of any
+ * size against a reference.  Not finite: the plain sum. */
+static double orc_sum_prod(double a, double b, double c, double* lo) {
+    double p = b * c, pe = fma(b, c, -p);
+    double t = a + p, bb = t - a;
+    double te = (a - (t - bb)) + (p - bb);
+    *lo = isfinite(t) && isfinite(pe) ? te + pe : 0.0;
+    return t;
+}
+
 ORC_API void orc_clothoid_eval(double kappa0, double dkappa, double s, double out[4]) {
     double IC[3], IS[3];
     orc_fresnel_moments(0.5 * dkappa * s * s, kappa0 * s, 0.0, IC, IS);
-    double th = s * (kappa0 + 0.5 * s * dkappa);
-    double k = kappa0 + dkappa * s;
+    double lo, hi = orc_sum_prod(kappa0, 0.5 * s, dkappa, &lo);    /* theta = s (kappa0 + s dkappa / 2) */
+    double th = s * hi;
+    if (isfinite(th)) th += fma(s, hi, -th) + s * lo;
+    double k = orc_sum_prod(kappa0, dkappa, s, &lo);                /* kappa = kappa0 + dkappa s */
+    k += lo;
     double xdd = -sin(th) * k, ydd = cos(th) * k;
     out[0] = s * IC[0];
     out[1] = s * IS[0];

@@ -2,8 +2,8 @@
 
 SURVEY.md 8(d) estimates "~140 fp32 op-equivalents per candidate-step" and asks the builder to "replace these estimates by an exact count
 from its own CPU restatement".  This module is that count: the candidate path of oracle/f1p_oracle.c (orc_clothoid_g1 :244-283,
-orc_fresnel_moments :218-236, orc_clothoid_eval / orc_sample_traj :287-306, the station loop + eval of orc_lattice_candidate :415-474,
-orc_cell_occupied :318-325) restated on a float subclass whose arithmetic operators count themselves.  Pure-Python loops, so it runs on
+orc_fresnel_moments :218-236, orc_clothoid_eval / orc_sample_traj :287-320, the station loop + eval of orc_lattice_candidate :429-488,
+orc_cell_occupied :332-339) restated on a float subclass whose arithmetic operators count themselves.  Pure-Python loops, so it runs on
 a handful of candidates (one ego's 256 take a few seconds); tests/test_oracle_opcount.py checks that the restatement reproduces the C
 oracle's per-candidate costs (so it IS the same algorithm) before its count is believed.
 
@@ -142,7 +142,7 @@ def _row_tail(k0, dk, s):
 
 
 def sample_traj_reference(k0, dk, L, S):
-    """orc_sample_traj / orc_clothoid_eval (f1p_oracle.c:287-306): every station from 0, as utils/utils.py:289-293 does"""
+    """orc_sample_traj / orc_clothoid_eval (f1p_oracle.c:287-320): every station from 0, as utils/utils.py:289-293 does"""
     den = max(S - 1, 1)
     rows = []
     for i in range(S):
@@ -174,7 +174,7 @@ def sample_traj_incremental(k0, dk, L, S):
 
 
 def cell_occupied(img, res, ox, oy, occupied_below, x, y):
-    """orc_cell_occupied (f1p_oracle.c:318-325); the 1 / res is per map, not per station"""
+    """orc_cell_occupied (f1p_oracle.c:332-339); the 1 / res is per map, not per station"""
     inv_res = 1.0 / res
     fx = floor((x - ox) * inv_res); fy = floor((y - oy) * inv_res)
     h, w = img.shape
@@ -185,7 +185,7 @@ def cell_occupied(img, res, ox, oy, occupied_below, x, y):
 
 
 def candidate(goal, pose, cfg, grid=None, prev_theta=None, scheme="incremental"):
-    """orc_lattice_candidate (f1p_oracle.c:415-474) for a valid goal in the ego frame -> cost (inf when infeasible / in collision)"""
+    """orc_lattice_candidate (f1p_oracle.c:429-488) for a valid goal in the ego frame -> cost (inf when infeasible / in collision)"""
     S = cfg.n_stations
     ok, k0, dk, L = clothoid_g1(F(goal[0]), F(goal[1]), F(goal[2]))
     if not ok:

@@ -134,6 +134,20 @@ def sample_traj(k0, dk, length, npts):
     return tr
 
 
+class _Cubic(C.Structure):
+    _fields_ = [("m", C.c_double), ("gx", C.c_double), ("gy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("ok", C.c_int)]
+
+
+def cubic_rows(gx, gy, gth, npts):
+    """the cubic generator's rows [npts, 4] (orc_cubic_setup / orc_cubic_row) at u_i = i / max(npts - 1, 1)"""
+    lib().orc_cubic_setup.restype = _Cubic
+    q = lib().orc_cubic_setup(C.c_double(gx), C.c_double(gy), C.c_double(gth))
+    tr = np.zeros((npts, 4))
+    for i in range(npts):
+        lib().orc_cubic_row(C.byref(q), C.c_double(float(i) / float(max(npts - 1, 1))), _p(tr[i]))
+    return tr
+
+
 def fresnel_moments(a, b, c):
     ic = np.zeros(3); is_ = np.zeros(3)
     lib().orc_fresnel_moments(C.c_double(a), C.c_double(b), C.c_double(c), _p(ic), _p(is_))
