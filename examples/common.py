@@ -155,8 +155,8 @@ def opponent_runs(args, rl, waypoints, cfg, make_planner, batch_states, gap=1.5,
     with args.groups = G the pack is G independent races (vehicle e in race e % G) and distances count within a race."""
     from f1tenth_planning_amd import Rivals, sim
     E, M = args.envs, min(args.opponents, args.envs - 1, 16)
-    if args.solver == "qp" or E < 2:
-        raise SystemExit("--opponents needs the shooting solver and --envs >= 2")
+    if (args.solver == "qp" and not getattr(args, "avoid", False)) or E < 2:
+        raise SystemExit("--opponents needs the shooting solver (or the kinematic MPC's --solver qp --avoid) and --envs >= 2")
     groups, apart = rival_groups(args, E)
     seg = np.hypot(np.diff(rl[:, 0]), np.diff(rl[:, 1]))
     k0 = int(np.argmin(np.abs(rl[:, 3])))                                # start where the heading is far from the +-pi seam
@@ -184,7 +184,7 @@ def opponent_runs(args, rl, waypoints, cfg, make_planner, batch_states, gap=1.5,
                 obs = np.stack([o[:, :, 0], o[:, :, 1], o[:, :, 2] * np.cos(o[:, :, 3]), o[:, :, 2] * np.sin(o[:, :, 3]), np.full((E, M), radius)], 2)
             planner.obstacles = obs
             out = planner.plan_batch(batch_states(env))
-            n_stop += int((out["best_idx"] < 0).sum())
+            n_stop += int((out["best_idx"] < 0).sum()) if "best_idx" in out else 0      # (the QP solver has no rollouts to block)
             env.step(np.column_stack([out["steer"], out["speed"] * scale]))
         closest[on] = d_min
         print(f"obstacle test {'on ' if on else 'off'}: smallest distance between two vehicles {d_min:.3f} m"

@@ -9,7 +9,10 @@ twice: each vehicle planning as if it were alone, then with its M nearest other 
 velocity (planner.obstacles).  It reports the smallest distance between two vehicles over each run.  With --rivals the opponents are not
 built here but found on the device by every plan (planner.rivals = Rivals(count=M, radius=...)); --groups G then splits the pack into G
 independent races.  --predict track predicts each rival along the raceline over the planner's
-horizon instead of at constant velocity (Rivals(predict="track"))."""
+horizon instead of at constant velocity (Rivals(predict="track")).
+
+--solver qp --avoid (mpc_config.QP_AVOID) lets the QP take the same obstacles and rivals as soft half-plane rows; without
+--avoid the QP takes none and --opponents with it is an error."""
 import os
 import sys
 
@@ -38,13 +41,17 @@ def main():
     ap.add_argument("--obstacles", type=int, default=0, help="park N obstacles (discs of 0.3 m) on the line and compare the loop with the occupancy test off / on")
     ap.add_argument("--opponents", type=int, default=0, help="with --envs E: each vehicle's M nearest other vehicles are moving obstacles of its rollouts; compares the pack with the test off / on")
     common.add_rival_flags(ap)
+    ap.add_argument("--avoid", action="store_true", help="with --solver qp: the opponents / rivals as soft half-plane rows of the QP (mpc_config.QP_AVOID)")
     ap.add_argument("--substeps", type=int, default=4, help="tested points per time step of a rollout (mpc_config.COLLISION_SUBSTEPS)")
     args = ap.parse_args()
+    if args.avoid and args.solver != "qp":
+        ap.error("--avoid adds rows to the QP: use it with --solver qp")
     rl = common.raceline(args, centerline=True)
     waypoints = [rl[:, 0], rl[:, 1], rl[:, 3], rl[:, 2]]          # [x, y, yaw, v]
     cfg = mpc_config()
     cfg.N_ROLLOUTS = args.rollouts
     cfg.SOLVER = args.solver
+    cfg.QP_AVOID = args.avoid
     if args.obstacles > 0:
         return obstacle_runs(args, rl, waypoints, cfg)
     if args.opponents > 0:

@@ -97,6 +97,17 @@ def kmpc_qp_opts(max_iter=50, tol=1e-10):
     return o
 
 
+class KmpcQpAvoid(C.Structure):
+    """struct f1p_kmpc_qp_avoid (include/f1p.h)"""
+    _fields_ = [("on", C.c_int32), ("pad", C.c_int32), ("margin", C.c_double), ("rho", C.c_double), ("lin", C.c_double)]
+
+
+def kmpc_qp_avoid(on=True, margin=0.0, rho=1e4, lin=10.0):
+    a = KmpcQpAvoid()
+    a.on, a.pad, a.margin, a.rho, a.lin = 1 if on else 0, 0, float(margin), float(rho), float(lin)
+    return a
+
+
 class StmpcCfg(C.Structure):
     """struct f1p_stmpc_cfg (include/f1p.h)"""
     _fields_ = [
@@ -291,6 +302,12 @@ PROTOTYPES = {
     "f1p_kmpc_qp_warm_get": (C.c_int, [_P, _P, _I, _I]),
     "f1p_kmpc_qp_warm_set": (C.c_int, [_P, _P, _I, _I]),
     "f1p_kmpc_qp_set_pack": (C.c_int, [_P, _I]),
+    "f1p_kmpc_qp_avoid_default": (None, [C.POINTER(KmpcQpAvoid)]),
+    "f1p_kmpc_qp_avoid_batch": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(KmpcCfg), C.POINTER(KmpcQpOpts), _P, _I, C.POINTER(KmpcQpAvoid),
+                                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f1p_kmpc_qp_avoid_dev": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(KmpcCfg), C.POINTER(KmpcQpOpts), _P, _I, C.POINTER(KmpcQpAvoid),
+                                        _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f1p_kmpc_qp_set_avoid": (C.c_int, [_P, C.POINTER(KmpcQpAvoid)]),
     "f1p_stmpc_qp_batch": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcQpOpts), _P, _P, _P, _P, _P, _P, _P, _P]),
     "f1p_stmpc_qp_dev": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcQpOpts), _P, _P, _P, _P, _P, _P, _P, _P]),
     "f1p_stmpc_qp_plan_batch": (C.c_int, [_P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcCfg), _D, _D, _D, C.POINTER(KmpcQpOpts), _P, _P,

@@ -152,6 +152,18 @@ def check_solver(c, weights, substeps, tk_within_t=False):
                 raise ValueError(f"SOLVER='qp' takes diagonal {n}x{n} weights only; mpc_config.{name} is not")
         if tk_within_t and c.TK > c.T:
             raise ValueError("SOLVER='qp' needs TK <= T (the reference's kinematic branch would linearise about a cut-short prediction)")
+    if getattr(c, "QP_AVOID", False):
+        if c.SOLVER != "qp":
+            raise ValueError("mpc_config.QP_AVOID adds avoidance rows to the QP; the shooting solver tests its rollouts without it (SOLVER='qp')")
+        rho, lin, margin = float(c.QP_AVOID_RHO), float(c.QP_AVOID_LIN), float(c.QP_AVOID_MARGIN)
+        if not (rho > 0.0 and np.isfinite(rho)):
+            raise ValueError(f"mpc_config.QP_AVOID_RHO must be finite and > 0, not {c.QP_AVOID_RHO!r}")
+        if not (lin >= 0.0 and np.isfinite(lin)):
+            raise ValueError(f"mpc_config.QP_AVOID_LIN must be finite and >= 0, not {c.QP_AVOID_LIN!r}")
+        if not np.isfinite(margin):
+            raise ValueError(f"mpc_config.QP_AVOID_MARGIN must be finite, not {c.QP_AVOID_MARGIN!r}")
+        if int(c.TK) > 31:
+            raise ValueError("mpc_config.QP_AVOID needs TK <= 31 (the slack takes the 64th lane's place)")
     if c.COLLISION:
         if c.SOLVER == "qp":
             raise ValueError("mpc_config.COLLISION tests the shooting solver's rollouts; SOLVER='qp' has none")
@@ -162,6 +174,13 @@ def check_solver(c, weights, substeps, tk_within_t=False):
 
 def qp_opts(c):
     return _abi.kmpc_qp_opts(max_iter=c.QP_MAX_ITER, tol=c.QP_TOL)
+
+
+def qp_avoid(c):
+    """mpc_config.QP_AVOID* as the f1p_kmpc_qp_avoid struct, None while it is off"""
+    if not getattr(c, "QP_AVOID", False):
+        return None
+    return _abi.kmpc_qp_avoid(True, c.QP_AVOID_MARGIN, c.QP_AVOID_RHO, c.QP_AVOID_LIN)
 
 
 def kin_cfg_struct(c, n_rollouts=None):
@@ -217,7 +236,9 @@ class MPCPlanner(OccupancyMap, Planner):
             return None
         c = self.config
         if c.SOLVER == "qp":
-            raise ValueError("obstacles are tested on the shooting solver's rollouts; SOLVER='qp' takes none")
+            if not getattr(c, "QP_AVOID", False):
+                raise ValueError("obstacles are tested on the shooting solver's rollouts; SOLVER='qp' takes none")
+            return check_obstacle_shape(obstacles, E, single)      # (mpc_config.QP_AVOID: rows of the QP, no tested points)
         o = check_obstacle_shape(obstacles, E, single)
         for name in self._SUBSTEPS:
             if not 1 <= int(getattr(c, name)) <= 16:
@@ -226,7 +247,10 @@ class MPCPlanner(OccupancyMap, Planner):
 
     def _check_rivals(self, rivals, E, obstacles):
         """the attribute `rivals` of a plan_batch over E egos; ValueError before anything touches the GPU"""
-        check_rivals(rivals, E, obstacles, self.config.SOLVER)
+        qp_rows = self.config.SOLVER == "qp" and getattr(self.config, "QP_AVOID", False)
+        check_rivals(rivals, E, obstacles, None if qp_rows else self.config.SOLVER)
+        if qp_rows:
+            return
         for name in self._SUBSTEPS:
             if not 1 <= int(getattr(self.config, name)) <= 16:
                 raise ValueError(f"{name} must be in [1, 16]")

@@ -28,6 +28,11 @@ obstacles: while it is set, every plan_batch finds each ego's M nearest other ve
 (f1p_rivals_dev) and tests the rollouts against them as above.  Persistent until set to None; not together with `obstacles`.
 predict="track" predicts each rival along the course it follows (the call's tracks / track_ids, else the raceline) over TK * DTK seconds
 (f1p_rivals_predict_dev).
+
+mpc_config.QP_AVOID = True (SOLVER="qp" only) lets the QP take `obstacles` (plan and plan_batch) and `rivals` (plan_batch) as well: per step
+the two discs nearest to the previous solution's path become half-plane rows of the QP, softened by one slack variable with the cost
+QP_AVOID_RHO eps^2 + QP_AVOID_LIN eps (f1p_kmpc_qp_set_avoid).  The rows are linearised and soft -- an avoidance term, not a
+guarantee; QP_AVOID_MARGIN [m] widens every disc.  TK <= 31.
 """
 import warnings
 from dataclasses import dataclass, field
@@ -35,10 +40,10 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ... import _abi
-from ..._planner import MPCPlanner, _track_columns, qp_opts
+from ..._planner import MPCPlanner, _track_columns, qp_avoid, qp_opts
 from ..._planner import kin_cfg_struct as _cfg_struct
 from ..._rivals import SINGLE_EGO, RivalFeed
-from ...runtime import Context, kmpc_set_obstacles, kmpc_set_obstacles_dev
+from ...runtime import Context, kmpc_qp_set_avoid, kmpc_set_obstacles, kmpc_set_obstacles_dev
 
 
 @dataclass
@@ -74,6 +79,12 @@ class mpc_config:
     # occupancy test on the shooting solver's rollouts (set_map / load_map): a rollout through an occupied cell cannot win
     COLLISION: bool = False
     COLLISION_SUBSTEPS: int = 1  # tested points per time step, 1 .. 16 (a step covers up to MAX_SPEED * DTK metres)
+    # SOLVER="qp" only: planner.obstacles / planner.rivals become soft, linearised half-plane rows of the QP
+    # (repr=False: the config's repr is part of KMPCPlanner.__init__'s signature, a pinned record -- tests/test_runtime_calls.py)
+    QP_AVOID: bool = field(default=False, repr=False)
+    QP_AVOID_MARGIN: float = field(default=0.0, repr=False)  # added to every disc's radius [m]
+    QP_AVOID_RHO: float = field(default=1e4, repr=False)  # the slack's quadratic penalty
+    QP_AVOID_LIN: float = field(default=10.0, repr=False)  # the slack's linear penalty
 
 
 @dataclass
@@ -126,6 +137,7 @@ class KMPCPlanner(MPCPlanner):
         self._inflate = 0.0
         self.obstacles = None              # moving discs of the NEXT plan, which takes them: [M, 5] for plan(), [E, M, 5] for plan_batch()
         self._obstacles_set = False        # the context holds obstacles of an earlier plan
+        self._qp_avoid_set = False         # the context's avoidance rows are switched on (mpc_config.QP_AVOID of an earlier plan)
         self.rivals = None                 # Rivals(...): every plan_batch tests each ego against its nearest other vehicles; persistent
         self._rival_feed = RivalFeed("xyvyaw", lambda ctx: kmpc_set_obstacles_dev(ctx, None))
         self._check_solver()
@@ -134,9 +146,15 @@ class KMPCPlanner(MPCPlanner):
         """the occupancy switch and the obstacles of this plan (None clears them); COLLISION_SUBSTEPS serves both tests.  rivals: the slots
         are filled on the device from the call's x0 and the context borrows them"""
         c = self.config
-        if c.SOLVER != "qp":
-            tested = obstacles is not None or rivals is not None
-            ctx.kmpc_set_collision(bool(c.COLLISION), int(c.COLLISION_SUBSTEPS) if (c.COLLISION or tested) else 1)
+        if c.SOLVER == "qp":
+            av = qp_avoid(c)
+            if av is not None or self._qp_avoid_set:             # (off after plans with it off: nothing to switch, no call -- as before QP_AVOID)
+                kmpc_qp_set_avoid(ctx, av)                       # (None: off -- the QP then ignores whatever the context holds)
+                self._qp_avoid_set = av is not None
+        if c.SOLVER != "qp" or c.QP_AVOID:
+            if c.SOLVER != "qp":
+                tested = obstacles is not None or rivals is not None
+                ctx.kmpc_set_collision(bool(c.COLLISION), int(c.COLLISION_SUBSTEPS) if (c.COLLISION or tested) else 1)
             if rivals is not None:
                 d_obs, _, E, M = self._rival_feed.run(ctx, rivals, x0, horizon=(float(c.TK) * float(c.DTK), 0.0), track_ids=track_ids)
                 kmpc_set_obstacles_dev(ctx, d_obs, E, M)

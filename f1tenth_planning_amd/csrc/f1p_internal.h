@@ -114,6 +114,7 @@ struct f1p_ctx {
     WarmBuf kmpc_qp_warm;
     bool kmpc_qp_warm_valid = false;
     int kmpc_qp_pack = 0;              // egos per wave at T <= 8: 0 = default, 1 or 4 forces it (timing runs)
+    f1p_kmpc_qp_avoid kmpc_qp_av = {0, 0, 0.0, 1e4, 10.0};   // f1p_kmpc_qp_set_avoid: on = the plan entry points take kmpc_obs as half-plane rows
     // the dynamic-MPC QP plan (f1p_stmpc_qp_plan_batch): fp64 warm start [E][W][2] = (oa, odelta_v), W = max(T, TK), keyed by (E, W);
     // per ego the length of the reference's self.oa (0: None) -- the branch's horizon -- on the host (the branch split is made there)
     WarmBuf stmpc_qp_warm;
@@ -293,6 +294,12 @@ int launch_kmpc_qp(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const 
                    const f1p_kmpc_cfg* cfg, int max_iter, double tol, double* d_steer, double* d_speed, int32_t* d_status, double* d_u,
                    double* d_xk, double* d_obj, double* d_duals, int32_t* d_iters, double* d_warm_out);
 int kmpc_qp_pack(const f1p_ctx* ctx, int T);
+// k_kmpc_qp.hip, the avoidance variant (f1p_kmpc_qp_avoid_*): d_obs [E][M][5] (M = 0: none), T <= 31; d_eps [E], d_planes [E][T][2][4] and
+// d_avoid_duals [E][2T+1] nullable
+int launch_kmpc_qp_avoid(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
+                         const f1p_kmpc_cfg* cfg, int max_iter, double tol, const double* d_obs, int M, const f1p_kmpc_qp_avoid* avoid,
+                         double* d_steer, double* d_speed, int32_t* d_status, double* d_u, double* d_xk, double* d_obj, double* d_duals,
+                         int32_t* d_iters, double* d_warm_out, double* d_eps, double* d_planes, double* d_avoid_duals);
 // k_stmpc_qp.hip: prev (oa, od_v) read at pa[(e T + t) pstride], pd[...] (nullable: zeros); warm_out [E][T][2] = (oa, od_v)
 int launch_stmpc_qp(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
                     const f1p_stmpc_cfg* cfg, int max_iter, double tol, double* d_steer, double* d_speed, int32_t* d_status, double* d_u,

@@ -15,6 +15,12 @@
 //   i = 2t   (a_t):     a_t upper, a_t lower, v_{t+1} upper, v_{t+1} lower
 //   i = 2t+1 (delta_t): delta_t upper, delta_t lower, rate_t upper, rate_t lower (none for t = T-1)
 // An ego's result does not depend on its neighbours (tests/test_gpu_kmpc_qp.py: batch invariance).
+//
+// AV (f1p_kmpc_qp_avoid_*): moving-disc avoidance.  One slack eps is input number 2T (n + 1 lanes per ego: G = 32, two egos
+// per wave, while 2T + 1 <= 32, else G = 64; T <= 31), cost rho eps^2 + lin eps, row -eps <= 0.  Per step t = 1..T the two live discs with
+// the least clearance at the linearisation path's point pbar_t give half-planes  -n.(S_xy(t) u) - eps <= n.(s_xy(t) - c) - (r + margin);
+// step t's first row is the fifth row of lane 2(t-1) (a_{t-1}), its second that of lane 2(t-1)+1 (delta_{t-1}), the eps lane's fifth row
+// is -eps <= 0.  The rows' u-coefficients are dense: kept in LDS (A, one row per lane, odd stride) before S becomes the Newton matrix.
 #include "qp_ipm.h"
 
 namespace f1p {
@@ -25,6 +31,11 @@ namespace {
 __host__ __device__ inline int qp_lds_doubles(int T) {
     const int n = 2 * T, Tp = T + 1;
     return 4 * Tp * n + n * n + 3 * n + T + 4 + 8 * Tp + 6 * T;
+}
+// ... of the avoidance variant: H, U, W, Y over nq = n + 1 inputs; the rows A [n][nq], WA [nq], pbar (x, y, yaw) [T] each, the discs
+__host__ __device__ inline int qp_lds_doubles_av(int T) {
+    const int n = 2 * T, Tp = T + 1, nq = n + 1;
+    return 4 * Tp * n + nq * nq + 3 * nq + T + 4 + 8 * Tp + 6 * T + n * nq + nq + 3 * T + 5 * F1P_KMPC_MAX_OBS;
 }
 
 struct QpLds {
@@ -42,22 +53,58 @@ struct QpLds {
     }
 };
 
+// the avoidance variant's: nq = n + 1 inputs (H, U, W, Y; (n + 1)^2 <= 4 (T+1) n still), and the avoidance rows A [n][nq] (odd stride: a lane
+// per row reads conflict-free), their published w / D WA [nq], pbar_1..T (x, y, yaw), the discs [16][5]
+struct QpLdsAv : QpLds {
+    double *A, *WA, *px, *py, *pw, *ob;
+    __device__ QpLdsAv(double* b, int T) : QpLds(b, T) {
+        const int n = 2 * T, Tp = T + 1, nq = n + 1;
+        S = b; M = b; b += 4 * Tp * n;
+        H = b; b += nq * nq;
+        U = b; b += nq; W = b; b += nq; Y = b; b += nq;
+        SUF = b; b += T;
+        x0 = b; b += 4;
+        ref = b; b += 4 * Tp;
+        fr = b; b += 4 * Tp;
+        vb = b; b += T; pb = b; b += T; cp = b; b += T; sp = b; b += T; pa = b; b += T; pd = b; b += T;
+        A = b; b += n * nq;
+        WA = b; b += nq;
+        px = b; b += T; py = b; b += T; pw = b; b += T;
+        ob = b;
+    }
+};
+
+// the avoidance variant's arguments: obs [E][M][5] (nullable with M = 0), the f1p_kmpc_qp_avoid numbers, and its outputs (nullable)
+struct QpAvoidArgs {
+    const double* obs;
+    int M;
+    double margin, rho, lin;
+    double *eps, *planes, *duals;
+};
+__device__ __forceinline__ QpAvoidArgs qp_avoid_args() { return QpAvoidArgs{}; }
+__device__ __forceinline__ QpAvoidArgs qp_avoid_args(const QpAvoidArgs& a) { return a; }
+
 }  // namespace
 
-template <int G>
+// AvArgs: none (the plain QP), or one QpAvoidArgs (AV)
+template <int G, class... AvArgs>
 __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, const double* __restrict__ refg,
                                                 const double* pa_g, const double* pd_g, int pstride, int E, f1p_kmpc_cfg cfg,
                                                 int max_iter, double tol, double* __restrict__ steer, double* __restrict__ speed,
                                                 int32_t* __restrict__ status, double* __restrict__ u_out, double* __restrict__ xk_out,
                                                 double* __restrict__ obj_out, double* __restrict__ duals, int32_t* __restrict__ iters_out,
-                                                double* warm_out) {
+                                                double* warm_out, AvArgs... av_args) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
+    constexpr bool AV = sizeof...(AvArgs) == 1;
+    [[maybe_unused]] const QpAvoidArgs av = qp_avoid_args(av_args...);
     constexpr int EPW = 64 / G;
+    constexpr int R = AV ? 5 : 4;                  // inequality rows per lane
     const int T = cfg.horizon, n = 2 * T, Tp = T + 1;
+    const int nq = AV ? n + 1 : n;                 // the QP's inputs: u, and eps with AV
     const int grp = threadIdx.x / G, i = threadIdx.x % G;
     const int e = blockIdx.x * EPW + grp;
     const bool ego = e < E;
-    QpLds L(reinterpret_cast<double*>(lds_raw) + (size_t)grp * qp_lds_doubles(T), T);
+    std::conditional_t<AV, QpLdsAv, QpLds> L(reinterpret_cast<double*>(lds_raw) + (size_t)grp * (AV ? qp_lds_doubles_av(T) : qp_lds_doubles(T)), T);
     const int tau = i >> 1, j = i & 1;
     const bool in_n = i < n;
     const double DTK = cfg.dt;
@@ -72,6 +119,15 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
             const double a = pa_g ? pa_g[((size_t)e * T + k) * pstride] : 0.0;
             const double d = pd_g ? pd_g[((size_t)e * T + k) * pstride] : 0.0;
             L.pa[k] = a; L.pd[k] = d; bad |= !(isfinite(a) && isfinite(d));
+        }
+        if constexpr (AV) {
+            for (int m = i; m < av.M; m += G) {                // a live slot (r >= 0) must be finite; an empty one is kept as r = -1
+                const double* o = av.obs + ((size_t)e * av.M + m) * 5;
+                const double ox = o[0], oy = o[1], ovx = o[2], ovy = o[3], r = o[4];
+                const bool live = r >= 0.0;
+                L.ob[5 * m] = ox; L.ob[5 * m + 1] = oy; L.ob[5 * m + 2] = ovx; L.ob[5 * m + 3] = ovy; L.ob[5 * m + 4] = live ? r : -1.0;
+                bad |= live && !(isfinite(ox) && isfinite(oy) && isfinite(ovx) && isfinite(ovy) && isfinite(r));
+            }
         }
     }
     bad = gmax<G>(bad ? 1.0 : 0.0) > 0.0;
@@ -97,6 +153,7 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
             fx = nx; fy = ny;
             L.fr[t + 1] = fx; L.fr[Tp + t + 1] = fy; L.fr[2 * Tp + t + 1] = fv; L.fr[3 * Tp + t + 1] = fw;
             kmpc_step<false>(s, L.pa[t], L.pd[t], cfg);
+            if constexpr (AV) { L.px[t] = s.x; L.py[t] = s.y; L.pw[t] = s.yaw; }      // pbar_{t+1}
         }
     }
     __syncthreads();
@@ -133,21 +190,69 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
             }
             if (c == i) h += 2.0 * (cfg.r[j] + ((tau > 0) + (tau < T - 1)) * cfg.rd[j]);
             if (c == i - 2 || c == i + 2) h -= 2.0 * cfg.rd[j];
-            L.H[i * n + c] = h;
+            L.H[i * nq + c] = h;
+        }
+        if constexpr (AV) L.H[i * nq + n] = 0.0;
+    }
+    // AV: this lane's half-plane (step tau + 1, the j-th nearest live disc), its row of A, and the eps lane's row of H
+    double pl_nx = 0.0, pl_ny = 0.0, pl_h = 0.0;
+    int pl_slot = -1;
+    if constexpr (AV) {
+        if (in_n && !done) {
+            const int t = tau + 1;
+            const double tt = (double)t * DTK, px = L.px[tau], py = L.py[tau];
+            double c0 = INFINITY, c1 = INFINITY;
+            int m0 = -1, m1 = -1;
+            for (int m = 0; m < av.M; ++m) {               // the two least clearances, ties to the lower slot
+                const double r = L.ob[5 * m + 4];
+                if (!(r >= 0.0)) continue;
+                const double dx = px - (L.ob[5 * m] + L.ob[5 * m + 2] * tt), dy = py - (L.ob[5 * m + 1] + L.ob[5 * m + 3] * tt);
+                const double clear = sqrt(dx * dx + dy * dy) - r;
+                if (clear < c0) { c1 = c0; m1 = m0; c0 = clear; m0 = m; }
+                else if (clear < c1) { c1 = clear; m1 = m; }
+            }
+            const int ms = j == 0 ? m0 : m1;
+            if (ms >= 0) {
+                const double r = L.ob[5 * ms + 4];
+                const double cx = L.ob[5 * ms] + L.ob[5 * ms + 2] * tt, cy = L.ob[5 * ms + 1] + L.ob[5 * ms + 3] * tt;
+                const double dx = px - cx, dy = py - cy, dist = sqrt(dx * dx + dy * dy);
+                if (dist < 1e-9) {                           // on the disc's centre: stay behind it
+                    double sn, cs;
+                    sincos(L.pw[tau], &sn, &cs);
+                    pl_nx = -cs; pl_ny = -sn;
+                } else {
+                    pl_nx = dx / dist; pl_ny = dy / dist;
+                }
+                pl_h = pl_nx * (L.fr[t] - cx) + pl_ny * (L.fr[Tp + t] - cy) - (r + av.margin);
+                pl_slot = ms;
+            }
+            for (int c = 0; c < n; ++c)
+                L.A[i * nq + c] = pl_slot >= 0 ? -(pl_nx * L.S[(4 * t + 0) * n + c] + pl_ny * L.S[(4 * t + 1) * n + c]) : 0.0;
+        }
+        if (i == n && !done) {
+            for (int c = 0; c < n; ++c) L.H[n * nq + c] = 0.0;
+            L.H[n * nq + n] = 2.0 * av.rho;
+            g = av.lin;
         }
     }
 
     // ---- 3. interior point (qp_ipm.h) ----------------------------------------------------------------------------------------------------
     const double MD = cfg.max_dsteer * DTK;
-    double h[4];
-    bool valid[4];
+    double h[R];
+    bool valid[R];
     if (j == 0) { h[0] = cfg.max_accel; h[1] = cfg.max_accel; h[2] = cfg.max_speed - v0; h[3] = v0 - cfg.min_speed; }
     else        { h[0] = cfg.max_steer; h[1] = cfg.max_steer; h[2] = MD; h[3] = MD; }
 #pragma unroll
     for (int r = 0; r < 4; ++r) valid[r] = in_n && (j == 0 || r < 2 || tau < T - 1);
+    double m_rows = 8.0 * T - 2.0;
+    if constexpr (AV) {
+        h[4] = in_n ? pl_h : 0.0;
+        valid[4] = in_n ? pl_slot >= 0 : i == n;
+        m_rows += 1.0 + gsum<G>(in_n && pl_slot >= 0 ? 1.0 : 0.0);
+    }
 
     // G x for this lane's rows (x published in vec[])
-    auto gmul = [&](const double* vec, const double (&x)[1], double (&out)[4]) {
+    auto gmul = [&](const double* vec, const double (&x)[1], double (&out)[R]) {
         const double xi = x[0];
         if (!in_n) {
             out[0] = out[1] = out[2] = out[3] = 0.0;
@@ -161,12 +266,21 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) out[r] = valid[r] ? out[r] : 0.0;
+        if constexpr (AV) {                                  // A_i . u - eps; the eps lane: -eps  (A_i is zero from column 2 (tau + 1))
+            double o = 0.0;
+            if (valid[4]) {
+                if (in_n) for (int c = 0; c < 2 * tau + 2; ++c) o += L.A[i * nq + c] * vec[c];
+                o -= vec[n];
+            }
+            out[4] = o;
+        }
     };
     // (G' w)_i: the rows' w_2 - w_3 published in W[]
-    auto gtmul = [&](const double (&w)[4], double (&o)[1]) {
+    auto gtmul = [&](const double (&w)[R], double (&o)[1]) {
         double w2 = valid[2] ? w[2] - w[3] : 0.0;
         __syncthreads();
         if (in_n) L.W[i] = w2;
+        if constexpr (AV) { if (i < nq) L.WA[i] = valid[4] ? w[4] : 0.0; }
         __syncthreads();
         o[0] = (valid[0] ? w[0] : 0.0) - (valid[1] ? w[1] : 0.0);
         if (!in_n) {
@@ -178,12 +292,25 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
         } else {
             o[0] += -w2 + (tau > 0 ? L.W[i - 2] : 0.0);
         }
+        if constexpr (AV) {                                  // column i of A over the rows of steps > tau; the eps lane: minus every row's w
+            if (in_n) {
+                double a = 0.0;
+                for (int r = 2 * tau; r < n; ++r) a += L.A[r * nq + i] * L.WA[r];
+                o[0] += a;
+            } else if (i == n) {
+                double a = 0.0;
+                for (int r = 0; r < nq; ++r) a += L.WA[r];
+                o[0] = -a;
+            }
+        }
     };
     // row i of M = H + G' diag(D) G, lower triangle: a diagonal, the rate rows' tridiagonal (delta), DTK^2 x suffix sums of the
     // v rows' D over max(tau, c / 2) (a)
-    auto newton_rows = [&](const double (&D)[4]) {
+    // AV: + sum_r D_r A_r A_r' on the u block, -sum_r D_r A_r in the eps row, 2 rho + sum_r D_r + D_eps on its diagonal
+    auto newton_rows = [&](const double (&D)[R]) {
         __syncthreads();
         if (in_n) L.W[i] = D[2] + D[3];
+        if constexpr (AV) { if (i < nq) L.WA[i] = D[4]; }
         __syncthreads();
         if (j == 0 && in_n) {
             double suf = 0.0;
@@ -193,19 +320,36 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
         __syncthreads();
         if (in_n) {
             for (int c = 0; c <= i; ++c) {
-                double m = L.H[i * n + c];
+                double m = L.H[i * nq + c];
                 if (j == 0 && (c & 1) == 0) m += DTK * DTK * L.SUF[max(tau, c >> 1)];
                 if (c == i) m += D[0] + D[1] + (j == 1 ? L.W[i] + (tau > 0 ? L.W[i - 2] : 0.0) : 0.0);
                 if (j == 1 && c == i - 2) m -= L.W[i - 2];
-                L.M[i * n + c] = m;
+                if constexpr (AV) {
+                    double a = 0.0;
+                    for (int r = 2 * tau; r < n; ++r) a += L.WA[r] * L.A[r * nq + i] * L.A[r * nq + c];
+                    m += a;
+                }
+                L.M[i * nq + c] = m;
+            }
+        }
+        if constexpr (AV) {
+            if (i == n) {
+                double sd = 0.0;
+                for (int r = 0; r < nq; ++r) sd += L.WA[r];
+                for (int c = 0; c < n; ++c) {
+                    double a = 0.0;
+                    for (int r = c & ~1; r < n; ++r) a += L.WA[r] * L.A[r * nq + c];
+                    L.M[n * nq + c] = -a;
+                }
+                L.M[n * nq + n] = 2.0 * av.rho + sd;
             }
         }
     };
 
     const double gv[1] = {g};
-    double u[1], lam[4];
+    double u[1], lam[R];
     int it_done;
-    qp_ipm<G, 1, 4, true>(QpIpmLds{L.H, L.M, L.U, L.Y}, n, i, gv, h, valid, 8.0 * T - 2.0, max_iter, tol, done, st, it_done, u, lam, gmul, gtmul,
+    qp_ipm<G, 1, R, true>(QpIpmLds{L.H, L.M, L.U, L.Y}, nq, i, gv, h, valid, m_rows, max_iter, tol, done, st, it_done, u, lam, gmul, gtmul,
                     newton_rows);
 
     // ---- outputs --------------------------------------------------------------------------------------------------------------------
@@ -224,6 +368,19 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
                 du_[2 * T + tau] = ok ? lam[0] : NaN; du_[3 * T + tau] = ok ? lam[1] : NaN;
                 if (tau < T - 1) { du_[R4 + tau] = ok ? lam[2] : NaN; du_[R4 + T - 1 + tau] = ok ? lam[3] : NaN; }
             }
+        }
+        if constexpr (AV) {
+            if (av.planes) {
+                double* p = av.planes + ((size_t)e * n + i) * 4;
+                p[0] = ok ? pl_nx : NaN; p[1] = ok ? pl_ny : NaN; p[2] = ok ? pl_h : NaN; p[3] = ok ? (double)pl_slot : NaN;
+            }
+            if (av.duals) av.duals[(size_t)e * nq + i] = ok ? lam[4] : NaN;
+        }
+    }
+    if constexpr (AV) {
+        if (i == n) {
+            if (av.duals) av.duals[(size_t)e * nq + n] = ok ? lam[4] : NaN;
+            if (av.eps) av.eps[e] = ok ? u[0] : NaN;
         }
     }
     if (i == 0) {
@@ -254,6 +411,7 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
                 const double nw = w + (DTK * vb / cfg.wheelbase) * d;
                 x = nx; y = ny; v = nv; w = nw;
             }
+            if constexpr (AV) f += av.rho * L.U[n] * L.U[n] + av.lin * L.U[n];
             if (obj_out) obj_out[e] = ok ? f : NaN;
         }
     }
@@ -281,6 +439,25 @@ int launch_kmpc_qp(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const 
     hipLaunchKernelGGL(kern, dim3((unsigned)((E + epw - 1) / epw)), dim3(64), lds, ctx->stream, d_x0, d_ref, d_pa, d_pd, pstride, E, *cfg,
                        max_iter, tol, d_steer, d_speed, d_status, d_u, d_xk, d_obj, d_duals, d_iters, d_warm_out);
     return check_hip(ctx, hipGetLastError(), "k_kmpc_qp launch");
+}
+
+// the avoidance variant: 2T + 1 lanes per ego -- two egos per wave while they fit 32 lanes (T <= 15), else one
+int launch_kmpc_qp_avoid(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
+                         const f1p_kmpc_cfg* cfg, int max_iter, double tol, const double* d_obs, int M, const f1p_kmpc_qp_avoid* avoid,
+                         double* d_steer, double* d_speed, int32_t* d_status, double* d_u, double* d_xk, double* d_obj, double* d_duals,
+                         int32_t* d_iters, double* d_warm_out, double* d_eps, double* d_planes, double* d_avoid_duals) {
+    if (E <= 0) return F1P_OK;
+    const int T = cfg->horizon;
+    if (T > 31 || M < 0 || M > F1P_KMPC_MAX_OBS || (M > 0 && !d_obs)) return set_error(ctx, F1P_EINVAL, "kmpc qp avoid: bad horizon / obstacles");
+    const int epw = 2 * T + 1 <= 32 ? 2 : 1;
+    const size_t lds = sizeof(double) * (size_t)qp_lds_doubles_av(T) * epw;
+    const auto kern = epw == 2 ? &k_kmpc_qp<32, QpAvoidArgs> : &k_kmpc_qp<64, QpAvoidArgs>;
+    const int rc = qp_lds_opt_in(ctx, reinterpret_cast<const void*>(kern), lds, "kmpc qp: horizon too long for the CU's LDS");
+    if (rc) return rc;
+    const QpAvoidArgs av{d_obs, M, avoid->margin, avoid->rho, avoid->lin, d_eps, d_planes, d_avoid_duals};
+    hipLaunchKernelGGL(kern, dim3((unsigned)((E + epw - 1) / epw)), dim3(64), lds, ctx->stream, d_x0, d_ref, d_pa, d_pd, pstride, E, *cfg,
+                       max_iter, tol, d_steer, d_speed, d_status, d_u, d_xk, d_obj, d_duals, d_iters, d_warm_out, av);
+    return check_hip(ctx, hipGetLastError(), "k_kmpc_qp_avoid launch");
 }
 
 }  // namespace f1p

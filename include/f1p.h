@@ -654,7 +654,8 @@ int f1p_kmpc_set_groups(f1p_ctx* ctx, int32_t groups);
  * With the test on, the entry points above return an error and launch nothing when no grid is loaded (F1P_ESTATE), when an
  * oriented footprint is installed (f1p_set_footprint with n_discs > 0: this is a point / disc test, use f1p_inflate_grid;
  * F1P_ESTATE) or when f1p_kmpc_set_groups(> 0) is in force (F1P_ESTATE).  n_sub outside [1, 16]: F1P_EINVAL, nothing changes.
- * Not covered: f1p_kmpc_qp_*.  f1p_stmpc_* has a switch of its own, f1p_stmpc_set_collision; this one does not reach it. */
+ * Not covered: f1p_kmpc_qp_* (the QP has no rollouts to test; the grid is not among its constraints).  f1p_stmpc_* has a switch of its
+ * own, f1p_stmpc_set_collision; this one does not reach it. */
 int f1p_kmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub);
 /* Moving obstacles on the rollouts of the shooting solver: per ego up to F1P_KMPC_MAX_OBS discs at constant
  * velocity, obs [E][M][5] fp64 rows (x, y, vx, vy, r) in the map frame.  A slot with !(r >= 0) -- r negative or NaN -- is EMPTY;
@@ -672,7 +673,9 @@ int f1p_kmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub);
  * then evaluated in plain fp64 whatever the mode and equal f1p_kmpc_plan_dev bit for bit.
  * Errors, nothing launched: M outside [1, 16]: F1P_EINVAL; a plan whose E is not the E the obstacles were set for: F1P_ESTATE;
  * f1p_kmpc_set_groups(> 0) while obstacles are set (and setting obstacles while groups are forced): F1P_ESTATE.
- * Not covered: f1p_stmpc_* (f1p_stmpc_set_obstacles is its own), f1p_kmpc_qp_*, and a MultiContext's sharded plans. */
+ * f1p_kmpc_qp_plan_batch / f1p_kmpc_qp_dev take the same discs as soft half-plane rows of the QP while f1p_kmpc_qp_set_avoid is on
+ * (below), and ignore them while it is off.
+ * Not covered: f1p_stmpc_* (f1p_stmpc_set_obstacles is its own) and a MultiContext's sharded plans. */
 #define F1P_KMPC_MAX_OBS 16
 int f1p_kmpc_set_obstacles(f1p_ctx* ctx, const double* obs, int32_t E, int32_t M);
 int f1p_kmpc_set_obstacles_dev(f1p_ctx* ctx, const double* d_obs, int32_t E, int32_t M);
@@ -731,6 +734,44 @@ int f1p_kmpc_qp_warm_get(f1p_ctx* ctx, double* warm, int32_t E, int32_t T);
 int f1p_kmpc_qp_warm_set(f1p_ctx* ctx, const double* warm, int32_t E, int32_t T);
 /* egos per wave of the QP kernel at T <= 8: 0 = default, 1 or 4 forces it (timing runs; longer horizons always take one per wave) */
 int f1p_kmpc_qp_set_pack(f1p_ctx* ctx, int32_t egos_per_wave);
+
+/* Moving-disc avoidance in the QP: f1p_kmpc_set_obstacles' discs as SOFT, LINEARISED half-plane rows.  An avoidance
+ * term, not a guarantee: the rows are linearised about the previous solution's path and softened by a slack; margin is the knob.
+ * The problem of f1p_kmpc_qp_* is kept -- the same u, linearisation path and 8T-2 rows -- and gains
+ *   one slack eps as input number 2T (n = 2T + 1): cost rho eps^2 + lin eps, row -eps <= 0;
+ *   at most two rows per step t = 1..T.  pbar_t: the position of the linearisation path (predict_motion_kinematic of the previous
+ *     solution) at step t.  A live slot (r >= 0) is predicted at tau = (double)t * dt: c = (x + vx tau, y + vy tau), d = pbar_t - c,
+ *     dist = sqrt(dx^2 + dy^2), clear = dist - r.  The two live slots with the smallest clear are taken, ties to the lower slot;
+ *     each gives the normal n = d / dist (dist < 1e-9: n = -(cos psibar_t, sin psibar_t), stay behind it) and, with x_t = S(t) u + s(t)
+ *     the linear model's state, the row   -n.(S_xy(t) u) - eps <= n.(s_xy(t) - c) - (r + margin).
+ * An ego without a live slot has no such row and keeps eps and -eps <= 0.  Always feasible when f1p_kmpc_qp_* is (status 1 as there);
+ * a live slot with a non-finite number: status 3.  2 <= horizon <= 31 (else F1P_EINVAL).  The warm start stays u [E][T][2]; eps is not
+ * carried.  obj includes rho eps^2 + lin eps.
+ * f1p_kmpc_qp_avoid_batch / _dev: f1p_kmpc_qp_batch / _dev with obs [E][M][5] (M in 1..16) and avoid (NULL: the defaults; `on` is not
+ *   read), and the nullable outputs eps [E]; planes [E][T][2][4] = (n_x, n_y, right-hand side, slot as a double; slot -1 and zeros for
+ *   an absent row); avoid_duals [E][2T+1]: the multipliers of the 2T avoidance rows in step order (0 for an absent row), then of
+ *   -eps <= 0.  duals [E][8T-2] keeps its layout.  Statuses 1 and 3: NaN in all of them.
+ * f1p_kmpc_qp_set_avoid: NULL or on = 0 turns it off (the default).  While on, f1p_kmpc_qp_plan_batch and f1p_kmpc_qp_dev solve this
+ *   problem with the discs held by f1p_kmpc_set_obstacles[_dev] (none held: no avoidance rows); a plan whose E is not the E the
+ *   obstacles were set for: F1P_ESTATE; horizon 32: F1P_EINVAL.  rho > 0, lin >= 0 and a finite margin are required, otherwise
+ *   F1P_EINVAL and nothing changes. */
+typedef struct f1p_kmpc_qp_avoid {
+    int32_t on;              /* f1p_kmpc_qp_set_avoid: 0 turns the rows off   */
+    int32_t pad;
+    double margin;           /* added to every disc's radius [m] (0)          */
+    double rho;              /* quadratic slack penalty (1e4)                 */
+    double lin;              /* linear slack penalty (10)                     */
+} f1p_kmpc_qp_avoid;
+void f1p_kmpc_qp_avoid_default(f1p_kmpc_qp_avoid* avoid);
+int f1p_kmpc_qp_avoid_batch(f1p_ctx* ctx, const double* x0, const double* ref, const double* oa_prev, const double* od_prev, int32_t E,
+                            const f1p_kmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* obs, int32_t M,
+                            const f1p_kmpc_qp_avoid* avoid, double* steer, double* speed, int32_t* status, double* u, double* xk,
+                            double* obj, double* duals, int32_t* iters, double* eps, double* planes, double* avoid_duals);
+int f1p_kmpc_qp_avoid_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_prev, int32_t E,
+                          const f1p_kmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* d_obs, int32_t M,
+                          const f1p_kmpc_qp_avoid* avoid, double* d_steer, double* d_speed, int32_t* d_status, double* d_u, double* d_xk,
+                          double* d_obj, double* d_duals, int32_t* d_iters, double* d_eps, double* d_planes, double* d_avoid_duals);
+int f1p_kmpc_qp_set_avoid(f1p_ctx* ctx, const f1p_kmpc_qp_avoid* avoid);
 
 /* ------------------------------------------------------------------------------------------------
  * Dynamic single-track MPC as the reference solves it: the linearised QP of control/dynamic_mpc/dynamic_mpc.py, batched, fp64

@@ -1,0 +1,37 @@
+#!/usr/bin/env python3
+"""tests/golden/g20_kmpc_qp_avoid.npz: the exact optima of the avoidance-row scenes (tests/kmpc_qp_avoid_scenes.py: 64 egos for each of
+T in {2, 8, 31} x M in {1, 4, 16}) from tests/kmpc_qp_avoid_ref.py.  The T = 31 batches take a minute each, too long for a unit test; the
+tests rebuild every problem and certify the recorded points on it, and recompute the short horizons outright.  CPU only.
+
+    python tools/gen_golden_kmpc_qp_avoid.py [T ...]      (the horizons to redo; the others are kept from the file)
+"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import kmpc_qp_avoid_scenes as SC  # noqa: E402
+
+
+def main():
+    path = os.path.join(ROOT, "tests", "golden", SC.GOLDEN_FILE)
+    only = [int(a) for a in sys.argv[1:]]
+    out = dict(np.load(path, allow_pickle=False)) if only else {}
+    for T, M in SC.SHAPES:
+        if only and T not in only:
+            continue
+        sols = SC.solve_scene(T, M)
+        n, k = 2 * T, f"T{T}_M{M}_"
+        out[k + "solved"] = np.array([s is not None for s in sols])
+        out[k + "w"] = np.array([s["w"] if s else np.full(n + 1, np.nan) for s in sols])
+        out[k + "lam"] = np.array([s["lam"][:8 * T - 2] if s else np.full(8 * T - 2, np.nan) for s in sols])
+        out[k + "avoid_lam"] = np.array([s["avoid_lam"] if s else np.full(n + 1, np.nan) for s in sols])
+        out[k + "degenerate"] = np.array([bool(s and s["degenerate"]) for s in sols])
+        print(T, M, "solved", int(out[k + "solved"].sum()), "degenerate", int(out[k + "degenerate"].sum()), flush=True)
+    np.savez_compressed(path, **out)
+
+
+if __name__ == "__main__":
+    main()
