@@ -544,7 +544,10 @@ int f1p_lattice_emit_dev(f1p_ctx* ctx, const double* d_poses, const double* d_go
 
 /* Clothoid leaf: G1 Hermite fit from (0,0,0) to each goal (x, y, theta) -- what
  * pyclothoids.Clothoid.G1Hermite(0,0,0,x,y,theta) returns (lattice_planner.py:196).
- * goals [n][3] -> kappa0 [n], dkappa [n], length [n], ok [n] (0 = Newton did not converge / degenerate). */
+ * goals [n][3] -> kappa0 [n], dkappa [n], length [n], ok [n] (0 = Newton did not converge / degenerate).
+ * Domain: a chord r = hypot(x, y) <= 1e-12 or a value that is not finite is rejected (ok = 0, zero parameters) and wherever ok = 1
+ * all three parameters are finite; pinned to a 50-digit reference for r = 1.1e-12 .. 1e150 and any finite theta (reduced by whole multiples of
+ * the double 2 pi; straight behind the ego the sign of a zero y picks the side).  From r ~ 1.3e154 length^2 overflows and dkappa is 0. */
 int f1p_clothoid_g1_batch(f1p_ctx* ctx, const double* goals, int32_t n, double* kappa0, double* dkappa,
                           double* length, int32_t* ok);
 

@@ -122,10 +122,10 @@ def intersect_first_batch(px, py, radius, wx, wy, tstart, wrap=True, window=64):
 
 
 def _ieee_remainder(x, y):
-    """C remainder(x, y): x - n*y with n = round-half-even(x / y); numpy has no ufunc for it"""
-    n = np.rint(x / y)
-    r = x - n * y
-    # a mis-rounded quotient at the +-y/2 seam
+    """C remainder(x, y), y > 0: x - n*y with n = round(x / y), EXACT for any finite x (numpy has no ufunc for it).  fmod is exact; the step
+    from its result in (-y, y) to [-y/2, y/2] subtracts y from a number in (y/2, y): exact too.  (x - rint(x / y) * y rounds n * y: off by
+    1e-10 at x = 1e6, and on the wrong side of the +-y/2 seam when x is within that of it.)  At an exact tie the sign is x's, not the even n's."""
+    r = np.fmod(x, y)
     r = np.where(r > 0.5 * y, r - y, r)
     r = np.where(r < -0.5 * y, r + y, r)
     return r

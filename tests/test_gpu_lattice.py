@@ -1,6 +1,7 @@
 """K3 parity on the MI355X: the fused lattice planner through the C-ABI against the CPU oracle.
 Bar: nearest / best-candidate indices and status bit-exact; steer/speed 1e-5 (north_star), measured ~1e-12;
-best_traj 1e-4, measured ~1e-12; clothoid parameters 1e-9."""
+best_traj 1e-4, measured ~1e-12; clothoid parameters 1e-12 against the independent solver's fixture, 1e-11 (scale-free) against
+the oracle, whose Newton iteration stops at |g| <= 1e-13."""
 import numpy as np
 import pytest
 
@@ -41,8 +42,8 @@ def test_clothoid_fit_vs_oracle_and_known_answers(ctx, orc):
     for j in range(0, 2000, 7):
         o_ok, o_k0, o_dk, o_L = orc.clothoid_g1(*goals[j])
         assert bool(ok[j]) == o_ok
-        if o_ok:
-            assert abs(k0[j] - o_k0) < 1e-9 and abs(dk[j] - o_dk) < 1e-9 and abs(L[j] - o_L) < 1e-10
+        if o_ok:                                                        # k0 L, kappa' L^2, L / L: the units of the oracle's 1e-11 (L is 0.3 .. 7 m here)
+            assert abs(k0[j] - o_k0) * o_L < 1e-11 and abs(dk[j] - o_dk) * o_L * o_L < 1e-11 and abs(L[j] - o_L) < 1e-11 * o_L
 
 
 def test_lattice_device_goals_vs_oracle(ctx, orc, scene):
@@ -395,7 +396,8 @@ def test_long_station_counts_fit_the_lds_or_fail_cleanly(ctx, orc, scene):
 
 def test_g1_fit_branch_against_the_independent_solver(ctx, golden):
     """f1p_clothoid_g1_batch (the kernel's g1_fit) against tools/gen_clothoid_g14.py's fixture: 1704 goals incl. goals behind the
-    ego, |theta| up to pi and the normalisation seams; kappa0, kappa', L to 1e-9 relative, agreed failure set."""
+    ego, |theta| up to pi and the normalisation seams; kappa0, kappa', L to 1e-12 relative to max(1, |.|) (the fixture is good to rounding:
+    DESIGN.md 5q), agreed failure set."""
     g = golden("g14_clothoid_g1.npz")
     G = g["goals"]
     k0, dk, L, ok = ctx.clothoid_g1(G)
@@ -403,9 +405,9 @@ def test_g1_fit_branch_against_the_independent_solver(ctx, golden):
     sel = (g["ok"] == 1) & (g["ambiguous"] == 0)
     for name, got in (("k0", k0), ("dk", dk), ("L", L)):
         scale = np.maximum(1.0, np.abs(g[name][sel]))
-        assert (np.abs(got[sel] - g[name][sel]) / scale).max() < 1e-9, name
+        assert (np.abs(got[sel] - g[name][sel]) / scale).max() < 1e-12, name
     for i in np.nonzero(g["ambiguous"])[0]:
-        assert abs(L[i] - g["L"][i]) < 1e-9 and abs(abs(k0[i]) - abs(g["k0"][i])) < 1e-9
+        assert abs(L[i] - g["L"][i]) < 1e-12 * max(1.0, g["L"][i]) and abs(abs(k0[i]) - abs(g["k0"][i])) < 1e-12 * max(1.0, abs(g["k0"][i]))
 
 
 def test_candidate_slices_over_several_workgroups(ctx, scene):
