@@ -156,7 +156,7 @@ def opponent_runs(args, rl, waypoints, cfg, make_planner, batch_states, gap=1.5,
     from f1tenth_planning_amd import Rivals, sim
     E, M = args.envs, min(args.opponents, args.envs - 1, 16)
     if (args.solver == "qp" and not getattr(args, "avoid", False)) or E < 2:
-        raise SystemExit("--opponents needs the shooting solver (or the kinematic MPC's --solver qp --avoid) and --envs >= 2")
+        raise SystemExit("--opponents needs the shooting solver (or --solver qp --avoid) and --envs >= 2")
     groups, apart = rival_groups(args, E)
     seg = np.hypot(np.diff(rl[:, 0]), np.diff(rl[:, 1]))
     k0 = int(np.argmin(np.abs(rl[:, 3])))                                # start where the heading is far from the +-pi seam

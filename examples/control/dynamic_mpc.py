@@ -9,7 +9,10 @@ twice: each vehicle planning as if it were alone, then with its M nearest other 
 velocity (planner.obstacles; both branches of the model test them).  It reports the smallest distance between two vehicles over each run.
 With --rivals the opponents are not built here but found on the device by every plan (planner.rivals = Rivals(count=M, radius=...));
 --groups G then splits the pack into G independent races.  --predict track predicts each rival along the raceline over the planner's
-horizon instead of at constant velocity (Rivals(predict="track"))."""
+horizon instead of at constant velocity (Rivals(predict="track")).
+
+--solver qp --avoid (mpc_config.QP_AVOID) lets the QPs of both branches take the same obstacles and rivals as soft half-plane rows
+(DESIGN.md 5r); without --avoid the QP takes none and --opponents with it is an error."""
 import os
 import sys
 
@@ -28,14 +31,17 @@ def main():
     ap.add_argument("--obstacles", type=int, default=0, help="park N obstacles (discs of 0.3 m) on the line and compare the loop with the occupancy test off / on")
     ap.add_argument("--opponents", type=int, default=0, help="with --envs E: each vehicle's M nearest other vehicles are moving obstacles of its rollouts; compares the pack with the test off / on")
     common.add_rival_flags(ap)
+    ap.add_argument("--avoid", action="store_true", help="with --solver qp: the opponents / rivals as soft half-plane rows of the QPs (mpc_config.QP_AVOID)")
     ap.add_argument("--substeps", type=int, default=1, help="tested points per step of the dynamic model (mpc_config.COLLISION_SUBSTEPS; the kinematic branch tests twice as many)")
     args = ap.parse_args()
+    if args.avoid and args.solver != "qp":
+        ap.error("--avoid adds rows to the QP: use it with --solver qp")
     lanes = ids = None
     if args.tracks > 0:
         if args.solver != "qp":
             raise SystemExit("--tracks plans with STMPCPlanner.plan_batch, which needs --solver qp")
         args.envs = args.tracks
-    if args.envs != 1 and args.tracks == 0 and args.solver != "shooting":
+    if args.envs != 1 and args.tracks == 0 and args.solver != "shooting" and not (args.avoid and args.opponents > 0):
         raise SystemExit("--envs N drives N vehicles with the shooting solver's plan_batch; with --solver qp use --tracks N")
     rl = common.raceline(args, centerline=True)
     if args.obstacles > 0:
@@ -50,7 +56,7 @@ def main():
     if args.opponents > 0:
         if args.tracks > 0:
             raise SystemExit("--opponents drives the pack on the raceline with the shooting solver")
-        cfg = mpc_config(SOLVER=args.solver)
+        cfg = mpc_config(SOLVER=args.solver, QP_AVOID=args.avoid)
         cfg.COLLISION_SUBSTEPS, cfg.COLLISION_SUBSTEPS_K = args.substeps, min(2 * args.substeps, 16)
         return common.opponent_runs(args, rl, [rl[:, 0], rl[:, 1], rl[:, 3], rl[:, 2]], cfg, lambda wp, c: STMPCPlanner(waypoints=wp, config=c),
                                     lambda env: env.state)

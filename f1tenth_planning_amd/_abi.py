@@ -108,6 +108,9 @@ def kmpc_qp_avoid(on=True, margin=0.0, rho=1e4, lin=10.0):
     return a
 
 
+STMPC_QP_AVOID_MAX_T = 40   # F1P_STMPC_QP_AVOID_MAX_T (include/f1p.h)
+
+
 class StmpcCfg(C.Structure):
     """struct f1p_stmpc_cfg (include/f1p.h)"""
     _fields_ = [
@@ -308,6 +311,12 @@ PROTOTYPES = {
     "f1p_kmpc_qp_avoid_dev": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(KmpcCfg), C.POINTER(KmpcQpOpts), _P, _I, C.POINTER(KmpcQpAvoid),
                                         _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "f1p_kmpc_qp_set_avoid": (C.c_int, [_P, C.POINTER(KmpcQpAvoid)]),
+    "f1p_stmpc_qp_avoid_batch": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcQpOpts), _P, _I, C.POINTER(KmpcQpAvoid),
+                                           _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f1p_stmpc_qp_avoid_dev": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcQpOpts), _P, _I, C.POINTER(KmpcQpAvoid),
+                                         _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f1p_stmpc_qp_set_avoid": (C.c_int, [_P, C.POINTER(KmpcQpAvoid)]),
+    "f1p_stmpc_qp_avoid_lds_bytes": (C.c_int64, [_I]),
     "f1p_stmpc_qp_batch": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcQpOpts), _P, _P, _P, _P, _P, _P, _P, _P]),
     "f1p_stmpc_qp_dev": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcQpOpts), _P, _P, _P, _P, _P, _P, _P, _P]),
     "f1p_stmpc_qp_plan_batch": (C.c_int, [_P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcCfg), _D, _D, _D, C.POINTER(KmpcQpOpts), _P, _P,

@@ -138,10 +138,10 @@ def _diag(m):
     return np.diag(m) if m.ndim == 2 else m
 
 
-def check_solver(c, weights, substeps, tk_within_t=False):
+def check_solver(c, weights, substeps, tk_within_t=False, avoid_max_t=None):
     """ValueError before anything touches the GPU: an unknown SOLVER, weights the QP path does not take (diagonal only), a COLLISION
     setting without meaning.  weights: ((mpc_config field, size), ...) of the QP's weight matrices; substeps: the fields that count tested
-    points per step; tk_within_t: the QP also needs TK <= T (STMPCPlanner)."""
+    points per step; tk_within_t: the QP also needs TK <= T (STMPCPlanner); avoid_max_t: QP_AVOID's cap on T (STMPCPlanner's dynamic QP)."""
     if c.SOLVER not in SOLVERS:
         raise ValueError(f"mpc_config.SOLVER must be one of {SOLVERS}, not {c.SOLVER!r}")
     if c.SOLVER == "qp":
@@ -164,6 +164,8 @@ def check_solver(c, weights, substeps, tk_within_t=False):
             raise ValueError(f"mpc_config.QP_AVOID_MARGIN must be finite, not {c.QP_AVOID_MARGIN!r}")
         if int(c.TK) > 31:
             raise ValueError("mpc_config.QP_AVOID needs TK <= 31 (the slack takes the 64th lane's place)")
+        if avoid_max_t is not None and int(c.T) > avoid_max_t:
+            raise ValueError(f"mpc_config.QP_AVOID needs T <= {avoid_max_t} (F1P_STMPC_QP_AVOID_MAX_T: the avoidance rows share the CU's LDS with the Newton matrix)")
     if c.COLLISION:
         if c.SOLVER == "qp":
             raise ValueError("mpc_config.COLLISION tests the shooting solver's rollouts; SOLVER='qp' has none")
@@ -215,9 +217,10 @@ class MPCPlanner(OccupancyMap, Planner):
     _QP_WEIGHTS = ()                       # ((mpc_config field, size), ...)
     _SUBSTEPS = ()
     _TK_WITHIN_T = False
+    _QP_AVOID_MAX_T = None                 # mpc_config.QP_AVOID's cap on T, where the planner's QP has one
 
     def _check_solver(self):
-        check_solver(self.config, self._QP_WEIGHTS, self._SUBSTEPS, self._TK_WITHIN_T)
+        check_solver(self.config, self._QP_WEIGHTS, self._SUBSTEPS, self._TK_WITHIN_T, self._QP_AVOID_MAX_T)
 
     def _check_collision(self):
         """ValueError before anything touches the GPU: the checks of check_solver, and COLLISION without a map"""

@@ -23,6 +23,11 @@ ego's M nearest other vehicles of its race among the call's own states on the de
 tests the rollouts of both branches against them.  Persistent until set to None; not together with `obstacles`.
 predict="track" predicts each rival along the planner's raceline over max(T * DT, TK * DTK) seconds, one value for both branches
 (f1p_rivals_predict_dev).
+
+mpc_config.QP_AVOID = True (SOLVER="qp" only) lets the QP take `obstacles` (plan and plan_batch) and `rivals` (plan_batch, with and without
+`tracks`) as well: in both branches the two discs nearest to the previous solution's path become, per step, half-plane rows of the QP,
+softened by one slack variable with the cost QP_AVOID_RHO eps^2 + QP_AVOID_LIN eps (f1p_stmpc_qp_set_avoid).  The rows are
+linearised and soft -- an avoidance term, not a guarantee; QP_AVOID_MARGIN [m] widens every disc.  T <= 40, TK <= 31.
 """
 import warnings
 from dataclasses import dataclass, field
@@ -30,9 +35,9 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ... import _abi
-from ..._planner import MPCPlanner, _course_columns, _diag, _track_columns, kin_cfg_struct, qp_opts
+from ..._planner import MPCPlanner, _course_columns, _diag, _track_columns, kin_cfg_struct, qp_avoid, qp_opts
 from ..._rivals import SINGLE_EGO, RivalFeed
-from ...runtime import Context, kmpc_set_obstacles, stmpc_set_obstacles, stmpc_set_obstacles_dev
+from ...runtime import Context, kmpc_set_obstacles, stmpc_qp_set_avoid, stmpc_set_obstacles, stmpc_set_obstacles_dev
 from ..kinematic_mpc.kinematic_mpc import State  # noqa: F401  (same 7-field dataclass, :89-98)
 
 
@@ -81,6 +86,12 @@ class mpc_config:
     COLLISION: bool = False
     COLLISION_SUBSTEPS: int = 1    # tested points per step of the dynamic model, 1 .. 16 (a step covers up to MAX_SPEED * DT = 0.15 m)
     COLLISION_SUBSTEPS_K: int = 2  # ... per step of the kinematic branch, 1 .. 16 (up to V_KS * DTK + acceleration)
+    # SOLVER="qp" only: planner.obstacles / planner.rivals become soft, linearised half-plane rows of both branches' QPs
+    # (repr=False: the config's repr is part of STMPCPlanner.__init__'s signature, a pinned record -- tests/test_runtime_calls.py)
+    QP_AVOID: bool = field(default=False, repr=False)
+    QP_AVOID_MARGIN: float = field(default=0.0, repr=False)  # added to every disc's radius [m]
+    QP_AVOID_RHO: float = field(default=1e4, repr=False)  # the slack's quadratic penalty
+    QP_AVOID_LIN: float = field(default=10.0, repr=False)  # the slack's linear penalty
 
 
 class STMPCPlanner(MPCPlanner):
@@ -95,6 +106,7 @@ class STMPCPlanner(MPCPlanner):
     _QP_WEIGHTS = (("R", 2), ("Rd", 2), ("Q", 7), ("Qf", 7), ("Rk", 2), ("Rdk", 2), ("Qk", 4), ("Qfk", 4))
     _SUBSTEPS = ("COLLISION_SUBSTEPS", "COLLISION_SUBSTEPS_K")
     _TK_WITHIN_T = True
+    _QP_AVOID_MAX_T = _abi.STMPC_QP_AVOID_MAX_T
 
     def __init__(self, waypoints=None, config=mpc_config(),
                  params=np.array([3.74, 0.15875, 0.17145, 0.074, 4.718, 5.4562, 0.04712, 1.0489]), debug=False, device=None):
@@ -114,15 +126,30 @@ class STMPCPlanner(MPCPlanner):
         self._inflate = 0.0
         self.obstacles = None              # moving discs of the NEXT plan, which takes them: [M, 5] for plan(), [E, M, 5] for plan_batch()
         self._obstacles_set = [False, False]   # the context holds obstacles of an earlier plan: the kmpc state, the stmpc state
+        self._qp_avoid_set = False         # the context's avoidance rows are switched on (mpc_config.QP_AVOID of an earlier plan)
         self.rivals = None                 # Rivals(...): every plan_batch tests each ego against its nearest other vehicles; persistent
         self._rival_feed = RivalFeed("st7", lambda ctx: stmpc_set_obstacles_dev(ctx, None))
         self._check_solver()
 
-    def _collision_switch(self, ctx, obstacles=None, kinematic=False, rivals=None, states=None):
+    def _collision_switch(self, ctx, obstacles=None, kinematic=False, rivals=None, states=None, track_ids=None):
         """the planner's context follows mpc_config: the stmpc switch (plan_batch, plan()'s dynamic branch) and, for plan()'s kinematic
         branch through ctx.kmpc_shoot, the kmpc switch with COLLISION_SUBSTEPS_K.  The obstacles of this plan (None clears them) go to
         the stmpc state, or (kinematic: plan()'s kinematic branch) to the kmpc state; the substep counts serve both tests"""
         c = self.config
+        if c.SOLVER == "qp":
+            av = qp_avoid(c)
+            if av is not None or self._qp_avoid_set:             # (off after plans with it off: nothing to switch, no call -- as before QP_AVOID)
+                stmpc_qp_set_avoid(ctx, av)                      # (None: off -- the QP then ignores whatever the context holds)
+                self._qp_avoid_set = av is not None
+            if av is not None:                                   # both branches of the QP plan read the stmpc state, in the caller's order
+                if rivals is not None:
+                    d_obs, _, E, M = self._rival_feed.run(ctx, rivals, states, horizon=(max(float(c.T) * float(c.DT), float(c.TK) * float(c.DTK)), 0.0),
+                                                          track_ids=track_ids)
+                    stmpc_set_obstacles_dev(ctx, d_obs, E, M)
+                    self._obstacles_set[1] = True
+                elif obstacles is not None or self._obstacles_set[1]:
+                    stmpc_set_obstacles(ctx, obstacles)
+                    self._obstacles_set[1] = obstacles is not None
         if c.SOLVER != "qp":
             on = bool(c.COLLISION)
             sub = on or obstacles is not None or rivals is not None
@@ -227,10 +254,13 @@ class STMPCPlanner(MPCPlanner):
             ctx.set_tracks_cached(cols, cols=(0, 1, 2, 3))
             x0 = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 7)
             c = self.config
+            self._collision_switch(ctx, obstacles, rivals=rivals, states=x0, track_ids=track_ids)
             return ctx.stmpc_qp_plan_tracks(x0, Context._ids(track_ids, x0.shape[0]), self._dyn_cfg(), self._kin_cfg(), v_ks=c.V_KS,
                                             dl=c.dl, dlk=c.dlk, opts=qp_opts(c), want_u=want_u)
         ctx = self._bind(waypoints)
-        return self._qp(ctx, np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 7), want_u=want_u)
+        x0 = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 7)
+        self._collision_switch(ctx, obstacles, rivals=rivals, states=x0)
+        return self._qp(ctx, x0, want_u=want_u)
 
     def reset(self):
         """forget the warm start (a new episode)"""

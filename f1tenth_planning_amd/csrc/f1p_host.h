@@ -146,6 +146,7 @@ inline int validate_stmpc(f1p_ctx* ctx, const f1p_stmpc_cfg* cfg, int E) { retur
 // f1p_kmpc.hip: the QP's cfg checks, and opts (nullable: the defaults) into *o, range-checked
 int validate_kmpc_qp(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, int E, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o);
 int qp_opts(f1p_ctx* ctx, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o, const char* what);
+int validate_qp_avoid(f1p_ctx* ctx, const f1p_kmpc_qp_avoid* a);
 // f1p_kmpc.hip: the argument checks of the four reference extractions (f1p_{kmpc,stmpc}_ref[_tracks]_{batch,dev}), and the *_batch body behind them:
 // ncol = 4 (kinematic rows) or 7 (dynamic rows); track_id (host) is read when tracks, else every ego follows the raceline
 int validate_ref(f1p_ctx* ctx, const void* states, const int32_t* track_id, bool tracks, int E, int horizon, double dt, double dl, const void* ref);

@@ -118,6 +118,7 @@ struct f1p_ctx {
     // the dynamic-MPC QP plan (f1p_stmpc_qp_plan_batch): fp64 warm start [E][W][2] = (oa, odelta_v), W = max(T, TK), keyed by (E, W);
     // per ego the length of the reference's self.oa (0: None) -- the branch's horizon -- on the host (the branch split is made there)
     WarmBuf stmpc_qp_warm;
+    f1p_kmpc_qp_avoid stmpc_qp_av = {0, 0, 0.0, 1e4, 10.0};  // f1p_stmpc_qp_set_avoid: on = the QP entry points take stmpc_obs as half-plane rows
     std::vector<int32_t> stmpc_qp_len;
     // the dynamic-MPC shooting plan (f1p_stmpc_plan_*): f32 warm start [E][W][2], W = max(T, TK), keyed by (E, T, TK), and per ego the
     // branch that wrote its row -- 0: none (zeros are generated around), 1: kinematic ([TK][2] = (accel, steer)), 2: dynamic
@@ -305,6 +306,15 @@ int launch_stmpc_qp(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const
                     const f1p_stmpc_cfg* cfg, int max_iter, double tol, double* d_steer, double* d_speed, int32_t* d_status, double* d_u,
                     double* d_x, double* d_obj, double* d_duals, int32_t* d_iters, double* d_warm_out);
 size_t stmpc_qp_lds_bytes(int T);
+// k_stmpc_qp.hip, the avoidance variant (f1p_stmpc_qp_avoid_*): d_obs [E][M][5] (M = 0: none), T <= F1P_STMPC_QP_AVOID_MAX_T; d_eps [E],
+// d_planes [E][T][2][4] and d_avoid_duals [E][2T+1] nullable
+int launch_stmpc_qp_avoid(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
+                          const f1p_stmpc_cfg* cfg, int max_iter, double tol, const double* d_obs, int M, const f1p_kmpc_qp_avoid* avoid,
+                          double* d_steer, double* d_speed, int32_t* d_status, double* d_u, double* d_x, double* d_obj, double* d_duals,
+                          int32_t* d_iters, double* d_warm_out, double* d_eps, double* d_planes, double* d_avoid_duals);
+size_t stmpc_qp_avoid_lds_bytes(int T);
+// a plan branch's discs: d_obs [idx[k]][M][5] (the caller's ego order) -> d_out [k][M][5]
+int launch_stmpc_qp_obs_in(f1p_ctx* ctx, const double* d_obs, const int32_t* d_idx, int nb, int M, double* d_out);
 int launch_stmpc_qp_warm_in(f1p_ctx* ctx, const double* d_warm, const int32_t* d_idx, const int32_t* d_use, int nb, int Tb, int W, double* d_out);
 int launch_stmpc_qp_warm_out(f1p_ctx* ctx, const double* d_in, const int32_t* d_idx, int nb, int Tb, int W, double* d_warm);
 int launch_stmpc_qp_kref(f1p_ctx* ctx, const double* d_ref7, int nb, int T, double* d_ref4);

@@ -343,7 +343,7 @@ static int qp_avoid_plan_check(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, int E) {
     return F1P_OK;
 }
 
-static int validate_qp_avoid(f1p_ctx* ctx, const f1p_kmpc_qp_avoid* a) {
+int f1p::validate_qp_avoid(f1p_ctx* ctx, const f1p_kmpc_qp_avoid* a) {     // (f1p_stmpc_qp_avoid_* checks its numbers with it too)
     if (!(a->rho > 0) || !isfinite(a->rho) || !(a->lin >= 0) || !isfinite(a->lin) || !isfinite(a->margin))
         return set_error(ctx, F1P_EINVAL, "kmpc qp avoid: rho must be finite and > 0, lin finite and >= 0, margin finite");
     return F1P_OK;

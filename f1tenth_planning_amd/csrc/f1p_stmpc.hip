@@ -209,6 +209,86 @@ static int validate_stmpc_qp(f1p_ctx* ctx, const f1p_stmpc_cfg* cfg, int E, cons
     return qp_opts(ctx, opts, o, "stmpc qp");
 }
 
+// f1p_stmpc_qp_set_avoid is on: what the QP entry points check before they launch the avoidance variants on the context's discs
+// (kcfg: the plan's kinematic branch, which runs k_kmpc_qp's variant; E: the caller's ego count, the order the discs are held in)
+static int stqp_avoid_plan_check(f1p_ctx* ctx, const f1p_stmpc_cfg* cfg, const f1p_kmpc_cfg* kcfg, int E) {
+    if (cfg->horizon > F1P_STMPC_QP_AVOID_MAX_T)
+        return set_error(ctx, F1P_EINVAL, "stmpc qp avoid: horizon must be <= F1P_STMPC_QP_AVOID_MAX_T (40: the packed avoidance rows beside H and the Newton matrix in LDS)");
+    if (kcfg && kcfg->horizon > 31) return set_error(ctx, F1P_EINVAL, "stmpc qp avoid: the kinematic branch's horizon must be <= 31 (2TK + 1 inputs, one lane each)");
+    const ObsState& st = ctx->stmpc_obs;
+    if (st.cur && E != st.E)
+        return set_error(ctx, F1P_ESTATE, "stmpc obstacles were set for " + std::to_string(st.E) + " egos, this plan has " + std::to_string(E) + " (f1p_stmpc_set_obstacles)");
+    return F1P_OK;
+}
+
+int64_t f1p_stmpc_qp_avoid_lds_bytes(int32_t horizon) { return horizon < 2 ? -1 : (int64_t)stmpc_qp_avoid_lds_bytes(horizon); }
+
+int f1p_stmpc_qp_set_avoid(f1p_ctx* ctx, const f1p_kmpc_qp_avoid* avoid) {
+    F1P_ENTER(ctx);
+    if (!avoid || !avoid->on) { ctx->stmpc_qp_av.on = 0; return F1P_OK; }
+    const int rc = validate_qp_avoid(ctx, avoid); if (rc) return rc;
+    ctx->stmpc_qp_av = *avoid;
+    ctx->stmpc_qp_av.on = 1; ctx->stmpc_qp_av.pad = 0;
+    return F1P_OK;
+}
+
+// the checks of the two stateless avoidance entry points -> *a (avoid, or the defaults)
+static int validate_stqp_avoid_call(f1p_ctx* ctx, const f1p_stmpc_cfg* cfg, int E, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o, const void* obs,
+                                    int M, const f1p_kmpc_qp_avoid* avoid, f1p_kmpc_qp_avoid* a) {
+    int rc = validate_stmpc_qp(ctx, cfg, E, opts, o); if (rc) return rc;
+    if (cfg->horizon > F1P_STMPC_QP_AVOID_MAX_T)
+        return set_error(ctx, F1P_EINVAL, "stmpc qp avoid: horizon must be <= F1P_STMPC_QP_AVOID_MAX_T (40: the packed avoidance rows beside H and the Newton matrix in LDS)");
+    if (M < 1 || M > F1P_KMPC_MAX_OBS) return set_error(ctx, F1P_EINVAL, "stmpc qp avoid: M must be in [1, 16]");
+    if (E > 0 && !obs) return set_error(ctx, F1P_EINVAL, "stmpc qp avoid: obs is NULL");
+    f1p_kmpc_qp_avoid_default(a);
+    if (avoid) *a = *avoid;
+    return validate_qp_avoid(ctx, a);
+}
+
+int f1p_stmpc_qp_avoid_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_v_prev,
+                           int32_t E, const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* d_obs, int32_t M,
+                           const f1p_kmpc_qp_avoid* avoid, double* d_steer, double* d_speed, int32_t* d_status, double* d_u, double* d_x,
+                           double* d_obj, double* d_duals, int32_t* d_iters, double* d_eps, double* d_planes, double* d_avoid_duals) {
+    F1P_ENTER(ctx);
+    f1p_kmpc_qp_opts o;
+    f1p_kmpc_qp_avoid a;
+    int rc = validate_stqp_avoid_call(ctx, cfg, E, opts, &o, d_obs, M, avoid, &a); if (rc) return rc;
+    if (E > 0 && (!d_x0 || !d_ref || !d_steer || !d_speed || !d_status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
+    return launch_stmpc_qp_avoid(ctx, d_x0, d_ref, d_oa_prev, d_od_v_prev, 1, E, cfg, o.max_iter, o.tol, d_obs, M, &a, d_steer, d_speed, d_status,
+                                 d_u, d_x, d_obj, d_duals, d_iters, nullptr, d_eps, d_planes, d_avoid_duals);
+}
+
+int f1p_stmpc_qp_avoid_batch(f1p_ctx* ctx, const double* x0, const double* ref, const double* oa_prev, const double* od_v_prev, int32_t E,
+                             const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* obs, int32_t M,
+                             const f1p_kmpc_qp_avoid* avoid, double* steer, double* speed, int32_t* status, double* u, double* x,
+                             double* obj, double* duals, int32_t* iters, double* eps, double* planes, double* avoid_duals) {
+    F1P_ENTER(ctx);
+    f1p_kmpc_qp_opts o;
+    f1p_kmpc_qp_avoid a;
+    int rc = validate_stqp_avoid_call(ctx, cfg, E, opts, &o, obs, M, avoid, &a); if (rc) return rc;
+    if (E > 0 && (!x0 || !ref || !steer || !speed || !status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
+    if (E == 0) return F1P_OK;
+    const size_t T = cfg->horizon, e = E, m = M;
+    Stage s(ctx);
+    s.need(8 * 7 * e); s.need(8 * e * 7 * (T + 1)); s.need(8 * e * T, oa_prev); s.need(8 * e * T, od_v_prev); s.need(8 * e * m * 5);
+    s.need(8 * e); s.need(8 * e); s.need(4 * e); s.need(8 * e * T * 2, u); s.need(8 * e * 7 * (T + 1), x); s.need(8 * e, obj);
+    s.need(8 * e * (10 * T - 2), duals); s.need(4 * e, iters); s.need(8 * e, eps); s.need(8 * e * T * 8, planes); s.need(8 * e * (2 * T + 1), avoid_duals);
+    if ((rc = s.begin())) return rc;
+    const double *d_x0, *d_ref, *d_oa, *d_od, *d_obs;
+    if ((rc = s.in(x0, 7 * e, &d_x0))) return rc;
+    if ((rc = s.in(ref, e * 7 * (T + 1), &d_ref))) return rc;
+    if ((rc = s.in(oa_prev, e * T, &d_oa))) return rc;
+    if ((rc = s.in(od_v_prev, e * T, &d_od))) return rc;
+    if ((rc = s.in(obs, e * m * 5, &d_obs))) return rc;
+    double* d_steer = s.out(steer, e); double* d_speed = s.out(speed, e); int32_t* d_st = s.out(status, e);
+    double* d_u = s.out(u, e * T * 2); double* d_x = s.out(x, e * 7 * (T + 1)); double* d_obj = s.out(obj, e);
+    double* d_du = s.out(duals, e * (10 * T - 2)); int32_t* d_it = s.out(iters, e);
+    double* d_eps = s.out(eps, e); double* d_pl = s.out(planes, e * T * 8); double* d_ad = s.out(avoid_duals, e * (2 * T + 1));
+    if ((rc = launch_stmpc_qp_avoid(ctx, d_x0, d_ref, d_oa, d_od, 1, E, cfg, o.max_iter, o.tol, d_obs, M, &a, d_steer, d_speed, d_st, d_u, d_x,
+                                    d_obj, d_du, d_it, nullptr, d_eps, d_pl, d_ad))) return rc;
+    return s.finish();
+}
+
 int f1p_stmpc_qp_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_v_prev, int32_t E,
                      const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, double* d_steer, double* d_speed, int32_t* d_status,
                      double* d_u, double* d_x, double* d_obj, double* d_duals, int32_t* d_iters) {
@@ -216,6 +296,12 @@ int f1p_stmpc_qp_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, cons
     f1p_kmpc_qp_opts o;
     int rc = validate_stmpc_qp(ctx, cfg, E, opts, &o); if (rc) return rc;
     if (E > 0 && (!d_x0 || !d_ref || !d_steer || !d_speed || !d_status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
+    if (ctx->stmpc_qp_av.on) {
+        if ((rc = stqp_avoid_plan_check(ctx, cfg, nullptr, E))) return rc;
+        return launch_stmpc_qp_avoid(ctx, d_x0, d_ref, d_oa_prev, d_od_v_prev, 1, E, cfg, o.max_iter, o.tol, ctx->stmpc_obs.cur, ctx->stmpc_obs.M,
+                                     &ctx->stmpc_qp_av, d_steer, d_speed, d_status, d_u, d_x, d_obj, d_duals, d_iters, nullptr, nullptr, nullptr,
+                                     nullptr);
+    }
     return launch_stmpc_qp(ctx, d_x0, d_ref, d_oa_prev, d_od_v_prev, 1, E, cfg, o.max_iter, o.tol, d_steer, d_speed, d_status, d_u, d_x,
                            d_obj, d_duals, d_iters, nullptr);
 }
@@ -274,6 +360,10 @@ static int stmpc_qp_plan_impl(f1p_ctx* ctx, const double* x0, const int32_t* tra
         return set_error(ctx, F1P_ESTATE, "waypoints with a heading column are required");
     }
     if (E == 0) return F1P_OK;
+    const bool av = ctx->stmpc_qp_av.on != 0;
+    if (av && (rc = stqp_avoid_plan_check(ctx, dcfg, kcfg, E))) return rc;
+    const double* d_obs_all = av ? ctx->stmpc_obs.cur : nullptr;              // [E][M][5] in the caller's order, or none held
+    const int Mo = d_obs_all ? ctx->stmpc_obs.M : 0;
     const int T = dcfg->horizon, TK = kcfg->horizon, W = T;                   // W = max(T, TK)
     if ((rc = ensure_stqp_warm(ctx, E, W))) return rc;
     double* d_warm = ctx->stmpc_qp_warm.as<double>();
@@ -284,7 +374,7 @@ static int stmpc_qp_plan_impl(f1p_ctx* ctx, const double* x0, const int32_t* tra
         for (const int e : sp.idx[b]) { const int len = ctx->stmpc_qp_len[e]; use[b].push_back(b ? (len >= T) : (len > 0 && len <= TK)); }
     const size_t nd = sp.idx[1].size(), nk = sp.idx[0].size();
     const size_t need = sp.arena_bytes() + 2 * al256(8 * 2 * T * nd) + 2 * al256(8 * 2 * TK * nk) + al256(4 * nd) + al256(4 * nk) +
-                        3 * al256(8 * (size_t)E) + al256(4 * (size_t)E);
+                        3 * al256(8 * (size_t)E) + al256(4 * (size_t)E) + al256(8 * 5 * (size_t)Mo * nd) + al256(8 * 5 * (size_t)Mo * nk);
     if ((rc = arena_reset(ctx, need))) return rc;
     std::vector<double> hs(E), hv(E), ho(E), hw[2];
     std::vector<int32_t> hst(E);
@@ -305,7 +395,19 @@ static int stmpc_qp_plan_impl(f1p_ctx* ctx, const double* x0, const int32_t* tra
         if ((rc = launch_stmpc_qp_warm_in(ctx, d_warm, sp.d_idx[b], d_use, nb, Tb, W, d_win))) return rc;
         // this branch's egos are written contiguously from offset 0 of its own slice: kinematic egos after the dynamic ones
         const size_t off = b ? 0 : nd;
-        if (b) rc = launch_stmpc_qp(ctx, sp.d_x7, sp.d_ref7[1], d_win, d_win + 1, 2, nb, dcfg, o.max_iter, o.tol, d_steer + off, d_speed + off, d_st + off,
+        if (av) {                                                             // this branch's discs, gathered on the device; each branch its own variant
+            double* d_obs = nullptr;
+            if (Mo) {
+                d_obs = (double*)arena_take(ctx, 8 * 5 * (size_t)Mo * nb);
+                if ((rc = launch_stmpc_qp_obs_in(ctx, d_obs_all, sp.d_idx[b], nb, Mo, d_obs))) return rc;
+            }
+            if (b) rc = launch_stmpc_qp_avoid(ctx, sp.d_x7, sp.d_ref7[1], d_win, d_win + 1, 2, nb, dcfg, o.max_iter, o.tol, d_obs, Mo, &ctx->stmpc_qp_av,
+                                              d_steer + off, d_speed + off, d_st + off, nullptr, nullptr, d_obj + off, nullptr, nullptr, d_wout[b],
+                                              nullptr, nullptr, nullptr);
+            else rc = launch_kmpc_qp_avoid(ctx, sp.d_s4[0], sp.d_ref4, d_win, d_win + 1, 2, nb, kcfg, ok_.max_iter, ok_.tol, d_obs, Mo, &ctx->stmpc_qp_av,
+                                           d_steer + off, d_speed + off, d_st + off, nullptr, nullptr, d_obj + off, nullptr, nullptr, d_wout[b],
+                                           nullptr, nullptr, nullptr);
+        } else if (b) rc = launch_stmpc_qp(ctx, sp.d_x7, sp.d_ref7[1], d_win, d_win + 1, 2, nb, dcfg, o.max_iter, o.tol, d_steer + off, d_speed + off, d_st + off,
                                     nullptr, nullptr, d_obj + off, nullptr, nullptr, d_wout[b]);
         else rc = launch_kmpc_qp(ctx, sp.d_s4[0], sp.d_ref4, d_win, d_win + 1, 2, nb, kcfg, ok_.max_iter, ok_.tol, d_steer + off, d_speed + off, d_st + off,
                                  nullptr, nullptr, d_obj + off, nullptr, nullptr, d_wout[b]);

@@ -24,6 +24,13 @@
 // Mapping: one wave per ego; lane tau owns time step tau -- both inputs (rows 2 tau, 2 tau + 1 of H and of the Newton matrix) and the
 // ten inequality rows of step tau -- so T <= 64 on one wave; the LDS of H and the Newton matrix (2 n^2 doubles) bounds T at
 // F1P_STMPC_QP_MAX_T.  An ego's arithmetic depends on nothing outside its own workgroup: results are batch invariant.
+//
+// AV (f1p_stmpc_qp_avoid_*): moving-disc avoidance.  The QP has nq = 2T + 2 inputs: lane T owns the slack eps (input 2T, cost
+// rho eps^2 + lin eps, row -eps <= 0; solved for as eps / sig, sig = 1 / sqrt(2 rho)) and a padding input 2T + 1 (H = 1, g = 0, no row: it stays 0) that keeps nq a multiple of the two
+// inputs a lane owns.  Lane t - 1 owns the two avoidance rows of step t (rows 10 and 11 of its twelve): the two live discs with the least
+// clearance at the linearisation path's point pbar_t give  -n.(S_xy(t) u) - eps <= n.(s_xy(t) - c) - (r + margin).  Their u-coefficients
+// are taken from step t's slab as it passes through LDS and kept packed: the rows of step t are zero from column 2t on, so row 2(t-1) + j
+// holds 2t doubles at A[2 t (t-1) + 2 t j], 2T(T+1) in all.
 #include "qp_ipm.h"
 
 namespace f1p {
@@ -38,6 +45,17 @@ __host__ __device__ inline int stqp_lds_doubles(int T) {
     const int n = 2 * T, Tp = T + 1;
     return 2 * n * n + 8 + 14 * Tp + NJ * T + 7 * n + 3 * n + 8 * T;
 }
+
+// ... of the avoidance variant: H and M over nq = n + 2 inputs, U / W / Y at nq; the packed rows A, their published w / D WA [n + 1],
+// pbar_1..T (x, y, yaw + beta), the discs [16][5]
+__host__ __device__ constexpr int stqp_lds_doubles_av(int T) {
+    const int n = 2 * T, Tp = T + 1, nq = n + 2;
+    return 2 * nq * nq + 8 + 14 * Tp + NJ * T + 7 * n + 3 * nq + 8 * T + n * Tp + (n + 1) + 3 * T + 5 * F1P_KMPC_MAX_OBS;
+}
+// the default horizon must run; F1P_STMPC_QP_AVOID_MAX_T is the longest horizon whose layout one workgroup may claim (160 KiB) with
+// room left for the 1 KiB the plain kernel's cap leaves too
+static_assert(8 * stqp_lds_doubles_av(F1P_STMPC_QP_AVOID_MAX_T) <= 160 * 1024 - 1024, "F1P_STMPC_QP_AVOID_MAX_T does not fit the CU's LDS");
+static_assert(8 * stqp_lds_doubles_av(F1P_STMPC_QP_AVOID_MAX_T + 1) > 160 * 1024 - 1024, "F1P_STMPC_QP_AVOID_MAX_T is not the cap");
 
 struct StQpLds {
     double *H, *M, *x0, *ref, *fr, *J, *SL, *U, *W, *Y, *Wd, *Wv, *Wr, *Sd, *Sv, *pa, *pd, *pv;
@@ -56,6 +74,37 @@ struct StQpLds {
     }
 };
 
+struct StQpLdsAv {
+    double *H, *M, *x0, *ref, *fr, *J, *SL, *U, *W, *Y, *Wd, *Wv, *Wr, *Sd, *Sv, *pa, *pd, *pv, *A, *WA, *px, *py, *pw, *ob;
+    __device__ StQpLdsAv(double* b, int T) {
+        const int n = 2 * T, Tp = T + 1, nq = n + 2;
+        H = b; b += nq * nq;
+        M = b; b += nq * nq;
+        x0 = b; b += 8;
+        ref = b; b += 7 * Tp;
+        fr = b; b += 7 * Tp;
+        J = b; b += NJ * T;
+        SL = b; b += 7 * n;
+        U = b; b += nq; W = b; b += nq; Y = b; b += nq;
+        Wd = b; b += T; Wv = b; b += T; Wr = b; b += T; Sd = b; b += T; Sv = b; b += T;
+        pa = b; b += T; pd = b; b += T; pv = b; b += T;
+        A = b; b += n * Tp;                 // rows 2 q, 2 q + 1 (step q + 1): 2 (q + 1) doubles each from A[2 q (q + 1)]
+        WA = b; b += n + 1;
+        px = b; b += T; py = b; b += T; pw = b; b += T;
+        ob = b;
+    }
+};
+
+// the avoidance variant's arguments: obs [E][M][5] (nullable with M = 0), the f1p_kmpc_qp_avoid numbers, and its outputs (nullable)
+struct StQpAvoidArgs {
+    const double* obs;
+    int M;
+    double margin, rho, lin;
+    double *eps, *planes, *duals;
+};
+__device__ __forceinline__ StQpAvoidArgs stqp_avoid_args() { return StQpAvoidArgs{}; }
+__device__ __forceinline__ StQpAvoidArgs stqp_avoid_args(const StQpAvoidArgs& a) { return a; }
+
 // y = A_t x (the structure of :478-511)
 __device__ __forceinline__ void amul(const double* J, int T, int t, double DT, const double x[7], double y[7]) {
     const double* j = J + t;
@@ -70,17 +119,27 @@ __device__ __forceinline__ void amul(const double* J, int T, int t, double DT, c
 
 }  // namespace
 
+// AvArgs: none (the plain QP), or one StQpAvoidArgs (AV)
+template <class... AvArgs>
 __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g, const double* __restrict__ refg, const double* pa_g,
                                                  const double* pd_g, int pstride, int E, f1p_stmpc_cfg cfg, int max_iter, double tol,
                                                  double* __restrict__ steer, double* __restrict__ speed, int32_t* __restrict__ status,
                                                  double* __restrict__ u_out, double* __restrict__ x_out, double* __restrict__ obj_out,
-                                                 double* __restrict__ duals, int32_t* __restrict__ iters_out, double* warm_out) {
+                                                 double* __restrict__ duals, int32_t* __restrict__ iters_out, double* warm_out,
+                                                 AvArgs... av_args) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
+    constexpr bool AV = sizeof...(AvArgs) == 1;
+    [[maybe_unused]] const StQpAvoidArgs av = stqp_avoid_args(av_args...);
+    constexpr int R = AV ? 12 : 10;                      // inequality rows per lane
+    // AV: the solver's slack is e' = eps / sig, sig = 1 / sqrt(2 rho): its curvature is 1 like the inputs' (2 rho = 2e4 beside weights of
+    // 0.01 leaves the dual residual a floor at the stopping rule's 1e-10).  The rows, hence the multipliers, are the unscaled problem's.
+    [[maybe_unused]] const double sig = AV ? 1.0 / sqrt(2.0 * av.rho) : 1.0;
     const int T = cfg.horizon, n = 2 * T, Tp = T + 1;
+    const int nq = AV ? n + 2 : n;                       // the QP's inputs: u, and (eps, padding) with AV
     const int tau = threadIdx.x, i0 = 2 * tau, i1 = 2 * tau + 1;
     const int e = blockIdx.x;
     if (e >= E) return;                                  // (one ego per workgroup: uniform)
-    StQpLds L(reinterpret_cast<double*>(lds_raw), T);
+    std::conditional_t<AV, StQpLdsAv, StQpLds> L(reinterpret_cast<double*>(lds_raw), T);
     const bool in_n = tau < T;
     const double DT = cfg.dt;
     const double NaN = __builtin_nan("");
@@ -93,6 +152,15 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
         const double a = pa_g ? pa_g[((size_t)e * T + k) * pstride] : 0.0;
         const double d = pd_g ? pd_g[((size_t)e * T + k) * pstride] : 0.0;
         L.pa[k] = a; L.pd[k] = d; bad |= !(isfinite(a) && isfinite(d));
+    }
+    if constexpr (AV) {
+        for (int m = tau; m < av.M; m += 64) {               // a live slot (r >= 0) must be finite; an empty one is kept as r = -1
+            const double* o = av.obs + ((size_t)e * av.M + m) * 5;
+            const double ox = o[0], oy = o[1], ovx = o[2], ovy = o[3], r = o[4];
+            const bool live = r >= 0.0;
+            L.ob[5 * m] = ox; L.ob[5 * m + 1] = oy; L.ob[5 * m + 2] = ovx; L.ob[5 * m + 3] = ovy; L.ob[5 * m + 4] = live ? r : -1.0;
+            bad |= live && !(isfinite(ox) && isfinite(oy) && isfinite(ovx) && isfinite(ovy) && isfinite(r));
+        }
     }
     bad = gmax<64>(bad ? 1.0 : 0.0) > 0.0;
     __syncthreads();
@@ -108,6 +176,7 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
         for (int t = 0; t < T; ++t) {                    // path_predict[2..6, t] -> pd / pv and J scratch (rows JC*, overwritten below)
             L.J[JC0 * T + t] = s.delta; L.J[JC1 * T + t] = s.v; L.J[JC5 * T + t] = s.yaw; L.J[JC6 * T + t] = s.yr; L.pv[t] = s.beta;
             dyn_step<false>(s, L.pa[t], L.pd[t], cfg, kc);
+            if constexpr (AV) { L.px[t] = s.x; L.py[t] = s.y; L.pw[t] = s.yaw + s.beta; }      // pbar_{t+1} and its direction of travel
         }
     }
     __syncthreads();
@@ -170,10 +239,55 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
     if (!done && nf) { st = 3; done = true; }            // non-finite model data (a predicted speed of 0)
     __syncthreads();
 
+    // AV: this lane's two half-planes (step tau + 1: the nearest and the second nearest live disc)
+    [[maybe_unused]] double pl_nx[2] = {0.0, 0.0}, pl_ny[2] = {0.0, 0.0}, pl_h[2] = {0.0, 0.0};
+    [[maybe_unused]] int pl_slot[2] = {-1, -1};
+    [[maybe_unused]] const int a_off = 2 * tau * (tau + 1), a_len = 2 * (tau + 1);     // this lane's packed rows: A[a_off + j a_len + c]
+    if constexpr (AV) {
+        if (in_n && !done) {
+            const int t = tau + 1;
+            const double tt = (double)t * DT, px = L.px[tau], py = L.py[tau];
+            double c0 = INFINITY, c1 = INFINITY;
+            int m0 = -1, m1 = -1;
+            for (int m = 0; m < av.M; ++m) {               // the two least clearances, ties to the lower slot
+                const double r = L.ob[5 * m + 4];
+                if (!(r >= 0.0)) continue;
+                const double dx = px - (L.ob[5 * m] + L.ob[5 * m + 2] * tt), dy = py - (L.ob[5 * m + 1] + L.ob[5 * m + 3] * tt);
+                const double clear = sqrt(dx * dx + dy * dy) - r;
+                if (clear < c0) { c1 = c0; m1 = m0; c0 = clear; m0 = m; }
+                else if (clear < c1) { c1 = clear; m1 = m; }
+            }
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj) {
+                const int ms = jj == 0 ? m0 : m1;
+                if (ms < 0) continue;
+                const double r = L.ob[5 * ms + 4];
+                const double cx = L.ob[5 * ms] + L.ob[5 * ms + 2] * tt, cy = L.ob[5 * ms + 1] + L.ob[5 * ms + 3] * tt;
+                const double dx = px - cx, dy = py - cy, dist = sqrt(dx * dx + dy * dy);
+                if (dist < 1e-9) {                           // on the disc's centre: stay behind it
+                    double sn, cs;
+                    sincos(L.pw[tau], &sn, &cs);
+                    pl_nx[jj] = -cs; pl_ny[jj] = -sn;
+                } else {
+                    pl_nx[jj] = dx / dist; pl_ny[jj] = dy / dist;
+                }
+                pl_h[jj] = pl_nx[jj] * (L.fr[t] - cx) + pl_ny[jj] * (L.fr[Tp + t] - cy) - (r + av.margin);
+                pl_slot[jj] = ms;
+            }
+        }
+    }
+
     // ---- 2. condensing: H and g, one slab per step -----------------------------------------------------------------------------------
     double g0 = 0.0, g1 = 0.0;
     if (!done) {
-        if (in_n) for (int c = 0; c < n; ++c) { L.H[i0 * n + c] = 0.0; L.H[i1 * n + c] = 0.0; }
+        if (in_n) for (int c = 0; c < nq; ++c) { L.H[i0 * nq + c] = 0.0; L.H[i1 * nq + c] = 0.0; }
+        if constexpr (AV) {
+            if (tau == T) {                              // eps and the padding input
+                for (int c = 0; c < nq; ++c) { L.H[i0 * nq + c] = 0.0; L.H[i1 * nq + c] = 0.0; }
+                L.H[i0 * nq + i0] = 1.0; L.H[i1 * nq + i1] = 1.0;         // 2 rho sig^2
+                g0 = av.lin * sig;
+            }
+        }
         double dv[7] = {0, 0, 0, 0, 0, 0, 0}, ev[7] = {0, 0, 0, 0, 0, 0, 0};
         for (int t = 1; t < Tp; ++t) {
             if (in_n) {
@@ -204,33 +318,48 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
                         h0 += s * dv[k];
                         h1 += s * ev[k];
                     }
-                    L.H[i0 * n + c] += h0;
-                    L.H[i1 * n + c] += h1;
+                    L.H[i0 * nq + c] += h0;
+                    L.H[i1 * nq + c] += h1;
+                }
+                if constexpr (AV) {
+                    if (t == tau + 1) {                  // this lane's rows, from the slab of its step (c < 2 t = a_len)
+#pragma unroll
+                        for (int jj = 0; jj < 2; ++jj)
+                            for (int c = 0; c < a_len; ++c)
+                                L.A[a_off + jj * a_len + c] = pl_slot[jj] >= 0 ? -(pl_nx[jj] * L.SL[c] + pl_ny[jj] * L.SL[n + c]) : 0.0;
+                    }
                 }
             }
             __syncthreads();
         }
         if (in_n) {                                      // R and Rd (:616, :622)
             const int nb = (tau > 0) + (tau < T - 1);
-            L.H[i0 * n + i0] += 2.0 * (cfg.r[0] + nb * cfg.rd[0]);
-            L.H[i1 * n + i1] += 2.0 * (cfg.r[1] + nb * cfg.rd[1]);
-            if (tau > 0) { L.H[i0 * n + i0 - 2] -= 2.0 * cfg.rd[0]; L.H[i1 * n + i1 - 2] -= 2.0 * cfg.rd[1]; }
-            if (tau < T - 1) { L.H[i0 * n + i0 + 2] -= 2.0 * cfg.rd[0]; L.H[i1 * n + i1 + 2] -= 2.0 * cfg.rd[1]; }
+            L.H[i0 * nq + i0] += 2.0 * (cfg.r[0] + nb * cfg.rd[0]);
+            L.H[i1 * nq + i1] += 2.0 * (cfg.r[1] + nb * cfg.rd[1]);
+            if (tau > 0) { L.H[i0 * nq + i0 - 2] -= 2.0 * cfg.rd[0]; L.H[i1 * nq + i1 - 2] -= 2.0 * cfg.rd[1]; }
+            if (tau < T - 1) { L.H[i0 * nq + i0 + 2] -= 2.0 * cfg.rd[0]; L.H[i1 * nq + i1 + 2] -= 2.0 * cfg.rd[1]; }
         }
     }
     __syncthreads();
 
     // ---- 3. interior point (qp_ipm.h) ----------------------------------------------------------------------------------------------------
     const double MSV = cfg.max_steer_v;
-    double h[10];
-    bool valid[10];
+    double h[R];
+    bool valid[R];
     h[0] = MSV; h[1] = MSV; h[2] = cfg.max_accel; h[3] = cfg.max_accel;
     h[4] = cfg.max_steer - d0; h[5] = cfg.max_steer + d0; h[6] = cfg.max_speed - v0; h[7] = v0 - cfg.min_speed; h[8] = MSV; h[9] = MSV;
 #pragma unroll
     for (int r = 0; r < 10; ++r) valid[r] = in_n && (r < 8 || tau < T - 1);
+    double m_rows = 10.0 * T - 2.0;
+    if constexpr (AV) {                                  // rows 10, 11: the half-planes; lane T: -eps <= 0
+        h[10] = pl_h[0]; h[11] = pl_h[1];
+        valid[10] = in_n ? pl_slot[0] >= 0 : tau == T;
+        valid[11] = in_n && pl_slot[1] >= 0;
+        m_rows += 1.0 + gsum<64>((double)((in_n && pl_slot[0] >= 0) + (in_n && pl_slot[1] >= 0)));
+    }
 
     // G x for this lane's rows (x published in vec[])
-    auto gmul = [&](const double* vec, const double (&x)[2], double (&out)[10]) {
+    auto gmul = [&](const double* vec, const double (&x)[2], double (&out)[R]) {
         double p0 = 0.0, p1 = 0.0;
         if (in_n) for (int q = 0; q <= tau; ++q) { p0 += vec[2 * q]; p1 += vec[2 * q + 1]; }
         const double r = in_n && tau < T - 1 ? vec[i0 + 2] - x[0] : 0.0;
@@ -238,12 +367,40 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
         out[4] = DT * p0; out[5] = -(DT * p0); out[6] = DT * p1; out[7] = -(DT * p1); out[8] = r; out[9] = -r;
 #pragma unroll
         for (int k = 0; k < 10; ++k) out[k] = valid[k] ? out[k] : 0.0;
+        if constexpr (AV) {                              // A_r . u - eps; lane T: -eps
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj) {
+                double o = 0.0;
+                if (valid[10 + jj]) {
+                    if (in_n) for (int c = 0; c < a_len; ++c) o += L.A[a_off + jj * a_len + c] * vec[c];
+                    o -= sig * vec[n];
+                }
+                out[10 + jj] = o;
+            }
+        }
+    };
+    // AV: (sum_r w_r A_r) at columns i0 and i1 over the rows of steps > tau, w published in WA[]
+    [[maybe_unused]] auto a_cols = [&](double& o0, double& o1) {
+        o0 = o1 = 0.0;
+        if constexpr (AV) {
+            for (int q = tau; q < T; ++q) {
+                const int len = 2 * (q + 1);
+                const double* a = L.A + 2 * q * (q + 1);
+                const double w0 = L.WA[2 * q], w1 = L.WA[2 * q + 1];
+                o0 += w0 * a[i0] + w1 * a[len + i0];
+                o1 += w0 * a[i1] + w1 * a[len + i1];
+            }
+        }
     };
     // (G' w) at u0_tau, u1_tau: the rows' differences published in Wd[], Wv[], Wr[]
-    auto gtmul = [&](const double (&w)[10], double (&o)[2]) {
+    auto gtmul = [&](const double (&w)[R], double (&o)[2]) {
         const double wd = valid[4] ? w[4] - w[5] : 0.0, wv = valid[6] ? w[6] - w[7] : 0.0, wr = valid[8] ? w[8] - w[9] : 0.0;
         __syncthreads();
         if (in_n) { L.Wd[tau] = wd; L.Wv[tau] = wv; L.Wr[tau] = wr; }
+        if constexpr (AV) {
+            if (in_n) { L.WA[i0] = valid[10] ? w[10] : 0.0; L.WA[i1] = valid[11] ? w[11] : 0.0; }
+            else if (tau == T) L.WA[n] = w[10];
+        }
         __syncthreads();
         o[0] = o[1] = 0.0;
         if (in_n) {
@@ -252,11 +409,28 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
             o[0] = (valid[0] ? w[0] - w[1] : 0.0) + DT * sd - wr + (tau > 0 ? L.Wr[tau - 1] : 0.0);
             o[1] = (valid[2] ? w[2] - w[3] : 0.0) + DT * sv;
         }
+        if constexpr (AV) {
+            if (in_n) {
+                double a0, a1;
+                a_cols(a0, a1);
+                o[0] += a0; o[1] += a1;
+            } else if (tau == T) {                       // eps: minus every row's w
+                double a = 0.0;
+                for (int r = 0; r <= n; ++r) a += L.WA[r];
+                o[0] = -(sig * a);
+            }
+        }
     };
     // rows i0 and i1 of M = H + G' diag(D) G, lower triangle
-    auto newton_rows = [&](const double (&D)[10]) {
+    // AV: + sum_r D_r A_r A_r' on the u block; the scaled slack's row: -sig sum_r D_r A_r (each lane its own two columns),
+    // 1 + sig^2 (sum_r D_r + D_eps) on the diagonal; the padding input's row: its unit diagonal
+    auto newton_rows = [&](const double (&D)[R]) {
         __syncthreads();
         if (in_n) { L.Wd[tau] = D[4] + D[5]; L.Wv[tau] = D[6] + D[7]; L.Wr[tau] = D[8] + D[9]; }
+        if constexpr (AV) {
+            if (in_n) { L.WA[i0] = D[10]; L.WA[i1] = D[11]; }
+            else if (tau == T) L.WA[n] = D[10];
+        }
         __syncthreads();
         if (in_n) {
             double sd = 0.0, sv = 0.0;
@@ -268,23 +442,45 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
             const double wr = L.Wr[tau], wrm = tau > 0 ? L.Wr[tau - 1] : 0.0;
             for (int c = 0; c <= i1; ++c) {
                 const int q = c >> 1, m_ = max(tau, q);
-                double m0 = L.H[i0 * n + c], m1 = L.H[i1 * n + c];
+                double m0 = L.H[i0 * nq + c], m1 = L.H[i1 * nq + c];
                 if ((c & 1) == 0) m0 += DT * DT * L.Sd[m_];
                 else m1 += DT * DT * L.Sv[m_];
                 if (c == i0) m0 += D[0] + D[1] + wr + wrm;
                 if (c == i0 - 2) m0 -= wrm;
                 if (c == i1) m1 += D[2] + D[3];
-                if (c <= i0) L.M[i0 * n + c] = m0;
-                L.M[i1 * n + c] = m1;
+                if constexpr (AV) {
+                    for (int q = tau; q < T; ++q) {
+                        const int len = 2 * (q + 1);
+                        const double* a = L.A + 2 * q * (q + 1);
+                        const double w0 = L.WA[2 * q] * a[c], w1 = L.WA[2 * q + 1] * a[len + c];
+                        m0 += w0 * a[i0] + w1 * a[len + i0];
+                        m1 += w0 * a[i1] + w1 * a[len + i1];
+                    }
+                }
+                if (c <= i0) L.M[i0 * nq + c] = m0;
+                L.M[i1 * nq + c] = m1;
+            }
+        }
+        if constexpr (AV) {
+            if (in_n) {
+                double a0, a1;
+                a_cols(a0, a1);
+                L.M[n * nq + i0] = -(sig * a0); L.M[n * nq + i1] = -(sig * a1);
+            } else if (tau == T) {
+                double sd = 0.0;
+                for (int r = 0; r <= n; ++r) sd += L.WA[r];
+                L.M[n * nq + n] = 1.0 + sig * sig * sd;
+                for (int c = 0; c <= n; ++c) L.M[(n + 1) * nq + c] = 0.0;
+                L.M[(n + 1) * nq + n + 1] = 1.0;
             }
         }
     };
 
     const double gv[2] = {g0, g1};
-    double u[2], lam[10];
+    double u[2], lam[R];
     int it_done;
-    qp_ipm<64, 2, 10>(QpIpmLds{L.H, L.M, L.U, L.Y}, n, tau, gv, h, valid, 10.0 * T - 2.0, max_iter, tol, done, st, it_done, u, lam, gmul,
-                      gtmul, newton_rows);
+    qp_ipm<64, 2, R>(QpIpmLds{L.H, L.M, L.U, L.Y}, nq, tau, gv, h, valid, m_rows, max_iter, tol, done, st, it_done, u, lam, gmul,
+                     gtmul, newton_rows);
 
     // ---- outputs --------------------------------------------------------------------------------------------------------------------
     const bool ok = st == 0 || st == 2;
@@ -302,6 +498,22 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
                 const int blk = r < 4 ? 4 + r : r - 4;   // rows 4..7 (delta, v) come before rows 0..3 (the boxes)
                 du_[R2 + blk * T + tau] = ok ? lam[r] : NaN;
             }
+        }
+        if constexpr (AV) {
+            if (av.planes) {
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj) {
+                    double* p = av.planes + ((size_t)e * n + i0 + jj) * 4;
+                    p[0] = ok ? pl_nx[jj] : NaN; p[1] = ok ? pl_ny[jj] : NaN; p[2] = ok ? pl_h[jj] : NaN; p[3] = ok ? (double)pl_slot[jj] : NaN;
+                }
+            }
+            if (av.duals) { av.duals[(size_t)e * (n + 1) + i0] = ok ? lam[10] : NaN; av.duals[(size_t)e * (n + 1) + i1] = ok ? lam[11] : NaN; }
+        }
+    }
+    if constexpr (AV) {
+        if (tau == T) {
+            if (av.duals) av.duals[(size_t)e * (n + 1) + n] = ok ? lam[10] : NaN;
+            if (av.eps) av.eps[e] = ok ? sig * u[0] : NaN;
         }
     }
     if (tau == 0) {
@@ -335,6 +547,7 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
                 y[6] += L.J[JB61 * T + t] * a1 + L.J[JC6 * T + t];
                 for (int k = 0; k < 7; ++k) x[k] = y[k];
             }
+            if constexpr (AV) { const double eps = sig * L.U[n]; f += av.rho * eps * eps + av.lin * eps; }
             if (obj_out) obj_out[e] = ok ? f : NaN;
         }
     }
@@ -367,18 +580,54 @@ __global__ __launch_bounds__(256) void k_stmpc_qp_kref(const double* __restrict_
     ref4[j] = ref7[((size_t)k * 7 + row) * Tp + t];
 }
 
+// gather an ego subset's discs [idx[k]][M][5] into [k][M][5]
+__global__ __launch_bounds__(256) void k_stmpc_qp_obs_in(const double* __restrict__ obs, const int32_t* __restrict__ idx, int nb, int M5,
+                                                         double* __restrict__ out) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nb * M5) return;
+    const int k = j / M5, r = j % M5;
+    out[j] = obs[(size_t)idx[k] * M5 + r];
+}
+
 size_t stmpc_qp_lds_bytes(int T) { return sizeof(double) * (size_t)stqp_lds_doubles(T); }
+size_t stmpc_qp_avoid_lds_bytes(int T) { return sizeof(double) * (size_t)stqp_lds_doubles_av(T); }
 
 int launch_stmpc_qp(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
                     const f1p_stmpc_cfg* cfg, int max_iter, double tol, double* d_steer, double* d_speed, int32_t* d_status, double* d_u,
                     double* d_x, double* d_obj, double* d_duals, int32_t* d_iters, double* d_warm_out) {
     if (E <= 0) return F1P_OK;
     const size_t lds = stmpc_qp_lds_bytes(cfg->horizon);
-    const int rc = qp_lds_opt_in(ctx, reinterpret_cast<const void*>(&k_stmpc_qp), lds, "stmpc qp: horizon too long for the CU's LDS");
+    const int rc = qp_lds_opt_in(ctx, reinterpret_cast<const void*>(&k_stmpc_qp<>), lds, "stmpc qp: horizon too long for the CU's LDS");
     if (rc) return rc;
-    hipLaunchKernelGGL(k_stmpc_qp, dim3((unsigned)E), dim3(64), lds, ctx->stream, d_x0, d_ref, d_pa, d_pd, pstride, E, *cfg, max_iter, tol,
+    hipLaunchKernelGGL(k_stmpc_qp<>, dim3((unsigned)E), dim3(64), lds, ctx->stream, d_x0, d_ref, d_pa, d_pd, pstride, E, *cfg, max_iter, tol,
                        d_steer, d_speed, d_status, d_u, d_x, d_obj, d_duals, d_iters, d_warm_out);
     return check_hip(ctx, hipGetLastError(), "k_stmpc_qp launch");
+}
+
+// the avoidance variant: one wave per ego as the plain kernel, lane T takes the slack
+int launch_stmpc_qp_avoid(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
+                          const f1p_stmpc_cfg* cfg, int max_iter, double tol, const double* d_obs, int M, const f1p_kmpc_qp_avoid* avoid,
+                          double* d_steer, double* d_speed, int32_t* d_status, double* d_u, double* d_x, double* d_obj, double* d_duals,
+                          int32_t* d_iters, double* d_warm_out, double* d_eps, double* d_planes, double* d_avoid_duals) {
+    if (E <= 0) return F1P_OK;
+    const int T = cfg->horizon;
+    if (T > F1P_STMPC_QP_AVOID_MAX_T || M < 0 || M > F1P_KMPC_MAX_OBS || (M > 0 && !d_obs))
+        return set_error(ctx, F1P_EINVAL, "stmpc qp avoid: bad horizon / obstacles");
+    const size_t lds = stmpc_qp_avoid_lds_bytes(T);
+    const auto kern = &k_stmpc_qp<StQpAvoidArgs>;
+    const int rc = qp_lds_opt_in(ctx, reinterpret_cast<const void*>(kern), lds, "stmpc qp avoid: horizon too long for the CU's LDS");
+    if (rc) return rc;
+    const StQpAvoidArgs av{d_obs, M, avoid->margin, avoid->rho, avoid->lin, d_eps, d_planes, d_avoid_duals};
+    hipLaunchKernelGGL(kern, dim3((unsigned)E), dim3(64), lds, ctx->stream, d_x0, d_ref, d_pa, d_pd, pstride, E, *cfg, max_iter, tol, d_steer,
+                       d_speed, d_status, d_u, d_x, d_obj, d_duals, d_iters, d_warm_out, av);
+    return check_hip(ctx, hipGetLastError(), "k_stmpc_qp_avoid launch");
+}
+
+int launch_stmpc_qp_obs_in(f1p_ctx* ctx, const double* d_obs, const int32_t* d_idx, int nb, int M, double* d_out) {
+    if (nb <= 0 || M <= 0) return F1P_OK;
+    const int n = nb * M * 5;
+    hipLaunchKernelGGL(k_stmpc_qp_obs_in, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_obs, d_idx, nb, M * 5, d_out);
+    return check_hip(ctx, hipGetLastError(), "k_stmpc_qp_obs_in launch");
 }
 
 int launch_stmpc_qp_warm_in(f1p_ctx* ctx, const double* d_warm, const int32_t* d_idx, const int32_t* d_use, int nb, int Tb, int W, double* d_out) {

@@ -67,6 +67,41 @@ def kmpc_qp_set_avoid(ctx, avoid):
     ctx._check(ctx.lib.f1p_kmpc_qp_set_avoid(ctx.h, _ref(avoid)))
 
 
+def stmpc_qp_avoid(ctx, x0, ref, obs, cfg, avoid=None, oa_prev=None, od_v_prev=None, opts=None, want_u=True, want_x=False, want_obj=True,
+                   want_duals=False, want_iters=True, want_eps=True, want_planes=False, want_avoid_duals=False):
+    """Context.stmpc_qp with moving-disc avoidance rows (f1p_stmpc_qp_avoid_batch) on Context `ctx`: obs [E, M, 5] fp64 rows
+    (x, y, vx, vy, r), M in 1..16, r < 0 or NaN = an empty slot; avoid: _abi.kmpc_qp_avoid(margin, rho, lin) (None: the defaults); horizon
+    <= _abi.STMPC_QP_AVOID_MAX_T.  A soft, linearised avoidance term, not a guarantee.  -> stmpc_qp's dict[, eps [E], planes [E, T, 2, 4] =
+    (n_x, n_y, right-hand side, slot; -1 and zeros: absent), avoid_duals [E, 2T+1]: the 2T avoidance rows in step order, then -eps <= 0];
+    obj includes the slack's cost.  (A module function: Context's public methods are a pinned record, tests/test_runtime_calls.py.)"""
+    x0 = _f64(x0, (-1, 7)); E = x0.shape[0]; T = cfg.horizon
+    ref = _f64(ref, (E, 7, T + 1))
+    o = _f64(obs)
+    if o.ndim != 3 or o.shape[0] != E or o.shape[2] != 5:
+        raise ValueError(f"obstacles must be [E={E}, M, 5] = (x, y, vx, vy, r)")
+    oa = None if oa_prev is None else _f64(oa_prev, (E, T))
+    od = None if od_v_prev is None else _f64(od_v_prev, (E, T))
+    out = dict(steer=np.empty(E), speed=np.empty(E), status=np.empty(E, np.int32))
+    for k, want, shape, dt in (("u", want_u, (E, T, 2), np.float64), ("x", want_x, (E, 7, T + 1), np.float64), ("obj", want_obj, (E,), np.float64),
+                               ("duals", want_duals, (E, 10 * T - 2), np.float64), ("iters", want_iters, (E,), np.int32),
+                               ("eps", want_eps, (E,), np.float64), ("planes", want_planes, (E, T, 2, 4), np.float64),
+                               ("avoid_duals", want_avoid_duals, (E, 2 * T + 1), np.float64)):
+        if want:
+            out[k] = np.empty(shape, dt)
+    ctx._check(ctx.lib.f1p_stmpc_qp_avoid_batch(ctx.h, _ptr(x0), _ptr(ref), _ptr(oa), _ptr(od), E, C.byref(cfg), _ref(opts), _ptr(o), o.shape[1],
+                                                _ref(avoid), _ptr(out["steer"]), _ptr(out["speed"]), _ptr(out["status"]), _ptr(out.get("u")),
+                                                _ptr(out.get("x")), _ptr(out.get("obj")), _ptr(out.get("duals")), _ptr(out.get("iters")),
+                                                _ptr(out.get("eps")), _ptr(out.get("planes")), _ptr(out.get("avoid_duals"))))
+    return out
+
+
+def stmpc_qp_set_avoid(ctx, avoid):
+    """f1p_stmpc_qp_set_avoid on Context `ctx`, a switch of its own beside kmpc_qp_set_avoid: while on, stmpc_qp_plan, stmpc_qp_plan_tracks
+    and stmpc_qp_dev take the discs of stmpc_set_obstacles[_dev] (the caller's ego order) as soft half-plane rows of both branches' QPs;
+    avoid: _abi.kmpc_qp_avoid(...), None (or on=False) turns it off"""
+    ctx._check(ctx.lib.f1p_stmpc_qp_set_avoid(ctx.h, _ref(avoid)))
+
+
 class _Mpc:
     # ---- MPC: the kinematic (kmpc_*, state width 4) and the dynamic (stmpc_*, 7) wrappers share their bodies -----------------------
     def kmpc_ref(self, states, horizon, dt=0.1, dl=0.03):

@@ -836,6 +836,46 @@ int f1p_stmpc_qp_plan_tracks_batch(f1p_ctx* ctx, const double* x0, const int32_t
                                    const f1p_kmpc_cfg* kcfg, double v_ks, double dl, double dlk, const f1p_kmpc_qp_opts* opts,
                                    double* steer, double* speed, int32_t* status, int32_t* branch, double* u, double* obj);
 
+/* Moving-disc avoidance in the dynamic QP: f1p_stmpc_set_obstacles' discs as SOFT, LINEARISED half-plane rows, the
+ * dynamic twin of f1p_kmpc_qp_avoid_* with the same struct and defaults (f1p_kmpc_qp_avoid, f1p_kmpc_qp_avoid_default).  An avoidance
+ * term, not a guarantee.  The problem of f1p_stmpc_qp_* is kept -- u = (steer_v_0, accel_0, ...), the linearisation about
+ * predict_motion(x0, oa_prev, od_v_prev), the same 10T-2 rows -- and gains
+ *   one slack eps: cost rho eps^2 + lin eps, uncoupled from u in H, row -eps <= 0;
+ *   at most two rows per step t = 1..T.  pbar_t: the position of the linearisation path after t steps (update_state with its clamps,
+ *     t = T included).  A live slot (r >= 0) is predicted at tau = (double)t * DT: c = (x + vx tau, y + vy tau), d = pbar_t - c,
+ *     dist = sqrt(dx^2 + dy^2), clear = dist - r.  The two live slots with the smallest clear are taken, ties to the lower slot; each
+ *     gives the normal n = d / dist (dist < 1e-9: n = -(cos, sin)(psibar_t + betabar_t), the direction of travel: stay behind it) and,
+ *     with x_t = S(t) u + s(t) the linear model's state (rows 0 and 1: x and y), the row
+ *       -n.(S_xy(t) u) - eps <= n.(s_xy(t) - c) - (r + margin).
+ * An empty slot is r < 0 or r NaN; an ego without a live slot has no such row and the optimum of f1p_stmpc_qp_* (eps = 0).  A live slot
+ * with a non-finite number: status 3.  Status 1 as for f1p_stmpc_qp_* (|delta0| > MAX_STEER or v0 outside its bounds).
+ * 2 <= horizon <= F1P_STMPC_QP_AVOID_MAX_T (the longest horizon whose LDS layout, the packed avoidance rows included, one workgroup may
+ * claim; else F1P_EINVAL).  The warm start stays (oa, odelta_v); eps is not carried.  obj includes rho eps^2 + lin eps.
+ * f1p_stmpc_qp_avoid_batch / _dev: f1p_stmpc_qp_batch / _dev with obs [E][M][5] (M in 1..16) and avoid (NULL: the defaults; `on` is not
+ *   read), and the nullable outputs eps [E]; planes [E][T][2][4] = (n_x, n_y, right-hand side, slot as a double; slot -1 and zeros for an
+ *   absent row); avoid_duals [E][2T+1]: the multipliers of the 2T avoidance rows in step order (0 for an absent row), then of -eps <= 0.
+ *   duals [E][10T-2] keeps its layout.  Statuses 1 and 3: NaN in all of them.
+ * f1p_stmpc_qp_set_avoid: a switch of its own beside f1p_kmpc_qp_set_avoid; NULL or on = 0 turns it off (the default).  While on,
+ *   f1p_stmpc_qp_dev, f1p_stmpc_qp_plan_batch and f1p_stmpc_qp_plan_tracks_batch solve this problem with the discs held by
+ *   f1p_stmpc_set_obstacles[_dev] (none held: no avoidance rows), which are in the CALLER'S ego order: each branch of a plan gets its
+ *   egos' rows gathered on the device.  The plan's kinematic branch solves f1p_kmpc_qp_avoid_*'s problem on kcfg with the same discs and
+ *   numbers, whatever f1p_kmpc_qp_set_avoid says: kcfg->horizon <= 31.  A plan whose E is not the E the obstacles were set for:
+ *   F1P_ESTATE; a horizon past either cap: F1P_EINVAL.  rho > 0, lin >= 0 and a finite margin are required, otherwise F1P_EINVAL and
+ *   nothing changes.  Off: every entry point is what it is without this call. */
+#define F1P_STMPC_QP_AVOID_MAX_T 40
+int f1p_stmpc_qp_avoid_batch(f1p_ctx* ctx, const double* x0, const double* ref, const double* oa_prev, const double* od_v_prev, int32_t E,
+                             const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* obs, int32_t M,
+                             const f1p_kmpc_qp_avoid* avoid, double* steer, double* speed, int32_t* status, double* u, double* x,
+                             double* obj, double* duals, int32_t* iters, double* eps, double* planes, double* avoid_duals);
+int f1p_stmpc_qp_avoid_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_v_prev,
+                           int32_t E, const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* d_obs, int32_t M,
+                           const f1p_kmpc_qp_avoid* avoid, double* d_steer, double* d_speed, int32_t* d_status, double* d_u, double* d_x,
+                           double* d_obj, double* d_duals, int32_t* d_iters, double* d_eps, double* d_planes, double* d_avoid_duals);
+int f1p_stmpc_qp_set_avoid(f1p_ctx* ctx, const f1p_kmpc_qp_avoid* avoid);
+/* bytes of LDS one ego's workgroup of the avoidance variant claims at this horizon (F1P_STMPC_QP_AVOID_MAX_T is the longest that fits the
+ * CU; above 64 KiB the kernel is opted in to the larger allocation, a launch path of its own); -1: horizon < 2.  Needs no context. */
+int64_t f1p_stmpc_qp_avoid_lds_bytes(int32_t horizon);
+
 /* ------------------------------------------------------------------------------------------------
  * SURVEY.md 8f rank 2 -- the dynamic single-track model as a second model for shooting MPC
  * (control/dynamic_mpc/dynamic_mpc.py): predict_motion / update_state (:280-404), calc_ref_trajectory (:195-233),
@@ -877,7 +917,7 @@ int f1p_stmpc_set_mode(f1p_ctx* ctx, int32_t mixed, float* d_cost32, int32_t* d_
  * nothing and leave the warm-start tags alone when no grid is loaded (F1P_ESTATE), when an oriented footprint is installed
  * (f1p_set_footprint with n_discs > 0; F1P_ESTATE) or, f1p_stmpc_plan_batch only, when f1p_kmpc_set_groups(> 0) is in force
  * (F1P_ESTATE).  A count outside [1, 16]: F1P_EINVAL, the switch keeps its state.
- * Not covered: f1p_stmpc_qp_*. */
+ * Not covered: f1p_stmpc_qp_* (the QP has no rollouts to test; the grid is not among its constraints). */
 int f1p_stmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub, int32_t n_sub_k);
 /* Moving obstacles on the rollouts of the dynamic MPC's shooting solver: f1p_kmpc_set_obstacles' discs and rule
  * for f1p_stmpc_*.  obs [E][M][5] fp64 rows (x, y, vx, vy, r) in the map frame, M <= F1P_KMPC_MAX_OBS, INDEXED BY THE CALLER'S EGO
@@ -896,7 +936,9 @@ int f1p_stmpc_set_collision(f1p_ctx* ctx, int32_t on, int32_t n_sub, int32_t n_s
  * evaluated in plain fp64 whatever the mode and equal f1p_stmpc_plan_dev bit for bit.
  * Errors, nothing launched and no warm tag touched: M outside [1, 16]: F1P_EINVAL; a plan whose E is not the obstacles' E (for
  * plan_batch the caller's E): F1P_ESTATE; f1p_stmpc_plan_batch under f1p_kmpc_set_groups(> 0) with obstacles set: F1P_ESTATE.
- * Not covered: f1p_stmpc_qp_*, a MultiContext's sharded plans, f1p_kmpc_*. */
+ * f1p_stmpc_qp_dev / f1p_stmpc_qp_plan_batch / f1p_stmpc_qp_plan_tracks_batch take the same discs as soft half-plane rows of the QP
+ * while f1p_stmpc_qp_set_avoid is on (above), and ignore them while it is off.
+ * Not covered: a MultiContext's sharded plans, f1p_kmpc_*. */
 int f1p_stmpc_set_obstacles(f1p_ctx* ctx, const double* obs, int32_t E, int32_t M);
 int f1p_stmpc_set_obstacles_dev(f1p_ctx* ctx, const double* d_obs, int32_t E, int32_t M);
 int f1p_stmpc_shoot_batch(f1p_ctx* ctx, const double* x0, const double* ref, const float* controls, int32_t E,

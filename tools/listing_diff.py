@@ -12,7 +12,7 @@ kernel descriptor (.amdhsa_*: registers, scratch, LDS) is compared with the inst
 
 --map FILE: lines `old_name new_name`, demangled, without namespace and arguments, e.g.
     k_kmpc_plan_gen_idx k_kmpc_plan_gen_t<KmpcIdxArgs>
-A kernel not in the map is looked up under its own name.  Exit status 1 when a kernel differs or is missing.  CPU only.
+A kernel not in the map is looked up under its own name, then as `name<>` (it became a template whose plain instantiation takes no arguments).  Exit status 1 when a kernel differs or is missing.  CPU only.
 """
 import difflib
 import os
@@ -85,6 +85,8 @@ def main():
         print(f"{label}: {len(a)} kernels")
         for k in sorted(a):
             kb = names.get(k, k)
+            if kb not in b and kb + "<>" in b:                      # a kernel that became the empty instantiation of a variadic template
+                kb += "<>"
             if kb not in b:
                 print(f"  {k:<44} MISSING ({kb})")
                 bad += 1
