@@ -888,16 +888,38 @@ __device__ __forceinline__ bool candidate_goal_rec(const f1p_lattice_cfg& cfg, i
 // slot transform in fp64 (the ego's frame is in its record) and leaves the live slots for k_lattice_refine (LatObs::xf, n_live).
 // The instantiations without obstacles keep their signature and their code.
 template <int CR, bool DBG = false, bool HG = false, int GEN = F1P_GEN_CLOTHOID, bool FOOT = false, typename... OB>
-__global__ __launch_bounds__(256, F1P_MIX_FILTER_WAVES) void k_lattice_filter3(LatticeArgs a, f1p_lattice_cfg cfg, MixArgs mx, const unsigned char* __restrict__ recs, OB... obx) {
+__global__ __launch_bounds__(256, F1P_MIX_FILTER_WAVES) void k_lattice_filter3(const unsigned char* __restrict__ recs, const int32_t* __restrict__ h_perm, unsigned int h_rec_bytes, int h_perm_rs, int h_e0, int h_E,
+                                                                                  LatticeArgs a, f1p_lattice_cfg cfg, MixArgs mx, OB... obx) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     constexpr bool OBS = sizeof...(OB) > 0;
     constexpr int STM = OBS ? 0x3f : 0x7f;                        // the state proper (bit 7: can no longer turn out FREE by the first look; OBS, bit 6: nor by any look -- a disc may block it)
-    warm_kernargs<sizeof(LatticeArgs) + sizeof(f1p_lattice_cfg) + sizeof(MixArgs) + 8 + (sizeof(OB) + ... + 0)>();
+    // recs and h_* (MixArgs::perm / perm_rs, the record stride, LatticeArgs::e0 / E once more) are LEADING parameters: they arrive in SGPRs at wave launch
+    // (kernarg preload, lattice_device.h), so the workgroup's place in the dispatch order and the first 4 KB of its ego's record are requested before the
+    // argument segment has been read; where the record goes in LDS is known only after that
+#if F1P_MIX_F3_EGOS_PER_WG == 1
+    int ka[32];
+    warm_kernargs_touch<32 + sizeof(LatticeArgs) + sizeof(f1p_lattice_cfg) + sizeof(MixArgs) + (sizeof(OB) + ... + 0)>(ka);
+    int e = h_e0 + (int)blockIdx.x;                              // (no loop in the default build: under the 64-register cap its live ranges spill)
+    if (h_perm) e = h_perm[(blockIdx.x % F1P_MIX_OREG) * (unsigned)h_perm_rs + blockIdx.x / F1P_MIX_OREG] - 1;   // heavy egos first (MixArgs::perm); an empty slot: -1
+    if (e >= h_E || e < 0) return;
+    // (EARLY: the piece waits in four registers until the LDS layout is known.  The instantiations with hooks, host goals, the oriented footprint or moving discs
+    // have none to spare under the 64-register cap -- they spilled -- and request the record behind the wait, as before)
+    constexpr bool EARLY = !DBG && !HG && !FOOT && !OBS;
+    uint4 rec_head = make_uint4(0u, 0u, 0u, 0u);                 // 16-byte piece threadIdx.x of the record (the stride and the LDS block are 16-byte aligned)
+    if constexpr (EARLY) {
+        if (threadIdx.x < (h_rec_bytes >> 4)) rec_head = reinterpret_cast<const uint4*>(recs + (size_t)e * h_rec_bytes)[threadIdx.x];
+        warm_kernargs_wait(ka, rec_head.x);
+    } else {
+        warm_kernargs_wait(ka);
+    }
+#else
+    warm_kernargs<32 + sizeof(LatticeArgs) + sizeof(f1p_lattice_cfg) + sizeof(MixArgs) + (sizeof(OB) + ... + 0)>();
+#endif
     const int pitch = a.tile_words + 1;
     const unsigned tile_bytes = (unsigned)(a.tile_rows + 1) * (unsigned)pitch * 4u;
     uint32_t* tile = reinterpret_cast<uint32_t*>(lds_raw);       // (clearance word, bitmap word) pairs: (tile_rows + 1) x pitch, the last row / column the guard
     const int nl = cfg.n_lookahead;
-    const size_t rec_bytes = ego_rec_stride(nl);
+    const size_t rec_bytes = h_rec_bytes;                         // (= ego_rec_stride(nl), from the launcher)
     unsigned char* rec = lds_raw + (((size_t)tile_bytes * 2 + 15) & ~(size_t)15);
     EgoRecHdr* hdr = reinterpret_cast<EgoRecHdr*>(rec);
     double* cen = reinterpret_cast<double*>(rec + sizeof(EgoRecHdr));
@@ -925,15 +947,17 @@ __global__ __launch_bounds__(256, F1P_MIX_FILTER_WAVES) void k_lattice_filter3(L
     for (int e = a.e0 + blockIdx.x; e < a.E; e += gridDim.x) {
 #else
     {
-    int e = a.e0 + blockIdx.x;                                   // (no loop in the default build: under the 64-register cap its live ranges spill)
-    if (mx.perm) e = mx.perm[(blockIdx.x % F1P_MIX_OREG) * (unsigned)mx.perm_rs + blockIdx.x / F1P_MIX_OREG] - 1;   // heavy egos first (MixArgs::perm); an empty slot: -1
-    if (e >= a.E || e < 0) return;
 #endif
     // ---- the ego's record: one coalesced copy into LDS ----------------------------------------------------------------------------
     {
         const uint4* src = reinterpret_cast<const uint4*>(recs + (size_t)e * rec_bytes);   // (the stride and the LDS block are 16-byte aligned)
         uint4* dst = reinterpret_cast<uint4*>(rec);
+#if F1P_MIX_F3_EGOS_PER_WG == 1
+        if (EARLY && tid < (int)(rec_bytes >> 4)) dst[tid] = rec_head;   // (requested at the head of the kernel)
+        for (int q = tid + (EARLY ? (int)blockDim.x : 0); q < (int)(rec_bytes >> 4); q += blockDim.x) dst[q] = src[q];
+#else
         for (int q = tid; q < (int)(rec_bytes >> 4); q += blockDim.x) dst[q] = src[q];
+#endif
     }
     if (tid >= 128 && tid < 128 + F1P_MAX_WIDTHS) wtab[tid - 128] = tid - 128 < cfg.n_width ? cfg.width[tid - 128] : 0.0;
     if (tid == 0) cnt[0] = 0;
@@ -1410,29 +1434,30 @@ template <int CR>
 static void filter3_launch(bool hooks, bool host_goals, bool cubic, bool foot, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a,
                            const f1p_lattice_cfg& cfg, const MixArgs& mx, const unsigned char* recs, const LatObs* ob) {
     const dim3 g(grid), fb(F1P_MIX_FILTER_BLOCK);
+    const unsigned int rec_bytes = (unsigned int)ego_rec_stride(cfg.n_lookahead);
     if (ob) {                                                    // (the schedule sends only clothoids with the point footprint here while discs are set)
-        if (host_goals && hooks) hipLaunchKernelGGL((k_lattice_filter3<CR, true, true, F1P_GEN_CLOTHOID, false, LatObs>), g, fb, lds, st, a, cfg, mx, recs, *ob);
-        else if (host_goals) hipLaunchKernelGGL((k_lattice_filter3<CR, false, true, F1P_GEN_CLOTHOID, false, LatObs>), g, fb, lds, st, a, cfg, mx, recs, *ob);
-        else if (hooks) hipLaunchKernelGGL((k_lattice_filter3<CR, true, false, F1P_GEN_CLOTHOID, false, LatObs>), g, fb, lds, st, a, cfg, mx, recs, *ob);
-        else hipLaunchKernelGGL((k_lattice_filter3<CR, false, false, F1P_GEN_CLOTHOID, false, LatObs>), g, fb, lds, st, a, cfg, mx, recs, *ob);
+        if (host_goals && hooks) hipLaunchKernelGGL((k_lattice_filter3<CR, true, true, F1P_GEN_CLOTHOID, false, LatObs>), g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx, *ob);
+        else if (host_goals) hipLaunchKernelGGL((k_lattice_filter3<CR, false, true, F1P_GEN_CLOTHOID, false, LatObs>), g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx, *ob);
+        else if (hooks) hipLaunchKernelGGL((k_lattice_filter3<CR, true, false, F1P_GEN_CLOTHOID, false, LatObs>), g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx, *ob);
+        else hipLaunchKernelGGL((k_lattice_filter3<CR, false, false, F1P_GEN_CLOTHOID, false, LatObs>), g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx, *ob);
         return;
     }
-    if (cubic && foot && host_goals) hipLaunchKernelGGL((k_lattice_filter3<CR, true, true, F1P_GEN_CUBIC, true>), g, fb, lds, st, a, cfg, mx, recs);   // (oriented footprint: one instantiation per goal source, hooks included)
-    else if (cubic && foot) hipLaunchKernelGGL((k_lattice_filter3<CR, true, false, F1P_GEN_CUBIC, true>), g, fb, lds, st, a, cfg, mx, recs);
-    else if (cubic && host_goals) hipLaunchKernelGGL((k_lattice_filter3<CR, true, true, F1P_GEN_CUBIC>), g, fb, lds, st, a, cfg, mx, recs);             // (host goals: hooks included)
+    if (cubic && foot && host_goals) hipLaunchKernelGGL((k_lattice_filter3<CR, true, true, F1P_GEN_CUBIC, true>), g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx);   // (oriented footprint: one instantiation per goal source, hooks included)
+    else if (cubic && foot) hipLaunchKernelGGL((k_lattice_filter3<CR, true, false, F1P_GEN_CUBIC, true>), g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx);
+    else if (cubic && host_goals) hipLaunchKernelGGL((k_lattice_filter3<CR, true, true, F1P_GEN_CUBIC>), g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx);             // (host goals: hooks included)
     else if (cubic) {
-        if (hooks) hipLaunchKernelGGL((k_lattice_filter3<CR, true, false, F1P_GEN_CUBIC>), g, fb, lds, st, a, cfg, mx, recs);
-        else hipLaunchKernelGGL((k_lattice_filter3<CR, false, false, F1P_GEN_CUBIC>), g, fb, lds, st, a, cfg, mx, recs);
+        if (hooks) hipLaunchKernelGGL((k_lattice_filter3<CR, true, false, F1P_GEN_CUBIC>), g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx);
+        else hipLaunchKernelGGL((k_lattice_filter3<CR, false, false, F1P_GEN_CUBIC>), g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx);
     } else if (foot) {
-        if (host_goals) hipLaunchKernelGGL((k_lattice_filter3<CR, true, true, F1P_GEN_CLOTHOID, true>), g, fb, lds, st, a, cfg, mx, recs);
-        else if (hooks) hipLaunchKernelGGL((k_lattice_filter3<CR, true, false, F1P_GEN_CLOTHOID, true>), g, fb, lds, st, a, cfg, mx, recs);
-        else hipLaunchKernelGGL((k_lattice_filter3<CR, false, false, F1P_GEN_CLOTHOID, true>), g, fb, lds, st, a, cfg, mx, recs);                       // (device goals without hooks: the instantiation without spills)
+        if (host_goals) hipLaunchKernelGGL((k_lattice_filter3<CR, true, true, F1P_GEN_CLOTHOID, true>), g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx);
+        else if (hooks) hipLaunchKernelGGL((k_lattice_filter3<CR, true, false, F1P_GEN_CLOTHOID, true>), g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx);
+        else hipLaunchKernelGGL((k_lattice_filter3<CR, false, false, F1P_GEN_CLOTHOID, true>), g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx);                       // (device goals without hooks: the instantiation without spills)
     } else if (host_goals) {                                     // (the reference's add_sample_function plug-in: with and, round 6, without the test hooks)
-        if (hooks) hipLaunchKernelGGL((k_lattice_filter3<CR, true, true>), g, fb, lds, st, a, cfg, mx, recs);
-        else hipLaunchKernelGGL((k_lattice_filter3<CR, false, true>), g, fb, lds, st, a, cfg, mx, recs);
+        if (hooks) hipLaunchKernelGGL((k_lattice_filter3<CR, true, true>), g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx);
+        else hipLaunchKernelGGL((k_lattice_filter3<CR, false, true>), g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx);
     } else {
-        if (hooks) hipLaunchKernelGGL((k_lattice_filter3<CR, true>), g, fb, lds, st, a, cfg, mx, recs);
-        else hipLaunchKernelGGL(k_lattice_filter3<CR>, g, fb, lds, st, a, cfg, mx, recs);
+        if (hooks) hipLaunchKernelGGL((k_lattice_filter3<CR, true>), g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx);
+        else hipLaunchKernelGGL(k_lattice_filter3<CR>, g, fb, lds, st, recs, mx.perm, rec_bytes, mx.perm_rs, a.e0, a.E, a, cfg, mx);
     }
 }
 

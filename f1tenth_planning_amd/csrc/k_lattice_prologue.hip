@@ -544,23 +544,38 @@ __device__ __forceinline__ void half_argmin_2step(double& d, int& i, bool hi_hal
     d = hi_half ? bd1 : bd0; i = hi_half ? bi1 : bi0;
 }
 
-__global__ __launch_bounds__(256) void k_lattice_prologue2(LatticeArgs a, f1p_lattice_cfg cfg, MixArgs mx, unsigned char* __restrict__ recs) {
+__global__ __launch_bounds__(256) void k_lattice_prologue2(const double* __restrict__ h_poses, const double* __restrict__ h_wx, const double* __restrict__ h_wy, const double* __restrict__ h_wbox,
+                                                           int h_n, int h_e0, int h_E, LatticeArgs a, f1p_lattice_cfg cfg, MixArgs mx, unsigned char* __restrict__ recs) {
     __shared__ double s_seg[4][2][5][64];                         // per ego: the 64 virtual segments' start x, y, end x, y, start heading
     __shared__ int s_first[4][2][32];
     __shared__ int s_pairs[4][2][64];
-    warm_kernargs<sizeof(LatticeArgs) + sizeof(f1p_lattice_cfg) + sizeof(MixArgs) + 8>();
+    // h_*: LatticeArgs::poses / wx / wy / wbox / n / e0 / E once more, as LEADING parameters: they arrive in SGPRs at wave launch (kernarg preload,
+    // lattice_device.h), so the pose, the chunk boxes and the sample waypoints are requested before the argument segment has been read
+    int ka[32];
+    warm_kernargs_touch<48 + sizeof(LatticeArgs) + sizeof(f1p_lattice_cfg) + sizeof(MixArgs) + 8>(ka);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool hh = lane >= 32;
     const int h = hh ? 1 : 0, hl = lane & 31, hbase = lane & 32;
-    const int e_first = a.e0 + ((blockIdx.x * 4 + wave) << 1);
-    if (e_first >= a.E) return;                                  // wave-uniform
-    const bool valid = e_first + h < a.E;
-    const int e = valid ? e_first + h : a.E - 1;                 // an odd batch's last wave: its second half repeats the last ego and stores nothing
-    const int nl = cfg.n_lookahead, S = cfg.n_stations, n = a.n;
+    const int e_first = h_e0 + ((blockIdx.x * 4 + wave) << 1);
+    if (e_first >= h_E) return;                                  // wave-uniform
+    const bool valid = e_first + h < h_E;
+    const int e = valid ? e_first + h : h_E - 1;                 // an odd batch's last wave: its second half repeats the last ego and stores nothing
+    const int n = h_n;
+    const double* __restrict__ wx = h_wx; const double* __restrict__ wy = h_wy;
+    // ---- what does not depend on the pose: chunk boxes, sample waypoints (32 per ego: the bound only prunes) ---------------------------------
+    const int nseg = n - 1, nchunk = (nseg + 63) >> 6;
+    double b0x = 0.0, b0X = 0.0, b0y = 0.0, b0Y = 0.0;
+    if (hl < nchunk) { b0x = h_wbox[4 * hl]; b0X = h_wbox[4 * hl + 1]; b0y = h_wbox[4 * hl + 2]; b0Y = h_wbox[4 * hl + 3]; }
+    int sj0 = hl * ((n + 63) >> 6), sj1 = (hl + 32) * ((n + 63) >> 6);   // 64 sample waypoints per ego, two per lane (32: 1.67 scan trips per wave on the bench's track, 64: 1.38)
+    if (sj0 > n - 1) sj0 = n - 1;
+    if (sj1 > n - 1) sj1 = n - 1;
+    double smx0 = wx[sj0], smy0 = wy[sj0], smx1 = wx[sj1], smy1 = wy[sj1];
+    double px = h_poses[4 * e], py = h_poses[4 * e + 1], theta = h_poses[4 * e + 2];
+    warm_kernargs_wait(ka, b0x, b0X, b0y, b0Y, smx0, smy0, smx1, smy1, px, py, theta);
+    const int nl = cfg.n_lookahead, S = cfg.n_stations;
     double (*seg)[64] = s_seg[wave][h];
     int* lds_first = s_first[wave][h];
     int* lds_pairs = s_pairs[wave][h];
-    const double* __restrict__ wx = a.wx; const double* __restrict__ wy = a.wy;
 #ifdef F1P_PRO2_PHASES
     long long pph[10], lat[5] = {0, 0, 0, 0, 0}; int npp = 0;
 #define F1P_PPH() do { __builtin_amdgcn_s_waitcnt(0); pph[npp++] = clock64(); } while (0)
@@ -570,15 +585,6 @@ __global__ __launch_bounds__(256) void k_lattice_prologue2(LatticeArgs a, f1p_la
 #define F1P_LAT(k) do {} while (0)
 #endif
     F1P_PPH();
-    // ---- what does not depend on the pose: chunk boxes, sample waypoints (32 per ego: the bound only prunes) ---------------------------------
-    const int nseg = n - 1, nchunk = (nseg + 63) >> 6;
-    double b0x = 0.0, b0X = 0.0, b0y = 0.0, b0Y = 0.0;
-    if (hl < nchunk) { b0x = a.wbox[4 * hl]; b0X = a.wbox[4 * hl + 1]; b0y = a.wbox[4 * hl + 2]; b0Y = a.wbox[4 * hl + 3]; }
-    int sj0 = hl * ((n + 63) >> 6), sj1 = (hl + 32) * ((n + 63) >> 6);   // 64 sample waypoints per ego, two per lane (32: 1.67 scan trips per wave on the bench's track, 64: 1.38)
-    if (sj0 > n - 1) sj0 = n - 1;
-    if (sj1 > n - 1) sj1 = n - 1;
-    const double smx0 = wx[sj0], smy0 = wy[sj0], smx1 = wx[sj1], smy1 = wy[sj1];
-    const double px = a.poses[4 * e], py = a.poses[4 * e + 1], theta = a.poses[4 * e + 2];
     if (a.pose_copy && hl < 4 && valid) a.pose_copy[4 * e + hl] = a.poses[4 * e + hl];
     const int sim_m = S - cfg.n_shift - cfg.n_cull;
     double pm0 = 0.0, pm1 = 0.0, pm2 = 0.0;
@@ -863,7 +869,7 @@ __global__ __launch_bounds__(256) void k_lattice_prologue2(LatticeArgs a, f1p_la
 void mixed_launch_prologue(bool two_per_wave, bool tracks, int egos, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx,
                            unsigned char* recs) {
     if (tracks) hipLaunchKernelGGL(k_lattice_prologue<true>, dim3((egos + 3) / 4), dim3(256), 0, st, a, cfg, mx, recs);   // (one ego per wave at every size)
-    else if (two_per_wave) hipLaunchKernelGGL(k_lattice_prologue2, dim3((egos + 7) / 8), dim3(256), 0, st, a, cfg, mx, recs);
+    else if (two_per_wave) hipLaunchKernelGGL(k_lattice_prologue2, dim3((egos + 7) / 8), dim3(256), 0, st, a.poses, a.wx, a.wy, a.wbox, a.n, a.e0, a.E, a, cfg, mx, recs);
     else hipLaunchKernelGGL(k_lattice_prologue<false>, dim3((egos + 3) / 4), dim3(256), 0, st, a, cfg, mx, recs);
 }
 

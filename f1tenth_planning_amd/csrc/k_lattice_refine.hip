@@ -34,13 +34,35 @@ __device__ __forceinline__ double group_shr1(double v) {
 // times, against the slots the candidate kernel transformed (LatObs::xf) -- for every entry it did not prove clear of every disc (ok != -2).  The
 // instantiations without obstacles keep their signature and their code.
 template <int GS, bool FOOT = false, typename... OB>
-__global__ __launch_bounds__(256, 2) void k_lattice_refine(LatticeArgs a, f1p_lattice_cfg cfg, MixArgs mx, OB... obx) {
+__global__ __launch_bounds__(256, 2) void k_lattice_refine(const unsigned int* __restrict__ h_qcount, const RefEntry* __restrict__ h_q, unsigned int h_q_shard_cap, unsigned int h_grid,
+                                                           LatticeArgs a, f1p_lattice_cfg cfg, MixArgs mx, OB... obx) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     constexpr bool OBS = sizeof...(OB) > 0;
-    warm_kernargs<sizeof(LatticeArgs) + sizeof(f1p_lattice_cfg) + sizeof(MixArgs) + (sizeof(OB) + ... + 0)>();
+    // h_*: MixArgs::qcount / q / q_shard_cap and the grid size once more, as LEADING parameters: they arrive in SGPRs at wave launch (kernarg preload,
+    // lattice_device.h), so the shard's count and the group's first entry are requested before the argument segment has been read (gridDim and blockDim
+    // sit behind that segment: the head takes the grid size from h_grid and the block size from the launcher's constant)
+    int ka[32];
+    warm_kernargs_touch<24 + sizeof(LatticeArgs) + sizeof(f1p_lattice_cfg) + sizeof(MixArgs) + (sizeof(OB) + ... + 0)>(ka);
     constexpr int GPW = 64 / GS;                                 // groups (entries) per wave
+    constexpr unsigned int WPB = F1P_MIX_REFINE_BLOCK / 64;      // waves per workgroup
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int gl = lane & (GS - 1), grp = lane / GS, gbase = lane & ~(GS - 1);
+    // group g works on shard g % shards, entries g / shards, + groups / shards, ... (the launcher makes the group count a multiple of the shard count)
+    const unsigned int ngroups_total = h_grid * WPB * GPW;
+    const unsigned int g0 = (blockIdx.x * WPB + wave) * GPW + grp;
+    // A wave's groups take CONSECUTIVE entries of one shard -- an ego's own entries, or neighbouring egos': alike goals, alike phase lengths.
+    // The groups of a wave run in lockstep, so every phase costs the maximum over its four entries; with the groups of a wave spread
+    // over the shards (entries of unrelated egos) the refinement took 20.5 us against 19.3 (round 4).
+    const unsigned int sh = (g0 / GPW) % F1P_MIX_QSHARDS, lstride = ngroups_total / F1P_MIX_QSHARDS;
+    const unsigned int li_first = (g0 / (GPW * F1P_MIX_QSHARDS)) * GPW + g0 % GPW;
+    // The group's first entry is requested TOGETHER with the shard's count, not after it (slots past the count hold stale entries of
+    // earlier plans -- readable memory, masked below).  Written as two loads and one use of both: with the entry's load behind the
+    // `any live` exit, which needs the count, the two round trips ran one after the other (4.4 k cycles per entry, tools/refine_phases.py).
+    RefEntry r_first;
+    r_first.ok = 0; r_first.e = 0; r_first.c = 0; r_first.gx = 0; r_first.gy = 0; r_first.gth = 0; r_first.cost = 0; r_first.k0 = 0; r_first.dk = 0; r_first.L = 0; r_first.pad = 0;
+    unsigned int n = h_qcount[sh * 32u];
+    if (li_first < h_q_shard_cap) r_first = h_q[sh * h_q_shard_cap + li_first];
+    warm_kernargs_wait(ka, n, r_first.ok);
     const int S_arg = cfg.n_stations;
     if (mx.perm_fill) {                                          // the dispatch order's slots and counters: consumed by the candidate kernel, cleared here, filled by k_lattice_select
         const int np = F1P_MIX_OREG * mx.perm_rs;
@@ -60,21 +82,6 @@ __global__ __launch_bounds__(256, 2) void k_lattice_refine(LatticeArgs a, f1p_la
 #endif
     F1P_RPH();
     const bool collide_on = cfg.check_collision && a.has_grid;
-    // group g works on shard g % shards, entries g / shards, + groups / shards, ... (the launcher makes the group count a multiple of the shard count)
-    const unsigned int ngroups_total = gridDim.x * (blockDim.x >> 6) * GPW;
-    const unsigned int g0 = (blockIdx.x * (blockDim.x >> 6) + wave) * GPW + grp;
-    // A wave's groups take CONSECUTIVE entries of one shard -- an ego's own entries, or neighbouring egos': alike goals, alike phase lengths.
-    // The groups of a wave run in lockstep, so every phase costs the maximum over its four entries; with the groups of a wave spread
-    // over the shards (entries of unrelated egos) the refinement took 20.5 us against 19.3 (round 4).
-    const unsigned int sh = (g0 / GPW) % F1P_MIX_QSHARDS, lstride = ngroups_total / F1P_MIX_QSHARDS;
-    const unsigned int li_first = (g0 / (GPW * F1P_MIX_QSHARDS)) * GPW + g0 % GPW;
-    // The group's first entry is requested TOGETHER with the shard's count, not after it (slots past the count hold stale entries of
-    // earlier plans -- readable memory, masked below).  Written as two loads and one use of both: with the entry's load behind the
-    // `any live` exit, which needs the count, the two round trips ran one after the other (4.4 k cycles per entry, tools/refine_phases.py).
-    RefEntry r_first;
-    r_first.ok = 0; r_first.e = 0; r_first.c = 0; r_first.gx = 0; r_first.gy = 0; r_first.gth = 0; r_first.cost = 0; r_first.k0 = 0; r_first.dk = 0; r_first.L = 0; r_first.pad = 0;
-    unsigned int n = mx.qcount[sh * 32u];
-    if (li_first < mx.q_shard_cap) r_first = mx.q[sh * mx.q_shard_cap + li_first];
     // ... and the tables go to LDS while both are on their way (they used to be staged, and waited for, before the count was even asked for)
     if (tid < 96) s_gl_wu[tid / 6][tid % 6] = c_gl_wu[tid / 6][tid % 6];
     else if (tid < 112) s_gl_x[tid - 96] = c_gl_x[tid - 96];
@@ -623,18 +630,18 @@ bool mixed_refine_cubic_fits(f1p_ctx* ctx, size_t lds) {
 
 void mixed_launch_refine(bool cubic, int lanes, bool foot, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx,
                          const LatObs* ob) {
-    const dim3 g(grid), b(256);
+    const dim3 g(grid), b(F1P_MIX_REFINE_BLOCK);
     if (ob) {                                                    // (the schedule sends only clothoids with the point footprint here while discs are set)
-        if (lanes == 16) hipLaunchKernelGGL((k_lattice_refine<16, false, LatObs>), g, b, lds, st, a, cfg, mx, *ob);
-        else hipLaunchKernelGGL((k_lattice_refine<64, false, LatObs>), g, b, lds, st, a, cfg, mx, *ob);
+        if (lanes == 16) hipLaunchKernelGGL((k_lattice_refine<16, false, LatObs>), g, b, lds, st, mx.qcount, mx.q, mx.q_shard_cap, grid, a, cfg, mx, *ob);
+        else hipLaunchKernelGGL((k_lattice_refine<64, false, LatObs>), g, b, lds, st, mx.qcount, mx.q, mx.q_shard_cap, grid, a, cfg, mx, *ob);
     } else if (cubic && foot) hipLaunchKernelGGL((k_lattice_refine_cubic<16, true>), g, b, lds, st, a, cfg, mx);
     else if (cubic) hipLaunchKernelGGL(k_lattice_refine_cubic<16>, g, b, lds, st, a, cfg, mx);
     else if (lanes == 16) {
-        if (foot) hipLaunchKernelGGL((k_lattice_refine<16, true>), g, b, lds, st, a, cfg, mx);
-        else hipLaunchKernelGGL(k_lattice_refine<16>, g, b, lds, st, a, cfg, mx);
+        if (foot) hipLaunchKernelGGL((k_lattice_refine<16, true>), g, b, lds, st, mx.qcount, mx.q, mx.q_shard_cap, grid, a, cfg, mx);
+        else hipLaunchKernelGGL(k_lattice_refine<16>, g, b, lds, st, mx.qcount, mx.q, mx.q_shard_cap, grid, a, cfg, mx);
     } else {
-        if (foot) hipLaunchKernelGGL((k_lattice_refine<64, true>), g, b, lds, st, a, cfg, mx);
-        else hipLaunchKernelGGL(k_lattice_refine<64>, g, b, lds, st, a, cfg, mx);
+        if (foot) hipLaunchKernelGGL((k_lattice_refine<64, true>), g, b, lds, st, mx.qcount, mx.q, mx.q_shard_cap, grid, a, cfg, mx);
+        else hipLaunchKernelGGL(k_lattice_refine<64>, g, b, lds, st, mx.qcount, mx.q, mx.q_shard_cap, grid, a, cfg, mx);
     }
 }
 

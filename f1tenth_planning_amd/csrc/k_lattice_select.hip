@@ -7,23 +7,31 @@ namespace f1p {
 // wave per ego: select() over the refined candidates, winner re-emission, tracking (the tail of k_lattice_eval)
 // TRK = a track plan (LatticeArgs::track_id): the speed command is the ego's own track's; an id outside [0, K) gets the bad-track outputs
 template <int GEN = F1P_GEN_CLOTHOID, bool TRK = false>
-__global__ __launch_bounds__(256, 3) void k_lattice_select(LatticeArgs a, f1p_lattice_cfg cfg, MixArgs mx) {
+__global__ __launch_bounds__(256, 3) void k_lattice_select(const int32_t* __restrict__ h_ego_base, const int32_t* __restrict__ h_ego_n, const int32_t* __restrict__ h_ego_ni, int h_e0,
+                                                           int h_E, LatticeArgs a, f1p_lattice_cfg cfg, MixArgs mx) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    warm_kernargs<sizeof(LatticeArgs) + sizeof(f1p_lattice_cfg) + sizeof(MixArgs)>();
+    // h_*: MixArgs::ego_base / ego_n / ego_ni and LatticeArgs::e0 / E once more, as LEADING parameters: they arrive in SGPRs at wave launch (kernarg preload,
+    // lattice_device.h), so the ego's queue slice is requested before the argument segment has been read -- one round trip instead of two in front of the entries
+    int ka[32];
+    warm_kernargs_touch<32 + sizeof(LatticeArgs) + sizeof(f1p_lattice_cfg) + sizeof(MixArgs)>(ka);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n_sel = (a.E - a.e0 + 3) / 4;                      // selection workgroups; the ones behind them (launched when mx.perm_fill is set) place the egos
+    const int e_head = h_e0 + (int)blockIdx.x * 4 + wave;
+    const int e_load = e_head < h_E ? e_head : h_E - 1;           // (the placing workgroups and the last workgroup's spare waves: a valid address, values unused)
+    int base = h_ego_base[e_load], n = h_ego_n[e_load], ni = h_ego_ni[e_load];
+    warm_kernargs_wait(ka, base, n, ni);
+    const int n_sel = (h_E - h_e0 + 3) / 4;                      // selection workgroups; the ones behind them (launched when mx.perm_fill is set) place the egos
     if ((int)blockIdx.x >= n_sel) {                              // ... in the NEXT plan's dispatch order, heavy egos from the front of their region, the others from its back
-        const int eo = a.e0 + ((int)blockIdx.x - n_sel) * (int)blockDim.x + tid;
-        if (mx.perm_fill && eo < a.E) {
+        const int eo = h_e0 + ((int)blockIdx.x - n_sel) * (int)blockDim.x + tid;
+        if (mx.perm_fill && eo < h_E) {
             const unsigned r = (unsigned)eo % F1P_MIX_OREG;
             const int slot = mx.heavy[eo] ? (int)atomicAdd(&mx.ocnt[r * 64u], 1u) : mx.perm_rs - 1 - (int)atomicAdd(&mx.ocnt[r * 64u + 32u], 1u);
             mx.perm_fill[r * (unsigned)mx.perm_rs + (unsigned)slot] = eo + 1;
         }
         return;
     }
-    const int e = a.e0 + blockIdx.x * 4 + wave;
+    const int e = e_head;
     if (blockIdx.x == 0 && tid < F1P_MIX_QSHARDS) mx.qcount[tid * 32u] = 0u;   // the refinement kernel is done with them: ready for the next plan
-    if (e >= a.E) return;
+    if (e >= h_E) return;
     if constexpr (TRK) {
         if (!lattice_bind_track(a, e)) { lattice_bad_track(a, cfg, e, lane, 64); return; }   // (wave-uniform)
     }
@@ -35,7 +43,6 @@ __global__ __launch_bounds__(256, 3) void k_lattice_select(LatticeArgs a, f1p_la
 #ifdef F1P_MIX_PHASES
     long long sph[8]; sph[0] = clock64();
 #endif
-    const int base = mx.ego_base[e], n = mx.ego_n[e], ni = mx.ego_ni[e];
     const double v_near = a.wv[ni];                              // the tracker's speed command: requested with the entries, consumed at the end
     const int c0 = cfg.cand_begin;
     // Round 4: ONE round trip for everything the usual ego needs.  Lane j takes the WHOLE record of entry j (cost, index, clothoid) -- the
@@ -143,10 +150,10 @@ bool mixed_select_fits(f1p_ctx* ctx, bool cubic, size_t lds, bool tracks) {
 
 void mixed_launch_select(bool cubic, bool tracks, unsigned grid, size_t lds, hipStream_t st, const LatticeArgs& a, const f1p_lattice_cfg& cfg, const MixArgs& mx) {
     if (tracks) {
-        if (cubic) hipLaunchKernelGGL((k_lattice_select<F1P_GEN_CUBIC, true>), dim3(grid), dim3(256), lds, st, a, cfg, mx);
-        else hipLaunchKernelGGL((k_lattice_select<F1P_GEN_CLOTHOID, true>), dim3(grid), dim3(256), lds, st, a, cfg, mx);
-    } else if (cubic) hipLaunchKernelGGL(k_lattice_select<F1P_GEN_CUBIC>, dim3(grid), dim3(256), lds, st, a, cfg, mx);
-    else hipLaunchKernelGGL(k_lattice_select<F1P_GEN_CLOTHOID>, dim3(grid), dim3(256), lds, st, a, cfg, mx);
+        if (cubic) hipLaunchKernelGGL((k_lattice_select<F1P_GEN_CUBIC, true>), dim3(grid), dim3(256), lds, st, mx.ego_base, mx.ego_n, mx.ego_ni, a.e0, a.E, a, cfg, mx);
+        else hipLaunchKernelGGL((k_lattice_select<F1P_GEN_CLOTHOID, true>), dim3(grid), dim3(256), lds, st, mx.ego_base, mx.ego_n, mx.ego_ni, a.e0, a.E, a, cfg, mx);
+    } else if (cubic) hipLaunchKernelGGL(k_lattice_select<F1P_GEN_CUBIC>, dim3(grid), dim3(256), lds, st, mx.ego_base, mx.ego_n, mx.ego_ni, a.e0, a.E, a, cfg, mx);
+    else hipLaunchKernelGGL(k_lattice_select<F1P_GEN_CLOTHOID>, dim3(grid), dim3(256), lds, st, mx.ego_base, mx.ego_n, mx.ego_ni, a.e0, a.E, a, cfg, mx);
 }
 
 }  // namespace f1p

@@ -132,6 +132,7 @@ namespace f1p {
 #ifndef F1P_MIX_REFINE_WG_PER_CU
 #define F1P_MIX_REFINE_WG_PER_CU 4   // workgroups of k_lattice_refine<16> per CU the grid is capped at (grid-stride over the queue beyond that; measured: 2 / 3 / 4 -> 65.7 / 65.6 / 65.8 us per plan, no difference)
 #endif
+#define F1P_MIX_REFINE_BLOCK 256      // threads per workgroup of k_lattice_refine: a constant of kernel and launcher (the kernel's head runs before blockDim can be read)
 #ifndef F1P_PRO2
 #define F1P_PRO2 1              // k_lattice_prologue2 (two egos per wave) where it applies; 0: k_lattice_prologue always (A/B)
 #endif
