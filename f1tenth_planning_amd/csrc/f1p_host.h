@@ -147,6 +147,81 @@ inline int validate_stmpc(f1p_ctx* ctx, const f1p_stmpc_cfg* cfg, int E) { retur
 int validate_kmpc_qp(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, int E, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o);
 int qp_opts(f1p_ctx* ctx, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o, const char* what);
 int validate_qp_avoid(f1p_ctx* ctx, const f1p_kmpc_qp_avoid* a);
+// f1p_kmpc.hip: f1p_{kmpc,stmpc}_qp_set_avoid on the planner's own switch `state`
+int qp_set_avoid(f1p_ctx* ctx, f1p_kmpc_qp_avoid* state, const f1p_kmpc_qp_avoid* avoid);
+
+// The stateless QP entry points f1p_{kmpc,stmpc}_qp[_avoid]_{batch,dev} are one body (qp_call) over a model Q: KinQp (f1p_kmpc.hip) or DynQp
+// (f1p_stmpc.hip), each with
+//   Cfg; NX (the state width), DUALS (rows per step: duals [E][DUALS T - 2]), AVOID_MAX_T (the avoidance variant's longest horizon)
+//   who ("kmpc" / "stmpc": the prefix of the messages), avoid_cap (the message past AVOID_MAX_T)
+//   EMPTY_RETURNS (the *_batch entries return F1P_OK at E == 0 before they stage)
+//   validate(ctx, cfg, E, opts, o), launch(ctx, E, cfg, max_iter, tol, io, avoid)
+//   obs(ctx), av(ctx): the planner's discs and its set_avoid switch
+// set_avoid is on: what the entry points check before they launch the avoidance variant on the context's discs, held in the order of the
+// caller's E egos (kcfg: a plan's kinematic branch, which runs k_kmpc_qp's variant)
+template <class Q>
+int qp_avoid_plan_check(f1p_ctx* ctx, const typename Q::Cfg* cfg, int E, const f1p_kmpc_cfg* kcfg = nullptr) {
+    const std::string w = Q::who;
+    if (cfg->horizon > Q::AVOID_MAX_T) return set_error(ctx, F1P_EINVAL, w + Q::avoid_cap);
+    if (kcfg && kcfg->horizon > 31) return set_error(ctx, F1P_EINVAL, w + " qp avoid: the kinematic branch's horizon must be <= 31 (2TK + 1 inputs, one lane each)");
+    const ObsState& st = Q::obs(ctx);
+    if (st.cur && E != st.E)
+        return set_error(ctx, F1P_ESTATE, w + " obstacles were set for " + std::to_string(st.E) + " egos, this plan has " + std::to_string(E) + " (f1p_" + w + "_set_obstacles)");
+    return F1P_OK;
+}
+
+// io: the caller's arrays, on the host (staged: *_batch) or on the device (*_dev).  avoid null: the plain QP -- which a *_dev call runs as
+// the avoidance variant on the context's discs while set_avoid is on.  Else avoid holds the call's obs, M and outputs, and `numbers`
+// (nullable: the defaults) its margin, rho and lin.
+template <class Q>
+int qp_call(f1p_ctx* ctx, bool staged, int E, const typename Q::Cfg* cfg, const f1p_kmpc_qp_opts* opts, const QpIo& io, const QpAvoidArgs* avoid,
+            const f1p_kmpc_qp_avoid* numbers) {
+    F1P_ENTER(ctx);
+    const std::string w = Q::who;
+    f1p_kmpc_qp_opts o;
+    QpAvoidArgs av;
+    int rc = Q::validate(ctx, cfg, E, opts, &o); if (rc) return rc;
+    if (avoid) {
+        if (cfg->horizon > Q::AVOID_MAX_T) return set_error(ctx, F1P_EINVAL, w + Q::avoid_cap);
+        if (avoid->M < 1 || avoid->M > F1P_KMPC_MAX_OBS) return set_error(ctx, F1P_EINVAL, w + " qp avoid: M must be in [1, 16]");
+        if (E > 0 && !avoid->obs) return set_error(ctx, F1P_EINVAL, w + " qp avoid: obs is NULL");
+        f1p_kmpc_qp_avoid a;
+        f1p_kmpc_qp_avoid_default(&a);
+        if (numbers) a = *numbers;
+        if ((rc = validate_qp_avoid(ctx, &a))) return rc;
+        av = *avoid;
+        av.margin = a.margin; av.rho = a.rho; av.lin = a.lin;
+    }
+    if (E > 0 && (!io.x0 || !io.ref || !io.steer || !io.speed || !io.status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
+    if (!staged) {
+        if (!avoid && Q::av(ctx).on) {
+            if ((rc = qp_avoid_plan_check<Q>(ctx, cfg, E))) return rc;
+            av = QpAvoidArgs(Q::obs(ctx).cur, Q::obs(ctx).M, Q::av(ctx));
+            avoid = &av;
+        }
+        return Q::launch(ctx, E, cfg, o.max_iter, o.tol, io, avoid ? &av : nullptr);
+    }
+    if (Q::EMPTY_RETURNS && E == 0) return F1P_OK;
+    const size_t T = cfg->horizon, e = E, m = av.M, NX = Q::NX, ND = Q::DUALS * T - 2;
+    Stage s(ctx);
+    s.need(8 * NX * e); s.need(8 * e * NX * (T + 1)); s.need(8 * e * T, io.pa); s.need(8 * e * T, io.pd); s.need(8 * e * m * 5, avoid);
+    s.need(8 * e); s.need(8 * e); s.need(4 * e); s.need(8 * e * T * 2, io.u); s.need(8 * e * NX * (T + 1), io.x); s.need(8 * e, io.obj);
+    s.need(8 * e * ND, io.duals); s.need(4 * e, io.iters);
+    s.need(8 * e, av.eps); s.need(8 * e * T * 8, av.planes); s.need(8 * e * (2 * T + 1), av.duals);
+    if ((rc = s.begin())) return rc;
+    QpIo d;
+    if ((rc = s.in(io.x0, NX * e, &d.x0))) return rc;
+    if ((rc = s.in(io.ref, e * NX * (T + 1), &d.ref))) return rc;
+    if ((rc = s.in(io.pa, e * T, &d.pa))) return rc;
+    if ((rc = s.in(io.pd, e * T, &d.pd))) return rc;
+    if ((rc = s.in(av.obs, e * m * 5, &av.obs))) return rc;
+    d.steer = s.out(io.steer, e); d.speed = s.out(io.speed, e); d.status = s.out(io.status, e);
+    d.u = s.out(io.u, e * T * 2); d.x = s.out(io.x, e * NX * (T + 1)); d.obj = s.out(io.obj, e);
+    d.duals = s.out(io.duals, e * ND); d.iters = s.out(io.iters, e);
+    av.eps = s.out(av.eps, e); av.planes = s.out(av.planes, e * T * 8); av.duals = s.out(av.duals, e * (2 * T + 1));
+    if ((rc = Q::launch(ctx, E, cfg, o.max_iter, o.tol, d, avoid ? &av : nullptr))) return rc;
+    return s.finish();
+}
 // f1p_kmpc.hip: the argument checks of the four reference extractions (f1p_{kmpc,stmpc}_ref[_tracks]_{batch,dev}), and the *_batch body behind them:
 // ncol = 4 (kinematic rows) or 7 (dynamic rows); track_id (host) is read when tracks, else every ego follows the raceline
 int validate_ref(f1p_ctx* ctx, const void* states, const int32_t* track_id, bool tracks, int E, int horizon, double dt, double dl, const void* ref);

@@ -290,28 +290,27 @@ int launch_kmpc_plan_gen(f1p_ctx* ctx, const double* d_x0, const double* d_ref, 
                          const int32_t* d_ids = nullptr, int wstride = 0, uint32_t ego_off = 0u);
 int launch_kmpc_gen_controls(f1p_ctx* ctx, float* d_controls, int E, const f1p_kmpc_cfg* cfg, const f1p_kmpc_sampler* smp, const float* d_warm);
 int kmpc_plan_groups(const f1p_ctx* ctx, int E, int R);
-// k_kmpc_qp.hip: prev (oa, od) read at pa[(e T + t) pstride], pd[...] (nullable: zeros); every output but steer / speed nullable
-int launch_kmpc_qp(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
-                   const f1p_kmpc_cfg* cfg, int max_iter, double tol, double* d_steer, double* d_speed, int32_t* d_status, double* d_u,
-                   double* d_xk, double* d_obj, double* d_duals, int32_t* d_iters, double* d_warm_out);
-int kmpc_qp_pack(const f1p_ctx* ctx, int T);
-// k_kmpc_qp.hip, the avoidance variant (f1p_kmpc_qp_avoid_*): d_obs [E][M][5] (M = 0: none), T <= 31; d_eps [E], d_planes [E][T][2][4] and
-// d_avoid_duals [E][2T+1] nullable
-int launch_kmpc_qp_avoid(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
-                         const f1p_kmpc_cfg* cfg, int max_iter, double tol, const double* d_obs, int M, const f1p_kmpc_qp_avoid* avoid,
-                         double* d_steer, double* d_speed, int32_t* d_status, double* d_u, double* d_xk, double* d_obj, double* d_duals,
-                         int32_t* d_iters, double* d_warm_out, double* d_eps, double* d_planes, double* d_avoid_duals);
-// k_stmpc_qp.hip: prev (oa, od_v) read at pa[(e T + t) pstride], pd[...] (nullable: zeros); warm_out [E][T][2] = (oa, od_v)
-int launch_stmpc_qp(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
-                    const f1p_stmpc_cfg* cfg, int max_iter, double tol, double* d_steer, double* d_speed, int32_t* d_status, double* d_u,
-                    double* d_x, double* d_obj, double* d_duals, int32_t* d_iters, double* d_warm_out);
-size_t stmpc_qp_lds_bytes(int T);
-// k_stmpc_qp.hip, the avoidance variant (f1p_stmpc_qp_avoid_*): d_obs [E][M][5] (M = 0: none), T <= F1P_STMPC_QP_AVOID_MAX_T; d_eps [E],
-// d_planes [E][T][2][4] and d_avoid_duals [E][2T+1] nullable
-int launch_stmpc_qp_avoid(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
-                          const f1p_stmpc_cfg* cfg, int max_iter, double tol, const double* d_obs, int M, const f1p_kmpc_qp_avoid* avoid,
-                          double* d_steer, double* d_speed, int32_t* d_status, double* d_u, double* d_x, double* d_obj, double* d_duals,
-                          int32_t* d_iters, double* d_warm_out, double* d_eps, double* d_planes, double* d_avoid_duals);
+// What a launch of either QP kernel takes (k_kmpc_qp.hip, k_stmpc_qp.hip), device pointers all: x0 [E][NX], ref [E][NX][T+1] (NX = 4 kinematic,
+// 7 dynamic); the previous solution, read at pa[(e T + t) pstride], pd[...] (null: zeros); the outputs, warm_out [E][T][2] = the next (oa, od)
+struct QpIo {
+    const double *x0 = nullptr, *ref = nullptr, *pa = nullptr, *pd = nullptr;
+    int pstride = 1;
+    double *steer = nullptr, *speed = nullptr; int32_t* status = nullptr;                                                 // always written
+    double *u = nullptr, *x = nullptr, *obj = nullptr, *duals = nullptr, *warm_out = nullptr; int32_t* iters = nullptr;   // nullable
+};
+// ... and what the avoidance variant takes beside it (handed to the kernel as it is): obs [E][M][5] (null with M = 0), the f1p_kmpc_qp_avoid
+// numbers, and the nullable outputs eps [E], planes [E][T][2][4], duals [E][2T+1]
+struct QpAvoidArgs {
+    const double* obs = nullptr;
+    int M = 0;
+    double margin = 0.0, rho = 0.0, lin = 0.0;
+    double *eps = nullptr, *planes = nullptr, *duals = nullptr;
+    QpAvoidArgs() = default;
+    QpAvoidArgs(const double* obs_, int M_, const f1p_kmpc_qp_avoid& a) : obs(obs_), M(M_), margin(a.margin), rho(a.rho), lin(a.lin) {}
+};
+// avoid null: the plain QP.  With it: T <= 31 (kinematic: 2T + 1 lanes per ego) / F1P_STMPC_QP_AVOID_MAX_T (dynamic), M in [0, 16]
+int launch_kmpc_qp(f1p_ctx* ctx, int E, const f1p_kmpc_cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid);
+int launch_stmpc_qp(f1p_ctx* ctx, int E, const f1p_stmpc_cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid);
 size_t stmpc_qp_avoid_lds_bytes(int T);
 // a plan branch's discs: d_obs [idx[k]][M][5] (the caller's ego order) -> d_out [k][M][5]
 int launch_stmpc_qp_obs_in(f1p_ctx* ctx, const double* d_obs, const int32_t* d_idx, int nb, int M, double* d_out);

@@ -334,14 +334,19 @@ void f1p_kmpc_qp_opts_default(f1p_kmpc_qp_opts* opts) {
     opts->max_iter = 50; opts->tol = 1e-10;
 }
 
-// f1p_kmpc_qp_set_avoid is on: what the plan entry points check before they launch the avoidance variant on the context's discs
-static int qp_avoid_plan_check(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, int E) {
-    if (cfg->horizon > 31) return set_error(ctx, F1P_EINVAL, "kmpc qp avoid: horizon must be <= 31 (2T + 1 inputs, one lane each)");
-    const ObsState& st = ctx->kmpc_obs;
-    if (st.cur && E != st.E)
-        return set_error(ctx, F1P_ESTATE, "kmpc obstacles were set for " + std::to_string(st.E) + " egos, this plan has " + std::to_string(E) + " (f1p_kmpc_set_obstacles)");
-    return F1P_OK;
-}
+// the kinematic QP as qp_call's model (f1p_host.h)
+struct KinQp {
+    using Cfg = f1p_kmpc_cfg;
+    static constexpr int NX = 4, DUALS = 8, AVOID_MAX_T = 31;
+    static constexpr const char *who = "kmpc", *avoid_cap = " qp avoid: horizon must be <= 31 (2T + 1 inputs, one lane each)";
+    static constexpr bool EMPTY_RETURNS = false;
+    static int validate(f1p_ctx* ctx, const Cfg* cfg, int E, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o) { return validate_kmpc_qp(ctx, cfg, E, opts, o); }
+    static int launch(f1p_ctx* ctx, int E, const Cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid) {
+        return launch_kmpc_qp(ctx, E, cfg, max_iter, tol, io, avoid);
+    }
+    static const ObsState& obs(const f1p_ctx* ctx) { return ctx->kmpc_obs; }
+    static const f1p_kmpc_qp_avoid& av(const f1p_ctx* ctx) { return ctx->kmpc_qp_av; }
+};
 
 int f1p::validate_qp_avoid(f1p_ctx* ctx, const f1p_kmpc_qp_avoid* a) {     // (f1p_stmpc_qp_avoid_* checks its numbers with it too)
     if (!(a->rho > 0) || !isfinite(a->rho) || !(a->lin >= 0) || !isfinite(a->lin) || !isfinite(a->margin))
@@ -349,47 +354,31 @@ int f1p::validate_qp_avoid(f1p_ctx* ctx, const f1p_kmpc_qp_avoid* a) {     // (f
     return F1P_OK;
 }
 
+int f1p::qp_set_avoid(f1p_ctx* ctx, f1p_kmpc_qp_avoid* state, const f1p_kmpc_qp_avoid* avoid) {
+    F1P_ENTER(ctx);
+    if (!avoid || !avoid->on) { state->on = 0; return F1P_OK; }
+    const int rc = validate_qp_avoid(ctx, avoid); if (rc) return rc;
+    *state = *avoid;
+    state->on = 1; state->pad = 0;
+    return F1P_OK;
+}
+
 int f1p_kmpc_qp_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_prev, int32_t E,
                     const f1p_kmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, double* d_steer, double* d_speed, int32_t* d_status,
                     double* d_u, double* d_xk, double* d_obj, double* d_duals, int32_t* d_iters) {
-    F1P_ENTER(ctx);
-    f1p_kmpc_qp_opts o;
-    int rc = validate_kmpc_qp(ctx, cfg, E, opts, &o); if (rc) return rc;
-    if (E > 0 && (!d_x0 || !d_ref || !d_steer || !d_speed || !d_status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
-    if (ctx->kmpc_qp_av.on) {
-        if ((rc = qp_avoid_plan_check(ctx, cfg, E))) return rc;
-        return launch_kmpc_qp_avoid(ctx, d_x0, d_ref, d_oa_prev, d_od_prev, 1, E, cfg, o.max_iter, o.tol, ctx->kmpc_obs.cur, ctx->kmpc_obs.M,
-                                    &ctx->kmpc_qp_av, d_steer, d_speed, d_status, d_u, d_xk, d_obj, d_duals, d_iters, nullptr, nullptr, nullptr,
-                                    nullptr);
-    }
-    return launch_kmpc_qp(ctx, d_x0, d_ref, d_oa_prev, d_od_prev, 1, E, cfg, o.max_iter, o.tol, d_steer, d_speed, d_status, d_u, d_xk, d_obj,
-                          d_duals, d_iters, nullptr);
+    QpIo io;
+    io.x0 = d_x0; io.ref = d_ref; io.pa = d_oa_prev; io.pd = d_od_prev;
+    io.steer = d_steer; io.speed = d_speed; io.status = d_status; io.u = d_u; io.x = d_xk; io.obj = d_obj; io.duals = d_duals; io.iters = d_iters;
+    return qp_call<KinQp>(ctx, false, E, cfg, opts, io, nullptr, nullptr);
 }
 
 int f1p_kmpc_qp_batch(f1p_ctx* ctx, const double* x0, const double* ref, const double* oa_prev, const double* od_prev, int32_t E,
                       const f1p_kmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, double* steer, double* speed, int32_t* status, double* u,
                       double* xk, double* obj, double* duals, int32_t* iters) {
-    F1P_ENTER(ctx);
-    f1p_kmpc_qp_opts o;
-    int rc = validate_kmpc_qp(ctx, cfg, E, opts, &o); if (rc) return rc;
-    if (E > 0 && (!x0 || !ref || !steer || !speed || !status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
-    const size_t T = cfg->horizon, e = E;
-    Stage s(ctx);
-    s.need(8 * 4 * e); s.need(8 * e * 4 * (T + 1)); s.need(8 * e * T, oa_prev); s.need(8 * e * T, od_prev);
-    s.need(8 * e); s.need(8 * e); s.need(4 * e); s.need(8 * e * T * 2, u); s.need(8 * e * 4 * (T + 1), xk); s.need(8 * e, obj);
-    s.need(8 * e * (8 * T - 2), duals); s.need(4 * e, iters);
-    if ((rc = s.begin())) return rc;
-    const double *d_x0, *d_ref, *d_oa, *d_od;
-    if ((rc = s.in(x0, 4 * e, &d_x0))) return rc;
-    if ((rc = s.in(ref, e * 4 * (T + 1), &d_ref))) return rc;
-    if ((rc = s.in(oa_prev, e * T, &d_oa))) return rc;
-    if ((rc = s.in(od_prev, e * T, &d_od))) return rc;
-    double* d_steer = s.out(steer, e); double* d_speed = s.out(speed, e); int32_t* d_st = s.out(status, e);
-    double* d_u = s.out(u, e * T * 2); double* d_xk = s.out(xk, e * 4 * (T + 1)); double* d_obj = s.out(obj, e);
-    double* d_du = s.out(duals, e * (8 * T - 2)); int32_t* d_it = s.out(iters, e);
-    if ((rc = launch_kmpc_qp(ctx, d_x0, d_ref, d_oa, d_od, 1, E, cfg, o.max_iter, o.tol, d_steer, d_speed, d_st, d_u, d_xk, d_obj, d_du, d_it,
-                             nullptr))) return rc;
-    return s.finish();
+    QpIo io;
+    io.x0 = x0; io.ref = ref; io.pa = oa_prev; io.pd = od_prev;
+    io.steer = steer; io.speed = speed; io.status = status; io.u = u; io.x = xk; io.obj = obj; io.duals = duals; io.iters = iters;
+    return qp_call<KinQp>(ctx, true, E, cfg, opts, io, nullptr, nullptr);
 }
 
 int f1p_kmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_kmpc_cfg* cfg, double dl, const f1p_kmpc_qp_opts* opts,
@@ -401,7 +390,7 @@ int f1p_kmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_
     if (!(dl > 0)) return set_error(ctx, F1P_EINVAL, "dl must be > 0");
     if (ctx->n_wp < 2 || !ctx->has_psi) return set_error(ctx, F1P_ESTATE, "waypoints with a heading column are required");
     if (E == 0) return F1P_OK;
-    if (ctx->kmpc_qp_av.on && (rc = qp_avoid_plan_check(ctx, cfg, E))) return rc;
+    if (ctx->kmpc_qp_av.on && (rc = qp_avoid_plan_check<KinQp>(ctx, cfg, E))) return rc;
     const size_t T = cfg->horizon, e = E;
     if ((rc = ensure_qp_warm(ctx, E, cfg->horizon))) return rc;
     Stage s(ctx);
@@ -416,13 +405,11 @@ int f1p_kmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_
     if ((rc = launch_kmpc_ref(ctx, d_x0, E, cfg->horizon, cfg->dt, dl, d_ref))) return rc;            // calc_ref_trajectory_kinematic :162-206
     const double* warm = ctx->kmpc_qp_warm_valid ? ctx->kmpc_qp_warm.as<double>() : nullptr;                   // None on the first call (:461-463)
     // (oa, od) interleaved in the warm buffer [E][T][2]: stride 2; each ego's group reads its slice before it writes it
-    if (ctx->kmpc_qp_av.on)
-        rc = launch_kmpc_qp_avoid(ctx, d_x0, d_ref, warm, warm ? warm + 1 : nullptr, 2, E, cfg, o.max_iter, o.tol, ctx->kmpc_obs.cur,
-                                  ctx->kmpc_obs.M, &ctx->kmpc_qp_av, d_steer, d_speed, d_st, d_u, nullptr, d_obj, nullptr, nullptr,
-                                  ctx->kmpc_qp_warm.as<double>(), nullptr, nullptr, nullptr);
-    else
-        rc = launch_kmpc_qp(ctx, d_x0, d_ref, warm, warm ? warm + 1 : nullptr, 2, E, cfg, o.max_iter, o.tol, d_steer, d_speed, d_st, d_u,
-                            nullptr, d_obj, nullptr, nullptr, ctx->kmpc_qp_warm.as<double>());
+    QpIo io;
+    io.x0 = d_x0; io.ref = d_ref; io.pa = warm; io.pd = warm ? warm + 1 : nullptr; io.pstride = 2;
+    io.steer = d_steer; io.speed = d_speed; io.status = d_st; io.u = d_u; io.obj = d_obj; io.warm_out = ctx->kmpc_qp_warm.as<double>();
+    const QpAvoidArgs av(ctx->kmpc_obs.cur, ctx->kmpc_obs.M, ctx->kmpc_qp_av);
+    rc = launch_kmpc_qp(ctx, E, cfg, o.max_iter, o.tol, io, ctx->kmpc_qp_av.on ? &av : nullptr);
     if (rc) return rc;
     ctx->kmpc_qp_warm_valid = true;
     return s.finish();
@@ -435,68 +422,30 @@ void f1p_kmpc_qp_avoid_default(f1p_kmpc_qp_avoid* avoid) {
     avoid->margin = 0.0; avoid->rho = 1e4; avoid->lin = 10.0;
 }
 
-int f1p_kmpc_qp_set_avoid(f1p_ctx* ctx, const f1p_kmpc_qp_avoid* avoid) {
-    F1P_ENTER(ctx);
-    if (!avoid || !avoid->on) { ctx->kmpc_qp_av.on = 0; return F1P_OK; }
-    const int rc = validate_qp_avoid(ctx, avoid); if (rc) return rc;
-    ctx->kmpc_qp_av = *avoid;
-    ctx->kmpc_qp_av.on = 1; ctx->kmpc_qp_av.pad = 0;
-    return F1P_OK;
-}
-
-// the checks of the two stateless entry points -> *a (avoid, or the defaults)
-static int validate_qp_avoid_call(f1p_ctx* ctx, const f1p_kmpc_cfg* cfg, int E, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o, const void* obs,
-                                  int M, const f1p_kmpc_qp_avoid* avoid, f1p_kmpc_qp_avoid* a) {
-    int rc = validate_kmpc_qp(ctx, cfg, E, opts, o); if (rc) return rc;
-    if (cfg->horizon > 31) return set_error(ctx, F1P_EINVAL, "kmpc qp avoid: horizon must be <= 31 (2T + 1 inputs, one lane each)");
-    if (M < 1 || M > F1P_KMPC_MAX_OBS) return set_error(ctx, F1P_EINVAL, "kmpc qp avoid: M must be in [1, 16]");
-    if (E > 0 && !obs) return set_error(ctx, F1P_EINVAL, "kmpc qp avoid: obs is NULL");
-    f1p_kmpc_qp_avoid_default(a);
-    if (avoid) *a = *avoid;
-    return validate_qp_avoid(ctx, a);
-}
+int f1p_kmpc_qp_set_avoid(f1p_ctx* ctx, const f1p_kmpc_qp_avoid* avoid) { return qp_set_avoid(ctx, ctx ? &ctx->kmpc_qp_av : nullptr, avoid); }
 
 int f1p_kmpc_qp_avoid_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_prev, int32_t E,
                           const f1p_kmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* d_obs, int32_t M,
                           const f1p_kmpc_qp_avoid* avoid, double* d_steer, double* d_speed, int32_t* d_status, double* d_u, double* d_xk,
                           double* d_obj, double* d_duals, int32_t* d_iters, double* d_eps, double* d_planes, double* d_avoid_duals) {
-    F1P_ENTER(ctx);
-    f1p_kmpc_qp_opts o;
-    f1p_kmpc_qp_avoid a;
-    int rc = validate_qp_avoid_call(ctx, cfg, E, opts, &o, d_obs, M, avoid, &a); if (rc) return rc;
-    if (E > 0 && (!d_x0 || !d_ref || !d_steer || !d_speed || !d_status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
-    return launch_kmpc_qp_avoid(ctx, d_x0, d_ref, d_oa_prev, d_od_prev, 1, E, cfg, o.max_iter, o.tol, d_obs, M, &a, d_steer, d_speed, d_status,
-                                d_u, d_xk, d_obj, d_duals, d_iters, nullptr, d_eps, d_planes, d_avoid_duals);
+    QpIo io;
+    io.x0 = d_x0; io.ref = d_ref; io.pa = d_oa_prev; io.pd = d_od_prev;
+    io.steer = d_steer; io.speed = d_speed; io.status = d_status; io.u = d_u; io.x = d_xk; io.obj = d_obj; io.duals = d_duals; io.iters = d_iters;
+    QpAvoidArgs av;
+    av.obs = d_obs; av.M = M; av.eps = d_eps; av.planes = d_planes; av.duals = d_avoid_duals;
+    return qp_call<KinQp>(ctx, false, E, cfg, opts, io, &av, avoid);
 }
 
 int f1p_kmpc_qp_avoid_batch(f1p_ctx* ctx, const double* x0, const double* ref, const double* oa_prev, const double* od_prev, int32_t E,
                             const f1p_kmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* obs, int32_t M,
                             const f1p_kmpc_qp_avoid* avoid, double* steer, double* speed, int32_t* status, double* u, double* xk,
                             double* obj, double* duals, int32_t* iters, double* eps, double* planes, double* avoid_duals) {
-    F1P_ENTER(ctx);
-    f1p_kmpc_qp_opts o;
-    f1p_kmpc_qp_avoid a;
-    int rc = validate_qp_avoid_call(ctx, cfg, E, opts, &o, obs, M, avoid, &a); if (rc) return rc;
-    if (E > 0 && (!x0 || !ref || !steer || !speed || !status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
-    const size_t T = cfg->horizon, e = E, m = M;
-    Stage s(ctx);
-    s.need(8 * 4 * e); s.need(8 * e * 4 * (T + 1)); s.need(8 * e * T, oa_prev); s.need(8 * e * T, od_prev); s.need(8 * e * m * 5);
-    s.need(8 * e); s.need(8 * e); s.need(4 * e); s.need(8 * e * T * 2, u); s.need(8 * e * 4 * (T + 1), xk); s.need(8 * e, obj);
-    s.need(8 * e * (8 * T - 2), duals); s.need(4 * e, iters); s.need(8 * e, eps); s.need(8 * e * T * 8, planes); s.need(8 * e * (2 * T + 1), avoid_duals);
-    if ((rc = s.begin())) return rc;
-    const double *d_x0, *d_ref, *d_oa, *d_od, *d_obs;
-    if ((rc = s.in(x0, 4 * e, &d_x0))) return rc;
-    if ((rc = s.in(ref, e * 4 * (T + 1), &d_ref))) return rc;
-    if ((rc = s.in(oa_prev, e * T, &d_oa))) return rc;
-    if ((rc = s.in(od_prev, e * T, &d_od))) return rc;
-    if ((rc = s.in(obs, e * m * 5, &d_obs))) return rc;
-    double* d_steer = s.out(steer, e); double* d_speed = s.out(speed, e); int32_t* d_st = s.out(status, e);
-    double* d_u = s.out(u, e * T * 2); double* d_xk = s.out(xk, e * 4 * (T + 1)); double* d_obj = s.out(obj, e);
-    double* d_du = s.out(duals, e * (8 * T - 2)); int32_t* d_it = s.out(iters, e);
-    double* d_eps = s.out(eps, e); double* d_pl = s.out(planes, e * T * 8); double* d_ad = s.out(avoid_duals, e * (2 * T + 1));
-    if ((rc = launch_kmpc_qp_avoid(ctx, d_x0, d_ref, d_oa, d_od, 1, E, cfg, o.max_iter, o.tol, d_obs, M, &a, d_steer, d_speed, d_st, d_u, d_xk,
-                                   d_obj, d_du, d_it, nullptr, d_eps, d_pl, d_ad))) return rc;
-    return s.finish();
+    QpIo io;
+    io.x0 = x0; io.ref = ref; io.pa = oa_prev; io.pd = od_prev;
+    io.steer = steer; io.speed = speed; io.status = status; io.u = u; io.x = xk; io.obj = obj; io.duals = duals; io.iters = iters;
+    QpAvoidArgs av;
+    av.obs = obs; av.M = M; av.eps = eps; av.planes = planes; av.duals = avoid_duals;
+    return qp_call<KinQp>(ctx, true, E, cfg, opts, io, &av, avoid);
 }
 
 int f1p_kmpc_qp_warm_reset(f1p_ctx* ctx) {

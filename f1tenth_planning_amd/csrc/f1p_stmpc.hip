@@ -209,128 +209,64 @@ static int validate_stmpc_qp(f1p_ctx* ctx, const f1p_stmpc_cfg* cfg, int E, cons
     return qp_opts(ctx, opts, o, "stmpc qp");
 }
 
-// f1p_stmpc_qp_set_avoid is on: what the QP entry points check before they launch the avoidance variants on the context's discs
-// (kcfg: the plan's kinematic branch, which runs k_kmpc_qp's variant; E: the caller's ego count, the order the discs are held in)
-static int stqp_avoid_plan_check(f1p_ctx* ctx, const f1p_stmpc_cfg* cfg, const f1p_kmpc_cfg* kcfg, int E) {
-    if (cfg->horizon > F1P_STMPC_QP_AVOID_MAX_T)
-        return set_error(ctx, F1P_EINVAL, "stmpc qp avoid: horizon must be <= F1P_STMPC_QP_AVOID_MAX_T (40: the packed avoidance rows beside H and the Newton matrix in LDS)");
-    if (kcfg && kcfg->horizon > 31) return set_error(ctx, F1P_EINVAL, "stmpc qp avoid: the kinematic branch's horizon must be <= 31 (2TK + 1 inputs, one lane each)");
-    const ObsState& st = ctx->stmpc_obs;
-    if (st.cur && E != st.E)
-        return set_error(ctx, F1P_ESTATE, "stmpc obstacles were set for " + std::to_string(st.E) + " egos, this plan has " + std::to_string(E) + " (f1p_stmpc_set_obstacles)");
-    return F1P_OK;
-}
+// the dynamic QP as qp_call's model (f1p_host.h)
+struct DynQp {
+    using Cfg = f1p_stmpc_cfg;
+    static constexpr int NX = 7, DUALS = 10, AVOID_MAX_T = F1P_STMPC_QP_AVOID_MAX_T;
+    static constexpr const char *who = "stmpc", *avoid_cap = " qp avoid: horizon must be <= F1P_STMPC_QP_AVOID_MAX_T (40: the packed avoidance rows beside H and the Newton matrix in LDS)";
+    static constexpr bool EMPTY_RETURNS = true;
+    static int validate(f1p_ctx* ctx, const Cfg* cfg, int E, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o) { return validate_stmpc_qp(ctx, cfg, E, opts, o); }
+    static int launch(f1p_ctx* ctx, int E, const Cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid) {
+        return launch_stmpc_qp(ctx, E, cfg, max_iter, tol, io, avoid);
+    }
+    static const ObsState& obs(const f1p_ctx* ctx) { return ctx->stmpc_obs; }
+    static const f1p_kmpc_qp_avoid& av(const f1p_ctx* ctx) { return ctx->stmpc_qp_av; }
+};
 
 int64_t f1p_stmpc_qp_avoid_lds_bytes(int32_t horizon) { return horizon < 2 ? -1 : (int64_t)stmpc_qp_avoid_lds_bytes(horizon); }
 
-int f1p_stmpc_qp_set_avoid(f1p_ctx* ctx, const f1p_kmpc_qp_avoid* avoid) {
-    F1P_ENTER(ctx);
-    if (!avoid || !avoid->on) { ctx->stmpc_qp_av.on = 0; return F1P_OK; }
-    const int rc = validate_qp_avoid(ctx, avoid); if (rc) return rc;
-    ctx->stmpc_qp_av = *avoid;
-    ctx->stmpc_qp_av.on = 1; ctx->stmpc_qp_av.pad = 0;
-    return F1P_OK;
-}
-
-// the checks of the two stateless avoidance entry points -> *a (avoid, or the defaults)
-static int validate_stqp_avoid_call(f1p_ctx* ctx, const f1p_stmpc_cfg* cfg, int E, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o, const void* obs,
-                                    int M, const f1p_kmpc_qp_avoid* avoid, f1p_kmpc_qp_avoid* a) {
-    int rc = validate_stmpc_qp(ctx, cfg, E, opts, o); if (rc) return rc;
-    if (cfg->horizon > F1P_STMPC_QP_AVOID_MAX_T)
-        return set_error(ctx, F1P_EINVAL, "stmpc qp avoid: horizon must be <= F1P_STMPC_QP_AVOID_MAX_T (40: the packed avoidance rows beside H and the Newton matrix in LDS)");
-    if (M < 1 || M > F1P_KMPC_MAX_OBS) return set_error(ctx, F1P_EINVAL, "stmpc qp avoid: M must be in [1, 16]");
-    if (E > 0 && !obs) return set_error(ctx, F1P_EINVAL, "stmpc qp avoid: obs is NULL");
-    f1p_kmpc_qp_avoid_default(a);
-    if (avoid) *a = *avoid;
-    return validate_qp_avoid(ctx, a);
-}
+int f1p_stmpc_qp_set_avoid(f1p_ctx* ctx, const f1p_kmpc_qp_avoid* avoid) { return qp_set_avoid(ctx, ctx ? &ctx->stmpc_qp_av : nullptr, avoid); }
 
 int f1p_stmpc_qp_avoid_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_v_prev,
                            int32_t E, const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* d_obs, int32_t M,
                            const f1p_kmpc_qp_avoid* avoid, double* d_steer, double* d_speed, int32_t* d_status, double* d_u, double* d_x,
                            double* d_obj, double* d_duals, int32_t* d_iters, double* d_eps, double* d_planes, double* d_avoid_duals) {
-    F1P_ENTER(ctx);
-    f1p_kmpc_qp_opts o;
-    f1p_kmpc_qp_avoid a;
-    int rc = validate_stqp_avoid_call(ctx, cfg, E, opts, &o, d_obs, M, avoid, &a); if (rc) return rc;
-    if (E > 0 && (!d_x0 || !d_ref || !d_steer || !d_speed || !d_status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
-    return launch_stmpc_qp_avoid(ctx, d_x0, d_ref, d_oa_prev, d_od_v_prev, 1, E, cfg, o.max_iter, o.tol, d_obs, M, &a, d_steer, d_speed, d_status,
-                                 d_u, d_x, d_obj, d_duals, d_iters, nullptr, d_eps, d_planes, d_avoid_duals);
+    QpIo io;
+    io.x0 = d_x0; io.ref = d_ref; io.pa = d_oa_prev; io.pd = d_od_v_prev;
+    io.steer = d_steer; io.speed = d_speed; io.status = d_status; io.u = d_u; io.x = d_x; io.obj = d_obj; io.duals = d_duals; io.iters = d_iters;
+    QpAvoidArgs av;
+    av.obs = d_obs; av.M = M; av.eps = d_eps; av.planes = d_planes; av.duals = d_avoid_duals;
+    return qp_call<DynQp>(ctx, false, E, cfg, opts, io, &av, avoid);
 }
 
 int f1p_stmpc_qp_avoid_batch(f1p_ctx* ctx, const double* x0, const double* ref, const double* oa_prev, const double* od_v_prev, int32_t E,
                              const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* obs, int32_t M,
                              const f1p_kmpc_qp_avoid* avoid, double* steer, double* speed, int32_t* status, double* u, double* x,
                              double* obj, double* duals, int32_t* iters, double* eps, double* planes, double* avoid_duals) {
-    F1P_ENTER(ctx);
-    f1p_kmpc_qp_opts o;
-    f1p_kmpc_qp_avoid a;
-    int rc = validate_stqp_avoid_call(ctx, cfg, E, opts, &o, obs, M, avoid, &a); if (rc) return rc;
-    if (E > 0 && (!x0 || !ref || !steer || !speed || !status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
-    if (E == 0) return F1P_OK;
-    const size_t T = cfg->horizon, e = E, m = M;
-    Stage s(ctx);
-    s.need(8 * 7 * e); s.need(8 * e * 7 * (T + 1)); s.need(8 * e * T, oa_prev); s.need(8 * e * T, od_v_prev); s.need(8 * e * m * 5);
-    s.need(8 * e); s.need(8 * e); s.need(4 * e); s.need(8 * e * T * 2, u); s.need(8 * e * 7 * (T + 1), x); s.need(8 * e, obj);
-    s.need(8 * e * (10 * T - 2), duals); s.need(4 * e, iters); s.need(8 * e, eps); s.need(8 * e * T * 8, planes); s.need(8 * e * (2 * T + 1), avoid_duals);
-    if ((rc = s.begin())) return rc;
-    const double *d_x0, *d_ref, *d_oa, *d_od, *d_obs;
-    if ((rc = s.in(x0, 7 * e, &d_x0))) return rc;
-    if ((rc = s.in(ref, e * 7 * (T + 1), &d_ref))) return rc;
-    if ((rc = s.in(oa_prev, e * T, &d_oa))) return rc;
-    if ((rc = s.in(od_v_prev, e * T, &d_od))) return rc;
-    if ((rc = s.in(obs, e * m * 5, &d_obs))) return rc;
-    double* d_steer = s.out(steer, e); double* d_speed = s.out(speed, e); int32_t* d_st = s.out(status, e);
-    double* d_u = s.out(u, e * T * 2); double* d_x = s.out(x, e * 7 * (T + 1)); double* d_obj = s.out(obj, e);
-    double* d_du = s.out(duals, e * (10 * T - 2)); int32_t* d_it = s.out(iters, e);
-    double* d_eps = s.out(eps, e); double* d_pl = s.out(planes, e * T * 8); double* d_ad = s.out(avoid_duals, e * (2 * T + 1));
-    if ((rc = launch_stmpc_qp_avoid(ctx, d_x0, d_ref, d_oa, d_od, 1, E, cfg, o.max_iter, o.tol, d_obs, M, &a, d_steer, d_speed, d_st, d_u, d_x,
-                                    d_obj, d_du, d_it, nullptr, d_eps, d_pl, d_ad))) return rc;
-    return s.finish();
+    QpIo io;
+    io.x0 = x0; io.ref = ref; io.pa = oa_prev; io.pd = od_v_prev;
+    io.steer = steer; io.speed = speed; io.status = status; io.u = u; io.x = x; io.obj = obj; io.duals = duals; io.iters = iters;
+    QpAvoidArgs av;
+    av.obs = obs; av.M = M; av.eps = eps; av.planes = planes; av.duals = avoid_duals;
+    return qp_call<DynQp>(ctx, true, E, cfg, opts, io, &av, avoid);
 }
 
 int f1p_stmpc_qp_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_v_prev, int32_t E,
                      const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, double* d_steer, double* d_speed, int32_t* d_status,
                      double* d_u, double* d_x, double* d_obj, double* d_duals, int32_t* d_iters) {
-    F1P_ENTER(ctx);
-    f1p_kmpc_qp_opts o;
-    int rc = validate_stmpc_qp(ctx, cfg, E, opts, &o); if (rc) return rc;
-    if (E > 0 && (!d_x0 || !d_ref || !d_steer || !d_speed || !d_status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
-    if (ctx->stmpc_qp_av.on) {
-        if ((rc = stqp_avoid_plan_check(ctx, cfg, nullptr, E))) return rc;
-        return launch_stmpc_qp_avoid(ctx, d_x0, d_ref, d_oa_prev, d_od_v_prev, 1, E, cfg, o.max_iter, o.tol, ctx->stmpc_obs.cur, ctx->stmpc_obs.M,
-                                     &ctx->stmpc_qp_av, d_steer, d_speed, d_status, d_u, d_x, d_obj, d_duals, d_iters, nullptr, nullptr, nullptr,
-                                     nullptr);
-    }
-    return launch_stmpc_qp(ctx, d_x0, d_ref, d_oa_prev, d_od_v_prev, 1, E, cfg, o.max_iter, o.tol, d_steer, d_speed, d_status, d_u, d_x,
-                           d_obj, d_duals, d_iters, nullptr);
+    QpIo io;
+    io.x0 = d_x0; io.ref = d_ref; io.pa = d_oa_prev; io.pd = d_od_v_prev;
+    io.steer = d_steer; io.speed = d_speed; io.status = d_status; io.u = d_u; io.x = d_x; io.obj = d_obj; io.duals = d_duals; io.iters = d_iters;
+    return qp_call<DynQp>(ctx, false, E, cfg, opts, io, nullptr, nullptr);
 }
 
 int f1p_stmpc_qp_batch(f1p_ctx* ctx, const double* x0, const double* ref, const double* oa_prev, const double* od_v_prev, int32_t E,
                        const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, double* steer, double* speed, int32_t* status, double* u,
                        double* x, double* obj, double* duals, int32_t* iters) {
-    F1P_ENTER(ctx);
-    f1p_kmpc_qp_opts o;
-    int rc = validate_stmpc_qp(ctx, cfg, E, opts, &o); if (rc) return rc;
-    if (E > 0 && (!x0 || !ref || !steer || !speed || !status)) return set_error(ctx, F1P_EINVAL, "x0, ref, steer, speed and status are required");
-    if (E == 0) return F1P_OK;
-    const size_t T = cfg->horizon, e = E;
-    Stage s(ctx);
-    s.need(8 * 7 * e); s.need(8 * e * 7 * (T + 1)); s.need(8 * e * T, oa_prev); s.need(8 * e * T, od_v_prev);
-    s.need(8 * e); s.need(8 * e); s.need(4 * e); s.need(8 * e * T * 2, u); s.need(8 * e * 7 * (T + 1), x); s.need(8 * e, obj);
-    s.need(8 * e * (10 * T - 2), duals); s.need(4 * e, iters);
-    if ((rc = s.begin())) return rc;
-    const double *d_x0, *d_ref, *d_oa, *d_od;
-    if ((rc = s.in(x0, 7 * e, &d_x0))) return rc;
-    if ((rc = s.in(ref, e * 7 * (T + 1), &d_ref))) return rc;
-    if ((rc = s.in(oa_prev, e * T, &d_oa))) return rc;
-    if ((rc = s.in(od_v_prev, e * T, &d_od))) return rc;
-    double* d_steer = s.out(steer, e); double* d_speed = s.out(speed, e); int32_t* d_st = s.out(status, e);
-    double* d_u = s.out(u, e * T * 2); double* d_x = s.out(x, e * 7 * (T + 1)); double* d_obj = s.out(obj, e);
-    double* d_du = s.out(duals, e * (10 * T - 2)); int32_t* d_it = s.out(iters, e);
-    if ((rc = launch_stmpc_qp(ctx, d_x0, d_ref, d_oa, d_od, 1, E, cfg, o.max_iter, o.tol, d_steer, d_speed, d_st, d_u, d_x, d_obj, d_du, d_it,
-                              nullptr))) return rc;
-    return s.finish();
+    QpIo io;
+    io.x0 = x0; io.ref = ref; io.pa = oa_prev; io.pd = od_v_prev;
+    io.steer = steer; io.speed = speed; io.status = status; io.u = u; io.x = x; io.obj = obj; io.duals = duals; io.iters = iters;
+    return qp_call<DynQp>(ctx, true, E, cfg, opts, io, nullptr, nullptr);
 }
 
 // the ctx's plan warm start for (E, W); a change of shape drops the old contents (every length back to 0 = None)
@@ -361,7 +297,7 @@ static int stmpc_qp_plan_impl(f1p_ctx* ctx, const double* x0, const int32_t* tra
     }
     if (E == 0) return F1P_OK;
     const bool av = ctx->stmpc_qp_av.on != 0;
-    if (av && (rc = stqp_avoid_plan_check(ctx, dcfg, kcfg, E))) return rc;
+    if (av && (rc = qp_avoid_plan_check<DynQp>(ctx, dcfg, E, kcfg))) return rc;
     const double* d_obs_all = av ? ctx->stmpc_obs.cur : nullptr;              // [E][M][5] in the caller's order, or none held
     const int Mo = d_obs_all ? ctx->stmpc_obs.M : 0;
     const int T = dcfg->horizon, TK = kcfg->horizon, W = T;                   // W = max(T, TK)
@@ -395,22 +331,22 @@ static int stmpc_qp_plan_impl(f1p_ctx* ctx, const double* x0, const int32_t* tra
         if ((rc = launch_stmpc_qp_warm_in(ctx, d_warm, sp.d_idx[b], d_use, nb, Tb, W, d_win))) return rc;
         // this branch's egos are written contiguously from offset 0 of its own slice: kinematic egos after the dynamic ones
         const size_t off = b ? 0 : nd;
-        if (av) {                                                             // this branch's discs, gathered on the device; each branch its own variant
-            double* d_obs = nullptr;
-            if (Mo) {
-                d_obs = (double*)arena_take(ctx, 8 * 5 * (size_t)Mo * nb);
-                if ((rc = launch_stmpc_qp_obs_in(ctx, d_obs_all, sp.d_idx[b], nb, Mo, d_obs))) return rc;
-            }
-            if (b) rc = launch_stmpc_qp_avoid(ctx, sp.d_x7, sp.d_ref7[1], d_win, d_win + 1, 2, nb, dcfg, o.max_iter, o.tol, d_obs, Mo, &ctx->stmpc_qp_av,
-                                              d_steer + off, d_speed + off, d_st + off, nullptr, nullptr, d_obj + off, nullptr, nullptr, d_wout[b],
-                                              nullptr, nullptr, nullptr);
-            else rc = launch_kmpc_qp_avoid(ctx, sp.d_s4[0], sp.d_ref4, d_win, d_win + 1, 2, nb, kcfg, ok_.max_iter, ok_.tol, d_obs, Mo, &ctx->stmpc_qp_av,
-                                           d_steer + off, d_speed + off, d_st + off, nullptr, nullptr, d_obj + off, nullptr, nullptr, d_wout[b],
-                                           nullptr, nullptr, nullptr);
-        } else if (b) rc = launch_stmpc_qp(ctx, sp.d_x7, sp.d_ref7[1], d_win, d_win + 1, 2, nb, dcfg, o.max_iter, o.tol, d_steer + off, d_speed + off, d_st + off,
-                                    nullptr, nullptr, d_obj + off, nullptr, nullptr, d_wout[b]);
-        else rc = launch_kmpc_qp(ctx, sp.d_s4[0], sp.d_ref4, d_win, d_win + 1, 2, nb, kcfg, ok_.max_iter, ok_.tol, d_steer + off, d_speed + off, d_st + off,
-                                 nullptr, nullptr, d_obj + off, nullptr, nullptr, d_wout[b]);
+        QpIo q;
+        q.pa = d_win; q.pd = d_win + 1; q.pstride = 2;
+        q.steer = d_steer + off; q.speed = d_speed + off; q.status = d_st + off; q.obj = d_obj + off; q.warm_out = d_wout[b];
+        QpAvoidArgs qa(nullptr, Mo, ctx->stmpc_qp_av);
+        if (av && Mo) {                                                       // this branch's discs, gathered on the device; each branch its own variant
+            double* d_obs = (double*)arena_take(ctx, 8 * 5 * (size_t)Mo * nb);
+            if ((rc = launch_stmpc_qp_obs_in(ctx, d_obs_all, sp.d_idx[b], nb, Mo, d_obs))) return rc;
+            qa.obs = d_obs;
+        }
+        if (b) {
+            q.x0 = sp.d_x7; q.ref = sp.d_ref7[1];
+            rc = launch_stmpc_qp(ctx, nb, dcfg, o.max_iter, o.tol, q, av ? &qa : nullptr);
+        } else {
+            q.x0 = sp.d_s4[0]; q.ref = sp.d_ref4;
+            rc = launch_kmpc_qp(ctx, nb, kcfg, ok_.max_iter, ok_.tol, q, av ? &qa : nullptr);
+        }
         if (rc) return rc;
         if ((rc = launch_stmpc_qp_warm_out(ctx, d_wout[b], sp.d_idx[b], nb, Tb, W, d_warm))) return rc;
     }

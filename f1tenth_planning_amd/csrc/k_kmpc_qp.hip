@@ -21,45 +21,21 @@
 // the least clearance at the linearisation path's point pbar_t give half-planes  -n.(S_xy(t) u) - eps <= n.(s_xy(t) - c) - (r + margin);
 // step t's first row is the fifth row of lane 2(t-1) (a_{t-1}), its second that of lane 2(t-1)+1 (delta_{t-1}), the eps lane's fifth row
 // is -eps <= 0.  The rows' u-coefficients are dense: kept in LDS (A, one row per lane, odd stride) before S becomes the Newton matrix.
-#include "qp_ipm.h"
+// The disc load, the choice of the two discs, the half-plane and its `planes` record are qp_avoid.h's, shared with k_stmpc_qp.hip.
+#include "qp_avoid.h"
 
 namespace f1p {
 
 namespace {
 
-// doubles of LDS per ego
-__host__ __device__ inline int qp_lds_doubles(int T) {
-    const int n = 2 * T, Tp = T + 1;
-    return 4 * Tp * n + n * n + 3 * n + T + 4 + 8 * Tp + 6 * T;
-}
-// ... of the avoidance variant: H, U, W, Y over nq = n + 1 inputs; the rows A [n][nq], WA [nq], pbar (x, y, yaw) [T] each, the discs
-__host__ __device__ inline int qp_lds_doubles_av(int T) {
-    const int n = 2 * T, Tp = T + 1, nq = n + 1;
-    return 4 * Tp * n + nq * nq + 3 * nq + T + 4 + 8 * Tp + 6 * T + n * nq + nq + 3 * T + 5 * F1P_KMPC_MAX_OBS;
-}
-
-struct QpLds {
-    double *S, *M, *H, *U, *W, *Y, *SUF, *x0, *ref, *fr, *vb, *pb, *cp, *sp, *pa, *pd;
-    __device__ QpLds(double* b, int T) {
-        const int n = 2 * T, Tp = T + 1;
-        S = b; M = b; b += 4 * Tp * n;             // S until H and g are formed, then the Newton matrix (n * n <= 4 (T+1) n)
-        H = b; b += n * n;
-        U = b; b += n; W = b; b += n; Y = b; b += n;
-        SUF = b; b += T;
-        x0 = b; b += 4;
-        ref = b; b += 4 * Tp;
-        fr = b; b += 4 * Tp;
-        vb = b; b += T; pb = b; b += T; cp = b; b += T; sp = b; b += T; pa = b; b += T; pd = b; b += T;
-    }
-};
-
-// the avoidance variant's: nq = n + 1 inputs (H, U, W, Y; (n + 1)^2 <= 4 (T+1) n still), and the avoidance rows A [n][nq] (odd stride: a lane
-// per row reads conflict-free), their published w / D WA [nq], pbar_1..T (x, y, yaw), the discs [16][5]
-struct QpLdsAv : QpLds {
-    double *A, *WA, *px, *py, *pw, *ob;
-    __device__ QpLdsAv(double* b, int T) : QpLds(b, T) {
-        const int n = 2 * T, Tp = T + 1, nq = n + 1;
-        S = b; M = b; b += 4 * Tp * n;
+// One ego's LDS, carved from b in doubles: the kernel's pointers (P = double*), or with P = int from 0 the members' offsets, `end` the
+// size.  extra: the QP's inputs beyond u (nq = n + extra; AV: the slack).
+template <class P>
+struct QpLdsT {
+    P S{}, M{}, H{}, U{}, W{}, Y{}, SUF{}, x0{}, ref{}, fr{}, vb{}, pb{}, cp{}, sp{}, pa{}, pd{}, end{};
+    __host__ __device__ constexpr QpLdsT(P b, int T, int extra = 0) {
+        const int n = 2 * T, Tp = T + 1, nq = n + extra;
+        S = b; M = b; b += 4 * Tp * n;             // S until H and g are formed, then the Newton matrix (nq * nq <= 4 (T+1) n)
         H = b; b += nq * nq;
         U = b; b += nq; W = b; b += nq; Y = b; b += nq;
         SUF = b; b += T;
@@ -67,26 +43,31 @@ struct QpLdsAv : QpLds {
         ref = b; b += 4 * Tp;
         fr = b; b += 4 * Tp;
         vb = b; b += T; pb = b; b += T; cp = b; b += T; sp = b; b += T; pa = b; b += T; pd = b; b += T;
+        end = b;
+    }
+};
+// the avoidance variant's: nq = n + 1 inputs, and behind the common members the avoidance rows A [n][nq] (odd stride: a lane per row reads
+// conflict-free), their published w / D WA [nq], pbar_1..T (x, y, yaw), the discs [16][5]
+template <class P>
+struct QpLdsAvT : QpLdsT<P> {
+    P A{}, WA{}, px{}, py{}, pw{}, ob{};
+    __host__ __device__ constexpr QpLdsAvT(P b, int T) : QpLdsT<P>(b, T, 1) {
+        const int n = 2 * T, nq = n + 1;
+        b = this->end;
         A = b; b += n * nq;
         WA = b; b += nq;
         px = b; b += T; py = b; b += T; pw = b; b += T;
-        ob = b;
+        ob = b; b += 5 * F1P_KMPC_MAX_OBS;
+        this->end = b;
     }
 };
-
-// the avoidance variant's arguments: obs [E][M][5] (nullable with M = 0), the f1p_kmpc_qp_avoid numbers, and its outputs (nullable)
-struct QpAvoidArgs {
-    const double* obs;
-    int M;
-    double margin, rho, lin;
-    double *eps, *planes, *duals;
-};
-__device__ __forceinline__ QpAvoidArgs qp_avoid_args() { return QpAvoidArgs{}; }
-__device__ __forceinline__ QpAvoidArgs qp_avoid_args(const QpAvoidArgs& a) { return a; }
+template <bool AV> using QpLds = std::conditional_t<AV, QpLdsAvT<double*>, QpLdsT<double*>>;
+// doubles of LDS per ego
+__host__ __device__ constexpr int qp_lds_doubles(int T, bool av) { return av ? QpLdsAvT<int>(0, T).end : QpLdsT<int>(0, T).end; }
 
 }  // namespace
 
-// AvArgs: none (the plain QP), or one QpAvoidArgs (AV)
+// AvArgs: none (the plain QP), or one QpAvoidArgs (AV; f1p_internal.h)
 template <int G, class... AvArgs>
 __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, const double* __restrict__ refg,
                                                 const double* pa_g, const double* pd_g, int pstride, int E, f1p_kmpc_cfg cfg,
@@ -104,7 +85,7 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
     const int grp = threadIdx.x / G, i = threadIdx.x % G;
     const int e = blockIdx.x * EPW + grp;
     const bool ego = e < E;
-    std::conditional_t<AV, QpLdsAv, QpLds> L(reinterpret_cast<double*>(lds_raw) + (size_t)grp * (AV ? qp_lds_doubles_av(T) : qp_lds_doubles(T)), T);
+    QpLds<AV> L(reinterpret_cast<double*>(lds_raw) + (size_t)grp * qp_lds_doubles(T, AV), T);
     const int tau = i >> 1, j = i & 1;
     const bool in_n = i < n;
     const double DTK = cfg.dt;
@@ -120,15 +101,7 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
             const double d = pd_g ? pd_g[((size_t)e * T + k) * pstride] : 0.0;
             L.pa[k] = a; L.pd[k] = d; bad |= !(isfinite(a) && isfinite(d));
         }
-        if constexpr (AV) {
-            for (int m = i; m < av.M; m += G) {                // a live slot (r >= 0) must be finite; an empty one is kept as r = -1
-                const double* o = av.obs + ((size_t)e * av.M + m) * 5;
-                const double ox = o[0], oy = o[1], ovx = o[2], ovy = o[3], r = o[4];
-                const bool live = r >= 0.0;
-                L.ob[5 * m] = ox; L.ob[5 * m + 1] = oy; L.ob[5 * m + 2] = ovx; L.ob[5 * m + 3] = ovy; L.ob[5 * m + 4] = live ? r : -1.0;
-                bad |= live && !(isfinite(ox) && isfinite(oy) && isfinite(ovx) && isfinite(ovy) && isfinite(r));
-            }
-        }
+        if constexpr (AV) bad |= qp_avoid_load<G>(av, e, i, L.ob);
     }
     bad = gmax<G>(bad ? 1.0 : 0.0) > 0.0;
     __syncthreads();
@@ -195,39 +168,16 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
         if constexpr (AV) L.H[i * nq + n] = 0.0;
     }
     // AV: this lane's half-plane (step tau + 1, the j-th nearest live disc), its row of A, and the eps lane's row of H
-    double pl_nx = 0.0, pl_ny = 0.0, pl_h = 0.0;
-    int pl_slot = -1;
+    [[maybe_unused]] QpPlane pl;
     if constexpr (AV) {
         if (in_n && !done) {
             const int t = tau + 1;
             const double tt = (double)t * DTK, px = L.px[tau], py = L.py[tau];
-            double c0 = INFINITY, c1 = INFINITY;
-            int m0 = -1, m1 = -1;
-            for (int m = 0; m < av.M; ++m) {               // the two least clearances, ties to the lower slot
-                const double r = L.ob[5 * m + 4];
-                if (!(r >= 0.0)) continue;
-                const double dx = px - (L.ob[5 * m] + L.ob[5 * m + 2] * tt), dy = py - (L.ob[5 * m + 1] + L.ob[5 * m + 3] * tt);
-                const double clear = sqrt(dx * dx + dy * dy) - r;
-                if (clear < c0) { c1 = c0; m1 = m0; c0 = clear; m0 = m; }
-                else if (clear < c1) { c1 = clear; m1 = m; }
-            }
-            const int ms = j == 0 ? m0 : m1;
-            if (ms >= 0) {
-                const double r = L.ob[5 * ms + 4];
-                const double cx = L.ob[5 * ms] + L.ob[5 * ms + 2] * tt, cy = L.ob[5 * ms + 1] + L.ob[5 * ms + 3] * tt;
-                const double dx = px - cx, dy = py - cy, dist = sqrt(dx * dx + dy * dy);
-                if (dist < 1e-9) {                           // on the disc's centre: stay behind it
-                    double sn, cs;
-                    sincos(L.pw[tau], &sn, &cs);
-                    pl_nx = -cs; pl_ny = -sn;
-                } else {
-                    pl_nx = dx / dist; pl_ny = dy / dist;
-                }
-                pl_h = pl_nx * (L.fr[t] - cx) + pl_ny * (L.fr[Tp + t] - cy) - (r + av.margin);
-                pl_slot = ms;
-            }
+            const QpNearest nr = qp_avoid_nearest(L.ob, av.M, px, py, tt);
+            const int ms = j == 0 ? nr.m0 : nr.m1;
+            if (ms >= 0) pl = qp_avoid_plane(L.ob, ms, px, py, L.pw[tau], tt, L.fr[t], L.fr[Tp + t], av.margin);
             for (int c = 0; c < n; ++c)
-                L.A[i * nq + c] = pl_slot >= 0 ? -(pl_nx * L.S[(4 * t + 0) * n + c] + pl_ny * L.S[(4 * t + 1) * n + c]) : 0.0;
+                L.A[i * nq + c] = pl.slot >= 0 ? -(pl.nx * L.S[(4 * t + 0) * n + c] + pl.ny * L.S[(4 * t + 1) * n + c]) : 0.0;
         }
         if (i == n && !done) {
             for (int c = 0; c < n; ++c) L.H[n * nq + c] = 0.0;
@@ -246,9 +196,9 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
     for (int r = 0; r < 4; ++r) valid[r] = in_n && (j == 0 || r < 2 || tau < T - 1);
     double m_rows = 8.0 * T - 2.0;
     if constexpr (AV) {
-        h[4] = in_n ? pl_h : 0.0;
-        valid[4] = in_n ? pl_slot >= 0 : i == n;
-        m_rows += 1.0 + gsum<G>(in_n && pl_slot >= 0 ? 1.0 : 0.0);
+        h[4] = in_n ? pl.h : 0.0;
+        valid[4] = in_n ? pl.slot >= 0 : i == n;
+        m_rows += 1.0 + gsum<G>(in_n && pl.slot >= 0 ? 1.0 : 0.0);
     }
 
     // G x for this lane's rows (x published in vec[])
@@ -370,10 +320,7 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
             }
         }
         if constexpr (AV) {
-            if (av.planes) {
-                double* p = av.planes + ((size_t)e * n + i) * 4;
-                p[0] = ok ? pl_nx : NaN; p[1] = ok ? pl_ny : NaN; p[2] = ok ? pl_h : NaN; p[3] = ok ? (double)pl_slot : NaN;
-            }
+            if (av.planes) qp_avoid_write_plane(av.planes + ((size_t)e * n + i) * 4, pl, ok);
             if (av.duals) av.duals[(size_t)e * nq + i] = ok ? lam[4] : NaN;
         }
     }
@@ -421,43 +368,30 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
 #define F1P_KMPC_QP_PACK_T8 4         // egos per wave at T <= 8 (1 or 4)
 #endif
 
-int kmpc_qp_pack(const f1p_ctx* ctx, int T) {
+static int kmpc_qp_pack(const f1p_ctx* ctx, int T) {
     if (T > 8) return 1;
     return ctx->kmpc_qp_pack > 0 ? ctx->kmpc_qp_pack : F1P_KMPC_QP_PACK_T8;
 }
 
-int launch_kmpc_qp(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
-                   const f1p_kmpc_cfg* cfg, int max_iter, double tol, double* d_steer, double* d_speed, int32_t* d_status, double* d_u,
-                   double* d_xk, double* d_obj, double* d_duals, int32_t* d_iters, double* d_warm_out) {
+// egos per wave: the plain QP four or one (kmpc_qp_pack); the avoidance variant, 2T + 1 lanes per ego, two while they fit 32 lanes
+// (T <= 15), else one
+int launch_kmpc_qp(f1p_ctx* ctx, int E, const f1p_kmpc_cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid) {
     if (E <= 0) return F1P_OK;
     const int T = cfg->horizon;
-    const int epw = kmpc_qp_pack(ctx, T) == 4 ? 4 : 1;
-    const size_t lds = sizeof(double) * (size_t)qp_lds_doubles(T) * epw;
-    const auto kern = epw == 4 ? &k_kmpc_qp<16> : &k_kmpc_qp<64>;
-    const int rc = qp_lds_opt_in(ctx, reinterpret_cast<const void*>(kern), lds, "kmpc qp: horizon too long for the CU's LDS");
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((E + epw - 1) / epw)), dim3(64), lds, ctx->stream, d_x0, d_ref, d_pa, d_pd, pstride, E, *cfg,
-                       max_iter, tol, d_steer, d_speed, d_status, d_u, d_xk, d_obj, d_duals, d_iters, d_warm_out);
-    return check_hip(ctx, hipGetLastError(), "k_kmpc_qp launch");
-}
-
-// the avoidance variant: 2T + 1 lanes per ego -- two egos per wave while they fit 32 lanes (T <= 15), else one
-int launch_kmpc_qp_avoid(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
-                         const f1p_kmpc_cfg* cfg, int max_iter, double tol, const double* d_obs, int M, const f1p_kmpc_qp_avoid* avoid,
-                         double* d_steer, double* d_speed, int32_t* d_status, double* d_u, double* d_xk, double* d_obj, double* d_duals,
-                         int32_t* d_iters, double* d_warm_out, double* d_eps, double* d_planes, double* d_avoid_duals) {
-    if (E <= 0) return F1P_OK;
-    const int T = cfg->horizon;
-    if (T > 31 || M < 0 || M > F1P_KMPC_MAX_OBS || (M > 0 && !d_obs)) return set_error(ctx, F1P_EINVAL, "kmpc qp avoid: bad horizon / obstacles");
-    const int epw = 2 * T + 1 <= 32 ? 2 : 1;
-    const size_t lds = sizeof(double) * (size_t)qp_lds_doubles_av(T) * epw;
-    const auto kern = epw == 2 ? &k_kmpc_qp<32, QpAvoidArgs> : &k_kmpc_qp<64, QpAvoidArgs>;
-    const int rc = qp_lds_opt_in(ctx, reinterpret_cast<const void*>(kern), lds, "kmpc qp: horizon too long for the CU's LDS");
-    if (rc) return rc;
-    const QpAvoidArgs av{d_obs, M, avoid->margin, avoid->rho, avoid->lin, d_eps, d_planes, d_avoid_duals};
-    hipLaunchKernelGGL(kern, dim3((unsigned)((E + epw - 1) / epw)), dim3(64), lds, ctx->stream, d_x0, d_ref, d_pa, d_pd, pstride, E, *cfg,
-                       max_iter, tol, d_steer, d_speed, d_status, d_u, d_xk, d_obj, d_duals, d_iters, d_warm_out, av);
-    return check_hip(ctx, hipGetLastError(), "k_kmpc_qp_avoid launch");
+    if (avoid && (T > 31 || avoid->M < 0 || avoid->M > F1P_KMPC_MAX_OBS || (avoid->M > 0 && !avoid->obs)))
+        return set_error(ctx, F1P_EINVAL, "kmpc qp avoid: bad horizon / obstacles");
+    const int epw = avoid ? (2 * T + 1 <= 32 ? 2 : 1) : (kmpc_qp_pack(ctx, T) == 4 ? 4 : 1);
+    const size_t lds = sizeof(double) * (size_t)qp_lds_doubles(T, avoid != nullptr) * epw;
+    const auto launch = [&](auto kern, const char* what, auto... av) {
+        const int rc = qp_lds_opt_in(ctx, reinterpret_cast<const void*>(kern), lds, "kmpc qp: horizon too long for the CU's LDS");
+        if (rc) return rc;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((E + epw - 1) / epw)), dim3(64), lds, ctx->stream, io.x0, io.ref, io.pa, io.pd, io.pstride, E,
+                           *cfg, max_iter, tol, io.steer, io.speed, io.status, io.u, io.x, io.obj, io.duals, io.iters, io.warm_out, av...);
+        return check_hip(ctx, hipGetLastError(), what);
+    };
+    if (avoid) return epw == 2 ? launch(&k_kmpc_qp<32, QpAvoidArgs>, "k_kmpc_qp_avoid launch", *avoid)
+                               : launch(&k_kmpc_qp<64, QpAvoidArgs>, "k_kmpc_qp_avoid launch", *avoid);
+    return epw == 4 ? launch(&k_kmpc_qp<16>, "k_kmpc_qp launch") : launch(&k_kmpc_qp<64>, "k_kmpc_qp launch");
 }
 
 }  // namespace f1p

@@ -30,8 +30,9 @@
 // inputs a lane owns.  Lane t - 1 owns the two avoidance rows of step t (rows 10 and 11 of its twelve): the two live discs with the least
 // clearance at the linearisation path's point pbar_t give  -n.(S_xy(t) u) - eps <= n.(s_xy(t) - c) - (r + margin).  Their u-coefficients
 // are taken from step t's slab as it passes through LDS and kept packed: the rows of step t are zero from column 2t on, so row 2(t-1) + j
-// holds 2t doubles at A[2 t (t-1) + 2 t j], 2T(T+1) in all.
-#include "qp_ipm.h"
+// holds 2t doubles at A[2 t (t-1) + 2 t j], 2T(T+1) in all.  The disc load, the choice of the two discs, the half-plane and its `planes`
+// record are qp_avoid.h's, shared with k_kmpc_qp.hip.
+#include "qp_avoid.h"
 
 namespace f1p {
 
@@ -40,70 +41,48 @@ namespace {
 // Jacobian entries per step (get_dynamic_model_matrix :428-535); the unit diagonal of rows 0-4, A[4, 5] = B[2, 0] = B[3, 1] = DT are implicit
 enum { J03, J04, J06, J13, J14, J16, J52, J53, J55, J56, J62, J63, J65, J66, JB51, JB61, JC0, JC1, JC5, JC6, NJ };
 
-// doubles of LDS per ego
-__host__ __device__ inline int stqp_lds_doubles(int T) {
-    const int n = 2 * T, Tp = T + 1;
-    return 2 * n * n + 8 + 14 * Tp + NJ * T + 7 * n + 3 * n + 8 * T;
-}
-
-// ... of the avoidance variant: H and M over nq = n + 2 inputs, U / W / Y at nq; the packed rows A, their published w / D WA [n + 1],
-// pbar_1..T (x, y, yaw + beta), the discs [16][5]
-__host__ __device__ constexpr int stqp_lds_doubles_av(int T) {
-    const int n = 2 * T, Tp = T + 1, nq = n + 2;
-    return 2 * nq * nq + 8 + 14 * Tp + NJ * T + 7 * n + 3 * nq + 8 * T + n * Tp + (n + 1) + 3 * T + 5 * F1P_KMPC_MAX_OBS;
-}
-// the default horizon must run; F1P_STMPC_QP_AVOID_MAX_T is the longest horizon whose layout one workgroup may claim (160 KiB) with
-// room left for the 1 KiB the plain kernel's cap leaves too
-static_assert(8 * stqp_lds_doubles_av(F1P_STMPC_QP_AVOID_MAX_T) <= 160 * 1024 - 1024, "F1P_STMPC_QP_AVOID_MAX_T does not fit the CU's LDS");
-static_assert(8 * stqp_lds_doubles_av(F1P_STMPC_QP_AVOID_MAX_T + 1) > 160 * 1024 - 1024, "F1P_STMPC_QP_AVOID_MAX_T is not the cap");
-
-struct StQpLds {
-    double *H, *M, *x0, *ref, *fr, *J, *SL, *U, *W, *Y, *Wd, *Wv, *Wr, *Sd, *Sv, *pa, *pd, *pv;
-    __device__ StQpLds(double* b, int T) {
-        const int n = 2 * T, Tp = T + 1;
-        H = b; b += n * n;
-        M = b; b += n * n;
-        x0 = b; b += 8;
-        ref = b; b += 7 * Tp;
-        fr = b; b += 7 * Tp;
-        J = b; b += NJ * T;                 // J[k * T + t]
-        SL = b; b += 7 * n;                 // the slab of step t: SL[k * n + i] = d x_t[k] / d u_i
-        U = b; b += n; W = b; b += n; Y = b; b += n;
-        Wd = b; b += T; Wv = b; b += T; Wr = b; b += T; Sd = b; b += T; Sv = b; b += T;
-        pa = b; b += T; pd = b; b += T; pv = b; b += T;
-    }
-};
-
-struct StQpLdsAv {
-    double *H, *M, *x0, *ref, *fr, *J, *SL, *U, *W, *Y, *Wd, *Wv, *Wr, *Sd, *Sv, *pa, *pd, *pv, *A, *WA, *px, *py, *pw, *ob;
-    __device__ StQpLdsAv(double* b, int T) {
-        const int n = 2 * T, Tp = T + 1, nq = n + 2;
+// One ego's LDS, carved from b in doubles: the kernel's pointers (P = double*), or with P = int from 0 the members' offsets, `end` the
+// size.  extra: the QP's inputs beyond u (nq = n + extra; AV: the slack and its padding).
+template <class P>
+struct StQpLdsT {
+    P H{}, M{}, x0{}, ref{}, fr{}, J{}, SL{}, U{}, W{}, Y{}, Wd{}, Wv{}, Wr{}, Sd{}, Sv{}, pa{}, pd{}, pv{}, end{};
+    __host__ __device__ constexpr StQpLdsT(P b, int T, int extra = 0) {
+        const int n = 2 * T, Tp = T + 1, nq = n + extra;
         H = b; b += nq * nq;
         M = b; b += nq * nq;
         x0 = b; b += 8;
         ref = b; b += 7 * Tp;
         fr = b; b += 7 * Tp;
-        J = b; b += NJ * T;
-        SL = b; b += 7 * n;
+        J = b; b += NJ * T;                 // J[k * T + t]
+        SL = b; b += 7 * n;                 // the slab of step t: SL[k * n + i] = d x_t[k] / d u_i
         U = b; b += nq; W = b; b += nq; Y = b; b += nq;
         Wd = b; b += T; Wv = b; b += T; Wr = b; b += T; Sd = b; b += T; Sv = b; b += T;
         pa = b; b += T; pd = b; b += T; pv = b; b += T;
+        end = b;
+    }
+};
+// the avoidance variant's: nq = n + 2 inputs, and behind the common members the packed rows A, their published w / D WA [n + 1], pbar_1..T
+// (x, y, yaw + beta), the discs [16][5]
+template <class P>
+struct StQpLdsAvT : StQpLdsT<P> {
+    P A{}, WA{}, px{}, py{}, pw{}, ob{};
+    __host__ __device__ constexpr StQpLdsAvT(P b, int T) : StQpLdsT<P>(b, T, 2) {
+        const int n = 2 * T, Tp = T + 1;
+        b = this->end;
         A = b; b += n * Tp;                 // rows 2 q, 2 q + 1 (step q + 1): 2 (q + 1) doubles each from A[2 q (q + 1)]
         WA = b; b += n + 1;
         px = b; b += T; py = b; b += T; pw = b; b += T;
-        ob = b;
+        ob = b; b += 5 * F1P_KMPC_MAX_OBS;
+        this->end = b;
     }
 };
-
-// the avoidance variant's arguments: obs [E][M][5] (nullable with M = 0), the f1p_kmpc_qp_avoid numbers, and its outputs (nullable)
-struct StQpAvoidArgs {
-    const double* obs;
-    int M;
-    double margin, rho, lin;
-    double *eps, *planes, *duals;
-};
-__device__ __forceinline__ StQpAvoidArgs stqp_avoid_args() { return StQpAvoidArgs{}; }
-__device__ __forceinline__ StQpAvoidArgs stqp_avoid_args(const StQpAvoidArgs& a) { return a; }
+template <bool AV> using StQpLds = std::conditional_t<AV, StQpLdsAvT<double*>, StQpLdsT<double*>>;
+// doubles of LDS per ego
+__host__ __device__ constexpr int stqp_lds_doubles(int T, bool av) { return av ? StQpLdsAvT<int>(0, T).end : StQpLdsT<int>(0, T).end; }
+// the default horizon must run; F1P_STMPC_QP_AVOID_MAX_T is the longest horizon whose layout one workgroup may claim (160 KiB) with
+// room left for the 1 KiB the plain kernel's cap leaves too
+static_assert(8 * stqp_lds_doubles(F1P_STMPC_QP_AVOID_MAX_T, true) <= 160 * 1024 - 1024, "F1P_STMPC_QP_AVOID_MAX_T does not fit the CU's LDS");
+static_assert(8 * stqp_lds_doubles(F1P_STMPC_QP_AVOID_MAX_T + 1, true) > 160 * 1024 - 1024, "F1P_STMPC_QP_AVOID_MAX_T is not the cap");
 
 // y = A_t x (the structure of :478-511)
 __device__ __forceinline__ void amul(const double* J, int T, int t, double DT, const double x[7], double y[7]) {
@@ -119,7 +98,7 @@ __device__ __forceinline__ void amul(const double* J, int T, int t, double DT, c
 
 }  // namespace
 
-// AvArgs: none (the plain QP), or one StQpAvoidArgs (AV)
+// AvArgs: none (the plain QP), or one QpAvoidArgs (AV; f1p_internal.h)
 template <class... AvArgs>
 __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g, const double* __restrict__ refg, const double* pa_g,
                                                  const double* pd_g, int pstride, int E, f1p_stmpc_cfg cfg, int max_iter, double tol,
@@ -129,7 +108,7 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
                                                  AvArgs... av_args) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     constexpr bool AV = sizeof...(AvArgs) == 1;
-    [[maybe_unused]] const StQpAvoidArgs av = stqp_avoid_args(av_args...);
+    [[maybe_unused]] const QpAvoidArgs av = qp_avoid_args(av_args...);
     constexpr int R = AV ? 12 : 10;                      // inequality rows per lane
     // AV: the solver's slack is e' = eps / sig, sig = 1 / sqrt(2 rho): its curvature is 1 like the inputs' (2 rho = 2e4 beside weights of
     // 0.01 leaves the dual residual a floor at the stopping rule's 1e-10).  The rows, hence the multipliers, are the unscaled problem's.
@@ -139,7 +118,7 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
     const int tau = threadIdx.x, i0 = 2 * tau, i1 = 2 * tau + 1;
     const int e = blockIdx.x;
     if (e >= E) return;                                  // (one ego per workgroup: uniform)
-    std::conditional_t<AV, StQpLdsAv, StQpLds> L(reinterpret_cast<double*>(lds_raw), T);
+    StQpLds<AV> L(reinterpret_cast<double*>(lds_raw), T);
     const bool in_n = tau < T;
     const double DT = cfg.dt;
     const double NaN = __builtin_nan("");
@@ -153,15 +132,7 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
         const double d = pd_g ? pd_g[((size_t)e * T + k) * pstride] : 0.0;
         L.pa[k] = a; L.pd[k] = d; bad |= !(isfinite(a) && isfinite(d));
     }
-    if constexpr (AV) {
-        for (int m = tau; m < av.M; m += 64) {               // a live slot (r >= 0) must be finite; an empty one is kept as r = -1
-            const double* o = av.obs + ((size_t)e * av.M + m) * 5;
-            const double ox = o[0], oy = o[1], ovx = o[2], ovy = o[3], r = o[4];
-            const bool live = r >= 0.0;
-            L.ob[5 * m] = ox; L.ob[5 * m + 1] = oy; L.ob[5 * m + 2] = ovx; L.ob[5 * m + 3] = ovy; L.ob[5 * m + 4] = live ? r : -1.0;
-            bad |= live && !(isfinite(ox) && isfinite(oy) && isfinite(ovx) && isfinite(ovy) && isfinite(r));
-        }
-    }
+    if constexpr (AV) bad |= qp_avoid_load<64>(av, e, tau, L.ob);
     bad = gmax<64>(bad ? 1.0 : 0.0) > 0.0;
     __syncthreads();
     const double d0 = L.x0[2], v0 = L.x0[3];
@@ -240,39 +211,17 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
     __syncthreads();
 
     // AV: this lane's two half-planes (step tau + 1: the nearest and the second nearest live disc)
-    [[maybe_unused]] double pl_nx[2] = {0.0, 0.0}, pl_ny[2] = {0.0, 0.0}, pl_h[2] = {0.0, 0.0};
-    [[maybe_unused]] int pl_slot[2] = {-1, -1};
+    [[maybe_unused]] QpPlane pl[2];
     [[maybe_unused]] const int a_off = 2 * tau * (tau + 1), a_len = 2 * (tau + 1);     // this lane's packed rows: A[a_off + j a_len + c]
     if constexpr (AV) {
         if (in_n && !done) {
             const int t = tau + 1;
             const double tt = (double)t * DT, px = L.px[tau], py = L.py[tau];
-            double c0 = INFINITY, c1 = INFINITY;
-            int m0 = -1, m1 = -1;
-            for (int m = 0; m < av.M; ++m) {               // the two least clearances, ties to the lower slot
-                const double r = L.ob[5 * m + 4];
-                if (!(r >= 0.0)) continue;
-                const double dx = px - (L.ob[5 * m] + L.ob[5 * m + 2] * tt), dy = py - (L.ob[5 * m + 1] + L.ob[5 * m + 3] * tt);
-                const double clear = sqrt(dx * dx + dy * dy) - r;
-                if (clear < c0) { c1 = c0; m1 = m0; c0 = clear; m0 = m; }
-                else if (clear < c1) { c1 = clear; m1 = m; }
-            }
+            const QpNearest nr = qp_avoid_nearest(L.ob, av.M, px, py, tt);
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
-                const int ms = jj == 0 ? m0 : m1;
-                if (ms < 0) continue;
-                const double r = L.ob[5 * ms + 4];
-                const double cx = L.ob[5 * ms] + L.ob[5 * ms + 2] * tt, cy = L.ob[5 * ms + 1] + L.ob[5 * ms + 3] * tt;
-                const double dx = px - cx, dy = py - cy, dist = sqrt(dx * dx + dy * dy);
-                if (dist < 1e-9) {                           // on the disc's centre: stay behind it
-                    double sn, cs;
-                    sincos(L.pw[tau], &sn, &cs);
-                    pl_nx[jj] = -cs; pl_ny[jj] = -sn;
-                } else {
-                    pl_nx[jj] = dx / dist; pl_ny[jj] = dy / dist;
-                }
-                pl_h[jj] = pl_nx[jj] * (L.fr[t] - cx) + pl_ny[jj] * (L.fr[Tp + t] - cy) - (r + av.margin);
-                pl_slot[jj] = ms;
+                const int ms = jj == 0 ? nr.m0 : nr.m1;
+                if (ms >= 0) pl[jj] = qp_avoid_plane(L.ob, ms, px, py, L.pw[tau], tt, L.fr[t], L.fr[Tp + t], av.margin);
             }
         }
     }
@@ -326,7 +275,7 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
 #pragma unroll
                         for (int jj = 0; jj < 2; ++jj)
                             for (int c = 0; c < a_len; ++c)
-                                L.A[a_off + jj * a_len + c] = pl_slot[jj] >= 0 ? -(pl_nx[jj] * L.SL[c] + pl_ny[jj] * L.SL[n + c]) : 0.0;
+                                L.A[a_off + jj * a_len + c] = pl[jj].slot >= 0 ? -(pl[jj].nx * L.SL[c] + pl[jj].ny * L.SL[n + c]) : 0.0;
                     }
                 }
             }
@@ -352,10 +301,10 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
     for (int r = 0; r < 10; ++r) valid[r] = in_n && (r < 8 || tau < T - 1);
     double m_rows = 10.0 * T - 2.0;
     if constexpr (AV) {                                  // rows 10, 11: the half-planes; lane T: -eps <= 0
-        h[10] = pl_h[0]; h[11] = pl_h[1];
-        valid[10] = in_n ? pl_slot[0] >= 0 : tau == T;
-        valid[11] = in_n && pl_slot[1] >= 0;
-        m_rows += 1.0 + gsum<64>((double)((in_n && pl_slot[0] >= 0) + (in_n && pl_slot[1] >= 0)));
+        h[10] = pl[0].h; h[11] = pl[1].h;
+        valid[10] = in_n ? pl[0].slot >= 0 : tau == T;
+        valid[11] = in_n && pl[1].slot >= 0;
+        m_rows += 1.0 + gsum<64>((double)((in_n && pl[0].slot >= 0) + (in_n && pl[1].slot >= 0)));
     }
 
     // G x for this lane's rows (x published in vec[])
@@ -502,10 +451,7 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
         if constexpr (AV) {
             if (av.planes) {
 #pragma unroll
-                for (int jj = 0; jj < 2; ++jj) {
-                    double* p = av.planes + ((size_t)e * n + i0 + jj) * 4;
-                    p[0] = ok ? pl_nx[jj] : NaN; p[1] = ok ? pl_ny[jj] : NaN; p[2] = ok ? pl_h[jj] : NaN; p[3] = ok ? (double)pl_slot[jj] : NaN;
-                }
+                for (int jj = 0; jj < 2; ++jj) qp_avoid_write_plane(av.planes + ((size_t)e * n + i0 + jj) * 4, pl[jj], ok);
             }
             if (av.duals) { av.duals[(size_t)e * (n + 1) + i0] = ok ? lam[10] : NaN; av.duals[(size_t)e * (n + 1) + i1] = ok ? lam[11] : NaN; }
         }
@@ -589,38 +535,24 @@ __global__ __launch_bounds__(256) void k_stmpc_qp_obs_in(const double* __restric
     out[j] = obs[(size_t)idx[k] * M5 + r];
 }
 
-size_t stmpc_qp_lds_bytes(int T) { return sizeof(double) * (size_t)stqp_lds_doubles(T); }
-size_t stmpc_qp_avoid_lds_bytes(int T) { return sizeof(double) * (size_t)stqp_lds_doubles_av(T); }
+size_t stmpc_qp_avoid_lds_bytes(int T) { return sizeof(double) * (size_t)stqp_lds_doubles(T, true); }
 
-int launch_stmpc_qp(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
-                    const f1p_stmpc_cfg* cfg, int max_iter, double tol, double* d_steer, double* d_speed, int32_t* d_status, double* d_u,
-                    double* d_x, double* d_obj, double* d_duals, int32_t* d_iters, double* d_warm_out) {
-    if (E <= 0) return F1P_OK;
-    const size_t lds = stmpc_qp_lds_bytes(cfg->horizon);
-    const int rc = qp_lds_opt_in(ctx, reinterpret_cast<const void*>(&k_stmpc_qp<>), lds, "stmpc qp: horizon too long for the CU's LDS");
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_stmpc_qp<>, dim3((unsigned)E), dim3(64), lds, ctx->stream, d_x0, d_ref, d_pa, d_pd, pstride, E, *cfg, max_iter, tol,
-                       d_steer, d_speed, d_status, d_u, d_x, d_obj, d_duals, d_iters, d_warm_out);
-    return check_hip(ctx, hipGetLastError(), "k_stmpc_qp launch");
-}
-
-// the avoidance variant: one wave per ego as the plain kernel, lane T takes the slack
-int launch_stmpc_qp_avoid(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_pa, const double* d_pd, int pstride, int E,
-                          const f1p_stmpc_cfg* cfg, int max_iter, double tol, const double* d_obs, int M, const f1p_kmpc_qp_avoid* avoid,
-                          double* d_steer, double* d_speed, int32_t* d_status, double* d_u, double* d_x, double* d_obj, double* d_duals,
-                          int32_t* d_iters, double* d_warm_out, double* d_eps, double* d_planes, double* d_avoid_duals) {
+// one wave per ego; in the avoidance variant lane T takes the slack
+int launch_stmpc_qp(f1p_ctx* ctx, int E, const f1p_stmpc_cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid) {
     if (E <= 0) return F1P_OK;
     const int T = cfg->horizon;
-    if (T > F1P_STMPC_QP_AVOID_MAX_T || M < 0 || M > F1P_KMPC_MAX_OBS || (M > 0 && !d_obs))
+    if (avoid && (T > F1P_STMPC_QP_AVOID_MAX_T || avoid->M < 0 || avoid->M > F1P_KMPC_MAX_OBS || (avoid->M > 0 && !avoid->obs)))
         return set_error(ctx, F1P_EINVAL, "stmpc qp avoid: bad horizon / obstacles");
-    const size_t lds = stmpc_qp_avoid_lds_bytes(T);
-    const auto kern = &k_stmpc_qp<StQpAvoidArgs>;
-    const int rc = qp_lds_opt_in(ctx, reinterpret_cast<const void*>(kern), lds, "stmpc qp avoid: horizon too long for the CU's LDS");
-    if (rc) return rc;
-    const StQpAvoidArgs av{d_obs, M, avoid->margin, avoid->rho, avoid->lin, d_eps, d_planes, d_avoid_duals};
-    hipLaunchKernelGGL(kern, dim3((unsigned)E), dim3(64), lds, ctx->stream, d_x0, d_ref, d_pa, d_pd, pstride, E, *cfg, max_iter, tol, d_steer,
-                       d_speed, d_status, d_u, d_x, d_obj, d_duals, d_iters, d_warm_out, av);
-    return check_hip(ctx, hipGetLastError(), "k_stmpc_qp_avoid launch");
+    const size_t lds = sizeof(double) * (size_t)stqp_lds_doubles(T, avoid != nullptr);
+    const auto launch = [&](auto kern, const char* too_long, const char* what, auto... av) {
+        const int rc = qp_lds_opt_in(ctx, reinterpret_cast<const void*>(kern), lds, too_long);
+        if (rc) return rc;
+        hipLaunchKernelGGL(kern, dim3((unsigned)E), dim3(64), lds, ctx->stream, io.x0, io.ref, io.pa, io.pd, io.pstride, E, *cfg, max_iter, tol,
+                           io.steer, io.speed, io.status, io.u, io.x, io.obj, io.duals, io.iters, io.warm_out, av...);
+        return check_hip(ctx, hipGetLastError(), what);
+    };
+    if (avoid) return launch(&k_stmpc_qp<QpAvoidArgs>, "stmpc qp avoid: horizon too long for the CU's LDS", "k_stmpc_qp_avoid launch", *avoid);
+    return launch(&k_stmpc_qp<>, "stmpc qp: horizon too long for the CU's LDS", "k_stmpc_qp launch");
 }
 
 int launch_stmpc_qp_obs_in(f1p_ctx* ctx, const double* d_obs, const int32_t* d_idx, int nb, int M, double* d_out) {

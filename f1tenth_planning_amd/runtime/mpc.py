@@ -40,25 +40,8 @@ def kmpc_qp_avoid(ctx, x0, ref, obs, cfg, avoid=None, oa_prev=None, od_prev=None
     linearised avoidance term, not a guarantee.  -> kmpc_qp's dict[, eps [E], planes [E, T, 2, 4] = (n_x, n_y, right-hand side, slot; -1 and
     zeros: absent), avoid_duals [E, 2T+1]: the 2T avoidance rows in step order, then -eps <= 0]; obj includes the slack's cost.
     (A module function: Context's public methods are a pinned record, tests/test_runtime_calls.py.)"""
-    x0 = _f64(x0, (-1, 4)); E = x0.shape[0]; T = cfg.horizon
-    ref = _f64(ref, (E, 4, T + 1))
-    o = _f64(obs)
-    if o.ndim != 3 or o.shape[0] != E or o.shape[2] != 5:
-        raise ValueError(f"obstacles must be [E={E}, M, 5] = (x, y, vx, vy, r)")
-    oa = None if oa_prev is None else _f64(oa_prev, (E, T))
-    od = None if od_prev is None else _f64(od_prev, (E, T))
-    out = dict(steer=np.empty(E), speed=np.empty(E), status=np.empty(E, np.int32))
-    for k, want, shape, dt in (("u", want_u, (E, T, 2), np.float64), ("xk", want_xk, (E, 4, T + 1), np.float64), ("obj", want_obj, (E,), np.float64),
-                               ("duals", want_duals, (E, 8 * T - 2), np.float64), ("iters", want_iters, (E,), np.int32),
-                               ("eps", want_eps, (E,), np.float64), ("planes", want_planes, (E, T, 2, 4), np.float64),
-                               ("avoid_duals", want_avoid_duals, (E, 2 * T + 1), np.float64)):
-        if want:
-            out[k] = np.empty(shape, dt)
-    ctx._check(ctx.lib.f1p_kmpc_qp_avoid_batch(ctx.h, _ptr(x0), _ptr(ref), _ptr(oa), _ptr(od), E, C.byref(cfg), _ref(opts), _ptr(o), o.shape[1],
-                                               _ref(avoid), _ptr(out["steer"]), _ptr(out["speed"]), _ptr(out["status"]), _ptr(out.get("u")),
-                                               _ptr(out.get("xk")), _ptr(out.get("obj")), _ptr(out.get("duals")), _ptr(out.get("iters")),
-                                               _ptr(out.get("eps")), _ptr(out.get("planes")), _ptr(out.get("avoid_duals"))))
-    return out
+    return _mpc_qp(ctx, ctx.lib.f1p_kmpc_qp_avoid_batch, 4, "xk", 8, x0, ref, cfg, oa_prev, od_prev, opts, want_u, want_xk, want_obj, want_duals,
+                   want_iters, (obs, avoid, want_eps, want_planes, want_avoid_duals))
 
 
 def kmpc_qp_set_avoid(ctx, avoid):
@@ -74,25 +57,8 @@ def stmpc_qp_avoid(ctx, x0, ref, obs, cfg, avoid=None, oa_prev=None, od_v_prev=N
     <= _abi.STMPC_QP_AVOID_MAX_T.  A soft, linearised avoidance term, not a guarantee.  -> stmpc_qp's dict[, eps [E], planes [E, T, 2, 4] =
     (n_x, n_y, right-hand side, slot; -1 and zeros: absent), avoid_duals [E, 2T+1]: the 2T avoidance rows in step order, then -eps <= 0];
     obj includes the slack's cost.  (A module function: Context's public methods are a pinned record, tests/test_runtime_calls.py.)"""
-    x0 = _f64(x0, (-1, 7)); E = x0.shape[0]; T = cfg.horizon
-    ref = _f64(ref, (E, 7, T + 1))
-    o = _f64(obs)
-    if o.ndim != 3 or o.shape[0] != E or o.shape[2] != 5:
-        raise ValueError(f"obstacles must be [E={E}, M, 5] = (x, y, vx, vy, r)")
-    oa = None if oa_prev is None else _f64(oa_prev, (E, T))
-    od = None if od_v_prev is None else _f64(od_v_prev, (E, T))
-    out = dict(steer=np.empty(E), speed=np.empty(E), status=np.empty(E, np.int32))
-    for k, want, shape, dt in (("u", want_u, (E, T, 2), np.float64), ("x", want_x, (E, 7, T + 1), np.float64), ("obj", want_obj, (E,), np.float64),
-                               ("duals", want_duals, (E, 10 * T - 2), np.float64), ("iters", want_iters, (E,), np.int32),
-                               ("eps", want_eps, (E,), np.float64), ("planes", want_planes, (E, T, 2, 4), np.float64),
-                               ("avoid_duals", want_avoid_duals, (E, 2 * T + 1), np.float64)):
-        if want:
-            out[k] = np.empty(shape, dt)
-    ctx._check(ctx.lib.f1p_stmpc_qp_avoid_batch(ctx.h, _ptr(x0), _ptr(ref), _ptr(oa), _ptr(od), E, C.byref(cfg), _ref(opts), _ptr(o), o.shape[1],
-                                                _ref(avoid), _ptr(out["steer"]), _ptr(out["speed"]), _ptr(out["status"]), _ptr(out.get("u")),
-                                                _ptr(out.get("x")), _ptr(out.get("obj")), _ptr(out.get("duals")), _ptr(out.get("iters")),
-                                                _ptr(out.get("eps")), _ptr(out.get("planes")), _ptr(out.get("avoid_duals"))))
-    return out
+    return _mpc_qp(ctx, ctx.lib.f1p_stmpc_qp_avoid_batch, 7, "x", 10, x0, ref, cfg, oa_prev, od_v_prev, opts, want_u, want_x, want_obj, want_duals,
+                   want_iters, (obs, avoid, want_eps, want_planes, want_avoid_duals))
 
 
 def stmpc_qp_set_avoid(ctx, avoid):
@@ -100,6 +66,35 @@ def stmpc_qp_set_avoid(ctx, avoid):
     and stmpc_qp_dev take the discs of stmpc_set_obstacles[_dev] (the caller's ego order) as soft half-plane rows of both branches' QPs;
     avoid: _abi.kmpc_qp_avoid(...), None (or on=False) turns it off"""
     ctx._check(ctx.lib.f1p_stmpc_qp_set_avoid(ctx.h, _ref(avoid)))
+
+
+def _mpc_qp(ctx, fn, n, xname, duals_per_step, x0, ref, cfg, oa_prev, od_prev, opts, want_u, want_x, want_obj, want_duals, want_iters, av=None):
+    """the four stateless QP calls (Context.kmpc_qp / stmpc_qp, kmpc_qp_avoid / stmpc_qp_avoid).  n: the state width; xname: the key of the
+    predicted states [E, n, T+1]; duals [E, duals_per_step * T - 2]; av: None, or the avoidance rows' (obs, avoid, want_eps, want_planes,
+    want_avoid_duals)"""
+    x0 = _f64(x0, (-1, n)); E = x0.shape[0]; T = cfg.horizon
+    ref = _f64(ref, (E, n, T + 1))
+    wants = [("u", want_u, (E, T, 2), np.float64), (xname, want_x, (E, n, T + 1), np.float64), ("obj", want_obj, (E,), np.float64),
+             ("duals", want_duals, (E, duals_per_step * T - 2), np.float64), ("iters", want_iters, (E,), np.int32)]
+    av_in, av_keys = (), ()
+    if av is not None:
+        obs, avoid, want_eps, want_planes, want_avoid_duals = av
+        o = _f64(obs)
+        if o.ndim != 3 or o.shape[0] != E or o.shape[2] != 5:
+            raise ValueError(f"obstacles must be [E={E}, M, 5] = (x, y, vx, vy, r)")
+        wants += [("eps", want_eps, (E,), np.float64), ("planes", want_planes, (E, T, 2, 4), np.float64),
+                  ("avoid_duals", want_avoid_duals, (E, 2 * T + 1), np.float64)]
+        av_in, av_keys = (_ptr(o), o.shape[1], _ref(avoid)), ("eps", "planes", "avoid_duals")
+    oa = None if oa_prev is None else _f64(oa_prev, (E, T))
+    od = None if od_prev is None else _f64(od_prev, (E, T))
+    out = dict(steer=np.empty(E), speed=np.empty(E), status=np.empty(E, np.int32))
+    for k, want, shape, dt in wants:
+        if want:
+            out[k] = np.empty(shape, dt)
+    ctx._check(fn(ctx.h, _ptr(x0), _ptr(ref), _ptr(oa), _ptr(od), E, C.byref(cfg), _ref(opts), *av_in, _ptr(out["steer"]), _ptr(out["speed"]),
+                  _ptr(out["status"]), _ptr(out.get("u")), _ptr(out.get(xname)), _ptr(out.get("obj")), _ptr(out.get("duals")),
+                  _ptr(out.get("iters")), *(_ptr(out.get(k)) for k in av_keys)))
+    return out
 
 
 class _Mpc:
@@ -333,32 +328,16 @@ class _Mpc:
         """linear_mpc_control_kinematic (kinematic_mpc.py:452-475) solved exactly for E egos: x0 [E, 4], ref [E, 4, T+1], the previous
         solution oa_prev / od_prev [E, T] (None: zeros) -> dict(steer, speed, status[, u [E, T, 2], xk [E, 4, T+1], obj, duals [E, 8T-2],
         iters]).  status: 0 solved, 1 infeasible, 2 not converged, 3 non-finite input (1 and 3: NaN outputs)."""
-        return self._mpc_qp(self.lib.f1p_kmpc_qp_batch, 4, "xk", 8, x0, ref, cfg, oa_prev, od_prev, opts, want_u, want_xk, want_obj, want_duals,
-                            want_iters)
+        return _mpc_qp(self, self.lib.f1p_kmpc_qp_batch, 4, "xk", 8, x0, ref, cfg, oa_prev, od_prev, opts, want_u, want_xk, want_obj, want_duals,
+                       want_iters)
 
     def stmpc_qp(self, x0, ref, cfg: _abi.StmpcCfg, oa_prev=None, od_v_prev=None, opts=None, want_u=True, want_x=False, want_obj=True,
                  want_duals=False, want_iters=True):
         """linear_mpc_control (dynamic_mpc.py:995-1040) solved exactly for E egos: x0 [E, 7], ref [E, 7, T+1], the previous solution
         oa_prev / od_v_prev [E, T] (None: zeros) -> dict(steer, speed, status[, u [E, T, 2] (steering speed, accel), x [E, 7, T+1], obj,
         duals [E, 10T-2], iters]).  status: 0 solved, 1 infeasible, 2 not converged, 3 non-finite input or model data (1, 3: NaN outputs)."""
-        return self._mpc_qp(self.lib.f1p_stmpc_qp_batch, 7, "x", 10, x0, ref, cfg, oa_prev, od_v_prev, opts, want_u, want_x, want_obj,
-                            want_duals, want_iters)
-
-    def _mpc_qp(self, fn, n, xname, duals_per_step, x0, ref, cfg, oa_prev, od_prev, opts, want_u, want_x, want_obj, want_duals, want_iters):
-        """xname: the key of the predicted states [E, n, T+1]; duals [E, duals_per_step * T - 2]"""
-        x0 = _f64(x0, (-1, n)); E = x0.shape[0]; T = cfg.horizon
-        ref = _f64(ref, (E, n, T + 1))
-        oa = None if oa_prev is None else _f64(oa_prev, (E, T))
-        od = None if od_prev is None else _f64(od_prev, (E, T))
-        out = dict(steer=np.empty(E), speed=np.empty(E), status=np.empty(E, np.int32))
-        for k, want, shape, dt in (("u", want_u, (E, T, 2), np.float64), (xname, want_x, (E, n, T + 1), np.float64), ("obj", want_obj, (E,), np.float64),
-                                   ("duals", want_duals, (E, duals_per_step * T - 2), np.float64), ("iters", want_iters, (E,), np.int32)):
-            if want:
-                out[k] = np.empty(shape, dt)
-        self._check(fn(self.h, _ptr(x0), _ptr(ref), _ptr(oa), _ptr(od), E, C.byref(cfg), _ref(opts), _ptr(out["steer"]), _ptr(out["speed"]),
-                       _ptr(out["status"]), _ptr(out.get("u")), _ptr(out.get(xname)), _ptr(out.get("obj")), _ptr(out.get("duals")),
-                       _ptr(out.get("iters"))))
-        return out
+        return _mpc_qp(self, self.lib.f1p_stmpc_qp_batch, 7, "x", 10, x0, ref, cfg, oa_prev, od_v_prev, opts, want_u, want_x, want_obj,
+                       want_duals, want_iters)
 
     def kmpc_qp_dev(self, d_x0, d_ref, E, cfg: KmpcCfg, d_steer, d_speed, d_status, d_oa_prev=None, d_od_prev=None, opts=None, d_u=None,
                     d_xk=None, d_obj=None, d_duals=None, d_iters=None):

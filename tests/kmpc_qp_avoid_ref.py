@@ -10,68 +10,26 @@ import math
 import numpy as np
 
 import kmpc_qp_ref as Q
+import qp_avoid_ref as R
 
 DEFAULTS = dict(margin=0.0, rho=1e4, lin=10.0)
 
 
+def _heading(path, t):
+    return path[3, t]
+
+
 def planes(d, c, obs, p, margin):
     """-> (planes [T, 2, 4] = (n_x, n_y, right-hand side, slot; slot -1 and zeros: absent), A [2T, 2T]: the rows' u-coefficients -n.S_xy(t))"""
-    T, DTK = p["T"], p["DTK"]
-    path, Z, z0 = d["path"], c["Z"], c["z0"]
-    obs = np.asarray(obs, float).reshape(-1, 5)
-    pl = np.zeros((T, 2, 4))
-    pl[:, :, 3] = -1.0
-    A = np.zeros((2 * T, 2 * T))
-    for t in range(1, T + 1):
-        tau = float(t) * DTK
-        px, py = path[0, t], path[1, t]
-        c0 = c1 = math.inf
-        m0 = m1 = -1
-        for m, (x, y, vx, vy, r) in enumerate(obs):
-            if not r >= 0.0:
-                continue
-            dx, dy = px - (x + vx * tau), py - (y + vy * tau)
-            clear = math.sqrt(dx * dx + dy * dy) - r
-            if clear < c0:
-                c1, m1, c0, m0 = c0, m0, clear, m
-            elif clear < c1:
-                c1, m1 = clear, m
-        for k, m in enumerate((m0, m1)):
-            if m < 0:
-                continue
-            x, y, vx, vy, r = obs[m]
-            cx, cy = x + vx * tau, y + vy * tau
-            dx, dy = px - cx, py - cy
-            dist = math.sqrt(dx * dx + dy * dy)
-            if dist < 1e-9:
-                nx, ny = -math.cos(path[3, t]), -math.sin(path[3, t])
-            else:
-                nx, ny = dx / dist, dy / dist
-            rhs = nx * (z0[4 * t] - cx) + ny * (z0[4 * t + 1] - cy) - (r + margin)
-            pl[t - 1, k] = (nx, ny, rhs, m)
-            A[2 * (t - 1) + k] = -(nx * Z[4 * t] + ny * Z[4 * t + 1])
-    return pl, A
+    return R.planes(d, c, obs, p["T"], 4, p["DTK"], _heading, margin)
 
 
 def build(x0, ref, oa, od, obs, p, margin=0.0, rho=1e4, lin=10.0):
     """the avoidance QP over w = (u, eps): dict(H, g, G, h [rows: the plain 8T-2, the 2T avoidance rows in step order (absent ones left
     out: `rows` lists the kept ones' indices into the 2T), then -eps <= 0], planes, data, cond)"""
-    T = p["T"]
     d = Q.qp_data(x0, ref, oa, od, p)
-    c = Q.condense(d, T)
-    pl, A = planes(d, c, obs, p, margin)
-    n = 2 * T
-    keep = np.flatnonzero(pl.reshape(-1, 4)[:, 3] >= 0)
-    H = np.zeros((n + 1, n + 1)); H[:n, :n] = c["H"]; H[n, n] = 2.0 * rho
-    g = np.concatenate([c["g"], [lin]])
-    m0 = len(c["h"])
-    G = np.zeros((m0 + len(keep) + 1, n + 1))
-    G[:m0, :n] = c["G"]
-    G[m0:m0 + len(keep), :n] = A[keep]
-    G[m0:m0 + len(keep), n] = -1.0
-    G[-1, n] = -1.0
-    h = np.concatenate([c["h"], pl.reshape(-1, 4)[keep, 2], [0.0]])
-    return dict(H=H, g=g, G=G, h=h, planes=pl, rows=keep, m0=m0, data=d, cond=c)
+    c = Q.condense(d, p["T"])
+    return R.build(d, c, *planes(d, c, obs, p, margin), p["T"], rho, lin)
 
 
 def cert(b, w, lam):
@@ -87,9 +45,7 @@ def cert_ok(c):
     return c["primal"] <= 1e-9 and c["dual"] >= -1e-10 and c["comp"] <= 1e-9 and c["stat"] <= 1e-8
 
 
-def lam_full(b, duals, avoid_duals):
-    """the multipliers of build()'s rows from the GPU's duals [8T-2] and avoid_duals [2T+1]"""
-    return np.concatenate([duals, avoid_duals[:-1][b["rows"]], avoid_duals[-1:]])
+lam_full = R.lam_full           # the multipliers of build()'s rows from the GPU's duals [8T-2] and avoid_duals [2T+1]
 
 
 def _polish(H, g, G, h, w, lam):

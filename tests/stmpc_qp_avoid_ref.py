@@ -11,70 +11,28 @@ import math
 
 import numpy as np
 
+import qp_avoid_ref as R
 import stmpc_qp_ref as SQ
 from kmpc_qp_avoid_ref import _polish, disc_at, moving_disc, parked_disc  # noqa: F401  (the levine scenes' discs are the kinematic tests')
 
 DEFAULTS = dict(margin=0.0, rho=1e4, lin=10.0)
 
 
+def _heading(path, t):
+    return path[4, t] + path[6, t]                               # the direction of travel: yaw + beta
+
+
 def planes(d, c, obs, p, margin):
     """-> (planes [T, 2, 4] = (n_x, n_y, right-hand side, slot; slot -1 and zeros: absent), A [2T, 2T]: the rows' u-coefficients -n.S_xy(t))"""
-    T, DT = p["T"], p["DT"]
-    path, Z, z0 = d["path"], c["Z"], c["z0"]
-    obs = np.asarray(obs, float).reshape(-1, 5)
-    pl = np.zeros((T, 2, 4))
-    pl[:, :, 3] = -1.0
-    A = np.zeros((2 * T, 2 * T))
-    for t in range(1, T + 1):
-        tau = float(t) * DT
-        px, py = path[0, t], path[1, t]
-        c0 = c1 = math.inf
-        m0 = m1 = -1
-        for m, (x, y, vx, vy, r) in enumerate(obs):
-            if not r >= 0.0:
-                continue
-            dx, dy = px - (x + vx * tau), py - (y + vy * tau)
-            clear = math.sqrt(dx * dx + dy * dy) - r
-            if clear < c0:
-                c1, m1, c0, m0 = c0, m0, clear, m
-            elif clear < c1:
-                c1, m1 = clear, m
-        for k, m in enumerate((m0, m1)):
-            if m < 0:
-                continue
-            x, y, vx, vy, r = obs[m]
-            cx, cy = x + vx * tau, y + vy * tau
-            dx, dy = px - cx, py - cy
-            dist = math.sqrt(dx * dx + dy * dy)
-            if dist < 1e-9:                                      # the direction of travel: yaw + beta
-                nx, ny = -math.cos(path[4, t] + path[6, t]), -math.sin(path[4, t] + path[6, t])
-            else:
-                nx, ny = dx / dist, dy / dist
-            rhs = nx * (z0[7 * t] - cx) + ny * (z0[7 * t + 1] - cy) - (r + margin)
-            pl[t - 1, k] = (nx, ny, rhs, m)
-            A[2 * (t - 1) + k] = -(nx * Z[7 * t] + ny * Z[7 * t + 1])
-    return pl, A
+    return R.planes(d, c, obs, p["T"], 7, p["DT"], _heading, margin)
 
 
 def build(x0, ref, oa, odv, obs, p, margin=0.0, rho=1e4, lin=10.0):
     """the avoidance QP over w = (u, eps): dict(H, g, G, h [rows: the plain 10T-2, the 2T avoidance rows in step order (absent ones left
-    out: `rows` lists the kept ones' indices into the 2T), then -eps <= 0], planes, data, cond)"""
-    T = p["T"]
+    out: `rows` lists the kept ones' indices into the 2T), then -eps <= 0], planes, data, cond, rho, lin)"""
     d = SQ.qp_data(x0, ref, oa, odv, p)
-    c = SQ.condense(d, T)
-    pl, A = planes(d, c, obs, p, margin)
-    n = 2 * T
-    keep = np.flatnonzero(pl.reshape(-1, 4)[:, 3] >= 0)
-    H = np.zeros((n + 1, n + 1)); H[:n, :n] = c["H"]; H[n, n] = 2.0 * rho
-    g = np.concatenate([c["g"], [lin]])
-    m0 = len(c["h"])
-    G = np.zeros((m0 + len(keep) + 1, n + 1))
-    G[:m0, :n] = c["G"]
-    G[m0:m0 + len(keep), :n] = A[keep]
-    G[m0:m0 + len(keep), n] = -1.0
-    G[-1, n] = -1.0
-    h = np.concatenate([c["h"], pl.reshape(-1, 4)[keep, 2], [0.0]])
-    return dict(H=H, g=g, G=G, h=h, planes=pl, rows=keep, m0=m0, data=d, cond=c, rho=rho, lin=lin)
+    c = SQ.condense(d, p["T"])
+    return R.build(d, c, *planes(d, c, obs, p, margin), p["T"], rho, lin)
 
 
 def cert(b, w, lam):
@@ -89,9 +47,7 @@ def cert_ok(c, lam):
     return SQ.cert_ok(c)
 
 
-def lam_full(b, duals, avoid_duals):
-    """the multipliers of build()'s rows from the GPU's duals [10T-2] and avoid_duals [2T+1]"""
-    return np.concatenate([duals, avoid_duals[:-1][b["rows"]], avoid_duals[-1:]])
+lam_full = R.lam_full           # the multipliers of build()'s rows from the GPU's duals [10T-2] and avoid_duals [2T+1]
 
 
 def scaled(b):
