@@ -108,6 +108,20 @@ def kmpc_qp_avoid(on=True, margin=0.0, rho=1e4, lin=10.0):
     return a
 
 
+class KmpcQpWalls(C.Structure):
+    """struct f1p_kmpc_qp_walls (include/f1p.h)"""
+    _fields_ = [("on", C.c_int32), ("n_samples", C.c_int32), ("margin", C.c_double)]
+
+
+KMPC_QP_WALL_MAX_SAMPLES = 256   # F1P_KMPC_QP_WALL_MAX_SAMPLES (include/f1p.h)
+
+
+def kmpc_qp_walls(on=True, n_samples=48, margin=0.0):
+    w = KmpcQpWalls()
+    w.on, w.n_samples, w.margin = 1 if on else 0, int(n_samples), float(margin)
+    return w
+
+
 STMPC_QP_AVOID_MAX_T = 40   # F1P_STMPC_QP_AVOID_MAX_T (include/f1p.h)
 
 
@@ -311,6 +325,12 @@ PROTOTYPES = {
     "f1p_kmpc_qp_avoid_dev": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(KmpcCfg), C.POINTER(KmpcQpOpts), _P, _I, C.POINTER(KmpcQpAvoid),
                                         _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "f1p_kmpc_qp_set_avoid": (C.c_int, [_P, C.POINTER(KmpcQpAvoid)]),
+    "f1p_kmpc_qp_walls_default": (None, [C.POINTER(KmpcQpWalls)]),
+    "f1p_kmpc_qp_walls_batch": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(KmpcCfg), C.POINTER(KmpcQpOpts), _P, _I, C.POINTER(KmpcQpAvoid),
+                                          C.POINTER(KmpcQpWalls), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f1p_kmpc_qp_walls_dev": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(KmpcCfg), C.POINTER(KmpcQpOpts), _P, _I, C.POINTER(KmpcQpAvoid),
+                                        C.POINTER(KmpcQpWalls), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f1p_kmpc_qp_set_walls": (C.c_int, [_P, C.POINTER(KmpcQpWalls)]),
     "f1p_stmpc_qp_avoid_batch": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcQpOpts), _P, _I, C.POINTER(KmpcQpAvoid),
                                            _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "f1p_stmpc_qp_avoid_dev": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcQpOpts), _P, _I, C.POINTER(KmpcQpAvoid),

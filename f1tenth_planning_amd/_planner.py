@@ -138,10 +138,11 @@ def _diag(m):
     return np.diag(m) if m.ndim == 2 else m
 
 
-def check_solver(c, weights, substeps, tk_within_t=False, avoid_max_t=None):
+def check_solver(c, weights, substeps, tk_within_t=False, avoid_max_t=None, walls=False):
     """ValueError before anything touches the GPU: an unknown SOLVER, weights the QP path does not take (diagonal only), a COLLISION
     setting without meaning.  weights: ((mpc_config field, size), ...) of the QP's weight matrices; substeps: the fields that count tested
-    points per step; tk_within_t: the QP also needs TK <= T (STMPCPlanner); avoid_max_t: QP_AVOID's cap on T (STMPCPlanner's dynamic QP)."""
+    points per step; tk_within_t: the QP also needs TK <= T (STMPCPlanner); avoid_max_t: QP_AVOID's cap on T (STMPCPlanner's dynamic QP);
+    walls: the planner's QP has wall rows (QP_WALLS: KMPCPlanner)."""
     if c.SOLVER not in SOLVERS:
         raise ValueError(f"mpc_config.SOLVER must be one of {SOLVERS}, not {c.SOLVER!r}")
     if c.SOLVER == "qp":
@@ -166,6 +167,18 @@ def check_solver(c, weights, substeps, tk_within_t=False, avoid_max_t=None):
             raise ValueError("mpc_config.QP_AVOID needs TK <= 31 (the slack takes the 64th lane's place)")
         if avoid_max_t is not None and int(c.T) > avoid_max_t:
             raise ValueError(f"mpc_config.QP_AVOID needs T <= {avoid_max_t} (F1P_STMPC_QP_AVOID_MAX_T: the avoidance rows share the CU's LDS with the Newton matrix)")
+    if getattr(c, "QP_WALLS", False):
+        if not walls:
+            raise ValueError("QP_WALLS: KMPCPlanner only")
+        if c.SOLVER != "qp":
+            raise ValueError("mpc_config.QP_WALLS adds wall rows to the QP; the shooting solver tests its rollouts with COLLISION (SOLVER='qp')")
+        reach, margin = float(c.QP_WALL_REACH), float(c.QP_WALL_MARGIN)
+        if not (reach > 0.0 and np.isfinite(reach)):
+            raise ValueError(f"mpc_config.QP_WALL_REACH must be finite and > 0, not {c.QP_WALL_REACH!r}")
+        if not np.isfinite(margin):
+            raise ValueError(f"mpc_config.QP_WALL_MARGIN must be finite, not {c.QP_WALL_MARGIN!r}")
+        if int(c.TK) > 31:
+            raise ValueError("mpc_config.QP_WALLS needs TK <= 31 (the slack takes the 64th lane's place)")
     if c.COLLISION:
         if c.SOLVER == "qp":
             raise ValueError("mpc_config.COLLISION tests the shooting solver's rollouts; SOLVER='qp' has none")
@@ -183,6 +196,22 @@ def qp_avoid(c):
     if not getattr(c, "QP_AVOID", False):
         return None
     return _abi.kmpc_qp_avoid(True, c.QP_AVOID_MARGIN, c.QP_AVOID_RHO, c.QP_AVOID_LIN)
+
+
+def qp_wall_samples(reach, resolution):
+    """the march's steps per side: ceil(reach / (resolution / 2)); ValueError past the library's 256"""
+    n = int(np.ceil(float(reach) / (0.5 * float(resolution))))
+    if n > _abi.KMPC_QP_WALL_MAX_SAMPLES:
+        raise ValueError(f"mpc_config.QP_WALL_REACH = {reach!r} m at a map resolution of {resolution!r} m needs {n} samples per side; "
+                         f"at most {_abi.KMPC_QP_WALL_MAX_SAMPLES} (reach <= {_abi.KMPC_QP_WALL_MAX_SAMPLES * 0.5 * float(resolution):g} m)")
+    return max(n, 1)
+
+
+def qp_walls(c, resolution):
+    """mpc_config.QP_WALL* as the f1p_kmpc_qp_walls struct for a map of this resolution, None while QP_WALLS is off"""
+    if not getattr(c, "QP_WALLS", False):
+        return None
+    return _abi.kmpc_qp_walls(True, qp_wall_samples(c.QP_WALL_REACH, resolution), c.QP_WALL_MARGIN)
 
 
 def kin_cfg_struct(c, n_rollouts=None):
@@ -218,15 +247,20 @@ class MPCPlanner(OccupancyMap, Planner):
     _SUBSTEPS = ()
     _TK_WITHIN_T = False
     _QP_AVOID_MAX_T = None                 # mpc_config.QP_AVOID's cap on T, where the planner's QP has one
+    _QP_WALLS = False                      # the planner's QP takes mpc_config.QP_WALLS
 
     def _check_solver(self):
-        check_solver(self.config, self._QP_WEIGHTS, self._SUBSTEPS, self._TK_WITHIN_T, self._QP_AVOID_MAX_T)
+        check_solver(self.config, self._QP_WEIGHTS, self._SUBSTEPS, self._TK_WITHIN_T, self._QP_AVOID_MAX_T, self._QP_WALLS)
 
     def _check_collision(self):
-        """ValueError before anything touches the GPU: the checks of check_solver, and COLLISION without a map"""
+        """ValueError before anything touches the GPU: the checks of check_solver, and COLLISION / QP_WALLS without a map"""
         self._check_solver()
         if self.config.COLLISION and self._map is None:
             raise ValueError("mpc_config.COLLISION needs an occupancy grid: call set_map / load_map first")
+        if getattr(self.config, "QP_WALLS", False):
+            if self._map is None:
+                raise ValueError("mpc_config.QP_WALLS needs an occupancy grid: call set_map / load_map first")
+            qp_wall_samples(self.config.QP_WALL_REACH, self._map[1])
 
     # the attribute `obstacles` (moving discs, DESIGN.md 5j / 5k): the next plan / plan_batch call TAKES it -- None again afterwards, also
     # when the call raises -- so obstacles are given per call, as a keyword argument would be

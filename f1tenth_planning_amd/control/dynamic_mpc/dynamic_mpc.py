@@ -92,6 +92,7 @@ class mpc_config:
     QP_AVOID_MARGIN: float = field(default=0.0, repr=False)  # added to every disc's radius [m]
     QP_AVOID_RHO: float = field(default=1e4, repr=False)  # the slack's quadratic penalty
     QP_AVOID_LIN: float = field(default=10.0, repr=False)  # the slack's linear penalty
+    QP_WALLS: bool = field(default=False, repr=False)  # the kinematic QP's wall rows: KMPCPlanner only, True raises here
 
 
 class STMPCPlanner(MPCPlanner):

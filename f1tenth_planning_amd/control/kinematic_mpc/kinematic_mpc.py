@@ -33,6 +33,12 @@ mpc_config.QP_AVOID = True (SOLVER="qp" only) lets the QP take `obstacles` (plan
 the two discs nearest to the previous solution's path become half-plane rows of the QP, softened by one slack variable with the cost
 QP_AVOID_RHO eps^2 + QP_AVOID_LIN eps (f1p_kmpc_qp_set_avoid).  The rows are linearised and soft -- an avoidance term, not a
 guarantee; QP_AVOID_MARGIN [m] widens every disc.  TK <= 31.
+
+mpc_config.QP_WALLS = True (SOLVER="qp" only, needs set_map / load_map) lets the QP see the map: per step the walls found within QP_WALL_REACH
+metres to the left and to the right of the previous solution's path, on the occupancy grid as inflated by set_map(inflate=...), compete with
+the discs for the step's two half-plane rows (f1p_kmpc_qp_set_walls).  Soft and linearised like the discs' rows and under the
+same slack; QP_WALL_MARGIN [m] keeps the rows that far off the contact.  Works with plan, plan_batch, tracks and rivals, with or without
+QP_AVOID.  TK <= 31.
 """
 import warnings
 from dataclasses import dataclass, field
@@ -40,10 +46,10 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ... import _abi
-from ..._planner import MPCPlanner, _track_columns, qp_avoid, qp_opts
+from ..._planner import MPCPlanner, _track_columns, qp_avoid, qp_opts, qp_walls
 from ..._planner import kin_cfg_struct as _cfg_struct
 from ..._rivals import SINGLE_EGO, RivalFeed
-from ...runtime import Context, kmpc_qp_set_avoid, kmpc_set_obstacles, kmpc_set_obstacles_dev
+from ...runtime import Context, kmpc_qp_set_avoid, kmpc_qp_set_walls, kmpc_set_obstacles, kmpc_set_obstacles_dev
 
 
 @dataclass
@@ -85,6 +91,10 @@ class mpc_config:
     QP_AVOID_MARGIN: float = field(default=0.0, repr=False)  # added to every disc's radius [m]
     QP_AVOID_RHO: float = field(default=1e4, repr=False)  # the slack's quadratic penalty
     QP_AVOID_LIN: float = field(default=10.0, repr=False)  # the slack's linear penalty
+    # SOLVER="qp" only: the occupancy grid of set_map / load_map as soft, linearised wall rows of the QP
+    QP_WALLS: bool = field(default=False, repr=False)
+    QP_WALL_REACH: float = field(default=1.5, repr=False)  # how far to each side a wall is looked for [m]: ceil(reach / (resolution / 2)) samples, <= 256
+    QP_WALL_MARGIN: float = field(default=0.0, repr=False)  # kept between the path and the last free sample before the wall [m]
 
 
 @dataclass
@@ -118,6 +128,7 @@ class KMPCPlanner(MPCPlanner):
     """
     _QP_WEIGHTS = (("Rk", 2), ("Rdk", 2), ("Qk", 4), ("Qfk", 4))
     _SUBSTEPS = ("COLLISION_SUBSTEPS",)
+    _QP_WALLS = True
 
     def __init__(self, waypoints=None, config=mpc_config(),
                  params=np.array([3.74, 0.15875, 0.17145, 0.074, 4.718, 5.4562, 0.04712, 1.0489]), debug=False, device=None):
@@ -138,6 +149,7 @@ class KMPCPlanner(MPCPlanner):
         self.obstacles = None              # moving discs of the NEXT plan, which takes them: [M, 5] for plan(), [E, M, 5] for plan_batch()
         self._obstacles_set = False        # the context holds obstacles of an earlier plan
         self._qp_avoid_set = False         # the context's avoidance rows are switched on (mpc_config.QP_AVOID of an earlier plan)
+        self._qp_walls_set = False         # ... and its wall rows (mpc_config.QP_WALLS of an earlier plan)
         self.rivals = None                 # Rivals(...): every plan_batch tests each ego against its nearest other vehicles; persistent
         self._rival_feed = RivalFeed("xyvyaw", lambda ctx: kmpc_set_obstacles_dev(ctx, None))
         self._check_solver()
@@ -151,6 +163,10 @@ class KMPCPlanner(MPCPlanner):
             if av is not None or self._qp_avoid_set:             # (off after plans with it off: nothing to switch, no call -- as before QP_AVOID)
                 kmpc_qp_set_avoid(ctx, av)                       # (None: off -- the QP then ignores whatever the context holds)
                 self._qp_avoid_set = av is not None
+            wl = qp_walls(c, self._map[1]) if c.QP_WALLS else None
+            if wl is not None or self._qp_walls_set:
+                kmpc_qp_set_walls(ctx, wl)
+                self._qp_walls_set = wl is not None
         if c.SOLVER != "qp" or c.QP_AVOID:
             if c.SOLVER != "qp":
                 tested = obstacles is not None or rivals is not None

@@ -155,7 +155,7 @@ int qp_set_avoid(f1p_ctx* ctx, f1p_kmpc_qp_avoid* state, const f1p_kmpc_qp_avoid
 //   Cfg; NX (the state width), DUALS (rows per step: duals [E][DUALS T - 2]), AVOID_MAX_T (the avoidance variant's longest horizon)
 //   who ("kmpc" / "stmpc": the prefix of the messages), avoid_cap (the message past AVOID_MAX_T)
 //   EMPTY_RETURNS (the *_batch entries return F1P_OK at E == 0 before they stage)
-//   validate(ctx, cfg, E, opts, o), launch(ctx, E, cfg, max_iter, tol, io, avoid)
+//   validate(ctx, cfg, E, opts, o), launch(ctx, E, cfg, max_iter, tol, io, avoid, walls)
 //   obs(ctx), av(ctx): the planner's discs and its set_avoid switch
 // set_avoid is on: what the entry points check before they launch the avoidance variant on the context's discs, held in the order of the
 // caller's E egos (kcfg: a plan's kinematic branch, which runs k_kmpc_qp's variant)
@@ -172,10 +172,11 @@ int qp_avoid_plan_check(f1p_ctx* ctx, const typename Q::Cfg* cfg, int E, const f
 
 // io: the caller's arrays, on the host (staged: *_batch) or on the device (*_dev).  avoid null: the plain QP -- which a *_dev call runs as
 // the avoidance variant on the context's discs while set_avoid is on.  Else avoid holds the call's obs, M and outputs, and `numbers`
-// (nullable: the defaults) its margin, rho and lin.
+// (nullable: the defaults) its margin, rho and lin.  walls (with avoid; KinQp only): the wall variant (f1p_kmpc_qp_walls_*), whose obs may
+// be null with M = 0.
 template <class Q>
 int qp_call(f1p_ctx* ctx, bool staged, int E, const typename Q::Cfg* cfg, const f1p_kmpc_qp_opts* opts, const QpIo& io, const QpAvoidArgs* avoid,
-            const f1p_kmpc_qp_avoid* numbers) {
+            const f1p_kmpc_qp_avoid* numbers, const QpWallArgs* walls = nullptr) {
     F1P_ENTER(ctx);
     const std::string w = Q::who;
     f1p_kmpc_qp_opts o;
@@ -183,8 +184,13 @@ int qp_call(f1p_ctx* ctx, bool staged, int E, const typename Q::Cfg* cfg, const 
     int rc = Q::validate(ctx, cfg, E, opts, &o); if (rc) return rc;
     if (avoid) {
         if (cfg->horizon > Q::AVOID_MAX_T) return set_error(ctx, F1P_EINVAL, w + Q::avoid_cap);
-        if (avoid->M < 1 || avoid->M > F1P_KMPC_MAX_OBS) return set_error(ctx, F1P_EINVAL, w + " qp avoid: M must be in [1, 16]");
-        if (E > 0 && !avoid->obs) return set_error(ctx, F1P_EINVAL, w + " qp avoid: obs is NULL");
+        if (walls) {
+            if (avoid->M < 0 || avoid->M > F1P_KMPC_MAX_OBS) return set_error(ctx, F1P_EINVAL, w + " qp walls: M must be in [0, 16]");
+            if (E > 0 && avoid->M > 0 && !avoid->obs) return set_error(ctx, F1P_EINVAL, w + " qp walls: obs is NULL with M > 0");
+        } else {
+            if (avoid->M < 1 || avoid->M > F1P_KMPC_MAX_OBS) return set_error(ctx, F1P_EINVAL, w + " qp avoid: M must be in [1, 16]");
+            if (E > 0 && !avoid->obs) return set_error(ctx, F1P_EINVAL, w + " qp avoid: obs is NULL");
+        }
         f1p_kmpc_qp_avoid a;
         f1p_kmpc_qp_avoid_default(&a);
         if (numbers) a = *numbers;
@@ -199,7 +205,7 @@ int qp_call(f1p_ctx* ctx, bool staged, int E, const typename Q::Cfg* cfg, const 
             av = QpAvoidArgs(Q::obs(ctx).cur, Q::obs(ctx).M, Q::av(ctx));
             avoid = &av;
         }
-        return Q::launch(ctx, E, cfg, o.max_iter, o.tol, io, avoid ? &av : nullptr);
+        return Q::launch(ctx, E, cfg, o.max_iter, o.tol, io, avoid ? &av : nullptr, walls);
     }
     if (Q::EMPTY_RETURNS && E == 0) return F1P_OK;
     const size_t T = cfg->horizon, e = E, m = av.M, NX = Q::NX, ND = Q::DUALS * T - 2;
@@ -219,7 +225,7 @@ int qp_call(f1p_ctx* ctx, bool staged, int E, const typename Q::Cfg* cfg, const 
     d.u = s.out(io.u, e * T * 2); d.x = s.out(io.x, e * NX * (T + 1)); d.obj = s.out(io.obj, e);
     d.duals = s.out(io.duals, e * ND); d.iters = s.out(io.iters, e);
     av.eps = s.out(av.eps, e); av.planes = s.out(av.planes, e * T * 8); av.duals = s.out(av.duals, e * (2 * T + 1));
-    if ((rc = Q::launch(ctx, E, cfg, o.max_iter, o.tol, d, avoid ? &av : nullptr))) return rc;
+    if ((rc = Q::launch(ctx, E, cfg, o.max_iter, o.tol, d, avoid ? &av : nullptr, walls))) return rc;
     return s.finish();
 }
 // f1p_kmpc.hip: the argument checks of the four reference extractions (f1p_{kmpc,stmpc}_ref[_tracks]_{batch,dev}), and the *_batch body behind them:

@@ -216,8 +216,8 @@ struct DynQp {
     static constexpr const char *who = "stmpc", *avoid_cap = " qp avoid: horizon must be <= F1P_STMPC_QP_AVOID_MAX_T (40: the packed avoidance rows beside H and the Newton matrix in LDS)";
     static constexpr bool EMPTY_RETURNS = true;
     static int validate(f1p_ctx* ctx, const Cfg* cfg, int E, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o) { return validate_stmpc_qp(ctx, cfg, E, opts, o); }
-    static int launch(f1p_ctx* ctx, int E, const Cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid) {
-        return launch_stmpc_qp(ctx, E, cfg, max_iter, tol, io, avoid);
+    static int launch(f1p_ctx* ctx, int E, const Cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid, const QpWallArgs*) {
+        return launch_stmpc_qp(ctx, E, cfg, max_iter, tol, io, avoid);          // (wall rows: the kinematic QP only, never handed here)
     }
     static const ObsState& obs(const f1p_ctx* ctx) { return ctx->stmpc_obs; }
     static const f1p_kmpc_qp_avoid& av(const f1p_ctx* ctx) { return ctx->stmpc_qp_av; }

@@ -22,7 +22,12 @@
 // step t's first row is the fifth row of lane 2(t-1) (a_{t-1}), its second that of lane 2(t-1)+1 (delta_{t-1}), the eps lane's fifth row
 // is -eps <= 0.  The rows' u-coefficients are dense: kept in LDS (A, one row per lane, odd stride) before S becomes the Newton matrix.
 // The disc load, the choice of the two discs, the half-plane and its `planes` record are qp_avoid.h's, shared with k_stmpc_qp.hip.
-#include "qp_avoid.h"
+//
+// WALL (f1p_kmpc_qp_walls_*): the AV variant whose two rows per step are the two nearest of {the two nearest live discs, the
+// wall to the left of pbar_t, the wall to its right} on the active occupancy bitmap.  The two lanes of a step march one side each (lane
+// 2(t-1) left, lane 2(t-1)+1 right: n_samples independent bit tests, qp_walls.h), swap their first hits, and each takes its own of the four
+// candidates; from the half-plane on everything is the AV variant's.  M = 0 (no discs) is allowed here.
+#include "qp_walls.h"
 
 namespace f1p {
 
@@ -67,7 +72,7 @@ __host__ __device__ constexpr int qp_lds_doubles(int T, bool av) { return av ? Q
 
 }  // namespace
 
-// AvArgs: none (the plain QP), or one QpAvoidArgs (AV; f1p_internal.h)
+// AvArgs: none (the plain QP), one QpAvoidArgs (AV; f1p_internal.h), or a QpAvoidArgs and a QpWallArgs (WALL)
 template <int G, class... AvArgs>
 __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, const double* __restrict__ refg,
                                                 const double* pa_g, const double* pd_g, int pstride, int E, f1p_kmpc_cfg cfg,
@@ -76,7 +81,8 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
                                                 double* __restrict__ obj_out, double* __restrict__ duals, int32_t* __restrict__ iters_out,
                                                 double* warm_out, AvArgs... av_args) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    constexpr bool AV = sizeof...(AvArgs) == 1;
+    constexpr bool AV = sizeof...(AvArgs) >= 1;
+    constexpr bool WALL = sizeof...(AvArgs) == 2;
     [[maybe_unused]] const QpAvoidArgs av = qp_avoid_args(av_args...);
     constexpr int EPW = 64 / G;
     constexpr int R = AV ? 5 : 4;                  // inequality rows per lane
@@ -169,7 +175,36 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
     }
     // AV: this lane's half-plane (step tau + 1, the j-th nearest live disc), its row of A, and the eps lane's row of H
     [[maybe_unused]] QpPlane pl;
-    if constexpr (AV) {
+    if constexpr (WALL) {
+        // this lane's side of step tau + 1 (j = 0: left, j = 1: right) marched from pbar, the first hits swapped between the step's two
+        // lanes, then the j-th of the four candidates.  (The swap is outside the branch: lanes 2 tau and 2 tau + 1 are in or out of it together.)
+        const QpWallArgs wl = qp_wall_args(av_args...);
+        const bool act = in_n && !done;
+        const int t = tau + 1;
+        double px = 0.0, py = 0.0, llx = 0.0, lly = 0.0;                  // pbar and the LEFT direction (the right one is its negative)
+        int ks = 0;
+        if (act) {
+            double sn, cs;
+            px = L.px[tau]; py = L.py[tau];
+            sincos(L.pw[tau], &sn, &cs);
+            llx = -sn; lly = cs;
+            ks = j == 0 ? qp_wall_march(wl, px, py, llx, lly) : qp_wall_march(wl, px, py, -llx, -lly);
+        }
+        const int ko = __shfl_xor(ks, 1);
+        if (act) {
+            const double tt = (double)t * DTK;
+            const QpNearest nr = qp_avoid_nearest(L.ob, av.M, px, py, tt);
+            const QpCand d0 = qp_disc_cand(L.ob, nr.m0, px, py, tt), d1 = qp_disc_cand(L.ob, nr.m1, px, py, tt);
+            const QpWallCand wL = qp_wall_cand(wl, px, py, llx, lly, j == 0 ? ks : ko, F1P_QP_WALL_SLOT_L);
+            const QpWallCand wR = qp_wall_cand(wl, px, py, -llx, -lly, j == 0 ? ko : ks, F1P_QP_WALL_SLOT_R);
+            const int pick = qp_select4(d0, d1, wL, wR, j);
+            if (pick == 0 || pick == 1) pl = qp_avoid_plane(L.ob, pick == 0 ? nr.m0 : nr.m1, px, py, L.pw[tau], tt, L.fr[t], L.fr[Tp + t], av.margin);
+            else if (pick == 2) pl = qp_wall_plane(wL, llx, lly, L.fr[t], L.fr[Tp + t], wl.margin);
+            else if (pick == 3) pl = qp_wall_plane(wR, -llx, -lly, L.fr[t], L.fr[Tp + t], wl.margin);
+            for (int c = 0; c < n; ++c)
+                L.A[i * nq + c] = pl.slot >= 0 ? -(pl.nx * L.S[(4 * t + 0) * n + c] + pl.ny * L.S[(4 * t + 1) * n + c]) : 0.0;
+        }
+    } else if constexpr (AV) {
         if (in_n && !done) {
             const int t = tau + 1;
             const double tt = (double)t * DTK, px = L.px[tau], py = L.py[tau];
@@ -179,6 +214,8 @@ __global__ __launch_bounds__(64) void k_kmpc_qp(const double* __restrict__ x0g, 
             for (int c = 0; c < n; ++c)
                 L.A[i * nq + c] = pl.slot >= 0 ? -(pl.nx * L.S[(4 * t + 0) * n + c] + pl.ny * L.S[(4 * t + 1) * n + c]) : 0.0;
         }
+    }
+    if constexpr (AV) {
         if (i == n && !done) {
             for (int c = 0; c < n; ++c) L.H[n * nq + c] = 0.0;
             L.H[n * nq + n] = 2.0 * av.rho;
@@ -374,12 +411,15 @@ static int kmpc_qp_pack(const f1p_ctx* ctx, int T) {
 }
 
 // egos per wave: the plain QP four or one (kmpc_qp_pack); the avoidance variant, 2T + 1 lanes per ego, two while they fit 32 lanes
-// (T <= 15), else one
-int launch_kmpc_qp(f1p_ctx* ctx, int E, const f1p_kmpc_cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid) {
+// (T <= 15), else one; the wall variant as the avoidance variant
+int launch_kmpc_qp(f1p_ctx* ctx, int E, const f1p_kmpc_cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid,
+                   const QpWallArgs* walls) {
     if (E <= 0) return F1P_OK;
     const int T = cfg->horizon;
     if (avoid && (T > 31 || avoid->M < 0 || avoid->M > F1P_KMPC_MAX_OBS || (avoid->M > 0 && !avoid->obs)))
         return set_error(ctx, F1P_EINVAL, "kmpc qp avoid: bad horizon / obstacles");
+    if (walls && (!avoid || !walls->g.bits || walls->g.w < 1 || walls->g.h < 1 || walls->n_samples < 1 || walls->n_samples > F1P_KMPC_QP_WALL_MAX_SAMPLES))
+        return set_error(ctx, F1P_EINVAL, "kmpc qp walls: bad grid / n_samples");
     const int epw = avoid ? (2 * T + 1 <= 32 ? 2 : 1) : (kmpc_qp_pack(ctx, T) == 4 ? 4 : 1);
     const size_t lds = sizeof(double) * (size_t)qp_lds_doubles(T, avoid != nullptr) * epw;
     const auto launch = [&](auto kern, const char* what, auto... av) {
@@ -389,6 +429,8 @@ int launch_kmpc_qp(f1p_ctx* ctx, int E, const f1p_kmpc_cfg* cfg, int max_iter, d
                            *cfg, max_iter, tol, io.steer, io.speed, io.status, io.u, io.x, io.obj, io.duals, io.iters, io.warm_out, av...);
         return check_hip(ctx, hipGetLastError(), what);
     };
+    if (walls) return epw == 2 ? launch(&k_kmpc_qp<32, QpAvoidArgs, QpWallArgs>, "k_kmpc_qp_walls launch", *avoid, *walls)
+                               : launch(&k_kmpc_qp<64, QpAvoidArgs, QpWallArgs>, "k_kmpc_qp_walls launch", *avoid, *walls);
     if (avoid) return epw == 2 ? launch(&k_kmpc_qp<32, QpAvoidArgs>, "k_kmpc_qp_avoid launch", *avoid)
                                : launch(&k_kmpc_qp<64, QpAvoidArgs>, "k_kmpc_qp_avoid launch", *avoid);
     return epw == 4 ? launch(&k_kmpc_qp<16>, "k_kmpc_qp launch") : launch(&k_kmpc_qp<64>, "k_kmpc_qp launch");

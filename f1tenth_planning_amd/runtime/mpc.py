@@ -50,6 +50,26 @@ def kmpc_qp_set_avoid(ctx, avoid):
     ctx._check(ctx.lib.f1p_kmpc_qp_set_avoid(ctx.h, _ref(avoid)))
 
 
+def kmpc_qp_walls(ctx, x0, ref, obs, cfg, avoid=None, walls=None, oa_prev=None, od_prev=None, opts=None, want_u=True, want_xk=False, want_obj=True,
+                  want_duals=False, want_iters=True, want_eps=True, want_planes=False, want_avoid_duals=False):
+    """kmpc_qp_avoid with wall rows from the context's ACTIVE occupancy bitmap (f1p_kmpc_qp_walls_batch): per step the two
+    nearest of {the two nearest live discs, the wall to the left of the previous solution's path, the wall to its right} become the step's
+    rows.  obs [E, M, 5] with M in 0..16, or None (no discs); walls: _abi.kmpc_qp_walls(n_samples, margin) (None: the defaults) -- n_samples
+    steps of res / 2 per side.  Needs set_grid and no oriented footprint.  A soft, linearised avoidance term, not a guarantee.  -> kmpc_qp_avoid's
+    dict; planes' slot 16 / 17: the left / right wall.  (A module function: Context's public methods are a pinned record.)"""
+    if obs is None:
+        obs = np.zeros((_f64(x0, (-1, 4)).shape[0], 0, 5))
+    return _mpc_qp(ctx, ctx.lib.f1p_kmpc_qp_walls_batch, 4, "xk", 8, x0, ref, cfg, oa_prev, od_prev, opts, want_u, want_xk, want_obj, want_duals,
+                   want_iters, (obs, avoid, want_eps, want_planes, want_avoid_duals), walls=(_ref(walls),))
+
+
+def kmpc_qp_set_walls(ctx, walls):
+    """f1p_kmpc_qp_set_walls on Context `ctx`: while on, kmpc_qp_plan and kmpc_qp_dev solve kmpc_qp_walls' problem on the grid the context
+    holds at each call, with the discs of kmpc_set_obstacles[_dev] while kmpc_qp_set_avoid is on as well (else none) and its rho / lin;
+    walls: _abi.kmpc_qp_walls(...), None (or on=False) turns it off"""
+    ctx._check(ctx.lib.f1p_kmpc_qp_set_walls(ctx.h, _ref(walls)))
+
+
 def stmpc_qp_avoid(ctx, x0, ref, obs, cfg, avoid=None, oa_prev=None, od_v_prev=None, opts=None, want_u=True, want_x=False, want_obj=True,
                    want_duals=False, want_iters=True, want_eps=True, want_planes=False, want_avoid_duals=False):
     """Context.stmpc_qp with moving-disc avoidance rows (f1p_stmpc_qp_avoid_batch) on Context `ctx`: obs [E, M, 5] fp64 rows
@@ -68,10 +88,11 @@ def stmpc_qp_set_avoid(ctx, avoid):
     ctx._check(ctx.lib.f1p_stmpc_qp_set_avoid(ctx.h, _ref(avoid)))
 
 
-def _mpc_qp(ctx, fn, n, xname, duals_per_step, x0, ref, cfg, oa_prev, od_prev, opts, want_u, want_x, want_obj, want_duals, want_iters, av=None):
-    """the four stateless QP calls (Context.kmpc_qp / stmpc_qp, kmpc_qp_avoid / stmpc_qp_avoid).  n: the state width; xname: the key of the
-    predicted states [E, n, T+1]; duals [E, duals_per_step * T - 2]; av: None, or the avoidance rows' (obs, avoid, want_eps, want_planes,
-    want_avoid_duals)"""
+def _mpc_qp(ctx, fn, n, xname, duals_per_step, x0, ref, cfg, oa_prev, od_prev, opts, want_u, want_x, want_obj, want_duals, want_iters, av=None,
+            walls=()):
+    """the stateless QP calls (Context.kmpc_qp / stmpc_qp, kmpc_qp_avoid / stmpc_qp_avoid, kmpc_qp_walls).  n: the state width; xname: the key
+    of the predicted states [E, n, T+1]; duals [E, duals_per_step * T - 2]; av: None, or the avoidance rows' (obs, avoid, want_eps,
+    want_planes, want_avoid_duals); walls: the arguments that follow `avoid` (kmpc_qp_walls: its struct), where obs may be [E, 0, 5]"""
     x0 = _f64(x0, (-1, n)); E = x0.shape[0]; T = cfg.horizon
     ref = _f64(ref, (E, n, T + 1))
     wants = [("u", want_u, (E, T, 2), np.float64), (xname, want_x, (E, n, T + 1), np.float64), ("obj", want_obj, (E,), np.float64),
@@ -84,7 +105,7 @@ def _mpc_qp(ctx, fn, n, xname, duals_per_step, x0, ref, cfg, oa_prev, od_prev, o
             raise ValueError(f"obstacles must be [E={E}, M, 5] = (x, y, vx, vy, r)")
         wants += [("eps", want_eps, (E,), np.float64), ("planes", want_planes, (E, T, 2, 4), np.float64),
                   ("avoid_duals", want_avoid_duals, (E, 2 * T + 1), np.float64)]
-        av_in, av_keys = (_ptr(o), o.shape[1], _ref(avoid)), ("eps", "planes", "avoid_duals")
+        av_in, av_keys = (None if walls and not o.size else _ptr(o), o.shape[1], _ref(avoid), *walls), ("eps", "planes", "avoid_duals")
     oa = None if oa_prev is None else _f64(oa_prev, (E, T))
     od = None if od_prev is None else _f64(od_prev, (E, T))
     out = dict(steer=np.empty(E), speed=np.empty(E), status=np.empty(E, np.int32))

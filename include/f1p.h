@@ -776,6 +776,59 @@ int f1p_kmpc_qp_avoid_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref,
                           double* d_obj, double* d_duals, int32_t* d_iters, double* d_eps, double* d_planes, double* d_avoid_duals);
 int f1p_kmpc_qp_set_avoid(f1p_ctx* ctx, const f1p_kmpc_qp_avoid* avoid);
 
+/* Walls in the QP: the occupancy grid as SOFT, LINEARISED half-plane rows beside the discs'.  An avoidance term, not a
+ * guarantee.  The problem of f1p_kmpc_qp_avoid_* is kept as it is -- the same u and the same linearisation path pbar_t, psibar_t (the
+ * walk of the previous solution), the same 8T-2 plain rows, the same slack eps as input 2T with cost rho eps^2 + lin eps and the row
+ * -eps <= 0, and AT MOST TWO avoidance rows per step t = 1..T, one per lane of the step.  New: per step two wall candidates compete with
+ * the live discs for those two rows.  The bitmap is the ACTIVE one (f1p_set_grid dilated by f1p_inflate_grid), the cell rule the
+ * collision tests' (cell = floor((p - origin) * (1 / res))); a cell outside the image or a non-finite coordinate counts as occupied.  res is
+ * f1p_set_grid's and h = 0.5 * res.  For side sigma = +1 (left, slot 16) and sigma = -1 (right, slot 17):
+ *   l = sigma (-sin psibar_t, cos psibar_t);
+ *   the samples are q_k = pbar_t + ((double)k * h) l for k = 1 .. n_samples;
+ *   k* is the first k whose q_k is occupied; if there is none, this side has no candidate;
+ *   the contact is the last free sample, c = q_{k*-1}, with q_0 = pbar_t;
+ *   the candidate's clearance is clear = (double)(k* - 1) * h -- pbar_t's own cell is not tested;
+ *   the normal is n = -l;
+ *   the row is  -n.(S_xy(t) u) - eps <= n.(s_xy(t) - c) - wall_margin.
+ * Selection per step: among the live discs (clear = dist - r, unchanged) and the two wall candidates the two smallest clear are taken,
+ * ties to the lower slot -- discs before walls, left before right; lane j of the step takes the j-th.
+ * planes[e][t][j] = (n_x, n_y, right-hand side, slot) with slots 0..15 a disc, 16 / 17 a wall, and -1 with zeros when absent;
+ * avoid_duals keeps its layout.
+ * The problem is feasible whenever the plain one is; statuses 1 and 3 keep their causes (the bitmap adds none); an ego with no candidate
+ * at any step has the plain QP's optimum.
+ * Limits: the rows are soft and linearised, an avoidance term and not a guarantee.  Two rows per step is a cap: with two discs nearer than
+ * both walls at a step, that step has no wall row.  A march at res / 2 can step over the corner of a cell.  A pbar_t that already lies
+ * inside the inflated wall is softly pinned between its two contacts, not pushed out.
+ * Status 2 (not converged: the last iterate) is returned as for f1p_kmpc_qp_avoid_*; rows that bind with a positive slack make it more
+ * frequent than in the plain QP, and the iterate is then usually the optimum to many digits.
+ * Arguments: n_samples in 1..256 (else F1P_EINVAL), wall_margin (`margin`) finite, 2 <= horizon <= 31; the calls need a grid
+ * (F1P_ESTATE without one) and no oriented footprint (f1p_set_footprint with n_discs > 0: F1P_ESTATE -- the rows are a point / disc
+ * test, use f1p_inflate_grid).
+ * f1p_kmpc_qp_walls_batch / _dev: f1p_kmpc_qp_avoid_batch / _dev with obs nullable and M in 0..16, and `walls` after `avoid` (NULL: the
+ *   defaults; `on` is not read); the same outputs.
+ * f1p_kmpc_qp_set_walls: NULL or on = 0 turns it off (the default).  While on, f1p_kmpc_qp_plan_batch and f1p_kmpc_qp_dev solve this
+ *   problem: the discs are those of f1p_kmpc_set_obstacles[_dev], taken only while f1p_kmpc_qp_set_avoid is on as well (otherwise M = 0);
+ *   rho and lin (and the discs' margin) are the context's f1p_kmpc_qp_set_avoid values whether or not it is on -- the defaults if it was
+ *   never called.  The bitmap is read at launch: a later f1p_set_grid / f1p_inflate_grid is picked up by the next call. */
+#define F1P_KMPC_QP_WALL_MAX_SAMPLES 256
+typedef struct f1p_kmpc_qp_walls {
+    int32_t on;              /* f1p_kmpc_qp_set_walls: 0 turns the rows off                       */
+    int32_t n_samples;       /* samples per side, h = res / 2 apart, 1 .. 256 (48)                */
+    double margin;           /* wall_margin: the rows keep this far from the contact [m] (0)     */
+} f1p_kmpc_qp_walls;
+void f1p_kmpc_qp_walls_default(f1p_kmpc_qp_walls* walls);
+int f1p_kmpc_qp_walls_batch(f1p_ctx* ctx, const double* x0, const double* ref, const double* oa_prev, const double* od_prev, int32_t E,
+                            const f1p_kmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* obs, int32_t M,
+                            const f1p_kmpc_qp_avoid* avoid, const f1p_kmpc_qp_walls* walls, double* steer, double* speed, int32_t* status,
+                            double* u, double* xk, double* obj, double* duals, int32_t* iters, double* eps, double* planes,
+                            double* avoid_duals);
+int f1p_kmpc_qp_walls_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_prev, int32_t E,
+                          const f1p_kmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* d_obs, int32_t M,
+                          const f1p_kmpc_qp_avoid* avoid, const f1p_kmpc_qp_walls* walls, double* d_steer, double* d_speed,
+                          int32_t* d_status, double* d_u, double* d_xk, double* d_obj, double* d_duals, int32_t* d_iters, double* d_eps,
+                          double* d_planes, double* d_avoid_duals);
+int f1p_kmpc_qp_set_walls(f1p_ctx* ctx, const f1p_kmpc_qp_walls* walls);
+
 /* ------------------------------------------------------------------------------------------------
  * Dynamic single-track MPC as the reference solves it: the linearised QP of control/dynamic_mpc/dynamic_mpc.py, batched, fp64
  * (csrc/k_stmpc_qp.hip).  Per ego:
