@@ -331,6 +331,11 @@ PROTOTYPES = {
     "f1p_kmpc_qp_walls_dev": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(KmpcCfg), C.POINTER(KmpcQpOpts), _P, _I, C.POINTER(KmpcQpAvoid),
                                         C.POINTER(KmpcQpWalls), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "f1p_kmpc_qp_set_walls": (C.c_int, [_P, C.POINTER(KmpcQpWalls)]),
+    "f1p_stmpc_qp_walls_batch": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcQpOpts), _P, _I, C.POINTER(KmpcQpAvoid),
+                                           C.POINTER(KmpcQpWalls), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f1p_stmpc_qp_walls_dev": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcQpOpts), _P, _I, C.POINTER(KmpcQpAvoid),
+                                         C.POINTER(KmpcQpWalls), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "f1p_stmpc_qp_set_walls": (C.c_int, [_P, C.POINTER(KmpcQpWalls)]),
     "f1p_stmpc_qp_avoid_batch": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcQpOpts), _P, _I, C.POINTER(KmpcQpAvoid),
                                            _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "f1p_stmpc_qp_avoid_dev": (C.c_int, [_P, _P, _P, _P, _P, _I, C.POINTER(StmpcCfg), C.POINTER(KmpcQpOpts), _P, _I, C.POINTER(KmpcQpAvoid),

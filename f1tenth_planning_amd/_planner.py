@@ -138,11 +138,19 @@ def _diag(m):
     return np.diag(m) if m.ndim == 2 else m
 
 
-def check_solver(c, weights, substeps, tk_within_t=False, avoid_max_t=None, walls=False):
+def qp_walls_field(c):
+    """the name of the config's wall switch that is on -- QP_WALLS (KMPCPlanner's mpc_config) or QP_WALLS_ST (STMPCPlanner's) -- or None"""
+    for name in ("QP_WALLS", "QP_WALLS_ST"):
+        if getattr(c, name, False):
+            return name
+    return None
+
+
+def check_solver(c, weights, substeps, tk_within_t=False, avoid_max_t=None, walls=False, walls_st=False):
     """ValueError before anything touches the GPU: an unknown SOLVER, weights the QP path does not take (diagonal only), a COLLISION
     setting without meaning.  weights: ((mpc_config field, size), ...) of the QP's weight matrices; substeps: the fields that count tested
     points per step; tk_within_t: the QP also needs TK <= T (STMPCPlanner); avoid_max_t: QP_AVOID's cap on T (STMPCPlanner's dynamic QP);
-    walls: the planner's QP has wall rows (QP_WALLS: KMPCPlanner)."""
+    walls: the planner's QP has wall rows behind QP_WALLS (KMPCPlanner); walls_st: behind QP_WALLS_ST (STMPCPlanner, both branches)."""
     if c.SOLVER not in SOLVERS:
         raise ValueError(f"mpc_config.SOLVER must be one of {SOLVERS}, not {c.SOLVER!r}")
     if c.SOLVER == "qp":
@@ -167,18 +175,23 @@ def check_solver(c, weights, substeps, tk_within_t=False, avoid_max_t=None, wall
             raise ValueError("mpc_config.QP_AVOID needs TK <= 31 (the slack takes the 64th lane's place)")
         if avoid_max_t is not None and int(c.T) > avoid_max_t:
             raise ValueError(f"mpc_config.QP_AVOID needs T <= {avoid_max_t} (F1P_STMPC_QP_AVOID_MAX_T: the avoidance rows share the CU's LDS with the Newton matrix)")
-    if getattr(c, "QP_WALLS", False):
-        if not walls:
-            raise ValueError("QP_WALLS: KMPCPlanner only")
+    if getattr(c, "QP_WALLS", False) and not walls:
+        raise ValueError("QP_WALLS: KMPCPlanner only")
+    if getattr(c, "QP_WALLS_ST", False) and not walls_st:
+        raise ValueError("QP_WALLS_ST: STMPCPlanner only")
+    wf = qp_walls_field(c)
+    if wf:
         if c.SOLVER != "qp":
-            raise ValueError("mpc_config.QP_WALLS adds wall rows to the QP; the shooting solver tests its rollouts with COLLISION (SOLVER='qp')")
+            raise ValueError(f"mpc_config.{wf} adds wall rows to the QP; the shooting solver tests its rollouts with COLLISION (SOLVER='qp')")
         reach, margin = float(c.QP_WALL_REACH), float(c.QP_WALL_MARGIN)
         if not (reach > 0.0 and np.isfinite(reach)):
             raise ValueError(f"mpc_config.QP_WALL_REACH must be finite and > 0, not {c.QP_WALL_REACH!r}")
         if not np.isfinite(margin):
             raise ValueError(f"mpc_config.QP_WALL_MARGIN must be finite, not {c.QP_WALL_MARGIN!r}")
         if int(c.TK) > 31:
-            raise ValueError("mpc_config.QP_WALLS needs TK <= 31 (the slack takes the 64th lane's place)")
+            raise ValueError(f"mpc_config.{wf} needs TK <= 31 (the slack takes the 64th lane's place)")
+        if wf == "QP_WALLS_ST" and avoid_max_t is not None and int(c.T) > avoid_max_t:
+            raise ValueError(f"mpc_config.QP_WALLS_ST needs T <= {avoid_max_t} (F1P_STMPC_QP_AVOID_MAX_T: the wall rows share the CU's LDS with the Newton matrix)")
     if c.COLLISION:
         if c.SOLVER == "qp":
             raise ValueError("mpc_config.COLLISION tests the shooting solver's rollouts; SOLVER='qp' has none")
@@ -208,8 +221,8 @@ def qp_wall_samples(reach, resolution):
 
 
 def qp_walls(c, resolution):
-    """mpc_config.QP_WALL* as the f1p_kmpc_qp_walls struct for a map of this resolution, None while QP_WALLS is off"""
-    if not getattr(c, "QP_WALLS", False):
+    """mpc_config.QP_WALL* as the f1p_kmpc_qp_walls struct for a map of this resolution, None while QP_WALLS / QP_WALLS_ST is off"""
+    if not qp_walls_field(c):
         return None
     return _abi.kmpc_qp_walls(True, qp_wall_samples(c.QP_WALL_REACH, resolution), c.QP_WALL_MARGIN)
 
@@ -248,18 +261,20 @@ class MPCPlanner(OccupancyMap, Planner):
     _TK_WITHIN_T = False
     _QP_AVOID_MAX_T = None                 # mpc_config.QP_AVOID's cap on T, where the planner's QP has one
     _QP_WALLS = False                      # the planner's QP takes mpc_config.QP_WALLS
+    _QP_WALLS_ST = False                   # ... mpc_config.QP_WALLS_ST (STMPCPlanner: its config's QP_WALLS keeps raising)
 
     def _check_solver(self):
-        check_solver(self.config, self._QP_WEIGHTS, self._SUBSTEPS, self._TK_WITHIN_T, self._QP_AVOID_MAX_T, self._QP_WALLS)
+        check_solver(self.config, self._QP_WEIGHTS, self._SUBSTEPS, self._TK_WITHIN_T, self._QP_AVOID_MAX_T, self._QP_WALLS, self._QP_WALLS_ST)
 
     def _check_collision(self):
         """ValueError before anything touches the GPU: the checks of check_solver, and COLLISION / QP_WALLS without a map"""
         self._check_solver()
         if self.config.COLLISION and self._map is None:
             raise ValueError("mpc_config.COLLISION needs an occupancy grid: call set_map / load_map first")
-        if getattr(self.config, "QP_WALLS", False):
+        wf = qp_walls_field(self.config)
+        if wf:
             if self._map is None:
-                raise ValueError("mpc_config.QP_WALLS needs an occupancy grid: call set_map / load_map first")
+                raise ValueError(f"mpc_config.{wf} needs an occupancy grid: call set_map / load_map first")
             qp_wall_samples(self.config.QP_WALL_REACH, self._map[1])
 
     # the attribute `obstacles` (moving discs, DESIGN.md 5j / 5k): the next plan / plan_batch call TAKES it -- None again afterwards, also

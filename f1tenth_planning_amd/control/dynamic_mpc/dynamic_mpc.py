@@ -28,6 +28,13 @@ mpc_config.QP_AVOID = True (SOLVER="qp" only) lets the QP take `obstacles` (plan
 `tracks`) as well: in both branches the two discs nearest to the previous solution's path become, per step, half-plane rows of the QP,
 softened by one slack variable with the cost QP_AVOID_RHO eps^2 + QP_AVOID_LIN eps (f1p_stmpc_qp_set_avoid).  The rows are
 linearised and soft -- an avoidance term, not a guarantee; QP_AVOID_MARGIN [m] widens every disc.  T <= 40, TK <= 31.
+
+mpc_config.QP_WALLS_ST = True (SOLVER="qp" only, needs set_map / load_map) lets both branches' QPs see the map: per step the walls found within
+QP_WALL_REACH metres to the left and to the right of the previous solution's path -- of its direction of travel yaw + beta in the dynamic
+branch -- on the occupancy grid as inflated by set_map(inflate=...) compete with the discs for the step's two half-plane rows
+(f1p_stmpc_qp_set_walls).  Soft and linearised like the discs' rows and under the same slack; QP_WALL_MARGIN [m] keeps the rows
+that far off the contact.  Works with plan, plan_batch, tracks, obstacles and rivals, with or without QP_AVOID.  T <= 40, TK <= 31.  (The
+field is not called QP_WALLS: that name was KMPCPlanner's first and raises here, a pinned behaviour.)
 """
 import warnings
 from dataclasses import dataclass, field
@@ -35,9 +42,9 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ... import _abi
-from ..._planner import MPCPlanner, _course_columns, _diag, _track_columns, kin_cfg_struct, qp_avoid, qp_opts
+from ..._planner import MPCPlanner, _course_columns, _diag, _track_columns, kin_cfg_struct, qp_avoid, qp_opts, qp_walls
 from ..._rivals import SINGLE_EGO, RivalFeed
-from ...runtime import Context, kmpc_set_obstacles, stmpc_qp_set_avoid, stmpc_set_obstacles, stmpc_set_obstacles_dev
+from ...runtime import Context, kmpc_set_obstacles, stmpc_qp_set_avoid, stmpc_qp_set_walls, stmpc_set_obstacles, stmpc_set_obstacles_dev
 from ..kinematic_mpc.kinematic_mpc import State  # noqa: F401  (same 7-field dataclass, :89-98)
 
 
@@ -93,6 +100,11 @@ class mpc_config:
     QP_AVOID_RHO: float = field(default=1e4, repr=False)  # the slack's quadratic penalty
     QP_AVOID_LIN: float = field(default=10.0, repr=False)  # the slack's linear penalty
     QP_WALLS: bool = field(default=False, repr=False)  # the kinematic QP's wall rows: KMPCPlanner only, True raises here
+    # SOLVER="qp" only: the occupancy grid of set_map / load_map as soft, linearised wall rows of both branches' QPs.  Not
+    # QP_WALLS: that field raises "KMPCPlanner only" here, which tests/test_kmpc_qp_walls_host.py pins, so this planner's switch has a name of its own
+    QP_WALLS_ST: bool = field(default=False, repr=False)
+    QP_WALL_REACH: float = field(default=1.5, repr=False)  # how far to each side a wall is looked for [m]: ceil(reach / (resolution / 2)) samples, <= 256
+    QP_WALL_MARGIN: float = field(default=0.0, repr=False)  # kept between the path and the last free sample before the wall [m]
 
 
 class STMPCPlanner(MPCPlanner):
@@ -108,6 +120,7 @@ class STMPCPlanner(MPCPlanner):
     _SUBSTEPS = ("COLLISION_SUBSTEPS", "COLLISION_SUBSTEPS_K")
     _TK_WITHIN_T = True
     _QP_AVOID_MAX_T = _abi.STMPC_QP_AVOID_MAX_T
+    _QP_WALLS_ST = True
 
     def __init__(self, waypoints=None, config=mpc_config(),
                  params=np.array([3.74, 0.15875, 0.17145, 0.074, 4.718, 5.4562, 0.04712, 1.0489]), debug=False, device=None):
@@ -128,6 +141,7 @@ class STMPCPlanner(MPCPlanner):
         self.obstacles = None              # moving discs of the NEXT plan, which takes them: [M, 5] for plan(), [E, M, 5] for plan_batch()
         self._obstacles_set = [False, False]   # the context holds obstacles of an earlier plan: the kmpc state, the stmpc state
         self._qp_avoid_set = False         # the context's avoidance rows are switched on (mpc_config.QP_AVOID of an earlier plan)
+        self._qp_walls_set = False         # ... and its wall rows (mpc_config.QP_WALLS_ST of an earlier plan)
         self.rivals = None                 # Rivals(...): every plan_batch tests each ego against its nearest other vehicles; persistent
         self._rival_feed = RivalFeed("st7", lambda ctx: stmpc_set_obstacles_dev(ctx, None))
         self._check_solver()
@@ -142,6 +156,10 @@ class STMPCPlanner(MPCPlanner):
             if av is not None or self._qp_avoid_set:             # (off after plans with it off: nothing to switch, no call -- as before QP_AVOID)
                 stmpc_qp_set_avoid(ctx, av)                      # (None: off -- the QP then ignores whatever the context holds)
                 self._qp_avoid_set = av is not None
+            wl = qp_walls(c, self._map[1]) if c.QP_WALLS_ST else None
+            if wl is not None or self._qp_walls_set:
+                stmpc_qp_set_walls(ctx, wl)
+                self._qp_walls_set = wl is not None
             if av is not None:                                   # both branches of the QP plan read the stmpc state, in the caller's order
                 if rivals is not None:
                     d_obs, _, E, M = self._rival_feed.run(ctx, rivals, states, horizon=(max(float(c.T) * float(c.DT), float(c.TK) * float(c.DTK)), 0.0),

@@ -172,7 +172,7 @@ int qp_avoid_plan_check(f1p_ctx* ctx, const typename Q::Cfg* cfg, int E, const f
 
 // io: the caller's arrays, on the host (staged: *_batch) or on the device (*_dev).  avoid null: the plain QP -- which a *_dev call runs as
 // the avoidance variant on the context's discs while set_avoid is on.  Else avoid holds the call's obs, M and outputs, and `numbers`
-// (nullable: the defaults) its margin, rho and lin.  walls (with avoid; KinQp only): the wall variant (f1p_kmpc_qp_walls_*), whose obs may
+// (nullable: the defaults) its margin, rho and lin.  walls (with avoid): the wall variant (f1p_{kmpc,stmpc}_qp_walls_*), whose obs may
 // be null with M = 0.
 template <class Q>
 int qp_call(f1p_ctx* ctx, bool staged, int E, const typename Q::Cfg* cfg, const f1p_kmpc_qp_opts* opts, const QpIo& io, const QpAvoidArgs* avoid,
@@ -228,6 +228,62 @@ int qp_call(f1p_ctx* ctx, bool staged, int E, const typename Q::Cfg* cfg, const 
     if ((rc = Q::launch(ctx, E, cfg, o.max_iter, o.tol, d, avoid ? &av : nullptr, walls))) return rc;
     return s.finish();
 }
+
+// ---- wall rows (k_kmpc_qp.hip / k_stmpc_qp.hip WALL): one body over KinQp / DynQp ------------------------------------
+template <class Q>
+int validate_qp_walls(f1p_ctx* ctx, const f1p_kmpc_qp_walls* w) {
+    if (w->n_samples < 1 || w->n_samples > F1P_KMPC_QP_WALL_MAX_SAMPLES || !isfinite(w->margin))
+        return set_error(ctx, F1P_EINVAL, std::string(Q::who) + " qp walls: n_samples must be in [1, 256] and margin finite");
+    return F1P_OK;
+}
+
+// w (nullable: the defaults), checked, and the context's grid as it is now -> the kernel's arguments
+template <class Q>
+int qp_wall_args(f1p_ctx* ctx, const f1p_kmpc_qp_walls* w, QpWallArgs* out) {
+    const std::string who = Q::who;
+    f1p_kmpc_qp_walls d;
+    f1p_kmpc_qp_walls_default(&d);
+    if (w) d = *w;
+    const int rc = validate_qp_walls<Q>(ctx, &d); if (rc) return rc;
+    if (!ctx->has_grid) return set_error(ctx, F1P_ESTATE, who + " qp walls are on but no occupancy grid is loaded (f1p_set_grid)");
+    if (ctx->n_disc > 0)
+        return set_error(ctx, F1P_ESTATE, who + " qp walls are a point / disc test: remove the oriented footprint (f1p_set_footprint) and use f1p_inflate_grid");
+    out->g = grid_dev(ctx);
+    out->h = 0.5 * ctx->res;
+    out->n_samples = d.n_samples;
+    out->margin = d.margin;
+    return F1P_OK;
+}
+
+// f1p_{kmpc,stmpc}_qp_set_walls on the planner's own switch `state`
+template <class Q>
+int qp_set_walls(f1p_ctx* ctx, f1p_kmpc_qp_walls* state, const f1p_kmpc_qp_walls* walls) {
+    F1P_ENTER(ctx);
+    if (!walls || !walls->on) { state->on = 0; return F1P_OK; }
+    const int rc = validate_qp_walls<Q>(ctx, walls); if (rc) return rc;
+    *state = *walls;
+    state->on = 1;
+    return F1P_OK;
+}
+
+// the wall problem of E egos.  av null: the discs the context holds (while the planner's set_avoid is on, else none) with its numbers.
+// cfg, opts and the horizon's cap are qp_call's to check.
+template <class Q>
+int qp_walls_call(f1p_ctx* ctx, bool staged, int E, const typename Q::Cfg* cfg, const f1p_kmpc_qp_opts* opts, const QpIo& io, const QpAvoidArgs* av,
+                  const f1p_kmpc_qp_avoid* numbers, const f1p_kmpc_qp_walls* walls) {
+    F1P_ENTER(ctx);
+    QpWallArgs wl;
+    int rc = qp_wall_args<Q>(ctx, walls, &wl); if (rc) return rc;
+    QpAvoidArgs held;
+    if (!av) {
+        const bool on = Q::av(ctx).on;
+        if (on && cfg && (rc = qp_avoid_plan_check<Q>(ctx, cfg, E))) return rc;
+        held = QpAvoidArgs(on ? Q::obs(ctx).cur : nullptr, on ? Q::obs(ctx).M : 0, Q::av(ctx));
+        av = &held; numbers = &Q::av(ctx);
+    }
+    return qp_call<Q>(ctx, staged, E, cfg, opts, io, av, numbers, &wl);
+}
+
 // f1p_kmpc.hip: the argument checks of the four reference extractions (f1p_{kmpc,stmpc}_ref[_tracks]_{batch,dev}), and the *_batch body behind them:
 // ncol = 4 (kinematic rows) or 7 (dynamic rows); track_id (host) is read when tracks, else every ego follows the raceline
 int validate_ref(f1p_ctx* ctx, const void* states, const int32_t* track_id, bool tracks, int E, int horizon, double dt, double dl, const void* ref);

@@ -116,6 +116,7 @@ struct f1p_ctx {
     int kmpc_qp_pack = 0;              // egos per wave at T <= 8: 0 = default, 1 or 4 forces it (timing runs)
     f1p_kmpc_qp_avoid kmpc_qp_av = {0, 0, 0.0, 1e4, 10.0};   // f1p_kmpc_qp_set_avoid: on = the plan entry points take kmpc_obs as half-plane rows
     f1p_kmpc_qp_walls kmpc_qp_walls = {0, 48, 0.0};          // f1p_kmpc_qp_set_walls: on = they take the active bitmap's walls as rows too
+    f1p_kmpc_qp_walls stmpc_qp_walls = {0, 48, 0.0};         // f1p_stmpc_qp_set_walls: the dynamic planner's own switch
     // the dynamic-MPC QP plan (f1p_stmpc_qp_plan_batch): fp64 warm start [E][W][2] = (oa, odelta_v), W = max(T, TK), keyed by (E, W);
     // per ego the length of the reference's self.oa (0: None) -- the branch's horizon -- on the host (the branch split is made there)
     WarmBuf stmpc_qp_warm;
@@ -318,10 +319,11 @@ struct QpWallArgs {
     double margin = 0.0;
 };
 // avoid null: the plain QP.  With it: T <= 31 (kinematic: 2T + 1 lanes per ego) / F1P_STMPC_QP_AVOID_MAX_T (dynamic), M in [0, 16].
-// walls (with avoid; kinematic only): the wall variant
+// walls (with avoid): the wall variant
 int launch_kmpc_qp(f1p_ctx* ctx, int E, const f1p_kmpc_cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid,
                    const QpWallArgs* walls = nullptr);
-int launch_stmpc_qp(f1p_ctx* ctx, int E, const f1p_stmpc_cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid);
+int launch_stmpc_qp(f1p_ctx* ctx, int E, const f1p_stmpc_cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid,
+                    const QpWallArgs* walls = nullptr);
 size_t stmpc_qp_avoid_lds_bytes(int T);
 // a plan branch's discs: d_obs [idx[k]][M][5] (the caller's ego order) -> d_out [k][M][5]
 int launch_stmpc_qp_obs_in(f1p_ctx* ctx, const double* d_obs, const int32_t* d_idx, int nb, int M, double* d_out);

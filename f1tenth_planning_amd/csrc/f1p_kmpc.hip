@@ -364,44 +364,7 @@ int f1p::qp_set_avoid(f1p_ctx* ctx, f1p_kmpc_qp_avoid* state, const f1p_kmpc_qp_
 }
 
 // ---- wall rows (k_kmpc_qp.hip WALL) -------------------------------------------------------------------------------------
-static int validate_qp_walls(f1p_ctx* ctx, const f1p_kmpc_qp_walls* w) {
-    if (w->n_samples < 1 || w->n_samples > F1P_KMPC_QP_WALL_MAX_SAMPLES || !isfinite(w->margin))
-        return set_error(ctx, F1P_EINVAL, "kmpc qp walls: n_samples must be in [1, 256] and margin finite");
-    return F1P_OK;
-}
-
-// w (nullable: the defaults), checked, and the context's grid as it is now -> the kernel's arguments
-static int qp_wall_args(f1p_ctx* ctx, const f1p_kmpc_qp_walls* w, QpWallArgs* out) {
-    f1p_kmpc_qp_walls d;
-    f1p_kmpc_qp_walls_default(&d);
-    if (w) d = *w;
-    const int rc = validate_qp_walls(ctx, &d); if (rc) return rc;
-    if (!ctx->has_grid) return set_error(ctx, F1P_ESTATE, "kmpc qp walls are on but no occupancy grid is loaded (f1p_set_grid)");
-    if (ctx->n_disc > 0)
-        return set_error(ctx, F1P_ESTATE, "kmpc qp walls are a point / disc test: remove the oriented footprint (f1p_set_footprint) and use f1p_inflate_grid");
-    out->g = grid_dev(ctx);
-    out->h = 0.5 * ctx->res;
-    out->n_samples = d.n_samples;
-    out->margin = d.margin;
-    return F1P_OK;
-}
-
-// the wall problem of E egos.  av null: the discs the context holds (while f1p_kmpc_qp_set_avoid is on, else none) with its numbers.
-// cfg, opts and the horizon's cap are qp_call's to check.
-static int qp_walls_call(f1p_ctx* ctx, bool staged, int E, const f1p_kmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const QpIo& io, const QpAvoidArgs* av,
-                         const f1p_kmpc_qp_avoid* numbers, const f1p_kmpc_qp_walls* walls) {
-    F1P_ENTER(ctx);
-    QpWallArgs wl;
-    int rc = qp_wall_args(ctx, walls, &wl); if (rc) return rc;
-    QpAvoidArgs held;
-    if (!av) {
-        const bool on = ctx->kmpc_qp_av.on;
-        if (on && cfg && (rc = qp_avoid_plan_check<KinQp>(ctx, cfg, E))) return rc;
-        held = QpAvoidArgs(on ? ctx->kmpc_obs.cur : nullptr, on ? ctx->kmpc_obs.M : 0, ctx->kmpc_qp_av);
-        av = &held; numbers = &ctx->kmpc_qp_av;
-    }
-    return qp_call<KinQp>(ctx, staged, E, cfg, opts, io, av, numbers, &wl);
-}
+// (validate_qp_walls / qp_wall_args / qp_set_walls / qp_walls_call: f1p_host.h, one body with the dynamic QP)
 
 int f1p_kmpc_qp_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_prev, int32_t E,
                     const f1p_kmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, double* d_steer, double* d_speed, int32_t* d_status,
@@ -409,7 +372,7 @@ int f1p_kmpc_qp_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const
     QpIo io;
     io.x0 = d_x0; io.ref = d_ref; io.pa = d_oa_prev; io.pd = d_od_prev;
     io.steer = d_steer; io.speed = d_speed; io.status = d_status; io.u = d_u; io.x = d_xk; io.obj = d_obj; io.duals = d_duals; io.iters = d_iters;
-    if (ctx && ctx->kmpc_qp_walls.on) return qp_walls_call(ctx, false, E, cfg, opts, io, nullptr, nullptr, &ctx->kmpc_qp_walls);
+    if (ctx && ctx->kmpc_qp_walls.on) return qp_walls_call<KinQp>(ctx, false, E, cfg, opts, io, nullptr, nullptr, &ctx->kmpc_qp_walls);
     return qp_call<KinQp>(ctx, false, E, cfg, opts, io, nullptr, nullptr);
 }
 
@@ -434,7 +397,7 @@ int f1p_kmpc_qp_plan_batch(f1p_ctx* ctx, const double* x0, int32_t E, const f1p_
     const bool av_on = ctx->kmpc_qp_av.on, walls_on = ctx->kmpc_qp_walls.on;
     QpWallArgs wl;
     if (walls_on && !av_on && cfg->horizon > KinQp::AVOID_MAX_T) return set_error(ctx, F1P_EINVAL, std::string(KinQp::who) + KinQp::avoid_cap);
-    if (walls_on && (rc = qp_wall_args(ctx, &ctx->kmpc_qp_walls, &wl))) return rc;
+    if (walls_on && (rc = qp_wall_args<KinQp>(ctx, &ctx->kmpc_qp_walls, &wl))) return rc;
     if (av_on && (rc = qp_avoid_plan_check<KinQp>(ctx, cfg, E))) return rc;
     const size_t T = cfg->horizon, e = E;
     if ((rc = ensure_qp_warm(ctx, E, cfg->horizon))) return rc;
@@ -500,14 +463,7 @@ void f1p_kmpc_qp_walls_default(f1p_kmpc_qp_walls* walls) {
     walls->n_samples = 48; walls->margin = 0.0;
 }
 
-int f1p_kmpc_qp_set_walls(f1p_ctx* ctx, const f1p_kmpc_qp_walls* walls) {
-    F1P_ENTER(ctx);
-    if (!walls || !walls->on) { ctx->kmpc_qp_walls.on = 0; return F1P_OK; }
-    const int rc = validate_qp_walls(ctx, walls); if (rc) return rc;
-    ctx->kmpc_qp_walls = *walls;
-    ctx->kmpc_qp_walls.on = 1;
-    return F1P_OK;
-}
+int f1p_kmpc_qp_set_walls(f1p_ctx* ctx, const f1p_kmpc_qp_walls* walls) { return qp_set_walls<KinQp>(ctx, ctx ? &ctx->kmpc_qp_walls : nullptr, walls); }
 
 int f1p_kmpc_qp_walls_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_prev, int32_t E,
                           const f1p_kmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* d_obs, int32_t M,
@@ -519,7 +475,7 @@ int f1p_kmpc_qp_walls_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref,
     io.steer = d_steer; io.speed = d_speed; io.status = d_status; io.u = d_u; io.x = d_xk; io.obj = d_obj; io.duals = d_duals; io.iters = d_iters;
     QpAvoidArgs av;
     av.obs = d_obs; av.M = M; av.eps = d_eps; av.planes = d_planes; av.duals = d_avoid_duals;
-    return qp_walls_call(ctx, false, E, cfg, opts, io, &av, avoid, walls);
+    return qp_walls_call<KinQp>(ctx, false, E, cfg, opts, io, &av, avoid, walls);
 }
 
 int f1p_kmpc_qp_walls_batch(f1p_ctx* ctx, const double* x0, const double* ref, const double* oa_prev, const double* od_prev, int32_t E,
@@ -532,7 +488,7 @@ int f1p_kmpc_qp_walls_batch(f1p_ctx* ctx, const double* x0, const double* ref, c
     io.steer = steer; io.speed = speed; io.status = status; io.u = u; io.x = xk; io.obj = obj; io.duals = duals; io.iters = iters;
     QpAvoidArgs av;
     av.obs = obs; av.M = M; av.eps = eps; av.planes = planes; av.duals = avoid_duals;
-    return qp_walls_call(ctx, true, E, cfg, opts, io, &av, avoid, walls);
+    return qp_walls_call<KinQp>(ctx, true, E, cfg, opts, io, &av, avoid, walls);
 }
 
 int f1p_kmpc_qp_warm_reset(f1p_ctx* ctx) {

@@ -216,8 +216,8 @@ struct DynQp {
     static constexpr const char *who = "stmpc", *avoid_cap = " qp avoid: horizon must be <= F1P_STMPC_QP_AVOID_MAX_T (40: the packed avoidance rows beside H and the Newton matrix in LDS)";
     static constexpr bool EMPTY_RETURNS = true;
     static int validate(f1p_ctx* ctx, const Cfg* cfg, int E, const f1p_kmpc_qp_opts* opts, f1p_kmpc_qp_opts* o) { return validate_stmpc_qp(ctx, cfg, E, opts, o); }
-    static int launch(f1p_ctx* ctx, int E, const Cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid, const QpWallArgs*) {
-        return launch_stmpc_qp(ctx, E, cfg, max_iter, tol, io, avoid);          // (wall rows: the kinematic QP only, never handed here)
+    static int launch(f1p_ctx* ctx, int E, const Cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid, const QpWallArgs* walls) {
+        return launch_stmpc_qp(ctx, E, cfg, max_iter, tol, io, avoid, walls);
     }
     static const ObsState& obs(const f1p_ctx* ctx) { return ctx->stmpc_obs; }
     static const f1p_kmpc_qp_avoid& av(const f1p_ctx* ctx) { return ctx->stmpc_qp_av; }
@@ -251,12 +251,41 @@ int f1p_stmpc_qp_avoid_batch(f1p_ctx* ctx, const double* x0, const double* ref, 
     return qp_call<DynQp>(ctx, true, E, cfg, opts, io, &av, avoid);
 }
 
+int f1p_stmpc_qp_set_walls(f1p_ctx* ctx, const f1p_kmpc_qp_walls* walls) { return qp_set_walls<DynQp>(ctx, ctx ? &ctx->stmpc_qp_walls : nullptr, walls); }
+
+int f1p_stmpc_qp_walls_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_v_prev,
+                           int32_t E, const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* d_obs, int32_t M,
+                           const f1p_kmpc_qp_avoid* avoid, const f1p_kmpc_qp_walls* walls, double* d_steer, double* d_speed,
+                           int32_t* d_status, double* d_u, double* d_x, double* d_obj, double* d_duals, int32_t* d_iters, double* d_eps,
+                           double* d_planes, double* d_avoid_duals) {
+    QpIo io;
+    io.x0 = d_x0; io.ref = d_ref; io.pa = d_oa_prev; io.pd = d_od_v_prev;
+    io.steer = d_steer; io.speed = d_speed; io.status = d_status; io.u = d_u; io.x = d_x; io.obj = d_obj; io.duals = d_duals; io.iters = d_iters;
+    QpAvoidArgs av;
+    av.obs = d_obs; av.M = M; av.eps = d_eps; av.planes = d_planes; av.duals = d_avoid_duals;
+    return qp_walls_call<DynQp>(ctx, false, E, cfg, opts, io, &av, avoid, walls);
+}
+
+int f1p_stmpc_qp_walls_batch(f1p_ctx* ctx, const double* x0, const double* ref, const double* oa_prev, const double* od_v_prev, int32_t E,
+                             const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* obs, int32_t M,
+                             const f1p_kmpc_qp_avoid* avoid, const f1p_kmpc_qp_walls* walls, double* steer, double* speed, int32_t* status,
+                             double* u, double* x, double* obj, double* duals, int32_t* iters, double* eps, double* planes,
+                             double* avoid_duals) {
+    QpIo io;
+    io.x0 = x0; io.ref = ref; io.pa = oa_prev; io.pd = od_v_prev;
+    io.steer = steer; io.speed = speed; io.status = status; io.u = u; io.x = x; io.obj = obj; io.duals = duals; io.iters = iters;
+    QpAvoidArgs av;
+    av.obs = obs; av.M = M; av.eps = eps; av.planes = planes; av.duals = avoid_duals;
+    return qp_walls_call<DynQp>(ctx, true, E, cfg, opts, io, &av, avoid, walls);
+}
+
 int f1p_stmpc_qp_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_v_prev, int32_t E,
                      const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, double* d_steer, double* d_speed, int32_t* d_status,
                      double* d_u, double* d_x, double* d_obj, double* d_duals, int32_t* d_iters) {
     QpIo io;
     io.x0 = d_x0; io.ref = d_ref; io.pa = d_oa_prev; io.pd = d_od_v_prev;
     io.steer = d_steer; io.speed = d_speed; io.status = d_status; io.u = d_u; io.x = d_x; io.obj = d_obj; io.duals = d_duals; io.iters = d_iters;
+    if (ctx && ctx->stmpc_qp_walls.on) return qp_walls_call<DynQp>(ctx, false, E, cfg, opts, io, nullptr, nullptr, &ctx->stmpc_qp_walls);
     return qp_call<DynQp>(ctx, false, E, cfg, opts, io, nullptr, nullptr);
 }
 
@@ -296,7 +325,13 @@ static int stmpc_qp_plan_impl(f1p_ctx* ctx, const double* x0, const int32_t* tra
         return set_error(ctx, F1P_ESTATE, "waypoints with a heading column are required");
     }
     if (E == 0) return F1P_OK;
-    const bool av = ctx->stmpc_qp_av.on != 0;
+    const bool av = ctx->stmpc_qp_av.on != 0, walls = ctx->stmpc_qp_walls.on != 0;
+    QpWallArgs wl;
+    if (walls && !av) {                                                       // the caps on T and TK hold with walls alone
+        if (dcfg->horizon > DynQp::AVOID_MAX_T) return set_error(ctx, F1P_EINVAL, std::string(DynQp::who) + DynQp::avoid_cap);
+        if (kcfg->horizon > 31) return set_error(ctx, F1P_EINVAL, "stmpc qp avoid: the kinematic branch's horizon must be <= 31 (2TK + 1 inputs, one lane each)");
+    }
+    if (walls && (rc = qp_wall_args<DynQp>(ctx, &ctx->stmpc_qp_walls, &wl))) return rc;
     if (av && (rc = qp_avoid_plan_check<DynQp>(ctx, dcfg, E, kcfg))) return rc;
     const double* d_obs_all = av ? ctx->stmpc_obs.cur : nullptr;              // [E][M][5] in the caller's order, or none held
     const int Mo = d_obs_all ? ctx->stmpc_obs.M : 0;
@@ -342,10 +377,10 @@ static int stmpc_qp_plan_impl(f1p_ctx* ctx, const double* x0, const int32_t* tra
         }
         if (b) {
             q.x0 = sp.d_x7; q.ref = sp.d_ref7[1];
-            rc = launch_stmpc_qp(ctx, nb, dcfg, o.max_iter, o.tol, q, av ? &qa : nullptr);
+            rc = launch_stmpc_qp(ctx, nb, dcfg, o.max_iter, o.tol, q, av || walls ? &qa : nullptr, walls ? &wl : nullptr);
         } else {
             q.x0 = sp.d_s4[0]; q.ref = sp.d_ref4;
-            rc = launch_kmpc_qp(ctx, nb, kcfg, ok_.max_iter, ok_.tol, q, av ? &qa : nullptr);
+            rc = launch_kmpc_qp(ctx, nb, kcfg, ok_.max_iter, ok_.tol, q, av || walls ? &qa : nullptr, walls ? &wl : nullptr);
         }
         if (rc) return rc;
         if ((rc = launch_stmpc_qp_warm_out(ctx, d_wout[b], sp.d_idx[b], nb, Tb, W, d_warm))) return rc;

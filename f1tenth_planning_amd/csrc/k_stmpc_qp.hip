@@ -32,7 +32,12 @@
 // are taken from step t's slab as it passes through LDS and kept packed: the rows of step t are zero from column 2t on, so row 2(t-1) + j
 // holds 2t doubles at A[2 t (t-1) + 2 t j], 2T(T+1) in all.  The disc load, the choice of the two discs, the half-plane and its `planes`
 // record are qp_avoid.h's, shared with k_kmpc_qp.hip.
-#include "qp_avoid.h"
+//
+// WALL (f1p_stmpc_qp_walls_*): the AV variant whose two rows per step are the two nearest of {the two nearest live discs, the
+// wall to the left of pbar_t, the wall to its right} on the active occupancy bitmap, left and right of the direction of travel
+// psibar_t + betabar_t (L.pw).  Lane t - 1 marches both sides of step t itself (qp_walls.h) and takes the first and the second of the four
+// candidates; lanes >= T march nothing.  From the half-plane on everything is the AV variant's.  M = 0 (no discs) is allowed here.
+#include "qp_walls.h"
 
 namespace f1p {
 
@@ -98,7 +103,7 @@ __device__ __forceinline__ void amul(const double* J, int T, int t, double DT, c
 
 }  // namespace
 
-// AvArgs: none (the plain QP), or one QpAvoidArgs (AV; f1p_internal.h)
+// AvArgs: none (the plain QP), one QpAvoidArgs (AV; f1p_internal.h), or a QpAvoidArgs and a QpWallArgs (WALL)
 template <class... AvArgs>
 __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g, const double* __restrict__ refg, const double* pa_g,
                                                  const double* pd_g, int pstride, int E, f1p_stmpc_cfg cfg, int max_iter, double tol,
@@ -107,7 +112,8 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
                                                  double* __restrict__ duals, int32_t* __restrict__ iters_out, double* warm_out,
                                                  AvArgs... av_args) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    constexpr bool AV = sizeof...(AvArgs) == 1;
+    constexpr bool AV = sizeof...(AvArgs) >= 1;
+    constexpr bool WALL = sizeof...(AvArgs) == 2;
     [[maybe_unused]] const QpAvoidArgs av = qp_avoid_args(av_args...);
     constexpr int R = AV ? 12 : 10;                      // inequality rows per lane
     // AV: the solver's slack is e' = eps / sig, sig = 1 / sqrt(2 rho): its curvature is 1 like the inputs' (2 rho = 2e4 beside weights of
@@ -213,7 +219,30 @@ __global__ __launch_bounds__(64) void k_stmpc_qp(const double* __restrict__ x0g,
     // AV: this lane's two half-planes (step tau + 1: the nearest and the second nearest live disc)
     [[maybe_unused]] QpPlane pl[2];
     [[maybe_unused]] const int a_off = 2 * tau * (tau + 1), a_len = 2 * (tau + 1);     // this lane's packed rows: A[a_off + j a_len + c]
-    if constexpr (AV) {
+    if constexpr (WALL) {
+        // both sides of step tau + 1 marched from pbar along +-l, l = (-sin w, cos w), w the direction of travel; then the first and the
+        // second of the four candidates.  The two marches are independent: their word loads may be in flight together.
+        if (in_n && !done) {
+            const QpWallArgs wl = qp_wall_args(av_args...);
+            const int t = tau + 1;
+            const double tt = (double)t * DT, px = L.px[tau], py = L.py[tau];
+            double sn, cs;
+            sincos(L.pw[tau], &sn, &cs);
+            const double llx = -sn, lly = cs;                             // the LEFT direction (the right one is its negative)
+            const int kl = qp_wall_march(wl, px, py, llx, lly), kr = qp_wall_march(wl, px, py, -llx, -lly);
+            const QpNearest nr = qp_avoid_nearest(L.ob, av.M, px, py, tt);
+            const QpCand d0 = qp_disc_cand(L.ob, nr.m0, px, py, tt), d1 = qp_disc_cand(L.ob, nr.m1, px, py, tt);
+            const QpWallCand wL = qp_wall_cand(wl, px, py, llx, lly, kl, F1P_QP_WALL_SLOT_L);
+            const QpWallCand wR = qp_wall_cand(wl, px, py, -llx, -lly, kr, F1P_QP_WALL_SLOT_R);
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj) {
+                const int pick = qp_select4(d0, d1, wL, wR, jj);
+                if (pick == 0 || pick == 1) pl[jj] = qp_avoid_plane(L.ob, pick == 0 ? nr.m0 : nr.m1, px, py, L.pw[tau], tt, L.fr[t], L.fr[Tp + t], av.margin);
+                else if (pick == 2) pl[jj] = qp_wall_plane(wL, llx, lly, L.fr[t], L.fr[Tp + t], wl.margin);
+                else if (pick == 3) pl[jj] = qp_wall_plane(wR, -llx, -lly, L.fr[t], L.fr[Tp + t], wl.margin);
+            }
+        }
+    } else if constexpr (AV) {
         if (in_n && !done) {
             const int t = tau + 1;
             const double tt = (double)t * DT, px = L.px[tau], py = L.py[tau];
@@ -537,12 +566,15 @@ __global__ __launch_bounds__(256) void k_stmpc_qp_obs_in(const double* __restric
 
 size_t stmpc_qp_avoid_lds_bytes(int T) { return sizeof(double) * (size_t)stqp_lds_doubles(T, true); }
 
-// one wave per ego; in the avoidance variant lane T takes the slack
-int launch_stmpc_qp(f1p_ctx* ctx, int E, const f1p_stmpc_cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid) {
+// one wave per ego; in the avoidance variant lane T takes the slack; the wall variant as the avoidance variant
+int launch_stmpc_qp(f1p_ctx* ctx, int E, const f1p_stmpc_cfg* cfg, int max_iter, double tol, const QpIo& io, const QpAvoidArgs* avoid,
+                    const QpWallArgs* walls) {
     if (E <= 0) return F1P_OK;
     const int T = cfg->horizon;
     if (avoid && (T > F1P_STMPC_QP_AVOID_MAX_T || avoid->M < 0 || avoid->M > F1P_KMPC_MAX_OBS || (avoid->M > 0 && !avoid->obs)))
         return set_error(ctx, F1P_EINVAL, "stmpc qp avoid: bad horizon / obstacles");
+    if (walls && (!avoid || !walls->g.bits || walls->g.w < 1 || walls->g.h < 1 || walls->n_samples < 1 || walls->n_samples > F1P_KMPC_QP_WALL_MAX_SAMPLES))
+        return set_error(ctx, F1P_EINVAL, "stmpc qp walls: bad grid / n_samples");
     const size_t lds = sizeof(double) * (size_t)stqp_lds_doubles(T, avoid != nullptr);
     const auto launch = [&](auto kern, const char* too_long, const char* what, auto... av) {
         const int rc = qp_lds_opt_in(ctx, reinterpret_cast<const void*>(kern), lds, too_long);
@@ -551,6 +583,8 @@ int launch_stmpc_qp(f1p_ctx* ctx, int E, const f1p_stmpc_cfg* cfg, int max_iter,
                            io.steer, io.speed, io.status, io.u, io.x, io.obj, io.duals, io.iters, io.warm_out, av...);
         return check_hip(ctx, hipGetLastError(), what);
     };
+    if (walls)
+        return launch(&k_stmpc_qp<QpAvoidArgs, QpWallArgs>, "stmpc qp walls: horizon too long for the CU's LDS", "k_stmpc_qp_walls launch", *avoid, *walls);
     if (avoid) return launch(&k_stmpc_qp<QpAvoidArgs>, "stmpc qp avoid: horizon too long for the CU's LDS", "k_stmpc_qp_avoid launch", *avoid);
     return launch(&k_stmpc_qp<>, "stmpc qp: horizon too long for the CU's LDS", "k_stmpc_qp launch");
 }

@@ -50,7 +50,8 @@ from .core import DeviceBuffer, F1PError, _Core, _f64, _ptr  # noqa: E402, F401
 from .comm import _Comm  # noqa: E402
 from .lattice import _Lattice, lattice_set_obstacles, lattice_set_obstacles_dev  # noqa: E402, F401
 from .mpc import (_Mpc, kmpc_qp_avoid, kmpc_qp_set_avoid, kmpc_qp_set_walls, kmpc_qp_walls, kmpc_set_obstacles,  # noqa: E402, F401
-                  kmpc_set_obstacles_dev, stmpc_qp_avoid, stmpc_qp_set_avoid, stmpc_set_obstacles, stmpc_set_obstacles_dev)
+                  kmpc_set_obstacles_dev, stmpc_qp_avoid, stmpc_qp_set_avoid, stmpc_qp_set_walls, stmpc_qp_walls, stmpc_set_obstacles,
+                  stmpc_set_obstacles_dev)
 from .rivals import _Rivals, rivals, rivals_dev, rivals_predict, rivals_predict_dev, rivals_set_course, rivals_set_groups  # noqa: E402, F401
 from .scene import _Scene  # noqa: E402
 from .trackers import _Trackers  # noqa: E402

@@ -88,11 +88,32 @@ def stmpc_qp_set_avoid(ctx, avoid):
     ctx._check(ctx.lib.f1p_stmpc_qp_set_avoid(ctx.h, _ref(avoid)))
 
 
+def stmpc_qp_walls(ctx, x0, ref, obs, cfg, avoid=None, walls=None, oa_prev=None, od_v_prev=None, opts=None, want_u=True, want_x=False, want_obj=True,
+                   want_duals=False, want_iters=True, want_eps=True, want_planes=False, want_avoid_duals=False):
+    """stmpc_qp_avoid with wall rows from the context's ACTIVE occupancy bitmap (f1p_stmpc_qp_walls_batch): per step the two
+    nearest of {the two nearest live discs, the wall to the left of the previous solution's path, the wall to its right} become the step's
+    rows; left and right of the direction of travel yaw + beta.  obs [E, M, 5] with M in 0..16, or None (no discs); walls:
+    _abi.kmpc_qp_walls(n_samples, margin) (None: the defaults).  Needs set_grid and no oriented footprint; horizon <=
+    _abi.STMPC_QP_AVOID_MAX_T.  -> stmpc_qp_avoid's dict; planes' slot 16 / 17: the left / right wall.  (A module function, as kmpc_qp_walls.)"""
+    if obs is None:
+        obs = np.zeros((_f64(x0, (-1, 7)).shape[0], 0, 5))
+    return _mpc_qp(ctx, ctx.lib.f1p_stmpc_qp_walls_batch, 7, "x", 10, x0, ref, cfg, oa_prev, od_v_prev, opts, want_u, want_x, want_obj, want_duals,
+                   want_iters, (obs, avoid, want_eps, want_planes, want_avoid_duals), walls=(_ref(walls),))
+
+
+def stmpc_qp_set_walls(ctx, walls):
+    """f1p_stmpc_qp_set_walls on Context `ctx`, a switch of its own beside kmpc_qp_set_walls: while on, stmpc_qp_plan, stmpc_qp_plan_tracks
+    and stmpc_qp_dev solve the wall problem in both branches on the grid the context holds at each call, with the discs of
+    stmpc_set_obstacles[_dev] while stmpc_qp_set_avoid is on as well (else none) and its rho / lin; walls: _abi.kmpc_qp_walls(...), None (or
+    on=False) turns it off"""
+    ctx._check(ctx.lib.f1p_stmpc_qp_set_walls(ctx.h, _ref(walls)))
+
+
 def _mpc_qp(ctx, fn, n, xname, duals_per_step, x0, ref, cfg, oa_prev, od_prev, opts, want_u, want_x, want_obj, want_duals, want_iters, av=None,
             walls=()):
-    """the stateless QP calls (Context.kmpc_qp / stmpc_qp, kmpc_qp_avoid / stmpc_qp_avoid, kmpc_qp_walls).  n: the state width; xname: the key
+    """the stateless QP calls (Context.kmpc_qp / stmpc_qp, kmpc_qp_avoid / stmpc_qp_avoid, kmpc_qp_walls / stmpc_qp_walls).  n: the state width; xname: the key
     of the predicted states [E, n, T+1]; duals [E, duals_per_step * T - 2]; av: None, or the avoidance rows' (obs, avoid, want_eps,
-    want_planes, want_avoid_duals); walls: the arguments that follow `avoid` (kmpc_qp_walls: its struct), where obs may be [E, 0, 5]"""
+    want_planes, want_avoid_duals); walls: the arguments that follow `avoid` (kmpc_qp_walls / stmpc_qp_walls: the struct), where obs may be [E, 0, 5]"""
     x0 = _f64(x0, (-1, n)); E = x0.shape[0]; T = cfg.horizon
     ref = _f64(ref, (E, n, T + 1))
     wants = [("u", want_u, (E, T, 2), np.float64), (xname, want_x, (E, n, T + 1), np.float64), ("obj", want_obj, (E,), np.float64),

@@ -929,6 +929,54 @@ int f1p_stmpc_qp_set_avoid(f1p_ctx* ctx, const f1p_kmpc_qp_avoid* avoid);
  * CU; above 64 KiB the kernel is opted in to the larger allocation, a launch path of its own); -1: horizon < 2.  Needs no context. */
 int64_t f1p_stmpc_qp_avoid_lds_bytes(int32_t horizon);
 
+/* Walls in the dynamic QP: the occupancy grid as SOFT, LINEARISED half-plane rows beside the discs', the dynamic twin of
+ * f1p_kmpc_qp_walls_* with the same struct and defaults (f1p_kmpc_qp_walls, f1p_kmpc_qp_walls_default).  An avoidance term, not a
+ * guarantee.  The problem of f1p_stmpc_qp_avoid_* is kept as it is -- the same u, the linearisation about predict_motion(x0, oa_prev,
+ * od_v_prev), the same 10T-2 plain rows, the same slack eps (cost rho eps^2 + lin eps, row -eps <= 0, solved for scaled by
+ * 1 / sqrt(2 rho)) and AT MOST TWO avoidance rows per step t = 1..T.  New: per step two wall candidates compete with the live discs for
+ * those two rows.  The bitmap is the ACTIVE one (f1p_set_grid dilated by f1p_inflate_grid), the cell rule the collision tests'
+ * (cell = floor((p - origin) * (1 / res))); a cell outside the image or a non-finite coordinate counts as occupied.  res is f1p_set_grid's
+ * and h = 0.5 * res.  pbar_t is the linearisation path's position after t steps and w_t = psibar_t + betabar_t its direction of travel
+ * there (yaw + slip angle: the angle f1p_stmpc_qp_avoid_*'s on-centre normal uses, NOT the bare yaw).  For side sigma = +1 (left, slot
+ * 16) and sigma = -1 (right, slot 17):
+ *   l = sigma (-sin w_t, cos w_t);
+ *   the samples are q_k = pbar_t + ((double)k * h) l for k = 1 .. n_samples;
+ *   k* is the first k whose q_k is occupied; if there is none, this side has no candidate;
+ *   the contact is the last free sample, c = q_{k*-1}, with q_0 = pbar_t;
+ *   the candidate's clearance is clear = (double)(k* - 1) * h -- pbar_t's own cell is not tested;
+ *   the normal is n = -l;
+ *   the row is  -n.(S_xy(t) u) - eps <= n.(s_xy(t) - c) - wall_margin.
+ * Selection per step: of {the live disc with the least clear = dist - r, the one with the second least, wall L, wall R} the two smallest
+ * clear are taken, ties to the lower slot -- discs before walls, left before right; the step's first row is the first of them.
+ * planes[e][t][j] = (n_x, n_y, right-hand side, slot) with slots 0..15 a disc, 16 / 17 a wall, and -1 with zeros when absent;
+ * avoid_duals keeps its layout.
+ * The problem is feasible whenever the plain one is; statuses 1 and 3 keep their causes (the bitmap adds none); an ego with no candidate
+ * at any step has the optimum of f1p_stmpc_qp_avoid_* (of f1p_stmpc_qp_* without a live disc).  The limits are f1p_kmpc_qp_walls_*'s:
+ * soft and linearised rows, two rows per step, a march that can step over a cell's corner, a pbar_t inside the wall pinned and not pushed
+ * out; status 2 as there.
+ * Arguments: n_samples in 1..256 (else F1P_EINVAL), wall_margin (`margin`) finite, 2 <= horizon <= F1P_STMPC_QP_AVOID_MAX_T; the calls
+ * need a grid (F1P_ESTATE without one) and no oriented footprint (f1p_set_footprint with n_discs > 0: F1P_ESTATE).
+ * f1p_stmpc_qp_walls_batch / _dev: f1p_stmpc_qp_avoid_batch / _dev with obs nullable and M in 0..16, and `walls` after `avoid` (NULL: the
+ *   defaults; `on` is not read); the same outputs.
+ * f1p_stmpc_qp_set_walls: a switch of its own beside f1p_kmpc_qp_set_walls; NULL or on = 0 turns it off (the default).  While on,
+ *   f1p_stmpc_qp_dev, f1p_stmpc_qp_plan_batch and f1p_stmpc_qp_plan_tracks_batch solve this problem in both branches: the dynamic egos
+ *   here, the kinematic ones f1p_kmpc_qp_walls_*'s problem on kcfg with the same numbers (kcfg->horizon <= 31, horizon <=
+ *   F1P_STMPC_QP_AVOID_MAX_T, else F1P_EINVAL).  The discs are those of f1p_stmpc_set_obstacles[_dev], taken only while
+ *   f1p_stmpc_qp_set_avoid is on as well (otherwise M = 0); rho and lin (and the discs' margin) are the context's f1p_stmpc_qp_set_avoid
+ *   values whether or not it is on -- the defaults if it was never called.  The bitmap is read at launch: a later f1p_set_grid /
+ *   f1p_inflate_grid is picked up by the next call.  Off: every entry point is what it is without this call. */
+int f1p_stmpc_qp_walls_batch(f1p_ctx* ctx, const double* x0, const double* ref, const double* oa_prev, const double* od_v_prev, int32_t E,
+                             const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* obs, int32_t M,
+                             const f1p_kmpc_qp_avoid* avoid, const f1p_kmpc_qp_walls* walls, double* steer, double* speed, int32_t* status,
+                             double* u, double* x, double* obj, double* duals, int32_t* iters, double* eps, double* planes,
+                             double* avoid_duals);
+int f1p_stmpc_qp_walls_dev(f1p_ctx* ctx, const double* d_x0, const double* d_ref, const double* d_oa_prev, const double* d_od_v_prev,
+                           int32_t E, const f1p_stmpc_cfg* cfg, const f1p_kmpc_qp_opts* opts, const double* d_obs, int32_t M,
+                           const f1p_kmpc_qp_avoid* avoid, const f1p_kmpc_qp_walls* walls, double* d_steer, double* d_speed,
+                           int32_t* d_status, double* d_u, double* d_x, double* d_obj, double* d_duals, int32_t* d_iters, double* d_eps,
+                           double* d_planes, double* d_avoid_duals);
+int f1p_stmpc_qp_set_walls(f1p_ctx* ctx, const f1p_kmpc_qp_walls* walls);
+
 /* ------------------------------------------------------------------------------------------------
  * SURVEY.md 8f rank 2 -- the dynamic single-track model as a second model for shooting MPC
  * (control/dynamic_mpc/dynamic_mpc.py): predict_motion / update_state (:280-404), calc_ref_trajectory (:195-233),
