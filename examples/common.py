@@ -132,6 +132,9 @@ def add_rival_flags(ap):
     ap.add_argument("--groups", type=int, default=0, help="with --rivals: split the pack into G independent races (vehicle e in race e %% G)")
     ap.add_argument("--predict", choices=("velocity", "track"), default="velocity", help="with --rivals: 'track' predicts each rival along the raceline "
                     "over the planner's horizon instead of at constant velocity (Rivals(predict='track'))")
+    ap.add_argument("--rival-speed", choices=("constant", "profile"), default="constant", help="with --predict track: 'profile' moves each rival with the "
+                    "raceline's speed profile, scaled by its speed now -- it brakes into the bends -- instead of at its current speed "
+                    "(Rivals(predict='track', speed='profile'))")
 
 
 def rival_groups(args, E):
@@ -140,6 +143,8 @@ def rival_groups(args, E):
         raise SystemExit("--groups needs --rivals (the host construction of --opponents knows one race of all)")
     if args.predict != "velocity" and not args.rivals:
         raise SystemExit("--predict needs --rivals (the host construction of --opponents moves every opponent at constant velocity)")
+    if args.rival_speed != "constant" and args.predict != "track":
+        raise SystemExit("--rival-speed profile needs --predict track (the speed profile is the one of the course the rival is predicted along)")
     if args.groups <= 0:
         return None, np.diag(np.full(E, np.inf))
     groups = (np.arange(E) % args.groups).astype(np.int32)
@@ -169,7 +174,7 @@ def opponent_runs(args, rl, waypoints, cfg, make_planner, batch_states, gap=1.5,
     for on in (False, True):
         planner = make_planner([w.copy() for w in waypoints], cfg)
         if on and args.rivals:
-            planner.rivals = Rivals(count=M, radius=radius, groups=groups, predict=args.predict)      # every plan_batch finds them itself, on the device
+            planner.rivals = Rivals(count=M, radius=radius, groups=groups, predict=args.predict, speed=args.rival_speed)      # every plan_batch finds them itself, on the device
         env = sim.make("f110_gym:f110-v0", num_agents=E)
         env.reset(poses)
         d_min, n_stop = np.inf, 0

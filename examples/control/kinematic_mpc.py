@@ -9,7 +9,8 @@ twice: each vehicle planning as if it were alone, then with its M nearest other 
 velocity (planner.obstacles).  It reports the smallest distance between two vehicles over each run.  With --rivals the opponents are not
 built here but found on the device by every plan (planner.rivals = Rivals(count=M, radius=...)); --groups G then splits the pack into G
 independent races.  --predict track predicts each rival along the raceline over the planner's
-horizon instead of at constant velocity (Rivals(predict="track")).
+horizon instead of at constant velocity (Rivals(predict="track")); --rival-speed profile then moves it with the raceline's speed profile
+instead of at its current speed (Rivals(predict="track", speed="profile")).
 
 --solver qp --avoid (mpc_config.QP_AVOID) lets the QP take the same obstacles and rivals as soft half-plane rows; without
 --avoid the QP takes none and --opponents with it is an error.

@@ -6,7 +6,8 @@ each vehicle planning as if it were alone, then with its M nearest other vehicle
 predicted at constant velocity; f1p_lattice_set_obstacles) -- and prints the smallest distance between two vehicles over each run.  With --rivals
 the opponents are not built here but found on the device by every plan (LatticePlanner.rivals = Rivals(count=M, radius=...)); --groups G then
 splits the pack into G independent races.  --predict track predicts each rival along the raceline over the planner's
-horizon instead of at constant velocity (Rivals(predict="track"))."""
+horizon instead of at constant velocity (Rivals(predict="track")); --rival-speed profile then moves it with the raceline's speed profile instead of at
+its current speed (Rivals(predict="track", speed="profile"))."""
 import os
 import sys
 
@@ -45,7 +46,7 @@ def opponent_runs(args, waypoints, gap=1.5, radius=0.45):
     for on in (False, True):
         planner = make_planner(args, waypoints)
         if on and args.rivals:
-            planner.rivals = Rivals(count=M, radius=radius, groups=groups, predict=args.predict)     # every plan_batch finds them itself, on the device
+            planner.rivals = Rivals(count=M, radius=radius, groups=groups, predict=args.predict, speed=args.rival_speed)     # every plan_batch finds them itself, on the device
         env = sim.make("f110_gym:f110-v0", num_agents=E)
         env.reset(poses0)
         d_min, n_stop = np.inf, 0

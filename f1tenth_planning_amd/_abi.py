@@ -56,12 +56,16 @@ class KmpcSampler(C.Structure):
 class RivalsPredict(C.Structure):
     """struct f1p_rivals_predict (include/f1p.h)"""
     _fields_ = [("horizon_s", C.c_double), ("horizon_m", C.c_double), ("knots", C.c_int32), ("inflate", C.c_int32), ("wrap", C.c_int32),
-                ("reserved", C.c_int32)]
+                ("speed", C.c_int32)]
 
 
-def rivals_predict(horizon_s, horizon_m=0.0, knots=8, inflate=True, wrap=True):
+RIVALS_SPEED_CONSTANT, RIVALS_SPEED_PROFILE = 0, 1
+
+
+def rivals_predict(horizon_s, horizon_m=0.0, knots=8, inflate=True, wrap=True, speed=0):
     p = RivalsPredict()
     p.horizon_s, p.horizon_m, p.knots, p.inflate, p.wrap = float(horizon_s), float(horizon_m), int(knots), 1 if inflate else 0, 1 if wrap else 0
+    p.speed = int(speed)
     return p
 
 

@@ -17,7 +17,9 @@ class Rivals:
     has no rivals and is nobody's rival; None: one race of all.  Persistent, unlike `obstacles`: it stays until set to None.
     predict="track": each rival is predicted along the course it follows -- the call's tracks / track_ids where the planner takes them, else the
     planner's raceline -- and its slot carries the chord of that path over the planner's horizon, sampled at knots + 1 points; inflate: the radius
-    grows by the path's largest distance from the chord; wrap: the courses are loops.  horizon [s]: overrides the planner's own."""
+    grows by the path's largest distance from the chord; wrap: the courses are loops.  horizon [s]: overrides the planner's own.
+    speed="profile" (with predict="track"): the rival follows its course's speed column, scaled by its speed now over the course's speed where it
+    stands -- it brakes into the bend its raceline brakes into -- instead of keeping |v| along the course ("constant")."""
     count: int
     radius: float
     reach: float = float("inf")
@@ -27,6 +29,7 @@ class Rivals:
     knots: int = 8
     inflate: bool = True
     wrap: bool = True
+    speed: str = "constant"
 
 
 SINGLE_EGO = "plan() drives one ego, which has no rivals: set planner.rivals = None, or use plan_batch()"
@@ -46,6 +49,10 @@ def check_rivals(rivals, E, obstacles=None, solver=None, devices=None):
         raise ValueError("Rivals.radius and Rivals.reach must be >= 0")
     if rivals.predict not in ("velocity", "track"):
         raise ValueError(f"Rivals.predict must be 'velocity' or 'track', not {rivals.predict!r}")
+    if rivals.speed not in ("constant", "profile"):
+        raise ValueError(f"Rivals.speed must be 'constant' or 'profile', not {rivals.speed!r}")
+    if rivals.speed == "profile" and rivals.predict != "track":
+        raise ValueError("Rivals.speed='profile' is a speed along the rival's course: it needs predict='track'")
     if not 1 <= int(rivals.knots) <= 16:
         raise ValueError(f"Rivals.knots must be in [1, 16], not {rivals.knots!r}")
     if rivals.horizon is not None and not float(rivals.horizon) > 0.0:
@@ -92,7 +99,7 @@ class RivalFeed:
                 self._course = ckey
             hs, hm = (float(rivals.horizon), 0.0) if rivals.horizon is not None else horizon
             rivals_predict_dev(ctx, d_states, self.layout, E, M, float(rivals.radius), d_obs, hs, hm, int(rivals.knots), bool(rivals.inflate),
-                               bool(rivals.wrap), d_pace, None, None, float(rivals.reach), float(min_speed))
+                               bool(rivals.wrap), d_pace, None, None, float(rivals.reach), float(min_speed), speed=rivals.speed)
             return d_obs, d_pace, E, M
         rivals_dev(ctx, d_states, self.layout, E, M, float(rivals.radius), d_obs, d_pace, None, float(rivals.reach), float(min_speed))
         return d_obs, d_pace, E, M

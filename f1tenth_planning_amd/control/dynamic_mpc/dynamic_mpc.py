@@ -22,7 +22,8 @@ planner.rivals = Rivals(count=M, radius=r[, reach, groups]) (shooting only, plan
 ego's M nearest other vehicles of its race among the call's own states on the device (heading yaw + beta; f1p_rivals_dev) and
 tests the rollouts of both branches against them.  Persistent until set to None; not together with `obstacles`.
 predict="track" predicts each rival along the planner's raceline over max(T * DT, TK * DTK) seconds, one value for both branches
-(f1p_rivals_predict_dev).
+(f1p_rivals_predict_dev); with speed="profile" the rival moves with the raceline's speed column, scaled by its speed now
+(DESIGN.md 5u).
 
 mpc_config.QP_AVOID = True (SOLVER="qp" only) lets the QP take `obstacles` (plan and plan_batch) and `rivals` (plan_batch, with and without
 `tracks`) as well: in both branches the two discs nearest to the previous solution's path become, per step, half-plane rows of the QP,

@@ -27,7 +27,8 @@ planner.rivals = Rivals(count=M, radius=r[, reach, groups, predict, horizon, kno
 obstacles: while it is set, every plan_batch finds each ego's M nearest other vehicles of its race among the call's own x0 ON THE DEVICE
 (f1p_rivals_dev) and tests the rollouts against them as above.  Persistent until set to None; not together with `obstacles`.
 predict="track" predicts each rival along the course it follows (the call's tracks / track_ids, else the raceline) over TK * DTK seconds
-(f1p_rivals_predict_dev).
+(f1p_rivals_predict_dev); with speed="profile" the rival moves with that course's speed column, scaled by its speed now
+(DESIGN.md 5u).
 
 mpc_config.QP_AVOID = True (SOLVER="qp" only) lets the QP take `obstacles` (plan and plan_batch) and `rivals` (plan_batch) as well: per step
 the two discs nearest to the previous solution's path become half-plane rows of the QP, softened by one slack variable with the cost

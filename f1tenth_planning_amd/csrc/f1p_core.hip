@@ -139,7 +139,7 @@ void f1p_destroy(f1p_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     f1p_comm_destroy(ctx);
-    void* ptrs[] = {ctx->lat_obs.d, ctx->d_lat_pace, ctx->d_lat_obs_xf, ctx->d_wx, ctx->d_wy, ctx->d_wv, ctx->d_wpsi, ctx->d_wkappa, ctx->d_wbox, ctx->d_tx, ctx->d_ty, ctx->d_tv, ctx->d_tpsi, ctx->d_tkappa, ctx->d_tbox, ctx->d_ttab, ctx->d_bits, ctx->d_bits0, ctx->d_bits_clear, ctx->d_bb_scratch, ctx->d_arena, ctx->d_comm_key, ctx->d_comm_idx, ctx->kmpc_warm.d, ctx->kmpc_qp_warm.d, ctx->stmpc_qp_warm.d, ctx->stmpc_warm.d, ctx->d_kmpc_scratch, ctx->d_mix_scratch, ctx->d_split_scratch, ctx->d_rec_scratch, ctx->d_st_scratch, ctx->d_audit, ctx->d_audit_buf, ctx->d_cl_theta[0], ctx->d_cl_theta[1], ctx->d_step, ctx->d_comm_rec, ctx->d_order, ctx->d_kmpc_cfg, ctx->kmpc_obs.d, ctx->stmpc_obs.d, ctx->d_riv_mem, ctx->d_riv_rng, ctx->arc_wp.cum, ctx->arc_wp.ok, ctx->arc_trk.cum, ctx->arc_trk.ok, ctx->d_riv_tid, ctx->d_riv_rec, ctx->d_riv_idx};
+    void* ptrs[] = {ctx->lat_obs.d, ctx->d_lat_pace, ctx->d_lat_obs_xf, ctx->d_wx, ctx->d_wy, ctx->d_wv, ctx->d_wpsi, ctx->d_wkappa, ctx->d_wbox, ctx->d_tx, ctx->d_ty, ctx->d_tv, ctx->d_tpsi, ctx->d_tkappa, ctx->d_tbox, ctx->d_ttab, ctx->d_bits, ctx->d_bits0, ctx->d_bits_clear, ctx->d_bb_scratch, ctx->d_arena, ctx->d_comm_key, ctx->d_comm_idx, ctx->kmpc_warm.d, ctx->kmpc_qp_warm.d, ctx->stmpc_qp_warm.d, ctx->stmpc_warm.d, ctx->d_kmpc_scratch, ctx->d_mix_scratch, ctx->d_split_scratch, ctx->d_rec_scratch, ctx->d_st_scratch, ctx->d_audit, ctx->d_audit_buf, ctx->d_cl_theta[0], ctx->d_cl_theta[1], ctx->d_step, ctx->d_comm_rec, ctx->d_order, ctx->d_kmpc_cfg, ctx->kmpc_obs.d, ctx->stmpc_obs.d, ctx->d_riv_mem, ctx->d_riv_rng, ctx->arc_wp.cum, ctx->arc_wp.ok, ctx->arc_trk.cum, ctx->arc_trk.ok, ctx->arc_wp.tim, ctx->arc_wp.pok, ctx->arc_trk.tim, ctx->arc_trk.pok, ctx->d_riv_tid, ctx->d_riv_rec, ctx->d_riv_idx};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);

@@ -185,7 +185,12 @@ struct f1p_ctx {
     // rivals predicted along their courses (f1p_rivals_predict_*): the arc tables of the raceline and of the track set, each built by
     // k_course_arc for the generation of its course (wp_gen / trk_gen count the f1p_set_waypoints* / f1p_set_track_set calls), the vehicles' track ids
     // (f1p_rivals_set_course; riv_course_E == 0: every vehicle on the raceline) and the per-call scratch: the Frenet records [cap][4], the indices [cap][16]
-    struct ArcTab { double* cum = nullptr; int32_t* ok = nullptr; size_t rows = 0; int K = 0; unsigned long long gen = 0; };
+    // speed = F1P_RIVALS_SPEED_PROFILE: the time table tim [rows] and the per-course flag pok [K] of k_course_time, built only when a
+    // profile call asks for them, for the generation tgen of the course and the call's min_speed (the floor of the segment speeds)
+    struct ArcTab {
+        double* cum = nullptr; int32_t* ok = nullptr; size_t rows = 0; int K = 0; unsigned long long gen = 0;
+        double* tim = nullptr; int32_t* pok = nullptr; size_t trows = 0; int tK = 0; unsigned long long tgen = 0; double min_speed = 0.0;
+    };
     unsigned long long wp_gen = 1, trk_gen = 1;
     ArcTab arc_wp, arc_trk;
     int32_t* d_riv_tid = nullptr;      // [riv_tid_cap]
@@ -373,9 +378,12 @@ int launch_rivals(f1p_ctx* ctx, const double* d_states, int layout, int E, int M
 // k_rivals_predict.hip: the arc table of the track set (tracks) or of the raceline; the Frenet records and the predicted (vx, vy, r) of the live
 // slots k_rivals wrote.  d_tid null: every vehicle on the raceline
 int launch_course_arc(f1p_ctx* ctx, bool tracks, double* d_cum, int32_t* d_ok);
+// the time table of the same course for pr->speed == F1P_RIVALS_SPEED_PROFILE (after launch_course_arc on the stream: it reads d_ok)
+int launch_course_time(f1p_ctx* ctx, bool tracks, double min_speed, const int32_t* d_ok, double* d_tim, int32_t* d_pok);
+// d_tim / d_pok: read only when pr->speed == F1P_RIVALS_SPEED_PROFILE
 int launch_rivals_predict(f1p_ctx* ctx, const double* d_states, int layout, int E, int M, double radius, double min_speed,
-                          const f1p_rivals_predict* pr, const int32_t* d_tid, const double* d_cum, const int32_t* d_ok, double* d_rec,
-                          const int32_t* d_idx, double* d_obs, double* d_frenet);
+                          const f1p_rivals_predict* pr, const int32_t* d_tid, const double* d_cum, const int32_t* d_ok, const double* d_tim,
+                          const int32_t* d_pok, double* d_rec, const int32_t* d_idx, double* d_obs, double* d_frenet);
 int launch_argmin_key(f1p_ctx* ctx, const double* d_cost, uint64_t* d_key, int E);
 int launch_argmin_mask(f1p_ctx* ctx, const uint64_t* d_own, const uint64_t* d_min, const int32_t* d_idx, int32_t* d_masked,
                        double* d_cost_out, int E);

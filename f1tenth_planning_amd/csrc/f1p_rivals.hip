@@ -117,6 +117,8 @@ static int predict_check(f1p_ctx* ctx, const f1p_rivals_predict* pr, int E) {
     if (pr->knots < 1 || pr->knots > F1P_RIVALS_KNOTS_MAX) return set_error(ctx, F1P_EINVAL, "rivals: knots must be in [1, 16]");
     if (!(pr->horizon_s >= 0.0) || !(pr->horizon_m >= 0.0)) return set_error(ctx, F1P_EINVAL, "rivals: horizon_s and horizon_m must be >= 0");
     if (pr->horizon_s == 0.0 && pr->horizon_m == 0.0) return set_error(ctx, F1P_EINVAL, "rivals: horizon_s and horizon_m are both zero");
+    if (pr->speed != F1P_RIVALS_SPEED_CONSTANT && pr->speed != F1P_RIVALS_SPEED_PROFILE)
+        return set_error(ctx, F1P_EINVAL, "rivals: speed must be F1P_RIVALS_SPEED_CONSTANT or F1P_RIVALS_SPEED_PROFILE");
     if (ctx->riv_course_E > 0) {
         if (ctx->riv_course_E != E)
             return set_error(ctx, F1P_ESTATE, "rivals: the courses were set for " + std::to_string(ctx->riv_course_E) + " vehicles, this call has " +
@@ -151,6 +153,25 @@ static int ensure_arc(f1p_ctx* ctx, bool tracks, f1p_ctx::ArcTab** out) {
     return F1P_OK;
 }
 
+// the time table next to it (speed = profile only; after ensure_arc: k_course_time reads the arc table's flags), rebuilt (one launch) when the course
+// has changed since it was built or the call's min_speed, the floor of the segment speeds, is another one
+static int ensure_time(f1p_ctx* ctx, bool tracks, double min_speed, f1p_ctx::ArcTab& a) {
+    if (a.tgen == a.gen && a.min_speed == min_speed) return F1P_OK;
+    if (a.rows > a.trows || a.K > a.tK) {
+        F1P_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (a.tim) (void)hipFree(a.tim);
+        if (a.pok) (void)hipFree(a.pok);
+        a.tim = nullptr; a.pok = nullptr; a.trows = 0; a.tK = 0; a.tgen = 0;
+        F1P_HIP(ctx, hipMalloc((void**)&a.tim, sizeof(double) * a.rows));
+        F1P_HIP(ctx, hipMalloc((void**)&a.pok, sizeof(int32_t) * (size_t)a.K));
+        a.trows = a.rows; a.tK = a.K;
+    }
+    a.tgen = 0;
+    if (const int rc = launch_course_time(ctx, tracks, min_speed, a.ok, a.tim, a.pok)) return rc;
+    a.tgen = a.gen; a.min_speed = min_speed;
+    return F1P_OK;
+}
+
 static int predict_launch(f1p_ctx* ctx, const double* d_states, int layout, int E, int M, double radius, double reach, double min_speed,
                           const f1p_rivals_predict* pr, double* d_obs, double* d_pace, int32_t* d_idx, double* d_frenet) {
     if (E > ctx->riv_scr_cap) {
@@ -166,10 +187,11 @@ static int predict_launch(f1p_ctx* ctx, const double* d_states, int layout, int 
     f1p_ctx::ArcTab* arc;
     int rc;
     if ((rc = ensure_arc(ctx, tracks, &arc))) return rc;
+    if (pr->speed == F1P_RIVALS_SPEED_PROFILE && (rc = ensure_time(ctx, tracks, min_speed, *arc))) return rc;
     int32_t* idx = d_idx ? d_idx : ctx->d_riv_idx;
     if ((rc = rivals_launch(ctx, d_states, layout, E, M, radius, reach, min_speed, d_obs, d_pace, idx))) return rc;
-    return launch_rivals_predict(ctx, d_states, layout, E, M, radius, min_speed, pr, tracks ? ctx->d_riv_tid : nullptr, arc->cum, arc->ok,
-                                 ctx->d_riv_rec, idx, d_obs, d_frenet);
+    return launch_rivals_predict(ctx, d_states, layout, E, M, radius, min_speed, pr, tracks ? ctx->d_riv_tid : nullptr, arc->cum, arc->ok, arc->tim,
+                                 arc->pok, ctx->d_riv_rec, idx, d_obs, d_frenet);
 }
 
 int f1p_rivals_predict_dev(f1p_ctx* ctx, const double* d_states, int32_t layout, int32_t E, int32_t M, double radius, double reach,

@@ -13,6 +13,8 @@
 //                     deviation is reduced by an xor butterfly inside the group; the group's lane 0 overwrites (vx, vy, r).  No LDS, no atomics;
 //                     the loads sit in divergent code, every cross-lane operation in code the whole wave runs.  A slot that falls back is not
 //                     touched: it keeps the bits k_rivals wrote, and nothing is indexed with a value that failed a test.
+//   k_course_time     (speed = profile) k_course_arc's sibling for the course's TIME coordinate tim [n] and the "profile-usable" flag;
+//                     k_rivals_predict<CourseTime> then advances a rival in tim, scaled by its speed relative to the course's where it stands.
 #include "f1p_internal.h"
 #include "tracker_device.h"
 
@@ -49,6 +51,53 @@ __global__ __launch_bounds__(64) void k_course_arc(const double* __restrict__ x,
     const bool all_good = __ballot(!good) == 0ull;
     if (lane == 0) ok[k] = (rows >= 2 && all_good && acc > 0.0 && acc < __builtin_huge_val()) ? 1 : 0;
 }
+
+// The time coordinate of the same courses (include/f1p.h "Rivals, predicted with the course's speed profile"): tim_{k+1} = tim_k +
+// len_k / c_k with c_k the mean of the two |speeds| of segment k, floored at vfloor.  k_course_arc's sibling: the 64 quotients are formed in parallel
+// and added ONE BY ONE in index order, so the table is the sequential fp64 sum whatever the launch shape.  pok [k]: the course is usable (ok, written
+// by k_course_arc earlier on the stream), every speed is finite, and the lap time is finite and positive.
+__global__ __launch_bounds__(64) void k_course_time(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ w,
+                                                    const int4* __restrict__ tab, int n, double vfloor, const int32_t* __restrict__ ok,
+                                                    double* __restrict__ tim, int32_t* __restrict__ pok) {
+    const int k = blockIdx.x, lane = threadIdx.x;
+    int off = 0, rows = n;
+    if (tab) { const int4 t = tab[k]; off = __builtin_amdgcn_readfirstlane(t.x); rows = __builtin_amdgcn_readfirstlane(t.y); }
+    x += off; y += off; w += off; tim += off;
+    double acc = 0.0;
+    bool good = true;
+    if (lane == 0 && rows > 0) tim[0] = 0.0;
+    for (int base = 0; base < rows - 1; base += 64) {                 // (wave-uniform)
+        const int i = base + lane;
+        double q = 0.0;                                               // past the end: + 0.0 leaves the sum's bits alone
+        if (i < rows - 1) {
+            const double dx = x[i + 1] - x[i], dy = y[i + 1] - y[i];
+            const double len = __builtin_sqrt(dx * dx + dy * dy);     // (k_course_arc's expression: the same bits)
+            const double w0 = w[i], w1 = w[i + 1];
+            if (!finite_d(w0) || !finite_d(w1)) good = false;
+            double c = 0.5 * (fabs(w0) + fabs(w1));
+            if (!(c >= vfloor)) c = vfloor;
+            q = len / c;
+        }
+        const int lo = __double2loint(q), hi = __double2hiint(q);
+        double mine = 0.0;
+#pragma unroll 4
+        for (int l = 0; l < 64; ++l) {
+            acc = acc + __hiloint2double(__builtin_amdgcn_readlane(hi, l), __builtin_amdgcn_readlane(lo, l));
+            if (lane == l) mine = acc;
+        }
+        if (i < rows - 1) tim[i + 1] = mine;
+    }
+    const bool all_good = __ballot(!good) == 0ull;
+    if (lane == 0) pok[k] = (ok[k] != 0 && all_good && acc > 0.0 && acc < __builtin_huge_val()) ? 1 : 0;
+}
+
+// what the profile instantiation of k_rivals_predict reads on top of CourseDev: k_course_time's table (rows as the course arrays'), its flags
+// [K] / [1], and the speed columns of the raceline and of the track set
+struct CourseTime {
+    const double* tim;
+    const int32_t* pok;
+    const double *wv, *tv;
+};
 
 // the courses of a rivals call: track tid[j] of the set for vehicle j, or (tid null) the raceline for all
 struct CourseDev {
@@ -110,9 +159,38 @@ __global__ __launch_bounds__(256) void k_rivals_frenet(const double* __restrict_
     }
 }
 
+// The start of vehicle j in the TIME coordinate of its course (cum, n), from its record r = (s0, d, dir, b): the table to search (tim), th0, rho and the
+// course's speed column.  false, with nothing of the time table read and the outputs untouched: the course is not profile-usable.  b is a segment of
+// this course (k_rivals_frenet wrote dir and b together, and dir is not NaN here); it is tested all the same, so that no load is indexed without a test.
+__device__ __forceinline__ bool profile_start(const CourseTime& ct, const CourseDev& c, int j, const double* __restrict__ r, double av, double vfloor,
+                                              const double* __restrict__ cum, int n, const double*& tab, double& th0, double& rho, const double*& spd) {
+    const double *tim = ct.tim, *pw = ct.wv;
+    int course = 0;
+    if (c.tid) {
+        course = c.tid[j];                                            // (in [0, K): k_rivals_frenet wrote a record)
+        const int off = c.ts.tab[course].x;
+        tim += off; pw = ct.tv + off;
+    }
+    if (ct.pok[course] == 0) return false;
+    const int b = (int)r[3];
+    if (b < 0 || b > n - 2) return false;
+    double cb = 0.5 * (fabs(pw[b]) + fabs(pw[b + 1]));
+    if (!(cb >= vfloor)) cb = vfloor;
+    rho = av / cb;
+    th0 = tim[b] + (r[0] - cum[b]) / cb;
+    tab = tim; spd = pw;
+    return true;
+}
+
+// k_rivals_predict<>: speed = constant, the kernel as it was.  k_rivals_predict<CourseTime>: speed = profile -- the same walk in another coordinate: a
+// lane whose vehicle's course is profile-usable starts at th0, advances at rho and searches tim instead of (s0, |v_j|, cum), then turns the time on the
+// segment into metres with that segment's c_k, recomputed from the two speeds it loads; a lane on any other course keeps (s0, |v_j|, cum), which are
+// the constant instantiation's expressions on the same operands.
+template <typename... Prof>
 __global__ __launch_bounds__(256) void k_rivals_predict(const double* __restrict__ st, int stride, int iv, int E, int M, double radius, double min_speed,
                                                         double hs, double hm, int K, int inflate, int wrap, CourseDev c,
-                                                        const double* __restrict__ rec, const int32_t* __restrict__ idx, double* __restrict__ obs) {
+                                                        const double* __restrict__ rec, const int32_t* __restrict__ idx, double* __restrict__ obs,
+                                                        Prof... prof) {
     const int lane = threadIdx.x & 63;
     const int e = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     if (e >= E) return;                                               // (the whole wave)
@@ -140,22 +218,38 @@ __global__ __launch_bounds__(256) void k_rivals_predict(const double* __restrict
                         const int4 t = c.ts.tab[c.tid[j]];            // (in [0, K): k_rivals_frenet wrote a record)
                         px = c.ts.x + t.x; py = c.ts.y + t.x; cum = c.cum + t.x; n = t.y;
                     }
-                    const double L = cum[n - 1];
+                    // the table the knot is searched in, and the start and the speed in its coordinate: (cum, s0, |v_j|), or (tim, th0, rho)
+                    const double* tab = cum;
+                    [[maybe_unused]] double th0 = 0.0, rho = 0.0;
+                    [[maybe_unused]] const double* spd = nullptr;     // the course's speed column: this lane follows the profile
+                    if constexpr (sizeof...(Prof) > 0) (profile_start(prof, c, j, r, av, min_speed, cum, n, tab, th0, rho, spd), ...);
+                    const double L = tab[n - 1];
                     const double tau = (H * (double)kn) / (double)K;
                     double sa = r[0] + (dir * av) * tau;
+                    if constexpr (sizeof...(Prof) > 0) {
+                        if (spd) sa = th0 + (dir * rho) * tau;
+                    }
                     if (wrap) sa = sa - L * floor(sa / L);
                     if (sa < 0.0) sa = 0.0;
                     if (sa > L) sa = L;
-                    int lo = 0, hi = n - 2;                           // the largest k <= n - 2 with cum_k <= s (cum_0 = 0 <= s)
+                    int lo = 0, hi = n - 2;                           // the largest k <= n - 2 with tab_k <= s (tab_0 = 0 <= s)
                     while (lo < hi) {
                         const int mid = (lo + hi + 1) >> 1;
-                        if (cum[mid] <= sa) lo = mid; else hi = mid - 1;
+                        if (tab[mid] <= sa) lo = mid; else hi = mid - 1;
                     }
                     const double ax = px[lo], ay = py[lo];
                     const double dx = px[lo + 1] - ax, dy = py[lo + 1] - ay;
                     const double len = __builtin_sqrt(dx * dx + dy * dy);
                     const double ux = dx / len, uy = dy / len;
-                    const double w = sa - cum[lo], d = r[1];
+                    double w = sa - tab[lo];
+                    const double d = r[1];
+                    if constexpr (sizeof...(Prof) > 0) {
+                        if (spd) {                                    // time on the segment -> metres: c_lo, recomputed from its two speeds
+                            double cl = 0.5 * (fabs(spd[lo]) + fabs(spd[lo + 1]));
+                            if (!(cl >= min_speed)) cl = min_speed;
+                            w = w * cl;
+                        }
+                    }
                     cx = ax + ux * w + (-uy) * d;
                     cy = ay + uy * w + ux * d;
                     live = true;
@@ -196,9 +290,19 @@ int launch_course_arc(f1p_ctx* ctx, bool tracks, double* d_cum, int32_t* d_ok) {
     return check_hip(ctx, hipGetLastError(), "k_course_arc launch");
 }
 
+int launch_course_time(f1p_ctx* ctx, bool tracks, double min_speed, const int32_t* d_ok, double* d_tim, int32_t* d_pok) {
+    if (tracks)
+        hipLaunchKernelGGL(k_course_time, dim3(ctx->trk_K), dim3(64), 0, ctx->stream, ctx->d_tx, ctx->d_ty, ctx->d_tv, (const int4*)ctx->d_ttab, 0, min_speed,
+                           d_ok, d_tim, d_pok);
+    else
+        hipLaunchKernelGGL(k_course_time, dim3(1), dim3(64), 0, ctx->stream, ctx->d_wx, ctx->d_wy, ctx->d_wv, (const int4*)nullptr, ctx->n_wp, min_speed,
+                           d_ok, d_tim, d_pok);
+    return check_hip(ctx, hipGetLastError(), "k_course_time launch");
+}
+
 int launch_rivals_predict(f1p_ctx* ctx, const double* d_states, int layout, int E, int M, double radius, double min_speed,
-                          const f1p_rivals_predict* pr, const int32_t* d_tid, const double* d_cum, const int32_t* d_ok, double* d_rec,
-                          const int32_t* d_idx, double* d_obs, double* d_frenet) {
+                          const f1p_rivals_predict* pr, const int32_t* d_tid, const double* d_cum, const int32_t* d_ok, const double* d_tim,
+                          const int32_t* d_pok, double* d_rec, const int32_t* d_idx, double* d_obs, double* d_frenet) {
     if (E <= 0) return F1P_OK;
     int stride, iv, ih, ib;
     layout_columns(layout, &stride, &iv, &ih, &ib);
@@ -209,8 +313,14 @@ int launch_rivals_predict(f1p_ctx* ctx, const double* d_states, int layout, int 
     c.cum = d_cum; c.ok = d_ok;
     hipLaunchKernelGGL(k_rivals_frenet, dim3((E + 3) / 4), dim3(256), 0, ctx->stream, d_states, stride, iv, ih, ib, E, c, d_rec, d_frenet);
     if (const int rc = check_hip(ctx, hipGetLastError(), "k_rivals_frenet launch")) return rc;
-    hipLaunchKernelGGL(k_rivals_predict, dim3((E + 3) / 4), dim3(256), 0, ctx->stream, d_states, stride, iv, E, M, radius, min_speed, pr->horizon_s,
-                       pr->horizon_m, (int)pr->knots, (int)pr->inflate, (int)pr->wrap, c, (const double*)d_rec, d_idx, d_obs);
+    if (pr->speed == F1P_RIVALS_SPEED_PROFILE) {
+        const CourseTime ct{d_tim, d_pok, ctx->d_wv, ctx->d_tv};
+        hipLaunchKernelGGL(k_rivals_predict<CourseTime>, dim3((E + 3) / 4), dim3(256), 0, ctx->stream, d_states, stride, iv, E, M, radius, min_speed,
+                           pr->horizon_s, pr->horizon_m, (int)pr->knots, (int)pr->inflate, (int)pr->wrap, c, (const double*)d_rec, d_idx, d_obs, ct);
+    } else {
+        hipLaunchKernelGGL(k_rivals_predict<>, dim3((E + 3) / 4), dim3(256), 0, ctx->stream, d_states, stride, iv, E, M, radius, min_speed, pr->horizon_s,
+                           pr->horizon_m, (int)pr->knots, (int)pr->inflate, (int)pr->wrap, c, (const double*)d_rec, d_idx, d_obs);
+    }
     return check_hip(ctx, hipGetLastError(), "k_rivals_predict launch");
 }
 

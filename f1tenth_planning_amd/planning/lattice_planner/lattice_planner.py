@@ -28,7 +28,8 @@ every plan_batch() / step_batch() finds each ego's M nearest other vehicles of i
 1 / max(|v|, obstacle_min_speed) (f1p_rivals_dev, DESIGN.md 5m), and tests the candidates against them as above.  Persistent until set to None;
 not together with `obstacles`, not for plan() (one ego has no rivals), not for multi-GPU plans.
 predict="track" predicts each rival along the course it follows (the call's tracks / track_ids, else the raceline) over the time ego e needs for
-its longest look-ahead, max(lookahead_distances) * pace_e (f1p_rivals_predict_dev).
+its longest look-ahead, max(lookahead_distances) * pace_e (f1p_rivals_predict_dev); with speed="profile" the rival moves with that
+course's speed column, scaled by its speed now.
 """
 import warnings
 

@@ -1,6 +1,7 @@
 """Context's rivals: each ego's nearest other vehicles of its race as the moving discs the three sampling planners test
 (csrc/f1p_rivals.hip, csrc/k_rivals.hip; the rule: include/f1p.h "Rivals").
-Predicted along the course each rival follows: csrc/k_rivals_predict.hip; include/f1p.h "Rivals, predicted along the course", DESIGN.md 5n."""
+Predicted along the course each rival follows: csrc/k_rivals_predict.hip; include/f1p.h "Rivals, predicted along the course", DESIGN.md 5n.
+speed="profile": the rival moves along that course with the course's speed profile, scaled by its own speed now."""
 import ctypes as C
 
 import numpy as np
@@ -9,6 +10,7 @@ from .. import _abi
 from .core import _dev, _f64, _ptr
 
 LAYOUTS = {"xyvyaw": _abi.RIVALS_XYVYAW, "pose": _abi.RIVALS_POSE, "st7": _abi.RIVALS_ST7}
+SPEEDS = {"constant": _abi.RIVALS_SPEED_CONSTANT, "profile": _abi.RIVALS_SPEED_PROFILE}
 
 
 def rivals_set_groups(ctx, groups):
@@ -38,23 +40,36 @@ def rivals_set_course(ctx, track_ids):
     ctx._rivals_set_course(track_ids)
 
 
-def rivals_predict(ctx, states, layout, M, radius, horizon_s, horizon_m=0.0, knots=8, inflate=True, wrap=True, reach=np.inf, min_speed=0.5):
+def rivals_predict(ctx, states, layout, M, radius, horizon_s, horizon_m=0.0, knots=8, inflate=True, wrap=True, reach=np.inf, min_speed=0.5,
+                   speed="constant"):
     """rivals() with every live slot predicted along the course its vehicle follows (f1p_rivals_predict_batch): (vx, vy) is the chord of the
     vehicle's path along its course over H_i = horizon_s + horizon_m * pace_i, sampled at `knots` + 1 points, and with `inflate` the radius
-    grows by the path's largest distance from that chord; wrap: the course is a loop -> dict(obs, pace, idx as rivals(),
-    frenet [E, 3] = (s0, d, dir) per vehicle, a NaN row for one that keeps the constant-velocity slot)"""
-    return ctx._rivals_predict(states, layout, M, radius, reach, min_speed, _abi.rivals_predict(horizon_s, horizon_m, knots, inflate, wrap))
+    grows by the path's largest distance from that chord; wrap: the course is a loop; speed: "constant" / RIVALS_SPEED_CONSTANT, the vehicle keeps
+    |v| along its course, or "profile", it follows the course's speed column scaled by |v| over the course's speed where it stands, floored at
+    min_speed -> dict(obs, pace, idx as rivals(), frenet [E, 3] = (s0, d, dir) per vehicle, a NaN row for one that keeps the
+    constant-velocity slot)"""
+    return ctx._rivals_predict(states, layout, M, radius, reach, min_speed,
+                               _abi.rivals_predict(horizon_s, horizon_m, knots, inflate, wrap, _speed(speed)))
 
 
 def rivals_predict_dev(ctx, d_states, layout, E, M, radius, d_obs, horizon_s, horizon_m=0.0, knots=8, inflate=True, wrap=True, d_pace=None,
-                       d_idx=None, d_frenet=None, reach=np.inf, min_speed=0.5):
+                       d_idx=None, d_frenet=None, reach=np.inf, min_speed=0.5, speed="constant"):
     """rivals_predict on device buffers, asynchronous on the context's stream (f1p_rivals_predict_dev); d_frenet [E][3] fp64, nullable"""
     ctx._rivals_predict_dev(d_states, layout, E, M, radius, d_obs, d_pace, d_idx, d_frenet, reach, min_speed,
-                            _abi.rivals_predict(horizon_s, horizon_m, knots, inflate, wrap))
+                            _abi.rivals_predict(horizon_s, horizon_m, knots, inflate, wrap, _speed(speed)))
 
 
 def _layout(layout):
     return LAYOUTS[layout] if isinstance(layout, str) else int(layout)
+
+
+def _speed(speed):
+    """a name of SPEEDS, or the C-ABI's integer as it is (the library rejects an unknown one)"""
+    if isinstance(speed, str):
+        if speed not in SPEEDS:
+            raise ValueError(f"speed must be 'constant' or 'profile', not {speed!r}")
+        return SPEEDS[speed]
+    return int(speed)
 
 
 class _Rivals:

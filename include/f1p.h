@@ -1195,17 +1195,39 @@ int f1p_rivals_batch(f1p_ctx* ctx, const double* states, int32_t layout, int32_t
  * live in buffers of the context and are rebuilt, by one launch, when f1p_set_waypoints* / f1p_set_track_set has been called since.
  * f1p_rivals_predict_batch: the same on host arrays, synchronous.
  * Errors, nothing launched: everything f1p_rivals_dev rejects, knots outside [1, 16], a negative or NaN horizon_s / horizon_m, both
- * zero, a NULL pr (set_course: E < 1 with an id array): F1P_EINVAL; E different from the E the courses were set for, or no track set
- * (ids set) / no raceline (no ids): F1P_ESTATE.
+ * zero, a speed other than the two below, a NULL pr (set_course: E < 1 with an id array): F1P_EINVAL; E different from the E the
+ * courses were set for, or no track set (ids set) / no raceline (no ids): F1P_ESTATE.
+ *
+ * Rivals, predicted with the course's speed profile (speed = F1P_RIVALS_SPEED_PROFILE).  With speed =
+ * F1P_RIVALS_SPEED_CONSTANT (0, the default) a rival keeps |v_j| along its course, the rule above.  With F1P_RIVALS_SPEED_PROFILE it
+ * advances in the course's TIME coordinate, scaled by how fast it is going now relative to the course's speed where it stands: a rival at
+ * raceline speed brakes and accelerates with the raceline, one at 80 % does 80 % of it, a standing one stands.  Everything above stays;
+ * only the map from tau to a point on the course changes.  All in fp64, in this operation order, no contraction.
+ * Per course, w_k its speed column (the raceline's / the track's v column), len_k and cum_k as above, floor = the call's min_speed:
+ *   - c_k = 0.5 * (|w_k| + |w_{k+1}|), k = 0 .. n-2;  if !(c_k >= floor) then c_k = floor.
+ *   - tim_0 = 0; tim_{k+1} = tim_k + len_k / c_k, added one by one in index order; Tl = tim_{n-1}.
+ *   - The course is PROFILE-USABLE if it is usable in the sense above, every w_k is finite and Tl is finite and positive.
+ * Per vehicle j with Frenet record (s0, d, dir, b):
+ *   - rho = |v_j| / c_b;  th0 = tim_b + (s0 - cum_b) / c_b.
+ * Position at time tau:
+ *   - th = th0 + (dir * rho) * tau;  with wrap: th = th - Tl * floor(th / Tl);  in both modes th is then clamped into [0, Tl].
+ *   - k = the largest index <= n - 2 with tim_k <= th (a binary search in tim).
+ *   - P(tau) = p_k + u_k * ((th - tim_k) * c_k) + n_k * d, per component, left to right.
+ * A vehicle on a course that is usable but not profile-usable is predicted by the constant-speed rule: its slots are bit-equal to the
+ * same call with speed = F1P_RIVALS_SPEED_CONSTANT.  Every other fallback is unchanged and keeps the constant-velocity bits.
+ * The time tables live next to the arc tables, are built only when a profile call asks for them, and are rebuilt, by one launch, when
+ * the course has been replaced since or the call's min_speed differs from the one they were built with.
  * ---------------------------------------------------------------------------------------------- */
 #define F1P_RIVALS_KNOTS_MAX 16
+#define F1P_RIVALS_SPEED_CONSTANT 0
+#define F1P_RIVALS_SPEED_PROFILE 1
 typedef struct f1p_rivals_predict {
     double horizon_s;              /* H_i = horizon_s [s] + horizon_m [m] * pace_i */
     double horizon_m;
     int32_t knots;                 /* K in [1, 16] */
     int32_t inflate;               /* != 0: r = radius + dev */
     int32_t wrap;                  /* != 0: the course is a loop */
-    int32_t reserved;
+    int32_t speed;                 /* F1P_RIVALS_SPEED_CONSTANT (0): |v_j| along the course; F1P_RIVALS_SPEED_PROFILE: the course's speed profile */
 } f1p_rivals_predict;
 int f1p_rivals_set_course(f1p_ctx* ctx, const int32_t* track_id, int32_t E);
 int f1p_rivals_predict_dev(f1p_ctx* ctx, const double* d_states, int32_t layout, int32_t E, int32_t M, double radius, double reach,

@@ -17,7 +17,12 @@ shapes; "expected" in the record says whether it held.  Prints one JSON object; 
     kernels  device events around chained launches: k_rivals alone, and k_rivals + k_rivals_frenet + k_rivals_predict; "new_kernels_ms" is the difference
 The paths are ALTERNATED block by block.  Compared first: the constant-velocity slots of both libraries bit for bit, and idx, x, y of the predicted
 slots against them.  THE EXPECTATION: the constant-velocity path's median stays inside the parent's own block-to-block band (its kernel is unchanged,
-only the launch path gained a branch).  The prediction's own cost is reported, not judged."""
+only the launch path gained a branch).  The prediction's own cost is reported, not judged.
+
+--predict --speed profile: the rivals predicted with the raceline's speed profile beside the constant-speed prediction, same process, same
+shapes, same protocol -- the paths "profile", "predict" and "device" ALTERNATED block by block, the kernels' row "kernel_profile" (k_rivals + k_rivals_frenet
++ k_rivals_predict<CourseTime>; the time table is built once, before the clock) next to "kernel_predict".  Compared first: idx, x, y, pace of the profile
+slots against the constant-speed ones, bit for bit.  Reported, not judged: "profile_ms" = profile - predict medians, "profile_kernels_ms" likewise."""
 import argparse
 import ctypes as C
 import json
@@ -71,7 +76,7 @@ def predict_main(args):
     E, M, H, K = args.egos, args.slots, 0.8, 8
     rng = np.random.default_rng(0)
     rl = synth.make_raceline(seed=0)
-    res = {"tool": "tools/time_rivals.py --predict", "egos": E, "slots": M, "horizon_s": H, "knots": K, "raceline_points": int(rl.shape[0]),
+    res = {"tool": "tools/time_rivals.py --predict" + (" --speed profile" if args.speed == "profile" else ""), "egos": E, "slots": M, "horizon_s": H, "knots": K, "raceline_points": int(rl.shape[0]),
            "repeats": args.repeats, "dev_calls": args.dev_calls, "kernel_calls": args.calls, "parent_lib": bool(args.parent_lib), "rows": []}
     ok = True
     with Context(0) as ctx:
@@ -101,6 +106,13 @@ def predict_main(args):
                 kmpc_set_obstacles_dev(ctx, d_obs, E, M)
                 ctx.sync()
 
+            def profile():
+                d_st, d_obs, _ = bufs[0]
+                d_st.upload(st)
+                rivals_predict_dev(ctx, d_st, "xyvyaw", E, M, RADIUS, d_obs, H, 0.0, K, speed="profile")
+                kmpc_set_obstacles_dev(ctx, d_obs, E, M)
+                ctx.sync()
+
             outs = []
             for c, b in zip(ctxs, bufs):
                 rivals_dev(c, b[0].upload(st), "xyvyaw", E, M, RADIUS, b[1], None, b[2])
@@ -111,7 +123,12 @@ def predict_main(args):
             same = bool(all(o.tobytes() == outs[0][0].tobytes() and i.tobytes() == outs[0][1].tobytes() for o, i in outs)
                         and (pidx == outs[0][1]).all() and pobs[..., :2].tobytes() == outs[0][0][..., :2].tobytes())
             moved = float((np.abs(pobs[..., 2:4] - outs[0][0][..., 2:4]).max(axis=2)[pidx >= 0] > 0.05).mean())
-            paths = [("predict", predict), ("device", lambda: velocity(ctx, bufs[0]))] + ([("parent", lambda: velocity(ctxs[1], bufs[1]))] if args.parent_lib else [])
+            if args.speed == "profile":
+                rivals_predict_dev(ctx, d_st, "xyvyaw", E, M, RADIUS, d_obs, H, 0.0, K, d_idx=d_idx, speed="profile")
+                qobs, qidx = d_obs.download(np.float64, (E, M, 5)), d_idx.download(np.int32, (E, M))
+                same = bool(same and (qidx == pidx).all() and qobs[..., :2].tobytes() == pobs[..., :2].tobytes() and np.isfinite(qobs).all())
+                moved_profile = float((np.abs(qobs[..., 2:4] - pobs[..., 2:4]).max(axis=2)[pidx >= 0] > 0.05).mean())
+            paths = ([("profile", profile)] if args.speed == "profile" else []) + [("predict", predict), ("device", lambda: velocity(ctx, bufs[0]))] + ([("parent", lambda: velocity(ctxs[1], bufs[1]))] if args.parent_lib else [])
             for _, fn in paths * 2:                                  # warm-up of every path
                 fn()
             per = {key: [] for key, _ in paths}
@@ -127,6 +144,12 @@ def predict_main(args):
             row["kernel_predict"] = _time(ctx, lambda: rivals_predict_dev(ctx, d_st, "xyvyaw", E, M, RADIUS, d_obs, H, 0.0, K), args.calls, args.repeats, 3)
             row["new_kernels_ms"] = row["kernel_predict"]["ms_median"] - row["kernel_velocity"]["ms_median"]
             row["prediction_ms"] = row["predict"]["ms_median"] - row["device"]["ms_median"]
+            if args.speed == "profile":
+                row["slots_moved_by_profile"] = moved_profile
+                row["kernel_profile"] = _time(ctx, lambda: rivals_predict_dev(ctx, d_st, "xyvyaw", E, M, RADIUS, d_obs, H, 0.0, K, speed="profile"), args.calls,
+                                              args.repeats, 3)
+                row["profile_kernels_ms"] = row["kernel_profile"]["ms_median"] - row["kernel_predict"]["ms_median"]
+                row["profile_ms"] = row["profile"]["ms_median"] - row["predict"]["ms_median"]
             row["expected"] = same
             if args.parent_lib:
                 row["expected"] = bool(same and row["device"]["ms_median"] <= row["parent"]["ms_max"])
@@ -161,8 +184,12 @@ def main():
     ap.add_argument("--calls", type=int, default=50, help="chained launches per block of the kernel-only row")
     ap.add_argument("--out")
     ap.add_argument("--predict", action="store_true", help="time the prediction along the raceline (DESIGN.md 5n) instead")
+    ap.add_argument("--speed", choices=("constant", "profile"), default="constant", help="--predict: 'profile' also times the prediction with the raceline's "
+                    "speed profile (DESIGN.md 5u), alternated with the constant-speed one")
     ap.add_argument("--parent-lib", help="--predict: libf1p.so of the parent commit, its constant-velocity path alternated with this tree's")
     args = ap.parse_args()
+    if args.speed != "constant" and not args.predict:
+        ap.error("--speed profile needs --predict")
     if args.predict:
         predict_main(args)
     E, M = args.egos, args.slots
